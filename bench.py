@@ -4,9 +4,11 @@
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by
 torch.distributed.run with one rank per GPU.  A "step" is one BPR epoch = CountFeedback()
 SGD samples over one rank's resident dataset (model/cf/model.go:446-494).  Rank 0 prints ONE
-JSON line.
+JSON line.  A plain run times the headline workload alone; --full adds what the headline does not need: the
+other legs of the default line, the CPU baselines and their row checks against the oracle, and the epochs through the
+synchronous entry point.  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy.
 
-Workloads (BASELINE.json configs):
+Workloads (BASELINE.json configs; "the default run/line" below = a --full run without --workload):
   ml1m   (default) C2: S-ml1m shape 6040 x 3706 x 994,169, nFactors 64, fp32.  With N ranks every
          rank trains its own S-ml1m-shaped USER SHARD against the shared item matrix (weak scaling:
          N*6040 users), Q replicated, one all-reduce of the item-factor delta per epoch over RCCL.
@@ -174,11 +176,21 @@ class ClockSampler:
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps of the workload the line is about (default 20; 5 for --workload c3full, 3 for big, "
+                         "--topk-steps for topk); the other legs of a --full line keep their own")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 3; 2 for c3full, 1 for big and topk)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines and their row checks against the oracle, "
+                         "the synchronous-entry-point epochs and, on the default line, the top-k leg and the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy, the same "
+                         "bit for bit from run to run (a BPR leg: the triplets its last epoch applied, not the factors, which a "
+                         "Hogwild epoch leaves differently on every run)")
     ap.add_argument("--workload", default=None, choices=["ml1m", "c3", "c3full", "big", "ml100k", "topk", "als", "i2i"],
-                    help="default: ml1m (C2) on one GPU -- the line then also carries topk (C4), c3 (whole C3), i2i, als and "
-                         "ml100k objects; the C3 shard per rank + sharded topk on N > 1")
+                    help="default: ml1m (C2) on one GPU -- with --full the line then also carries topk (C4), c3 (whole C3), i2i, als "
+                         "and ml100k objects; the C3 shard per rank (+ sharded topk with --full) on N > 1")
     ap.add_argument("--factors", type=int, default=0, help="nFactors override of a BPR workload")
     ap.add_argument("--big-draws", type=int, default=1_250_000_000, help="feedback draws of --workload big (about 80 %% remain distinct)")
     ap.add_argument("--bpr-chunk", type=int, default=0, help="probe: samples per chunk of the BPR pipeline (0 = the library's choice)")
@@ -202,7 +214,30 @@ def parse():
                          "0 = atomics only, 1 = sequential, 2 = racy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    for name in ("steps", "warmup"):
+        v = getattr(args, name)
+        if v is not None and v < (1 if name == "steps" else 0):
+            ap.error("--%s must be at least %d" % (name, 1 if name == "steps" else 0))
+    return args
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> array a caller of the timed path receives) as path/<name>.npy, floats as float32 and
+    integers as float64 (exact for int32).  Past DUMP_BYTES in all, every array keeps the same fixed, seeded sample of its rows,
+    so two runs with the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    kind = {k: np.float32 if a.dtype.kind == "f" else np.float64 for k, a in arrays.items()}
+    total = sum(a.size * np.dtype(kind[k]).itemsize for k, a in arrays.items())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.ndim >= 1 and a.shape[0] > 1:
+            m = max(1, int(a.shape[0] * DUMP_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], m, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, kind[name]))
 
 
 BIG_DRAWS_DEFAULT_LINE = 250_000_000  # scripts/gen_golden_ndcg.py big and the -m gpu test at that size use the same set
@@ -327,12 +362,17 @@ def topk_cpu_baseline(Xe, k, seconds, idx_gpu, dist_gpu, q_begin):
                       "bit for bit with the GPU rows" % (len(qs), N, Xe.shape[1], threads, dt, ok)}
 
 
-def bench_topk(args, world, rank, local, fence):
+def bench_topk(args, world, rank, local, fence, dump=None, steps=None, warmup=None):
     """BASELINE config C4: item-to-item cosine top-100 over N x 128 bf16 embeddings, X replicated.  Over N > 1 ranks either the
     TRIANGLE of the symmetric sweep is sharded (--topk-shard tri, the default: rank r sweeps the query blocks r, r + N,
     ..., the pilot thresholds are all-gathered and the foreign candidate lists exchanged all-to-all inside the timed region) or the
     query rows (rows: no collective).  A step = one all-pairs pass (this rank's share of it); the N x k indices +
-    distances stay in HBM (timed region: embeddings resident -> results resident)."""
+    distances stay in HBM (timed region: embeddings resident -> results resident).  dump: a directory for the rows of the timed
+    range (rank 0's; one more pass of the exact search with the results fetched, which returns what the last timed pass left).
+    steps: timed passes (default --topk-steps); warmup: untimed whole passes before them, after the first pass that allocates
+    (default 1)."""
+    steps = args.topk_steps if steps is None else steps
+    warmup = 1 if warmup is None else warmup
     N, d, k = args.topk_n, 128, 100
     Xb, Xe = synth.s_emb(N, d, 44)
     t = capi.TopK(Xb, capi.METRIC_COSINE, dtype=capi.DTYPE_BF16, device=local)
@@ -343,12 +383,13 @@ def bench_topk(args, world, rank, local, fence):
         eng = gdist.HipTriEngine(t, fetch=False, device="cuda" if BACKEND == "nccl" else "cpu")
         tcomm = gdist.TorchComm()
         gdist.refresh_neighbors_triangle(eng, tcomm, k, gather=False)  # allocations, code objects
-        gdist.refresh_neighbors_triangle(eng, tcomm, k, gather=False)
+        for _ in range(warmup):
+            gdist.refresh_neighbors_triangle(eng, tcomm, k, gather=False)
         fence()
         t.set_profiling(True)
         with ClockSampler(local) as clk:
             t0 = time.perf_counter()
-            for _ in range(args.topk_steps):
+            for _ in range(steps):
                 gdist.refresh_neighbors_triangle(eng, tcomm, k, gather=False)
             fence()
             dt = time.perf_counter() - t0
@@ -368,17 +409,18 @@ def bench_topk(args, world, rank, local, fence):
         fence()
         per_query = (time.perf_counter() - t0) / probe_q
         full = q1 - q0
-        if per_query * full * args.topk_steps > args.topk_budget:
-            q1 = q0 + max(probe_q, int(args.topk_budget / args.topk_steps / per_query) // 8192 * 8192)
+        if per_query * full * steps > args.topk_budget:
+            q1 = q0 + max(probe_q, int(args.topk_budget / steps / per_query) // 8192 * 8192)
             q1 = min(q1, q0 + full)
-        # one untimed pass over exactly the timed query range: the tie path sizes its buffers by the number of queries with
-        # ties (1 % of them), so a short warm-up leaves allocations inside the first timed step
-        t.all_pairs(k, q0, q1, fetch=False)
+        # untimed passes over exactly the timed query range (one by default): the tie path sizes its buffers by the number of
+        # queries with ties (1 % of them), so a short warm-up leaves allocations inside the first timed step
+        for _ in range(warmup):
+            t.all_pairs(k, q0, q1, fetch=False)
         fence()
         t.set_profiling(True)
         with ClockSampler(local) as clk:
             t0 = time.perf_counter()
-            for _ in range(args.topk_steps):
+            for _ in range(steps):
                 t.all_pairs(k, q0, q1, fetch=False)
             fence()
             dt = time.perf_counter() - t0
@@ -398,13 +440,13 @@ def bench_topk(args, world, rank, local, fence):
         return None
     # rows sharded: every rank answers its q1 - q0 query rows; triangle: the ranks TOGETHER answer all N (a rank owns own_queries of them)
     pairs_step = (q1 - q0) * (N - 1) / (world if tri else 1)
-    flops_launch = 2.0 * d * (q1 - q0) / (world if tri else 1) * N * args.topk_steps / max(launches, 1)  # 2*d flop per scored pair
+    flops_launch = 2.0 * d * (q1 - q0) / (world if tri else 1) * N * steps / max(launches, 1)  # 2*d flop per scored pair
     avg_ms = sweep_ms / max(launches, 1)
     achieved = flops_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
     out = {
         "metric": "item x item cosine top-%d pairs/sec (whole job, N GPUs)" % k,
-        "value": world * pairs_step * args.topk_steps / dt, "unit": "pairs/s",
-        "n_gpus": world, "steps": args.topk_steps, "ms_per_step": dt / args.topk_steps * 1e3,
+        "value": world * pairs_step * steps / dt, "unit": "pairs/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
         "higher_is_better": True, "scaling": "strong", "dtype": "bf16", "data": "synthetic",
         "config": {"workload": "S-emb %dx%d bf16, cosine, k=%d (C4), %s x%d" % (N, d, k, "the triangle of the symmetric sweep sharded" if tri else "query rows sharded", world),
                    "sharding": "triangle" if tri else "rows",
@@ -420,12 +462,19 @@ def bench_topk(args, world, rank, local, fence):
                                   "lower than this fraction" if symmetric else "achieved = algorithmic flops (2 d per scored pair) over the sweep launches' time",
                      "clock_ghz": clk.ghz(),  # mean shader clock over the timed steps (pp_dpm_sclk), None if unreadable
                      "rescore_avg_ms": resc_ms / max(r_launches, 1),
-                     "tie_history_sweep_ms_per_step": hist_ms / max(args.topk_steps, 1),
-                     "tie_replay_ms_per_step": replay_ms / max(args.topk_steps, 1)},
+                     "tie_history_sweep_ms_per_step": hist_ms / max(steps, 1),
+                     "tie_replay_ms_per_step": replay_ms / max(steps, 1)},
     }
     if N == 1_000_000 and q1 - q0 == N:
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic("topk")
-    if world == 1 and not args.no_cpu_baseline and not tri:
+    if dump and not tri:
+        idx, dst = t.all_pairs(k, q0, q1)
+        dump_outputs(dump, {"indices": idx, "distances": dst})
+        del idx, dst
+    elif dump:
+        print("--dump-outputs: the triangle-sharded pass of N > 1 ranks has no rows of its own to write; nothing written",
+              file=sys.stderr)
+    if args.full and world == 1 and not args.no_cpu_baseline and not tri:
         try:
             m = min(q1 - q0, 65536)
             idx, dst = t.all_pairs(k, q0, q0 + m)
@@ -437,10 +486,10 @@ def bench_topk(args, world, rank, local, fence):
     return out
 
 
-def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=None):
+def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=None, dump=None):
     """The sparse similarity refresh (logics/item_to_item.go "users" kind over a sparse Dot collection): every item's
     top-100 neighbours by the inner product of the sqrt(idf)-weighted user sets.  A step = one all-pairs pass over this
-    rank's query rows; results stay in HBM."""
+    rank's query rows; results stay in HBM.  dump: a directory for rank 0's rows (one more pass with the results fetched)."""
     k = 100
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -460,7 +509,7 @@ def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=
     comm = gdist.TorchComm() if world > 1 else None
     # warm-up steps are whole steps (the pass the timed region repeats): scratch allocation, code objects, and the work plan the
     # handle keeps for its all-pairs pass (csrc/sparse.hip, gorse_sparse::Plan)
-    for _ in range(max(warmup, 1)):
+    for _ in range(warmup):
         gdist.refresh_neighbors_sharded(eng, comm, k, gather=False)
     fence()
     sp.set_profiling(True)
@@ -479,6 +528,10 @@ def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=
     sp.set_profiling(False)
     if rank != 0:
         return None
+    if dump:
+        gi, gs, gc = sp.all_pairs(k, q0, q1)
+        dump_outputs(dump, {"indices": gi, "scores": gs, "counts": gc})
+        del gi, gs, gc
     # The unit of work is the reference's: one multiply-add per (query entry, posting of its index) -- what the unsymmetric walk (and
     # the CPU baseline) performs.  The symmetric form of a full pass (round 6) meets fewer postings for the same result: `walked`.
     lens = np.bincount(idx, minlength=int(idx.max()) + 1 if idx.size else 1)
@@ -491,7 +544,7 @@ def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=
     out = {
         "metric": "sparse item x item top-%d multiply-adds/sec (postings of the reference's walk, whole job, N GPUs)" % k,
         "value": world * postings * steps / dt, "unit": "postings/s", "n_gpus": world, "steps": steps,
-        "warmup": max(warmup, 1), "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "strong",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "users item-to-item over %s: %d sparse vectors, %d entries, k=%d, query rows sharded x%d"
                                % (desc, N, int(ptr[-1]), k, world),
@@ -503,7 +556,7 @@ def bench_sparse(args, world, rank, local, fence, data=None, steps=None, warmup=
     }
     if world == 1 and N == 200_000 and q1 - q0 == N:  # the C3-shard pass the PMC passes were taken on
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic("i2i")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = sparse_cpu_baseline(ptr, idx, val, k, args.cpu_seconds, sp, q0)
         except AssertionError:
@@ -600,10 +653,11 @@ def als_cpu_baseline(uptr, uidx, iptr, P, Q, w, reg, seconds):
                       "half-sweep), hence entries / (2 x time)" % (rows, n, threads, dt, t_gram)}
 
 
-def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=64, data=None):
+def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=64, data=None, dump=None):
     """BASELINE config C5: eALS, nFactors 64 (factors: another width on the same set -- the default line carries 16, the
     reference's default nFactors, model.go:583-596).  Every rank holds the dataset and both factor matrices and solves its
-    row ranges (gorse_amd.dist.run_als_epoch); a step = one epoch = 2 half-sweeps + 2 all-gathers."""
+    row ranges (gorse_amd.dist.run_als_epoch); a step = one epoch = 2 half-sweeps + 2 all-gathers.  dump: a directory for the
+    factors the last timed epoch left."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     sc = args.als_scale
@@ -616,7 +670,7 @@ def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=
     mf.set_factors(P0, Q0)
     comm, comm_label = make_comm(args, world, rank, local)
     eng = gdist.HipAlsEngine(mf, rank, world, staging=not isinstance(comm, gdist.LibComm))
-    for _ in range(max(warmup, 1)):
+    for _ in range(warmup):
         gdist.run_als_epoch(eng, comm, w, reg)
     mf.synchronize()
     fence()
@@ -638,6 +692,8 @@ def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=
     P, Q = mf.get_factors()
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, {"P": P, "Q": Q})
     (u0, u1), (i0, i1) = eng.range
     own = int(uptr[u1] - uptr[u0]) + int(iptr[i1] - iptr[i0])  # gathered rows of this rank's two half-sweeps
     algo = own * d * 4.0 + 2.0 * ((u1 - u0) + (i1 - i0)) * d * 4  # gathers + factor rows read/written
@@ -653,7 +709,7 @@ def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=
     out = {
         "metric": "ALS feedback entries/sec (nnz per epoch x epochs / time, whole job, N GPUs)",
         "value": n * steps / dt, "unit": "entries/s", "n_gpus": world, "steps": steps,
-        "warmup": max(warmup, 1), "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
+        "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "S-als %dx%dx%d (C5%s), nFactors=%d, weight=%g reg=%g" % (U, I, n, "" if sc == 1.0 else " x%g" % sc, d, w, reg),
                    "parallelism": "rows sharded x%d, factors replicated, 2 all-gathers((U+I)*d fp32)/epoch over %s" % (world, comm_label)
@@ -673,7 +729,7 @@ def bench_als(args, world, rank, local, fence, steps=None, warmup=None, factors=
     }
     if world == 1 and sc == 1.0 and d == 64:
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic("als")
-    if world == 1 and not args.no_cpu_baseline and d == 64:
+    if args.full and world == 1 and not args.no_cpu_baseline and d == 64:
         try:
             out["cpu_baseline"] = als_cpu_baseline(uptr, uidx, iptr, P0, Q0, w, reg, args.cpu_seconds)
         except Exception as e:
@@ -710,8 +766,32 @@ def make_comm(args, world, rank, local):
     return gdist.TorchComm(), label
 
 
-def bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmup, data=None, with_cpu=True, factors=0):
-    """One BPR leg: a step = one epoch = CountFeedback() samples over this rank's resident shard + the item-factor exchange."""
+def bpr_epoch_draws(mf, n_samples, seed, epoch, sample_base, user_runs):
+    """--dump-outputs of a BPR leg: the (user, positive, negative) triplets of the epoch (seed, epoch, sample_base) -- the
+    first DUMP_BYTES worth of its samples -- as the preparation kernels of the timed path lay them out: on the user-run schedule
+    launch_prepare_users (the counting sort by user + the item draws by run, gorse_hip_test_bpr_prepare_chunk), otherwise the
+    per-sample sampler (gorse_bpr_sample_triplets).  Users ascending, failed user draws (-1) last; within a user's run the order
+    the counting sort leaves varies from run to run, so the run is written sorted by (positive, negative).
+    These are what the epoch applies, and the same bit for bit on every run with the same arguments.  The factors it leaves
+    are not: on the Hogwild schedules concurrent updates land in an order of the device's choosing (include/gorse_hip.h,
+    tests/test_gpu_cf_parity.py::_ndcg_run), so they cannot be compared output for output."""
+    m = min(n_samples, DUMP_BYTES // 24)
+    if user_runs:
+        off, i, j = mf.bpr_prepare_chunk(m, seed, epoch, sample_base)
+        assert off[0] == 0 and off[mf.U + 1] == m, "user-run preparation: run offsets do not cover the samples"
+        u = np.repeat(np.arange(mf.U + 1, dtype=np.int32), np.diff(off.astype(np.int64)))
+        u[off[mf.U]:] = -1
+        i[off[mf.U]:] = -1  # positions of failed user draws are never written: (-1, -1, -1), as the per-sample sampler gives
+        j[off[mf.U]:] = -1
+    else:
+        u, i, j = mf.bpr_sample_triplets(m, seed, epoch, sample_base)
+    order = np.lexsort((j, i, np.where(u < 0, mf.U, u)))
+    return {"users": u[order], "positives": i[order], "negatives": j[order]}
+
+
+def bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmup, data=None, with_cpu=True, factors=0, dump=None):
+    """One BPR leg: a step = one epoch = CountFeedback() samples over this rank's resident shard + the item-factor exchange.
+    dump: a directory for the triplets the last timed epoch trained on (rank 0's; bpr_epoch_draws)."""
     if data is None:
         data = make_data(workload, rank, args)[0]
     d, desc = make_data_desc(workload, factors or args.factors)
@@ -759,6 +839,9 @@ def bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmu
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if dump and rank == 0:
+        runs = args.mode in (capi.BPR_HOGWILD_ATOMIC, capi.BPR_HOGWILD_STORES) and mf.bpr_user_runs()  # the route the epochs took
+        dump_outputs(dump, bpr_epoch_draws(mf, n_samples, 2024, warmup + steps, rank * (1 << 40), runs))
     launches, upd_ms = mf.get_profile(capi.PROF_BPR_UPDATE)
     s_launches, smp_ms = mf.get_profile(capi.PROF_BPR_SAMPLE)
     o_launches, sort_ms = mf.get_profile(capi.PROF_BPR_SORT)
@@ -768,7 +851,7 @@ def bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmu
     # the same epochs through the SYNCHRONOUS entry point (gorse_bpr_epoch: what a Fit loop that evaluates after every epoch
     # calls): each call drains both streams, so nothing of epoch e + 1 is prepared under epoch e
     sync_ms = None
-    if world == 1 and args.sync_steps > 0 and args.mode != capi.BPR_SEQUENTIAL:
+    if args.full and world == 1 and args.sync_steps > 0 and args.mode != capi.BPR_SEQUENTIAL:
         t0 = time.perf_counter()
         for s in range(args.sync_steps):
             mf.bpr_epoch(n_samples, lr, reg, 2024, warmup + steps + s + 1, mode=args.mode)
@@ -837,7 +920,7 @@ def bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmu
         out["roofline"]["traffic_full_launch"], out["roofline"]["full_launch_samples"] = tr, full_launch
         out["roofline"]["traffic"] = tr * samples_per_launch / full_launch if tr is not None else None
         out["roofline"]["traffic_source"] = src
-    if world == 1 and with_cpu and not args.no_cpu_baseline:
+    if args.full and world == 1 and with_cpu and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(data, d, lr, reg, args.cpu_seconds if with_cpu is True else float(with_cpu))
         except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
@@ -1045,6 +1128,11 @@ def main():
     torch.cuda.set_device(local)
     # BASELINE.json quotes the single-GPU number on C2 (S-ml1m) and the 8-GPU number on C3: that is what N = 1 / N > 1 run
     workload = args.workload or ("ml1m" if world == 1 else "c3")
+    # the defaults are sized for a 0.7 ms epoch; c3full and big take fewer.  An explicit --steps / --warmup always holds.
+    if args.steps is None:
+        args.steps = {"c3full": 5, "big": 3, "topk": args.topk_steps}.get(workload, 20)
+    if args.warmup is None:
+        args.warmup = {"c3full": 2, "big": 1, "topk": 1}.get(workload, 3)
     if args.bpr_chunk:
         capi.lib().gorse_hip_test_set_bpr_chunk(args.bpr_chunk)
 
@@ -1056,13 +1144,12 @@ def main():
 
     if workload in ("topk", "als", "i2i"):
         if workload == "als":
-            out = bench_als(args, world, rank, local, fence0)
+            out = bench_als(args, world, rank, local, fence0, dump=args.dump_outputs)
         elif workload == "i2i":
-            out = bench_sparse(args, world, rank, local, fence0)
+            out = bench_sparse(args, world, rank, local, fence0, dump=args.dump_outputs)
         else:
-            out = bench_topk(args, world, rank, local, fence0)
+            out = bench_topk(args, world, rank, local, fence0, dump=args.dump_outputs, steps=args.steps, warmup=args.warmup)
             if rank == 0:
-                out["warmup"] = 1
                 out["vs_baseline"] = None
         if rank == 0:
             emit(out, workload)
@@ -1072,14 +1159,11 @@ def main():
         return
 
     comm, comm_label = make_comm(args, world, rank, local)
-    steps, warmup = args.steps, args.warmup
-    if workload in ("c3full", "big") and args.steps == 20 and args.warmup == 3:  # the defaults are sized for a 0.7 ms epoch
-        steps, warmup = (5, 2) if workload == "c3full" else (3, 1)
-    out = bench_bpr(args, workload, world, rank, local, comm, comm_label, steps, warmup)
-    full_line = args.workload is None and world == 1  # the default single-GPU run carries the other configurations too
+    out = bench_bpr(args, workload, world, rank, local, comm, comm_label, args.steps, args.warmup, dump=args.dump_outputs)
+    full_line = args.workload is None and world == 1  # the default single-GPU run carries the other configurations too (--full)
     # BASELINE.json's metric has two halves; the second one rides on the C2 line of one GPU and on the C3 line of N > 1
-    # (query rows sharded over the ranks, no collective)
-    if ((workload == "ml1m" and world == 1) or (workload == "c3" and world > 1 and args.workload is None)) and not args.no_topk:
+    # (query rows sharded over the ranks, no collective) -- with --full: a plain run times the headline alone
+    if args.full and ((workload == "ml1m" and world == 1) or (workload == "c3" and world > 1 and args.workload is None)) and not args.no_topk:
         # N > 1: the top-k leg's exchanges (the triangle shard's all-gather and all-to-all over RCCL) have run on emulated ranks and over
         # gloo only -- no multi-GPU node was ever available to the builder.  A collective that never completes must not cost the line
         # its BPR half: a watchdog on every rank emits the line WITHOUT the leg (rank 0) and leaves, should the leg not return in time.
@@ -1099,7 +1183,7 @@ def main():
             dog.cancel()
         if rank == 0:
             out["topk"] = topk
-    if full_line and not args.no_extra:
+    if full_line and args.full and not args.no_extra:
         full = synth.s_big_full()
         out["c3"] = leg(lambda: bench_bpr(args, "c3full", 1, 0, local, None, "single GPU", 5, 2, data=full, with_cpu=5.0),
                         "BPR positive-samples/sec, C3 whole on one GPU")

@@ -6,7 +6,7 @@
 #   info                 host cores / memory, GPU memory
 #   pytest[:<expr>]      the GPU suite (or `-k <expr>`), output with the tests' printed error figures
 #   pyfile:<path>[:<k>]  one test file (optionally -k <k>)
-#   bench[:<workload>]   python bench.py [--workload W]            -> <tag>_bench_<W>.json
+#   bench[:<workload>]   python bench.py [--workload W] --full     -> <tag>_bench_<W>.json
 #   stats[:<workload>]   rocprofv3 --kernel-trace --stats of the same command (no CPU baseline) -> <tag>_kernel_stats_<W>.txt
 #   pmc:<workload>:<kernel substring>:<key>[:wide]   FETCH_SIZE and WRITE_SIZE passes -> <tag>_traffic.json[key]
 #   sq:<workload>:<kernel substring>                 one SQ pass (MFMA busy, wave cycles, waits) -> <tag>_pmc_SQ_<W>.txt
@@ -22,10 +22,10 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-bench_args() {  # workload name -> bench.py arguments
+bench_args() {  # workload name -> bench.py arguments (--full: every leg, CPU baseline and check the line carries)
     case "$1" in
-        default) echo "" ;;
-        *) echo "--workload $1" ;;
+        default) echo "--full" ;;
+        *) echo "--workload $1 --full" ;;
     esac
 }
 for STAGE in "$@"; do

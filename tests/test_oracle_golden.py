@@ -165,18 +165,24 @@ def test_mm_bit_equal_fixture(oracle):
 
 
 def test_bit_equal_to_live_reference_kernels(oracle, ref):
-    """Same check against oracle/_ref run live, on fresh random data."""
-    if ref is None:
-        pytest.skip("oracle/_ref/libgorse_ref.so absent or host lacks AVX512")
-    rng = np.random.default_rng(7)
-    for n in list(range(1, 140)) + [255, 256, 257]:
-        a = rng.standard_normal(n).astype(np.float32)
-        b = rng.standard_normal(n).astype(np.float32)
-        for isa in (orc.ISA_AVX, orc.ISA_AVX512):
+    """Same check against oracle/_ref run live, on seeded random data; where oracle/_ref is absent (or the host lacks
+    AVX512), against the outputs those kernels recorded on the same data (tests/golden/ref_live_vectors.npz,
+    scripts/gen_golden_live_ref_vectors.py), which the live kernels must reproduce too where they run."""
+    z = np.load(os.path.join(GOLD, "ref_live_vectors.npz"))
+    sizes = list(range(1, 140)) + [255, 256, 257]
+    assert z["sizes"].tolist() == sizes
+    off = 0
+    for j, n in enumerate(sizes):  # the vectors np.random.default_rng(7) drew, recorded with the outputs
+        a, b = z["a"][off:off + n], z["b"][off:off + n]
+        off += n
+        for isa, tag in ((orc.ISA_AVX, "256"), (orc.ISA_AVX512, "512")):
             oracle.set_isa(isa)
-            assert np.float32(oracle.dot(a, b)).view(np.uint32) == np.float32(ref.dot(isa, a, b)).view(np.uint32)
-            assert np.float32(oracle.euclidean(a, b)).view(np.uint32) == \
-                np.float32(ref.euclidean(isa, a, b)).view(np.uint32)
+            want_dot, want_euc = z["dot" + tag][j], z["euc" + tag][j]
+            if ref is not None:
+                assert np.float32(ref.dot(isa, a, b)).view(np.uint32) == want_dot.view(np.uint32)
+                assert np.float32(ref.euclidean(isa, a, b)).view(np.uint32) == want_euc.view(np.uint32)
+            assert np.float32(oracle.dot(a, b)).view(np.uint32) == want_dot.view(np.uint32)
+            assert np.float32(oracle.euclidean(a, b)).view(np.uint32) == want_euc.view(np.uint32)
 
 
 def test_simd_equals_scalar_on_integers(oracle):
