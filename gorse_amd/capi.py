@@ -19,6 +19,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_NEG_DOT, METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_EUCLIDEAN_BF16 = 0, 1, 2, 3
 PROF_BPR_UPDATE, PROF_BPR_SAMPLE, PROF_ALS_SWEEP, PROF_ALS_GRAM, PROF_BPR_SORT, PROF_COMM = 0, 1, 2, 3, 4, 5
 COMM_ID_BYTES = 128
+OPT_SGD, OPT_ADAM = 0, 1
 PROF_TOPK_SCORE, PROF_TOPK_RESCORE, PROF_TOPK_SWEEP, PROF_TOPK_SELECT, PROF_TOPK_HIST, PROF_TOPK_REPLAY = 0, 1, 2, 3, 4, 5
 
 _f32p = C.POINTER(C.c_float)
@@ -99,6 +100,13 @@ SIGNATURES = {
                                     _f32p, C.c_int32, _f32p, C.c_int32]),
     "gorse_hip_sgemm_device": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32,
                                            _vp, C.c_int32, _vp, C.c_int32]),
+    "gorse_fm_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64, C.c_int32]),
+    "gorse_fm_destroy": (C.c_int32, [_vp]),
+    "gorse_fm_set_params": (C.c_int32, [_vp, C.c_float, _f32p, _f32p]),
+    "gorse_fm_get_params": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
+    "gorse_fm_set_train": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p]),
+    "gorse_fm_epoch": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, _i32p, _f32p]),
+    "gorse_fm_predict": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p]),
     "gorse_hip_test_set_exact_exp": (None, [C.c_int32]),
     "gorse_hip_test_set_variant": (None, [C.c_int32]),
     "gorse_hip_test_set_topk_path": (None, [C.c_int32]),
@@ -374,6 +382,64 @@ class MF:
         n, ms = C.c_int64(0), C.c_double(0)
         check(lib().gorse_mf_get_profile(self.h, cls, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+class FM:
+    """One gorse_fm handle: a factorization machine (ctr.AFM without the embedding branch) resident on one GPU.
+    Rows are n x width matrices of feature indices and values, padded with index 0 / value 0."""
+
+    def __init__(self, n_features, n_factors, device=0):
+        self.nf, self.d = int(n_features), int(n_factors)
+        self.h = _vp()
+        check(lib().gorse_fm_create(C.byref(self.h), device, self.nf, self.d))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gorse_fm_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_params(self, B, W, V):
+        W = _arr(W, np.float32).reshape(-1)
+        V = _arr(V, np.float32).reshape(-1)
+        if W.size != self.nf or V.size != self.nf * self.d:
+            raise GorseHipError(ERR_INVALID, "W must hold n_features and V n_features x d values")
+        check(lib().gorse_fm_set_params(self.h, float(B), _p(W, _f32p), _p(V, _f32p)))
+
+    def get_params(self):
+        B = np.zeros(1, np.float32)
+        W = np.empty(self.nf, np.float32)
+        V = np.empty((self.nf, self.d), np.float32)
+        check(lib().gorse_fm_get_params(self.h, _p(B, _f32p), _p(W, _f32p), _p(V, _f32p)))
+        return B[0], W, V
+
+    @staticmethod
+    def _rows(indices, values):
+        idx, val = _arr(indices, np.int32), _arr(values, np.float32)
+        if idx.ndim != 2 or idx.shape != val.shape:
+            raise GorseHipError(ERR_INVALID, "indices and values must be n x width matrices of one shape")
+        return idx, val
+
+    def set_train(self, indices, values, target):
+        idx, val = self._rows(indices, values)
+        tgt = _arr(target, np.float32)
+        if tgt.size != idx.shape[0]:
+            raise GorseHipError(ERR_INVALID, "one target per row")
+        check(lib().gorse_fm_set_train(self.h, idx.shape[0], idx.shape[1], _p(idx, _i32p), _p(val, _f32p), _p(tgt, _f32p)))
+
+    def epoch(self, batch_size, optimizer, lr, wd, cancel=None):
+        """one epoch over the training set; returns the cost (sum of the batches' mean losses)"""
+        cost = C.c_float(0)
+        check(lib().gorse_fm_epoch(self.h, batch_size, optimizer, lr, wd, _p(cancel, _i32p) if cancel is not None else None,
+                                   C.byref(cost)))
+        return cost.value
+
+    def predict(self, indices, values):
+        idx, val = self._rows(indices, values)
+        out = np.empty(idx.shape[0], np.float32)
+        check(lib().gorse_fm_predict(self.h, idx.shape[0], idx.shape[1], _p(idx, _i32p), _p(val, _f32p), _p(out, _f32p)))
+        return out
 
 
 class TopK:

@@ -1,0 +1,684 @@
+// fm.hip -- ctr.AFM without the item-embedding branch (model/ctr/fm.go:111-126): the factorization machine
+// logit = B + sum_j W[idx_j] x_j + 0.5 sum_f ((sum_j V[idx_j,f] x_j)^2 - sum_j V[idx_j,f]^2 x_j^2), trained with
+// BCEWithLogits on contiguous batches (fm.go:362-378) and the reference's dense SGD / Adam steps
+// (common/nn/optimizers.go:70-84, 118-156), plus batch scoring (BatchInternalPredict, fm.go:156-178).
+//
+// One training step = three launches, enqueued for a whole epoch without a host round trip:
+//   fm_forward_kernel  one sample per G-lane group: gathers the row's V / W entries, DPP-reduces the pairwise term, writes the
+//                      sample's loss, its loss gradient g_b = (sigmoid(logit) - y) / n_batch and its vx_f = sum_j V[idx_j,f] x_j;
+//   fm_accum_kernel    one wave per feature the batch touches (the batch's (feature, position) list is sorted once per training
+//                      set and batch size): the row's gradient summed over its positions in position order, in a fixed shape,
+//                      no atomics; one extra block reduces dB and the batch's mean loss in a fixed tree;
+//   fm_opt_kernel      one pass over every parameter (and the Adam moments) with 16-byte accesses: the dense step the reference
+//                      takes, with the touched rows' gradient found through a per-row tag (step, slot).
+// Every floats.* call of the reference runs the AVX512 kernels of common/floats/src/floats_avx512.c: a 16-lane FMA body and
+// unfused 8-lane / scalar tails, and partitionAligned(.., 32) leaves the tail at the tensor's last len % 16 elements; the
+// optimizer kernel applies the same rule by element position (fmaf vs. mul then add; the library builds with -ffp-contract=off).
+#include "common.hpp"
+#include "cf_device.hpp"
+
+struct gorse_fm {
+    int device = 0;
+    int64_t nf = 0;
+    int d = 0;
+    hipStream_t s = nullptr;
+    gorse::DevBuf<float> V, W, B, mV, mW, mB, vV, vW, vB;  // parameters and Adam moments, one allocation per tensor
+    gorse::DevBuf<int64_t> tag;                            // per feature row: ((step + 1) << 32) | slot of the step that touched it
+    int64_t step = 0;                                      // training steps this handle has run (the tags' clock)
+    int64_t adam_t = 0;                                    // nn.Adam's t: reset by set_params (a new Fit)
+    // training set
+    int64_t n = 0;
+    int width = 0;
+    std::vector<int32_t> h_idx;
+    std::vector<float> h_val;
+    gorse::DevBuf<int32_t> idx;
+    gorse::DevBuf<float> val, tgt;
+    // per-batch-size plan: for every batch the features it touches (ascending) and each one's positions (ascending)
+    int plan_bs = 0;
+    std::vector<int64_t> uoff;  // n_batches + 1: slots of batch k = [uoff[k], uoff[k+1])
+    int64_t max_slots = 0;
+    gorse::DevBuf<int32_t> uniq, seg, pos;
+    // scratch
+    gorse::DevBuf<float> gs, loss, vx, gV, gW, gB, cost;
+    gorse::DevBuf<int32_t> p_idx;
+    gorse::DevBuf<float> p_val, p_out;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+namespace gorse {
+namespace fm {
+
+constexpr int kBlock = 256;
+constexpr int kMaxFactors = 128;
+constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kEps = 1e-8f;
+
+// lanes per sample: the smallest of 8 / 16 / 32 / 64 that holds d (two factors per lane above 64)
+inline int lanes_for(int d) {
+    int g = 8;
+    while (g < d && g < 64) g *= 2;
+    return g;
+}
+
+// sum over each aligned group of G lanes; the group's first lane holds the total (a fixed tree: deterministic)
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+    if constexpr (G == 8) {
+        v = group_tree8_halves(v);
+    } else {
+        v = group_tree16(v);
+        if constexpr (G >= 32) v = v + __shfl_xor(v, 16, 64);
+        if constexpr (G == 64) v = v + __shfl_xor(v, 32, 64);
+    }
+    return v;
+}
+
+struct FwdArgs {
+    const int32_t *idx;  // n x width
+    const float *val;
+    const float *tgt;    // training only
+    const float *V, *W, *B;
+    int64_t row0, nrows;
+    int width, d;
+    float inv_n;         // 1 / rows of the batch (training)
+    float *out;          // scoring: logits
+    float *gs, *loss, *vx;  // training: per sample g_b, loss_b, vx (nrows x d)
+};
+
+template <int G, int NF, bool TRAIN>
+__global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs a) {
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t b = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
+    if (b >= a.nrows) return;  // whole groups leave together
+    const int64_t r = a.row0 + b;
+    const int32_t *ri = a.idx + r * a.width;
+    const float *rv = a.val + r * a.width;
+    float vx[NF], sq[NF];
+#pragma unroll
+    for (int k = 0; k < NF; k++) vx[k] = sq[k] = 0.0f;
+    float lin = 0.0f;
+    for (int j = 0; j < a.width; j++) {
+        const float x = rv[j];
+        if (x == 0.0f) continue;  // padding (index 0, value 0) and zero values add only signed zeros
+        const int64_t id = ri[j];
+        const float *vr = a.V + id * a.d;
+        const float x2 = x * x;
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+            const int f = lane + k * G;
+            if (f < a.d) {
+                const float v = vr[f];
+                vx[k] = fmaf(v, x, vx[k]);
+                sq[k] = fmaf(v * v, x2, sq[k]);
+            }
+        }
+        lin = fmaf(a.W[id], x, lin);
+    }
+    float part = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NF; k++) part += vx[k] * vx[k] - sq[k];
+    part = group_sum<G>(part);
+    if (TRAIN) {
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+            const int f = lane + k * G;
+            if (f < a.d) a.vx[b * a.d + f] = vx[k];
+        }
+    }
+    if (lane != 0) return;
+    const float logit = (lin + 0.5f * part) + a.B[0];
+    if (!TRAIN) {
+        a.out[b] = logit;
+        return;
+    }
+    // BCEWithLogits (common/nn/functions.go:218-243) with y = (t + 1) / 2
+    const float y = (a.tgt[r] + 1.0f) * 0.5f;
+    a.loss[b] = fmaxf(logit, 0.0f) - logit * y + logf(1.0f + expf(-fabsf(logit)));
+    a.gs[b] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
+}
+
+struct AccArgs {
+    const int32_t *uniq, *seg, *pos;  // the batch's slots: uniq[s] = feature, positions pos[seg[s] .. seg[s+1])
+    int64_t slot0, nslots;
+    const float *val;  // batch rows' values (row0 * width applied)
+    const float *V;
+    const float *gs, *loss, *vx;
+    int64_t nrows;
+    int width, d;
+    int64_t tag_hi;  // (step + 1) << 32
+    int64_t *tag;
+    float *gV, *gW, *gB, *cost;
+};
+
+// One wave per touched feature.  The wave's 64 / G groups take every (64 / G)-th position of the feature's list in order, each
+// group's lanes hold the row's factors; the groups' partial sums are then added in a fixed butterfly.  The last block instead
+// sums dB and the batch's loss over the samples (one thread per stride, then an LDS tree) and adds the mean to the epoch's cost.
+template <int G, int NF>
+__global__ __launch_bounds__(kBlock) void fm_accum_kernel(AccArgs a) {
+    if (blockIdx.x == gridDim.x - 1) {
+        __shared__ float sg[kBlock], sl[kBlock];
+        float g = 0.0f, l = 0.0f;
+        for (int64_t b = threadIdx.x; b < a.nrows; b += kBlock) {
+            g += a.gs[b];
+            l += a.loss[b];
+        }
+        sg[threadIdx.x] = g;
+        sl[threadIdx.x] = l;
+        __syncthreads();
+        for (int o = kBlock / 2; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) {
+                sg[threadIdx.x] += sg[threadIdx.x + o];
+                sl[threadIdx.x] += sl[threadIdx.x + o];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            a.gB[0] = sg[0];
+            a.cost[0] = a.cost[0] + sl[0] / (float)a.nrows;
+        }
+        return;
+    }
+    constexpr int NG = 64 / G;
+    const int64_t s = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
+    if (s >= a.nslots) return;
+    const int lane = threadIdx.x & (G - 1);
+    const int grp = (threadIdx.x & 63) / G;
+    const int64_t gslot = a.slot0 + s;
+    const int32_t feat = a.uniq[gslot];
+    const int32_t beg = a.seg[gslot], end = a.seg[gslot + 1];
+    float vr[NF], acc[NF];
+#pragma unroll
+    for (int k = 0; k < NF; k++) {
+        const int f = lane + k * G;
+        vr[k] = f < a.d ? a.V[(int64_t)feat * a.d + f] : 0.0f;
+        acc[k] = 0.0f;
+    }
+    float accw = 0.0f;
+    constexpr int U = 4;  // positions whose loads are issued together; the sum still runs in position order
+    for (int q0 = beg + grp; q0 < end; q0 += U * NG) {
+        float gx[U], xx[U], x2[U];
+        int64_t bb[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int q = q0 + u * NG;
+            const int p = q < end ? a.pos[q] : 0;
+            const int64_t b = p / a.width;
+            const float x = q < end ? a.val[p] : 0.0f;
+            const float g = q < end ? a.gs[b] : 0.0f;
+            bb[u] = b;
+            xx[u] = x;
+            gx[u] = g;
+            x2[u] = x * x;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (q0 + u * NG >= end) break;
+            accw += gx[u] * xx[u];
+#pragma unroll
+            for (int k = 0; k < NF; k++) {
+                const int f = lane + k * G;
+                if (f < a.d) {
+                    const float t = xx[u] * a.vx[bb[u] * a.d + f] - vr[k] * x2[u];
+                    acc[k] += gx[u] * t;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+        for (int k = 0; k < NF; k++) acc[k] = acc[k] + __shfl_xor(acc[k], o, 64);
+        accw = accw + __shfl_xor(accw, o, 64);
+    }
+    if (grp != 0) return;
+#pragma unroll
+    for (int k = 0; k < NF; k++) {
+        const int f = lane + k * G;
+        if (f < a.d) a.gV[s * a.d + f] = acc[k];
+    }
+    if (lane == 0) {
+        a.gW[s] = accw;
+        a.tag[feat] = a.tag_hi | s;
+    }
+}
+
+struct OptArgs {  // tensor t = 0 (V), 1 (W), 2 (B); the kernel selects by constant index only (no private copy of the block)
+    float *p[3], *m[3], *v[3];
+    int64_t len[3];
+    int64_t blocks0, blocks1;  // blocks of V, then W; the last block is B
+    int d;
+    const int64_t *tag;
+    int64_t tag_hi;
+    const float *gV, *gW, *gB;
+    float wd, lr, c1, c2;  // c1 = 1 - beta1, c2 = 1 - beta2 (fp32, as the reference forms them)
+};
+
+template <bool ADAM>
+__device__ __forceinline__ void opt_elem(float &p, float &m, float &v, float g, bool fused, float wd, float lr, float c1,
+                                         float c2) {
+    // floats.MulConstAddTo(p, wd, grad, b1): b1 = grad + p * wd
+    const float b1 = fused ? fmaf(p, wd, g) : g + p * wd;
+    if (!ADAM) {
+        // floats.MulConstAdd(b, -lr, p)
+        p = fused ? fmaf(b1, -lr, p) : p + b1 * (-lr);
+        return;
+    }
+    float b2 = b1 - m;                                   // floats.SubTo(b1, m, b2)
+    m = fused ? fmaf(b2, c1, m) : m + b2 * c1;       // floats.MulConstAdd(b2, 1 - beta1, m)
+    b2 = b1 * b1;                                        // floats.MulTo(b1, b1, b2)
+    b2 = b2 - v;                                         // floats.Sub(b2, v)
+    v = fused ? fmaf(b2, c2, v) : v + b2 * c2;       // floats.MulConstAdd(b2, 1 - beta2, v)
+    // floats.SqrtTo(v, b2), correctly rounded: v_sqrt_f32 alone is not; the fp64 square root is, and rounding it to fp32
+    // again gives the correctly rounded fp32 root (53 >= 2 x 24 + 2 bits: double rounding is harmless for a square root)
+    b2 = (float)sqrt((double)v);
+    b2 = b2 + kEps;                                      // floats.AddConst(b2, eps)
+    const float q = m / b2;                              // floats.DivTo(m, b2, b1) (the division is correctly rounded)
+    p = fused ? fmaf(q, -lr, p) : p + q * (-lr);     // floats.MulConstAdd(b1, -lr, p)
+}
+
+template <bool ADAM>
+__global__ __launch_bounds__(kBlock) void fm_opt_kernel(OptArgs a) {
+    int t;
+    int64_t blk = blockIdx.x;
+    if (blk < a.blocks0) {
+        t = 0;
+    } else if (blk < a.blocks0 + a.blocks1) {
+        t = 1;
+        blk -= a.blocks0;
+    } else {
+        t = 2;
+        blk = 0;
+    }
+    const int64_t L = t == 0 ? a.len[0] : t == 1 ? a.len[1] : a.len[2];
+    const int64_t e0 = (blk * kBlock + threadIdx.x) * 4;
+    if (e0 >= L) return;
+    const int64_t body = L - L % 16;  // elements past this run the reference's unfused tails
+    const int rowlen = t == 0 ? a.d : 1;
+    float *P = t == 0 ? a.p[0] : t == 1 ? a.p[1] : a.p[2];
+    float *M = t == 0 ? a.m[0] : t == 1 ? a.m[1] : a.m[2];
+    float *Vm = t == 0 ? a.v[0] : t == 1 ? a.v[1] : a.v[2];
+    float p[4], m[4], v[4], g[4];
+    const bool full = e0 + 4 <= L;
+    if (full) {
+        const float4 p4 = *reinterpret_cast<const float4 *>(P + e0);
+        p[0] = p4.x, p[1] = p4.y, p[2] = p4.z, p[3] = p4.w;
+        if (ADAM) {
+            const float4 m4 = *reinterpret_cast<const float4 *>(M + e0);
+            const float4 v4 = *reinterpret_cast<const float4 *>(Vm + e0);
+            m[0] = m4.x, m[1] = m4.y, m[2] = m4.z, m[3] = m4.w;
+            v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            p[k] = e0 + k < L ? P[e0 + k] : 0.0f;
+            m[k] = ADAM && e0 + k < L ? M[e0 + k] : 0.0f;
+            v[k] = ADAM && e0 + k < L ? Vm[e0 + k] : 0.0f;
+        }
+    }
+    // gradient: the touched rows' sums through the tag of their row, zero elsewhere
+    // a 32-bit division wherever the index fits (the 64-bit one is a long instruction sequence)
+    int64_t row = e0 < ((int64_t)1 << 32) ? (int64_t)((uint32_t)e0 / (uint32_t)rowlen) : e0 / rowlen;
+    int col = (int)(e0 - row * rowlen);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float gk = 0.0f;
+        if (t == 2) {
+            gk = a.gB[0];
+        } else if (e0 + k < L) {
+            const int64_t tg = a.tag[row];
+            if ((tg & ~(int64_t)0xffffffff) == a.tag_hi) {
+                const int64_t slot = tg & 0xffffffff;
+                gk = t == 0 ? a.gV[slot * a.d + col] : a.gW[slot];
+            }
+        }
+        g[k] = gk;
+        if (++col == rowlen) {
+            col = 0;
+            row++;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) opt_elem<ADAM>(p[k], m[k], v[k], g[k], e0 + k < body, a.wd, a.lr, a.c1, a.c2);
+    if (full) {
+        *reinterpret_cast<float4 *>(P + e0) = make_float4(p[0], p[1], p[2], p[3]);
+        if (ADAM) {
+            *reinterpret_cast<float4 *>(M + e0) = make_float4(m[0], m[1], m[2], m[3]);
+            *reinterpret_cast<float4 *>(Vm + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (e0 + k < L) {
+                P[e0 + k] = p[k];
+                if (ADAM) {
+                    M[e0 + k] = m[k];
+                    Vm[e0 + k] = v[k];
+                }
+            }
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------
+
+// math32.Pow(x, y) for a positive integer y (chewxy/math32 pow.go, the float32 statement of Go's math.Pow):
+// x = x1 * 2^xe by Frexp, then square-and-multiply on the mantissa with the exponent kept apart.
+inline float pow_int(float x, int64_t y) {
+    int xe = 0;
+    float x1 = std::frexp(x, &xe);
+    float a1 = 1.0f;
+    int64_t ae = 0;
+    for (int64_t i = y; i != 0; i >>= 1) {
+        if (i & 1) {
+            a1 *= x1;
+            ae += xe;
+        }
+        x1 *= x1;
+        xe <<= 1;
+        if (x1 < 0.5f) {
+            x1 += x1;
+            xe--;
+        }
+    }
+    return std::ldexp(a1, (int)ae);
+}
+
+// nn.Adam.Step's lr for step t (optimizers.go:121-123), in fp32
+inline float adam_lr(float alpha, int64_t t) {
+    const float fix1 = 1.0f - pow_int(kBeta1, t);
+    const float fix2 = 1.0f - pow_int(kBeta2, t);
+    return alpha * std::sqrt(fix2) / fix1;
+}
+
+// train: the batches' position lists index a training set's padded positions in int32; scoring indexes in int64
+int32_t check_rows(const gorse_fm *h, int64_t n, int32_t width, const int32_t *indices, const float *values, bool train) {
+    if (n < 0 || width <= 0) return fail(GORSE_ERR_INVALID, "n must be >= 0 and width positive (n = %lld, width = %d)", (long long)n, width);
+    if (n > 0 && (!indices || !values)) return fail(GORSE_ERR_INVALID, "indices / values are NULL");
+    if (train && n * (int64_t)width > INT32_MAX) return fail(GORSE_ERR_INVALID, "a training set's n x width must fit int32");
+    for (int64_t e = 0; e < n * width; e++)
+        if (indices[e] < 0 || indices[e] >= h->nf)
+            return fail(GORSE_ERR_RANGE, "feature index %d at position %lld out of range [0,%lld)", indices[e], (long long)e,
+                        (long long)h->nf);
+    return GORSE_OK;
+}
+
+template <bool TRAIN>
+int32_t launch_forward(gorse_fm *h, const FwdArgs &a) {
+    const int G = lanes_for(h->d);
+    const int64_t grid = ceil_div(a.nrows * G, kBlock);
+    if (grid == 0) return GORSE_OK;
+#define FM_FWD(g, nf) fm_forward_kernel<g, nf, TRAIN><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a)
+    switch (G) {
+        case 8: FM_FWD(8, 1); break;
+        case 16: FM_FWD(16, 1); break;
+        case 32: FM_FWD(32, 1); break;
+        default:
+            if (h->d > 64) FM_FWD(64, 2); else FM_FWD(64, 1);
+    }
+#undef FM_FWD
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+int32_t launch_accum(gorse_fm *h, const AccArgs &a) {
+    const int G = lanes_for(h->d);
+    const int64_t grid = ceil_div(a.nslots * 64, kBlock) + 1;
+#define FM_ACC(g, nf) fm_accum_kernel<g, nf><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a)
+    switch (G) {
+        case 8: FM_ACC(8, 1); break;
+        case 16: FM_ACC(16, 1); break;
+        case 32: FM_ACC(32, 1); break;
+        default:
+            if (h->d > 64) FM_ACC(64, 2); else FM_ACC(64, 1);
+    }
+#undef FM_ACC
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+// The (feature, position) order of every batch: positions with a nonzero value, sorted by feature then position (the order
+// the reference's embedding backward adds them in, op.go:694-699).  Depends only on the training set and the batch size.
+int32_t build_plan(gorse_fm *h, int32_t bs) {
+    const int64_t nb = ceil_div(h->n, bs);
+    const int w = h->width;
+    std::vector<std::vector<uint64_t>> keys((size_t)nb);
+    parallel_rows(nb, nullptr, [&](int, int64_t k0, int64_t k1) {
+        for (int64_t k = k0; k < k1; k++) {
+            const int64_t r0 = k * bs, r1 = std::min<int64_t>(h->n, r0 + bs);
+            auto &ks = keys[(size_t)k];
+            ks.clear();
+            for (int64_t p = 0; p < (r1 - r0) * w; p++)
+                if (h->h_val[(size_t)(r0 * w + p)] != 0.0f)
+                    ks.push_back(((uint64_t)(uint32_t)h->h_idx[(size_t)(r0 * w + p)] << 32) | (uint64_t)p);
+            std::sort(ks.begin(), ks.end());
+        }
+    });
+    std::vector<int32_t> uniq, seg, pos;
+    h->uoff.assign((size_t)nb + 1, 0);
+    h->max_slots = 0;
+    for (int64_t k = 0; k < nb; k++) {
+        const auto &ks = keys[(size_t)k];
+        for (size_t q = 0; q < ks.size(); q++) {
+            const int32_t f = (int32_t)(ks[q] >> 32);
+            if (q == 0 || (int32_t)(ks[q - 1] >> 32) != f) {
+                uniq.push_back(f);
+                seg.push_back((int32_t)pos.size());
+            }
+            pos.push_back((int32_t)(ks[q] & 0xffffffffu));
+        }
+        h->uoff[(size_t)k + 1] = (int64_t)uniq.size();
+        h->max_slots = std::max<int64_t>(h->max_slots, h->uoff[(size_t)k + 1] - h->uoff[(size_t)k]);
+    }
+    seg.push_back((int32_t)pos.size());
+    GORSE_TRY(h->uniq.alloc(uniq.size()));
+    GORSE_TRY(h->seg.alloc(seg.size()));
+    GORSE_TRY(h->pos.alloc(pos.size()));
+    if (!uniq.empty()) GORSE_HIP_CHECK(hipMemcpy(h->uniq.p, uniq.data(), uniq.size() * 4, hipMemcpyHostToDevice));
+    GORSE_HIP_CHECK(hipMemcpy(h->seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice));
+    if (!pos.empty()) GORSE_HIP_CHECK(hipMemcpy(h->pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    GORSE_TRY(h->gV.ensure((size_t)std::max<int64_t>(1, h->max_slots) * h->d));
+    GORSE_TRY(h->gW.ensure((size_t)std::max<int64_t>(1, h->max_slots)));
+    GORSE_TRY(h->gs.ensure((size_t)bs));
+    GORSE_TRY(h->loss.ensure((size_t)bs));
+    GORSE_TRY(h->vx.ensure((size_t)bs * h->d));
+    h->plan_bs = bs;
+    return GORSE_OK;
+}
+
+}  // namespace fm
+}  // namespace gorse
+
+using namespace gorse;
+
+extern "C" int32_t gorse_fm_create(gorse_fm **out, int32_t device, int64_t n_features, int32_t n_factors) {
+    if (!out) return fail(GORSE_ERR_INVALID, "handle pointer is NULL");
+    *out = nullptr;
+    if (n_features <= 0 || n_features > INT32_MAX) return fail(GORSE_ERR_INVALID, "n_features must be in [1, 2^31)");
+    if (n_factors < 1 || n_factors > fm::kMaxFactors) return fail(GORSE_ERR_INVALID, "n_factors must be in 1..128 (got %d)", n_factors);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(GORSE_ERR_NO_DEVICE, "no HIP device visible (libgorse_hip needs an MI355X / gfx950)");
+    if (device < 0 || device >= ndev) return fail(GORSE_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
+    GORSE_HIP_CHECK(hipSetDevice(device));
+    gorse_fm *h = new (std::nothrow) gorse_fm();
+    if (!h) return fail(GORSE_ERR_NOMEM, "out of host memory");
+    h->device = device;
+    h->nf = n_features;
+    h->d = n_factors;
+    auto init = [&]() -> int32_t {
+        GORSE_HIP_CHECK(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+        GORSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev[0], hipEventDisableTiming));
+        GORSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev[1], hipEventDisableTiming));
+        const size_t nv = (size_t)n_features * n_factors, nw = (size_t)n_features;
+        for (auto *b : {&h->V, &h->mV, &h->vV}) GORSE_TRY(b->alloc(nv));
+        for (auto *b : {&h->W, &h->mW, &h->vW}) GORSE_TRY(b->alloc(nw));
+        for (auto *b : {&h->B, &h->mB, &h->vB, &h->gB, &h->cost}) GORSE_TRY(b->alloc(4));
+        GORSE_TRY(h->tag.alloc(nw));
+        GORSE_HIP_CHECK(hipMemsetAsync(h->tag.p, 0, nw * sizeof(int64_t), h->s));
+        for (auto *b : {&h->V, &h->mV, &h->vV, &h->W, &h->mW, &h->vW, &h->B, &h->mB, &h->vB})
+            GORSE_HIP_CHECK(hipMemsetAsync(b->p, 0, b->n * sizeof(float), h->s));
+        GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+        return GORSE_OK;
+    };
+    const int32_t rc = init();
+    if (rc != GORSE_OK) {
+        gorse_fm_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_destroy(gorse_fm *h) {
+    if (!h) return GORSE_OK;
+    (void)hipSetDevice(h->device);
+    if (h->s) (void)hipStreamSynchronize(h->s);
+    for (auto e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (h->s) (void)hipStreamDestroy(h->s);
+    delete h;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_set_params(gorse_fm *h, float B, const float *W, const float *V) {
+    if (!h || !W || !V) return fail(GORSE_ERR_INVALID, "handle / W / V is NULL");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    GORSE_HIP_CHECK(hipMemcpy(h->V.p, V, (size_t)h->nf * h->d * sizeof(float), hipMemcpyHostToDevice));
+    GORSE_HIP_CHECK(hipMemcpy(h->W.p, W, (size_t)h->nf * sizeof(float), hipMemcpyHostToDevice));
+    GORSE_HIP_CHECK(hipMemcpy(h->B.p, &B, sizeof(float), hipMemcpyHostToDevice));
+    for (auto *b : {&h->mV, &h->vV, &h->mW, &h->vW, &h->mB, &h->vB})
+        GORSE_HIP_CHECK(hipMemsetAsync(b->p, 0, b->n * sizeof(float), h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    h->adam_t = 0;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_get_params(gorse_fm *h, float *B, float *W, float *V) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    if (V) GORSE_HIP_CHECK(hipMemcpy(V, h->V.p, (size_t)h->nf * h->d * sizeof(float), hipMemcpyDeviceToHost));
+    if (W) GORSE_HIP_CHECK(hipMemcpy(W, h->W.p, (size_t)h->nf * sizeof(float), hipMemcpyDeviceToHost));
+    if (B) GORSE_HIP_CHECK(hipMemcpy(B, h->B.p, sizeof(float), hipMemcpyDeviceToHost));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_set_train(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices, const float *values,
+                                      const float *target) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (n <= 0) return fail(GORSE_ERR_INVALID, "the training set is empty");
+    if (!target) return fail(GORSE_ERR_INVALID, "target is NULL");
+    GORSE_TRY(fm::check_rows(h, n, width, indices, values, true));
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    const size_t ne = (size_t)n * width;
+    h->h_idx.assign(indices, indices + ne);
+    h->h_val.assign(values, values + ne);
+    GORSE_TRY(h->idx.alloc(ne));
+    GORSE_TRY(h->val.alloc(ne));
+    GORSE_TRY(h->tgt.alloc((size_t)n));
+    GORSE_HIP_CHECK(hipMemcpy(h->idx.p, indices, ne * 4, hipMemcpyHostToDevice));
+    GORSE_HIP_CHECK(hipMemcpy(h->val.p, values, ne * 4, hipMemcpyHostToDevice));
+    GORSE_HIP_CHECK(hipMemcpy(h->tgt.p, target, (size_t)n * 4, hipMemcpyHostToDevice));
+    h->n = n;
+    h->width = width;
+    h->plan_bs = 0;  // the batches' feature order is rebuilt for the new set
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optimizer, float lr, float wd,
+                                  const volatile int32_t *cancel, float *cost_out) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
+    if (optimizer != GORSE_OPT_SGD && optimizer != GORSE_OPT_ADAM) return fail(GORSE_ERR_INVALID, "unknown optimizer %d", optimizer);
+    if (h->n <= 0) return fail(GORSE_ERR_INVALID, "no training set (gorse_fm_set_train)");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    if (h->plan_bs != batch_size) GORSE_TRY(fm::build_plan(h, batch_size));
+    GORSE_HIP_CHECK(hipMemsetAsync(h->cost.p, 0, sizeof(float), h->s));
+    const int64_t nb = ceil_div(h->n, batch_size);
+    const bool adam = optimizer == GORSE_OPT_ADAM;
+    fm::OptArgs o{};
+    float *ps[3] = {h->V.p, h->W.p, h->B.p}, *ms[3] = {h->mV.p, h->mW.p, h->mB.p}, *vs[3] = {h->vV.p, h->vW.p, h->vB.p};
+    const int64_t lens[3] = {h->nf * h->d, h->nf, 1};
+    for (int t = 0; t < 3; t++) o.p[t] = ps[t], o.m[t] = ms[t], o.v[t] = vs[t], o.len[t] = lens[t];
+    o.blocks0 = ceil_div(ceil_div(lens[0], 4), fm::kBlock);
+    o.blocks1 = ceil_div(ceil_div(lens[1], 4), fm::kBlock);
+    o.d = h->d;
+    o.tag = h->tag.p;
+    o.gV = h->gV.p, o.gW = h->gW.p, o.gB = h->gB.p;
+    o.wd = wd;
+    o.c1 = 1.0f - fm::kBeta1;
+    o.c2 = 1.0f - fm::kBeta2;
+    const unsigned opt_grid = (unsigned)(o.blocks0 + o.blocks1 + 1);
+    for (int64_t k = 0; k < nb; k++) {
+        if (k % 64 == 0 && k >= 128) {
+            // at most two groups of 64 steps in flight: wait for the end of the group before the previous one
+            GORSE_HIP_CHECK(hipEventSynchronize(h->ev[(k / 64) & 1]));
+        }
+        if (cancel && *cancel) {
+            GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+            return fail(GORSE_ERR_CANCELLED, "cancelled");
+        }
+        const int64_t r0 = k * batch_size, nr = std::min<int64_t>(h->n, r0 + batch_size) - r0;
+        const int64_t tag_hi = (h->step + 1) << 32;
+        fm::FwdArgs f{};
+        f.idx = h->idx.p, f.val = h->val.p, f.tgt = h->tgt.p;
+        f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
+        f.row0 = r0, f.nrows = nr, f.width = h->width, f.d = h->d;
+        f.inv_n = 1.0f / (float)nr;
+        f.gs = h->gs.p, f.loss = h->loss.p, f.vx = h->vx.p;
+        GORSE_TRY(fm::launch_forward<true>(h, f));
+        fm::AccArgs a{};
+        a.uniq = h->uniq.p, a.seg = h->seg.p, a.pos = h->pos.p;
+        a.slot0 = h->uoff[(size_t)k], a.nslots = h->uoff[(size_t)k + 1] - h->uoff[(size_t)k];
+        a.val = h->val.p + r0 * h->width;
+        a.V = h->V.p;
+        a.gs = h->gs.p, a.loss = h->loss.p, a.vx = h->vx.p;
+        a.nrows = nr, a.width = h->width, a.d = h->d;
+        a.tag_hi = tag_hi, a.tag = h->tag.p;
+        a.gV = h->gV.p, a.gW = h->gW.p, a.gB = h->gB.p, a.cost = h->cost.p;
+        GORSE_TRY(fm::launch_accum(h, a));
+        o.tag_hi = tag_hi;
+        if (adam) {
+            h->adam_t++;
+            o.lr = fm::adam_lr(lr, h->adam_t);
+            fm::fm_opt_kernel<true><<<dim3(opt_grid), dim3(fm::kBlock), 0, h->s>>>(o);
+        } else {
+            o.lr = lr;
+            fm::fm_opt_kernel<false><<<dim3(opt_grid), dim3(fm::kBlock), 0, h->s>>>(o);
+        }
+        GORSE_HIP_CHECK(hipGetLastError());
+        h->step++;
+        if (k % 64 == 63) GORSE_HIP_CHECK(hipEventRecord(h->ev[(k / 64) & 1], h->s));
+    }
+    float cost = 0.0f;
+    GORSE_HIP_CHECK(hipMemcpyAsync(&cost, h->cost.p, sizeof(float), hipMemcpyDeviceToHost, h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    if (cost_out) *cost_out = cost;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices, const float *values,
+                                    float *logits_out) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_TRY(fm::check_rows(h, n, width, indices, values, false));
+    if (n == 0) return GORSE_OK;
+    if (!logits_out) return fail(GORSE_ERR_INVALID, "logits_out is NULL");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ne = (size_t)n * width;
+    GORSE_TRY(h->p_idx.ensure(ne));
+    GORSE_TRY(h->p_val.ensure(ne));
+    GORSE_TRY(h->p_out.ensure((size_t)n));
+    GORSE_HIP_CHECK(hipMemcpyAsync(h->p_idx.p, indices, ne * 4, hipMemcpyHostToDevice, h->s));
+    GORSE_HIP_CHECK(hipMemcpyAsync(h->p_val.p, values, ne * 4, hipMemcpyHostToDevice, h->s));
+    fm::FwdArgs f{};
+    f.idx = h->p_idx.p, f.val = h->p_val.p;
+    f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
+    f.row0 = 0, f.nrows = n, f.width = width, f.d = h->d;
+    f.out = h->p_out.p;
+    GORSE_TRY(fm::launch_forward<false>(h, f));
+    GORSE_HIP_CHECK(hipMemcpyAsync(logits_out, h->p_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    return GORSE_OK;
+}

@@ -1,0 +1,144 @@
+"""Python face of the host mirror of model/ctr (gorse_amd/host/gorse_ctr.*, in libgorse_host.so): the factorization
+machine's Fit loop and EvaluateClassification with their Go names, like cf.py for model/cf.  The model's numerics run on the
+MI355X through the gorse_fm_* entry points; nothing here computes them on the CPU."""
+import ctypes as C
+
+import numpy as np
+
+from . import cf
+
+_f32p, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+SGD, Adam = 0, 1
+_configured = False
+
+
+def host():
+    global _configured
+    H = cf.host()
+    if not _configured:
+        H.gh_ctr_metric.restype = C.c_float
+        H.gh_ctr_metric.argtypes = [C.c_int32, _f32p, C.c_int32, _f32p, C.c_int32]
+        H.gh_ctr_dataset_new.restype = C.c_void_p
+        H.gh_ctr_dataset_new.argtypes = [C.c_int64]
+        H.gh_ctr_dataset_free.argtypes = [C.c_void_p]
+        H.gh_ctr_dataset_add.argtypes = [C.c_void_p, C.c_int64, _i64p, _i32p, _f32p, _f32p]
+        H.gh_fm_new.restype = C.c_void_p
+        H.gh_fm_new.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64]
+        H.gh_fm_free.argtypes = [C.c_void_p]
+        H.gh_fm_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _i32p, _f32p]
+        H.gh_fm_evaluate.argtypes = [C.c_void_p, C.c_void_p, _f32p]
+        H.gh_fm_log.argtypes = [C.c_void_p, _i32p, _f32p, _f32p, C.c_int32]
+        H.gh_fm_params.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
+        _configured = True
+    return H
+
+
+def _f32(a):
+    a = np.ascontiguousarray(a, np.float32)
+    return a if a.size else np.zeros(1, np.float32)
+
+
+def _metric(i, pos, neg):
+    p, n = _f32(pos), _f32(neg)
+    return float(host().gh_ctr_metric(i, p.ctypes.data_as(_f32p), len(pos), n.ctypes.data_as(_f32p), len(neg)))
+
+
+def Precision(pos, neg):
+    return _metric(0, pos, neg)
+
+
+def Recall(pos, neg):
+    return _metric(1, pos, neg)
+
+
+def Accuracy(pos, neg):
+    return _metric(2, pos, neg)
+
+
+def AUC(pos, neg):
+    return _metric(3, pos, neg)
+
+
+class Score:
+    def __init__(self, v):
+        self.Precision, self.Recall, self.Accuracy, self.AUC = (float(x) for x in v)
+
+    def __eq__(self, o):
+        return (self.Precision, self.Recall, self.Accuracy, self.AUC) == (o.Precision, o.Recall, o.Accuracy, o.AUC)
+
+    def __repr__(self):
+        return "Score(Precision=%g, Recall=%g, Accuracy=%g, AUC=%g)" % (self.Precision, self.Recall, self.Accuracy, self.AUC)
+
+
+class Dataset:
+    """dataset.CTRSplit: rows of (feature indices, values, target +-1) over n_features features."""
+
+    def __init__(self, n_features, rows=None):
+        self.n_features = int(n_features)
+        self.p = C.c_void_p(host().gh_ctr_dataset_new(self.n_features))
+        self.n = 0
+        if rows is not None:
+            self.add_rows(*rows)
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            host().gh_ctr_dataset_free(self.p)
+            self.p = None
+
+    def add_rows(self, indptr, indices, values, target):
+        ip = np.ascontiguousarray(indptr, np.int64)
+        ii = np.ascontiguousarray(indices, np.int32)
+        vv = np.ascontiguousarray(values, np.float32)
+        tt = np.ascontiguousarray(target, np.float32)
+        if ii.size == 0:
+            ii, vv = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        host().gh_ctr_dataset_add(self.p, tt.size, ip.ctypes.data_as(_i64p), ii.ctypes.data_as(_i32p),
+                                  vv.ctypes.data_as(_f32p), tt.ctypes.data_as(_f32p))
+        self.n += tt.size
+
+    def Count(self):
+        return self.n
+
+
+class FM:
+    """ctr.AFM without item embeddings (model/ctr/fm.go), trained and scored on the device."""
+
+    def __init__(self, nFactors=8, nEpochs=10, batchSize=1024, lr=0.01, reg=0.0, optimizer=Adam, seed=0):
+        self.d = int(nFactors)
+        self.p = C.c_void_p(host().gh_fm_new(self.d, nEpochs, batchSize, lr, reg, optimizer, seed))
+        self.nf = 0
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            host().gh_fm_free(self.p)
+            self.p = None
+
+    def Fit(self, train, test, Verbose=10, Patience=0, cancel=None):
+        s = np.zeros(4, np.float32)
+        cp = cancel.ctypes.data_as(_i32p) if cancel is not None else None
+        rc = host().gh_fm_fit(self.p, train.p, test.p, Verbose, Patience, cp, s.ctypes.data_as(_f32p))
+        if rc != 0:
+            raise cf.HostError(rc)
+        self.nf = train.n_features
+        return Score(s)
+
+    def Evaluate(self, test):
+        s = np.zeros(4, np.float32)
+        rc = host().gh_fm_evaluate(self.p, test.p, s.ctypes.data_as(_f32p))
+        if rc != 0:
+            raise cf.HostError(rc)
+        return Score(s)
+
+    def log(self):
+        """[(epoch, cost, AUC)] of every evaluation of the last Fit"""
+        cap = 4096
+        e, c, a = np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        n = host().gh_fm_log(self.p, e.ctypes.data_as(_i32p), c.ctypes.data_as(_f32p), a.ctypes.data_as(_f32p), cap)
+        return [(int(e[i]), float(c[i]), float(a[i])) for i in range(min(n, cap))]
+
+    def params(self):
+        B = np.zeros(1, np.float32)
+        W = np.zeros(self.nf, np.float32)
+        V = np.zeros((self.nf, self.d), np.float32)
+        host().gh_fm_params(self.p, B.ctypes.data_as(_f32p), W.ctypes.data_as(_f32p), V.ctypes.data_as(_f32p))
+        return B[0], W, V

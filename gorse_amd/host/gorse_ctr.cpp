@@ -1,0 +1,168 @@
+// gorse_ctr.cpp -- see gorse_ctr.hpp.
+#include "gorse_ctr.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+#include "gorse_cf.hpp"
+
+namespace gorse {
+namespace ctr {
+
+int Dataset::MaxLen() const {
+    int m = 0;
+    for (size_t i = 0; i + 1 < indptr.size(); i++) m = std::max(m, (int)(indptr[i + 1] - indptr[i]));
+    return m;
+}
+
+void Dataset::Add(const int32_t *idx, const float *val, int len, float t) {
+    indices.insert(indices.end(), idx, idx + len);
+    values.insert(values.end(), val, val + len);
+    indptr.push_back((int64_t)indices.size());
+    target.push_back(t);
+}
+
+float Precision(const std::vector<float> &pos, const std::vector<float> &neg) {
+    float tp = 0, fp = 0;
+    for (float p : pos)
+        if (p > 0) tp++;
+    for (float p : neg)
+        if (p > 0) fp++;
+    if (tp + fp == 0) return 0;
+    return tp / (tp + fp);
+}
+
+float Recall(const std::vector<float> &pos, const std::vector<float> &) {
+    float tp = 0, fn = 0;
+    for (float p : pos) {
+        if (p > 0)
+            tp++;
+        else
+            fn++;
+    }
+    if (tp + fn == 0) return 0;
+    return tp / (tp + fn);
+}
+
+float Accuracy(const std::vector<float> &pos, const std::vector<float> &neg) {
+    float correct = 0;
+    for (float p : pos)
+        if (p > 0) correct++;
+    for (float p : neg)
+        if (p < 0) correct++;
+    if (pos.size() + neg.size() == 0) return 0;
+    return correct / (float)(pos.size() + neg.size());
+}
+
+float AUC(std::vector<float> pos, std::vector<float> neg) {
+    std::sort(pos.begin(), pos.end());
+    std::sort(neg.begin(), neg.end());
+    float sum = 0;
+    size_t nPos = 0;
+    for (float p : pos) {
+        while (nPos < neg.size() && neg[nPos] < p) nPos++;
+        sum += (float)nPos;
+    }
+    if (pos.size() * neg.size() == 0) return 0;
+    return sum / (float)(pos.size() * neg.size());
+}
+
+FM::~FM() {
+    if (h_) gorse_fm_destroy(h_);
+}
+
+// convertToTensors (fm.go:527-577): rows padded with index 0 / value 0 to the wider of the training width and the longest row
+static void pad_rows(const Dataset &ds, const std::vector<int64_t> &rows, int width, std::vector<int32_t> &idx,
+                     std::vector<float> &val) {
+    idx.assign(rows.size() * (size_t)width, 0);
+    val.assign(rows.size() * (size_t)width, 0.0f);
+    for (size_t r = 0; r < rows.size(); r++) {
+        const int64_t b = ds.indptr[(size_t)rows[r]], e = ds.indptr[(size_t)rows[r] + 1];
+        for (int64_t j = b; j < e; j++) {
+            idx[r * width + (size_t)(j - b)] = ds.indices[(size_t)j];
+            val[r * width + (size_t)(j - b)] = ds.values[(size_t)j];
+        }
+    }
+}
+
+std::vector<float> FM::BatchInternalPredict(const Dataset &ds, const std::vector<int64_t> &rows) {
+    std::vector<float> out(rows.size());
+    if (rows.empty()) return out;
+    if (!h_) throw std::invalid_argument("model is not fitted");
+    int width = std::max(1, numDimension_);
+    for (int64_t r : rows) width = std::max(width, (int)(ds.indptr[(size_t)r + 1] - ds.indptr[(size_t)r]));
+    std::vector<int32_t> idx;
+    std::vector<float> val;
+    pad_rows(ds, rows, width, idx, val);
+    check(gorse_fm_predict(h_, (int64_t)rows.size(), width, idx.data(), val.data(), out.data()));
+    return out;
+}
+
+Score EvaluateClassification(FM &m, const Dataset &test) {
+    std::vector<int64_t> pos, neg;
+    for (int64_t i = 0; i < test.Count(); i++) (test.target[(size_t)i] > 0 ? pos : neg).push_back(i);
+    const std::vector<float> pp = m.BatchInternalPredict(test, pos), np_ = m.BatchInternalPredict(test, neg);
+    if (test.Count() == 0) return Score{};
+    Score s;
+    s.Precision = Precision(pp, np_);
+    s.Recall = Recall(pp, np_);
+    s.Accuracy = Accuracy(pp, np_);
+    s.AUC = AUC(pp, np_);
+    return s;
+}
+
+Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
+    // Init (fm.go:247-270): B = 0, W and V from N(0, 0.01) (layers.go:82-87), W drawn first
+    nf_ = train.n_features;
+    numDimension_ = train.MaxLen();
+    if (h_) gorse_fm_destroy(h_), h_ = nullptr;
+    check(gorse_fm_create(&h_, device_, nf_, nFactors_));
+    util::RandomGenerator rng(seed_);
+    B = 0;
+    rng.NormalMatrix(nf_, 1, 0, 0.01f, W);
+    rng.NormalMatrix(nf_, nFactors_, 0, 0.01f, V);
+    check(gorse_fm_set_params(h_, B, W.data(), V.data()));
+    log.clear();
+
+    Score score = EvaluateClassification(*this, test);
+    std::vector<std::pair<int, float>> scores{{0, score.AUC}};
+    log.push_back({0, 0.0f, score});
+
+    const int width = std::max(1, numDimension_);
+    std::vector<int64_t> all((size_t)train.Count());
+    for (int64_t i = 0; i < train.Count(); i++) all[(size_t)i] = i;
+    std::vector<int32_t> idx;
+    std::vector<float> val;
+    pad_rows(train, all, width, idx, val);
+    check(gorse_fm_set_train(h_, train.Count(), width, idx.data(), val.data(), train.target.data()));
+
+    const int32_t opt = optimizer_ == 0 ? GORSE_OPT_SGD : GORSE_OPT_ADAM;
+    for (int epoch = 1; epoch <= nEpochs_; epoch++) {
+        float cost = 0;
+        const int32_t rc = (cfg.cancel && *cfg.cancel) ? GORSE_ERR_CANCELLED
+                                                       : gorse_fm_epoch(h_, batchSize_, opt, lr_, reg_, cfg.cancel, &cost);
+        if (rc == GORSE_ERR_CANCELLED) {  // "fit AFM canceled": Score{}, the tensors keep the steps taken
+            check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
+            return Score{};
+        }
+        check(rc);
+        if (epoch % cfg.Verbose == 0 || epoch == nEpochs_) {
+            score = EvaluateClassification(*this, test);
+            scores.push_back({epoch, score.AUC});
+            log.push_back({epoch, cost, score});
+            if (std::isnan(cost) || std::isnan(score.GetValue())) break;  // model diverged
+            if (cfg.Patience > 0 && epoch > cfg.Patience) {
+                // lo.MaxBy: the first maximum
+                auto best = scores[0];
+                for (const auto &s : scores)
+                    if (s.second > best.second) best = s;
+                if (best.first <= epoch - cfg.Patience) break;  // early stopping
+            }
+        }
+    }
+    check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
+    return score;
+}
+
+}  // namespace ctr
+}  // namespace gorse

@@ -1,0 +1,78 @@
+// gorse_ctr.hpp -- host mirror of the reference's model/ctr factorization machine (ctr.AFM without the item-embedding branch,
+// model/ctr/fm.go) and of its classification metrics (model/ctr/evaluator.go).  The numerics run on the device through the
+// gorse_fm_* entry points of the C ABI; this file holds AFM.Fit's loop (evaluation schedule, NaN stop, patience, cancel) and
+// EvaluateClassification as written.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "../../include/gorse_hip.h"
+
+namespace gorse {
+namespace ctr {
+
+struct Score {  // model/ctr/model.go Score (the classification fields)
+    float Precision = 0, Recall = 0, Accuracy = 0, AUC = 0;
+    float GetValue() const { return AUC; }
+};
+
+// dataset.CTRSplit flattened: row i = indices / values [indptr[i], indptr[i+1]), target +-1
+struct Dataset {
+    int64_t n_features = 0;
+    std::vector<int64_t> indptr{0};
+    std::vector<int32_t> indices;
+    std::vector<float> values;
+    std::vector<float> target;
+    int64_t Count() const { return (int64_t)target.size(); }
+    int MaxLen() const;
+    void Add(const int32_t *idx, const float *val, int len, float t);
+};
+
+// evaluator.go:85-153, all fp32 (AUC sorts its arguments)
+float Precision(const std::vector<float> &pos, const std::vector<float> &neg);
+float Recall(const std::vector<float> &pos, const std::vector<float> &neg);
+float Accuracy(const std::vector<float> &pos, const std::vector<float> &neg);
+float AUC(std::vector<float> pos, std::vector<float> neg);
+
+struct FitConfig {
+    int Verbose = 10, Patience = 0;
+    const volatile int32_t *cancel = nullptr;  // ctx.Err() != nil
+};
+
+struct EvalRecord {
+    int epoch;
+    float cost;  // 0 at epoch 0
+    Score score;
+};
+
+class FM {
+   public:
+    FM(int nFactors, int nEpochs, int batchSize, float lr, float reg, int optimizer, int64_t seed, int device = 0)
+        : nFactors_(nFactors), nEpochs_(nEpochs), batchSize_(batchSize), lr_(lr), reg_(reg), optimizer_(optimizer), seed_(seed),
+          device_(device) {}
+    ~FM();
+    FM(const FM &) = delete;
+    FM &operator=(const FM &) = delete;
+    // AFM.Fit (fm.go:307-417) for a training set without item embeddings
+    Score Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg);
+    // BatchInternalPredict (fm.go:156-178) of rows [0, ds.Count()) that satisfy keep (or all rows)
+    std::vector<float> BatchInternalPredict(const Dataset &ds, const std::vector<int64_t> &rows);
+    float B = 0;
+    std::vector<float> W, V;          // the parameters after Fit (copied back, as into the nn tensors)
+    std::vector<EvalRecord> log;      // every evaluation of the last Fit, epoch 0 first
+
+   private:
+    int nFactors_, nEpochs_, batchSize_;
+    float lr_, reg_;
+    int optimizer_;
+    int64_t seed_;
+    int device_;
+    int numDimension_ = 0;
+    int64_t nf_ = 0;
+    gorse_fm *h_ = nullptr;
+};
+
+Score EvaluateClassification(FM &m, const Dataset &test);  // evaluator.go:46-83
+
+}  // namespace ctr
+}  // namespace gorse

@@ -5,6 +5,7 @@
 #include <sstream>
 
 #include "gorse_cf.hpp"
+#include "gorse_ctr.hpp"
 #include "gorse_vectors.hpp"
 #include "../csrc/rank_keys.hpp"
 #include "../csrc/sparse_host.hpp"
@@ -953,5 +954,62 @@ uint32_t gh_test_hnsw_levels(int64_t n, int32_t *level) {
     uint32_t bits;
     memcpy(&bits, &f, 4);
     return bits;
+}
+// ---- model/ctr: the factorization machine's Fit loop and EvaluateClassification ---------------------------------------
+// metric: 0 Precision, 1 Recall, 2 Accuracy, 3 AUC (evaluator.go:85-153)
+float gh_ctr_metric(int32_t id, const float *pos, int32_t npos, const float *neg, int32_t nneg) {
+    const std::vector<float> p(pos, pos + npos), n(neg, neg + nneg);
+    switch (id) {
+        case 0: return ctr::Precision(p, n);
+        case 1: return ctr::Recall(p, n);
+        case 2: return ctr::Accuracy(p, n);
+        default: return ctr::AUC(p, n);
+    }
+}
+void *gh_ctr_dataset_new(int64_t n_features) {
+    auto *d = new ctr::Dataset();
+    d->n_features = n_features;
+    return d;
+}
+void gh_ctr_dataset_free(void *d) { delete (ctr::Dataset *)d; }
+// n rows at once: row i = idx / val [indptr[i], indptr[i+1])
+void gh_ctr_dataset_add(void *d, int64_t n, const int64_t *indptr, const int32_t *idx, const float *val, const float *target) {
+    for (int64_t i = 0; i < n; i++)
+        ((ctr::Dataset *)d)->Add(idx + indptr[i], val + indptr[i], (int)(indptr[i + 1] - indptr[i]), target[i]);
+}
+// optimizer: 0 SGD, 1 Adam (model.SGD / model.Adam)
+void *gh_fm_new(int32_t n_factors, int32_t n_epochs, int32_t batch_size, float lr, float reg, int32_t optimizer, int64_t seed) {
+    return new ctr::FM(n_factors, n_epochs, batch_size, lr, reg, optimizer, seed);
+}
+void gh_fm_free(void *m) { delete (ctr::FM *)m; }
+// score4 = Precision, Recall, Accuracy, AUC of the returned Score
+int32_t gh_fm_fit(void *m, void *train, void *test, int32_t verbose, int32_t patience, const int32_t *cancel, float *score4) {
+    return guard([&] {
+        ctr::FitConfig cfg;
+        cfg.Verbose = verbose;
+        cfg.Patience = patience;
+        cfg.cancel = cancel;
+        const ctr::Score s = ((ctr::FM *)m)->Fit(*(ctr::Dataset *)train, *(ctr::Dataset *)test, cfg);
+        score4[0] = s.Precision, score4[1] = s.Recall, score4[2] = s.Accuracy, score4[3] = s.AUC;
+    });
+}
+int32_t gh_fm_evaluate(void *m, void *test, float *score4) {
+    return guard([&] {
+        const ctr::Score s = ctr::EvaluateClassification(*(ctr::FM *)m, *(ctr::Dataset *)test);
+        score4[0] = s.Precision, score4[1] = s.Recall, score4[2] = s.Accuracy, score4[3] = s.AUC;
+    });
+}
+// the evaluations of the last Fit: epoch, cost, AUC; returns how many there are (at most cap are written)
+int32_t gh_fm_log(void *m, int32_t *epochs, float *costs, float *aucs, int32_t cap) {
+    const auto &lg = ((ctr::FM *)m)->log;
+    for (int32_t i = 0; i < cap && i < (int32_t)lg.size(); i++) epochs[i] = lg[i].epoch, costs[i] = lg[i].cost, aucs[i] = lg[i].score.AUC;
+    return (int32_t)lg.size();
+}
+// B, W (n_features), V (n_features x d) after Fit
+void gh_fm_params(void *m, float *B, float *W, float *V) {
+    const auto *f = (ctr::FM *)m;
+    *B = f->B;
+    std::copy(f->W.begin(), f->W.end(), W);
+    std::copy(f->V.begin(), f->V.end(), V);
 }
 }  // extern "C"

@@ -387,6 +387,35 @@ int32_t gorse_hip_sgemm_device(int32_t device, int32_t transA, int32_t transB, i
                                const float *a /*device*/, int32_t lda, const float *b /*device*/, int32_t ldb, float *c /*device*/,
                                int32_t ldc);
 
+
+/* ---- ctr.AFM without the item-embedding branch: the factorization machine (model/ctr/fm.go:111-126) -------------------
+ * n_features = dataset index length, d = nFactors in 1..128.  Parameters: bias B, linear W (n_features), pairwise V
+ * (n_features x d, row-major), initialised by the caller (fm.go:247-270: the Go side draws them) and read back into the nn
+ * tensors.  Samples are n x width matrices of feature indices and (already scaled) values, positions past a row's length
+ * hold index 0 with value 0 (convertToTensors, fm.go:527-577); an index outside [0, n_features) is GORSE_ERR_RANGE. */
+typedef struct gorse_fm gorse_fm;
+#define GORSE_OPT_SGD 0  /* nn.SGD  (common/nn/optimizers.go:70-84)   */
+#define GORSE_OPT_ADAM 1 /* nn.Adam (common/nn/optimizers.go:118-156) */
+int32_t gorse_fm_create(gorse_fm **h, int32_t device, int64_t n_features, int32_t n_factors);
+int32_t gorse_fm_destroy(gorse_fm *h);
+/* set the parameters and reset the optimizer state (moments and Adam's t): what a new Fit does */
+int32_t gorse_fm_set_params(gorse_fm *h, float B, const float *W /*host*/, const float *V /*host*/);
+int32_t gorse_fm_get_params(gorse_fm *h, float *B /*host or NULL*/, float *W /*host or NULL*/, float *V /*host or NULL*/);
+/* the training set (targets +-1); kept on the device until the next call.  n x width must not exceed 2^31 - 1
+ * (GORSE_ERR_INVALID): the per-batch position lists hold int32.  For every batch size an epoch is called with, the first such
+ * epoch sorts the batches' (feature, position) pairs once on the host; later epochs reuse the order. */
+int32_t gorse_fm_set_train(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices /*host*/, const float *values /*host*/,
+                           const float *target /*host*/);
+/* one epoch of AFM.Fit's inner loop (fm.go:362-378): contiguous batches of batch_size rows in dataset order (the last one
+ * partial), BCEWithLogits averaged over each batch, one optimizer step per batch with weight decay wd.  cost_out (host or
+ * NULL) = the fp32 sum of the batch means.  The cancel flag is read before every batch; at most 128 steps are in flight
+ * when it is seen, and the call then returns GORSE_ERR_CANCELLED with the steps run so far applied. */
+int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optimizer, float lr, float wd,
+                       const volatile int32_t *cancel /*host or NULL*/, float *cost_out /*host or NULL*/);
+/* BatchInternalPredict (fm.go:156-178): logits of n rows; width may differ from the training width */
+int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices /*host*/, const float *values /*host*/,
+                         float *logits_out /*host*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,180 @@
+//go:build cgo && hip && !xla
+
+package ctr
+
+// #include <stdlib.h>
+// #include "gorse_hip.h"
+import "C"
+
+import (
+	"context"
+	"fmt"
+	"sync/atomic"
+	"time"
+	"unsafe"
+
+	"github.com/chewxy/math32"
+	"github.com/gorse-io/gorse/common/log"
+	"github.com/gorse-io/gorse/common/monitor"
+	"github.com/gorse-io/gorse/dataset"
+	"github.com/gorse-io/gorse/model"
+	"github.com/samber/lo"
+	"go.uber.org/zap"
+)
+
+// hipFM keeps the factorization machine resident on one MI355X between Fit and the BatchInternalPredict calls that follow.
+type hipFM struct {
+	h *C.gorse_fm
+}
+
+func (m *hipFM) close() {
+	if m != nil && m.h != nil {
+		C.gorse_fm_destroy(m.h)
+		m.h = nil
+	}
+}
+
+// flatRows pads x to width columns (index 0 / value 0), the layout of convertToTensors (fm.go:527-577).
+func flatRows(x []lo.Tuple2[[]int32, []float32], width int) ([]int32, []float32) {
+	idx := make([]int32, len(x)*width)
+	val := make([]float32, len(x)*width)
+	for i := range x {
+		copy(idx[i*width:], x[i].A)
+		copy(val[i*width:], x[i].B)
+	}
+	return idx, val
+}
+
+// fitHIP is AFM.Fit (fm.go:307-417) for a model without item embeddings: one gorse_fm_epoch call per epoch; the evaluation
+// schedule, the NaN stop and early stopping stay here as written.  It is called right after Init (fm.go:315-322), before the
+// reference's epoch-0 evaluation, and builds the scaled training rows itself (fm.go:337-352).  ok = false sends the caller back
+// to the CPU code (a model with item embeddings, no device, or a training set the device refuses) with no handle left resident.
+func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, config *FitConfig) (score Score, ok bool) {
+	fm.hip.close() // the previous Fit's device model must not score this one's epoch 0
+	fm.hip = nil
+	if len(fm.embeddingDim) != 0 || trainSet.Count() == 0 {
+		return Score{}, false // the attention branch keeps the reference's CPU code
+	}
+	x := make([]lo.Tuple2[[]int32, []float32], trainSet.Count())
+	y := make([]float32, trainSet.Count())
+	for i := range x {
+		indices, values, _, target := trainSet.Get(i)
+		scaled := make([]float32, len(values))
+		copy(scaled, values)
+		for j, idx := range indices {
+			if scaler, ok := fm.Scalers[idx]; ok {
+				scaled[j] = scaler.Transform(values[j])
+			}
+		}
+		x[i], y[i] = lo.Tuple2[[]int32, []float32]{A: indices, B: scaled}, target
+	}
+	hm := &hipFM{}
+	if rc := C.gorse_fm_create(&hm.h, 0, C.int64_t(fm.numFeatures), C.int32_t(fm.nFactors)); rc != 0 {
+		log.Logger().Warn("fit AFM: no device, CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		return Score{}, false
+	}
+	// Init drew B, W and V in Go (fm.go:247-270); the nn tensors hold them
+	width := max(fm.numDimension, 1)
+	idx, val := flatRows(x, width)
+	if rc := C.gorse_fm_set_params(hm.h, C.float(fm.B.Data()[0]), (*C.float)(&fm.W.Data()[0]), (*C.float)(&fm.V.Data()[0])); rc != 0 {
+		log.Logger().Warn("fit AFM: gorse_fm_set_params, CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		hm.close()
+		return Score{}, false
+	}
+	if rc := C.gorse_fm_set_train(hm.h, C.int64_t(len(y)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		(*C.float)(&y[0])); rc != 0 { // e.g. more than 2^31 - 1 padded positions (GORSE_ERR_INVALID)
+		log.Logger().Warn("fit AFM: gorse_fm_set_train, CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		hm.close()
+		return Score{}, false
+	}
+	fm.hip = hm
+	opt := C.int32_t(C.GORSE_OPT_ADAM)
+	if fm.optimizer == model.SGD {
+		opt = C.GORSE_OPT_SGD
+	}
+	cancel := (*C.int32_t)(C.malloc(4)) // C memory: the library reads the flag during the call
+	defer C.free(unsafe.Pointer(cancel))
+	*cancel = 0
+	stop := context.AfterFunc(ctx, func() { atomic.StoreInt32((*int32)(unsafe.Pointer(cancel)), 1) })
+	defer stop()
+
+	score = EvaluateClassification(fm, testSet, config.Jobs)
+	scores := []lo.Tuple2[int, float32]{{A: 0, B: score.AUC}}
+	_, span := monitor.Start(ctx, "FM.Fit", fm.nEpochs)
+	defer span.End()
+	for epoch := 1; epoch <= fm.nEpochs; epoch++ {
+		fitStart := time.Now()
+		var cost C.float
+		rc := C.gorse_fm_epoch(hm.h, C.int32_t(fm.batchSize), opt, C.float(fm.lr), C.float(fm.reg), cancel, &cost)
+		if rc == C.GORSE_ERR_CANCELLED {
+			log.Logger().Info("fit AFM canceled", zap.Error(ctx.Err()))
+			fm.pullParams()
+			return Score{}, true
+		} else if rc != 0 {
+			// a device failure mid-Fit: keep the steps taken in the nn tensors, drop the handle (later scoring runs on the CPU)
+			log.Logger().Error("fit AFM", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+			fm.pullParams()
+			fm.hip.close()
+			fm.hip = nil
+			return Score{}, true
+		}
+		fitTime := time.Since(fitStart)
+		if epoch%config.Verbose == 0 || epoch == fm.nEpochs {
+			evalStart := time.Now()
+			score = EvaluateClassification(fm, testSet, config.Jobs) // BatchInternalPredict -> gorse_fm_predict
+			scores = append(scores, lo.Tuple2[int, float32]{A: epoch, B: score.AUC})
+			log.Logger().Info(fmt.Sprintf("fit AFM %v/%v", epoch, fm.nEpochs), append([]zap.Field{
+				zap.String("fit_time", fitTime.String()),
+				zap.String("eval_time", time.Since(evalStart).String()),
+				zap.Float32("loss", float32(cost)),
+			}, score.ZapFields()...)...)
+			if math32.IsNaN(float32(cost)) || math32.IsNaN(score.GetValue()) {
+				log.Logger().Warn("model diverged", zap.Float32("lr", fm.lr))
+				break
+			}
+			if config.Patience > 0 && epoch > config.Patience {
+				epochScore := lo.MaxBy(scores, func(a, b lo.Tuple2[int, float32]) bool { return a.B > b.B })
+				if epochScore.A <= epoch-config.Patience {
+					log.Logger().Info("early stopping", zap.Int("best_epoch", epochScore.A),
+						zap.Float32("best_auc", epochScore.B), zap.Int("patience", config.Patience))
+					break
+				}
+			}
+		}
+		span.Add(1)
+	}
+	fm.pullParams()
+	return score, true
+}
+
+// pullParams copies the device's parameters back into the nn tensors; nn.Save (Marshal) then writes them as today.
+func (fm *AFM) pullParams() {
+	var b C.float
+	if rc := C.gorse_fm_get_params(fm.hip.h, &b, (*C.float)(&fm.W.Data()[0]), (*C.float)(&fm.V.Data()[0])); rc != 0 {
+		log.Logger().Error("fit AFM: gorse_fm_get_params", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		return
+	}
+	fm.B.Data()[0] = float32(b)
+}
+
+// batchPredictHIP is BatchInternalPredict (fm.go:156-178) on the device for already scaled rows; ok = false when the model
+// is not resident (loaded by Unmarshal without a Fit in this process, or with item embeddings).
+func (fm *AFM) batchPredictHIP(x []lo.Tuple2[[]int32, []float32]) ([]float32, bool) {
+	if fm.hip == nil || fm.hip.h == nil || len(fm.embeddingDim) != 0 {
+		return nil, false
+	}
+	out := make([]float32, len(x))
+	if len(x) == 0 {
+		return out, true
+	}
+	width := max(fm.numDimension, 1)
+	for i := range x {
+		width = max(width, len(x[i].A))
+	}
+	idx, val := flatRows(x, width)
+	if rc := C.gorse_fm_predict(fm.hip.h, C.int64_t(len(x)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		(*C.float)(&out[0])); rc != 0 {
+		return nil, false
+	}
+	return out, true
+}
