@@ -156,6 +156,10 @@ SIGNATURES = {
     "gorse_hip_test_set_sgemm_valu": (None, [C.c_int32]),
     "gorse_hip_test_sgemm_last_ms": (C.c_double, []),
     "gorse_hip_test_set_bpr_cold_window": (None, [C.c_int64]),
+    "gorse_hip_test_set_bpr_replica_unit": (None, [C.c_double]),
+    "gorse_hip_test_set_bpr_fold_period": (None, [C.c_int32]),
+    "gorse_hip_test_bpr_fold_stats": (C.c_int32, [_vp, _vp]),
+    "gorse_hip_test_bpr_hot_state": (C.c_int32, [_vp, _vp, _vp, _vp]),
 }
 
 

@@ -563,59 +563,148 @@ __device__ __forceinline__ void update_elem(float *pu, float *qi, float *qj, int
 // waits in it (measured: positive-item atomics redirected away from the rows being read = 2.0x, spread
 // over 8 rows each = 2.7x on S-ml1m; profiles/r01_b_probe_rep.txt).  So the positive-item update of a HOT
 // item (share of the training feedback >= 1/8192, chosen at create time) -- and, in the user-run schedule, the update of a
-// hot item drawn as the NEGATIVE -- lands in one of kHotReplicas
-// private rows picked by the group id, and FOLDER workgroups of the same launch keep draining the
-// replicas into the real rows with one combined atomic per element and pass.  Q stays the only source of
-// truth for every reader; a hot row's update becomes visible one folder pass (tens of microseconds) late,
-// the same order as the latency of the atomics themselves.  A fold kernel after the launch leaves every
-// replica zero, so nothing outside bpr.hip ever sees them.
+// hot item drawn as the NEGATIVE -- lands in one of the item's R_s private rows picked by the group id (R_s = 1 .. kHotReplicas by the
+// item's expected update rate, gorse_mf_create / hot_rows.hpp), and FOLDER workgroups of the same launch drain the replicas into the
+// real rows with one combined atomic per element and pass, one pass per fold period of the device's constant-rate clock.  Q stays the
+// only source of truth for every reader; a hot row's update becomes visible one folder pass (a fold period) late, the same order as the
+// latency of the atomics themselves.  Once every worker workgroup has finished, the folders make a last pass: the launch leaves every
+// replica zero and Q complete, so nothing outside bpr.hip ever sees them.
 constexpr int kHotReplicas = GORSE_HOT_REPLICAS;
 constexpr int kFolderBlocks = 32;
+// Wall-clock ticks (100 MHz) from the start of one folder pass to the next: how late a hot row's update reaches Q.  Swept on C2
+// (profiles/r07_hr_sweep_replica_unit.txt, replica unit 0.001): 8 / 16 / 32 us -> 0.545 / 0.544 / 0.538 ms per epoch at nFactors 64,
+// 0.295 / 0.293 ms at 16 -- where 32 us DIVERGED (non-finite factors within 23 epochs, three handles of three): the hottest item takes
+// ~1.5 % of the updates, and at the small widths' sample rate a 32 us window holds ~1800 of them computed from one stale row.  8 us
+// keeps a factor of four from that; it costs nothing measurable at nFactors 64.
+constexpr uint32_t kDefaultFoldPeriod = 800;
+uint32_t g_fold_period = kDefaultFoldPeriod;  // gorse_hip_test_set_bpr_fold_period
+// folders that have waited this long (10 s) for the workers stop waiting (a launch of the largest chunk takes ~0.13 s): a last pass
+// while workers still run leaves some updates in the replicas, where the next launch's folders find them -- never a hung device
+constexpr uint64_t kFolderTimeout = 1000000000ull;
 
 struct HotRows {
-    const int32_t *slot;   // I entries: replica slot of an item, or -1
+    const int32_t *slot;   // I entries: class of an item -- hot_code(first replica row, log2 R_s) of a HOT item, -1 warm, -2 cold
     const int32_t *items;  // n_hot entries: item of a slot
-    float *rep;            // n_hot x kHotReplicas x d, all zero outside an update launch
-    int32_t *done;         // worker workgroups that have finished, counted in kDoneStripes words (zeroed before the launch)
+    const int32_t *meta;   // n_hot entries: hot_code of a slot
+    float *rep;            // replica rows of d floats, all zero outside an update launch
+    int32_t *done;         // two sets of arrival stripes (worker workgroups that have finished) + the folders' pass count
     int n_hot;
-    int64_t stride_s, stride_r;  // replica r of slot s starts at rep + s * stride_s + r * stride_r
+    int d;
+    int set;               // the set of stripes this launch counts in (launch parity: the launch zeroes the other one for the next)
+    uint32_t period;       // wall-clock ticks between two folder passes
 #ifdef GORSE_PROBE
     float *warm_scratch = nullptr;  // timing probe (variant bit 23): the atomics of the items WITHOUT replicas land here instead of on Q (results garbage)
 #endif
 };
 
+// the replica row that group `group` adds a hot item's update to (code: the item's hot_slot word)
+__device__ __forceinline__ float *hot_row(const HotRows &hot, int32_t code, int64_t group) {
+    return hot.rep + (hot_base(code) + (group & ((1 << hot_lg(code)) - 1))) * hot.d;
+}
+
 // The arrival counter of the worker workgroups, in kDoneStripes words 256 bytes apart: one 64-byte line serves 88 M atomics/s
 // (scripts/probe_atomics4.hip), and the per-sample kernel's 4096 workgroups, which all finish within a few microseconds of each other,
 // queued 46 us on a single word at the end of every launch (S-ml100k: a third of the kernel).
 constexpr int kDoneStripes = GORSE_HOT_DONE_STRIPES, kDoneStride = GORSE_HOT_DONE_STRIDE;
+constexpr int kFoldPassesWord = 2 * kDoneStripes * kDoneStride;  // hot.done[]: the last launch's folder passes (gorse_hip_test_bpr_fold_stats)
+__device__ __forceinline__ int32_t *done_set(const HotRows &hot, int set) { return hot.done + set * kDoneStripes * kDoneStride; }
+// The end of a worker workgroup (every thread calls it).  LAST: the launch's folders make the last pass themselves, once every worker
+// is counted -- so the workgroup's atomics on the replicas are performed, and released at agent scope, before it is counted.  Without
+// LAST (the per-sample kernel: bpr_fold_kernel follows its launch) the count only ends the folders' passes and needs no order; there a
+// release in each of the up to 4096 short-lived workgroups cost more than the fold kernel it saves (S-ml100k: update kernel 52 -> 126
+// us, and the sampler beside it 56 -> 124 us: each agent-scope release writes back the XCD's L2, which the sampler's stores fill;
+// profiles/r07_hr_full_ab.txt, session A).
+template <bool LAST>
 __device__ __forceinline__ void worker_done(const HotRows &hot) {
-    __hip_atomic_fetch_add(hot.done + (blockIdx.x & (kDoneStripes - 1)) * kDoneStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (LAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if constexpr (LAST) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __hip_atomic_fetch_add(done_set(hot, hot.set) + (blockIdx.x & (kDoneStripes - 1)) * kDoneStride, 1, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 __device__ __forceinline__ bool workers_done(const HotRows &hot, int workers) {  // (called by whole waves)
     const int lane = threadIdx.x & 63;
-    int v = lane < kDoneStripes ? __hip_atomic_load(hot.done + lane * kDoneStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    const int32_t *c = done_set(hot, hot.set);
+    int v = lane < kDoneStripes ? __hip_atomic_load(c + lane * kDoneStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v >= workers;
 }
 
-// one folder pass: (slot, element) pairs strided over the folder threads
-__device__ __forceinline__ void fold_pass(const HotRows &hot, float *Q, int d, int64_t tid, int64_t nthreads) {
+// one folder pass: (slot, element) pairs strided over the folder threads; each exchanges the slot's R_s rows and adds their sum once
+__device__ __forceinline__ void fold_pass(const HotRows &hot, float *Q, int64_t tid, int64_t nthreads) {
+    const int d = hot.d;
     const int64_t work = (int64_t)hot.n_hot * d;
     for (int64_t w = tid; w < work; w += nthreads) {
         const int64_t slot = w / d;
         const int e = (int)(w - slot * d);
-        float *r0 = hot.rep + slot * hot.stride_s + e;
+        const int32_t code = hot.meta[slot];
+        const int nr = 1 << hot_lg(code);
+        float *r0 = hot.rep + hot_base(code) * d + e;
         float v[kHotReplicas];
 #pragma unroll
         for (int r = 0; r < kHotReplicas; r++)
-            v[r] = __hip_atomic_exchange(r0 + r * hot.stride_r, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v[r] = r < nr ? __hip_atomic_exchange(r0 + (int64_t)r * d, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
         float sum = 0.0f;
 #pragma unroll
         for (int r = 0; r < kHotReplicas; r++) sum += v[r];
         if (sum != 0.0f)
             __hip_atomic_fetch_add(Q + (int64_t)hot.items[slot] * d + e, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// The folder workgroups (blockIdx.x < folders) of an update launch.  Wave 0 polls the workers' arrival count at the grain of one
+// load round trip and decides for the workgroup: a pass when the fold period has run out, and once every worker has finished,
+// with LAST, the last pass (an agent-scope acquire behind the count the workers released into).  So the end of the launch never
+// waits for a folder's sleep, and with LAST no fold kernel follows the launch.
+template <bool LAST>
+__device__ void run_folders(const HotRows &hot, float *Q, int folders) {
+    __shared__ int go;
+    const int workers = (int)gridDim.x - folders;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)folders * blockDim.x;
+    if (blockIdx.x == 0 && threadIdx.x < kDoneStripes)  // the stripes the launch before this one counted in: zero for the next launch
+        __hip_atomic_store(done_set(hot, hot.set ^ 1) + threadIdx.x * kDoneStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t t0 = wall_clock64();
+    uint64_t next = t0 + hot.period;
+    int passes = 0;
+    for (;;) {
+        if (threadIdx.x < 64) {
+            const bool all = workers_done(hot, workers);
+            if (threadIdx.x == 0) {
+                const uint64_t now = wall_clock64();
+                int g = 0;
+                if (all || now - t0 > kFolderTimeout) {
+                    if constexpr (LAST) {
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    }
+                    g = 2;
+                } else if (now >= next) {
+                    next = now + hot.period;
+                    g = 1;
+                }
+                go = g;
+            }
+        }
+        __syncthreads();
+        const int g = go;
+        __syncthreads();
+        if (g == 2) break;
+        if (g == 1) {
+            fold_pass(hot, Q, tid, nthreads);
+            passes++;
+        }
+    }
+    if constexpr (LAST) {
+        fold_pass(hot, Q, tid, nthreads);
+        passes++;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) hot.done[kFoldPassesWord] = passes;
 }
 
 template <int NC, int MODE>
@@ -627,15 +716,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(float *P, float *Q, 
                                                             double *loss, HotRows hot, int folders) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (MODE == MODE_ATOMIC && (int)blockIdx.x < folders) {
-        // folder workgroups: drain the replicas until every worker workgroup has finished.  Nobody waits
-        // for a folder, and the pass count is bounded, so an early exit only leaves more to the fold kernel.
-        const int workers = (int)gridDim.x - folders;
-        const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)folders * blockDim.x;
-        for (int pass = 0; pass < (1 << 16); pass++) {
-            fold_pass(hot, Q, d, tid, nthreads);
-            if (workers_done(hot, workers)) break;
-            __builtin_amdgcn_s_sleep(8);
-        }
+        run_folders<false>(hot, Q, folders);
         return;
     }
     const int lane = threadIdx.x & (kGroup - 1);
@@ -652,8 +733,8 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(float *P, float *Q, 
         float *pu = P + (int64_t)u * d, *qi = Q + (int64_t)i * d, *qj = Q + (int64_t)j * d;
         float *qiw = qi;  // where the positive item's update lands
         if (MODE == MODE_ATOMIC && hot.n_hot > 0) {
-            const int slot = hot.slot[i];
-            if (slot >= 0) qiw = hot.rep + (int64_t)slot * hot.stride_s + (int64_t)(group & (kHotReplicas - 1)) * hot.stride_r;
+            const int32_t code = hot.slot[i];
+            if (code >= 0) qiw = hot_row(hot, code, group);
         }
         if constexpr (NC > 0) {
             float p[NC], a[NC], b[NC];
@@ -688,29 +769,25 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(float *P, float *Q, 
         }
     }
     if (loss && lane == 0 && my_loss != 0.0) atomicAdd(loss, my_loss);
-    if (MODE == MODE_ATOMIC && folders > 0) {
-        __syncthreads();
-        if (threadIdx.x == 0) worker_done(hot);
-    }
+    if (MODE == MODE_ATOMIC && folders > 0) worker_done<false>(hot);
 }
 
-// after an update launch: Q[item] += sum of its replicas, replicas <- 0 (nothing else runs on the stream)
-__global__ __launch_bounds__(256) void bpr_fold_kernel(HotRows hot, float *Q, int d) {
+// after a per-sample update launch: Q[item] += the sum of its replicas, replicas <- 0 (nothing else runs on the stream)
+__global__ __launch_bounds__(256) void bpr_fold_kernel(HotRows hot, float *Q) {
+    const int d = hot.d;
     const int64_t work = (int64_t)hot.n_hot * d;
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < work; w += (int64_t)gridDim.x * blockDim.x) {
         const int64_t slot = w / d;
         const int e = (int)(w - slot * d);
-        float *r0 = hot.rep + slot * hot.stride_s + e;
+        const int32_t code = hot.meta[slot];
+        float *r0 = hot.rep + hot_base(code) * d + e;
         float sum = 0.0f;
-#pragma unroll
-        for (int r = 0; r < kHotReplicas; r++) {
-            sum += r0[r * hot.stride_r];
-            r0[r * hot.stride_r] = 0.0f;
+        for (int r = 0; r < (1 << hot_lg(code)); r++) {
+            sum += r0[(int64_t)r * d];
+            r0[(int64_t)r * d] = 0.0f;
         }
         if (sum != 0.0f) Q[(int64_t)hot.items[slot] * d + e] += sum;
     }
-    // every worker of the update launch has finished (stream order): the arrival counter goes back to zero for the next launch
-    if (blockIdx.x == 0 && threadIdx.x < kDoneStripes) hot.done[threadIdx.x * kDoneStride] = 0;
 }
 
 // ---- counting sort by user ---------------------------------------------------------------------
@@ -841,13 +918,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
                                                                  float lr, float reg, int exp_mode, double *loss,
                                                                  HotRows hot, int folders, int neg_replicas, int segs = 1) {
     if ((int)blockIdx.x < folders) {
-        const int workers = (int)gridDim.x - folders;
-        const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)folders * blockDim.x;
-        for (int pass = 0; pass < (1 << 16); pass++) {
-            fold_pass(hot, Q, d, tid, nthreads);
-            if (workers_done(hot, workers)) break;
-            __builtin_amdgcn_s_sleep(8);
-        }
+        run_folders<true>(hot, Q, folders);
         return;
     }
     // with the store route open for negatives their rows are gathered ONE sample ahead instead of two: what a store can
@@ -871,7 +942,6 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
     const bool look_i = hot.n_hot > 0 || (ST & ST_POS);
     const bool look_j = (hot.n_hot > 0 && neg_replicas) || (ST & ST_NEG);
     const int32_t *slot_of = (look_i || look_j) ? hot.slot : si;
-    const int64_t rep_r = (int64_t)(group & (kHotReplicas - 1)) * hot.stride_r;
     // the items of this group's last two samples: a row one of them wrote is NOT in the snapshot of the current sample (gathered
     // two samples ago), so its update goes through an atomic whatever its class -- a store would overwrite the group's own work
     int im1 = -1, jm1 = -1, im2 = -1, jm2 = -1;
@@ -938,8 +1008,8 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
             }
             const bool valid = j >= 0;  // j < 0: the sampler found no negative for this sample (bpr_sample_items_kernel)
             float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
-            if (hot.n_hot > 0 && slot >= 0) qi = hot.rep + (int64_t)slot * hot.stride_s + rep_r;
-            if (hot.n_hot > 0 && neg_replicas && slotj >= 0) qj = hot.rep + (int64_t)slotj * hot.stride_s + rep_r;
+            if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
+            if (hot.n_hot > 0 && neg_replicas && slotj >= 0) qj = hot_row(hot, slotj, group);
 #ifdef GORSE_PROBE
             if (hot.warm_scratch && !(hot.n_hot > 0 && slot >= 0)) qi = hot.warm_scratch + (int64_t)cl(i) * d;
             if (hot.warm_scratch && !(hot.n_hot > 0 && neg_replicas && slotj >= 0)) qj = hot.warm_scratch + (int64_t)cl(j) * d;
@@ -1014,10 +1084,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
         }
     }
     if (loss && (SUBS == 2 ? (glane & 7) == 0 : glane == 0) && my_loss != 0.0) atomicAdd(loss, my_loss);
-    if (folders > 0) {
-        __syncthreads();
-        if (threadIdx.x == 0) worker_done(hot);
-    }
+    if (folders > 0) worker_done<true>(hot);
 }
 
 #ifdef GORSE_PROBE
@@ -1049,13 +1116,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_ring_kernel(float *P, 
                                                                       float reg, int exp_mode, double *loss, HotRows hot,
                                                                       int folders, int neg_replicas) {
     if ((int)blockIdx.x < folders) {
-        const int workers = (int)gridDim.x - folders;
-        const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)folders * blockDim.x;
-        for (int pass = 0; pass < (1 << 16); pass++) {
-            fold_pass(hot, Q, d, tid, nthreads);
-            if (workers_done(hot, workers)) break;
-            __builtin_amdgcn_s_sleep(8);
-        }
+        run_folders<true>(hot, Q, folders);
         return;
     }
     static_assert(D >= 1 && R - D >= 2, "ids D steps ahead of the rows they address, rows at least two steps ahead of their use");
@@ -1080,7 +1141,6 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_ring_kernel(float *P, 
     constexpr bool no_atomics = false;
 #endif
     const int32_t *slot_of = look_i ? hot.slot : si;
-    const int64_t rep_r = (int64_t)(group & (kHotReplicas - 1)) * hot.stride_r;
     for (int64_t u = group; u < U; u += ngroups) {
         const int beg = off[u], end = off[u + 1];
         if (beg >= end) continue;
@@ -1126,8 +1186,8 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_ring_kernel(float *P, 
                 float(&a)[NC] = ra[K];
                 float(&b)[NC] = rb[K];
                 float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
-                if (hot.n_hot > 0 && slot >= 0) qi = hot.rep + (int64_t)slot * hot.stride_s + rep_r;
-                if (look_j && slotj >= 0) qj = hot.rep + (int64_t)slotj * hot.stride_s + rep_r;
+                if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
+                if (look_j && slotj >= 0) qj = hot_row(hot, slotj, group);
                 const float diff =
                     D8 ? group_tree8(p[0] * a[0]) - group_tree8(p[0] * b[0]) : dot512_regs<NC>(p, a) - dot512_regs<NC>(p, b);
                 const float ex = bpr_exp(-diff, exp_mode);
@@ -1158,10 +1218,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_ring_kernel(float *P, 
         }
     }
     if (loss && glane == 0 && my_loss != 0.0) atomicAdd(loss, my_loss);
-    if (folders > 0) {
-        __syncthreads();
-        if (threadIdx.x == 0) worker_done(hot);
-    }
+    if (folders > 0) worker_done<true>(hot);
 }
 #endif  // GORSE_PROBE
 
@@ -1273,9 +1330,17 @@ int g_user_gpw = 4;                      // probe builds: groups of a wave that 
 int g_user_block = kBlock;               // probe builds: threads per workgroup of the ring kernel
 int g_user_depth = 0;                  // probe builds: which (G, IA) pipeline of the atomics-only kernel (gorse_hip_test_set_bpr_user_depth)
 
+// the replica rows of a slot lie next to each other (r04_a: 4 KB apart or n_hot rows apart makes no difference); n_hot stays 0 (no
+// replicas, no folders) until the launch opens them: open_hot
 HotRows make_hot(const gorse_mf *h) {
-    // the eight replica rows of a slot lie next to each other (r04_a: 4 KB apart or n_hot rows apart makes no difference)
-    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_rep.p, h->hot_done.p, 0, (int64_t)kHotReplicas * h->d, h->d};
+    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_meta.p, h->hot_rep.p, h->hot_done.p, 0, h->d, 0, g_fold_period};
+}
+// an update launch with folders: the replicas open, the launch's set of arrival stripes by launch parity (the set of the launch before
+// is zeroed by this one's folders; gorse_mf_create zeroed both)
+int open_hot(gorse_mf *h, HotRows &hot) {
+    hot.n_hot = h->n_hot;
+    hot.set = (int)(h->hot_launches++ & 1);
+    return kFolderBlocks;
 }
 
 int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *bucket, size_t cap, float lr, float reg,
@@ -1286,15 +1351,11 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     const int64_t capb = 256 * 16;
     if (blocks > capb) blocks = capb;
     HotRows hot = make_hot(h);
-    int folders = 0;
-    if (h->n_hot > 0 && !(g_variant & 32)) {
-        hot.n_hot = h->n_hot;
-        folders = kFolderBlocks;  // hot_done is zero: gorse_mf_create, and every fold kernel leaves it so
-    }
+    const int folders = h->n_hot > 0 && !(g_variant & 32) ? open_hot(h, hot) : 0;
     blocks += folders;
-    // the negative's slot look-up is one more gather per sample: only where a draw has a fair chance of meeting a hot item (C2: a
-    // quarter of the items are hot; at the 10M x 1M set one in ten thousand, and the look-up cost 4 % of the epoch)
-    const int neg_rep = !(g_variant & (1 << 25)) && (int64_t)hot.n_hot * 64 >= h->I ? 1 : 0;
+    // the negative's slot look-up is one more gather per sample: where a draw has a fair chance of meeting a hot item (hot_rows.hpp;
+    // gorse_mf_create counted the negatives into the replica counts by the same rule)
+    const int neg_rep = !(g_variant & (1 << 25)) && hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I) ? 1 : 0;
 #ifdef GORSE_PROBE
     if (g_variant & (1 << 23)) {
         static DevBuf<float> scratch;  // (a probe: never released)
@@ -1377,11 +1438,6 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
 #undef PROBE_CASES
 #undef PROBE_DEPTHS
     GORSE_HIP_CHECK(hipGetLastError());
-    if (folders > 0) {
-        const int64_t fb = std::min<int64_t>(ceil_div((int64_t)hot.n_hot * d, 256), 512);
-        bpr_fold_kernel<<<dim3((unsigned)fb), dim3(256), 0, st>>>(hot, h->Q.p, d);
-        GORSE_HIP_CHECK(hipGetLastError());
-    }
     return GORSE_OK;
 }
 
@@ -1396,11 +1452,7 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
     const int64_t cap = 256 * 16;  // 16 workgroups of 4 waves per CU: grid-stride beyond that
     if (blocks > cap) blocks = cap;
     HotRows hot = make_hot(h);
-    int folders = 0;
-    if (MODE == MODE_ATOMIC && h->n_hot > 0 && !(g_variant & 32)) {
-        hot.n_hot = h->n_hot;
-        folders = kFolderBlocks;  // hot_done is zero: gorse_mf_create, and every fold kernel leaves it so
-    }
+    const int folders = MODE == MODE_ATOMIC && h->n_hot > 0 && !(g_variant & 32) ? open_hot(h, hot) : 0;
     blocks += folders;
     dim3 grid((unsigned)blocks), block(kBlock);
 #define LAUNCH(NC, SH)                                                                                               \
@@ -1418,9 +1470,9 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
         LAUNCH(0, (size_t)kGroupsPerBlock * 3 * d * sizeof(float));
 #undef LAUNCH
     GORSE_HIP_CHECK(hipGetLastError());
-    if (folders > 0) {
+    if (folders > 0) {  // (its folders make no last pass: worker_done)
         const int64_t fb = std::min<int64_t>(ceil_div((int64_t)hot.n_hot * d, 256), 512);
-        bpr_fold_kernel<<<dim3((unsigned)fb), dim3(256), 0, st>>>(hot, h->Q.p, d);
+        bpr_fold_kernel<<<dim3((unsigned)fb), dim3(256), 0, st>>>(hot, h->Q.p);
         GORSE_HIP_CHECK(hipGetLastError());
     }
     return GORSE_OK;
@@ -1721,6 +1773,33 @@ extern "C" void gorse_hip_test_set_bpr_store_mode(int32_t store_mode) {
 #ifndef GORSE_PROBE
     if (g_store_mode & ~1) g_store_mode &= 1;  // forms the shipped library does not carry fall back to the nearest one it does
 #endif
+}
+extern "C" void gorse_hip_test_set_bpr_fold_period(int32_t ticks) { g_fold_period = ticks > 0 ? (uint32_t)ticks : kDefaultFoldPeriod; }
+extern "C" int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3) {
+    if (!h || !out3) return fail(GORSE_ERR_INVALID, "NULL argument");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    int32_t passes = 0;
+    if (h->hot_done.p)
+        GORSE_HIP_CHECK(hipMemcpy(&passes, h->hot_done.p + kFoldPassesWord, sizeof(int32_t), hipMemcpyDeviceToHost));
+    out3[0] = passes, out3[1] = h->n_hot, out3[2] = h->hot_rows;
+    return GORSE_OK;
+}
+extern "C" int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items, int32_t *replicas, float *rep) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    const size_t n = (size_t)h->n_hot;
+    std::vector<int32_t> meta(n);
+    if (n > 0) {
+        if (items) GORSE_HIP_CHECK(hipMemcpy(items, h->hot_items.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GORSE_HIP_CHECK(hipMemcpy(meta.data(), h->hot_meta.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (replicas)
+        for (size_t s = 0; s < n; s++) replicas[s] = 1 << hot_lg(meta[s]);
+    if (rep && h->hot_rows > 0)
+        GORSE_HIP_CHECK(hipMemcpy(rep, h->hot_rep.p, (size_t)h->hot_rows * h->d * sizeof(float), hipMemcpyDeviceToHost));
+    return GORSE_OK;
 }
 extern "C" int32_t gorse_hip_test_probe_build(void) {
 #ifdef GORSE_PROBE

@@ -266,6 +266,14 @@ extern "C" void gorse_hip_test_set_prep_cu_stride(int32_t n) { g_mf_prep_cu_stri
 constexpr int64_t kDefaultColdWindow = 32768;
 int64_t g_mf_cold_window = kDefaultColdWindow;  // items expected to be touched less than once per this many samples are "cold" (0 = none)
 extern "C" void gorse_hip_test_set_bpr_cold_window(int64_t samples) { g_mf_cold_window = samples < 0 ? kDefaultColdWindow : samples; }
+// Expected updates per sample that one replica row of a hot item takes (hot_rows.hpp hot_replica_layout: R_s = share_s / unit rounded
+// up to a power of two, at most GORSE_HOT_REPLICAS).  Swept on C2 (profiles/r07_hr_sweep_replica_unit.txt, ms per epoch, min of three
+// handles): unit 0.0005 / 0.001 / 0.002 / 0.004 -> 0.556 / 0.543 / 0.556 / 0.644 at nFactors 64 (eight rows for every slot: 0.572);
+// 0.292 for all of them at nFactors 16.  0.001 gives the hottest slots (1.5 % of the updates) their eight rows and 703 of the 926 one
+// row; at 0.004 the hottest get four and queue again (as four for EVERY slot did in round 5).
+constexpr double kDefaultReplicaUnit = 0.001;
+double g_mf_replica_unit = kDefaultReplicaUnit;
+extern "C" void gorse_hip_test_set_bpr_replica_unit(double unit) { g_mf_replica_unit = unit > 0 ? unit : kDefaultReplicaUnit; }
 
 // the cold classes of one handle for another window: warm <-> cold only, the hot slots stay (include/gorse_hip.h)
 extern "C" int32_t gorse_mf_set_bpr_cold_window(gorse_mf *h, int64_t samples, int64_t *n_cold) {
@@ -278,7 +286,7 @@ extern "C" int32_t gorse_mf_set_bpr_cold_window(gorse_mf *h, int64_t samples, in
     h->n_cold = 0;
     for (int64_t i = 0; i < h->I; i++) {
         int32_t &s = h->h_hot_slot[(size_t)i];
-        if (s >= 0) continue;  // hot: replica slot
+        if (s >= 0) continue;  // hot: its replica rows stay as they are
         const bool cold = samples > 0 && h->nnz > 0 &&
                           ((double)h->h_item_count[(size_t)i] / (double)h->nnz + 1.0 / (double)h->I) * (double)samples < 1.0;
         s = cold ? -2 : -1;
@@ -420,22 +428,7 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
                     if (!pc.empty())
                         for (int64_t i = 0; i < I; i++) cnt[(size_t)i] += pc[(size_t)i];
             }
-            // 1/2048 until round 3: with the negatives routed through the replicas too, 1/8192 is 6 % faster at C2
-            // (profiles/r03_zx_probe_bpr_hot.txt).  A replica's content reaches Q one folder pass late, so the hot items stay a
-            // minority: at least 64 feedbacks, at most a quarter of the items (S-ml100k with two thirds of its items hot lost
-            // 0.011 of NDCG@10 in the per-sample schedule; with every item hot S-ml1m's fit diverges)
-            const int64_t hdiv = 8192;
-            const size_t hcap = (size_t)std::min<int64_t>(1024, std::max<int64_t>(1, I / 4));
-            const int64_t thr = std::max<int64_t>(64, (h->nnz + hdiv - 1) / hdiv);
-            std::vector<int32_t> hot;
-            for (int64_t i = 0; i < I; i++)
-                if (cnt[i] >= thr) hot.push_back((int32_t)i);
-            if (hot.size() > hcap) {
-                std::nth_element(hot.begin(), hot.begin() + hcap, hot.end(),
-                                 [&](int32_t a, int32_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
-                hot.resize(hcap);
-                std::sort(hot.begin(), hot.end());
-            }
+            const std::vector<int32_t> hot = hot_items_select(cnt, h->nnz);  // (hot_rows.hpp)
             std::vector<int32_t> slot((size_t)I, -1);
             // cold items (class -2, bpr.hip kCold): a sample touches item i with probability share(i) as its positive and 1 / I as
             // its negative; where fewer than one touch is expected per `cold window` samples the row's update may be a plain
@@ -453,20 +446,42 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
                         h->n_cold++;
                     }
             }
-            for (size_t k = 0; k < hot.size(); k++) slot[hot[k]] = (int32_t)k;
+            // replica rows per hot item, by its expected updates per sample (hot_rows.hpp hot_replica_layout): what a slot needs so that
+            // its replicas do not queue, instead of the eight rows every slot had until round 6 -- a folder pass exchanges every row, and
+            // at C2 the median hot item took ~18 updates per pass against 8 x 64 exchanged dwords
+            std::vector<int32_t> meta;
+            {
+                for (size_t k = 0; k < hot.size(); k++) slot[hot[k]] = (int32_t)k;
+                std::vector<std::vector<uint64_t>> part(64);
+                parallel_rows(U, user_indptr, [&](int t, int64_t r0, int64_t r1) {
+                    part[(size_t)t].assign(hot.size(), 0);
+                    hot_shares_rows(user_indptr, user_indices, slot.data(), r0, r1, part[(size_t)t].data());
+                });
+                std::vector<uint64_t> acc(hot.size(), 0);
+                for (auto &pc : part)
+                    for (size_t k = 0; k < pc.size(); k++) acc[k] += pc[k];
+                int64_t users = 0;
+                for (int64_t r = 0; r < U; r++) users += user_indptr[r + 1] > user_indptr[r];
+                h->hot_rows = hot_replica_layout(acc, users, I, hot_neg_replicas((int64_t)hot.size(), I), g_mf_replica_unit,
+                                                 GORSE_HOT_REPLICAS, meta);
+                for (size_t k = 0; k < hot.size(); k++) slot[hot[k]] = meta[k];
+            }
             h->h_hot_slot = slot;
             h->n_hot = (int)hot.size();
             GORSE_TRY(h->hot_slot.alloc((size_t)I));
             GORSE_TRY(h->hot_items.alloc(hot.size()));
-            GORSE_TRY(h->hot_rep.alloc(hot.size() * GORSE_HOT_REPLICAS_ALLOC * (size_t)d));
-            GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_STRIPES * GORSE_HOT_DONE_STRIDE));  // (bpr.hip worker_done)
-            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_done.p, 0, (size_t)GORSE_HOT_DONE_STRIPES * GORSE_HOT_DONE_STRIDE * sizeof(int32_t), h->stream));
+            GORSE_TRY(h->hot_meta.alloc(hot.size()));
+            GORSE_TRY(h->hot_rep.alloc((size_t)h->hot_rows * (size_t)d));
+            GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_WORDS));  // (bpr.hip worker_done)
+            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_done.p, 0, (size_t)GORSE_HOT_DONE_WORDS * sizeof(int32_t), h->stream));
             GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_slot.p, slot.data(), (size_t)I * sizeof(int32_t), hipMemcpyHostToDevice,
                                            h->stream));
-            if (!hot.empty())
+            if (!hot.empty()) {
                 GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_items.p, hot.data(), hot.size() * sizeof(int32_t),
                                                hipMemcpyHostToDevice, h->stream));
-            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_rep.p, 0, std::max<size_t>(1, hot.size() * GORSE_HOT_REPLICAS_ALLOC * (size_t)d) * sizeof(float),
+                GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_meta.p, meta.data(), hot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            }
+            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_rep.p, 0, std::max<size_t>(1, (size_t)h->hot_rows * (size_t)d) * sizeof(float),
                                            h->stream));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));  // slot / hot are host temporaries
         }

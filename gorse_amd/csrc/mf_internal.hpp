@@ -4,19 +4,15 @@
 
 #include "cf_device.hpp"
 
+#include "hot_rows.hpp"
+
 #define GORSE_HOT_DONE_STRIPES 32  // words of the workers' arrival counter (bpr.hip worker_done), GORSE_HOT_DONE_STRIDE words apart
 #define GORSE_HOT_DONE_STRIDE 64
+// hot_done: two sets of arrival stripes (update launches alternate between them) and one line for the folders' pass count
+#define GORSE_HOT_DONE_WORDS (2 * GORSE_HOT_DONE_STRIPES * GORSE_HOT_DONE_STRIDE + GORSE_HOT_DONE_STRIDE)
 #ifndef GORSE_HOT_REPLICAS
-#define GORSE_HOT_REPLICAS 8  // replica rows per hot item (bpr.hip kHotReplicas); A/B builds of bpr.hip: make ab AB_FLAGS=-DGORSE_HOT_REPLICAS=16
+#define GORSE_HOT_REPLICAS 8  // replica rows of the hottest items (the most a slot gets, gorse_mf_create; bpr.hip kHotReplicas)
 #endif
-// replica rows ALLOCATED (and cleared) per hot item by gorse_mf_create: exactly what the kernels use.  An A/B build of bpr.hip alone with
-// more replicas (make ab AB_SRC=bpr AB_FLAGS=-DGORSE_HOT_REPLICAS=16) needs mf.hip to allocate as many: build the library with
-// -DGORSE_HOT_REPLICAS_ALLOC=32 for such a session (round 5 always allocated 32: up to 16 MB of allocation + memset per handle at
-// nFactors 128, in the very Fit whose handle creation the same round had shortened)
-#ifndef GORSE_HOT_REPLICAS_ALLOC
-#define GORSE_HOT_REPLICAS_ALLOC GORSE_HOT_REPLICAS
-#endif
-static_assert(GORSE_HOT_REPLICAS_ALLOC >= GORSE_HOT_REPLICAS, "gorse_mf_create must allocate every replica row the kernels use");
 
 struct gorse_mf {
     int device = 0;
@@ -58,14 +54,17 @@ struct gorse_mf {
     gorse::DevBuf<int32_t> ubins;      // binned preparation: bin totals, bin starts at kMaxBins (preparations are serial: one copy)
     gorse::DevBuf<int32_t> ubinmat;    // binned preparation: the tile x bin count matrix
     int64_t chunk_seq = 0;             // chunks enqueued so far: buffer = chunk_seq & 1, across calls
-    // hot-row replicas of the Hogwild schedule (bpr.hip): popular items' positive updates land here
-    gorse::DevBuf<int32_t> hot_slot, hot_items, hot_done;
+    // hot-row replicas of the Hogwild schedule (bpr.hip): popular items' updates land here.  hot_meta[slot] = hot_code(first row,
+    // log2 replica count) (hot_rows.hpp), the same word hot_slot holds for the slot's item; hot_rep holds hot_rows rows of d floats.
+    gorse::DevBuf<int32_t> hot_slot, hot_items, hot_meta, hot_done;
     gorse::DevBuf<float> hot_rep;
     int n_hot = 0;
+    int64_t hot_rows = 0;       // replica rows in all (the sum of the slots' counts)
+    uint64_t hot_launches = 0;  // update launches with folders so far: the parity picks the launch's set of arrival stripes
     int64_t n_cold = 0;  // items of class "cold" in hot_slot (-2): updates by write-through store (bpr.hip)
     int64_t cold_window = 0;               // what n_cold was computed for (gorse_mf_set_bpr_cold_window)
     std::vector<int32_t> h_item_count;     // training feedbacks per item and
-    std::vector<int32_t> h_hot_slot;       // the class of every item (replica slot, -1 warm, -2 cold) as last uploaded: host copies for a re-classification
+    std::vector<int32_t> h_hot_slot;       // the class of every item (hot_code, -1 warm, -2 cold) as last uploaded: host copies for a re-classification
     gorse::DevBuf<int32_t> order;  // sequential mode: samples sorted by dependency level
     gorse::DevBuf<double> loss;
     gorse::DevBuf<int32_t> fail_count;

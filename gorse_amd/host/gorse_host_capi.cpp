@@ -11,6 +11,7 @@
 #include "../csrc/sparse_host.hpp"
 #include "../csrc/als_plan.hpp"
 #include "../csrc/bpr_bins.hpp"
+#include "../csrc/hot_rows.hpp"
 #include "../csrc/topk_sym.hpp"
 
 using namespace gorse;
@@ -929,6 +930,26 @@ int32_t gh_test_bpr_bins_emulate(int64_t U, const int32_t *key, int64_t n, int32
     std::copy(ps.begin(), ps.end(), pair_s);
     std::copy(pu.begin(), pu.end(), pair_u);
     return 1;
+}
+// the hot items of a BPR handle and their replica rows (csrc/hot_rows.hpp, the header gorse_mf_create includes) for a user CSR, with
+// replica unit `unit` and at most `max_r` rows per item: items[s], meta[s] = hot_code(first row, log2 R) for the returned number of
+// slots (at most min(1024, I / 4)); out1[0] = the rows in all
+int32_t gh_test_bpr_hot_layout(int64_t U, int64_t I, const int64_t *uptr, const int32_t *uidx, double unit, int32_t max_r, int32_t *items,
+                               int32_t *meta, int64_t *out1) {
+    std::vector<int64_t> cnt((size_t)I, 0);
+    for (int64_t t = 0; t < uptr[U]; t++) cnt[(size_t)uidx[t]]++;
+    const std::vector<int32_t> hot = gorse::hot_items_select(cnt, uptr[U]);
+    std::vector<int32_t> slot((size_t)I, -1);
+    for (size_t k = 0; k < hot.size(); k++) slot[(size_t)hot[k]] = (int32_t)k;
+    std::vector<uint64_t> acc(hot.size(), 0);
+    gorse::hot_shares_rows(uptr, uidx, slot.data(), 0, U, acc.data());
+    int64_t users = 0;
+    for (int64_t r = 0; r < U; r++) users += uptr[r + 1] > uptr[r];
+    std::vector<int32_t> m;
+    out1[0] = gorse::hot_replica_layout(acc, users, I, gorse::hot_neg_replicas((int64_t)hot.size(), I), unit, max_r, m);
+    std::copy(hot.begin(), hot.end(), items);
+    std::copy(m.begin(), m.end(), meta);
+    return (int32_t)hot.size();
 }
 // the ALS row plan's long-row threshold for a side of `side_entries` feedbacks (csrc/als_plan.hpp, the header als_build_plan includes)
 int64_t gh_test_als_long_row(int64_t side_entries, int32_t d) { return gorse::als_long_row_threshold(side_entries, d); }

@@ -188,6 +188,20 @@ int32_t gorse_hip_test_bpr_prepare_chunk(gorse_mf *h, int64_t n, uint64_t seed, 
 /* items expected to be touched (as a positive: their share of the feedback; as a negative: 1 / items) less than once per
  * `samples` samples are of class "cold" in handles created AFTERWARDS; 0 = no cold items (every update an atomic). */
 void gorse_hip_test_set_bpr_cold_window(int64_t samples);
+/* hot-row replicas of the Hogwild BPR schedules (csrc/bpr.hip HotRows, csrc/hot_rows.hpp).  Handles created AFTERWARDS give a hot item
+ * R = the smallest power of two >= (its expected updates per sample) / unit replica rows, 1 .. 8; unit <= 0 = the library's default.
+ * Results never depend on it beyond the Hogwild race itself. */
+void gorse_hip_test_set_bpr_replica_unit(double unit);
+/* wall-clock ticks (100 MHz) from one folder pass to the next in the update launches that follow; <= 0 = the library's default. */
+void gorse_hip_test_set_bpr_fold_period(int32_t ticks);
+/* after the handle's streams drain: out3[0] = folder passes of the last update launch with folders (its final pass included; folder
+ * workgroup 0's count), [1] = hot items, [2] = replica rows in all (the sum of their R).  Bytes one pass moves: (out3[2] exchanged +
+ * out3[1] added) x nFactors x 4. */
+int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3 /*host*/);
+/* the hot slots of a handle, after its streams drain: items[s] = the slot's item (ascending), replicas[s] = its R (the rows of slot s
+ * follow those of slot s - 1), rep = every replica row (sum of R x nFactors floats; all zero between two update launches).  Any of the
+ * three may be NULL. */
+int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items /*host*/, int32_t *replicas /*host*/, float *rep /*host*/);
 
 #ifdef __cplusplus
 }
