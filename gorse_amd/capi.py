@@ -107,6 +107,12 @@ SIGNATURES = {
     "gorse_fm_set_train": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p]),
     "gorse_fm_epoch": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_float, C.c_float, _i32p, _f32p]),
     "gorse_fm_predict": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p]),
+    "gorse_fm_set_embedding_dims": (C.c_int32, [_vp, C.c_int32, _i32p]),
+    "gorse_fm_set_embedding_params": (C.c_int32, [_vp, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "gorse_fm_get_embedding_params": (C.c_int32, [_vp, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "gorse_fm_set_train_embeddings": (C.c_int32, [_vp, C.c_int32, C.POINTER(C.c_uint16)]),
+    "gorse_fm_predict_embeddings": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, C.POINTER(C.POINTER(C.c_uint16)),
+                                                C.c_int32, _f32p]),
     "gorse_hip_test_set_exact_exp": (None, [C.c_int32]),
     "gorse_hip_test_set_variant": (None, [C.c_int32]),
     "gorse_hip_test_set_topk_path": (None, [C.c_int32]),
@@ -389,13 +395,61 @@ class MF:
 
 
 class FM:
-    """One gorse_fm handle: a factorization machine (ctr.AFM without the embedding branch) resident on one GPU.
-    Rows are n x width matrices of feature indices and values, padded with index 0 / value 0."""
+    """One gorse_fm handle: a factorization machine (ctr.AFM) resident on one GPU, with its item-embedding attention branch when
+    embedding_dims names fields.  Rows are n x width matrices of feature indices and values, padded with index 0 / value 0;
+    embeddings are n x D matrices of bf16 bit patterns (uint16)."""
 
-    def __init__(self, n_features, n_factors, device=0):
+    def __init__(self, n_features, n_factors, device=0, embedding_dims=None):
         self.nf, self.d = int(n_features), int(n_factors)
+        self.dims = ()
         self.h = _vp()
         check(lib().gorse_fm_create(C.byref(self.h), device, self.nf, self.d))
+        if embedding_dims is not None:
+            self.set_embedding_dims(embedding_dims)
+
+    def set_embedding_dims(self, dims):
+        """the item-embedding fields' dimensions (an empty list: the plain factorization machine)"""
+        dims = _arr(list(dims), np.int32).reshape(-1)
+        check(lib().gorse_fm_set_embedding_dims(self.h, dims.size, _p(dims, _i32p) if dims.size else None))
+        self.dims = tuple(int(x) for x in dims)
+
+    def _field_shapes(self, field):
+        D = self.dims[field]
+        return ((self.d, D), (D, self.d), (self.d,), (D, self.d), (self.d,))
+
+    def set_embedding_params(self, field, H, Wa, ba, We, be):
+        if not 0 <= field < len(self.dims):
+            raise GorseHipError(ERR_INVALID, "embedding field out of range")
+        arrs = [_arr(a, np.float32) for a in (H, Wa, ba, We, be)]
+        for a, shp in zip(arrs, self._field_shapes(field)):
+            if a.size != int(np.prod(shp)):
+                raise GorseHipError(ERR_INVALID, "H is d x D, Wa and We are D x d, ba and be hold d values")
+        check(lib().gorse_fm_set_embedding_params(self.h, field, *[_p(a, _f32p) for a in arrs]))
+
+    def get_embedding_params(self, field):
+        """(H, Wa, ba, We, be) of one field"""
+        if not 0 <= field < len(self.dims):
+            raise GorseHipError(ERR_INVALID, "embedding field out of range")
+        arrs = [np.empty(shp, np.float32) for shp in self._field_shapes(field)]
+        check(lib().gorse_fm_get_embedding_params(self.h, field, *[_p(a, _f32p) for a in arrs]))
+        return tuple(arrs)
+
+    def set_train_embeddings(self, field, emb):
+        """the training rows' embeddings of one field: an n x D matrix of bf16 bit patterns (uint16)"""
+        emb = _arr(emb, np.uint16)
+        check(lib().gorse_fm_set_train_embeddings(self.h, field, _p(emb, C.POINTER(C.c_uint16))))
+
+    def predict_embeddings(self, indices, values, embs, batch_size):
+        """logits of the rows scored in slices of batch_size rows; embs: one n x D uint16 (bf16) matrix per field"""
+        idx, val = self._rows(indices, values)
+        embs = [_arr(e, np.uint16) for e in embs]
+        if len(embs) != len(self.dims) or any(e.shape != (idx.shape[0], D) for e, D in zip(embs, self.dims)):
+            raise GorseHipError(ERR_INVALID, "one n x D embedding matrix per field")
+        ptrs = (C.POINTER(C.c_uint16) * max(1, len(embs)))(*[_p(e, C.POINTER(C.c_uint16)) for e in embs])
+        out = np.empty(idx.shape[0], np.float32)
+        check(lib().gorse_fm_predict_embeddings(self.h, idx.shape[0], idx.shape[1], _p(idx, _i32p), _p(val, _f32p), ptrs,
+                                                int(batch_size), _p(out, _f32p)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,4 +1,5 @@
-// fm.hip -- ctr.AFM without the item-embedding branch (model/ctr/fm.go:111-126): the factorization machine
+// fm.hip -- ctr.AFM (model/ctr/fm.go:111-134).  First the factorization machine itself (fm.go:111-126); the item-embedding
+// attention branch (fm.go:127-132) follows further down ("the item-embedding branch").  The factorization machine:
 // logit = B + sum_j W[idx_j] x_j + 0.5 sum_f ((sum_j V[idx_j,f] x_j)^2 - sum_j V[idx_j,f]^2 x_j^2), trained with
 // BCEWithLogits on contiguous batches (fm.go:362-378) and the reference's dense SGD / Adam steps
 // (common/nn/optimizers.go:70-84, 118-156), plus batch scoring (BatchInternalPredict, fm.go:156-178).
@@ -16,6 +17,34 @@
 // optimizer kernel applies the same rule by element position (fmaf vs. mul then add; the library builds with -ffp-contract=off).
 #include "common.hpp"
 #include "cf_device.hpp"
+
+namespace gorse {
+namespace fm {
+constexpr int kMaxFields = 8;     // embedding fields per model
+constexpr int kMaxEmbDim = 4096;  // floats per embedding
+constexpr int kGradSegs = 8;      // row segments the branch's parameter gradients are summed in (fixed: the order depends on shapes alone)
+
+// one dense tensor of the embedding branch for the optimizer pass: read from device memory by tensor number
+struct DenseDesc {
+    float *p, *m, *v;
+    const float *g;   // kGradSegs partial sums, gstride apart
+    int64_t len, gstride;
+};
+
+// One embedding field: H (d x D) | Wa (D x d) | ba (d) | We (D x d) | be (d) in one allocation, every tensor starting at a
+// multiple of four floats; the moments lie in the same layout.
+struct Field {
+    int D = 0;
+    size_t off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0}, total = 0;
+    DevBuf<float> p, m, v;
+    DevBuf<float> gpart;    // kGradSegs x (dH: d*D | dWa,dba: (D+1)*d | dWe,dbe: (D+1)*d)
+    DevBuf<uint16_t> x;     // the training set's embeddings, n x D bf16
+    bool have_x = false;
+    DevBuf<float> h, a;     // per batch: relu(pre) (rows x d), the softmax output (rows x D; holds s, then e, then a)
+    size_t gstride() const { return len[0] + 2 * (len[1] + len[2]); }
+};
+}  // namespace fm
+}  // namespace gorse
 
 struct gorse_fm {
     int device = 0;
@@ -43,6 +72,14 @@ struct gorse_fm {
     gorse::DevBuf<int32_t> p_idx;
     gorse::DevBuf<float> p_val, p_out;
     hipEvent_t ev[2] = {nullptr, nullptr};
+    // the item-embedding branch (fm.go:127-132): empty unless gorse_fm_set_embedding_dims configured fields
+    int n_fields = 0;
+    gorse::fm::Field fld[gorse::fm::kMaxFields];
+    gorse::DevBuf<gorse::fm::DenseDesc> descs;
+    int64_t dense_blocks = 0;  // blocks of the longest dense tensor
+    gorse::DevBuf<float> a_rmax, a_rsum, a_sumdx, a_gx, a_dpre, a_esum, a_vxe, a_logit;
+    gorse::DevBuf<uint16_t> p_x;
+    gorse::DevBuf<float> p_zero, p_gs, p_loss, p_vx;
 };
 
 namespace gorse {
@@ -80,7 +117,7 @@ struct FwdArgs {
     int64_t row0, nrows;
     int width, d;
     float inv_n;         // 1 / rows of the batch (training)
-    float *out;          // scoring: logits
+    float *out;          // scoring: logits; training: NULL, or where the embedding branch wants the FM's logit
     float *gs, *loss, *vx;  // training: per sample g_b, loss_b, vx (nrows x d)
 };
 
@@ -134,6 +171,7 @@ __global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs a) {
     const float y = (a.tgt[r] + 1.0f) * 0.5f;
     a.loss[b] = fmaxf(logit, 0.0f) - logit * y + logf(1.0f + expf(-fabsf(logit)));
     a.gs[b] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
+    if (a.out) a.out[b] = logit;  // with embedding fields att_loss_kernel forms loss and g again from the full logit
 }
 
 struct AccArgs {
@@ -359,6 +397,382 @@ __global__ __launch_bounds__(kBlock) void fm_opt_kernel(OptArgs a) {
     }
 }
 
+// ---- the item-embedding branch (fm.go:127-132; nn.Attention + nn.Linear, common/nn/layers.go:36-60, 160-190) ------------
+// Per field with embedding dimension D and a batch of n rows x (bf16, widened on load):
+//   pre = x Wa + ba, h = relu(pre), s = h H, a = Softmax(s, 1), z = a * x, enc = z We + be, logit += sum_f vx_f enc_f.
+// The reference's Softmax subtracts the maxima and divides by the sums through Tensor.sub / Tensor.div, which index the
+// (n x 1) operand by flat index % n (tensor.go:328-337, 370-379): element (r, c) uses row (r D + c) % n's maximum and sum,
+// forward and backward (op.go:760-777).  These kernels reproduce that indexing, so every maximum must exist before any
+// exponential and every sum before any a: three launches forward, two backward plus the parameter-gradient reduction.
+// One wave per row; lanes stride over the D columns; skinny products are formed 16 factors at a time and wave-reduced in
+// a fixed butterfly.
+
+constexpr int kFC = 16;  // factors per accumulator chunk
+
+struct AttArgs {
+    const uint16_t *x;  // the batch rows' embeddings, nrows x D bf16
+    const float *H, *Wa, *ba, *We, *be;
+    int64_t nrows;
+    int D, d;
+    float *h;           // nrows x d
+    float *s;           // nrows x D: s (att_score), e (att_exp), a (att_enc)
+    float *rmax, *rsum; // nrows
+    const float *vx;    // nrows x d
+    float *logit;       // nrows: the field's contribution is added
+    float *esum;        // nrows x d: sum of the fields' enc (training), or NULL
+    int first;          // field 0 writes esum, later fields add
+    // backward
+    const float *gs;    // nrows: the loss gradient of the rows' logits
+    float *gx;          // nrows x D: a * da, then ds
+    float *sumdx;       // nrows
+    float *dpre;        // nrows x d
+    float *gpart;       // kGradSegs x Field::gstride()
+    int64_t gstride;
+};
+
+__device__ __forceinline__ float bf16_f32(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// w[k] = M[c, f0 + k] of a row-major (D x d) matrix, zero past d; 16-byte loads where d is a multiple of four
+__device__ __forceinline__ void load_w16(const float *M, int64_t c, int d, int f0, bool vec, float (&w)[kFC]) {
+    const float *p = M + c * d + f0;
+    if (vec) {
+#pragma unroll
+        for (int j = 0; j < kFC / 4; j++) {
+            float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (f0 + 4 * j < d) t = *reinterpret_cast<const float4 *>(p + 4 * j);
+            w[4 * j] = t.x, w[4 * j + 1] = t.y, w[4 * j + 2] = t.z, w[4 * j + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kFC; k++) w[k] = f0 + k < d ? p[k] : 0.0f;
+    }
+}
+
+// the wave's total of every acc[k]; lane k keeps total k (selected without indexing the array by a register)
+__device__ __forceinline__ float reduce_pick(float (&acc)[kFC], int lane) {
+    float mine = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kFC; k++) {
+        const float t = wave_sum(acc[k]);
+        if (lane == k) mine = t;
+    }
+    return mine;
+}
+
+// pre, h = relu(pre), s = h H and each row's maximum of s
+__global__ __launch_bounds__(kBlock) void att_score_kernel(AttArgs a) {
+    __shared__ float sh[kBlock / 64][kMaxFactors];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
+    const bool live = r < a.nrows;
+    const bool vec = (a.d & 3) == 0;
+    if (live) {
+        const uint16_t *xr = a.x + r * a.D;
+        for (int f0 = 0; f0 < a.d; f0 += kFC) {
+            float acc[kFC];
+#pragma unroll
+            for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
+            for (int c = lane; c < a.D; c += 64) {
+                const float xv = bf16_f32(xr[c]);
+                float wv[kFC];
+                load_w16(a.Wa, c, a.d, f0, vec, wv);
+#pragma unroll
+                for (int k = 0; k < kFC; k++) acc[k] = fmaf(xv, wv[k], acc[k]);
+            }
+            const float mine = reduce_pick(acc, lane);
+            if (lane < kFC && f0 + lane < a.d) {
+                const float hv = fmaxf(mine + a.ba[f0 + lane], 0.0f);
+                sh[w][f0 + lane] = hv;
+                a.h[r * a.d + f0 + lane] = hv;
+            }
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    float *sr = a.s + r * a.D;
+    float mx = -INFINITY;
+    for (int c = lane; c < a.D; c += 64) {
+        float acc = 0.0f;
+        for (int f = 0; f < a.d; f++) acc = fmaf(sh[w][f], a.H[(int64_t)f * a.D + c], acc);  // floats.MM's chain over f
+        sr[c] = acc;
+        mx = fmaxf(mx, acc);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) a.rmax[r] = mx;
+}
+
+// e = exp(s - max[(r D + c) % n]) through fp64 (float32(math.Exp(float64(.))), tensor.go:414-419) and each row's sum of e
+__global__ __launch_bounds__(kBlock) void att_exp_kernel(AttArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= a.nrows) return;
+    const uint32_t n = (uint32_t)a.nrows;
+    const uint32_t m0 = (uint32_t)((r * a.D) % a.nrows);
+    float *sr = a.s + r * a.D;
+    float sum = 0.0f;
+    for (int c = lane; c < a.D; c += 64) {
+        const uint32_t m = (m0 + (uint32_t)c) % n;
+        const float e = (float)exp((double)(sr[c] - a.rmax[m]));
+        sr[c] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) a.rsum[r] = sum;
+}
+
+// a = e / sum[(r D + c) % n], z = a * x, enc = z We + be, logit += sum_f vx_f enc_f
+__global__ __launch_bounds__(kBlock) void att_enc_kernel(AttArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= a.nrows) return;
+    const bool vec = (a.d & 3) == 0;
+    const uint32_t n = (uint32_t)a.nrows;
+    const uint32_t m0 = (uint32_t)((r * a.D) % a.nrows);
+    const uint16_t *xr = a.x + r * a.D;
+    float *sr = a.s + r * a.D;
+    float contrib = 0.0f;
+    for (int f0 = 0; f0 < a.d; f0 += kFC) {
+        float acc[kFC];
+#pragma unroll
+        for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
+        for (int c = lane; c < a.D; c += 64) {
+            float av = sr[c];
+            if (f0 == 0) {  // the first chunk turns e into a in place (this lane owns the element in every chunk)
+                av = av / a.rsum[(m0 + (uint32_t)c) % n];
+                sr[c] = av;
+            }
+            const float zv = av * bf16_f32(xr[c]);
+            float wv[kFC];
+            load_w16(a.We, c, a.d, f0, vec, wv);
+#pragma unroll
+            for (int k = 0; k < kFC; k++) acc[k] = fmaf(zv, wv[k], acc[k]);
+        }
+        const float mine = reduce_pick(acc, lane);
+        float part = 0.0f;
+        if (lane < kFC && f0 + lane < a.d) {
+            const int64_t o = r * a.d + f0 + lane;
+            const float enc = mine + a.be[f0 + lane];
+            if (a.esum) a.esum[o] = a.first ? enc : a.esum[o] + enc;
+            part = a.vx[o] * enc;
+        }
+        contrib += wave_sum(part);
+    }
+    if (lane == 0) a.logit[r] = a.logit[r] + contrib;
+}
+
+struct LossArgs {
+    const float *logit, *tgt;  // tgt: the batch's rows
+    const float *vx, *esum;
+    int64_t nrows;
+    int d;
+    float inv_n;
+    float *gs, *loss, *vxe;
+};
+
+// loss and g from the full logit (the expressions of fm_forward_kernel), and vx + sum of enc: d logit / d vx, which
+// fm_accum_kernel reads in vx's place
+__global__ __launch_bounds__(kBlock) void att_loss_kernel(LossArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < a.nrows * a.d) a.vxe[i] = a.vx[i] + a.esum[i];
+    if (i >= a.nrows) return;
+    const float logit = a.logit[i];
+    const float y = (a.tgt[i] + 1.0f) * 0.5f;
+    a.loss[i] = fmaxf(logit, 0.0f) - logit * y + logf(1.0f + expf(-fabsf(logit)));
+    a.gs[i] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
+}
+
+// denc = g vx, dz = denc We^T, da = dz * x, gx = a * da and each row's sum of gx
+__global__ __launch_bounds__(kBlock) void att_bwd_gx_kernel(AttArgs a) {
+    __shared__ float sh[kBlock / 64][kMaxFactors];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
+    const bool live = r < a.nrows;
+    for (int f = lane; f < kMaxFactors; f += 64) sh[w][f] = live && f < a.d ? a.gs[r] * a.vx[r * a.d + f] : 0.0f;
+    __syncthreads();
+    if (!live) return;
+    const bool vec = (a.d & 3) == 0;
+    const uint16_t *xr = a.x + r * a.D;
+    const float *ar = a.s + r * a.D;
+    float *gr = a.gx + r * a.D;
+    float sum = 0.0f;
+    for (int c = lane; c < a.D; c += 64) {
+        float dz = 0.0f;
+        for (int f0 = 0; f0 < a.d; f0 += kFC) {
+            float wv[kFC];
+            load_w16(a.We, c, a.d, f0, vec, wv);
+#pragma unroll
+            for (int k = 0; k < kFC; k++) dz = fmaf(sh[w][f0 + k], wv[k], dz);
+        }
+        const float g = ar[c] * (dz * bf16_f32(xr[c]));
+        gr[c] = g;
+        sum += g;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) a.sumdx[r] = sum;
+}
+
+// ds = gx - a * sumdx[(r D + c) % n], dh = ds H^T, dpre = (pre > 0) dh
+__global__ __launch_bounds__(kBlock) void att_bwd_ds_kernel(AttArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= a.nrows) return;
+    const uint32_t n = (uint32_t)a.nrows;
+    const uint32_t m0 = (uint32_t)((r * a.D) % a.nrows);
+    const float *ar = a.s + r * a.D;
+    float *gr = a.gx + r * a.D;
+    for (int c = lane; c < a.D; c += 64) {  // gx.sub(y.mul(sumdx)): the product is rounded before the difference
+        const float t = ar[c] * a.sumdx[(m0 + (uint32_t)c) % n];
+        gr[c] = gr[c] - t;
+    }
+    for (int f0 = 0; f0 < a.d; f0 += kFC) {  // this lane re-reads the elements it wrote
+        float acc[kFC];
+#pragma unroll
+        for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
+        for (int c = lane; c < a.D; c += 64) {
+            const float dsv = gr[c];
+            // chunk entries past d re-read H's last row into sums nobody keeps: no per-entry condition to carry
+            const float *hp = a.H + c;
+#pragma unroll
+            for (int k = 0; k < kFC; k++) acc[k] = fmaf(dsv, hp[min(f0 + k, a.d - 1) * a.D], acc[k]);
+        }
+        const float mine = reduce_pick(acc, lane);
+        if (lane < kFC && f0 + lane < a.d) {
+            const int64_t o = r * a.d + f0 + lane;
+            a.dpre[o] = a.h[o] > 0.0f ? mine : 0.0f;
+        }
+    }
+}
+
+// The parameter gradients that reduce over the batch: dWe = z^T denc, dWa = x^T dpre, dH = h^T ds, and the bias sums as one
+// more column (c = D) whose z and x are 1.  Block (column tile of 64, factor chunk of 16, row segment): wave w takes every
+// fourth row of the segment in ascending order, the four waves' sums are added in wave order, and the kGradSegs segment sums
+// are added in segment order by the optimizer pass: the order depends on the shapes alone, no atomics.
+__global__ __launch_bounds__(kBlock) void att_grad_kernel(AttArgs a) {
+    __shared__ float sh[kBlock / 64][kFC][64];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int c = blockIdx.x * 64 + lane;
+    const int f0 = blockIdx.y * kFC;
+    const int seg = blockIdx.z;
+    const int64_t rps = (a.nrows + kGradSegs - 1) / kGradSegs;
+    const int64_t r_lo = seg * rps, r_hi = r_lo + rps < a.nrows ? r_lo + rps : a.nrows;
+    float aWe[kFC], aWa[kFC], aH[kFC];
+#pragma unroll
+    for (int k = 0; k < kFC; k++) aWe[k] = aWa[k] = aH[k] = 0.0f;
+    for (int64_t r = r_lo + w; r < r_hi; r += kBlock / 64) {
+        float xv = 0.0f, zv = 0.0f, dsv = 0.0f;
+        if (c < a.D) {
+            xv = bf16_f32(a.x[r * a.D + c]);
+            zv = a.s[r * a.D + c] * xv;
+            dsv = a.gx[r * a.D + c];
+        } else if (c == a.D) {
+            xv = zv = 1.0f;
+        }
+        const float g = a.gs[r];
+#pragma unroll
+        for (int k = 0; k < kFC; k++) {
+            if (f0 + k < a.d) {
+                const int64_t o = r * a.d + f0 + k;
+                aWe[k] = fmaf(zv, g * a.vx[o], aWe[k]);
+                aWa[k] = fmaf(xv, a.dpre[o], aWa[k]);
+                aH[k] = fmaf(dsv, a.h[o], aH[k]);
+            }
+        }
+    }
+    const int64_t nH = (int64_t)a.d * a.D, nW = (int64_t)(a.D + 1) * a.d;
+    float *gH = a.gpart + seg * a.gstride, *gWa = gH + nH, *gWe = gWa + nW;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        if (t) __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kFC; k++) sh[w][k][lane] = t == 0 ? aH[k] : t == 1 ? aWa[k] : aWe[k];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kFC / (kBlock / 64); j++) {
+            const int k = w + j * (kBlock / 64);
+            const float v = ((sh[0][k][lane] + sh[1][k][lane]) + sh[2][k][lane]) + sh[3][k][lane];
+            if (f0 + k >= a.d) continue;
+            if (t == 0) {
+                if (c < a.D) gH[(int64_t)(f0 + k) * a.D + c] = v;
+            } else if (c <= a.D) {
+                (t == 1 ? gWa : gWe)[(int64_t)c * a.d + f0 + k] = v;
+            }
+        }
+    }
+}
+
+// The dense step of the branch's tensors (blockIdx.y = tensor number in Parameters() order: per field H, Wa, ba, We, be), each
+// as its own tensor: the FMA body / unfused tail split lies at its own last len % 16 elements.  The descriptors are read
+// from device memory, so no by-value argument block is indexed by a runtime number.
+template <bool ADAM>
+__global__ __launch_bounds__(kBlock) void fm_dense_opt_kernel(const DenseDesc *descs, float wd, float lr, float c1, float c2) {
+    const DenseDesc t = descs[blockIdx.y];
+    const int64_t L = t.len;
+    const int64_t e0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 4;
+    if (e0 >= L) return;
+    const int64_t body = L - L % 16;
+    float p[4], m[4], v[4], g[4];
+    const bool full = e0 + 4 <= L;
+    if (full) {
+        const float4 p4 = *reinterpret_cast<const float4 *>(t.p + e0);
+        p[0] = p4.x, p[1] = p4.y, p[2] = p4.z, p[3] = p4.w;
+        if (ADAM) {
+            const float4 m4 = *reinterpret_cast<const float4 *>(t.m + e0);
+            const float4 v4 = *reinterpret_cast<const float4 *>(t.v + e0);
+            m[0] = m4.x, m[1] = m4.y, m[2] = m4.z, m[3] = m4.w;
+            v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            p[k] = e0 + k < L ? t.p[e0 + k] : 0.0f;
+            m[k] = ADAM && e0 + k < L ? t.m[e0 + k] : 0.0f;
+            v[k] = ADAM && e0 + k < L ? t.v[e0 + k] : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float gk = 0.0f;
+        if (e0 + k < L) {
+#pragma unroll
+            for (int s = 0; s < kGradSegs; s++) gk += t.g[s * t.gstride + e0 + k];
+        }
+        g[k] = gk;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) opt_elem<ADAM>(p[k], m[k], v[k], g[k], e0 + k < body, wd, lr, c1, c2);
+    if (full) {
+        *reinterpret_cast<float4 *>(t.p + e0) = make_float4(p[0], p[1], p[2], p[3]);
+        if (ADAM) {
+            *reinterpret_cast<float4 *>(t.m + e0) = make_float4(m[0], m[1], m[2], m[3]);
+            *reinterpret_cast<float4 *>(t.v + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (e0 + k < L) {
+                t.p[e0 + k] = p[k];
+                if (ADAM) {
+                    t.m[e0 + k] = m[k];
+                    t.v[e0 + k] = v[k];
+                }
+            }
+        }
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------
 
 // math32.Pow(x, y) for a positive integer y (chewxy/math32 pow.go, the float32 statement of Go's math.Pow):
@@ -485,6 +899,75 @@ int32_t build_plan(gorse_fm *h, int32_t bs) {
     return GORSE_OK;
 }
 
+// ---- the embedding branch: host side -----------------------------------------------------
+
+inline unsigned row_grid(int64_t nrows) { return (unsigned)ceil_div(nrows, kBlock / 64); }
+
+// per-batch buffers of the branch for batches of up to `rows` rows; train: also what the backward needs
+int32_t ensure_branch(gorse_fm *h, int64_t rows, bool train) {
+    int maxD = 1;
+    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
+    GORSE_TRY(h->a_rmax.ensure((size_t)rows));
+    GORSE_TRY(h->a_rsum.ensure((size_t)rows));
+    GORSE_TRY(h->a_logit.ensure((size_t)rows));
+    for (int k = 0; k < h->n_fields; k++) {
+        // scoring keeps nothing per field: every field works in field 0's buffers
+        Field &F = h->fld[train ? k : 0];
+        GORSE_TRY(F.h.ensure((size_t)rows * h->d));
+        GORSE_TRY(F.a.ensure((size_t)rows * (train ? F.D : maxD)));
+    }
+    if (!train) return GORSE_OK;
+    GORSE_TRY(h->a_sumdx.ensure((size_t)rows));
+    GORSE_TRY(h->a_gx.ensure((size_t)rows * maxD));
+    GORSE_TRY(h->a_dpre.ensure((size_t)rows * h->d));
+    GORSE_TRY(h->a_esum.ensure((size_t)rows * h->d));
+    GORSE_TRY(h->a_vxe.ensure((size_t)rows * h->d));
+    return GORSE_OK;
+}
+
+AttArgs branch_args(gorse_fm *h, int k, const uint16_t *x, int64_t nrows, const float *vx, bool train) {
+    Field &F = h->fld[k], &S = h->fld[train ? k : 0];
+    AttArgs a{};
+    a.x = x;
+    a.H = F.p.p + F.off[0], a.Wa = F.p.p + F.off[1], a.ba = F.p.p + F.off[2], a.We = F.p.p + F.off[3], a.be = F.p.p + F.off[4];
+    a.nrows = nrows, a.D = F.D, a.d = h->d;
+    a.h = S.h.p, a.s = S.a.p;
+    a.rmax = h->a_rmax.p, a.rsum = h->a_rsum.p;
+    a.vx = vx;
+    a.logit = h->a_logit.p;
+    a.esum = train ? h->a_esum.p : nullptr;
+    a.first = k == 0;
+    a.gs = h->gs.p, a.gx = h->a_gx.p, a.sumdx = h->a_sumdx.p, a.dpre = h->a_dpre.p;
+    a.gpart = F.gpart.p, a.gstride = (int64_t)F.gstride();
+    return a;
+}
+
+// the three forward launches of one field on the batch
+int32_t branch_forward(gorse_fm *h, const AttArgs &a) {
+    const unsigned grid = row_grid(a.nrows);
+    att_score_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
+    att_exp_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
+    att_enc_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+int32_t branch_backward(gorse_fm *h, const AttArgs &a) {
+    const unsigned grid = row_grid(a.nrows);
+    att_bwd_gx_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
+    att_bwd_ds_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
+    att_grad_kernel<<<dim3((unsigned)ceil_div(a.D + 1, 64), (unsigned)ceil_div(a.d, kFC), kGradSegs), dim3(kBlock), 0, h->s>>>(a);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+int32_t check_field(const gorse_fm *h, int32_t field) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (field < 0 || field >= h->n_fields)
+        return fail(GORSE_ERR_INVALID, "embedding field %d out of range [0,%d)", field, h->n_fields);
+    return GORSE_OK;
+}
+
 }  // namespace fm
 }  // namespace gorse
 
@@ -584,6 +1067,106 @@ extern "C" int32_t gorse_fm_set_train(gorse_fm *h, int64_t n, int32_t width, con
     h->n = n;
     h->width = width;
     h->plan_bs = 0;  // the batches' feature order is rebuilt for the new set
+    for (int k = 0; k < h->n_fields; k++) {  // the embeddings belong to the set they were uploaded for
+        h->fld[k].x.release();
+        h->fld[k].have_x = false;
+    }
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_set_embedding_dims(gorse_fm *h, int32_t n_fields, const int32_t *dims) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (n_fields < 0 || n_fields > fm::kMaxFields)
+        return fail(GORSE_ERR_INVALID, "n_fields must be in 0..%d (got %d)", fm::kMaxFields, n_fields);
+    if (n_fields > 0 && !dims) return fail(GORSE_ERR_INVALID, "dims is NULL");
+    for (int k = 0; k < n_fields; k++)
+        if (dims[k] < 1 || dims[k] > fm::kMaxEmbDim)
+            return fail(GORSE_ERR_INVALID, "embedding dimension %d of field %d outside 1..%d", dims[k], k, fm::kMaxEmbDim);
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    for (auto &F : h->fld) {
+        for (auto *b : {&F.p, &F.m, &F.v, &F.gpart, &F.h, &F.a}) b->release();
+        F.x.release();
+        F.have_x = false;
+        F.D = 0;
+    }
+    h->n_fields = 0;
+    h->dense_blocks = 0;
+    std::vector<fm::DenseDesc> descs;
+    for (int k = 0; k < n_fields; k++) {
+        fm::Field &F = h->fld[k];
+        F.D = dims[k];
+        const size_t D = (size_t)F.D, d = (size_t)h->d;
+        const size_t lens[5] = {d * D, D * d, d, D * d, d};  // H, Wa, ba, We, be
+        size_t o = 0;
+        for (int t = 0; t < 5; t++) {
+            F.off[t] = o;
+            F.len[t] = lens[t];
+            o += (lens[t] + 3) / 4 * 4;
+        }
+        F.total = o;
+        for (auto *b : {&F.p, &F.m, &F.v}) {
+            GORSE_TRY(b->alloc(F.total));
+            GORSE_HIP_CHECK(hipMemsetAsync(b->p, 0, F.total * sizeof(float), h->s));
+        }
+        GORSE_TRY(F.gpart.alloc(F.gstride() * fm::kGradSegs));
+        // gradient blocks of one segment: dH | dWa, dba | dWe, dbe
+        const size_t goff[5] = {0, lens[0], lens[0] + lens[1], lens[0] + lens[1] + lens[2], lens[0] + 2 * lens[1] + lens[2]};
+        for (int t = 0; t < 5; t++) {
+            descs.push_back({F.p.p + F.off[t], F.m.p + F.off[t], F.v.p + F.off[t], F.gpart.p + goff[t], (int64_t)lens[t],
+                             (int64_t)F.gstride()});
+            h->dense_blocks = std::max<int64_t>(h->dense_blocks, ceil_div(ceil_div((int64_t)lens[t], 4), fm::kBlock));
+        }
+    }
+    if (n_fields > 0) {
+        GORSE_TRY(h->descs.alloc(descs.size()));
+        GORSE_HIP_CHECK(hipMemcpy(h->descs.p, descs.data(), descs.size() * sizeof(fm::DenseDesc), hipMemcpyHostToDevice));
+    }
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    h->n_fields = n_fields;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_set_embedding_params(gorse_fm *h, int32_t field, const float *H, const float *Wa, const float *ba,
+                                                 const float *We, const float *be) {
+    GORSE_TRY(fm::check_field(h, field));
+    if (!H || !Wa || !ba || !We || !be) return fail(GORSE_ERR_INVALID, "H / Wa / ba / We / be is NULL");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    fm::Field &F = h->fld[field];
+    const float *src[5] = {H, Wa, ba, We, be};
+    for (int t = 0; t < 5; t++)
+        GORSE_HIP_CHECK(hipMemcpy(F.p.p + F.off[t], src[t], F.len[t] * sizeof(float), hipMemcpyHostToDevice));
+    for (auto *b : {&F.m, &F.v}) GORSE_HIP_CHECK(hipMemsetAsync(b->p, 0, F.total * sizeof(float), h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_get_embedding_params(gorse_fm *h, int32_t field, float *H, float *Wa, float *ba, float *We, float *be) {
+    GORSE_TRY(fm::check_field(h, field));
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    fm::Field &F = h->fld[field];
+    float *dst[5] = {H, Wa, ba, We, be};
+    for (int t = 0; t < 5; t++)
+        if (dst[t]) GORSE_HIP_CHECK(hipMemcpy(dst[t], F.p.p + F.off[t], F.len[t] * sizeof(float), hipMemcpyDeviceToHost));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_set_train_embeddings(gorse_fm *h, int32_t field, const uint16_t *emb) {
+    GORSE_TRY(fm::check_field(h, field));
+    if (h->n <= 0) return fail(GORSE_ERR_INVALID, "no training set (gorse_fm_set_train)");
+    if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
+    fm::Field &F = h->fld[field];
+    // n x D is formed in 64 bits everywhere; what bounds it is the device's memory
+    if (h->n > INT64_MAX / (int64_t)(F.D * sizeof(uint16_t))) return fail(GORSE_ERR_INVALID, "n x D overflows");
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    F.have_x = false;
+    const size_t ne = (size_t)h->n * (size_t)F.D;
+    GORSE_TRY(F.x.alloc(ne));
+    GORSE_HIP_CHECK(hipMemcpy(F.x.p, emb, ne * sizeof(uint16_t), hipMemcpyHostToDevice));
+    F.have_x = true;
     return GORSE_OK;
 }
 
@@ -593,8 +1176,12 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
     if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
     if (optimizer != GORSE_OPT_SGD && optimizer != GORSE_OPT_ADAM) return fail(GORSE_ERR_INVALID, "unknown optimizer %d", optimizer);
     if (h->n <= 0) return fail(GORSE_ERR_INVALID, "no training set (gorse_fm_set_train)");
+    for (int k = 0; k < h->n_fields; k++)
+        if (!h->fld[k].have_x)
+            return fail(GORSE_ERR_INVALID, "embedding field %d has no training embeddings (gorse_fm_set_train_embeddings)", k);
     GORSE_HIP_CHECK(hipSetDevice(h->device));
     if (h->plan_bs != batch_size) GORSE_TRY(fm::build_plan(h, batch_size));
+    if (h->n_fields > 0) GORSE_TRY(fm::ensure_branch(h, std::min<int64_t>(h->n, batch_size), true));
     GORSE_HIP_CHECK(hipMemsetAsync(h->cost.p, 0, sizeof(float), h->s));
     const int64_t nb = ceil_div(h->n, batch_size);
     const bool adam = optimizer == GORSE_OPT_ADAM;
@@ -628,13 +1215,28 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
         f.row0 = r0, f.nrows = nr, f.width = h->width, f.d = h->d;
         f.inv_n = 1.0f / (float)nr;
         f.gs = h->gs.p, f.loss = h->loss.p, f.vx = h->vx.p;
+        if (h->n_fields > 0) f.out = h->a_logit.p;
         GORSE_TRY(fm::launch_forward<true>(h, f));
+        if (h->n_fields > 0) {
+            // the branch's contribution joins the logit before loss and g are formed (fm.go:127-132)
+            for (int e = 0; e < h->n_fields; e++)
+                GORSE_TRY(fm::branch_forward(h, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true)));
+            fm::LossArgs l{};
+            l.logit = h->a_logit.p, l.tgt = h->tgt.p + r0;
+            l.vx = h->vx.p, l.esum = h->a_esum.p;
+            l.nrows = nr, l.d = h->d, l.inv_n = f.inv_n;
+            l.gs = h->gs.p, l.loss = h->loss.p, l.vxe = h->a_vxe.p;
+            fm::att_loss_kernel<<<dim3((unsigned)ceil_div(nr * h->d, fm::kBlock)), dim3(fm::kBlock), 0, h->s>>>(l);
+            for (int e = 0; e < h->n_fields; e++)
+                GORSE_TRY(fm::branch_backward(h, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true)));
+        }
         fm::AccArgs a{};
         a.uniq = h->uniq.p, a.seg = h->seg.p, a.pos = h->pos.p;
         a.slot0 = h->uoff[(size_t)k], a.nslots = h->uoff[(size_t)k + 1] - h->uoff[(size_t)k];
         a.val = h->val.p + r0 * h->width;
         a.V = h->V.p;
-        a.gs = h->gs.p, a.loss = h->loss.p, a.vx = h->vx.p;
+        a.gs = h->gs.p, a.loss = h->loss.p;
+        a.vx = h->n_fields > 0 ? h->a_vxe.p : h->vx.p;  // with fields: vx + sum of enc, so that dV carries g * enc
         a.nrows = nr, a.width = h->width, a.d = h->d;
         a.tag_hi = tag_hi, a.tag = h->tag.p;
         a.gV = h->gV.p, a.gW = h->gW.p, a.gB = h->gB.p, a.cost = h->cost.p;
@@ -647,6 +1249,13 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
         } else {
             o.lr = lr;
             fm::fm_opt_kernel<false><<<dim3(opt_grid), dim3(fm::kBlock), 0, h->s>>>(o);
+        }
+        if (h->n_fields > 0) {
+            const dim3 dg((unsigned)h->dense_blocks, (unsigned)(5 * h->n_fields));
+            if (adam)
+                fm::fm_dense_opt_kernel<true><<<dg, dim3(fm::kBlock), 0, h->s>>>(h->descs.p, wd, o.lr, o.c1, o.c2);
+            else
+                fm::fm_dense_opt_kernel<false><<<dg, dim3(fm::kBlock), 0, h->s>>>(h->descs.p, wd, o.lr, o.c1, o.c2);
         }
         GORSE_HIP_CHECK(hipGetLastError());
         h->step++;
@@ -662,6 +1271,8 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
 extern "C" int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices, const float *values,
                                     float *logits_out) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (h->n_fields > 0)
+        return fail(GORSE_ERR_INVALID, "the model has embedding fields: score it with gorse_fm_predict_embeddings");
     GORSE_TRY(fm::check_rows(h, n, width, indices, values, false));
     if (n == 0) return GORSE_OK;
     if (!logits_out) return fail(GORSE_ERR_INVALID, "logits_out is NULL");
@@ -679,6 +1290,57 @@ extern "C" int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const
     f.out = h->p_out.p;
     GORSE_TRY(fm::launch_forward<false>(h, f));
     GORSE_HIP_CHECK(hipMemcpyAsync(logits_out, h->p_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_predict_embeddings(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices, const float *values,
+                                               const uint16_t *const *emb, int32_t batch_size, float *logits_out) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (h->n_fields == 0) return gorse_fm_predict(h, n, width, indices, values, logits_out);
+    if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
+    GORSE_TRY(fm::check_rows(h, n, width, indices, values, false));
+    if (n == 0) return GORSE_OK;
+    if (!logits_out) return fail(GORSE_ERR_INVALID, "logits_out is NULL");
+    if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
+    for (int k = 0; k < h->n_fields; k++)
+        if (!emb[k]) return fail(GORSE_ERR_INVALID, "emb[%d] is NULL", k);
+    GORSE_HIP_CHECK(hipSetDevice(h->device));
+    const int64_t bs = std::min<int64_t>(n, batch_size);
+    const size_t ne = (size_t)n * width;
+    int maxD = 1;
+    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
+    GORSE_TRY(h->p_idx.ensure(ne));
+    GORSE_TRY(h->p_val.ensure(ne));
+    GORSE_TRY(h->p_x.ensure((size_t)bs * maxD));
+    GORSE_TRY(h->p_vx.ensure((size_t)bs * h->d));
+    GORSE_TRY(h->p_gs.ensure((size_t)bs));
+    GORSE_TRY(h->p_loss.ensure((size_t)bs));
+    if ((size_t)bs > h->p_zero.n) {
+        GORSE_TRY(h->p_zero.alloc((size_t)bs));
+        GORSE_HIP_CHECK(hipMemsetAsync(h->p_zero.p, 0, (size_t)bs * sizeof(float), h->s));
+    }
+    GORSE_TRY(fm::ensure_branch(h, bs, false));
+    GORSE_HIP_CHECK(hipMemcpyAsync(h->p_idx.p, indices, ne * 4, hipMemcpyHostToDevice, h->s));
+    GORSE_HIP_CHECK(hipMemcpyAsync(h->p_val.p, values, ne * 4, hipMemcpyHostToDevice, h->s));
+    // BatchInternalPredict's slices (fm.go:168-176): the softmax's indexing makes the slice length part of the result
+    for (int64_t r0 = 0; r0 < n; r0 += bs) {
+        const int64_t nr = std::min<int64_t>(n, r0 + bs) - r0;
+        fm::FwdArgs f{};
+        // the training instantiation writes vx; its loss and g (against zero targets) go to buffers nobody reads
+        f.idx = h->p_idx.p + r0 * width, f.val = h->p_val.p + r0 * width, f.tgt = h->p_zero.p;
+        f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
+        f.row0 = 0, f.nrows = nr, f.width = width, f.d = h->d;
+        f.inv_n = 1.0f;
+        f.out = h->a_logit.p, f.gs = h->p_gs.p, f.loss = h->p_loss.p, f.vx = h->p_vx.p;
+        GORSE_TRY(fm::launch_forward<true>(h, f));
+        for (int k = 0; k < h->n_fields; k++) {
+            const int64_t D = h->fld[k].D;
+            GORSE_HIP_CHECK(hipMemcpyAsync(h->p_x.p, emb[k] + r0 * D, (size_t)(nr * D) * sizeof(uint16_t), hipMemcpyHostToDevice, h->s));
+            GORSE_TRY(fm::branch_forward(h, fm::branch_args(h, k, h->p_x.p, nr, h->p_vx.p, false)));
+        }
+        GORSE_HIP_CHECK(hipMemcpyAsync(logits_out + r0, h->a_logit.p, (size_t)nr * 4, hipMemcpyDeviceToHost, h->s));
+    }
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
     return GORSE_OK;
 }

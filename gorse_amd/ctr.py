@@ -8,6 +8,7 @@ import numpy as np
 from . import cf
 
 _f32p, _i32p, _i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_u16p = C.POINTER(C.c_uint16)
 SGD, Adam = 0, 1
 _configured = False
 
@@ -29,6 +30,8 @@ def host():
         H.gh_fm_evaluate.argtypes = [C.c_void_p, C.c_void_p, _f32p]
         H.gh_fm_log.argtypes = [C.c_void_p, _i32p, _f32p, _f32p, C.c_int32]
         H.gh_fm_params.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
+        H.gh_ctr_dataset_set_embeddings.argtypes = [C.c_void_p, C.c_int32, _i32p, C.POINTER(_u16p)]
+        H.gh_fm_field_params.argtypes = [C.c_void_p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]
         _configured = True
     return H
 
@@ -77,6 +80,7 @@ class Dataset:
         self.n_features = int(n_features)
         self.p = C.c_void_p(host().gh_ctr_dataset_new(self.n_features))
         self.n = 0
+        self.dims = ()
         if rows is not None:
             self.add_rows(*rows)
 
@@ -96,17 +100,30 @@ class Dataset:
                                   vv.ctypes.data_as(_f32p), tt.ctypes.data_as(_f32p))
         self.n += tt.size
 
+    def set_embeddings(self, embs):
+        """item embeddings of the rows added so far: one Count() x D matrix of bf16 bit patterns (uint16) per field, an
+        all-zero row where a sample has none; an empty list removes them"""
+        embs = [np.ascontiguousarray(e, np.uint16) for e in embs]
+        if any(e.ndim != 2 or e.shape[0] != self.n for e in embs):
+            raise ValueError("one Count() x D matrix per field")
+        dims = np.array([e.shape[1] for e in embs] or [0], np.int32)
+        ptrs = (_u16p * max(1, len(embs)))(*[e.ctypes.data_as(_u16p) for e in embs])
+        host().gh_ctr_dataset_set_embeddings(self.p, len(embs), dims.ctypes.data_as(_i32p), ptrs)
+        self.dims = tuple(int(e.shape[1]) for e in embs)
+
     def Count(self):
         return self.n
 
 
 class FM:
-    """ctr.AFM without item embeddings (model/ctr/fm.go), trained and scored on the device."""
+    """ctr.AFM (model/ctr/fm.go), trained and scored on the device; a training set with item embeddings (Dataset.set_embeddings)
+    trains the attention branch as well."""
 
     def __init__(self, nFactors=8, nEpochs=10, batchSize=1024, lr=0.01, reg=0.0, optimizer=Adam, seed=0):
         self.d = int(nFactors)
         self.p = C.c_void_p(host().gh_fm_new(self.d, nEpochs, batchSize, lr, reg, optimizer, seed))
         self.nf = 0
+        self.dims = ()
 
     def __del__(self):
         if getattr(self, "p", None):
@@ -120,6 +137,7 @@ class FM:
         if rc != 0:
             raise cf.HostError(rc)
         self.nf = train.n_features
+        self.dims = train.dims
         return Score(s)
 
     def Evaluate(self, test):
@@ -142,3 +160,10 @@ class FM:
         V = np.zeros((self.nf, self.d), np.float32)
         host().gh_fm_params(self.p, B.ctypes.data_as(_f32p), W.ctypes.data_as(_f32p), V.ctypes.data_as(_f32p))
         return B[0], W, V
+
+    def field_params(self, field):
+        """(H, Wa, ba, We, be) of one embedding field after Fit"""
+        D, d = self.dims[field], self.d
+        arrs = [np.zeros(shp, np.float32) for shp in ((d, D), (D, d), (d,), (D, d), (d,))]
+        host().gh_fm_field_params(self.p, field, *[a.ctypes.data_as(_f32p) for a in arrs])
+        return tuple(arrs)

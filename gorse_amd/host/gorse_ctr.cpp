@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <stdexcept>
 
 #include "gorse_cf.hpp"
 
@@ -94,8 +95,33 @@ std::vector<float> FM::BatchInternalPredict(const Dataset &ds, const std::vector
     std::vector<int32_t> idx;
     std::vector<float> val;
     pad_rows(ds, rows, width, idx, val);
-    check(gorse_fm_predict(h_, (int64_t)rows.size(), width, idx.data(), val.data(), out.data()));
+    if (fields.empty()) {
+        check(gorse_fm_predict(h_, (int64_t)rows.size(), width, idx.data(), val.data(), out.data()));
+        return out;
+    }
+    // the rows' embeddings gathered per field (convertToTensors); a set without them scores with absent (zero) embeddings
+    if (!ds.emb_dims.empty() && ds.emb_dims.size() != fields.size()) throw std::invalid_argument("embedding fields differ from the fitted model's");
+    std::vector<std::vector<uint16_t>> emb(fields.size());
+    std::vector<const uint16_t *> ptrs(fields.size());
+    for (size_t k = 0; k < fields.size(); k++) {
+        const size_t D = (size_t)fields[k].D;
+        if (!ds.emb_dims.empty() && ds.emb_dims[k] != fields[k].D) throw std::invalid_argument("embedding dimension differs from the fitted model's");
+        emb[k].assign(rows.size() * D, 0);
+        if (!ds.emb_dims.empty())
+            for (size_t r = 0; r < rows.size(); r++)
+                std::copy(ds.emb[k].begin() + (size_t)rows[r] * D, ds.emb[k].begin() + ((size_t)rows[r] + 1) * D, emb[k].begin() + r * D);
+        ptrs[k] = emb[k].data();
+    }
+    check(gorse_fm_predict_embeddings(h_, (int64_t)rows.size(), width, idx.data(), val.data(), ptrs.data(), batchSize_, out.data()));
     return out;
+}
+
+void FM::ReadBack() {
+    check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
+    for (size_t k = 0; k < fields.size(); k++) {
+        Field &f = fields[k];
+        check(gorse_fm_get_embedding_params(h_, (int32_t)k, f.H.data(), f.Wa.data(), f.ba.data(), f.We.data(), f.be.data()));
+    }
 }
 
 Score EvaluateClassification(FM &m, const Dataset &test) {
@@ -121,7 +147,35 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
     B = 0;
     rng.NormalMatrix(nf_, 1, 0, 0.01f, W);
     rng.NormalMatrix(nf_, nFactors_, 0, 0.01f, V);
+    // the embedding fields (fm.go:257-264): nn.NewAttention draws its Linear (Wa ~ Uniform(+-1/sqrt(D)), ba = 0), then
+    // H ~ Normal(0, 0.01); nn.NewLinear draws We the same way, be = 0 (layers.go:42-48, 166-171)
+    fields.assign(train.emb_dims.size(), Field{});
+    if (!train.emb_dims.empty()) {
+        if (train.emb.size() != train.emb_dims.size()) throw std::invalid_argument("one embedding matrix per field");
+        for (size_t k = 0; k < fields.size(); k++)
+            if (train.emb[k].size() != (size_t)train.Count() * (size_t)train.emb_dims[k])
+                throw std::invalid_argument("an embedding matrix must hold Count() x D values");
+    }
+    check(gorse_fm_set_embedding_dims(h_, (int32_t)train.emb_dims.size(), train.emb_dims.data()));
+    auto uniform = [&](size_t n, float bound, std::vector<float> &out) {
+        out.resize(n);
+        for (auto &x : out) x = (float)rng.Float64() * (2 * bound) - bound;
+    };
+    for (size_t k = 0; k < fields.size(); k++) {
+        Field &f = fields[k];
+        f.D = train.emb_dims[k];
+        const float bound = 1.0f / std::sqrt((float)f.D);
+        uniform((size_t)f.D * nFactors_, bound, f.Wa);
+        f.ba.assign((size_t)nFactors_, 0.0f);
+        rng.NormalMatrix(nFactors_, f.D, 0, 0.01f, f.H);
+        uniform((size_t)f.D * nFactors_, bound, f.We);
+        f.be.assign((size_t)nFactors_, 0.0f);
+    }
     check(gorse_fm_set_params(h_, B, W.data(), V.data()));
+    for (size_t k = 0; k < fields.size(); k++) {
+        const Field &f = fields[k];
+        check(gorse_fm_set_embedding_params(h_, (int32_t)k, f.H.data(), f.Wa.data(), f.ba.data(), f.We.data(), f.be.data()));
+    }
     log.clear();
 
     Score score = EvaluateClassification(*this, test);
@@ -135,6 +189,7 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
     std::vector<float> val;
     pad_rows(train, all, width, idx, val);
     check(gorse_fm_set_train(h_, train.Count(), width, idx.data(), val.data(), train.target.data()));
+    for (size_t k = 0; k < fields.size(); k++) check(gorse_fm_set_train_embeddings(h_, (int32_t)k, train.emb[k].data()));
 
     const int32_t opt = optimizer_ == 0 ? GORSE_OPT_SGD : GORSE_OPT_ADAM;
     for (int epoch = 1; epoch <= nEpochs_; epoch++) {
@@ -142,7 +197,7 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
         const int32_t rc = (cfg.cancel && *cfg.cancel) ? GORSE_ERR_CANCELLED
                                                        : gorse_fm_epoch(h_, batchSize_, opt, lr_, reg_, cfg.cancel, &cost);
         if (rc == GORSE_ERR_CANCELLED) {  // "fit AFM canceled": Score{}, the tensors keep the steps taken
-            check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
+            ReadBack();
             return Score{};
         }
         check(rc);
@@ -160,7 +215,7 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
             }
         }
     }
-    check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
+    ReadBack();  // in Parameters() order: B, V, W, then per field H, Wa, ba, We, be
     return score;
 }
 

@@ -1,4 +1,4 @@
-// gorse_ctr.hpp -- host mirror of the reference's model/ctr factorization machine (ctr.AFM without the item-embedding branch,
+// gorse_ctr.hpp -- host mirror of the reference's model/ctr factorization machine (ctr.AFM with its item-embedding branch,
 // model/ctr/fm.go) and of its classification metrics (model/ctr/evaluator.go).  The numerics run on the device through the
 // gorse_fm_* entry points of the C ABI; this file holds AFM.Fit's loop (evaluation schedule, NaN stop, patience, cancel) and
 // EvaluateClassification as written.
@@ -23,6 +23,10 @@ struct Dataset {
     std::vector<int32_t> indices;
     std::vector<float> values;
     std::vector<float> target;
+    // item embeddings (GetItemEmbeddingDim, fm.go:555-561): per field its dimension and a Count() x D matrix of bf16 bit
+    // patterns, an all-zero row where a sample has none; empty for a set without embeddings
+    std::vector<int32_t> emb_dims;
+    std::vector<std::vector<uint16_t>> emb;
     int64_t Count() const { return (int64_t)target.size(); }
     int MaxLen() const;
     void Add(const int32_t *idx, const float *val, int len, float t);
@@ -53,12 +57,17 @@ class FM {
     ~FM();
     FM(const FM &) = delete;
     FM &operator=(const FM &) = delete;
-    // AFM.Fit (fm.go:307-417) for a training set without item embeddings
+    // AFM.Fit (fm.go:307-417); a training set with item embeddings trains the attention branch as well
     Score Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg);
     // BatchInternalPredict (fm.go:156-178) of rows [0, ds.Count()) that satisfy keep (or all rows)
     std::vector<float> BatchInternalPredict(const Dataset &ds, const std::vector<int64_t> &rows);
     float B = 0;
     std::vector<float> W, V;          // the parameters after Fit (copied back, as into the nn tensors)
+    struct Field {                    // one embedding field's tensors in Parameters() order (fm.go:136-146)
+        int32_t D = 0;
+        std::vector<float> H, Wa, ba, We, be;
+    };
+    std::vector<Field> fields;
     std::vector<EvalRecord> log;      // every evaluation of the last Fit, epoch 0 first
 
    private:
@@ -68,6 +77,7 @@ class FM {
     int64_t seed_;
     int device_;
     int numDimension_ = 0;
+    void ReadBack();
     int64_t nf_ = 0;
     gorse_fm *h_ = nullptr;
 };

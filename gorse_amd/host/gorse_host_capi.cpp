@@ -998,6 +998,28 @@ void gh_ctr_dataset_add(void *d, int64_t n, const int64_t *indptr, const int32_t
     for (int64_t i = 0; i < n; i++)
         ((ctr::Dataset *)d)->Add(idx + indptr[i], val + indptr[i], (int)(indptr[i + 1] - indptr[i]), target[i]);
 }
+// item embeddings of the rows added so far: per field its dimension and a Count() x D matrix of bf16 bit patterns (zero
+// rows where a sample has none); n_fields = 0 removes them.  Returns 0, or 1 when called before the rows are complete.
+int32_t gh_ctr_dataset_set_embeddings(void *d, int32_t n_fields, const int32_t *dims, const uint16_t *const *emb) {
+    auto *ds = (ctr::Dataset *)d;
+    ds->emb_dims.assign(dims, dims + n_fields);
+    ds->emb.assign((size_t)n_fields, {});
+    for (int32_t k = 0; k < n_fields; k++) ds->emb[(size_t)k].assign(emb[k], emb[k] + (size_t)ds->Count() * (size_t)dims[k]);
+    return 0;
+}
+// one embedding field's tensors after Fit: H (d x D), Wa (D x d), ba (d), We (D x d), be (d); returns the field count
+int32_t gh_fm_field_params(void *m, int32_t field, float *H, float *Wa, float *ba, float *We, float *be) {
+    const auto *f = (ctr::FM *)m;
+    if (field >= 0 && field < (int32_t)f->fields.size()) {
+        const auto &x = f->fields[(size_t)field];
+        std::copy(x.H.begin(), x.H.end(), H);
+        std::copy(x.Wa.begin(), x.Wa.end(), Wa);
+        std::copy(x.ba.begin(), x.ba.end(), ba);
+        std::copy(x.We.begin(), x.We.end(), We);
+        std::copy(x.be.begin(), x.be.end(), be);
+    }
+    return (int32_t)f->fields.size();
+}
 // optimizer: 0 SGD, 1 Adam (model.SGD / model.Adam)
 void *gh_fm_new(int32_t n_factors, int32_t n_epochs, int32_t batch_size, float lr, float reg, int32_t optimizer, int64_t seed) {
     return new ctr::FM(n_factors, n_epochs, batch_size, lr, reg, optimizer, seed);

@@ -388,7 +388,7 @@ int32_t gorse_hip_sgemm_device(int32_t device, int32_t transA, int32_t transB, i
                                int32_t ldc);
 
 
-/* ---- ctr.AFM without the item-embedding branch: the factorization machine (model/ctr/fm.go:111-126) -------------------
+/* ---- ctr.AFM: the factorization machine (model/ctr/fm.go:111-126); its item-embedding branch follows below --------------
  * n_features = dataset index length, d = nFactors in 1..128.  Parameters: bias B, linear W (n_features), pairwise V
  * (n_features x d, row-major), initialised by the caller (fm.go:247-270: the Go side draws them) and read back into the nn
  * tensors.  Samples are n x width matrices of feature indices and (already scaled) values, positions past a row's length
@@ -412,9 +412,42 @@ int32_t gorse_fm_set_train(gorse_fm *h, int64_t n, int32_t width, const int32_t 
  * when it is seen, and the call then returns GORSE_ERR_CANCELLED with the steps run so far applied. */
 int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optimizer, float lr, float wd,
                        const volatile int32_t *cancel /*host or NULL*/, float *cost_out /*host or NULL*/);
-/* BatchInternalPredict (fm.go:156-178): logits of n rows; width may differ from the training width */
+/* BatchInternalPredict (fm.go:156-178): logits of n rows; width may differ from the training width.  On a handle with
+ * embedding fields: GORSE_ERR_INVALID (use gorse_fm_predict_embeddings). */
 int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices /*host*/, const float *values /*host*/,
                          float *logits_out /*host*/);
+
+/* ---- the item-embedding branch of ctr.AFM (fm.go:127-132; nn.Attention and nn.Linear, common/nn/layers.go:36-60, 160-190) --
+ * Per embedding field of dimension D the model holds, in Parameters() order, H (d x D), Wa (D x d), ba (d), We (D x d),
+ * be (d), all row-major, and adds sum_f vx_f enc_f to a row's logit, where x is the row's embedding (bf16, widened; all
+ * zero where the sample has none), a = Softmax(relu(x Wa + ba) H, 1), enc = (a * x) We + be.  The Softmax is the
+ * reference's: maxima and sums are applied through Tensor.sub / Tensor.div, which index them by flat index % n
+ * (common/nn/op.go:760-777, tensor.go:328-379), so for a batch of n > 1 rows element (r, c) uses the maximum and sum of row
+ * (r D + c) % n, forward and backward, and a row's logit depends on the other rows of its batch and on the batch length.
+ * Caps: GORSE_FM_MAX_FIELDS fields, D in 1..GORSE_FM_MAX_EMBEDDING_DIM; beyond them GORSE_ERR_INVALID.
+ * A handle without fields (the state after gorse_fm_create, or after n_fields = 0) is the plain factorization machine. */
+#define GORSE_FM_MAX_FIELDS 8
+#define GORSE_FM_MAX_EMBEDDING_DIM 4096
+/* configure the fields (before gorse_fm_set_params / gorse_fm_set_embedding_params): allocates their parameters and moments as
+ * zeros and drops earlier fields with their training embeddings */
+int32_t gorse_fm_set_embedding_dims(gorse_fm *h, int32_t n_fields, const int32_t *dims /*host*/);
+/* one field's tensors; set resets the field's moments (Adam's t is shared with B, V, W and reset by gorse_fm_set_params).
+ * On get any pointer may be NULL. */
+int32_t gorse_fm_set_embedding_params(gorse_fm *h, int32_t field, const float *H /*host*/, const float *Wa /*host*/,
+                                      const float *ba /*host*/, const float *We /*host*/, const float *be /*host*/);
+int32_t gorse_fm_get_embedding_params(gorse_fm *h, int32_t field, float *H, float *Wa, float *ba, float *We, float *be);
+/* the training rows' embeddings of one field: n x D bf16 bit patterns (n of the last gorse_fm_set_train, which drops the
+ * embeddings of the set before it), zero rows where a sample has none; kept on the device as bf16.  Offsets into the matrix
+ * are 64-bit: n x D may exceed 2^31, and what bounds it is device memory (GORSE_ERR_NOMEM when it does not fit).
+ * gorse_fm_epoch on a handle with fields runs the branch (forward, backward and the dense step of every field's tensors) and
+ * returns GORSE_ERR_INVALID while a field's training embeddings are missing. */
+int32_t gorse_fm_set_train_embeddings(gorse_fm *h, int32_t field, const uint16_t *emb /*host, n x D*/);
+/* BatchInternalPredict with embeddings: rows are scored in slices of batch_size rows (the last one partial), as fm.go:168-176
+ * does; the slice length is part of the result (see above).  emb[k] = field k's n x D bf16 matrix.  Without fields: the same
+ * as gorse_fm_predict. */
+int32_t gorse_fm_predict_embeddings(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices /*host*/,
+                                    const float *values /*host*/, const uint16_t *const *emb /*host, n_fields pointers*/,
+                                    int32_t batch_size, float *logits_out /*host*/);
 
 #ifdef __cplusplus
 }

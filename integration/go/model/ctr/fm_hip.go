@@ -16,6 +16,7 @@ import (
 	"github.com/chewxy/math32"
 	"github.com/gorse-io/gorse/common/log"
 	"github.com/gorse-io/gorse/common/monitor"
+	"github.com/gorse-io/gorse/common/nn"
 	"github.com/gorse-io/gorse/dataset"
 	"github.com/gorse-io/gorse/model"
 	"github.com/samber/lo"
@@ -45,20 +46,43 @@ func flatRows(x []lo.Tuple2[[]int32, []float32], width int) ([]int32, []float32)
 	return idx, val
 }
 
-// fitHIP is AFM.Fit (fm.go:307-417) for a model without item embeddings: one gorse_fm_epoch call per epoch; the evaluation
+// flatEmbeddings lays field k's embeddings of the rows out as one n x D matrix of bf16 bit patterns, straight from the rows'
+// []uint16 (no fp32 copy): an all-zero row where a sample has none or one of another length (fm.go:555-561).
+func flatEmbeddings(e [][][]uint16, n, k, dim int) []uint16 {
+	out := make([]uint16, n*dim)
+	for i := 0; i < n && i < len(e); i++ {
+		if len(e[i]) > k && len(e[i][k]) == dim {
+			copy(out[i*dim:], e[i][k])
+		}
+	}
+	return out
+}
+
+// fieldTensors returns field k's tensors in Parameters() order (fm.go:136-146, layers.go:173-178): H, Wa, ba, We, be.
+func (fm *AFM) fieldTensors(k int) [5][]float32 {
+	a := fm.A[k].(*nn.Attention)
+	aw := a.W.(*nn.LinearLayer)
+	e := fm.E[k].(*nn.LinearLayer)
+	return [5][]float32{a.H.Data(), aw.W.Data(), aw.B.Data(), e.W.Data(), e.B.Data()}
+}
+
+// fitHIP is AFM.Fit (fm.go:307-417), with or without item embeddings: one gorse_fm_epoch call per epoch; the evaluation
 // schedule, the NaN stop and early stopping stay here as written.  It is called right after Init (fm.go:315-322), before the
 // reference's epoch-0 evaluation, and builds the scaled training rows itself (fm.go:337-352).  ok = false sends the caller back
-// to the CPU code (a model with item embeddings, no device, or a training set the device refuses) with no handle left resident.
+// to the CPU code (no device, or a model or training set the device refuses: GORSE_ERR_INVALID beyond the caps of
+// gorse_hip.h, GORSE_ERR_NOMEM when the embeddings do not fit) with no handle left resident.
 func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, config *FitConfig) (score Score, ok bool) {
 	fm.hip.close() // the previous Fit's device model must not score this one's epoch 0
 	fm.hip = nil
-	if len(fm.embeddingDim) != 0 || trainSet.Count() == 0 {
-		return Score{}, false // the attention branch keeps the reference's CPU code
+	if trainSet.Count() == 0 {
+		return Score{}, false
 	}
 	x := make([]lo.Tuple2[[]int32, []float32], trainSet.Count())
 	y := make([]float32, trainSet.Count())
+	e := make([][][]uint16, trainSet.Count())
 	for i := range x {
-		indices, values, _, target := trainSet.Get(i)
+		indices, values, embeddings, target := trainSet.Get(i)
+		e[i] = embeddings
 		scaled := make([]float32, len(values))
 		copy(scaled, values)
 		for j, idx := range indices {
@@ -76,16 +100,41 @@ func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, c
 	// Init drew B, W and V in Go (fm.go:247-270); the nn tensors hold them
 	width := max(fm.numDimension, 1)
 	idx, val := flatRows(x, width)
-	if rc := C.gorse_fm_set_params(hm.h, C.float(fm.B.Data()[0]), (*C.float)(&fm.W.Data()[0]), (*C.float)(&fm.V.Data()[0])); rc != 0 {
-		log.Logger().Warn("fit AFM: gorse_fm_set_params, CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+	giveUp := func(what string) (Score, bool) {
+		log.Logger().Warn("fit AFM: "+what+", CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
 		hm.close()
 		return Score{}, false
+	}
+	if len(fm.embeddingDim) != 0 { // more than GORSE_FM_MAX_FIELDS fields or a dimension above the cap: GORSE_ERR_INVALID
+		dims := make([]C.int32_t, len(fm.embeddingDim))
+		for k, dim := range fm.embeddingDim {
+			dims[k] = C.int32_t(dim)
+		}
+		if rc := C.gorse_fm_set_embedding_dims(hm.h, C.int32_t(len(dims)), &dims[0]); rc != 0 {
+			return giveUp("gorse_fm_set_embedding_dims")
+		}
+	}
+	if rc := C.gorse_fm_set_params(hm.h, C.float(fm.B.Data()[0]), (*C.float)(&fm.W.Data()[0]), (*C.float)(&fm.V.Data()[0])); rc != 0 {
+		return giveUp("gorse_fm_set_params")
+	}
+	for k := range fm.embeddingDim { // Init drew A[k] and E[k] in Go as well (fm.go:259-264)
+		t := fm.fieldTensors(k)
+		if rc := C.gorse_fm_set_embedding_params(hm.h, C.int32_t(k), (*C.float)(&t[0][0]), (*C.float)(&t[1][0]), (*C.float)(&t[2][0]),
+			(*C.float)(&t[3][0]), (*C.float)(&t[4][0])); rc != 0 {
+			return giveUp("gorse_fm_set_embedding_params")
+		}
 	}
 	if rc := C.gorse_fm_set_train(hm.h, C.int64_t(len(y)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
 		(*C.float)(&y[0])); rc != 0 { // e.g. more than 2^31 - 1 padded positions (GORSE_ERR_INVALID)
 		log.Logger().Warn("fit AFM: gorse_fm_set_train, CPU path", zap.String("err", C.GoString(C.gorse_hip_last_error())))
 		hm.close()
 		return Score{}, false
+	}
+	for k, dim := range fm.embeddingDim { // bf16 as stored, one field at a time; GORSE_ERR_NOMEM when it does not fit
+		emb := flatEmbeddings(e, len(y), k, dim)
+		if rc := C.gorse_fm_set_train_embeddings(hm.h, C.int32_t(k), (*C.uint16_t)(&emb[0])); rc != 0 {
+			return giveUp("gorse_fm_set_train_embeddings")
+		}
 	}
 	fm.hip = hm
 	opt := C.int32_t(C.GORSE_OPT_ADAM)
@@ -121,7 +170,7 @@ func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, c
 		fitTime := time.Since(fitStart)
 		if epoch%config.Verbose == 0 || epoch == fm.nEpochs {
 			evalStart := time.Now()
-			score = EvaluateClassification(fm, testSet, config.Jobs) // BatchInternalPredict -> gorse_fm_predict
+			score = EvaluateClassification(fm, testSet, config.Jobs) // BatchInternalPredict -> gorse_fm_predict(_embeddings)
 			scores = append(scores, lo.Tuple2[int, float32]{A: epoch, B: score.AUC})
 			log.Logger().Info(fmt.Sprintf("fit AFM %v/%v", epoch, fm.nEpochs), append([]zap.Field{
 				zap.String("fit_time", fitTime.String()),
@@ -155,12 +204,21 @@ func (fm *AFM) pullParams() {
 		return
 	}
 	fm.B.Data()[0] = float32(b)
+	for k := range fm.embeddingDim {
+		t := fm.fieldTensors(k)
+		if rc := C.gorse_fm_get_embedding_params(fm.hip.h, C.int32_t(k), (*C.float)(&t[0][0]), (*C.float)(&t[1][0]), (*C.float)(&t[2][0]),
+			(*C.float)(&t[3][0]), (*C.float)(&t[4][0])); rc != 0 {
+			log.Logger().Error("fit AFM: gorse_fm_get_embedding_params", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+			return
+		}
+	}
 }
 
-// batchPredictHIP is BatchInternalPredict (fm.go:156-178) on the device for already scaled rows; ok = false when the model
-// is not resident (loaded by Unmarshal without a Fit in this process, or with item embeddings).
-func (fm *AFM) batchPredictHIP(x []lo.Tuple2[[]int32, []float32]) ([]float32, bool) {
-	if fm.hip == nil || fm.hip.h == nil || len(fm.embeddingDim) != 0 {
+// batchPredictHIP is BatchInternalPredict (fm.go:156-178) on the device for already scaled rows and their embeddings; ok = false
+// when the model is not resident (loaded by Unmarshal without a Fit in this process).  With item embeddings the rows are scored in
+// slices of fm.batchSize rows, as the reference does: its Softmax makes the slice length part of the result.
+func (fm *AFM) batchPredictHIP(x []lo.Tuple2[[]int32, []float32], e [][][]uint16) ([]float32, bool) {
+	if fm.hip == nil || fm.hip.h == nil {
 		return nil, false
 	}
 	out := make([]float32, len(x))
@@ -172,8 +230,23 @@ func (fm *AFM) batchPredictHIP(x []lo.Tuple2[[]int32, []float32]) ([]float32, bo
 		width = max(width, len(x[i].A))
 	}
 	idx, val := flatRows(x, width)
-	if rc := C.gorse_fm_predict(fm.hip.h, C.int64_t(len(x)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
-		(*C.float)(&out[0])); rc != 0 {
+	if len(fm.embeddingDim) == 0 {
+		if rc := C.gorse_fm_predict(fm.hip.h, C.int64_t(len(x)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+			(*C.float)(&out[0])); rc != 0 {
+			return nil, false
+		}
+		return out, true
+	}
+	// the field matrices live in C memory for the call: a Go pointer to Go pointers must not cross cgo
+	ptrs := (*[C.GORSE_FM_MAX_FIELDS]*C.uint16_t)(C.malloc(C.size_t(C.GORSE_FM_MAX_FIELDS) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(ptrs))
+	for k, dim := range fm.embeddingDim {
+		emb := flatEmbeddings(e, len(x), k, dim)
+		ptrs[k] = (*C.uint16_t)(C.CBytes(unsafe.Slice((*byte)(unsafe.Pointer(&emb[0])), 2*len(emb))))
+		defer C.free(unsafe.Pointer(ptrs[k]))
+	}
+	if rc := C.gorse_fm_predict_embeddings(fm.hip.h, C.int64_t(len(x)), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		&ptrs[0], C.int32_t(fm.batchSize), (*C.float)(&out[0])); rc != 0 {
 		return nil, false
 	}
 	return out, true

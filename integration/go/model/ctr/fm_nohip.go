@@ -19,4 +19,6 @@ func (fm *AFM) fitHIP(context.Context, dataset.CTRSplit, dataset.CTRSplit, *FitC
 	return Score{}, false
 }
 
-func (fm *AFM) batchPredictHIP([]lo.Tuple2[[]int32, []float32]) ([]float32, bool) { return nil, false }
+func (fm *AFM) batchPredictHIP([]lo.Tuple2[[]int32, []float32], [][][]uint16) ([]float32, bool) {
+	return nil, false
+}
