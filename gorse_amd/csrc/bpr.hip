@@ -504,6 +504,77 @@ __global__ __launch_bounds__(256) void bpr_bin_sort_kernel(int32_t U, int shift,
     }
 }
 
+// ---- equal positives of a run next to each other ------------------------------------------------
+// The last step of launch_prepare_users (both forms).  The positive of a sample is drawn with replacement from the user's n_u
+// feedbacks and a run holds ~N / U samples whatever n_u, so about half the (user, positive) pairs of an S-ml1m epoch repeat one of
+// the same run (distinct share 0.49; C3 shapes 0.63): bpr_update_user_kernel sends ONE atomic row update for a stretch of samples
+// with the same positive, and this pass makes the repeats such stretches.  One wave per run sorts the run's (i, j) pairs in LDS
+// (bitonic, 64-bit keys) and writes them back in place: 8 bytes read and written per sample in whole lines, no global atomic, no
+// lone store -- nothing of what the update kernel beside it is sensitive to (see the binned preparation above).
+// The key's upper half is not i but a per-user BIJECTION of i: sorted by i itself every group would walk the item ids upwards at
+// the same pace, all 6040 of them inside the same narrow band of rows at any moment -- the rows' atomic queues and the staleness of
+// a hot row's gathers are what the replicas and the fold period exist to bound.  With the salted order a positive's place in its
+// run is uniform, as it was in arrival order.  The lower half is j: the order inside a run is a function of the run's multiset.
+// A sample without a negative (i = j = -1) gets the largest key and ends up last in its run; runs longer than kGroupCap samples
+// (a chunk is max(4M, 32 U) samples: more than 1024 per user only below 4096 users) stay in arrival order -- the update kernel
+// combines what is adjacent, whatever put it there.
+constexpr int kGroupCap = 1024;  // samples of a run the pass sorts: 8 KB of LDS per wave
+constexpr uint32_t kGroupMul = 0x9E3779B1u;
+constexpr uint32_t mul_inverse_u32(uint32_t m) {  // of an odd m, modulo 2^32 (Newton: five steps double 3 correct bits to 96)
+    uint32_t x = m;
+    for (int k = 0; k < 5; k++) x *= 2u - m * x;
+    return x;
+}
+constexpr uint32_t kGroupMulInv = mul_inverse_u32(kGroupMul);
+static_assert(kGroupMul * kGroupMulInv == 1u, "inverse of the mixing multiplier");
+__device__ __forceinline__ uint32_t group_salt(int32_t u) { return (uint32_t)u * 0x85EBCA6Bu + 0x7F4A7C15u; }
+__device__ __forceinline__ uint64_t group_key(int32_t i, int32_t j, uint32_t salt) {
+    if (j < 0) return ~0ull;
+    uint32_t x = ((uint32_t)i ^ salt) * kGroupMul;
+    x ^= x >> 16;
+    return ((uint64_t)x << 32) | (uint32_t)j;
+}
+__device__ __forceinline__ int2 group_unkey(uint64_t k, uint32_t salt) {
+    const int32_t j = (int32_t)(uint32_t)k;
+    if (j < 0) return make_int2(-1, -1);
+    uint32_t x = (uint32_t)(k >> 32);
+    x ^= x >> 16;
+    return make_int2((int32_t)((x * kGroupMulInv) ^ salt), j);
+}
+
+__global__ __launch_bounds__(64) void bpr_group_positives_kernel(int32_t U, const int32_t *__restrict__ off, int32_t *__restrict__ si,
+                                                                 int32_t *__restrict__ sj) {
+    __shared__ uint64_t key[kGroupCap];
+    const int lane = threadIdx.x;
+    for (int32_t u = blockIdx.x; u < U; u += gridDim.x) {
+        const int32_t beg = off[u], len = off[u + 1] - beg;
+        if (len < 3 || len > kGroupCap) continue;  // (two samples are adjacent anyway)
+        int P = 4;
+        while (P < len) P <<= 1;
+        const uint32_t salt = group_salt(u);
+        for (int k = lane; k < P; k += 64) key[k] = k < len ? group_key(si[beg + k], sj[beg + k], salt) : ~0ull;
+        __syncthreads();
+        for (int kk = 2; kk <= P; kk <<= 1) {
+            for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+                for (int t = lane; t < (P >> 1); t += 64) {
+                    const int lo = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), hi = lo | jj;
+                    const uint64_t a = key[lo], b = key[hi];
+                    if ((a > b) == ((lo & kk) == 0)) key[lo] = b, key[hi] = a;
+                }
+                __syncthreads();
+            }
+        }
+        // (the padding keys equal the key of a sample without a negative and decode to the same (-1, -1): the first `len` keys
+        // are the run's samples whichever of the equal keys they are)
+        for (int k = lane; k < len; k += 64) {
+            const int2 v = group_unkey(key[k], salt);
+            si[beg + k] = v.x;
+            sj[beg + k] = v.y;
+        }
+        __syncthreads();
+    }
+}
+
 // ---- memory access flavours ------------------------------------------------------------------
 template <int MODE>
 __device__ __forceinline__ float load_row(const float *p) {
@@ -884,9 +955,26 @@ __global__ __launch_bounds__(256) void bpr_scatter_by_kernel(const int32_t *__re
 // parallel.go:44-68) and one 16-lane group walks ALL samples of one user: p_u is loaded once, updated in registers
 // sample after sample -- exact sequential SGD on the user side, no lost or delayed update -- and stored once, so a
 // third of the fp32 atomics (the unit this kernel is bound by: ~1 dword/clk per L2 channel) and a third of the
-// gathers disappear.  q_i / q_j are gathered one sample ahead of the arithmetic and updated with atomics exactly as
-// in bpr_update_kernel (hot positive items through the replicas).  Users are drawn uniformly (model.go:452-458), so
+// gathers disappear.  q_i / q_j are gathered two samples (q_j with the store route: one) ahead of the arithmetic and updated
+// with atomics as in bpr_update_kernel (hot items through the replicas).  Users are drawn uniformly (model.go:452-458), so
 // the runs are Poisson(N / U)-sized: balanced without any work splitting.
+// POSITIVE SERIES.  A series is a maximal stretch of consecutive valid samples of a run with the same positive i (the preparation
+// puts a run's repeats of a positive next to each other: bpr_group_positives_kernel; the kernel combines whatever is adjacent).
+// Its first sample computes from the gathered snapshot as every sample did before; after each sample the group's own copy of the
+// row becomes mad(t1, lr, a), the next sample of the series computes from that copy -- the operands of the sequential code, not a
+// snapshot two samples stale -- and its row is not gathered at all; t1 * lr adds up in registers and goes out as ONE atomic per
+// element when the series ends: the next positive differs, the next sample is invalid, the run ends, or one of the two samples has
+// the series' positive as its NEGATIVE (hand-made streams; i == j included): such a sample's negative-side update then never meets a
+// row with a change pending, nothing is lost or counted twice.  A series of one sample issues exactly the atomic of t1 * lr it
+// always did.  The sum goes out in the iteration of the series' LAST sample, so no change is pending across iterations outside a
+// series, and inside one the previous sample's positive (im1) is the pending row: the own-history rule of the store route holds as
+// it stands.  Bound on the delay: a change waits for at most kSeriesFlush = 8 samples of its group (the sum goes out every 8
+// samples of a longer series, which keeps walking on its own copy) -- ~28 us at nFactors 64, ~14 us at 16 -- and it is ONE group's
+// change to the row, each sample of it computed from a row that holds the group's earlier ones.  The fold-period sweep
+// (kDefaultFoldPeriod) diverged when EVERY group's updates of a hot row, ~1800 of them, were computed from one stale row; here
+// the other groups' updates keep arriving and only the series' own group reads past them, for the length of the series (<= the
+// run; 2 samples on average at C2, ~9 for a user of 19 feedbacks).  tests/test_gpu_bpr_positive_series.py runs 30 epochs at
+// nFactors 8 and 16.
 // Item classes (hot.slot): >= 0 = replica slot of a HOT item, kWarm = fp32 atomics straight onto the row, kCold = an item whose
 // row is touched so rarely (expected touches per `cold window` samples < 1, gorse_mf_create) that the reference's own unlocked
 // load / fma / store (model.go:473-488 under parallel.go:44-81) loses next to nothing: its update is ONE write-through store of
@@ -895,6 +983,10 @@ __global__ __launch_bounds__(256) void bpr_scatter_by_kernel(const int32_t *__re
 // (diagnostic: a shorter window in which another group's update can be overwritten, one more gather per row).
 constexpr int kCold = -2;  // (-1 = "warm": fp32 atomics straight onto the row)
 constexpr int ST_NEG = 1, ST_POS = 2, ST_LIVE = 4;
+constexpr int kSeriesFlush = 8;  // samples of a positive series whose summed change goes out together (see POSITIVE SERIES below)
+#ifndef GORSE_BPR_SERIES_SKIP_GATHERS
+#define GORSE_BPR_SERIES_SKIP_GATHERS 1  // A/B: 0 = the positive's row is gathered for every sample, used or not
+#endif
 
 // D8: nFactors = 8 (the width of model_test.go:35-48): lanes 0..7 of the group own the eight elements -- the unfused 8-lane tail of
 // the AVX512 kernels (floats_avx512.c:350-358, VecShape::unfused) -- and lanes 8..15 mirror them (the reduction needs the products
@@ -924,6 +1016,11 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
     // with the store route open for negatives their rows are gathered ONE sample ahead instead of two: what a store can
     // overwrite is what other groups added between the gather and the store, and that window halves
     constexpr bool NEG1 = (ST & ST_NEG) != 0;
+    // positive series (see the comment block above): every form whose positive update is always an atomic
+    constexpr bool COMB = (ST & (ST_POS | ST_LIVE)) == 0;
+    // sample (i1, j1) continues the series of the sample (i0, j0) in front of it: the same positive, both samples valid, and neither
+    // negative is that positive (hand-made streams: such a sample's negative-side update must meet a row without pending change)
+    auto continues = [](int i0, int j0, int i1, int j1) { return i0 == i1 && (i0 | j0 | j1) >= 0 && i0 != j0 && i0 != j1; };
     const int glane = threadIdx.x & (kGroup - 1);
     const int lane = D8 ? (glane & 7) : glane;   // element owned inside a 16-float chunk
     // D8 (round 6): the two halves of a 16-lane group take a user run EACH (eight lanes own a row of eight: until round 5 lanes 8..15
@@ -977,6 +1074,11 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
 #pragma unroll
         for (int k = 0; k < G; k++) sli[k] = slot_of[idx_i(ii[k], jj[k])], slj[k] = slot_of[idx_j(ii[k], jj[k])];
         float p_in[SEG ? NC : 1];  // SEG: the row as this segment found it
+        // the series in flight: `cur` the positive's row as this group has left it, `acc` its change not yet sent (of `pending`
+        // samples), `cont` = the current sample continues the series of the one before
+        float cur[COMB ? NC : 1], acc[COMB ? NC : 1];
+        bool cont = false;
+        int pending = 0;
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             p[c] = load_row<MODE_ATOMIC>(pu + 16 * c + lane);
@@ -1001,11 +1103,23 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
                     bl[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(j) * d + 16 * c + lane);
                 }
             }
+            // the positive's row of sample s + G: not gathered where that sample will continue a series (it computes from `cur`)
+            const bool gather_i = !(COMB && GORSE_BPR_SERIES_SKIP_GATHERS) || !(s + G <= last && continues(ii[G - 1], jj[G - 1], ii[G], jj[G]));
 #pragma unroll
-            for (int c = 0; c < NC; c++) {
-                ran[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(ii[G]) * d + 16 * c + lane);
-                rbn[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(jj[GB]) * d + 16 * c + lane);
+            for (int c = 0; c < NC; c++) ran[c] = 0.0f;
+            if (gather_i) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) ran[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(ii[G]) * d + 16 * c + lane);
             }
+#pragma unroll
+            for (int c = 0; c < NC; c++) rbn[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(jj[GB]) * d + 16 * c + lane);
+            if constexpr (COMB) {
+                if (cont) {
+#pragma unroll
+                    for (int c = 0; c < NC; c++) a[c] = cur[c];
+                }
+            }
+            const bool more = COMB && s < last && continues(i, j, ii[1], jj[1]);  // the next sample continues this one's series
             const bool valid = j >= 0;  // j < 0: the sampler found no negative for this sample (bpr_sample_items_kernel)
             float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
             if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
@@ -1033,7 +1147,23 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
                 const float t3 = mad(p[c], nreg, (a[c] - b[c]) * grad);
                 p[c] = valid ? mad(t3, lr, p[c]) : p[c];
             }
-            if (!valid || !writer) {
+            if constexpr (COMB) {
+                if (valid) {  // (every lane keeps the series: the lanes that mirror a row of eight need `cur` as the writers do)
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        acc[c] = pending > 0 ? acc[c] + t1[c] * lr : t1[c] * lr;  // a series of one sends t1 * lr, as the kernel did without series
+                        cur[c] = mad(t1[c], lr, a[c]);
+                    }
+                    if (!more || ++pending >= kSeriesFlush) {
+                        pending = 0;
+                        if (writer) {
+#pragma unroll
+                            for (int c = 0; c < NC; c++)
+                                __hip_atomic_fetch_add(qi + 16 * c + lane, acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                    }
+                }
+            } else if (!valid || !writer) {
                 // nothing to write
             } else if (st_i) {
 #pragma unroll
@@ -1045,6 +1175,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
                 for (int c = 0; c < NC; c++)
                     __hip_atomic_fetch_add(qi + 16 * c + lane, t1[c] * lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            cont = more;
             if (!valid || !writer) {
             } else if (st_j) {
 #pragma unroll
@@ -1526,6 +1657,14 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
                                                                                   h->uidx_sorted.p, seed, epoch, base, n, pairs,
                                                                                   sorted + cap, sorted + 2 * cap, h->fail_count.p);
     };
+    // equal positives of a run next to each other (bpr_group_positives_kernel): one wave per run, in place
+    auto launch_group = [&]() {
+        if (g_variant & (1 << 20)) return;  // variant bit 20 (probes, A/B): the runs stay in arrival order
+        const int tok = h->prof.begin(GORSE_PROF_BPR_SORT, st);
+        bpr_group_positives_kernel<<<dim3((unsigned)std::min<int64_t>(h->U, 256 * 16)), dim3(64), 0, st>>>(
+            (int32_t)h->U, bucket, sorted + cap, sorted + 2 * cap);
+        h->prof.end(tok, st);
+    };
     if (pb.ok && !(g_variant & (1 << 21))) {  // variant bit 21 (probes, tests): the preparation without bins
         int32_t *key = trip;
         int2 *bp = reinterpret_cast<int2 *>(trip + cap), *pairs = reinterpret_cast<int2 *>(rank);  // (rank: 2 x cap words, ensure_user_sort)
@@ -1545,6 +1684,7 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
         tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
         launch_items(pairs);
         h->prof.end(tok, st);
+        launch_group();
         GORSE_HIP_CHECK(hipGetLastError());
         return GORSE_OK;
     }
@@ -1562,6 +1702,7 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
     tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
     launch_items(pairs);
     h->prof.end(tok, st);
+    launch_group();
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
