@@ -148,17 +148,12 @@ SIGNATURES = {
     "gorse_hip_test_set_sparse_split": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_heavy": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_atomic": (None, [C.c_int32]),
-    "gorse_hip_test_sparse_trace": (C.c_int64, [_vp, C.c_int32, C.POINTER(C.c_uint64), C.c_int64]),
     "gorse_hip_test_set_als_path": (None, [C.c_int32]),
     "gorse_hip_test_set_als_plan": (None, [C.c_int32, C.c_int32]),
-    "gorse_hip_test_als_profile": (C.c_int32, [_vp, C.c_int32, C.POINTER(C.c_uint64)]),
     "gorse_hip_test_set_bpr_chunk": (None, [C.c_int64]),
     "gorse_hip_test_bpr_prepare_chunk": (C.c_int32, [_vp, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _i32p, _i32p, _i32p]),
     "gorse_hip_test_set_bpr_store_mode": (None, [C.c_int32]),
     "gorse_hip_test_set_prep_cu_stride": (None, [C.c_int32]),
-    "gorse_hip_test_set_bpr_user_segments": (None, [C.c_int32]),
-    "gorse_hip_test_set_bpr_user_depth": (None, [C.c_int32]),
-    "gorse_hip_test_probe_build": (C.c_int32, []),
     "gorse_hip_test_set_sgemm_valu": (None, [C.c_int32]),
     "gorse_hip_test_sgemm_last_ms": (C.c_double, []),
     "gorse_hip_test_set_bpr_cold_window": (None, [C.c_int64]),
@@ -337,11 +332,6 @@ class MF:
         v = C.c_int32(0)
         check(lib().gorse_mf_bpr_schedule(self.h, C.byref(v)))
         return bool(v.value)
-
-    def als_profile(self, enable, fetch=False):
-        out = (C.c_uint64 * 16)() if fetch else None
-        check(lib().gorse_hip_test_als_profile(self.h, int(enable), out))
-        return [int(x) for x in out] if fetch else None
 
     def als_set_ranges(self, u_begin, u_end, i_begin, i_end):
         check(lib().gorse_als_set_ranges(self.h, u_begin, u_end, i_begin, i_end))
@@ -896,14 +886,6 @@ class Sparse:
         out = (C.c_int64 * 4)()
         lib().gorse_hip_test_sparse_sym_stats(self.h, out)
         return tuple(int(x) for x in out)
-
-    def trace(self, on=True):
-        """probe: switch the per-work-item records on / off; returns the records of the last call (n x 16 uint64)"""
-        n = lib().gorse_hip_test_sparse_trace(self.h, int(bool(on)), None, 0)
-        out = np.zeros((max(n, 0), 16), np.uint64)
-        if n > 0:
-            lib().gorse_hip_test_sparse_trace(self.h, int(bool(on)), out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
-        return out
 
 
 def sgemm(transA, transB, m, n, k, a, lda, b, ldb, c, ldc, device=0):

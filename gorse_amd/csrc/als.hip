@@ -752,9 +752,8 @@ __global__ __launch_bounds__(256, 2) void als_wide_kernel(float *__restrict__ A,
     // probe only (prof != null, MFMA rows): s_memtime ticks of the workgroup's first wave in [0] G, [1] M to LDS + S, [2] sweep;
     // [3] rows, [4] entries, [5] kernel ticks, [6] workgroups
     unsigned long long c_acc = 0, c_m = 0, c_solve = 0, c_rows = 0, c_ent = 0, t_begin = 0;
-#ifndef GORSE_PROBE
-    prof = nullptr;  // the phase counters exist in `make probe-lib` builds only: here every `if (prof)` folds away
-#endif
+    prof = nullptr;  // nothing fills the phase counters any more (every `if (prof)` folds away); the blocks stay because taking them
+                     // out changed the kernel's register allocation and branch layout
     if (prof) t_begin = __builtin_amdgcn_s_memtime();
     float *sM = smem;                           // 128 x 129
     float *sq = sM + 128 * kWideLd;             // 16 x 128: one batch of gathered rows
@@ -919,7 +918,6 @@ bool g_als_solve_adds = false;  // tests (path | 2048): no als_partial_reduce_ke
 int g_als_path = 0;         // 0 auto (Gram form: MFMA kernels for d <= 64, als_wide_kernel for d <= 128; else the residual
                             // sweep), 1 force the residual sweep, 2 force the MFMA Gram form (d <= 64)
 int g_als_wide_fma = 0;     // als_wide_kernel: G by fused multiply-adds (round 2) instead of the fp32 MFMA (probe: path | 8)
-bool g_als_prof = false;    // probe: 8 counters per side in h->als_prof (gorse_hip_test_als_profile)
 int g_als_slow_gather = 0;  // als_row_kernel / als_chunk_kernel: the first form of the gather stage whatever the shape (probe: path | 64)
 int g_als_wide_probe = 0;   // timing probes of als_wide_kernel (results are garbage): path | 16 = no sweep, path | 32 = S not added
 int g_als_nob3 = 0;         // no bf16 x 3 Gram: d = 32 / 64 take the fp32 16 x 16 tiles (probe: path | 1024)
@@ -1429,9 +1427,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
     // probe only (prof != null): s_memtime ticks per wave in [0] Gram accumulation, [1] M to LDS, [2] solve; [3] rows,
     // [4] feedback entries, [5] kernel ticks, [6] waves
     unsigned long long c_acc = 0, c_m = 0, c_solve = 0, c_rows = 0, c_ent = 0, t_begin = 0, c_load = 0;
-#ifndef GORSE_PROBE
-    prof = nullptr;  // the phase counters exist in `make probe-lib` builds only: here every `if (prof)` folds away
-#endif
+    prof = nullptr;  // nothing fills the phase counters any more (every `if (prof)` folds away); the blocks stay because taking them
+                     // out changed the kernel's register allocation and branch layout
     if (prof) t_begin = __builtin_amdgcn_s_memtime();
     // S (d x d, the same for every row of the half-sweep) is copied to LDS once: read from global memory inside the solve, its
     // 64 loads per row queued behind the sibling waves' gathers -- 24.6K of the solve's 40.5K cycles per row
@@ -1721,18 +1718,11 @@ int32_t run_sweep(gorse_mf *h, float *A, const float *B, const int64_t *ptr, con
         GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
         GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
         GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        unsigned long long *wprof = nullptr;
-        if (g_als_prof) {
-            const int side = A == h->P.p ? 0 : 1;
-            GORSE_TRY(h->als_prof.ensure(16));
-            GORSE_HIP_CHECK(hipMemsetAsync(h->als_prof.p + 8 * side, 0, 8 * sizeof(unsigned long long), h->stream));
-            wprof = h->als_prof.p + 8 * side;
-        }
         const int tokw = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
         if (pl.n_short > 0) {
             auto k = form == 2 ? als_wide_kernel<false, 2> : (form == 1 ? als_wide_kernel<false, 1> : als_wide_kernel<false, 0>);
             k<<<dim3((unsigned)std::min<int64_t>(pl.n_short, 512)), dim3(256), wlds, h->stream>>>(
-                A, B, ptr, idx, h->gram.p, pl.short_rows.p, nullptr, nullptr, pl.n_short, d, w, reg, nullptr, g_als_wide_probe, wprof);
+                A, B, ptr, idx, h->gram.p, pl.short_rows.p, nullptr, nullptr, pl.n_short, d, w, reg, nullptr, g_als_wide_probe, nullptr);
             GORSE_HIP_CHECK(hipGetLastError());
         }
         if (pl.n_long > 0) {
@@ -1769,9 +1759,6 @@ int32_t run_sweep(gorse_mf *h, float *A, const float *B, const int64_t *ptr, con
     return GORSE_OK;
 }
 
-
-// probe: 8 counters per side in h->als_prof when the hook is on
-unsigned long long *als_prof_slot(gorse_mf *h, int side) { return g_als_prof && h->als_prof.n >= 16 ? h->als_prof.p + 8 * side : nullptr; }
 
 // the row id of the zero row behind matrix F (mf.hip) when 32-bit gather offsets apply (offsets in 32 bits, row ids in 24); else -1
 int als_zero_row(const gorse_mf *h, const float *F) {
@@ -1883,10 +1870,6 @@ int32_t run_side_gram(gorse_mf *h, int side, float *A, const float *B, const int
     const int d = h->d;
     const int zrow = als_zero_row(h, B), pad_row = als_pad_row(h, B);
     gorse_mf::AlsPlan &pl = h->als_plan[side];
-    if (g_als_prof) {
-        GORSE_TRY(h->als_prof.ensure(16));
-        GORSE_HIP_CHECK(hipMemsetAsync(h->als_prof.p + 8 * side, 0, 8 * sizeof(unsigned long long), h->stream));
-    }
     int tok = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
     if (pl.n_short > 0) {
 #define ROW_LAUNCH(WAVES_, LDS_, ...)                                                                                  \
@@ -1895,7 +1878,7 @@ int32_t run_side_gram(gorse_mf *h, int side, float *A, const float *B, const int
         GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_row_kernel<__VA_ARGS__, WAVES_>,                         \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)));                 \
         als_row_kernel<__VA_ARGS__, WAVES_><<<dim3(grid_), dim3(64 * WAVES_), (LDS_), h->stream>>>(                    \
-            A, B, ptr, idx, h->gram.p, pl.short_rows.p, pl.n_short, d, w, reg, h->als_zeros.p, als_prof_slot(h, side), \
+            A, B, ptr, idx, h->gram.p, pl.short_rows.p, pl.n_short, d, w, reg, h->als_zeros.p, nullptr,                \
             g_als_phased, pad_row);                                                                                    \
     } while (0)
         const int mode = als_gram_mode(d, zrow);
@@ -2132,17 +2115,6 @@ extern "C" void gorse_hip_test_set_als_path(int32_t path) {
     g_als_waves8 = (path & 256) != 0;
     g_als_nob3 = (path & 1024) != 0;
     g_als_solve_adds = (path & 2048) != 0;
-}
-// probe: phase counters of als_row_kernel for the last half-sweep of each side (16 values: users, items)
-extern "C" int32_t gorse_hip_test_als_profile(gorse_mf *h, int32_t enable, uint64_t *out16) {
-    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
-    g_als_prof = enable != 0;
-    if (!out16) return GORSE_OK;
-    if (h->als_prof.n < 16) return fail(GORSE_ERR_INVALID, "no profiled ALS sweep has run on this handle");
-    GORSE_TRY(h->use());
-    GORSE_HIP_CHECK(hipMemcpyAsync(out16, h->als_prof.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return GORSE_OK;
 }
 // takes effect for handles created afterwards (the row plan is built in gorse_mf_create)
 extern "C" void gorse_hip_test_set_als_plan(int32_t long_row, int32_t chunk) {

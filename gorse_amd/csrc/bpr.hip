@@ -663,9 +663,6 @@ struct HotRows {
     int d;
     int set;               // the set of stripes this launch counts in (launch parity: the launch zeroes the other one for the next)
     uint32_t period;       // wall-clock ticks between two folder passes
-#ifdef GORSE_PROBE
-    float *warm_scratch = nullptr;  // timing probe (variant bit 23): the atomics of the items WITHOUT replicas land here instead of on Q (results garbage)
-#endif
 };
 
 // the replica row that group `group` adds a hot item's update to (code: the item's hot_slot word)
@@ -978,11 +975,9 @@ __global__ __launch_bounds__(256) void bpr_scatter_by_kernel(const int32_t *__re
 // Item classes (hot.slot): >= 0 = replica slot of a HOT item, kWarm = fp32 atomics straight onto the row, kCold = an item whose
 // row is touched so rarely (expected touches per `cold window` samples < 1, gorse_mf_create) that the reference's own unlocked
 // load / fma / store (model.go:473-488 under parallel.go:44-81) loses next to nothing: its update is ONE write-through store of
-// fma(t, lr, row) instead of d atomic dwords.  ST selects which side may take that route: ST_NEG the negative, ST_POS the
-// positive, ST_LIVE re-reads the row just before the store instead of adding to the snapshot gathered two samples earlier
-// (diagnostic: a shorter window in which another group's update can be overwritten, one more gather per row).
+// fma(t, lr, row) instead of d atomic dwords.  NEG_STORE opens that route for the NEGATIVE item of a sample; the positive's update is
+// always an atomic (by store it cost 0.003-0.005 of NDCG: see kDefaultStoreMode).
 constexpr int kCold = -2;  // (-1 = "warm": fp32 atomics straight onto the row)
-constexpr int ST_NEG = 1, ST_POS = 2, ST_LIVE = 4;
 constexpr int kSeriesFlush = 8;  // samples of a positive series whose summed change goes out together (see POSITIVE SERIES below)
 #ifndef GORSE_BPR_SERIES_SKIP_GATHERS
 #define GORSE_BPR_SERIES_SKIP_GATHERS 1  // A/B: 0 = the positive's row is gathered for every sample, used or not
@@ -991,33 +986,19 @@ constexpr int kSeriesFlush = 8;  // samples of a positive series whose summed ch
 // D8: nFactors = 8 (the width of model_test.go:35-48): lanes 0..7 of the group own the eight elements -- the unfused 8-lane tail of
 // the AVX512 kernels (floats_avx512.c:350-358, VecShape::unfused) -- and lanes 8..15 mirror them (the reduction needs the products
 // replicated there); only lanes 0..7 write.
-// SEG (round 5, nFactors <= 32; `make probe-lib` builds only -- a measured dead end, kept so that the measurement can be repeated): a
-// user's run is cut into `segs` consecutive segments, each taken by its own group: every segment starts from the row as it stood
-// before the launch and adds its own change to it with atomics at the end.  With 6040 users (S-ml1m) a group per user leaves the chip
-// at 1.5 waves per SIMD walking ~165 dependent samples each; the segments are the reference's own race -- two of its workers that drew
-// the same user both update p_u from what they read (model.go:449-488) -- made regular.  Result (profiles/r05_k_probe_gpu_probe_bpr_
-// segments.txt: S-ml1m, 30 epochs, three seeds): 3 segments take 5 % off the epoch (0.456 -> 0.432 ms at nFactors 8, 0.350 -> 0.332 at
-// 16, nothing at 32) for 0.001-0.003 of NDCG@10 -- the epoch is not the per-user chain but the chunk's preparation running beside
-// it -- and with 4 / 8 segments a fit DIVERGED (NaN) in two of 18 runs: a heavy user's segments each apply the whole run's
-// regularisation shrink to the same starting row, and the summed changes overshoot (n_u lr reg > 1 for 2000 feedbacks).
 #ifndef GORSE_BPR_D8_PAIRS
 #define GORSE_BPR_D8_PAIRS 1  // A/B: 0 = nFactors 8 with lanes 8..15 of a group mirroring lanes 0..7 (rounds 4-5)
 #endif
-template <int NC, int ST, bool D8 = false, int G = 2, int IA = 3, bool SEG = false>
+template <int NC, bool NEG_STORE, bool D8 = false>
 __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float *Q, const int32_t *__restrict__ si,
                                                                  const int32_t *__restrict__ sj,
                                                                  const int32_t *__restrict__ off, int32_t U, int d,
                                                                  float lr, float reg, int exp_mode, double *loss,
-                                                                 HotRows hot, int folders, int neg_replicas, int segs = 1) {
+                                                                 HotRows hot, int folders, int neg_replicas) {
     if ((int)blockIdx.x < folders) {
         run_folders<true>(hot, Q, folders);
         return;
     }
-    // with the store route open for negatives their rows are gathered ONE sample ahead instead of two: what a store can
-    // overwrite is what other groups added between the gather and the store, and that window halves
-    constexpr bool NEG1 = (ST & ST_NEG) != 0;
-    // positive series (see the comment block above): every form whose positive update is always an atomic
-    constexpr bool COMB = (ST & (ST_POS | ST_LIVE)) == 0;
     // sample (i1, j1) continues the series of the sample (i0, j0) in front of it: the same positive, both samples valid, and neither
     // negative is that positive (hand-made streams: such a sample's negative-side update must meet a row without pending change)
     auto continues = [](int i0, int j0, int i1, int j1) { return i0 == i1 && (i0 | j0 | j1) >= 0 && i0 != j0 && i0 != j1; };
@@ -1036,32 +1017,27 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
     double my_loss = 0.0;
     // which class look-ups this launch needs (every path issues the same loads from a valid address: a look-up nobody needs
     // reads a word that is in cache anyway)
-    const bool look_i = hot.n_hot > 0 || (ST & ST_POS);
-    const bool look_j = (hot.n_hot > 0 && neg_replicas) || (ST & ST_NEG);
+    const bool look_i = hot.n_hot > 0;
+    const bool look_j = (hot.n_hot > 0 && neg_replicas) || NEG_STORE;
     const int32_t *slot_of = (look_i || look_j) ? hot.slot : si;
     // the items of this group's last two samples: a row one of them wrote is NOT in the snapshot of the current sample (gathered
     // two samples ago), so its update goes through an atomic whatever its class -- a store would overwrite the group's own work
     int im1 = -1, jm1 = -1, im2 = -1, jm2 = -1;
-    const int64_t runs = SEG ? (int64_t)U * segs : (int64_t)U;
-    for (int64_t run = group; run < runs; run += ngroups) {
-        const int64_t u = SEG ? run / segs : run;
-        int beg = off[u], end = off[u + 1];
-        if constexpr (SEG) {  // segment run - u * segs of the user's run
-            const int64_t len = end - beg, sg = run - u * segs;
-            end = beg + (int)(len * (sg + 1) / segs);
-            beg = beg + (int)(len * sg / segs);
-        }
+    for (int64_t u = group; u < U; u += ngroups) {
+        const int beg = off[u], end = off[u + 1];
         if (beg >= end) continue;
         float *pu = P + u * d;
-        // item rows are gathered G samples ahead of the arithmetic (ra[0] / rb[0]: this sample, ra[k]: sample s + k, the row of sample
-        // s + G in flight), their indices IA ahead and the class of an item G ahead; positions past the run's end re-read the
+        // item rows are gathered G = 2 samples ahead of the arithmetic (ra[0] / rb[0]: this sample, ra[k]: sample s + k, the row of sample
+        // s + G in flight), their indices IA = 3 ahead and the class of an item G ahead; positions past the run's end re-read the
         // last sample (result unused).  Nothing is used in the iteration that loads it: the counter the waits go by also counts the
         // atomics and returns in order, so a wait for a load issued after them is a wait for their acknowledgement from the memory
         // side.  What a load waits behind is therefore the atomics of min(G, IA - G) iterations ago: with few groups per SIMD
-        // (C2: 6040 groups on 1024 SIMDs) that distance IS the time of an iteration.
-        static_assert(IA > G && G >= 2, "indices ahead of the rows they address");
-        static_assert(ST == 0 || G == 2, "the own-history rule of the store route looks two samples back");
-        constexpr int GB = NEG1 ? 1 : G;  // the negative's gather distance
+        // (C2: 6040 groups on 1024 SIMDs) that distance IS the time of an iteration.  (Deeper pipelines -- up to rows 6 and ids 9 ahead --
+        // and a ring without register rotation were measured and were no faster: profiles/r04_s_probe_bpr_depth.txt.)
+        constexpr int G = 2, IA = 3;  // (the own-history rule of the store route looks G = 2 samples back)
+        // with the store route open for negatives their rows are gathered ONE sample ahead instead of two: what a store can
+        // overwrite is what other groups added between the gather and the store, and that window halves
+        constexpr int GB = NEG_STORE ? 1 : G;  // the negative's gather distance
         float p[NC], ra[G][NC], rb[GB][NC];
         const int last = end - 1;
         auto at = [&](int s) { return s <= last ? s : last; };
@@ -1073,16 +1049,14 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
         for (int k = 0; k < IA; k++) ii[k] = si[at(beg + k)], jj[k] = sj[at(beg + k)];
 #pragma unroll
         for (int k = 0; k < G; k++) sli[k] = slot_of[idx_i(ii[k], jj[k])], slj[k] = slot_of[idx_j(ii[k], jj[k])];
-        float p_in[SEG ? NC : 1];  // SEG: the row as this segment found it
         // the series in flight: `cur` the positive's row as this group has left it, `acc` its change not yet sent (of `pending`
         // samples), `cont` = the current sample continues the series of the one before
-        float cur[COMB ? NC : 1], acc[COMB ? NC : 1];
+        float cur[NC], acc[NC];
         bool cont = false;
         int pending = 0;
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             p[c] = load_row<MODE_ATOMIC>(pu + 16 * c + lane);
-            if (SEG) p_in[SEG ? c : 0] = p[c];
 #pragma unroll
             for (int k = 0; k < G; k++) ra[k][c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(ii[k]) * d + 16 * c + lane);
 #pragma unroll
@@ -1095,16 +1069,9 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
             const int i = ii[0], j = jj[0], slot = sli[0], slotj = slj[0];
             float(&a)[NC] = ra[0];
             float(&b)[NC] = rb[0];
-            float al[NC], bl[NC], ran[NC], rbn[NC];
-            if constexpr ((ST & ST_LIVE) != 0) {
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    al[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(i) * d + 16 * c + lane);
-                    bl[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(j) * d + 16 * c + lane);
-                }
-            }
+            float ran[NC], rbn[NC];
             // the positive's row of sample s + G: not gathered where that sample will continue a series (it computes from `cur`)
-            const bool gather_i = !(COMB && GORSE_BPR_SERIES_SKIP_GATHERS) || !(s + G <= last && continues(ii[G - 1], jj[G - 1], ii[G], jj[G]));
+            const bool gather_i = !GORSE_BPR_SERIES_SKIP_GATHERS || !(s + G <= last && continues(ii[G - 1], jj[G - 1], ii[G], jj[G]));
 #pragma unroll
             for (int c = 0; c < NC; c++) ran[c] = 0.0f;
             if (gather_i) {
@@ -1113,27 +1080,19 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
             }
 #pragma unroll
             for (int c = 0; c < NC; c++) rbn[c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(jj[GB]) * d + 16 * c + lane);
-            if constexpr (COMB) {
-                if (cont) {
+            if (cont) {
 #pragma unroll
-                    for (int c = 0; c < NC; c++) a[c] = cur[c];
-                }
+                for (int c = 0; c < NC; c++) a[c] = cur[c];
             }
-            const bool more = COMB && s < last && continues(i, j, ii[1], jj[1]);  // the next sample continues this one's series
+            const bool more = s < last && continues(i, j, ii[1], jj[1]);  // the next sample continues this one's series
             const bool valid = j >= 0;  // j < 0: the sampler found no negative for this sample (bpr_sample_items_kernel)
             float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
             if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
             if (hot.n_hot > 0 && neg_replicas && slotj >= 0) qj = hot_row(hot, slotj, group);
-#ifdef GORSE_PROBE
-            if (hot.warm_scratch && !(hot.n_hot > 0 && slot >= 0)) qi = hot.warm_scratch + (int64_t)cl(i) * d;
-            if (hot.warm_scratch && !(hot.n_hot > 0 && neg_replicas && slotj >= 0)) qj = hot.warm_scratch + (int64_t)cl(j) * d;
-#endif
-            bool st_i = false, st_j = false;
-            if constexpr ((ST & (ST_POS | ST_NEG)) != 0) {
-                const bool own_i = i == j || i == im1 || i == jm1 || i == im2 || i == jm2;
+            bool st_j = false;
+            if constexpr (NEG_STORE) {
                 const bool own_j = i == j || j == im1 || j == jm1 || j == im2 || j == jm2;
-                st_i = (ST & ST_POS) && slot == kCold && !own_i;
-                st_j = (ST & ST_NEG) && slotj == kCold && !own_j;
+                st_j = slotj == kCold && !own_j;
             }
             const float diff = D8 ? tree8(p[0] * a[0]) - tree8(p[0] * b[0]) : dot512_regs<NC>(p, a) - dot512_regs<NC>(p, b);
             const float ex = bpr_exp(-diff, exp_mode);
@@ -1147,41 +1106,27 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
                 const float t3 = mad(p[c], nreg, (a[c] - b[c]) * grad);
                 p[c] = valid ? mad(t3, lr, p[c]) : p[c];
             }
-            if constexpr (COMB) {
-                if (valid) {  // (every lane keeps the series: the lanes that mirror a row of eight need `cur` as the writers do)
+            if (valid) {  // (every lane keeps the series: the lanes that mirror a row of eight need `cur` as the writers do)
 #pragma unroll
-                    for (int c = 0; c < NC; c++) {
-                        acc[c] = pending > 0 ? acc[c] + t1[c] * lr : t1[c] * lr;  // a series of one sends t1 * lr, as the kernel did without series
-                        cur[c] = mad(t1[c], lr, a[c]);
-                    }
-                    if (!more || ++pending >= kSeriesFlush) {
-                        pending = 0;
-                        if (writer) {
+                for (int c = 0; c < NC; c++) {
+                    acc[c] = pending > 0 ? acc[c] + t1[c] * lr : t1[c] * lr;  // a series of one sends t1 * lr, as the kernel did without series
+                    cur[c] = mad(t1[c], lr, a[c]);
+                }
+                if (!more || ++pending >= kSeriesFlush) {
+                    pending = 0;
+                    if (writer) {
 #pragma unroll
-                            for (int c = 0; c < NC; c++)
-                                __hip_atomic_fetch_add(qi + 16 * c + lane, acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
+                        for (int c = 0; c < NC; c++)
+                            __hip_atomic_fetch_add(qi + 16 * c + lane, acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
-            } else if (!valid || !writer) {
-                // nothing to write
-            } else if (st_i) {
-#pragma unroll
-                for (int c = 0; c < NC; c++)
-                    __hip_atomic_store(qi + 16 * c + lane, mad(t1[c], lr, (ST & ST_LIVE) ? al[c] : a[c]), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-#pragma unroll
-                for (int c = 0; c < NC; c++)
-                    __hip_atomic_fetch_add(qi + 16 * c + lane, t1[c] * lr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             cont = more;
             if (!valid || !writer) {
             } else if (st_j) {
 #pragma unroll
                 for (int c = 0; c < NC; c++)
-                    __hip_atomic_store(qj + 16 * c + lane, mad(t2[c], lr, (ST & ST_LIVE) ? bl[c] : b[c]), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(qj + 16 * c + lane, mad(t2[c], lr, b[c]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
 #pragma unroll
                 for (int c = 0; c < NC; c++)
@@ -1206,152 +1151,13 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
         }
         if (writer) {
 #pragma unroll
-            for (int c = 0; c < NC; c++) {
-                if (SEG)  // one of `segs` writers of this row: its own change, added
-                    __hip_atomic_fetch_add(pu + 16 * c + lane, p[c] - p_in[SEG ? c : 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else  // the only writer of this row in the launch
-                    __hip_atomic_store(pu + 16 * c + lane, p[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            for (int c = 0; c < NC; c++)  // the only writer of this row in the launch
+                __hip_atomic_store(pu + 16 * c + lane, p[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (loss && (SUBS == 2 ? (glane & 7) == 0 : glane == 0) && my_loss != 0.0) atomicAdd(loss, my_loss);
     if (folders > 0) worker_done<true>(hot);
 }
-
-#ifdef GORSE_PROBE
-// ---- PROBE BUILD ONLY (make probe-lib; scripts/gpu_probe_bpr_depth.py, gpu_probe_bpr_c2_limits.py): the user-run kernel without a
-// register rotation (atomics only).  A measured dead end, kept so that the measurement can be repeated:
-// bpr_update_user_kernel keeps its gathered rows in a, a1, a2 and moves them down at the end of every iteration: the move of a2 is
-// a USE of the row loaded in that very iteration, the wait in front of it counts (in order) everything issued since -- and because
-// the atomics sit behind a lane-dependent branch the compiler has to assume they were not issued: `s_waitcnt vmcnt(0)` at the end
-// of every sample.  Here the ring is addressed by a compile-time step index (the loop is unrolled R times, no value ever moves), the
-// atomics are issued unconditionally (a sample past the run's end or without a negative adds 0.0f), the smallest wait in the loop
-// is vmcnt(18): no atomic of the last sample is ever waited for.  Result (profiles/r04_s_probe_bpr_depth.txt, _c2_limits.txt):
-// C2 0.615-0.629 ms against 0.619-0.629, d = 16 0.320 against 0.336, d = 8 0.415 against 0.436, C3 shard 11.5-12.4 against 11.1 --
-// the waits were never what the kernel is bound by.  What is (profiles/r04_s_probe_atomics3.txt): the atomic unit itself, which
-// sustains 318 G dwords/s on a 3704-row table when nothing reads it and 243 G/s when the same rows are also LOADED (as every sample
-// must); on a 30K-row table 302-317 G/s either way.
-template <int N, class F, int... K>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, K...>) {
-    (f(std::integral_constant<int, K>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    static_for_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
-
-template <int NC, bool D8, int R, int D>
-__global__ __launch_bounds__(kBlock) void bpr_update_user_ring_kernel(float *P, float *Q, const int32_t *__restrict__ si,
-                                                                      const int32_t *__restrict__ sj,
-                                                                      const int32_t *__restrict__ off, int32_t U, int d, float lr,
-                                                                      float reg, int exp_mode, double *loss, HotRows hot,
-                                                                      int folders, int neg_replicas) {
-    if ((int)blockIdx.x < folders) {
-        run_folders<true>(hot, Q, folders);
-        return;
-    }
-    static_assert(D >= 1 && R - D >= 2, "ids D steps ahead of the rows they address, rows at least two steps ahead of their use");
-    constexpr int G = R - D;  // rows and classes are gathered G samples ahead, ids R ahead
-    const int glane = threadIdx.x & (kGroup - 1);
-    const int lane = D8 ? (glane & 7) : glane;
-    auto mad = [](float x, float y, float z) { return D8 ? x * y + z : fmaf(x, y, z); };
-    // gpw groups of a wave work (4 = all; fewer = more waves for the same runs, the other lanes idle), the launch may use smaller
-    // workgroups than kBlock
-    const int gpw = (neg_replicas >> 4) & 7, wave = threadIdx.x >> 6, giw = (threadIdx.x & 63) / kGroup;
-    const int gpb = ((int)blockDim.x >> 6) * gpw;
-    int64_t group = (int64_t)((int)blockIdx.x - folders) * gpb + wave * gpw + giw;
-    const int64_t ngroups = (int64_t)((int)gridDim.x - folders) * gpb;
-    if (giw >= gpw) group = U;  // an idle group: no run
-    const float nreg = -reg;
-    double my_loss = 0.0;
-    const bool look_i = hot.n_hot > 0;
-    const bool look_j = hot.n_hot > 0 && (neg_replicas & 1);
-#ifdef GORSE_PROBE
-    const bool no_atomics = (neg_replicas & 2) != 0;  // probe: what the kernel costs without its item updates
-#else
-    constexpr bool no_atomics = false;
-#endif
-    const int32_t *slot_of = look_i ? hot.slot : si;
-    for (int64_t u = group; u < U; u += ngroups) {
-        const int beg = off[u], end = off[u + 1];
-        if (beg >= end) continue;
-        float *pu = P + u * d;
-        const int last = end - 1;
-        auto at = [&](int s) { return s <= last ? s : last; };
-        auto cl = [](int x) { return x < 0 ? 0 : x; };
-        auto idx_i = [&](int i_) { return look_i ? cl(i_) : beg; };
-        auto idx_j = [&](int i_, int j_) { return look_j ? cl(j_) : idx_i(i_); };
-        // ring slot K holds sample beg + m with m % R == K: its item ids, the items' classes, their rows
-        float p[NC], ra[R][NC], rb[R][NC];
-        int ii[R], jj[R], sli[R], slj[R];
-#pragma unroll
-        for (int k = 0; k < R; k++) ii[k] = si[at(beg + k)], jj[k] = sj[at(beg + k)];
-#pragma unroll
-        for (int k = 0; k < G; k++) sli[k] = slot_of[idx_i(ii[k])], slj[k] = slot_of[idx_j(ii[k], jj[k])];
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            p[c] = load_row<MODE_ATOMIC>(pu + 16 * c + lane);
-#pragma unroll
-            for (int k = 0; k < G; k++) {
-                ra[k][c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(ii[k]) * d + 16 * c + lane);
-                rb[k][c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(jj[k]) * d + 16 * c + lane);
-            }
-        }
-        // nothing pending on entry: what the loop's waits count is then what the loop itself issued (a pending load of the
-        // prologue would be "a few instructions old" at the head of every iteration as far as the compiler can tell)
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        for (int s0 = beg; s0 < end; s0 += R) {
-            static_for<R>([&](auto KC) {
-                constexpr int K = decltype(KC)::value, KP = (K + G) % R;
-                const int s = s0 + K;
-                const int i = ii[K], j = jj[K], slot = sli[K], slotj = slj[K];
-                const bool valid = j >= 0 && s < end;  // j < 0: the sampler found no negative (bpr_sample_items_kernel)
-                // sample s + R's ids into the slot this sample leaves; class and rows of sample s + G (its ids were loaded D steps ago)
-                ii[K] = si[at(s + R)], jj[K] = sj[at(s + R)];
-                sli[KP] = slot_of[idx_i(ii[KP])], slj[KP] = slot_of[idx_j(ii[KP], jj[KP])];
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    ra[KP][c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(ii[KP]) * d + 16 * c + lane);
-                    rb[KP][c] = load_row<MODE_ATOMIC>(Q + (int64_t)cl(jj[KP]) * d + 16 * c + lane);
-                }
-                float(&a)[NC] = ra[K];
-                float(&b)[NC] = rb[K];
-                float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
-                if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
-                if (look_j && slotj >= 0) qj = hot_row(hot, slotj, group);
-                const float diff =
-                    D8 ? group_tree8(p[0] * a[0]) - group_tree8(p[0] * b[0]) : dot512_regs<NC>(p, a) - dot512_regs<NC>(p, b);
-                const float ex = bpr_exp(-diff, exp_mode);
-                const float grad = ex / (1.0f + ex);
-                if (loss && glane == 0 && valid) my_loss += (double)log1pf(ex);
-                const float step = valid ? lr : 0.0f;
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    const float t1 = mad(a[c], nreg, p[c] * grad);
-                    const float t2 = mad(b[c], nreg, p[c] * (-grad));
-                    const float t3 = mad(p[c], nreg, (a[c] - b[c]) * grad);
-                    p[c] = valid ? mad(t3, lr, p[c]) : p[c];
-                    if (no_atomics) continue;
-                    if constexpr (D8) {  // lanes 0..7 carry the positive's row, their mirrors 8..15 the negative's: one instruction
-                        __hip_atomic_fetch_add((glane < 8 ? qi : qj) + lane, (glane < 8 ? t1 : t2) * step, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-                        __hip_atomic_fetch_add(qi + 16 * c + lane, t1 * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_fetch_add(qj + 16 * c + lane, t2 * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            });
-        }
-        if (!D8 || glane < 8) {
-#pragma unroll
-            for (int c = 0; c < NC; c++)  // the only writer of this row in the launch
-                __hip_atomic_store(pu + 16 * c + lane, p[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (loss && glane == 0 && my_loss != 0.0) atomicAdd(loss, my_loss);
-    if (folders > 0) worker_done<true>(hot);
-}
-#endif  // GORSE_PROBE
 
 // the whole scan by ONE workgroup, tile after tile (a few thousand counters: two launches and two dependencies fewer)
 __global__ __launch_bounds__(256) void scan_small_kernel(int32_t *__restrict__ data, int64_t m) {
@@ -1439,27 +1245,11 @@ bool user_runs_supported(const gorse_mf *h) {
 }
 
 // which item updates may take the store route (gorse_hip_test_set_bpr_store_mode)
-// ST_NEG: measured at C3 whole (profiles/r04_b_probe_bpr_stores_*.txt): update kernel 89 -> 60 ms per epoch, 4 % of the updates of cold rows
+// Cold negatives by store: measured at C3 whole (profiles/r04_b_probe_bpr_stores_*.txt): update kernel 89 -> 60 ms per epoch, 4 % of the updates of cold rows
 // overwritten, NDCG@10 0.6100 against 0.6096 with atomics only (sequential oracle 0.6126); the positive side stays atomic -- by store
 // it costs 0.003-0.005 of NDCG for 6 % more speed
 constexpr int kDefaultStoreMode = 1;
-int g_store_mode = kDefaultStoreMode;  // ST_* bits of bpr_update_user_kernel
-#ifdef GORSE_PROBE
-constexpr bool kProbeBuild = true;
-#else
-constexpr bool kProbeBuild = false;
-#endif
-int g_user_segments = 0;               // segments per user run of the SEG form (gorse_hip_test_set_bpr_user_segments): 0 = the library's choice
-// segments per user run: the probe build's hook, nFactors <= 32
-int user_segments(const gorse_mf *h) {
-#ifdef GORSE_PROBE
-    if (h->d <= 32 && g_user_segments > 0) return std::min(g_user_segments, 8);
-#endif
-    return 1;  // the shipped library runs one group per user run (see bpr_update_user_kernel, SEG)
-}
-int g_user_gpw = 4;                      // probe builds: groups of a wave that work in the ring kernel (4 = all)
-int g_user_block = kBlock;               // probe builds: threads per workgroup of the ring kernel
-int g_user_depth = 0;                  // probe builds: which (G, IA) pipeline of the atomics-only kernel (gorse_hip_test_set_bpr_user_depth)
+int g_store_mode = kDefaultStoreMode;  // 1 = NEG_STORE of bpr_update_user_kernel where the handle has cold items, 0 = atomics only
 
 // the replica rows of a slot lie next to each other (r04_a: 4 KB apart or n_hot rows apart makes no difference); n_hot stays 0 (no
 // replicas, no folders) until the launch opens them: open_hot
@@ -1477,8 +1267,7 @@ int open_hot(gorse_mf *h, HotRows &hot) {
 int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *bucket, size_t cap, float lr, float reg,
                             int exp_mode, double *loss, hipStream_t st, bool stores) {
     const int d = h->d;
-    const int segs = user_segments(h);
-    int64_t blocks = ceil_div(h->U * segs, (int64_t)kGroupsPerBlock * (d == 8 && GORSE_BPR_D8_PAIRS ? 2 : 1));  // nFactors 8: two runs per group
+    int64_t blocks = ceil_div(h->U, (int64_t)kGroupsPerBlock * (d == 8 && GORSE_BPR_D8_PAIRS ? 2 : 1));  // nFactors 8: two runs per group
     const int64_t capb = 256 * 16;
     if (blocks > capb) blocks = capb;
     HotRows hot = make_hot(h);
@@ -1487,71 +1276,18 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     // the negative's slot look-up is one more gather per sample: where a draw has a fair chance of meeting a hot item (hot_rows.hpp;
     // gorse_mf_create counted the negatives into the replica counts by the same rule)
     const int neg_rep = !(g_variant & (1 << 25)) && hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I) ? 1 : 0;
-#ifdef GORSE_PROBE
-    if (g_variant & (1 << 23)) {
-        static DevBuf<float> scratch;  // (a probe: never released)
-        if (scratch.n < (size_t)h->I * d) GORSE_TRY(scratch.alloc((size_t)h->I * d));
-        hot.warm_scratch = scratch.p;
-    }
-#endif
     dim3 grid((unsigned)blocks), block(kBlock);
-#ifdef GORSE_PROBE
-    const int64_t rblocks = std::min<int64_t>(ceil_div(h->U, g_user_block / 64 * g_user_gpw), capb * (kBlock / g_user_block)) + folders;
-    dim3 rgrid((unsigned)rblocks), rblock(g_user_block);
-#endif
     // cold items by store only in GORSE_BPR_HOGWILD_STORES and where the handle has any (n_cold) -- the atomics-only instantiation otherwise
-    const int store_mode = stores && h->n_cold > 0 ? g_store_mode : 0;
-    // the library ships two forms of the kernel (atomics only; cold negatives by store); the positive-side and re-reading forms of
-    // the ablation (profiles/r04_*_probe_bpr_stores_*.txt) exist in `make probe-lib` builds only
-#ifdef GORSE_PROBE
-#define PROBE_CASES(NC) case 3: LAUNCH2(NC, 3, 2, 3); break; case 5: LAUNCH2(NC, 5, 2, 3); break; case 7: LAUNCH2(NC, 7, 2, 3); break;
-#define PROBE_DEPTHS(NC)                                                                                               \
-    case 1: LAUNCH2(NC, 0, 2, 4); break;                                                                               \
-    case 2: LAUNCH2(NC, 0, 3, 5); break;                                                                               \
-    case 3: LAUNCH2(NC, 0, 3, 6); break;                                                                               \
-    case 4: LAUNCH2(NC, 0, 4, 6); break;                                                                               \
-    case 5: LAUNCH2(NC, 0, 4, 8); break;                                                                               \
-    case 6: LAUNCH2(NC, 0, 6, 9); break;                                                                               \
-    case 10: LAUNCHR(NC, 3, 1); break;                                                                                 \
-    case 11: LAUNCHR(NC, 4, 2); break;                                                                                 \
-    case 12: LAUNCHR(NC, 6, 3); break;                                                                                 \
-    case 13: LAUNCHR(NC, 8, 4); break;                                                                                 \
-    case 14: LAUNCHR(NC, 6, 2); break;
-#else
-#define PROBE_CASES(NC)
-#define PROBE_DEPTHS(NC)
-#endif
-#define LAUNCH2(NC, ST, G, IA)                                                                                         \
-    do {                                                                                                               \
-        if constexpr (NC <= 2 && G == 2 && IA == 3 && kProbeBuild) {                                                   \
-            if (segs > 1) {                                                                                            \
-                bpr_update_user_kernel<(NC == 0 ? 1 : NC), ST, NC == 0, G, IA, true><<<grid, block, 0, st>>>(          \
-                    h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, folders, \
-                    neg_rep, segs);                                                                                    \
-                break;                                                                                                 \
-            }                                                                                                          \
-        }                                                                                                              \
-        bpr_update_user_kernel<(NC == 0 ? 1 : NC), ST, NC == 0, G, IA><<<grid, block, 0, st>>>(                        \
-            h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, folders, neg_rep); \
-    } while (0)
-#ifdef GORSE_PROBE
-#define LAUNCHR(NC, R, D)                                                                                              \
-    bpr_update_user_ring_kernel<(NC == 0 ? 1 : NC), NC == 0, R, D><<<rgrid, rblock, 0, st>>>(                          \
-        h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, folders, \
-        neg_rep | ((g_variant >> 23) & 2) | (g_user_gpw << 4))
-#endif
+    const bool neg_store = stores && h->n_cold > 0 && g_store_mode == 1;
+#define LAUNCH2(NC, NEG_STORE)                                                                                         \
+    bpr_update_user_kernel<(NC == 0 ? 1 : NC), NEG_STORE, NC == 0><<<grid, block, 0, st>>>(                            \
+        h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, folders, neg_rep)
 #define LAUNCH(NC)                                                                                                     \
     do {                                                                                                               \
-        switch (store_mode) {                                                                                          \
-        case 1: LAUNCH2(NC, 1, 2, 3); break;                                                                           \
-        PROBE_CASES(NC)                                                                                                \
-        default:                                                                                                       \
-            switch (g_user_depth) {                                                                                    \
-            PROBE_DEPTHS(NC)                                                                                           \
-            default: LAUNCH2(NC, 0, 2, 3); break;                                                                      \
-            }                                                                                                          \
-            break;                                                                                                     \
-        }                                                                                                              \
+        if (neg_store)                                                                                                 \
+            LAUNCH2(NC, true);                                                                                         \
+        else                                                                                                           \
+            LAUNCH2(NC, false);                                                                                        \
     } while (0)
     if (d == 8)
         LAUNCH(0);
@@ -1564,10 +1300,7 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     else
         LAUNCH(8);
 #undef LAUNCH2
-#undef LAUNCHR
 #undef LAUNCH
-#undef PROBE_CASES
-#undef PROBE_DEPTHS
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
@@ -1902,18 +1635,10 @@ extern "C" int32_t gorse_mf_bpr_schedule(gorse_mf *h, int32_t *user_runs) {
     return GORSE_OK;
 }
 extern "C" void gorse_hip_test_set_variant(int32_t v) { g_variant = v; }
-extern "C" void gorse_hip_test_set_bpr_user_depth(int32_t v) {
-    g_user_depth = v & 0xff;
-    g_user_block = ((v >> 8) & 0xfff) ? ((v >> 8) & 0xfff) : kBlock;  // bits 8..19: threads per workgroup of the ring kernel (64 / 128 / 256)
-    g_user_gpw = (v >> 20) ? (v >> 20) : 4;                           // bits 20..: working groups per wave (1 / 2 / 4)
-}
 extern "C" void gorse_hip_test_set_bpr_chunk(int64_t samples) { g_chunk_override = samples; }
-extern "C" void gorse_hip_test_set_bpr_user_segments(int32_t segments) { g_user_segments = segments < 0 ? 0 : segments; }
 extern "C" void gorse_hip_test_set_bpr_store_mode(int32_t store_mode) {
-    g_store_mode = store_mode < 0 ? kDefaultStoreMode : store_mode;
-#ifndef GORSE_PROBE
-    if (g_store_mode & ~1) g_store_mode &= 1;  // forms the shipped library does not carry fall back to the nearest one it does
-#endif
+    // only bit 0 selects a form the library carries (cold negatives by store); the forms bits 1 and 2 asked for were removed
+    g_store_mode = store_mode < 0 ? kDefaultStoreMode : (store_mode & 1);
 }
 extern "C" void gorse_hip_test_set_bpr_fold_period(int32_t ticks) { g_fold_period = ticks > 0 ? (uint32_t)ticks : kDefaultFoldPeriod; }
 extern "C" int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3) {
@@ -1941,13 +1666,6 @@ extern "C" int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items, int
     if (rep && h->hot_rows > 0)
         GORSE_HIP_CHECK(hipMemcpy(rep, h->hot_rep.p, (size_t)h->hot_rows * h->d * sizeof(float), hipMemcpyDeviceToHost));
     return GORSE_OK;
-}
-extern "C" int32_t gorse_hip_test_probe_build(void) {
-#ifdef GORSE_PROBE
-    return 1;
-#else
-    return 0;
-#endif
 }
 
 extern "C" int32_t gorse_bpr_epoch(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t seed, uint64_t epoch,

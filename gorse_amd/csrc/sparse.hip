@@ -59,9 +59,6 @@ struct gorse_sparse {
         std::vector<sparse::Work> work;
     } plan;
     int64_t last_sym[4] = {0, 0, 0, 0};  // the last call: ran symmetric, rows redone, foreign entries ranked, longest foreign list
-    DevBuf<sparse::Trace> trace;  // probe (gorse_hip_test_sparse_trace)
-    std::vector<sparse::Trace> trace_host;
-    bool trace_on = false;
     KernelProfile prof{1};
     int64_t last_postings = 0, last_hits = 0;
     int32_t use() const {
@@ -114,9 +111,6 @@ int32_t launch_tiles(const TileArgs &a, unsigned grid, size_t lds, bool atomic, 
     auto kern = atomic ? sparse::sparse_tile_kernel<KP, true, false> : sparse::sparse_tile_kernel<KP, false, false>;
     if (sym) kern = atomic ? sparse::sparse_tile_kernel<KP, true, false, 1> : sparse::sparse_tile_kernel<KP, false, false, 1>;
     if (sym && a.sym.front) kern = atomic ? sparse::sparse_tile_kernel<KP, true, false, 2> : sparse::sparse_tile_kernel<KP, false, false, 2>;
-#ifdef GORSE_PROBE  // the trace instantiation exists in `make probe-lib` builds only
-    if (a.trace && !sym) kern = atomic ? sparse::sparse_tile_kernel<KP, true, true> : sparse::sparse_tile_kernel<KP, false, true>;
-#endif
     GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     kern<<<dim3(grid), dim3(sparse::kBlock), lds, s>>>(a);
     return GORSE_OK;
@@ -156,7 +150,7 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
     // no tail there; one work item per group is what costs (the C3 shard pass: 24.3 ms with the rows longer than 2048 split, 21.9 with
     // those longer than 4096, profiles/r06_zo_probe_gpu_probe_sparse_knobs.txt): such a pass splits the front's rows only.
     const bool sym_call = g_sparse_sym != 0 && (g_sparse_sym > 0 || h->ngroups >= 2) && qp == h->r_ptr.p && q_first == 0 && nq == h->N &&
-                          exclude_self && !excl_dev && !h->has_mask && !h->trace_on;
+                          exclude_self && !excl_dev && !h->has_mask;
     const int64_t split_used = sym_call && h->front_cut > 0 && h->order.pad > 0 ? h->front_cut : g_sparse_split;
     const bool plan_hit = qp == h->r_ptr.p && plan.valid && plan.q_first == q_first && plan.nq == nq && plan.split == split_used &&
                           plan.heavy == g_sparse_heavy;
@@ -310,7 +304,6 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
     std::vector<sparse::Work> &work = plan.work;
     std::vector<int32_t> &heavy_t = plan.heavy_t, &heavy_pslot = plan.heavy_pslot, &nparts = plan.nparts;
     const bool one_launch = longs.size() <= per_launch;  // (a plan is kept across calls only then)
-    h->trace_host.clear();
     for (size_t l0 = 0; l0 == 0 || l0 < longs.size(); l0 += per_launch) {
         const size_t l1 = std::min(longs.size(), l0 + per_launch);
         if (!(plan_hit && one_launch)) {
@@ -368,13 +361,7 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
         // 18.7 ms with the dense-vector kernel 18.0 beside it, against 20.4 with 13.9).
         a.work = h->work.p, a.n_work = (int32_t)work.size();
         a.part_keys = h->part_keys.p, a.part_cnt = h->part_cnt.p;
-        a.trace = nullptr;
-#ifdef GORSE_PROBE
-        if (h->trace_on) {
-            GORSE_TRY(h->trace.ensure(work.size()));
-            a.trace = h->trace.p;
-        }
-#endif
+        a.trace = nullptr;  // (the kernel's TRACE instantiation is never built: see sparse_kernels.hpp)
         if (!work.empty()) GORSE_TRY(launch_work(work.size(), sym));
         if (!heavy_t.empty()) {
             const size_t nh = heavy_t.size();
@@ -405,13 +392,8 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
         }
         if (!heavy_t.empty()) GORSE_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         if (n_long > 0) GORSE_TRY(launch_merge(n_long));
-        // the host lists (work, heavy_*, nparts, split_t) and the trace buffer are reused by the next iteration
-        if ((n_long > 0 && !one_launch) || h->trace_on) GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->trace_on && a.trace) {  // (a.trace stays null outside `make probe-lib` builds: nothing was recorded)
-            const size_t at = h->trace_host.size();
-            h->trace_host.resize(at + work.size());
-            GORSE_HIP_CHECK(hipMemcpy(h->trace_host.data() + at, h->trace.p, work.size() * sizeof(sparse::Trace), hipMemcpyDeviceToHost));
-        }
+        // the host lists (work, heavy_*, nparts, split_t) are reused by the next iteration
+        if (n_long > 0 && !one_launch) GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
     }
     int32_t n_redo = 0;
     bool redo_overwrote = false;
@@ -783,23 +765,6 @@ extern "C" void gorse_hip_test_sparse_sym_stats(const gorse_sparse *h, int64_t o
     for (int i = 0; i < 4; i++) out[i] = h ? h->last_sym[i] : 0;
 }
 extern "C" void gorse_hip_test_set_sparse_table(int32_t cap_shift) { g_sparse_cap_shift = cap_shift >= 2 && cap_shift <= 6 ? cap_shift : 2; }
-// probe: per-work-item records of the NEXT calls of this handle (on != 0), or the records of the last call: up to cap rows of
-// 16 uint64 {t0, t1 (100 MHz ticks), query, group + 1 of a long query (0 = the whole query), entries, chunks taken 64 lists at once, their rounds, segments walked
-// one list at a time, groups read back densely, groups read back by re-walking, flattened batches, rows shared inside a batch}; returns the number of work items
-extern "C" int64_t gorse_hip_test_sparse_trace(gorse_sparse *h, int32_t on, uint64_t *out, int64_t cap) {
-    if (!h) return -1;
-    h->trace_on = on != 0;
-    if (!out) return (int64_t)h->trace_host.size();
-    const int64_t n = std::min<int64_t>(cap, (int64_t)h->trace_host.size());
-    for (int64_t i = 0; i < n; i++) {
-        const sparse::Trace &t = h->trace_host[(size_t)i];
-        uint64_t *o = out + i * 16;
-        o[10] = t.batches, o[11] = t.shared_rows, o[12] = t.ticks_once, o[13] = t.ticks_flat, o[14] = t.ticks_back, o[15] = t.ticks_head;
-        o[0] = t.t0, o[1] = t.t1, o[2] = (uint64_t)t.t, o[3] = (uint64_t)(t.part + 1), o[4] = t.entries;
-        o[5] = t.fast_chunks, o[6] = t.rounds, o[7] = t.slow_segments, o[8] = t.dense_groups, o[9] = t.sparse_groups;
-    }
-    return (int64_t)h->trace_host.size();
-}
 extern "C" void gorse_hip_test_set_sparse_tile(int32_t rows) { g_sparse_tile = rows; }
 extern "C" void gorse_hip_test_set_sparse_split(int64_t entries) { g_sparse_split = entries; }
 extern "C" void gorse_hip_test_set_sparse_heavy(int64_t entries) { g_sparse_heavy = entries; }

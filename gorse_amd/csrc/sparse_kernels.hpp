@@ -71,7 +71,8 @@ struct Work {
                     // runs at a raised priority
 };
 
-// probe (gorse_hip_test_sparse_trace): what one work item did
+// what one work item did: the record of the TRACE instantiation of sparse_tile_kernel, which nothing builds any more (its hook and the
+// probe build are gone; the parameter stays because taking the counters out changed the register allocation of the kernel)
 struct Trace {
     unsigned long long t0, t1;  // s_memrealtime (100 MHz) at its start / end
     int32_t t, part;
@@ -187,7 +188,7 @@ struct TileArgs {
     unsigned long long *part_keys;  // per (pslot, group): the best KP keys of the part in any order, padded with 0
     int32_t *part_cnt;              // per (pslot, group): rows scoring above / below zero
     unsigned long long *stat;       // [0] += postings walked, [1] += rows with a non-zero score
-    Trace *trace;                   // probe: one record per work item, or null
+    Trace *trace;                   // always null (TRACE instantiations only)
     SymArgs sym;                    // the SYM instantiation's whole-query items (see SymArgs)
 };
 

@@ -648,10 +648,10 @@ extern "C" int32_t gorse_hip_test_topk_get_pilot_state(gorse_topk *h, uint8_t *f
 // test hook: 0 = automatic path choice, 1 = path A only (literal scan), 2 = path B whenever its operands exist
 extern "C" void gorse_hip_test_set_topk_path(int32_t path) { gorse::g_topk_force_path = path; }
 extern "C" void gorse_hip_test_set_topk_variant(int32_t v) { gorse::g_topk_variant = v; }
-// probe: the 8 phase counters of the last instrumented sweep (variant bit 4) of this handle
+// probe: the counters of the last tie replay that ran with variant bit 4 on this handle
 extern "C" int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out16) {
     if (!h || !out16) return fail(GORSE_ERR_INVALID, "NULL argument");
-    if (h->sweep_prof.n < 16) return fail(GORSE_ERR_INVALID, "no instrumented sweep has run on this handle");
+    if (h->sweep_prof.n < 16) return fail(GORSE_ERR_INVALID, "no search with variant bit 4 has run on this handle");
     GORSE_TRY(h->use());
     GORSE_HIP_CHECK(hipMemcpyAsync(out16, h->sweep_prof.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));

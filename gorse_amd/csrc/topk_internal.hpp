@@ -40,7 +40,7 @@ struct gorse_topk {
     gorse::DevBuf<uint8_t> cflag;
     gorse::DevBuf<int32_t> res_idx, res_cnt;
     gorse::DevBuf<float> res_dist;
-    // tie replay (history sweep of the flagged queries + topk_tie_sort_kernel + topk_tie_replay_kernel)
+    // tie replay (history sweep of the flagged queries + topk_tie_sort_kernel + topk_tie_replay_lane_kernel)
     gorse::DevBuf<int32_t> rp_pos, rp_ccnt, rp_hcnt, fl_pos;  // fl_*: the chunk's flagged queries, listed on the device (flag_compact_kernel)
     gorse::DevBuf<int64_t> fl_self;
     gorse::DevBuf<long long> fl_cnt;
@@ -52,7 +52,7 @@ struct gorse_topk {
     gorse::DevBuf<uint8_t> rp_flag;
     gorse::DevBuf<int32_t> rp_sidx, rp_scount;
     gorse::DevBuf<float> rp_sdst;
-    gorse::DevBuf<unsigned long long> sweep_prof;  // probe: phase counters of the instrumented sweep
+    gorse::DevBuf<unsigned long long> sweep_prof;  // probe: counters of the tie replay (variant bit 4, gorse_hip_test_get_sweep_profile)
     gorse::KernelProfile prof{GORSE_PROF_TOPK_NCLASSES};
     // gorse_topk_set_mask: rows with mask == 0 take no part in any search (as if they had never been added)
     gorse::DevBuf<uint8_t> mask;

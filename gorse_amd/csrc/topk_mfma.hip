@@ -37,40 +37,17 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxRB = 4;      // a tile holds RB 32-row MFMA blocks (RB = 2 or 4: 64 or 128 candidate rows per barrier)
-#ifndef GORSE_SWEEP_WAVES
-#define GORSE_SWEEP_WAVES 8
-#endif
-constexpr int kWavesMain = GORSE_SWEEP_WAVES;  // waves per workgroup of the main sweep, two per SIMD (a build-time probe switch)
-#ifndef GORSE_SWEEP_NCB
-#define GORSE_SWEEP_NCB 2
-#endif
-#ifndef GORSE_SWEEP_ORDER
-#define GORSE_SWEEP_ORDER 0
-#endif
-#ifndef GORSE_SWEEP_PIPE
-#define GORSE_SWEEP_PIPE 1
-#endif
-#ifndef GORSE_SWEEP_HALVES
-#define GORSE_SWEEP_HALVES 1
-#endif
-#ifndef GORSE_SWEEP_YOUNG_PRIO
-#define GORSE_SWEEP_YOUNG_PRIO 0  // A/B switch: 1 = the second-dispatched half of a workgroup's waves runs the tile loop at s_setprio 1
-#endif
-constexpr int kNcbMain = GORSE_SWEEP_NCB;  // 32-query column blocks per wave for operand depths up to 8 (probe switch)
+constexpr int kWavesMain = 8;  // waves per workgroup of the main sweep, two per SIMD
+constexpr int kNcbMain = 2;    // 32-query column blocks per wave for operand depths up to 8
 // the history sweep serves the few queries with ties: small workgroups (2 waves = 64 * NCB queries) spread them over
 // many CUs instead of a handful of 8-wave workgroups; deep operands keep more waves (the tile prefetch registers of a
 // thread grow as the workgroup shrinks)
-// Round 6 (GORSE_HIST_DMA): at the power-of-two depths that have LDS-DMA tiles the history sweep takes the main sweep's form instead --
+// Round 6: at the power-of-two depths that have LDS-DMA tiles the history sweep takes the main sweep's form instead --
 // eight waves, 512 queries per workgroup, 64-row DMA tiles: the two-wave workgroups staged their tiles through registers and ran
 // the matrix pipe at 0.22 PFLOP/s (C4: 11.7 ms for 10,136 queries against 9.5 ms; profiles/r06_zzk_probe_topk_c4_hist_dma_warm.txt).
 // The other depths keep the two-wave form.
-#ifndef GORSE_HIST_DMA
-#define GORSE_HIST_DMA 1
-#endif
-constexpr bool sweep_hist_dma(int kp) { return GORSE_HIST_DMA && (kp == 2 || kp == 4 || kp == 8); }
+constexpr bool sweep_hist_dma(int kp) { return kp == 2 || kp == 4 || kp == 8; }
 constexpr int sweep_waves(bool hist, int kp) { return !hist || sweep_hist_dma(kp) ? kWavesMain : (kp <= 8 ? 2 : (kp <= 12 ? 4 : 8)); }
-constexpr int kWaves = kWavesMain;
-[[maybe_unused]] constexpr int kThreads = kWaves * 64;
 // Tiles reach LDS by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave-instruction, no VGPR round trip, no ds_write pass) when
 // the operand depth is a power of two and the sweep is a main sweep: the LDS image of a tile is then lane-linear (unpadded
 // rows), and the 16-byte pieces of a row are XOR-swizzled by the row number on the SOURCE address and again on the read, so
@@ -111,7 +88,7 @@ constexpr int kEPL = kCap / 64;
 constexpr int kCompactAt = kCap - 64;   // compact a list once it holds more than this (a block adds <= 32)
 constexpr int kOverflowAt = kCap - 128; // a compaction that keeps more than this cannot make progress
 constexpr int kMaxKth = 256;
-constexpr int kHistCap = 4096;          // history entries per query of the tie-replay sweep (see topk_tie_replay_kernel)
+constexpr int kHistCap = 4096;          // history entries per query of the tie-replay sweep (see ReplayParams)
 constexpr int kReplayCap = 8192;        // power of two >= kCap + kHistCap: entries the replay sorts
 constexpr int64_t kReplayChunk = 16384; // flagged queries per history sweep (history buffers = 512 MB per row slice)
 constexpr int kMaxSlices = 8;           // row slices of a history sweep (see topk_tie_sort_kernel)
@@ -141,7 +118,8 @@ struct SweepParams {
     int kth;
     int compact_at;        // a sub-list longer than this triggers the compaction of its query (<= kCompactAt / 2)
     int ep;                // EP_SCALE / EP_BIAS / EP_COARSE: what the epilogue does with the per-row values (host side: picks the kernel)
-    unsigned long long *prof;  // PROF instantiations: 16 cycle / event counters summed over all waves
+    unsigned long long *prof;  // host side only: the handle's counters when variant bit 4 asks the tie replay to count (ReplayParams::prof);
+                               // the main sweep then keeps its square form.  No sweep reads it.
     // warm start (see topk_mfma_search): a PILOT sweep walks every tile_stride-th tile with kth = a small j and writes the
     // threshold it ends with to f_out; the main sweep starts from f0 and verifies it (compact_query: a threshold that a later
     // K-th-best bound does not reach flags the query 2 = "sweep again from -inf")
@@ -303,11 +281,6 @@ constexpr int EP_COARSE = 3;  // the block's LARGEST raw score times the extreme
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ float max2f(float a, float b) { return fmaxf(a, b); }
 
-// PROF (probe only): s_memtime stamps around the phases of the tile loop, summed over the waves into p.prof:
-// [0] tile movement (DMA issue / tile store + prefetch issue), [1] MFMA + epilogues (candidate paths included), [2] candidate
-// paths alone, [3] waiting for a tile, [4] row blocks examined, [5] row blocks that took the candidate path, [6] whole kernel,
-// [7] waves, [8] candidate path: set-up + row scaling, [9] appends, [10] compaction check / compaction, [11] candidate paths
-//
 // SYM -- the symmetric form of an all-pairs sweep.  When the queries are the stored rows sym_q0 .. sym_q0 + nq themselves, the
 // score of (query c, row r) is also the score of (query r, row c): the workgroup of query block C multiplies only the row tiles
 // that do NOT lie in a later query block (the rows before the query range, the query blocks 0 .. C, the rows behind the range) and,
@@ -319,19 +292,15 @@ __device__ __forceinline__ float max2f(float a, float b) { return fmaxf(a, b); }
 // is covered exactly once: by the query's own workgroup when the row's tile is not one it skips, else by the workgroup of the
 // row's block (tests/test_topk_sym_schedule_cpu.py walks the schedule).  Workgroups are issued longest first (block C = grid - 1 -
 // blockIdx.x sweeps C + 1 query blocks): half the MFMA work of the square sweep, and no partial last round.
-template <int KP, int NCB, int EP, bool HIST, int RB, bool PROF = false, bool SYM = false>
+template <int KP, int NCB, int EP, bool HIST, int RB, bool SYM = false>
 __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) + 3) / 4 < 2 ? 2 : (sweep_waves(HIST, KP) + 3) / 4) void topk_sweep_kernel(SweepParams p) {
     constexpr int kWaves = sweep_waves(HIST, KP);
     constexpr int kThreads = kWaves * 64;
     constexpr int kTR = 32 * RB;
     constexpr bool SCALE = EP != EP_NONE;  // a per-row value travels with the tile
-    unsigned long long c_store = 0, c_comp = 0, c_slow = 0, c_bar = 0, n_blk = 0, n_slow = 0, t_begin = 0, ts = 0;
-    unsigned long long c_free = 0, c_issue = 0, c_land = 0, c_post = 0;  // the tile top: buffer wait, DMA issue, landing wait, announcement
-    unsigned long long c_s1 = 0, c_s2 = 0, c_s3 = 0, n_hits = 0;
-    if (PROF) t_begin = __builtin_amdgcn_s_memtime();
     constexpr int KPAD = KP * 16;
     constexpr bool DMA = sweep_dma(KP, HIST, RB, kWaves);
-    constexpr bool PIPE = GORSE_SWEEP_PIPE && KP <= 8 && !HIST;  // row blocks software-pipelined: see the row-block loop
+    constexpr bool PIPE = KP <= 8 && !HIST;  // row blocks software-pipelined: see the row-block loop
     static_assert(!DMA || SCALE, "the DMA sweeps mask the rows past N through the row values (NaN padding)");
     // register staging: +16 B per row, consecutive rows start 4 banks apart, ds_read_b128 conflict-free; DMA: unpadded rows,
     // the pieces of a row swizzled instead (see piece_swizzle)
@@ -341,7 +310,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
     constexpr int CHUNKS = kTR * KP * 2;  // 16-byte pieces per tile
     constexpr int CPT = (CHUNKS + kThreads - 1) / kThreads;
     constexpr int NBUF = sweep_bufs(KP, RB, BQ, kWaves, HIST, SYM);
-    static_assert(!SYM || (DMA && !HIST && !PROF && BQ % kTR == 0 && EP != EP_NONE), "SYM: a DMA main sweep whose query blocks are whole tiles");
+    static_assert(!SYM || (DMA && !HIST && BQ % kTR == 0 && EP != EP_NONE), "SYM: a DMA main sweep whose query blocks are whole tiles");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *s_tile = smem;
     float *s_rs = reinterpret_cast<float *>(smem + (size_t)NBUF * kTR * ROWB);
@@ -468,8 +437,8 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
     // eight at the top of every tile, both waves of every SIMD stood in that phase together (17 % of the sweep,
     // profiles/r03_l_probe_c4_prof.txt).  DMA instruction j of issuing wave wi covers pieces [(wi * DPW + j) * 64, +64) of
     // the tile; the row values (one dword per row) follow as instructions of 64 rows each, issued by the first kTR / 64 of them.
-    constexpr int ISS = !DMA ? 1 : (GORSE_SWEEP_HALVES && kWaves >= 4 ? kWaves / 2 : kWaves);  // waves that move one tile
-    constexpr bool HALVES = DMA && ISS < kWaves;
+    static_assert(!DMA || kWaves == kWavesMain, "every DMA sweep has the main sweep's workgroup: its waves move the tiles in two halves");
+    constexpr int ISS = DMA ? kWaves / 2 : 1;  // waves that move one tile
     constexpr int DPW = DMA ? CHUNKS / 64 / ISS : 0;  // tile instructions per issuing wave
     static_assert(!DMA || (CHUNKS % (64 * ISS) == 0 && kTR % 64 == 0 && kTR / 64 <= ISS), "DMA tiling");
     constexpr int RSW = DMA ? kTR / 64 : 0;              // issuing waves that also move a row-value instruction
@@ -479,7 +448,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
     // The DMA is issued from inline assembly: the builtin makes hipcc treat every later LDS access of the kernel (the tile
     // counters, the fragment reads) as dependent on it and put s_waitcnt vmcnt(0) in front -- which drains the very tiles
     // that are meant to stay in flight.  An asm statement is invisible to that bookkeeping (cdna_hip_programming.md 5.7);
-    // the waits are dma_wait's, by count.  M0 = LDS destination of lane 0; the statement saves and restores it.
+    // the waits are dma_wait's.  M0 = LDS destination of lane 0; the statement saves and restores it.
     // Addressing: the tile's first byte is a scalar (it advances by one tile per iteration), the lane's place inside the
     // tile a 32-bit register computed once -- global_load_lds with an SGPR base and a VGPR offset.  The last tile, whose
     // rows may lie past N, clamps its rows instead (their scores are discarded through the NaN padding of the row values).
@@ -488,7 +457,6 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
     const unsigned lds_fq = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)s_fq;
     const unsigned lds_fqr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)s_fqr;
     constexpr bool RAWF_ = EP == EP_COARSE && DMA;  // (RAWF below)
-    constexpr int NXD = SYM ? (RAWF_ ? 2 : 1) : 0;  // SYM: extra row-value DMA instructions per tile of the first RSW issuing waves
     unsigned dsrc[DMA ? DPW : 1];  // byte offset of this lane's piece of instruction j from the tile's first byte
     if constexpr (DMA) {
 #pragma unroll
@@ -545,18 +513,9 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
             }
         }
     };
-    // "everything this wave issued before the DMA instructions of its last `keep` (0 or 1) tiles has completed": loads (the DMA
-    // among them) retire in order, so once no more than one tile's instructions are outstanding, every older tile of this wave
-    // is in LDS -- whatever stores (the candidate appends) are still on their way.
-    auto dma_wait = [&](int keep) {
-        if constexpr (DMA) {
-            if (keep == 0)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (wi < RSW)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW + 1 + NXD) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW) : "memory");
-        }
+    // everything this wave has issued is complete: the tile it moved is in LDS (a wave has one tile in flight at a time)
+    auto dma_wait = [&]() {
+        if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     auto post = [&](int *ctr) {  // DMA: this wave's part of a tile is in LDS (dma_wait came first)
         asm volatile("" ::: "memory");
@@ -599,22 +558,14 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     __syncthreads();  // the per-query words and the counters are initialised
-    if constexpr (HALVES) {
+    if constexpr (DMA) {
         if (grp == 0 && NT > 0) {
             dma_tile(0, 0);
-            dma_wait(0);
+            dma_wait();
             landed(0);
             post(&s_sync[0]);
         }
         if (grp == 1 && NT > 1) dma_tile(1, 1);  // announced at the top of tile 0
-    } else if constexpr (DMA) {
-        if (NT > 0) dma_tile(0, 0);
-        if (NT > 1) dma_tile(1, 1);
-        if (NT > 0) {
-            dma_wait(NT > 1 ? 1 : 0);  // tile 0 has landed (tile 1 may be in flight)
-            landed(0);
-            post(&s_sync[0]);
-        }
     } else {
         if (NT > 0) {
             load_tile(0);
@@ -692,21 +643,10 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
         return DMA ? *reinterpret_cast<const bf16x8 *>(blk + aoff[DMA ? ks : 0])
                    : *reinterpret_cast<const bf16x8 *>(blk + (lane & 31) * ROWB + (lane >> 5) * 16 + ks * 32);
     };
-    // MI355X_MICROARCH.md "Two waves per SIMD", item 4: of the two waves that share a SIMD the younger one (w >= kWaves / 2) loses the
-    // issue arbitration on every segment; a static priority for that half is the A/B switch GORSE_SWEEP_YOUNG_PRIO
-    const bool young = GORSE_SWEEP_YOUNG_PRIO && !HIST && wu >= kWaves / 2;
-    auto base_prio = [&]() {
-        if (young)
-            __builtin_amdgcn_s_setprio(1);
-        else
-            __builtin_amdgcn_s_setprio(0);
-    };
-    if (GORSE_SWEEP_YOUNG_PRIO) base_prio();
     int buf = 0, round = 0;  // tile t lives in buffer t % NBUF and is that buffer's (t / NBUF)-th tile
     for (int64_t t = 0; t < NT; t++) {
-        if (PROF) ts = __builtin_amdgcn_s_memtime();
         const int nb = buf + 1 == NBUF ? 0 : buf + 1;
-        if constexpr (HALVES) {
+        if constexpr (DMA) {
             // This wave's half moves the tiles of its parity: at such a tile's top it issues tile t + 2 (into the buffer tile
             // t + 2 - NBUF was read from); at the other tiles' tops it waits for what it issued a tile ago -- everything it has
             // in flight: the appends of the last row blocks ride along, a few hundred cycles now and then -- and announces
@@ -714,92 +654,24 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
             const int b2 = nb + 1 == NBUF ? 0 : nb + 1;
             if ((int)(t & 1) == grp) {
                 if (t + 2 < NT) {
-                    if (t + 2 >= NBUF) {
-                        unsigned long long tw = 0;
-                        if (PROF) tw = __builtin_amdgcn_s_memtime();
-                        wait_for(&s_sync[NBUF + b2], kWaves * (int)((t + 2) / NBUF));
-                        if (PROF) {
-                            const unsigned long long now = __builtin_amdgcn_s_memtime();
-                            c_bar += now - tw;
-                            c_free += now - tw;
-                        }
-                    }
-                    unsigned long long ti = 0;
-                    if (PROF) ti = __builtin_amdgcn_s_memtime();
+                    if (t + 2 >= NBUF) wait_for(&s_sync[NBUF + b2], kWaves * (int)((t + 2) / NBUF));
                     dma_tile(t + 2, b2);
-                    if (PROF) c_issue += __builtin_amdgcn_s_memtime() - ti;
                 }
             } else if (t + 1 < NT) {
-                unsigned long long ti = 0;
-                if (PROF) ti = __builtin_amdgcn_s_memtime();
-                dma_wait(0);
-                if (PROF) {
-                    const unsigned long long now = __builtin_amdgcn_s_memtime();
-                    c_land += now - ti;
-                    ti = now;
-                }
+                dma_wait();
                 landed(nb);
                 post(&s_sync[nb]);
-                if (PROF) c_post += __builtin_amdgcn_s_memtime() - ti;
-            }
-        } else if constexpr (DMA) {
-            // tile t + 2 goes into the buffer tile t + 2 - NBUF was read from; tile t + 1 (issued a tile ago) has landed by now
-            // and is announced here, one tile ahead of its use, so that a wave may run a tile ahead of the slowest one
-            const int b2 = nb + 1 == NBUF ? 0 : nb + 1;
-            if (t + 2 < NT) {
-                if (t + 2 >= NBUF) {
-                    unsigned long long tw = 0;
-                    if (PROF) tw = __builtin_amdgcn_s_memtime();
-                    wait_for(&s_sync[NBUF + b2], kWaves * (int)((t + 2) / NBUF));
-                    if (PROF) {
-                        const unsigned long long now = __builtin_amdgcn_s_memtime();
-                        c_bar += now - tw;
-                        c_free += now - tw;
-                    }
-                }
-                unsigned long long ti = 0;
-                if (PROF) ti = __builtin_amdgcn_s_memtime();
-                dma_tile(t + 2, b2);
-                if (PROF) c_issue += __builtin_amdgcn_s_memtime() - ti;
-            }
-            if (t + 1 < NT) {
-                unsigned long long ti = 0;
-                if (PROF) ti = __builtin_amdgcn_s_memtime();
-                dma_wait(t + 2 < NT ? 1 : 0);
-                if (PROF) {
-                    const unsigned long long now = __builtin_amdgcn_s_memtime();
-                    c_land += now - ti;
-                    ti = now;
-                }
-                landed(nb);
-                post(&s_sync[nb]);
-                if (PROF) c_post += __builtin_amdgcn_s_memtime() - ti;
             }
         } else {
             if (t + 1 < NT) {  // rows of tile t + 1 (loaded during tile t - 1) into the buffer tile t + 1 - NBUF was read from
-                if (t + 1 >= NBUF) {
-                    unsigned long long tw = 0;
-                    if (PROF) tw = __builtin_amdgcn_s_memtime();
-                    wait_for(&s_sync[NBUF + nb], kWaves * (round + (nb == 0 ? 1 : 0)));  // = kWaves * ((t + 1) / NBUF)
-                    if (PROF) c_bar += __builtin_amdgcn_s_memtime() - tw;
-                }
+                if (t + 1 >= NBUF) wait_for(&s_sync[NBUF + nb], kWaves * (round + (nb == 0 ? 1 : 0)));  // = kWaves * ((t + 1) / NBUF)
                 store_tile(nb);
                 arrive(&s_sync[nb]);
             }
             if (t + 2 < NT) load_tile(t + 2);
         }
-        if (PROF) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            c_store += now - ts;
-            ts = now;
-        }
         // PIPE: tile t has been waited for inside the last row block of tile t - 1 (its first fragments are in registers)
         if (!PIPE || t == 0) wait_for(&s_sync[buf], ISS_OR_ALL * (round + 1));
-        if (PROF) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            c_bar += now - ts;
-            ts = now;
-        }
         const unsigned char *tb = s_tile + (size_t)buf * kTR * ROWB;
         if (PIPE && t == 0) {
 #pragma unroll
@@ -828,27 +700,10 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                 if (rb + 1 == RB) {
                     nx = tb;  // last tile: a re-read nobody uses
                     if (t + 1 < NT) {
-                        unsigned long long tw = 0;
-                        if (PROF) tw = __builtin_amdgcn_s_memtime();
                         wait_for(&s_sync[nb], ISS_OR_ALL * (round + (nb == 0 ? 1 : 0) + 1));
-                        if (PROF) c_bar += __builtin_amdgcn_s_memtime() - tw;
                         nx = s_tile + (size_t)nb * kTR * ROWB;
                     }
                 }
-#if GORSE_SWEEP_ORDER == 1
-#pragma unroll
-                for (int cb = 0; cb + 1 < NCB; cb++)
-#pragma unroll
-                    for (int ks = 0; ks < KP; ks++)
-                        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], bfrag[cb][ks], acc[cb], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < KP; ks++) {
-                    acc[NCB - 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], bfrag[NCB - 1][ks], acc[NCB - 1], 0, 0, 0);
-                    af[ks] = frag(nx, ks);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#else
 #pragma unroll
                 for (int ks = 0; ks < KP; ks++) {
 #pragma unroll
@@ -857,7 +712,6 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                     af[ks] = frag(nx, ks);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#endif
             } else {
             const unsigned char *rowp = tb + (rb * 32 + (lane & 31)) * ROWB + (lane >> 5) * 16;
             const unsigned char *blkp = tb + rb * 32 * ROWB;  // DMA: + aoff[ks]
@@ -990,13 +844,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                     const float mx = s_bmm[(buf * kMaxRB + rb) * 2 + 1];
                     m = m * (m >= 0.0f ? mx : mn);
                 }
-                if (PROF) n_blk++;
                 if (__builtin_amdgcn_ballot_w64(m >= (RAWF ? fraw[RAWF ? cb : 0] : fth[cb])) != 0) {
-                    unsigned long long tsl = 0;
-                    if (PROF) {
-                        tsl = __builtin_amdgcn_s_memtime();
-                        n_slow++;
-                    }
                     __builtin_amdgcn_s_setprio(3);  // the wave on this path is the one its workgroup waits for
                     if (EP == EP_COARSE && !RAWF) {
                         scale_rows();
@@ -1016,13 +864,6 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                     // and for flagged queries; rows past N are NaN.  A block that comes here holds one or two candidates among
                     // its 1024 scores: a quad is opened only if its maximum qualifies (a NaN maximum never does: the hardware
                     // maximum skips NaN operands, and a quad of four NaNs holds no candidate).
-                    unsigned long long tq = 0;
-                    int cnt_was = 0;
-                    if (PROF) {
-                        tq = __builtin_amdgcn_s_memtime();
-                        c_s1 += tq - tsl;
-                        cnt_was = cnt[cb];
-                    }
 #pragma unroll
                     for (int g = 0; g < 4; g++) {
                         if (gm[g] >= fq && p.probe != 2) {
@@ -1043,12 +884,6 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                                 }
                             }
                         }
-                    }
-                    if (PROF) {
-                        const unsigned long long now = __builtin_amdgcn_s_memtime();
-                        c_s2 += now - tq;
-                        tq = now;
-                        n_hits += __builtin_amdgcn_ballot_w64(cnt[cb] != cnt_was) != 0;  // blocks that did append something
                     }
                     uint64_t need = __builtin_amdgcn_ballot_w64(cnt[cb] > p.compact_at);
                     if (need) {
@@ -1071,41 +906,13 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                         fth[cb] = s_f[ql];
                         if (RAWF) fraw[RAWF ? cb : 0] = raw_threshold(fth[cb]);
                     }
-                    base_prio();
-                    if (PROF) {
-                        const unsigned long long now = __builtin_amdgcn_s_memtime();
-                        c_s3 += now - tq;
-                        c_slow += now - tsl;
-                    }
+                    __builtin_amdgcn_s_setprio(0);
                 }
             }
-        }
-        if (PROF) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            c_comp += now - ts;
-            ts = now;
         }
         arrive(&s_sync[NBUF + buf]);  // this wave has read tile t
         buf = nb;
         if (nb == 0) round++;
-    }
-    if (PROF && lane == 0) {
-        atomicAdd(p.prof + 0, c_store);
-        atomicAdd(p.prof + 1, c_comp);
-        atomicAdd(p.prof + 2, c_slow);
-        atomicAdd(p.prof + 3, c_bar);
-        atomicAdd(p.prof + 4, n_blk);
-        atomicAdd(p.prof + 5, n_slow);
-        atomicAdd(p.prof + 6, (unsigned long long)__builtin_amdgcn_s_memtime() - t_begin);
-        atomicAdd(p.prof + 7, 1ull);
-        atomicAdd(p.prof + 8, c_s1);
-        atomicAdd(p.prof + 9, c_s2);
-        atomicAdd(p.prof + 10, c_s3);
-        atomicAdd(p.prof + 11, n_hits);
-        atomicAdd(p.prof + 12, c_free);
-        atomicAdd(p.prof + 13, c_issue);
-        atomicAdd(p.prof + 14, c_land);
-        atomicAdd(p.prof + 15, c_post);
     }
     if (SYM && stage_n > 0) flush_stage();
     // final threshold + compaction of every list this wave owns
@@ -1486,7 +1293,7 @@ struct ReplayParams {
     const int32_t *hcnt;
     const float *fslice;   // nslices x nq: the threshold every slice of the history sweep ended with (-inf: none)
     int nslices;           // cbuf / ccnt / hbuf / hcnt / cflag / fslice hold nslices x nq entries, slice-major
-    unsigned long long *prof;  // probe (variant bit 4): replay counters, see gorse_hip_test_get_sweep_profile; else null
+    unsigned long long *prof;  // probe (variant bit 4): the replay's counters, see gorse_hip_test_get_sweep_profile; else null
     int64_t nq;
     uint8_t *cflag;        // in: flags of the history sweep (non-zero: undecidable); out [0, nq): 2 = undecided here
     int64_t N;
@@ -1605,273 +1412,10 @@ __global__ __launch_bounds__(kBlock) void topk_tie_sort_kernel(ReplayParams p) {
     if (tid == 0) p.scount[t] = s_misc[0] ? -1 : n;  // -1: a NaN distance (the reference panics on it): path A
 }
 
-// The reference's heap as a wave-uniform register structure: entry j lives in lane j & 63 of register j >> 6
-// (capacity 256 = kMaxKth), every index and weight the sift rules look at is a scalar (v_readlane / v_writelane), so a
-// Push or Pop costs no LDS or memory round trip.  The sift loops are the hole form of container/heap's swap loops
-// (goheap.hpp): the moving element is compared with the same neighbours and ends in the same slot, and every other
-// element is moved exactly as the swaps would move it.
-template <bool DESC>
-struct RegHeap {
-    int w[4], v[4];  // weights (float bits) and values
-    int n;
-    __device__ __forceinline__ RegHeap() : n(0) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) w[r] = v[r] = 0;
-    }
-    __device__ __forceinline__ static bool less(float a, float b) { return DESC ? a > b : a < b; }
-    __device__ __forceinline__ float getw(int j) const {
-        const int l = j & 63;
-        int x;
-        switch (j >> 6) {
-        case 0: x = __builtin_amdgcn_readlane(w[0], l); break;
-        case 1: x = __builtin_amdgcn_readlane(w[1], l); break;
-        case 2: x = __builtin_amdgcn_readlane(w[2], l); break;
-        default: x = __builtin_amdgcn_readlane(w[3], l); break;
-        }
-        return __int_as_float(x);
-    }
-    __device__ __forceinline__ int getv(int j) const {
-        const int l = j & 63;
-        switch (j >> 6) {
-        case 0: return __builtin_amdgcn_readlane(v[0], l);
-        case 1: return __builtin_amdgcn_readlane(v[1], l);
-        case 2: return __builtin_amdgcn_readlane(v[2], l);
-        default: return __builtin_amdgcn_readlane(v[3], l);
-        }
-    }
-    __device__ __forceinline__ void set(int j, float wt, int val) {
-        const bool me = (int)(threadIdx.x & 63) == (j & 63);
-        const int wb = __float_as_int(wt);
-        switch (j >> 6) {
-        case 0: w[0] = me ? wb : w[0]; v[0] = me ? val : v[0]; break;
-        case 1: w[1] = me ? wb : w[1]; v[1] = me ? val : v[1]; break;
-        case 2: w[2] = me ? wb : w[2]; v[2] = me ? val : v[2]; break;
-        default: w[3] = me ? wb : w[3]; v[3] = me ? val : v[3]; break;
-        }
-    }
-    __device__ __forceinline__ void push(int val, float wt) {  // heap.Push: append, up(n - 1)
-        int j = n++;
-        while (j > 0) {
-            const int i = (j - 1) / 2;
-            const float wi = getw(i);
-            if (!less(wt, wi)) break;
-            set(j, wi, getv(i));
-            j = i;
-        }
-        set(j, wt, val);
-    }
-    // heap.Pop: swap(0, n - 1), down(0, n - 1), take the last; returns the removed root
-    __device__ __forceinline__ void pop(int &val, float &wt) {
-        val = getv(0);
-        wt = getw(0);
-        const int m = --n;  // the last element (index m) moves to the root and sifts down over m elements
-        if (m == 0) return;
-        const float wl = getw(m);
-        const int vl = getv(m);
-        int i = 0;
-        for (;;) {
-            const int j1 = 2 * i + 1;
-            if (j1 >= m) break;
-            int j = j1;
-            float wj = getw(j1);
-            if (j1 + 1 < m) {
-                const float w2 = getw(j1 + 1);
-                if (less(w2, wj)) {
-                    j = j1 + 1;
-                    wj = w2;
-                }
-            }
-            if (!less(wj, wl)) break;
-            set(i, wj, getv(j));
-            i = j;
-        }
-        set(i, wl, vl);
-    }
-    // every lane: do the first n values equal those of `o`?
-    __device__ __forceinline__ bool same_values(const RegHeap &o, int lane) const {
-        bool diff = false;
-#pragma unroll
-        for (int r = 0; r < 4; r++) diff |= (lane + 64 * r < n) && v[r] != o.v[r];
-        return __builtin_amdgcn_ballot_w64(diff) == 0;
-    }
-};
-
-#ifdef GORSE_PROBE  // the round-2 replay (a wave per query): kept for `make probe-lib` only, the library ships the lane kernel
-// stage 2 of the tie path: one WAVE per query replays the reference's heap over the sorted entries (see the comment
-// above ReplayParams); four queries per workgroup, no LDS.
-__global__ __launch_bounds__(256) void topk_tie_replay_kernel(ReplayParams p, int64_t nq, int g_replay_literal) {
-    const int lane = threadIdx.x & 63;
-    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= nq) return;
-    if (p.cflag[t]) return;
-    const int n = p.scount[t];
-    const int k = p.k;
-    const int64_t self = p.self[t];
-    const int64_t row = p.pos[t];
-    bool undecided = n < 0;
-    const float kInf = __builtin_inff();
-    const unsigned long long t_begin = p.prof ? __builtin_amdgcn_s_memtime() : 0;
-    unsigned long long n_push = 0, n_tpow = 0, n_slow_tpow = 0, n_T = 0;
-    RegHeap<true> mx;
-    auto apply_T = [&]() {  // a push that goes to the root and is popped at once
-        int dv;
-        float dw;
-        mx.push(-1, kInf);
-        mx.pop(dv, dw);
-    };
-    // T leaves the heap array as it is unless equal weights sit where its push and pop look.  With the heap full (n = k),
-    // push(+inf) climbs from slot n to the root and shifts the path's elements down one level; pop then sends the element
-    // E that came to rest in slot n (the old occupant of slot p1 = parent(n)) back down from the root, and every level
-    // restores its old occupant iff (a) the path's child wins the comparison of the two children -- certain when it is the
-    // LEFT child (container/heap prefers the left on a tie), and when it is the right child only if the old parent is
-    // strictly greater than the left child -- and (b) the old parent is strictly greater than E.  E then stops in p1, whose
-    // remaining child cannot beat it.  A dozen scalar comparisons instead of two sift passes and a snapshot compare
-    // (tests/test_replay_claim_cpu.py checks the criterion against the literal T).
-    auto t_is_identity = [&]() -> bool {
-        const int n = mx.n;
-        if (n < 1) return false;
-        int child = (n - 1) / 2;  // p1
-        const float e = mx.getw(child);
-        if (!(e < kInf)) return false;
-        while (child > 0) {
-            const int parent = (child - 1) / 2;
-            const float wp = mx.getw(parent);
-            if (!(wp > e) || !(wp < kInf)) return false;
-            if ((child & 1) == 0 && !(wp > mx.getw(child - 1))) return false;  // right child: the left sibling must lose
-            child = parent;
-        }
-        return true;
-    };
-    auto t_pow = [&](int64_t gap) {
-        n_tpow++;
-        if (!(g_replay_literal) && t_is_identity()) return;
-        n_slow_tpow++;
-        int64_t steps = 0;
-        while (steps < gap && steps < 16) {  // fixpoint (the usual case: no equal distances on the path) or pre-period
-            const RegHeap<true> snap = mx;
-            apply_T();
-            steps++;
-            n_T++;
-            if (mx.same_values(snap, lane)) return;
-        }
-        if (steps == gap) return;
-        const RegHeap<true> snap = mx;  // inside the cycle now (or not: then the period search fails, query flagged)
-        int64_t period = 0;
-        bool closed = false;
-        while (period < 64) {
-            apply_T();
-            period++;
-            steps++;
-            n_T++;
-            if (steps == gap) return;
-            if (mx.same_values(snap, lane)) {
-                closed = true;
-                break;
-            }
-        }
-        if (!closed) {
-            undecided = true;
-            return;
-        }
-        const int64_t rem = (gap - steps) % period;
-        for (int64_t r = 0; r < rem; r++) apply_T();
-    };
-    const int32_t *sidx = p.sidx + t * kReplayCap;
-    const float *sdst = p.sdst + t * kReplayCap;
-    int64_t prev = -1;
-    int64_t pend = 0;  // T applications owed: unrecorded vectors + recorded ones that are strictly worse than the root
-    for (int e0 = 0; e0 < n && !undecided; e0 += 64) {
-        const int bi = e0 + lane < n ? sidx[e0 + lane] : 0;
-        const int bd = e0 + lane < n ? __float_as_int(sdst[e0 + lane]) : 0;
-        const int cntb = n - e0 < 64 ? n - e0 : 64;
-        for (int j = 0; j < cntb && !undecided; j++) {
-            const int64_t i = __builtin_amdgcn_readlane(bi, j);
-            const float dd = __int_as_float(__builtin_amdgcn_readlane(bd, j));
-            if (i == self) continue;
-            if (i == prev) {  // cannot happen: every recorded vector lives in exactly one place
-                undecided = true;
-                break;
-            }
-            int64_t gap = i - prev - 1;
-            if (self > prev && self < i) gap--;
-            if (gap > 0 && mx.n < k) {  // unrecorded vectors before the heap is full would have been accepted
-                undecided = true;
-                break;
-            }
-            pend += gap;
-            prev = i;
-            if (mx.n == k && dd > mx.getw(0)) {  // goes to the root and is popped at once: one more T
-                pend++;
-                continue;
-            }
-            if (pend > 0) {
-                t_pow(pend);
-                pend = 0;
-                if (undecided) break;
-            }
-            n_push++;
-            mx.push((int32_t)i, dd);
-            if (mx.n > k) {
-                int dv;
-                float dw;
-                mx.pop(dv, dw);
-            }
-        }
-    }
-    if (!undecided) {
-        int64_t gap = p.N - 1 - prev;
-        if (self > prev) gap--;
-        if (gap > 0 && mx.n < k) undecided = true;
-        pend += gap;
-        if (!undecided && pend > 0) t_pow(pend);
-    }
-    if (p.prof && lane == 0) {
-        const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_begin;
-        atomicAdd(p.prof + 0, dt);
-        atomicMax(p.prof + 1, dt);
-        atomicAdd(p.prof + 2, (unsigned long long)(n > 0 ? n : 0));
-        atomicAdd(p.prof + 3, 1ull);
-        atomicAdd(p.prof + 4, n_push);
-        atomicAdd(p.prof + 5, n_tpow);
-        atomicAdd(p.prof + 6, n_slow_tpow);
-        atomicAdd(p.prof + 7, n_T);
-        atomicMax(p.prof + 8, n_T);
-        atomicMax(p.prof + 9, (unsigned long long)(n > 0 ? n : 0));
-        atomicAdd(p.prof + 10, undecided ? 1ull : 0ull);
-    }
-    if (undecided) {
-        if (lane == 0) p.cflag[t] = 2;
-        return;
-    }
-    RegHeap<false> mn;  // Reverse(): re-push in array order (pq.go:121-128)
-    const int hn = mx.n;
-    for (int e = 0; e < hn; e++) mn.push(mx.getv(e), mx.getw(e));
-    int cnt = 0;
-    while (mn.n > 0) {
-        int v;
-        float w;
-        mn.pop(v, w);
-        if (!p.prune0 || w > 0) {
-            if (lane == 0) {
-                p.out_idx[row * k + cnt] = v;
-                p.out_dist[row * k + cnt] = w;
-            }
-            cnt++;
-        }
-    }
-    if (lane == 0) p.out_cnt[row] = cnt;
-    for (int e = cnt + lane; e < k; e += 64) {
-        p.out_idx[row * k + e] = -1;
-        p.out_dist[row * k + e] = kInf;
-    }
-}
-#endif  // GORSE_PROBE
-
-
-// ---- the same replay with one LANE per query ----------------------------------------------------------------------
-// The replay is scalar work: the wave-per-query kernel above issues ~1.8 M cycles of readlane / writelane traffic per
-// query (18 ms for the 9,934 tie queries of C4, profiles/r03_r_probe_c4_replay.txt).  Here every lane replays its own
-// query and keeps its heap in its own LDS column (slot j of lane q at word j * QPW + q: bank q whatever the slot, so the
+// ---- stage 2 of the tie path: the replay, one LANE per query ------------------------------------------------------
+// The replay is scalar work: round 2's kernel, a wave per query with the heap in registers, issued ~1.8 M cycles of readlane /
+// writelane traffic per query (18 ms for the 9,934 tie queries of C4, profiles/r03_r_probe_c4_replay.txt).  Here every lane
+// replays its own query over the sorted entries (see the comment above ReplayParams) and keeps its heap in its own LDS column (slot j of lane q at word j * QPW + q: bank q whatever the slot, so the
 // lanes never conflict, and no lane ever reads another's column: no barriers).  The ancestors of a push and the path of
 // the identity test are known before the first comparison, so their weights are read together -- one LDS round trip
 // instead of one per level; only the pop walks level by level.
@@ -1968,7 +1512,15 @@ __global__ __launch_bounds__(64) void topk_tie_replay_lane_kernel(ReplayParams p
     unsigned long long n_push = 0, n_tpow = 0, n_slow_tpow = 0, n_T = 0;
     LaneHeap<true, QPW> mx;
     mx.W = W, mx.V = V, mx.n = 0, mx.lg = nullptr, mx.nlog = 0;
-    // topk_tie_replay_kernel's t_is_identity, the path's weights read before the first comparison
+    // T leaves the heap array as it is unless equal weights sit where its push and pop look.  With the heap full (n = k),
+    // push(+inf) climbs from slot n to the root and shifts the path's elements down one level; pop then sends the element
+    // E that came to rest in slot n (the old occupant of slot p1 = parent(n)) back down from the root, and every level
+    // restores its old occupant iff (a) the path's child wins the comparison of the two children -- certain when it is the
+    // LEFT child (container/heap prefers the left on a tie), and when it is the right child only if the old parent is
+    // strictly greater than the left child -- and (b) the old parent is strictly greater than E.  E then stops in p1, whose
+    // remaining child cannot beat it.  A dozen comparisons instead of two sift passes and a snapshot compare
+    // (tests/test_replay_claim_cpu.py checks the criterion against the literal T).  The path's weights are read before the
+    // first comparison.
     auto t_is_identity = [&]() -> bool {
         const int hn = mx.n;
         if (hn < 1) return false;
@@ -1995,14 +1547,15 @@ __global__ __launch_bounds__(64) void topk_tie_replay_lane_kernel(ReplayParams p
         }
         return true;
     };
-    auto apply_T = [&]() {
+    auto apply_T = [&]() {  // a push that goes to the root and is popped at once
         int dv;
         float dw;
         mx.push(-1, kInf);
         mx.pop(dv, dw);
     };
     // T^gap when T is not the identity: literal applications until nothing changes (the change is read off the log of
-    // what T wrote), then topk_tie_replay_kernel's search for the period against a snapshot of the values
+    // what T wrote: a fixpoint is the usual case, else this is the pre-period), then the search for the period against a
+    // snapshot of the values
     auto t_pow = [&](int64_t gap) {
         n_tpow++;
         if (t_is_identity()) return;
@@ -2259,26 +1812,13 @@ int32_t launch_sweep_one(gorse_topk *h, const SweepParams &p) {
         if ((int64_t)grid <= p.sym_rank) return GORSE_OK;
         grid = (unsigned)ceil_div((int64_t)grid - p.sym_rank, p.sym_world);
     }
-    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_sweep_kernel<KP, NCB, EP, HIST, RB, false, SYM>),
+    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_sweep_kernel<KP, NCB, EP, HIST, RB, SYM>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    topk_sweep_kernel<KP, NCB, EP, HIST, RB, false, SYM>
+    topk_sweep_kernel<KP, NCB, EP, HIST, RB, SYM>
         <<<dim3(grid, HIST ? (unsigned)std::max(p.nslices, 1) : (SYM ? (unsigned)std::max(p.sym_slices, 1) : 1u)), dim3(WV * 64), lds, h->stream>>>(p);
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
-
-#ifdef GORSE_PROBE  // `make probe-lib`: the shipped library carries neither the instrumented twin nor its counters
-template <int RB>
-int32_t launch_sweep_prof(gorse_topk *h, const SweepParams &p) {  // the instrumented twin of the C4-shaped sweep (probe only)
-    constexpr int BQ = 32 * kNcbMain * kWaves;
-    const size_t lds = sweep_lds_bytes(8, RB, BQ, kWaves, false);
-    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_sweep_kernel<8, kNcbMain, EP_COARSE, false, RB, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    topk_sweep_kernel<8, kNcbMain, EP_COARSE, false, RB, true><<<dim3((unsigned)ceil_div(p.nq, BQ)), dim3(kThreads), lds, h->stream>>>(p);
-    GORSE_HIP_CHECK(hipGetLastError());
-    return GORSE_OK;
-}
-#endif
 
 template <int KP, int NCB, bool HIST, int RB, bool SYM = false>
 int32_t launch_sweep_ep(gorse_topk *h, const SweepParams &p) {
@@ -2302,12 +1842,6 @@ int32_t launch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym = 
     // 128-row tiles (one tile hand-over per four MFMA row blocks) where LDS allows; the history sweep of the few flagged
     // queries keeps the 64-row form
     const bool wide = !hist && KP <= 8 && topk_rows_per_tile() == 128;
-#ifdef GORSE_PROBE
-    if constexpr (KP == 8 && NCB == kNcbMain) {
-        if ((g_topk_variant & 16) && p.ep == EP_COARSE && !hist && p.prof)
-            return wide ? launch_sweep_prof<4>(h, p) : launch_sweep_prof<2>(h, p);
-    }
-#endif
     if (wide) {
         if constexpr (KP <= 8) return launch_sweep_ep<KP, NCB, false, 4>(h, p);
     }
@@ -2783,7 +2317,6 @@ int32_t chunk_pilots(gorse_topk *h, ChunkState &cs, int64_t lo, int64_t hi) {
     p2.kth = (g_topk_variant & 1024) ? 2 : pilot_kth(cs.kth, cs.pilot_stride);
     p2.tile_stride = cs.pilot_stride;
     p2.f_out = h->f0.p + lo;
-    p2.prof = nullptr;  // the instrumented twin profiles the main sweep only
     p2.probe = 0;
     if ((h->N >= (int64_t)1 << 18 || (g_topk_variant & 512)) && !(g_topk_variant & (1 << 22))) {
         SweepParams p1 = p2;
@@ -2928,7 +2461,7 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
     auto stored_id = [&](int64_t t) -> int64_t {
         return by_vector ? -1 : (qid_host ? qid_host[c0 + t] : q_contig_begin + c0 + t);
     };
-    // stage 2: history sweep + literal heap replay (topk_tie_sort_kernel, topk_tie_replay_kernel) for the flagged queries
+    // stage 2: history sweep + literal heap replay (topk_tie_sort_kernel, topk_tie_replay_lane_kernel) for the flagged queries
     std::vector<int64_t> rest;
     // (with a mask the replay's gap arithmetic -- which counts the rows between two recorded ones -- would count masked
     // rows too: those queries take the literal scan, which skips masked rows)
@@ -3018,7 +2551,7 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
             pp.hcnt = h->rp_hcnt.p;
             pp.fslice = h->rp_fslice.p;
             pp.nslices = nsl;
-            pp.prof = (g_topk_variant & 16) && h->sweep_prof.n >= 16 ? h->sweep_prof.p : nullptr;  // the sweep's counters are overwritten
+            pp.prof = (g_topk_variant & 16) && h->sweep_prof.n >= 16 ? h->sweep_prof.p : nullptr;
             if (pp.prof) GORSE_HIP_CHECK(hipMemsetAsync(pp.prof, 0, 16 * sizeof(unsigned long long), h->stream));
             pp.nq = m2;
             pp.cflag = h->rp_flag.p;
@@ -3042,13 +2575,7 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
             tok = h->prof.begin(GORSE_PROF_TOPK_REPLAY, h->stream);
             topk_tie_sort_kernel<<<dim3((unsigned)m2), dim3(kBlock), rlds, h->stream>>>(pp);
             GORSE_HIP_CHECK(hipGetLastError());
-            // one lane per query (probe build, variant bit 19 / 16: the round-2 kernel, a wave per query)
-#ifdef GORSE_PROBE
-            const bool lanes = !(g_topk_variant & (1 << 19)) && !(g_topk_variant & 65536);
-#else
-            const bool lanes = true;
-#endif
-            if (lanes) {
+            {  // one lane per query
                 const int slots = k + 1;
                 int qpw = 64;
                 while (qpw > 16 && (size_t)(3 * slots + 2 * kLaneLog) * qpw * 4 > (size_t)144 * 1024) qpw >>= 1;
@@ -3070,12 +2597,6 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
                 else if (qpw == 32) GORSE_TRY(launch_lanes(std::integral_constant<int, 32>()));
                 else GORSE_TRY(launch_lanes(std::integral_constant<int, 16>()));
             }
-#ifdef GORSE_PROBE
-            if (!lanes) {
-                topk_tie_replay_kernel<<<dim3((unsigned)ceil_div(m2, 4)), dim3(256), 0, h->stream>>>(pp, m2, (g_topk_variant & 65536) ? 1 : 0);
-                GORSE_HIP_CHECK(hipGetLastError());
-            }
-#endif
             h->prof.end(tok, h->stream);
             f2.resize((size_t)m2);
             GORSE_HIP_CHECK(hipMemcpyAsync(f2.data(), h->rp_flag.p, (size_t)m2, hipMemcpyDeviceToHost, h->stream));

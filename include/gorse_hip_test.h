@@ -31,12 +31,11 @@ void gorse_hip_test_set_variant(int32_t variant);
 void gorse_hip_test_set_topk_path(int32_t path);
 /* probe switches of the MFMA sweep: bit 0 = 64 candidate rows per LDS tile, bit 1 = 128 (default: what the library
  * ships with), bit 2 / bit 3 = block-level row-scale bound of the cosine sweep off / on (default: on when all norms
- * are within 2 % of each other), bit 4 = the instrumented twin (see below), bit 5 / bit 6 = compact a candidate list
+ * are within 2 % of each other), bit 4 = the tie replay counts its work (see gorse_hip_test_get_sweep_profile; the main
+ * sweep then keeps its square form), bit 5 / bit 6 = compact a candidate list
  * when one of its two sub-lists exceeds 224 / 96 entries (default 128), bit 14 = the history
  * sweep of the tie path in eight row slices whatever the index size (default: one slice per 32768 rows, at most eight),
- * bit 15 = in one slice, bit 16 = the tie replay applies every T = "push +inf, pop" literally instead of first testing
- * whether it leaves the heap as it is (and a wave per query), bit 19 = the tie replay with a wave per query for every query
- * (default: a lane per query), bits 17-18 = timing probes of the main sweep (1: no block ever qualifies, 2: a qualifying
+ * bit 15 = in one slice, bits 17-18 = timing probes of the main sweep (1: no block ever qualifies, 2: a qualifying
  * block does nothing, 3: it counts its candidates without storing them; the search then returns after the sweep, results
  * undefined), bits 20-22 = the warm start's pilot sample: every 8th / every 32nd row tile instead of every 16th, and without the
  * 1/256 pilot in front (scripts/gpu_probe_topk_c4.py pilot).  Results never depend on the others. */
@@ -66,12 +65,12 @@ int32_t gorse_hip_test_topk_get_foreign_counts(gorse_topk *h, int32_t *counts /*
 int32_t gorse_hip_test_topk_get_pilot_state(gorse_topk *h, uint8_t *flags /*host*/, int32_t *counts /*host*/, int64_t n);
 /* the warm-start thresholds of the last search's last chunk (the first n queries) */
 int32_t gorse_hip_test_topk_get_thresholds(gorse_topk *h, float *out /*host*/, int64_t n);
-/* variant bit 4 runs an instrumented twin of the C4-shaped sweep (d = 128 bf16, cosine); this returns its sixteen
- * counters summed over all waves: s_memtime ticks in [0] tile store + prefetch issue, [1] MFMA + epilogues, [2] the
- * candidate paths inside [1], [3] barrier wait, then [4] row blocks examined, [5] row blocks with a candidate, [6]
- * kernel ticks, [7] waves, and the candidate path split into [8] count + exchange, [9] appends, [10] compaction
- * check / compaction, with [11] candidate-path blocks that appended something; the tile top split into [12] wait for the
- * buffer, [13] LDS-DMA issue, [14] wait for the previous tile's DMA, [15] its announcement. */
+/* with variant bit 4 set, the tie replay (csrc/topk_mfma.hip topk_tie_replay_lane_kernel) of a search counts its work; this
+ * returns the sixteen counters of the handle's last such replay, over its queries: [0] s_memtime ticks summed, [1] the most of one
+ * query, [2] recorded entries summed, [3] queries, [4] heap pushes, [5] gaps evaluated (T^gap), [6] those where T was not the
+ * identity, [7] literal applications of T summed, [8] the most of one query, [9] the most recorded entries of one query,
+ * [10] queries left undecided; [11]..[15] are zero.  (The counters of the main sweep's instrumented twin, which this hook also
+ * served, left with the probe build.) */
 int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out16 /*host*/);
 /* 1 = every query of the literal scan (path A) goes through the one-thread-per-query heap kernel; 0 (default) = the queries whose
  * k + 1 smallest distances are pairwise distinct are answered by select_fast_kernel (same results). */
@@ -123,12 +122,6 @@ void gorse_hip_test_set_sparse_heavy(int64_t entries);
  * wave, -1 = the library's choice (ds_add_f32 unless a product of a stored and a query value could fall below 2^-100,
  * where partial sums may be subnormal and the LDS adder's handling of those is not relied upon). */
 void gorse_hip_test_set_sparse_atomic(int32_t mode);
-/* probe: with on != 0 the following calls of the handle record what every work item (a query, or one group of a long query)
- * did; with out != NULL copies up to cap records of the last call as 16 uint64 each: {start, end (100 MHz ticks), query,
- * group + 1 of a long query (0 = whole query), entries, chunks taken 64 lists at once, their rounds, segments walked one list at a time,
- * groups read back densely, groups read back by re-walking, flattened batches, rows two lists of a batch shared,
- * 10 ns ticks in the 64-lists-at-once path / in the batches / in the read-backs / until the end of the eighth group}.  Returns the number of work items of the last call. */
-int64_t gorse_hip_test_sparse_trace(gorse_sparse *h, int32_t on, uint64_t *out /*host or NULL*/, int64_t cap);
 /* ALS row-solve choice: 0 = automatic (Gram form: on the fp32 MFMA for nFactors <= 64, als_wide_kernel for 65..128; the residual
  * sweep beyond), 1 = always the residual sweep (the reference's own recurrence), 2 = always the MFMA Gram form (nFactors <= 64).
  * Both meet the 1e-4 relative bar; the hook lets the parity tests drive each one.  Probe bits on top of the choice: 4 = the
@@ -148,36 +141,21 @@ void gorse_hip_test_set_als_path(int32_t path);
  * share of one of ~4096 wave slots, a power of two between 256 (512 from nFactors 64 on) and 4096; chunk = the
  * threshold).  Lets small test inputs exercise the long-row path. */
 void gorse_hip_test_set_als_plan(int32_t long_row, int32_t chunk);
-/* probe: enable != 0 makes als_row_kernel stamp its phases with s_memtime; out16 (may be NULL) receives, for the last
- * user half-sweep and then the last item half-sweep, ticks summed over the waves in [0] Gram accumulation (gathers +
- * MFMA), [1] M to LDS, [2] the d-step solve, then [3] rows, [4] feedback entries, [5] kernel ticks, [6] waves, [7] 0. */
-int32_t gorse_hip_test_als_profile(gorse_mf *h, int32_t enable, uint64_t *out16 /*host or NULL*/);
 /* probe: samples per chunk of a gorse_mf handle created AFTERWARDS (0 = the library's choice: 32 x users, clamped to
  * [4M, 128M]); the user-run schedule applies a chunk at a time. */
 void gorse_hip_test_set_bpr_chunk(int64_t samples);
-/* which item updates of the user-run BPR kernel may take the STORE route (csrc/bpr.hip ST_*): bit 0 = the NEGATIVE item of a
+/* which item updates of the user-run BPR kernel may take the STORE route (csrc/bpr.hip NEG_STORE): bit 0 = the NEGATIVE item of a
  * sample, when its class is "cold", is updated by one write-through store of fma(t, lr, row) instead of d atomic dwords (the
- * reference's own unlocked write, model.go:478-488; its row is then gathered one sample ahead instead of two), bit 1 = the
- * positive item likewise, bit 2 = the store adds to a row re-read in the same iteration instead of the gathered snapshot;
- * < 0 = the library's default.  Which items are cold is fixed at gorse_mf_create (gorse_hip_test_set_bpr_cold_window). */
+ * reference's own unlocked write, model.go:478-488; its row is then gathered one sample ahead instead of two); < 0 = the
+ * library's default.  Only bit 0 is looked at: the forms that bits 1 and 2 once asked for (the positive item by store, the store
+ * adding to a row re-read in the same iteration) were measured, rejected and removed, and a value that sets them runs what bit 0
+ * alone selects.  Which items are cold is fixed at gorse_mf_create (gorse_hip_test_set_bpr_cold_window). */
 void gorse_hip_test_set_bpr_store_mode(int32_t store_mode);
-/* `make probe-lib` builds only (a measured dead end, csrc/bpr.hip SEG): n = 2..8 segments per user run of the user-run schedule at
- * nFactors <= 32; 0 / 1 = the plain form.  The shipped library ignores it. */
-void gorse_hip_test_set_bpr_user_segments(int32_t segments);
-/* probe builds (make probe-lib) only: which software pipeline of the atomics-only user-run kernel runs.  Bits 0..7: 0 = the shipped
- * one, 1..6 = (rows gathered G samples ahead, ids IA ahead) = (2,4) (3,5) (3,6) (4,6) (4,8) (6,9) of the same kernel, 10..14 = the ring
- * kernel without register rotation (ring size / id lead) = 3/1, 4/2, 6/3, 8/4, 6/2; bits 8..19: threads per workgroup of the ring
- * kernel (0 = 256); bits 20..: how many of a wave's four 16-lane groups work (0 = 4).  Ignored by the product build. */
-void gorse_hip_test_set_bpr_user_depth(int32_t which);
 /* floats.MM (csrc/sgemm.hip): 1 = the NN / TN / TT chains on the vector ALU whatever the shape (default: on the fp32 MFMA from 64 x 64
  * results on; both are the same l-ascending fmaf chain, bit for bit).  The second hook returns the kernel time of the last
  * gorse_hip_sgemm call in milliseconds (hipEvents around the launch, copies excluded): bench.py's `mm` object. */
 void gorse_hip_test_set_sgemm_valu(int32_t on);
 double gorse_hip_test_sgemm_last_ms(void);
-/* 1 = this is a `make probe-lib` build (csrc/Makefile, -DGORSE_PROBE): it also carries the instrumented twin of the top-k sweep, the
- * wave-per-query tie replay, the sparse kernel's trace instantiation and the positive-side / re-reading forms of the BPR store
- * route.  The library `make all` ships (0) answers the switches that would select those with its own nearest form. */
-int32_t gorse_hip_test_probe_build(void);
 /* test hook: runs the user-run schedule's preparation of ONE chunk (user draws, counting sort of the sample ids by user, item
  * draws by run: csrc/bpr.hip launch_prepare_users) for samples [sample_base, sample_base + n) and returns the run offsets
  * (off[u] .. off[u + 1] = the positions of user u's samples; off[U] .. off[U + 1] = samples whose user draw failed) and the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU probe: the user-run BPR update with write-through stores on cold item rows (csrc/bpr.hip ST_*), against the atomics-only
+"""GPU probe: the user-run BPR update with write-through stores on the cold NEGATIVE item rows (csrc/bpr.hip NEG_STORE), against the atomics-only
 form, per shape: update-kernel ms per epoch, end-to-end rate, NDCG@10 next to the sequential oracle, and the lost updates.
 
 Lost updates are counted, not guessed: with P = 2^-10 everywhere, Q = 0, reg = 0 and lr = 2^-20 every sample moves its positive
@@ -16,10 +16,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the positive-side and re-reading forms of the store route live in the probe build only (make -C gorse_amd/csrc probe-lib)
-_probe = os.path.join(ROOT, "gorse_amd", "lib", "libgorse_hip_probe.so")
-if os.path.exists(_probe) and os.path.getmtime(_probe) >= os.path.getmtime(os.path.join(ROOT, "gorse_amd", "lib", "libgorse_hip.so")):
-    os.environ.setdefault("GORSE_HIP_LIB", _probe)
 import numpy as np
 
 from gorse_amd import capi, synth
@@ -100,9 +96,7 @@ def run_case(name, data, d, epochs, ref_ndcg, variants, n_loss):
 def store_variants(windows):
     v = [("atomics only", 0, 0, 0), ("atomics only, round-3 preparation", 0, 0, 1 << 26)]
     for w in windows:
-        v += [("W=%d stores: negatives" % w, w, 1, 0), ("W=%d stores: negatives + positives" % w, w, 3, 0),
-              ("W=%d stores: negatives, live re-read" % w, w, 5, 0), ("W=%d stores: both, live re-read" % w, w, 7, 0)]
-    v += [("stores on every item but the hot ones", 1, 3, 0)]
+        v += [("W=%d stores: negatives" % w, w, 1, 0)]
     return v
 
 

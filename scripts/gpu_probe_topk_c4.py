@@ -93,27 +93,13 @@ def main():
             run(t, k, 0, nq, label, reps=2)
         L.gorse_hip_test_set_topk_variant(0)
         return
-    if "replay" in sys.argv[1:]:  # the tie replay's counters (they overwrite the sweep's)
+    if "replay" in sys.argv[1:]:  # the tie replay's counters (variant bit 4)
         L.gorse_hip_test_set_topk_variant(16)
         run(t, k, 0, nq, "instrumented", reps=1)
         c = t.sweep_profile()
         q = max(c[3], 1)
         print("  replay: %d queries, ticks per query mean %.0f max %d; entries mean %.0f max %d; pushes %.0f, T^gap calls %.0f of which not the identity %.0f, literal T %.0f (max %d) per query; undecided %d"
               % (c[3], c[0] / q, c[1], c[2] / q, c[9], c[4] / q, c[5] / q, c[6] / q, c[7] / q, c[8], c[10]), flush=True)
-        L.gorse_hip_test_set_topk_variant(0)
-        return
-    if "prof" in sys.argv[1:]:  # the instrumented twin of the main sweep: where a wave's cycles go (s_memtime ticks per wave)
-        for v, label in ((16, "warm main sweep"), (16 | 32, "warm main sweep, compaction at 224"), (16 | 64, "warm main sweep, compaction at 96"),
-                         (16 | 256 | (1 << 17), "cold sweep, no block ever qualifies")):
-            L.gorse_hip_test_set_topk_variant(v)
-            run(t, k, 0, nq, label + " (instrumented)", reps=1)
-            c = t.sweep_profile()
-            waves = max(c[7], 1)
-            print("  per wave: total %.0f = tile top %.0f + waits %.0f + row blocks %.0f (candidate path %.0f: scale %.0f append %.0f compact %.0f)"
-                  % (c[6] / waves, c[0] / waves, c[3] / waves, c[1] / waves, c[2] / waves, c[8] / waves, c[9] / waves, c[10] / waves))
-            print("  tile top per wave: buffer wait %.0f, DMA issue %.0f, landing wait %.0f, announcement %.0f" % tuple(x / waves for x in c[12:16]))
-            print("  blocks %d, on the candidate path %d (%.2f %%), of those with an append %d (%.1f %%), waves %d; ticks per block %.1f"
-                  % (c[4], c[5], 100.0 * c[5] / max(c[4], 1), c[11], 100.0 * c[11] / max(c[5], 1), waves, c[1] / max(c[4], 1)), flush=True)
         L.gorse_hip_test_set_topk_variant(0)
         return
     if "lanes" in sys.argv[1:]:  # the tie replay: queries per wave chosen by the launch's size (default) against always 64 (variant bit 28)

@@ -99,10 +99,8 @@ for STAGE in "$@"; do
         rm -rf "$OUT/pmc_${TAG}_mm_SQ" ;;
     probe)
         ARGS=$(echo "${B:-}" | tr '+' ' ')
-        PLIB="$ROOT/gorse_amd/lib/libgorse_hip_probe.so"  # the probe build (make -C gorse_amd/csrc probe-lib) when it exists
-        [ -f "$PLIB" ] && [ "$PLIB" -nt "$ROOT/gorse_amd/lib/libgorse_hip.so" ] && export GORSE_HIP_LIB="$PLIB"  # never a stale one
         timeout 900 python "scripts/$A" $ARGS > "$OUT/${TAG}_probe_$(basename "$A" .py)${C:+_$C}.txt" 2>&1
-        echo "probe $A exit $?"; unset GORSE_HIP_LIB; cut -c1-220 "$OUT/${TAG}_probe_$(basename "$A" .py)${C:+_$C}.txt" | tail -40 ;;
+        echo "probe $A exit $?"; cut -c1-220 "$OUT/${TAG}_probe_$(basename "$A" .py)${C:+_$C}.txt" | tail -40 ;;
     ranks2)  # FUNCTIONAL check of bench.py's N > 1 path on a one-GPU box: two ranks share the GPU, gloo carries the exchange
         W=${A:-c3}
         GORSE_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \

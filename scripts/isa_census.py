@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers and spills per kernel of one .hip file: compiles it to gfx950 assembly (device only) and reads the kernel metadata.
-usage: isa_census.py gorse_amd/csrc/als.hip [name substring] [-DGORSE_PROBE]"""
+usage: isa_census.py gorse_amd/csrc/als.hip [name substring] [-D...]"""
 import os
 import re
 import subprocess

@@ -22,9 +22,9 @@ def test_no_bpr_update_kernel_spills_or_scratch():
         if m:
             seen[m.group(1)] = tuple(int(m.group(i)) for i in (5, 6, 7))
     # the forms the product launches: the user-run kernel at every width (atomics only / cold negatives by store), the per-sample kernel
-    for name in ("bpr_update_user_kernel<4, 1, false, 2, 3, false>", "bpr_update_user_kernel<4, 0, false, 2, 3, false>",
-                 "bpr_update_user_kernel<1, 1, true, 2, 3, false>", "bpr_update_user_kernel<1, 1, false, 2, 3, false>",
-                 "bpr_update_user_kernel<2, 1, false, 2, 3, false>", "bpr_update_user_kernel<8, 1, false, 2, 3, false>",
+    for name in ("bpr_update_user_kernel<4, true, false>", "bpr_update_user_kernel<4, false, false>",
+                 "bpr_update_user_kernel<1, true, true>", "bpr_update_user_kernel<1, true, false>",
+                 "bpr_update_user_kernel<2, true, false>", "bpr_update_user_kernel<8, true, false>",
                  "bpr_update_kernel<0, 0>", "bpr_update_kernel<1, 0>", "bpr_update_kernel<4, 0>", "bpr_update_kernel<8, 0>"):
         assert name in seen, (name, sorted(seen))
     for name, (vspill, sspill, scratch) in seen.items():

@@ -433,12 +433,11 @@ def test_bpr_user_runs_equal_the_sequential_result_when_items_are_disjoint(oracl
     assert np.array_equal(bits(gQ[~touched]), bits(Q[~touched]))  # nothing else moved
 
 
-# store mode 1 (the shipped one) at every nFactors bpr_update_user_kernel<NC, 1, ...> is compiled for; the probe-only modes at 64
-# (the cases at 64 keep the ids they had while the test fixed d = 64: "1", "3", "5", "7"; the others are "1-d8", ...)
-@pytest.mark.parametrize("store_mode,d", [pytest.param(m, d, id=str(m) if d == 64 else "%d-d%d" % (m, d))
-                                          for m, d in [(m, 64) for m in (1, 3, 5, 7)] + [(1, d) for d in (8, 16, 32, 128)]])
+# store mode 1 (cold negatives by store) at every nFactors bpr_update_user_kernel<NC, true, ...> is compiled for
+# (the case at 64 keeps the id it had while the test fixed d = 64: "1"; the others are "1-d8", ...)
+@pytest.mark.parametrize("store_mode,d", [pytest.param(1, d, id="1" if d == 64 else "1-d%d" % d) for d in (64, 8, 16, 32, 128)])
 def test_bpr_user_runs_cold_rows_by_store_are_bit_exact(oracle, store_mode, d):
-    """The cold-row route of the user-run schedule (csrc/bpr.hip ST_*): an item expected to be touched less than once per cold
+    """The cold-row route of the user-run schedule (csrc/bpr.hip NEG_STORE): an item expected to be touched less than once per cold
     window gets its update as ONE write-through store of fma(t, lr, row) -- the reference's own unlocked write (model.go:478-488)
     -- instead of d atomic dwords.  With every item row touched by one sample and ranks in stream order the result is unique:
     P bit-exact, and the rows that took the store route equal the sequential oracle BIT FOR BIT (one fma, where the atomic
@@ -446,8 +445,6 @@ def test_bpr_user_runs_cold_rows_by_store_are_bit_exact(oracle, store_mode, d):
     predates the group's own write): the repeated triplets at the end exercise that."""
     oracle.set_exp(1)
     L = capi.lib()
-    if store_mode != 1 and not L.gorse_hip_test_probe_build():
-        pytest.skip("the positive-side / re-reading forms of the store route exist in `make probe-lib` builds only")
     L.gorse_hip_test_set_exact_exp(1)
     rng = np.random.default_rng(100 + store_mode)
     U, I, n = 37, 3000, 1400

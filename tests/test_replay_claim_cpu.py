@@ -1,4 +1,4 @@
-"""The claim behind topk_tie_replay_kernel (gorse_amd/csrc/topk_mfma.hip), checked on the CPU with Go's container/heap
+"""The claim behind topk_tie_replay_lane_kernel (gorse_amd/csrc/topk_mfma.hip), checked on the CPU with Go's container/heap
 rules restated in pure Python (same rules as gorse_amd/csrc/goheap.hpp / common/heap/pq.go):
 
   Bruteforce's queue (bruteforce.go:46-53: Push, then Pop once it holds more than k) ends in the same heap ARRAY
@@ -68,7 +68,7 @@ def literal(dist, k):
 
 
 def t_pow(h, gap):
-    """exactly the control flow of t_pow in topk_tie_replay_kernel"""
+    """exactly the control flow of t_pow in topk_tie_replay_lane_kernel"""
     def apply():
         h.push(-1, INF)
         h.pop()
@@ -100,7 +100,7 @@ def t_pow(h, gap):
 
 
 def replay(dist, k, recorded):
-    """the control flow of topk_tie_replay_kernel: unrecorded vectors and recorded ones that are strictly worse than
+    """the control flow of topk_tie_replay_lane_kernel: unrecorded vectors and recorded ones that are strictly worse than
     the root are T applications, batched until the next vector the heap really takes"""
     h = GoMaxHeap()
     prev, pend = -1, 0
@@ -180,7 +180,7 @@ def test_t_is_a_short_cycle():
 
 
 def t_is_identity(h):
-    """the criterion of t_is_identity in topk_tie_replay_kernel: T = push(+inf), pop leaves the array of a FULL heap as it is"""
+    """the criterion of t_is_identity in topk_tie_replay_lane_kernel: T = push(+inf), pop leaves the array of a FULL heap as it is"""
     n = len(h.v)
     if n < 1:
         return False
