@@ -39,6 +39,8 @@ SIGNATURES = {
     "gorse_mf_get_factors": (C.c_int32, [_vp, _f32p, _f32p]),
     "gorse_mf_score": (C.c_int32, [_vp, _i32p, _i32p, C.c_int64, _f32p]),
     "gorse_mf_rank": (C.c_int32, [_vp, C.c_int64, _i32p, _i64p, _i32p, C.c_int32, _i32p, _i32p]),
+    "gorse_mf_recommend": (C.c_int32, [_vp, C.c_int64, _i32p, C.c_int32, C.POINTER(C.c_uint8), _i64p, _i32p, _i32p, _f32p, _i32p]),
+    "gorse_mf_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
     "gorse_mf_sample_user_negatives": (C.c_int32, [_vp, _i64p, _i32p, C.c_int32, C.c_uint64, _i32p, _i32p]),
     "gorse_mf_resident_candidates": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_mf_resident_generation": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
@@ -161,6 +163,7 @@ SIGNATURES = {
     "gorse_hip_test_set_bpr_fold_period": (None, [C.c_int32]),
     "gorse_hip_test_bpr_fold_stats": (C.c_int32, [_vp, _vp]),
     "gorse_hip_test_bpr_hot_state": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
 }
 
 
@@ -257,6 +260,37 @@ class MF:
         check(lib().gorse_mf_rank(self.h, users.size, _p(users, _i32p), _p(cand_indptr, _i64p), _p(cand, _i32p), topk,
                                   _p(rank, _i32p), _p(rlen, _i32p)))
         return rank, rlen
+
+    def recommend(self, users, k, item_ok=None, seen_indptr=None, seen_items=None):
+        """every query's k best unseen items (gorse_mf_recommend): (items n x k padded with -1, scores n x k padded with 0, counts n).
+        users = None: all users of the handle, or an int n: the first n; seen rows are per QUERY (seen_indptr has n + 1 entries)."""
+        if users is None or isinstance(users, (int, np.integer)):
+            n, up = (self.U if users is None else int(users)), None
+        else:
+            up = _arr(users, np.int32)
+            n = up.size
+        ok = _arr(item_ok, np.uint8) if item_ok is not None else None
+        if ok is not None and ok.size != self.I:
+            raise GorseHipError(ERR_INVALID, "item_ok must have I entries")
+        sp = _arr(seen_indptr, np.int64) if seen_indptr is not None else None
+        if sp is not None and sp.size != n + 1:
+            raise GorseHipError(ERR_INVALID, "seen_indptr must have n_users + 1 entries")
+        si = _arr(seen_items, np.int32) if seen_items is not None else None
+        if si is not None and si.size == 0:
+            si = np.zeros(1, np.int32)
+        kk = max(int(k), 0)
+        items = np.full((n, kk), -2, np.int32)
+        scores = np.full((n, kk), np.nan, np.float32)
+        counts = np.full(n, -2, np.int32)
+        check(lib().gorse_mf_recommend(self.h, n, _p(up, _i32p), k, _p(ok, C.POINTER(C.c_uint8)), _p(sp, _i64p), _p(si, _i32p),
+                                       _p(items, _i32p), _p(scores, _f32p), _p(counts, _i32p)))
+        return items, scores, counts
+
+    def recommend_stats(self):
+        """the last recommend(): (queries answered by the threshold kernel, queries answered literally, device milliseconds)"""
+        nf, nl, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        check(lib().gorse_mf_recommend_stats(self.h, C.byref(nf), C.byref(nl), C.byref(ms)))
+        return nf.value, nl.value, ms.value
 
     def sample_user_negatives(self, test_indptr, test_indices, num_candidates, seed=0, fetch=True):
         """dataset.SampleUserNegatives on the device: (neg U x n padded with -1, len U); the candidate lists of the users with

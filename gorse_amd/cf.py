@@ -30,6 +30,8 @@ def host():
         H.gh_model_name.restype = C.c_char_p
         H.gh_model_marshal.restype = C.c_int64
         H.gh_metric.restype = C.c_float
+        H.gh_model_recommend_unseen.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _i32p,
+                                                C.POINTER(C.c_uint8), C.c_int32, _i32p, _f32p, _i32p]
         _H = H
     return _H
 
@@ -272,6 +274,30 @@ class _Model:
         """(P, Q): the model's UserFactor / ItemFactor rows as matrices"""
         U, I = self.CountUsers(), self.CountItems()
         return (np.stack([self.GetUserFactor(u) for u in range(U)]), np.stack([self.GetItemFactor(i) for i in range(I)]))
+
+    def HandleHoldsTrainingRows(self):
+        """whether RecommendUnseen excludes the users' training rows by itself (see gorse_cf.hpp); otherwise it requires `seen`"""
+        return bool(host().gh_model_holds_training_rows(self.p))
+
+    def RecommendUnseen(self, user_ids, n, seen=None, item_ok=None):
+        """every user's n best unseen items (cf::MatrixFactorization::RecommendUnseen): (item indices len(user_ids) x n padded
+        with -1, scores padded with 0, counts); seen = one list of item INDICES per user, item_ok = one flag per item index"""
+        ids = [str(u) for u in user_ids]
+        sp = si = None
+        if seen is not None:
+            sp = np.zeros(len(ids) + 1, np.int64)
+            sp[1:] = np.cumsum([len(r) for r in seen])
+            si = np.ascontiguousarray([i for r in seen for i in r] or [0], np.int32)
+        ok = np.ascontiguousarray(item_ok, np.uint8) if item_ok is not None else None
+        items = np.full((len(ids), n), -1, np.int32)
+        scores = np.zeros((len(ids), n), np.float32)
+        counts = np.zeros(len(ids), np.int32)
+        _ck(host().gh_model_recommend_unseen(self.p, "\n".join(ids).encode(), len(ids), n,
+                                             sp.ctypes.data_as(C.POINTER(C.c_int64)) if sp is not None else None,
+                                             si.ctypes.data_as(_i32p) if si is not None else None,
+                                             ok.ctypes.data_as(C.POINTER(C.c_uint8)) if ok is not None else None, ok.size if ok is not None else 0,
+                                             items.ctypes.data_as(_i32p), scores.ctypes.data_as(_f32p), counts.ctypes.data_as(_i32p)))
+        return items, scores, counts
 
     def load_factors(self, P, Q):
         P, Q = np.ascontiguousarray(P, np.float32), np.ascontiguousarray(Q, np.float32)

@@ -101,6 +101,10 @@ struct gorse_mf {
     uint64_t ev_generation = 0;  // bumped by every gorse_mf_sample_user_negatives (gorse_mf_resident_generation)
     // generic staging
     gorse::DevBuf<char> stage, rank_in;
+    // gorse_mf_recommend (recommend.hip): its inputs, the fast path's buffers, the literal path's candidate lists; the last call's split
+    gorse::DevBuf<char> rec_in, rec_buf, rec_lit;
+    int64_t rec_fast = 0, rec_literal = 0;
+    double rec_ms = 0.0;
     gorse::KernelProfile prof{GORSE_PROF_NCLASSES};
 
     int32_t use() const {
@@ -121,6 +125,7 @@ int32_t mf_epoch_harvest(gorse_mf *h, bool wait);
 int32_t mf_delta_export_async(gorse_mf *h, float *dst);        // mf.hip: dst <- Q - Q_sync, enqueued on h->stream
 int32_t mf_delta_import_async(gorse_mf *h, const float *src);  // mf.hip: Q <- Q_sync + src; Q_sync <- Q
 int32_t als_build_plan(gorse_mf *h, int side, const int64_t *ptr, int64_t rows, int64_t lo, int64_t hi);
+int32_t mf_score_device(gorse_mf *h, const int32_t *us, const int32_t *is, int64_t n, float *out);  // mf.hip: internalPredict, device pointers
 // mf.hip: Rank + TopKFilter for n_users users over candidate lists ALREADY on the device (nc entries in all); the rank lists go
 // to the host arrays (n_users * topk padded with -1, lengths), enqueued on h->stream -- the caller synchronises
 int32_t mf_rank_device(gorse_mf *h, int64_t n_users, const int32_t *d_users, const int64_t *d_cand_ptr, const int32_t *d_cand,

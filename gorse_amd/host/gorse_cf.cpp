@@ -192,6 +192,62 @@ void MatrixFactorization::ensure_resident() {
     check(gorse_mf_set_factors(h_, UserFactor.data(), ItemFactor.data()));
 }
 
+void MatrixFactorization::RecommendUnseenIndexed(const std::vector<int32_t> &users, int n, const std::vector<int64_t> &seenPtr,
+                                                 const std::vector<int32_t> &seenItems, const std::vector<bool> &itemOk,
+                                                 std::vector<int32_t> &items, std::vector<float> &scores, std::vector<int32_t> &count) {
+    if (n <= 0) throw std::invalid_argument("RecommendUnseen: n must be positive");
+    if (!seenPtr.empty() && seenPtr.size() != users.size() + 1) throw std::invalid_argument("RecommendUnseen: one seen list per user");
+    ensure_resident();
+    if (!HandleHoldsTrainingRows() && seenPtr.empty())
+        throw std::logic_error("RecommendUnseen: the model's handle holds no training rows (restored model, or a Fit on a lent handle): "
+                               "pass the seen lists");
+    const int32_t I = ItemIndex->Count();
+    if (!itemOk.empty() && (int32_t)itemOk.size() != I) throw std::invalid_argument("RecommendUnseen: one itemOk flag per item");
+    std::vector<uint8_t> ok((size_t)I);
+    for (int32_t i = 0; i < I; i++) ok[(size_t)i] = itemOk.empty() ? IsItemPredictable(i) : (bool)itemOk[(size_t)i];
+    std::vector<int32_t> us(users);
+    for (auto &u : us)
+        if (!IsUserPredictable(u)) u = -1;
+    items.assign(users.size() * (size_t)n, -1);
+    scores.assign(users.size() * (size_t)n, 0.0f);
+    count.assign(users.size(), 0);
+    if (users.empty()) return;
+    const int32_t dummy = 0;
+    check(gorse_mf_recommend(h_, (int64_t)us.size(), us.data(), n, ok.data(), seenPtr.empty() ? nullptr : seenPtr.data(),
+                             seenItems.empty() ? &dummy : seenItems.data(), items.data(), scores.data(), count.data()));
+}
+
+std::vector<std::vector<MatrixFactorization::Recommended>> MatrixFactorization::RecommendUnseen(
+    const std::vector<std::string> &userIds, int n, const std::vector<std::vector<std::string>> &seen, const std::vector<bool> &itemOk) {
+    if (!seen.empty() && seen.size() != userIds.size()) throw std::invalid_argument("RecommendUnseen: one seen list per user");
+    if (Invalid()) throw std::runtime_error("model is not fitted");
+    const int32_t I = ItemIndex->Count();
+    std::vector<int32_t> users(userIds.size()), flat;
+    std::vector<int64_t> ptr;
+    if (!seen.empty()) ptr.assign(userIds.size() + 1, 0);
+    for (size_t t = 0; t < userIds.size(); t++) {
+        users[t] = UserIndex->Id(userIds[t]);
+        if (seen.empty()) continue;
+        for (const auto &id : seen[t]) {
+            const int32_t i = ItemIndex->Id(id);
+            if (i >= 0 && i < I) flat.push_back(i);  // an item the model does not know cannot be recommended anyway
+        }
+        ptr[t + 1] = (int64_t)flat.size();
+    }
+    std::vector<int32_t> items, count;
+    std::vector<float> scores;
+    RecommendUnseenIndexed(users, n, ptr, flat, itemOk, items, scores, count);
+    std::vector<std::vector<Recommended>> out(userIds.size());
+    for (size_t t = 0; t < userIds.size(); t++)
+        for (int32_t r = 0; r < count[t]; r++) {
+            Recommended rec;
+            ItemIndex->String(items[t * (size_t)n + (size_t)r], rec.Id);
+            rec.Score = scores[t * (size_t)n + (size_t)r];
+            out[t].push_back(std::move(rec));
+        }
+    return out;
+}
+
 std::vector<float> Evaluate(MatrixFactorization &estimator, dataset::Dataset &testSet, dataset::Dataset &trainSet, int topK,
                             int numCandidates, int nJobs, const std::vector<Metric> &scorers) {
     (void)nJobs;  // the device ranks every user at once; sums are taken in user order (== nJobs 1)

@@ -710,6 +710,27 @@ class MatrixFactorization {
         return out;
     }
 
+    // Every user's n best unseen items on a fitted model (gorse_mf_recommend): the bulk form of the worker's per-user loop
+    // (worker/pipeline.go:403-448), for CacheSize = n the prefix of length n of the reference's list.  Excluded are the user's
+    // training row WHEN the resident handle holds the training set (HandleHoldsTrainingRows: true from Fit on, until the model is
+    // cleared; false after a Fit that borrowed a ResidentDataset's handle, and for a model restored by Unmarshal, whose handle is
+    // recreated from bare factors) and the items of seen[t].  So that no caller gets a user's training items back by accident, a
+    // model whose handle holds no rows REQUIRES the seen lists (std::logic_error otherwise; pass empty lists to say "nothing seen").
+    // itemOk = one flag per item index, empty = IsItemPredictable.  Unknown or unpredictable users get an empty list.
+    struct Recommended {
+        std::string Id;
+        float Score = 0;
+    };
+    bool HandleHoldsTrainingRows() const { return h_ != nullptr && handle_train_ != nullptr; }
+    std::vector<std::vector<Recommended>> RecommendUnseen(const std::vector<std::string> &userIds, int n,
+                                                          const std::vector<std::vector<std::string>> &seen = {},
+                                                          const std::vector<bool> &itemOk = {});
+    // the same on indices: users[t] < 0 or unpredictable = empty list; seen rows as CSR over item indices (seenPtr empty = none given);
+    // items / scores are users.size() x n padded with -1 / 0
+    void RecommendUnseenIndexed(const std::vector<int32_t> &users, int n, const std::vector<int64_t> &seenPtr,
+                                const std::vector<int32_t> &seenItems, const std::vector<bool> &itemOk, std::vector<int32_t> &items,
+                                std::vector<float> &scores, std::vector<int32_t> &count);
+
     model::Params Params;
     std::shared_ptr<dataset::FreqDict> UserIndex, ItemIndex;
     std::vector<bool> UserPredictable, ItemPredictable;

@@ -823,28 +823,64 @@ int32_t gh_logics_query_similar_typed_bulk(void *h, const char *collection, cons
 }
 double gh_logics_result_score(int64_t r) { return g_scores[(size_t)r]; }
 
+// MatrixFactorization::RecommendUnseen: user ids '\n'-joined; seen = NULL (no lists given) or CSR over ITEM INDICES (seen_ptr n_users + 1);
+// item_ok: one byte per item index or NULL.  items_out (item indices, padded with -1) and scores_out are n_users x n, count_out n_users.
+int32_t gh_model_recommend_unseen(void *m, const char *user_ids, int64_t n_users, int32_t n, const int64_t *seen_ptr,
+                                  const int32_t *seen_items, const uint8_t *item_ok, int32_t n_item_ok, int32_t *items_out,
+                                  float *scores_out, int32_t *count_out) {
+    return guard([&] {
+        auto *mf = (cf::MatrixFactorization *)m;
+        if (mf->Invalid()) throw std::runtime_error("model is not fitted");
+        std::vector<std::string> ids = split_lines(user_ids);
+        ids.resize((size_t)n_users);
+        std::vector<int32_t> users((size_t)n_users);
+        for (int64_t t = 0; t < n_users; t++) users[(size_t)t] = mf->UserIndex->Id(ids[(size_t)t]);
+        std::vector<int64_t> ptr;
+        std::vector<int32_t> flat;
+        if (seen_ptr) {
+            ptr.assign(seen_ptr, seen_ptr + n_users + 1);
+            flat.assign(seen_items, seen_items + ptr.back());
+        }
+        std::vector<bool> ok(item_ok, item_ok + (item_ok ? n_item_ok : 0));
+        std::vector<int32_t> items, count;
+        std::vector<float> scores;
+        mf->RecommendUnseenIndexed(users, n, ptr, flat, ok, items, scores, count);
+        std::copy(items.begin(), items.end(), items_out);
+        std::copy(scores.begin(), scores.end(), scores_out);
+        std::copy(count.begin(), count.end(), count_out);
+    });
+}
+int32_t gh_model_holds_training_rows(void *m) { return ((cf::MatrixFactorization *)m)->HandleHoldsTrainingRows(); }
+
 // users: Q is n_users x d; excludes: one '\n'-joined id list per user, users separated by '\x1e' (record separator)
+namespace {
+std::vector<logics::UserQuery> parse_user_queries(const float *Q, int64_t n_users, int32_t d, const char *excludes) {
+    std::vector<logics::UserQuery> users((size_t)n_users);
+    std::vector<std::string> per_user;
+    std::string cur;
+    for (const char *p = excludes ? excludes : "";; p++) {
+        if (*p == '\x1e' || *p == 0) {
+            per_user.push_back(cur);
+            cur.clear();
+            if (*p == 0) break;
+        } else {
+            cur.push_back(*p);
+        }
+    }
+    for (int64_t t = 0; t < n_users; t++) {
+        users[(size_t)t].Embedding.assign(Q + t * d, Q + (t + 1) * d);
+        if ((size_t)t < per_user.size()) users[(size_t)t].Exclude = split_lines(per_user[(size_t)t].c_str());
+    }
+    return users;
+}
+}  // namespace
 int32_t gh_logics_cf_recommend_bulk(void *h, const char *collection, const float *Q, int64_t n_users, int32_t d,
                                     const char *excludes, int32_t cache_size) {
-    return guard([&] {
-        std::vector<logics::UserQuery> users((size_t)n_users);
-        std::vector<std::string> per_user;
-        std::string cur;
-        for (const char *p = excludes ? excludes : "";; p++) {
-            if (*p == '\x1e' || *p == 0) {
-                per_user.push_back(cur);
-                cur.clear();
-                if (*p == 0) break;
-            } else {
-                cur.push_back(*p);
-            }
-        }
-        for (int64_t t = 0; t < n_users; t++) {
-            users[(size_t)t].Embedding.assign(Q + t * d, Q + (t + 1) * d);
-            if ((size_t)t < per_user.size()) users[(size_t)t].Exclude = split_lines(per_user[(size_t)t].c_str());
-        }
-        stage_scores(logics::CollaborativeRecommendBulk(vdb(h), collection, users, cache_size));
-    });
+    return guard([&] { stage_scores(logics::CollaborativeRecommendBulk(vdb(h), collection, parse_user_queries(Q, n_users, d, excludes), cache_size)); });
+}
+int32_t gh_logics_cf_recommend_unseen(void *h, const char *collection, const float *Q, int64_t n_users, int32_t d,
+                                      const char *excludes, int32_t cache_size) {
+    return guard([&] { stage_scores(logics::CollaborativeRecommendUnseen(vdb(h), collection, parse_user_queries(Q, n_users, d, excludes), cache_size)); });
 }
 // master/tasks.go:925-969: items of model `m` into collaborative_filtering_<model_id> of database `h`, users into a new
 // MatrixFactorizationUsers (returned; free with gh_mfusers_free).  hidden: one byte per item or NULL; categories: one

@@ -441,6 +441,62 @@ public:
         return out;
     }
 
+    // Every query's topK best admissible (not hidden) vectors of a dense Dot collection that are NOT among the query's excluded ids,
+    // with the exclusion applied on the device (gorse_mf_recommend): a throw-away gorse_mf whose item factors are the collection's
+    // rows, whose user factors are the queries and whose "training rows" are the exclude sets.  Ids the collection does not hold are
+    // ignored.  Unlike the searches above this goes straight to the library (no Searcher): there is no CPU form of it.
+    std::vector<std::vector<ScoredVector>> RecommendUnseenBatch(const std::string &name, const std::vector<float> &queries, int64_t nq,
+                                                               const std::vector<std::vector<std::string>> &exclude, int topK,
+                                                               int device = 0) {
+        std::lock_guard<std::mutex> g(mu_);
+        Collection &c = coll(name);
+        std::vector<std::vector<ScoredVector>> out((size_t)std::max<int64_t>(nq, 0));
+        if (topK <= 0 || nq <= 0) return out;
+        const int d = c.info.Dimension;
+        if (d == 0 || c.info.Dist != Dot) throw std::invalid_argument("RecommendUnseenBatch needs a dense Dot collection, " + name + " is not");
+        if ((int64_t)queries.size() != nq * d)
+            throw std::invalid_argument("query has dimension " + std::to_string(queries.size() / (size_t)nq) + ", collection " + name +
+                                        " has " + std::to_string(d));
+        if (!exclude.empty() && (int64_t)exclude.size() != nq) throw std::invalid_argument("one exclude set per query");
+        const int64_t n = (int64_t)c.rows.size();
+        if (n == 0) return out;
+        std::vector<int64_t> uptr((size_t)nq + 1, 0);
+        std::vector<int32_t> uidx;
+        for (int64_t t = 0; t < nq; t++) {
+            if (!exclude.empty())
+                for (const std::string &id : exclude[(size_t)t]) {
+                    auto it = c.by_id.find(id);
+                    if (it != c.by_id.end()) uidx.push_back((int32_t)it->second);
+                }
+            uptr[(size_t)t + 1] = (int64_t)uidx.size();
+        }
+        if (uidx.empty()) uidx.push_back(0);
+        std::vector<uint8_t> ok((size_t)n);
+        for (int64_t r = 0; r < n; r++) ok[(size_t)r] = admissible(c.rows[(size_t)r], {});
+        struct Handle {
+            gorse_mf *h = nullptr;
+            ~Handle() {
+                if (h) gorse_mf_destroy(h);
+            }
+        } mf;
+        auto check = [](int32_t rc) {
+            if (rc != GORSE_OK) throw std::runtime_error(gorse_hip_last_error());
+        };
+        check(gorse_mf_create(&mf.h, device, nq, n, d, uptr.data(), uidx.data(), nullptr, nullptr));
+        check(gorse_mf_set_factors(mf.h, queries.data(), c.data.data()));
+        std::vector<int32_t> items((size_t)nq * (size_t)topK), count((size_t)nq);
+        std::vector<float> scores((size_t)nq * (size_t)topK);
+        check(gorse_mf_recommend(mf.h, nq, nullptr, topK, ok.data(), nullptr, nullptr, items.data(), scores.data(), count.data()));
+        for (int64_t t = 0; t < nq; t++)
+            for (int32_t e = 0; e < count[(size_t)t]; e++) {
+                ScoredVector sv;
+                static_cast<Vector &>(sv) = c.rows[(size_t)items[(size_t)(t * topK + e)]];
+                sv.Score = scores[(size_t)(t * topK + e)];
+                out[(size_t)t].push_back(std::move(sv));
+            }
+        return out;
+    }
+
 private:
     struct Collection {
         CollectionInfo info;
@@ -764,6 +820,31 @@ inline std::vector<std::vector<Score>> CollaborativeRecommendBulk(vectors::HipDa
             out[t].push_back(std::move(sc));
         }
     }
+    return out;
+}
+
+// The same without the over-fetch (HipDatabase::RecommendUnseenBatch over gorse_mf_recommend): the exclude sets are tested on the
+// device, k stays cacheSize whatever the longest exclude set.  Each user's list is the first cacheSize entries of its
+// CollaborativeRecommendBulk list -- the reference keeps up to |exclude_u| further items, an artefact of its over-fetch.
+inline std::vector<std::vector<Score>> CollaborativeRecommendUnseen(vectors::HipDatabase &client, const std::string &collection,
+                                                                    const std::vector<UserQuery> &users, int cacheSize) {
+    std::vector<std::vector<Score>> out(users.size());
+    if (users.empty()) return out;
+    std::vector<float> Q;
+    std::vector<std::vector<std::string>> exclude;
+    for (const auto &u : users) {
+        Q.insert(Q.end(), u.Embedding.begin(), u.Embedding.end());
+        exclude.push_back(u.Exclude);
+    }
+    auto res = client.RecommendUnseenBatch(collection, Q, (int64_t)users.size(), exclude, cacheSize);
+    for (size_t t = 0; t < users.size(); t++)
+        for (const auto &v : res[t]) {
+            Score sc;
+            sc.Id = v.Id;
+            sc.Value = (double)v.Score;
+            sc.Categories = v.Categories;
+            out[t].push_back(std::move(sc));
+        }
     return out;
 }
 

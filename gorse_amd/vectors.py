@@ -286,6 +286,8 @@ def _logics_host():
         H.gh_logics_query_similar_bulk.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32]
         H.gh_logics_cf_recommend_bulk.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_char_p,
                                                   C.c_int32]
+        H.gh_logics_cf_recommend_unseen.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_char_p,
+                                                    C.c_int32]
         H.gh_logics_result_score.restype = C.c_double
         H.gh_logics_result_score.argtypes = [C.c_int64]
         H._logics_ready = True
@@ -419,6 +421,19 @@ def CollaborativeRecommendBulk(client, collection, embeddings, excludes, cache_s
     ex = "\x1e".join("\n".join(e) for e in excludes)
     _ck(H.gh_logics_cf_recommend_bulk(client.h, collection.encode(), Q.ctypes.data_as(C.POINTER(C.c_float)), Q.shape[0],
                                       Q.shape[1], ex.encode(), cache_size))
+    flat = _scores()
+    cuts = [int(H.gh_vdb_result_split(t)) for t in range(Q.shape[0] + 1)]
+    return [flat[cuts[t]:cuts[t + 1]] for t in range(Q.shape[0])]
+
+
+def CollaborativeRecommendUnseen(client, collection, embeddings, excludes, cache_size):
+    """the same without the over-fetch (gorse_vectors.hpp logics::CollaborativeRecommendUnseen over gorse_mf_recommend): the exclude
+    sets are tested on the device; every user's list is the first cache_size entries of its CollaborativeRecommendBulk list"""
+    H = _logics_host()
+    Q = np.ascontiguousarray(embeddings, np.float32)
+    ex = "\x1e".join("\n".join(e) for e in excludes)
+    _ck(H.gh_logics_cf_recommend_unseen(client.h, collection.encode(), Q.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(Q.shape[0]),
+                                        Q.shape[1], ex.encode(), cache_size))
     flat = _scores()
     cuts = [int(H.gh_vdb_result_split(t)) for t in range(Q.shape[0] + 1)]
     return [flat[cuts[t]:cuts[t + 1]] for t in range(Q.shape[0])]

@@ -110,6 +110,33 @@ int32_t gorse_mf_score(gorse_mf *h, const int32_t *u /*host*/, const int32_t *it
 int32_t gorse_mf_rank(gorse_mf *h, int64_t n_users, const int32_t *users /*host*/, const int64_t *cand_indptr /*host*/,
                       const int32_t *cand /*host*/, int32_t topk, int32_t *rank_out /*host*/, int32_t *rank_len /*host*/);
 
+/* Every user's k best UNSEEN items, straight from the resident model: the bulk form of worker/pipeline.go:403-448
+ * (updateCollaborativeRecommend), without its over-fetch.  For query t with user u = users[t] (users == NULL: u = t, and n_users must
+ * not exceed the handle's users) the candidates are the items i of [0, I), ascending, with
+ *   - item_ok[i] != 0 (item_ok == NULL: the item has at least one training feedback in the handle = IsItemPredictable, what
+ *     master/tasks.go:942 publishes),
+ *   - i not in u's training row held by the handle,
+ *   - i not in seen_items[seen_indptr[t] .. seen_indptr[t + 1]) (seen_indptr == NULL: no such rows; a row may be unsorted, repeat an
+ *     item and overlap the training row),
+ * and the result row is exactly what gorse_mf_rank returns for (u, that list, k): heap.TopKFilter(k) fed in ascending item order and
+ * popped descending, Go container/heap tie behaviour included.  items_out is n_users * k padded with -1, scores_out n_users * k padded
+ * with 0 and holds the bits of gorse_mf_score, count_out[t] = min(k, number of candidates); each may be NULL.  u < 0 gives count 0.
+ * u >= U or a seen item outside [0, I): GORSE_ERR_RANGE; k <= 0: GORSE_ERR_INVALID; everything is validated before anything is
+ * launched, and an error leaves the outputs untouched.  The call waits for epochs still enqueued on the handle and leaves the
+ * factors untouched.
+ * Relation to the reference: its per-user list is the CacheSize + |excludeSet| nearest items minus the excluded ones, so it may hold
+ * up to |excludeSet| items MORE than CacheSize -- an artefact of the over-fetch.  With k = CacheSize this call returns the prefix of
+ * length CacheSize of that list.
+ * A query whose k + 1 best candidate scores are pairwise different (as floats, -0 == +0) and that meets no NaN score is answered
+ * by the threshold kernel (k <= 256); every other query is answered literally (candidate list -> TopKFilter on the device). */
+int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_t *users /*host, or NULL: users[t] = t*/, int32_t k,
+                           const uint8_t *item_ok /*host, I bytes, or NULL*/, const int64_t *seen_indptr /*host, n_users+1, or NULL*/,
+                           const int32_t *seen_items /*host*/, int32_t *items_out /*host or NULL, n_users*k, padded with -1*/,
+                           float *scores_out /*host or NULL, n_users*k, padded with 0*/, int32_t *count_out /*host or NULL, n_users*/);
+/* the handle's last gorse_mf_recommend: queries answered by the threshold kernel (queries with u < 0, which need no answer, are
+ * counted here) / literally, and the device time of its launches (hipEvents around them, copies excluded) */
+int32_t gorse_mf_recommend_stats(gorse_mf *h, int64_t *n_fast, int64_t *n_literal, double *device_ms);
+
 /* dataset.SampleUserNegatives on the device (dataset/dataset.go:242-253 through RandomGenerator.SampleInt32,
  * common/util/random.go:108-132): for EVERY user num_candidates distinct items outside (the user's feedback in the test split
  * given here, union the user's train feedback the handle holds), in draw order -- or ALL remaining items ascending when no

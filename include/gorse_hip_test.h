@@ -180,6 +180,11 @@ int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3 /*host*/);
  * follow those of slot s - 1), rep = every replica row (sum of R x nFactors floats; all zero between two update launches).  Any of the
  * three may be NULL. */
 int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items /*host*/, int32_t *replicas /*host*/, float *rep /*host*/);
+/* gorse_mf_recommend (csrc/recommend.hip).  slices > 0 = the threshold kernel cuts the items into this many slices across workgroups
+ * (at most 8 and at most one per item; 0 = by the number of query blocks); buffer > 0 = entries of a query's survivor buffer (raised to
+ * k + 2 where smaller, the smallest that can hold k + 1 entries and one more: a compaction per survivor; 0 = max(32, 2 (k + 1)));
+ * literal_chunk > 0 = candidates materialised per launch of the literal path at most (0 = 2^22).  Results never depend on them. */
+void gorse_hip_test_set_recommend(int32_t slices, int32_t buffer, int64_t literal_chunk);
 
 #ifdef __cplusplus
 }

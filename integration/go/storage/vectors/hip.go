@@ -423,3 +423,76 @@ func (db *Hip) QuerySparseBatch(ctx context.Context, name string, queries []Vect
 	}
 	return db.querySparse(c, queries, categories, topK)
 }
+
+// RecommendUnseenBatch returns every query's topK best vectors of a dense Dot collection that are not hidden and not among the
+// query's excluded ids, with the exclusion applied on the device (gorse_mf_recommend): a throw-away gorse_mf whose item factors are
+// the collection's rows, whose user factors are the queries and whose "training rows" are the exclude sets.  Ids the collection does
+// not hold are ignored.  worker/pipeline_hip.go calls it with topK = CacheSize instead of over-fetching CacheSize + |excludeSet|.
+func (db *Hip) RecommendUnseenBatch(ctx context.Context, name string, queries [][]float32, exclude [][]string, topK int) ([][]ScoredVector, error) {
+	db.mu.Lock()
+	defer db.mu.Unlock()
+	c, err := db.coll(ctx, name)
+	if err != nil {
+		return nil, err
+	}
+	d, n, nq := c.info.Dimension, len(c.rows), len(queries)
+	out := make([][]ScoredVector, nq)
+	if d == 0 || c.info.Distance != Dot {
+		return nil, errors.Errorf("RecommendUnseenBatch needs a dense Dot collection, %s is not", name)
+	}
+	if exclude != nil && len(exclude) != nq {
+		return nil, errors.Errorf("%d exclude sets for %d queries", len(exclude), nq)
+	}
+	if n == 0 || nq == 0 || topK <= 0 {
+		return out, nil
+	}
+	flatQ := make([]float32, 0, nq*d)
+	uptr := make([]int64, nq+1)
+	uidx := make([]int32, 0, 1)
+	for t, q := range queries {
+		if len(q) != d {
+			return nil, errors.Errorf("query has dimension %d, collection %s has %d", len(q), name, d)
+		}
+		flatQ = append(flatQ, q...)
+		if exclude != nil {
+			for _, id := range exclude[t] {
+				if r, ok := c.byID[id]; ok {
+					uidx = append(uidx, int32(r))
+				}
+			}
+		}
+		uptr[t+1] = int64(len(uidx))
+	}
+	if len(uidx) == 0 {
+		uidx = append(uidx, 0) // &uidx[0] must exist
+	}
+	ok := make([]uint8, n)
+	for r := range c.rows {
+		if admissible(&c.rows[r], nil) {
+			ok[r] = 1
+		}
+	}
+	var h *C.gorse_mf
+	if rc := C.gorse_mf_create(&h, 0, C.int64_t(nq), C.int64_t(n), C.int32_t(d), (*C.int64_t)(unsafe.Pointer(&uptr[0])),
+		(*C.int32_t)(unsafe.Pointer(&uidx[0])), nil, nil); rc != C.GORSE_OK {
+		return nil, lastError("gorse_mf_create")
+	}
+	defer C.gorse_mf_destroy(h)
+	if rc := C.gorse_mf_set_factors(h, (*C.float)(unsafe.Pointer(&flatQ[0])), (*C.float)(unsafe.Pointer(&c.data[0]))); rc != C.GORSE_OK {
+		return nil, lastError("gorse_mf_set_factors")
+	}
+	items := make([]int32, nq*topK)
+	scores := make([]float32, nq*topK)
+	counts := make([]int32, nq)
+	if rc := C.gorse_mf_recommend(h, C.int64_t(nq), nil, C.int32_t(topK), (*C.uint8_t)(unsafe.Pointer(&ok[0])), nil, nil,
+		(*C.int32_t)(unsafe.Pointer(&items[0])), (*C.float)(unsafe.Pointer(&scores[0])), (*C.int32_t)(unsafe.Pointer(&counts[0]))); rc != C.GORSE_OK {
+		return nil, lastError("gorse_mf_recommend")
+	}
+	for t := range out {
+		out[t] = make([]ScoredVector, counts[t])
+		for e := range out[t] {
+			out[t][e] = ScoredVector{Vector: c.rows[items[t*topK+e]], Score: scores[t*topK+e]}
+		}
+	}
+	return out, nil
+}
