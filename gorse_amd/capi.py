@@ -115,6 +115,10 @@ SIGNATURES = {
     "gorse_fm_set_train_embeddings": (C.c_int32, [_vp, C.c_int32, C.POINTER(C.c_uint16)]),
     "gorse_fm_predict_embeddings": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, C.POINTER(C.POINTER(C.c_uint16)),
                                                 C.c_int32, _f32p]),
+    "gorse_fm_set_items": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, _f32p, _i32p, C.POINTER(C.POINTER(C.c_uint16))]),
+    "gorse_fm_rank_users": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, _f32p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p,
+                                        _i32p]),
+    "gorse_fm_rank_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p, _i64p, _f64p]),
     "gorse_hip_test_set_exact_exp": (None, [C.c_int32]),
     "gorse_hip_test_set_variant": (None, [C.c_int32]),
     "gorse_hip_test_set_topk_path": (None, [C.c_int32]),
@@ -164,6 +168,8 @@ SIGNATURES = {
     "gorse_hip_test_bpr_fold_stats": (C.c_int32, [_vp, _vp]),
     "gorse_hip_test_bpr_hot_state": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
+    "gorse_hip_test_set_fm_rank": (None, [C.c_int64, C.c_int32]),
+    "gorse_hip_test_fm_rank_sort": (C.c_int32, [_vp, C.c_int64, _i64p, _f32p, _i32p]),
 }
 
 
@@ -474,6 +480,66 @@ class FM:
         check(lib().gorse_fm_predict_embeddings(self.h, idx.shape[0], idx.shape[1], _p(idx, _i32p), _p(val, _f32p), ptrs,
                                                 int(batch_size), _p(out, _f32p)))
         return out
+
+    def set_items(self, indptr, indices, values, lead=None, embs=()):
+        """the resident item catalogue of rank_users: the items' feature rows as a CSR (item-id entry first when known, then the
+        labels), lead[i] = leading entries that precede the user's labels (None: 0), embs = one n_items x D uint16 (bf16) table
+        per field.  An empty catalogue (indptr of one entry) drops it."""
+        ptr = _arr(indptr, np.int64).reshape(-1)
+        n = ptr.size - 1
+        idx, val = _arr(indices, np.int32).reshape(-1), _arr(values, np.float32).reshape(-1)
+        if n < 0 or idx.size != val.size or (n > 0 and idx.size < ptr[-1]):
+            raise GorseHipError(ERR_INVALID, "indptr holds n_items + 1 entries and indices / values indptr[-1] each")
+        ld = _arr(lead, np.int32).reshape(-1) if lead is not None else None
+        if ld is not None and ld.size != n:
+            raise GorseHipError(ERR_INVALID, "one lead per item")
+        embs = [_arr(e, np.uint16) for e in embs]
+        if n > 0 and (len(embs) != len(self.dims) or any(e.shape != (n, D) for e, D in zip(embs, self.dims))):
+            raise GorseHipError(ERR_INVALID, "one n_items x D embedding table per field")
+        ptrs = (C.POINTER(C.c_uint16) * max(1, len(embs)))(*[_p(e, C.POINTER(C.c_uint16)) for e in embs])
+        check(lib().gorse_fm_set_items(self.h, max(n, 0), _p(ptr, _i64p), _p(idx, _i32p), _p(val, _f32p), _p(ld, _i32p),
+                                       ptrs if embs else None))
+
+    def rank_users(self, user_indptr, user_indices, user_values, cand_indptr, cand, batch_size, user_lead=None, cancel=None,
+                   scores=True, order=True):
+        """(scores, order) of every user's candidates (catalogue rows), flat in cand's layout: scores[cand_indptr[t] + r] = the
+        logit of user t's r-th candidate, order[cand_indptr[t] + r] = the position in t's list of its r-th ranked candidate.
+        scores / order: True = return a new array, False / None = not wanted (None in its place), an array = filled in place."""
+        uptr, cptr = _arr(user_indptr, np.int64).reshape(-1), _arr(cand_indptr, np.int64).reshape(-1)
+        n = uptr.size - 1
+        uidx, uval = _arr(user_indices, np.int32).reshape(-1), _arr(user_values, np.float32).reshape(-1)
+        cd = _arr(cand, np.int32).reshape(-1)
+        if n < 0 or cptr.size != n + 1 or uidx.size != uval.size:
+            raise GorseHipError(ERR_INVALID, "user_indptr and cand_indptr hold n_users + 1 entries each")
+        # the library reads indptr[-1] entries: only a well-formed pointer array may be trusted with that
+        for ptr, arr in ((uptr, uidx), (cptr, cd)):
+            if n > 0 and np.all(np.diff(ptr) >= 0) and ptr[0] == 0 and arr.size < ptr[-1]:
+                raise GorseHipError(ERR_INVALID, "fewer entries than the pointer array names")
+        ul = _arr(user_lead, np.int32).reshape(-1) if user_lead is not None else None
+        if ul is not None and ul.size != n:
+            raise GorseHipError(ERR_INVALID, "one lead per user")
+        total = int(cptr[-1]) if n >= 0 and cptr.size else 0
+        outs = []
+        for want, dt in ((scores, np.float32), (order, np.int32)):
+            if want is True:
+                outs.append(np.zeros(max(total, 0), dt))
+            elif want is None or want is False:
+                outs.append(None)
+            else:
+                if want.dtype != dt or not want.flags.c_contiguous or want.size < total:
+                    raise GorseHipError(ERR_INVALID, "an output array of the wrong type or size")
+                outs.append(want)
+        check(lib().gorse_fm_rank_users(self.h, max(n, 0), _p(uptr, _i64p), _p(uidx, _i32p), _p(uval, _f32p), _p(ul, _i32p),
+                                        _p(cptr, _i64p), _p(cd, _i32p), int(batch_size),
+                                        _p(cancel, _i32p) if cancel is not None else None, _p(outs[0], _f32p), _p(outs[1], _i32p)))
+        return outs[0], outs[1]
+
+    def rank_stats(self):
+        """the last rank_users: rows scored, slices, launch rounds, lists sorted by the host, device milliseconds"""
+        v = [C.c_int64(0) for _ in range(4)]
+        ms = C.c_double(0)
+        check(lib().gorse_fm_rank_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
+        return dict(rows=v[0].value, slices=v[1].value, rounds=v[2].value, host_sorted=v[3].value, device_ms=ms.value)
 
     def close(self):
         if getattr(self, "h", None):

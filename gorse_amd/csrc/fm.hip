@@ -15,99 +15,12 @@
 // Every floats.* call of the reference runs the AVX512 kernels of common/floats/src/floats_avx512.c: a 16-lane FMA body and
 // unfused 8-lane / scalar tails, and partitionAligned(.., 32) leaves the tail at the tensor's last len % 16 elements; the
 // optimizer kernel applies the same rule by element position (fmaf vs. mul then add; the library builds with -ffp-contract=off).
-#include "common.hpp"
-#include "cf_device.hpp"
-
-namespace gorse {
-namespace fm {
-constexpr int kMaxFields = 8;     // embedding fields per model
-constexpr int kMaxEmbDim = 4096;  // floats per embedding
-constexpr int kGradSegs = 8;      // row segments the branch's parameter gradients are summed in (fixed: the order depends on shapes alone)
-
-// one dense tensor of the embedding branch for the optimizer pass: read from device memory by tensor number
-struct DenseDesc {
-    float *p, *m, *v;
-    const float *g;   // kGradSegs partial sums, gstride apart
-    int64_t len, gstride;
-};
-
-// One embedding field: H (d x D) | Wa (D x d) | ba (d) | We (D x d) | be (d) in one allocation, every tensor starting at a
-// multiple of four floats; the moments lie in the same layout.
-struct Field {
-    int D = 0;
-    size_t off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0}, total = 0;
-    DevBuf<float> p, m, v;
-    DevBuf<float> gpart;    // kGradSegs x (dH: d*D | dWa,dba: (D+1)*d | dWe,dbe: (D+1)*d)
-    DevBuf<uint16_t> x;     // the training set's embeddings, n x D bf16
-    bool have_x = false;
-    DevBuf<float> h, a;     // per batch: relu(pre) (rows x d), the softmax output (rows x D; holds s, then e, then a)
-    size_t gstride() const { return len[0] + 2 * (len[1] + len[2]); }
-};
-}  // namespace fm
-}  // namespace gorse
-
-struct gorse_fm {
-    int device = 0;
-    int64_t nf = 0;
-    int d = 0;
-    hipStream_t s = nullptr;
-    gorse::DevBuf<float> V, W, B, mV, mW, mB, vV, vW, vB;  // parameters and Adam moments, one allocation per tensor
-    gorse::DevBuf<int64_t> tag;                            // per feature row: ((step + 1) << 32) | slot of the step that touched it
-    int64_t step = 0;                                      // training steps this handle has run (the tags' clock)
-    int64_t adam_t = 0;                                    // nn.Adam's t: reset by set_params (a new Fit)
-    // training set
-    int64_t n = 0;
-    int width = 0;
-    std::vector<int32_t> h_idx;
-    std::vector<float> h_val;
-    gorse::DevBuf<int32_t> idx;
-    gorse::DevBuf<float> val, tgt;
-    // per-batch-size plan: for every batch the features it touches (ascending) and each one's positions (ascending)
-    int plan_bs = 0;
-    std::vector<int64_t> uoff;  // n_batches + 1: slots of batch k = [uoff[k], uoff[k+1])
-    int64_t max_slots = 0;
-    gorse::DevBuf<int32_t> uniq, seg, pos;
-    // scratch
-    gorse::DevBuf<float> gs, loss, vx, gV, gW, gB, cost;
-    gorse::DevBuf<int32_t> p_idx;
-    gorse::DevBuf<float> p_val, p_out;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // the item-embedding branch (fm.go:127-132): empty unless gorse_fm_set_embedding_dims configured fields
-    int n_fields = 0;
-    gorse::fm::Field fld[gorse::fm::kMaxFields];
-    gorse::DevBuf<gorse::fm::DenseDesc> descs;
-    int64_t dense_blocks = 0;  // blocks of the longest dense tensor
-    gorse::DevBuf<float> a_rmax, a_rsum, a_sumdx, a_gx, a_dpre, a_esum, a_vxe, a_logit;
-    gorse::DevBuf<uint16_t> p_x;
-    gorse::DevBuf<float> p_zero, p_gs, p_loss, p_vx;
-};
+#include "fm_internal.hpp"
 
 namespace gorse {
 namespace fm {
 
-constexpr int kBlock = 256;
-constexpr int kMaxFactors = 128;
 constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kEps = 1e-8f;
-
-// lanes per sample: the smallest of 8 / 16 / 32 / 64 that holds d (two factors per lane above 64)
-inline int lanes_for(int d) {
-    int g = 8;
-    while (g < d && g < 64) g *= 2;
-    return g;
-}
-
-// sum over each aligned group of G lanes; the group's first lane holds the total (a fixed tree: deterministic)
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-    if constexpr (G == 8) {
-        v = group_tree8_halves(v);
-    } else {
-        v = group_tree16(v);
-        if constexpr (G >= 32) v = v + __shfl_xor(v, 16, 64);
-        if constexpr (G == 64) v = v + __shfl_xor(v, 32, 64);
-    }
-    return v;
-}
 
 struct FwdArgs {
     const int32_t *idx;  // n x width
@@ -136,24 +49,9 @@ __global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs a) {
     for (int j = 0; j < a.width; j++) {
         const float x = rv[j];
         if (x == 0.0f) continue;  // padding (index 0, value 0) and zero values add only signed zeros
-        const int64_t id = ri[j];
-        const float *vr = a.V + id * a.d;
-        const float x2 = x * x;
-#pragma unroll
-        for (int k = 0; k < NF; k++) {
-            const int f = lane + k * G;
-            if (f < a.d) {
-                const float v = vr[f];
-                vx[k] = fmaf(v, x, vx[k]);
-                sq[k] = fmaf(v * v, x2, sq[k]);
-            }
-        }
-        lin = fmaf(a.W[id], x, lin);
+        fm_entry<G, NF>(a.V, a.W, a.d, lane, ri[j], x, vx, sq, lin);
     }
-    float part = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NF; k++) part += vx[k] * vx[k] - sq[k];
-    part = group_sum<G>(part);
+    const float logit = fm_logit<G, NF>(vx, sq, lin, a.B);  // the group's first lane holds it
     if (TRAIN) {
 #pragma unroll
         for (int k = 0; k < NF; k++) {
@@ -162,7 +60,6 @@ __global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs a) {
         }
     }
     if (lane != 0) return;
-    const float logit = (lin + 0.5f * part) + a.B[0];
     if (!TRAIN) {
         a.out[b] = logit;
         return;
@@ -405,172 +302,16 @@ __global__ __launch_bounds__(kBlock) void fm_opt_kernel(OptArgs a) {
 // forward and backward (op.go:760-777).  These kernels reproduce that indexing, so every maximum must exist before any
 // exponential and every sum before any a: three launches forward, two backward plus the parameter-gradient reduction.
 // One wave per row; lanes stride over the D columns; skinny products are formed 16 factors at a time and wave-reduced in
-// a fixed butterfly.
-
-constexpr int kFC = 16;  // factors per accumulator chunk
-
-struct AttArgs {
-    const uint16_t *x;  // the batch rows' embeddings, nrows x D bf16
-    const float *H, *Wa, *ba, *We, *be;
-    int64_t nrows;
-    int D, d;
-    float *h;           // nrows x d
-    float *s;           // nrows x D: s (att_score), e (att_exp), a (att_enc)
-    float *rmax, *rsum; // nrows
-    const float *vx;    // nrows x d
-    float *logit;       // nrows: the field's contribution is added
-    float *esum;        // nrows x d: sum of the fields' enc (training), or NULL
-    int first;          // field 0 writes esum, later fields add
-    // backward
-    const float *gs;    // nrows: the loss gradient of the rows' logits
-    float *gx;          // nrows x D: a * da, then ds
-    float *sumdx;       // nrows
-    float *dpre;        // nrows x d
-    float *gpart;       // kGradSegs x Field::gstride()
-    int64_t gstride;
-};
-
-__device__ __forceinline__ float bf16_f32(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// w[k] = M[c, f0 + k] of a row-major (D x d) matrix, zero past d; 16-byte loads where d is a multiple of four
-__device__ __forceinline__ void load_w16(const float *M, int64_t c, int d, int f0, bool vec, float (&w)[kFC]) {
-    const float *p = M + c * d + f0;
-    if (vec) {
-#pragma unroll
-        for (int j = 0; j < kFC / 4; j++) {
-            float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (f0 + 4 * j < d) t = *reinterpret_cast<const float4 *>(p + 4 * j);
-            w[4 * j] = t.x, w[4 * j + 1] = t.y, w[4 * j + 2] = t.z, w[4 * j + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kFC; k++) w[k] = f0 + k < d ? p[k] : 0.0f;
-    }
-}
-
-// the wave's total of every acc[k]; lane k keeps total k (selected without indexing the array by a register)
-__device__ __forceinline__ float reduce_pick(float (&acc)[kFC], int lane) {
-    float mine = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kFC; k++) {
-        const float t = wave_sum(acc[k]);
-        if (lane == k) mine = t;
-    }
-    return mine;
-}
+// a fixed butterfly.  The three forward kernels' bodies are in fm_internal.hpp, shared with fm_rank.hip.
 
 // pre, h = relu(pre), s = h H and each row's maximum of s
-__global__ __launch_bounds__(kBlock) void att_score_kernel(AttArgs a) {
-    __shared__ float sh[kBlock / 64][kMaxFactors];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
-    const bool live = r < a.nrows;
-    const bool vec = (a.d & 3) == 0;
-    if (live) {
-        const uint16_t *xr = a.x + r * a.D;
-        for (int f0 = 0; f0 < a.d; f0 += kFC) {
-            float acc[kFC];
-#pragma unroll
-            for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
-            for (int c = lane; c < a.D; c += 64) {
-                const float xv = bf16_f32(xr[c]);
-                float wv[kFC];
-                load_w16(a.Wa, c, a.d, f0, vec, wv);
-#pragma unroll
-                for (int k = 0; k < kFC; k++) acc[k] = fmaf(xv, wv[k], acc[k]);
-            }
-            const float mine = reduce_pick(acc, lane);
-            if (lane < kFC && f0 + lane < a.d) {
-                const float hv = fmaxf(mine + a.ba[f0 + lane], 0.0f);
-                sh[w][f0 + lane] = hv;
-                a.h[r * a.d + f0 + lane] = hv;
-            }
-        }
-    }
-    __syncthreads();
-    if (!live) return;
-    float *sr = a.s + r * a.D;
-    float mx = -INFINITY;
-    for (int c = lane; c < a.D; c += 64) {
-        float acc = 0.0f;
-        for (int f = 0; f < a.d; f++) acc = fmaf(sh[w][f], a.H[(int64_t)f * a.D + c], acc);  // floats.MM's chain over f
-        sr[c] = acc;
-        mx = fmaxf(mx, acc);
-    }
-    mx = wave_max(mx);
-    if (lane == 0) a.rmax[r] = mx;
-}
+__global__ __launch_bounds__(kBlock) void att_score_kernel(AttArgs a) { att_score_body(a, BatchRows{}); }
 
 // e = exp(s - max[(r D + c) % n]) through fp64 (float32(math.Exp(float64(.))), tensor.go:414-419) and each row's sum of e
-__global__ __launch_bounds__(kBlock) void att_exp_kernel(AttArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (r >= a.nrows) return;
-    const uint32_t n = (uint32_t)a.nrows;
-    const uint32_t m0 = (uint32_t)((r * a.D) % a.nrows);
-    float *sr = a.s + r * a.D;
-    float sum = 0.0f;
-    for (int c = lane; c < a.D; c += 64) {
-        const uint32_t m = (m0 + (uint32_t)c) % n;
-        const float e = (float)exp((double)(sr[c] - a.rmax[m]));
-        sr[c] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) a.rsum[r] = sum;
-}
+__global__ __launch_bounds__(kBlock) void att_exp_kernel(AttArgs a) { att_exp_body(a, BatchRows{}); }
 
 // a = e / sum[(r D + c) % n], z = a * x, enc = z We + be, logit += sum_f vx_f enc_f
-__global__ __launch_bounds__(kBlock) void att_enc_kernel(AttArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (r >= a.nrows) return;
-    const bool vec = (a.d & 3) == 0;
-    const uint32_t n = (uint32_t)a.nrows;
-    const uint32_t m0 = (uint32_t)((r * a.D) % a.nrows);
-    const uint16_t *xr = a.x + r * a.D;
-    float *sr = a.s + r * a.D;
-    float contrib = 0.0f;
-    for (int f0 = 0; f0 < a.d; f0 += kFC) {
-        float acc[kFC];
-#pragma unroll
-        for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
-        for (int c = lane; c < a.D; c += 64) {
-            float av = sr[c];
-            if (f0 == 0) {  // the first chunk turns e into a in place (this lane owns the element in every chunk)
-                av = av / a.rsum[(m0 + (uint32_t)c) % n];
-                sr[c] = av;
-            }
-            const float zv = av * bf16_f32(xr[c]);
-            float wv[kFC];
-            load_w16(a.We, c, a.d, f0, vec, wv);
-#pragma unroll
-            for (int k = 0; k < kFC; k++) acc[k] = fmaf(zv, wv[k], acc[k]);
-        }
-        const float mine = reduce_pick(acc, lane);
-        float part = 0.0f;
-        if (lane < kFC && f0 + lane < a.d) {
-            const int64_t o = r * a.d + f0 + lane;
-            const float enc = mine + a.be[f0 + lane];
-            if (a.esum) a.esum[o] = a.first ? enc : a.esum[o] + enc;
-            part = a.vx[o] * enc;
-        }
-        contrib += wave_sum(part);
-    }
-    if (lane == 0) a.logit[r] = a.logit[r] + contrib;
-}
+__global__ __launch_bounds__(kBlock) void att_enc_kernel(AttArgs a) { att_enc_body(a, BatchRows{}); }
 
 struct LossArgs {
     const float *logit, *tgt;  // tgt: the batch's rows
@@ -901,8 +642,6 @@ int32_t build_plan(gorse_fm *h, int32_t bs) {
 
 // ---- the embedding branch: host side -----------------------------------------------------
 
-inline unsigned row_grid(int64_t nrows) { return (unsigned)ceil_div(nrows, kBlock / 64); }
-
 // per-batch buffers of the branch for batches of up to `rows` rows; train: also what the backward needs
 int32_t ensure_branch(gorse_fm *h, int64_t rows, bool train) {
     int maxD = 1;
@@ -1018,6 +757,8 @@ extern "C" int32_t gorse_fm_destroy(gorse_fm *h) {
     if (h->s) (void)hipStreamSynchronize(h->s);
     for (auto e : h->ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto e : h->r_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->s) (void)hipStreamDestroy(h->s);
     delete h;
     return GORSE_OK;
@@ -1090,6 +831,7 @@ extern "C" int32_t gorse_fm_set_embedding_dims(gorse_fm *h, int32_t n_fields, co
         F.have_x = false;
         F.D = 0;
     }
+    h->cat.reset();  // the resident item catalogue holds one table per field of the set that is going away
     h->n_fields = 0;
     h->dense_blocks = 0;
     std::vector<fm::DenseDesc> descs;

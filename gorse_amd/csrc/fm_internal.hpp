@@ -1,0 +1,350 @@
+// fm_internal.hpp -- what fm.hip (training, batch scoring) and fm_rank.hip (ranking from a resident item catalogue) share: the
+// handle, the per-entry body of the factorization machine's forward pass, and the bodies of the attention branch's three
+// forward kernels.  The bodies are written once and instantiated by both files' kernels, so the scores of the two agree in
+// every bit by construction.
+#pragma once
+#include <memory>
+
+#include "common.hpp"
+#include "cf_device.hpp"
+
+namespace gorse {
+namespace fm {
+constexpr int kMaxFields = 8;     // embedding fields per model
+constexpr int kMaxEmbDim = 4096;  // floats per embedding
+constexpr int kGradSegs = 8;      // row segments the branch's parameter gradients are summed in (fixed: the order depends on shapes alone)
+
+// one dense tensor of the embedding branch for the optimizer pass: read from device memory by tensor number
+struct DenseDesc {
+    float *p, *m, *v;
+    const float *g;   // kGradSegs partial sums, gstride apart
+    int64_t len, gstride;
+};
+
+// One embedding field: H (d x D) | Wa (D x d) | ba (d) | We (D x d) | be (d) in one allocation, every tensor starting at a
+// multiple of four floats; the moments lie in the same layout.
+struct Field {
+    int D = 0;
+    size_t off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0}, total = 0;
+    DevBuf<float> p, m, v;
+    DevBuf<float> gpart;    // kGradSegs x (dH: d*D | dWa,dba: (D+1)*d | dWe,dbe: (D+1)*d)
+    DevBuf<uint16_t> x;     // the training set's embeddings, n x D bf16
+    bool have_x = false;
+    DevBuf<float> h, a;     // per batch: relu(pre) (rows x d), the softmax output (rows x D; holds s, then e, then a)
+    size_t gstride() const { return len[0] + 2 * (len[1] + len[2]); }
+};
+
+// The resident item side of gorse_fm_rank_users (gorse_fm_set_items): the items' feature rows as one CSR, each row's number of
+// leading entries, and one n_items x D bf16 table per embedding field.  Replaced as a whole.
+struct Catalogue {
+    int64_t n_items = 0;
+    DevBuf<int64_t> ptr;    // n_items + 1
+    DevBuf<int32_t> idx, lead;
+    DevBuf<float> val;
+    DevBuf<uint16_t> emb[kMaxFields];
+};
+}  // namespace fm
+}  // namespace gorse
+
+struct gorse_fm {
+    int device = 0;
+    int64_t nf = 0;
+    int d = 0;
+    hipStream_t s = nullptr;
+    gorse::DevBuf<float> V, W, B, mV, mW, mB, vV, vW, vB;  // parameters and Adam moments, one allocation per tensor
+    gorse::DevBuf<int64_t> tag;                            // per feature row: ((step + 1) << 32) | slot of the step that touched it
+    int64_t step = 0;                                      // training steps this handle has run (the tags' clock)
+    int64_t adam_t = 0;                                    // nn.Adam's t: reset by set_params (a new Fit)
+    // training set
+    int64_t n = 0;
+    int width = 0;
+    std::vector<int32_t> h_idx;
+    std::vector<float> h_val;
+    gorse::DevBuf<int32_t> idx;
+    gorse::DevBuf<float> val, tgt;
+    // per-batch-size plan: for every batch the features it touches (ascending) and each one's positions (ascending)
+    int plan_bs = 0;
+    std::vector<int64_t> uoff;  // n_batches + 1: slots of batch k = [uoff[k], uoff[k+1])
+    int64_t max_slots = 0;
+    gorse::DevBuf<int32_t> uniq, seg, pos;
+    // scratch
+    gorse::DevBuf<float> gs, loss, vx, gV, gW, gB, cost;
+    gorse::DevBuf<int32_t> p_idx;
+    gorse::DevBuf<float> p_val, p_out;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // the item-embedding branch (fm.go:127-132): empty unless gorse_fm_set_embedding_dims configured fields
+    int n_fields = 0;
+    gorse::fm::Field fld[gorse::fm::kMaxFields];
+    gorse::DevBuf<gorse::fm::DenseDesc> descs;
+    int64_t dense_blocks = 0;  // blocks of the longest dense tensor
+    gorse::DevBuf<float> a_rmax, a_rsum, a_sumdx, a_gx, a_dpre, a_esum, a_vxe, a_logit;
+    gorse::DevBuf<uint16_t> p_x;
+    gorse::DevBuf<float> p_zero, p_gs, p_loss, p_vx;
+    // ranking from a resident catalogue (fm_rank.hip): buffers of its own, nothing here is read by training or by predict
+    std::unique_ptr<gorse::fm::Catalogue> cat;
+    gorse::DevBuf<int64_t> r_uptr, r_cptr;          // the call's user CSR pointer and candidate pointer
+    gorse::DevBuf<int32_t> r_uidx, r_ulead, r_desc;  // r_desc: user | item | slice row0 | slice length, each one entry per row
+    gorse::DevBuf<float> r_uval;
+    gorse::DevBuf<float> r_vx, r_h, r_s, r_rmax, r_rsum, r_scores;
+    gorse::DevBuf<int32_t> r_order;
+    hipEvent_t r_ev[2] = {nullptr, nullptr};  // timing events of gorse_fm_rank_stats, created by the first rank call
+    int64_t rk_rows = 0, rk_slices = 0, rk_rounds = 0, rk_host_sorted = 0;
+    double rk_ms = 0.0;
+};
+
+namespace gorse {
+namespace fm {
+
+constexpr int kBlock = 256;
+constexpr int kMaxFactors = 128;
+
+// lanes per sample: the smallest of 8 / 16 / 32 / 64 that holds d (two factors per lane above 64)
+inline int lanes_for(int d) {
+    int g = 8;
+    while (g < d && g < 64) g *= 2;
+    return g;
+}
+
+inline unsigned row_grid(int64_t nrows) { return (unsigned)ceil_div(nrows, kBlock / 64); }
+
+// sum over each aligned group of G lanes; the group's first lane holds the total (a fixed tree: deterministic)
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+    if constexpr (G == 8) {
+        v = group_tree8_halves(v);
+    } else {
+        v = group_tree16(v);
+        if constexpr (G >= 32) v = v + __shfl_xor(v, 16, 64);
+        if constexpr (G == 64) v = v + __shfl_xor(v, 32, 64);
+    }
+    return v;
+}
+
+// One nonzero entry (feature id, value x) of a row joins the lane's chains: vx_f += V[id, f] x, sq_f += V[id, f]^2 x^2 for the
+// lane's factors f = lane + k G, and lin += W[id] x.  The one statement of the forward pass's arithmetic.
+template <int G, int NF>
+__device__ __forceinline__ void fm_entry(const float *V, const float *W, int d, int lane, int64_t id, float x, float (&vx)[NF],
+                                         float (&sq)[NF], float &lin) {
+    const float *vr = V + id * d;
+    const float x2 = x * x;
+#pragma unroll
+    for (int k = 0; k < NF; k++) {
+        const int f = lane + k * G;
+        if (f < d) {
+            const float v = vr[f];
+            vx[k] = fmaf(v, x, vx[k]);
+            sq[k] = fmaf(v * v, x2, sq[k]);
+        }
+    }
+    lin = fmaf(W[id], x, lin);
+}
+
+// the row's logit from its chains (valid in the group's first lane)
+template <int G, int NF>
+__device__ __forceinline__ float fm_logit(const float (&vx)[NF], const float (&sq)[NF], float lin, const float *B) {
+    float part = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NF; k++) part += vx[k] * vx[k] - sq[k];
+    part = group_sum<G>(part);
+    return (lin + 0.5f * part) + B[0];
+}
+
+// ---- the item-embedding branch: forward bodies -----------------------------------------------------------------------------
+
+constexpr int kFC = 16;  // factors per accumulator chunk
+
+struct AttArgs {
+    const uint16_t *x;  // the batch rows' embeddings, nrows x D bf16 (ranking: the field's item table)
+    const float *H, *Wa, *ba, *We, *be;
+    int64_t nrows;
+    int D, d;
+    float *h;           // nrows x d
+    float *s;           // nrows x D: s (att_score), e (att_exp), a (att_enc)
+    float *rmax, *rsum; // nrows
+    const float *vx;    // nrows x d
+    float *logit;       // nrows: the field's contribution is added
+    float *esum;        // nrows x d: sum of the fields' enc (training), or NULL
+    int first;          // field 0 writes esum, later fields add
+    // backward
+    const float *gs;    // nrows: the loss gradient of the rows' logits
+    float *gx;          // nrows x D: a * da, then ds
+    float *sumdx;       // nrows
+    float *dpre;        // nrows x d
+    float *gpart;       // kGradSegs x Field::gstride()
+    int64_t gstride;
+};
+
+// Where a launch's rows come from.  BatchRows: the launch is one batch, row r's embedding is row r of x, and the Softmax's
+// maxima and sums are indexed over the whole launch.  SliceRows (ranking): the launch holds many slices, each a batch of its
+// own; row r's embedding is row item[r] of the field's table, read in place, and r carries its slice's first row and length.
+struct BatchRows {
+    __device__ __forceinline__ const uint16_t *x(const AttArgs &a, int64_t r) const { return a.x + r * a.D; }
+    // n = the slice's rows, base = its first row, returns (local row x D) % n
+    __device__ __forceinline__ uint32_t wrap(const AttArgs &a, int64_t r, uint32_t &n, int64_t &base) const {
+        n = (uint32_t)a.nrows;
+        base = 0;
+        return (uint32_t)((r * a.D) % a.nrows);
+    }
+};
+struct SliceRows {
+    const int32_t *item, *row0, *len;  // per row of the launch
+    __device__ __forceinline__ const uint16_t *x(const AttArgs &a, int64_t r) const { return a.x + (int64_t)item[r] * a.D; }
+    __device__ __forceinline__ uint32_t wrap(const AttArgs &a, int64_t r, uint32_t &n, int64_t &base) const {
+        const int64_t sn = len[r];
+        n = (uint32_t)sn;
+        base = row0[r];
+        return (uint32_t)(((r - base) * a.D) % sn);
+    }
+};
+
+__device__ __forceinline__ float bf16_f32(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// w[k] = M[c, f0 + k] of a row-major (D x d) matrix, zero past d; 16-byte loads where d is a multiple of four
+__device__ __forceinline__ void load_w16(const float *M, int64_t c, int d, int f0, bool vec, float (&w)[kFC]) {
+    const float *p = M + c * d + f0;
+    if (vec) {
+#pragma unroll
+        for (int j = 0; j < kFC / 4; j++) {
+            float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (f0 + 4 * j < d) t = *reinterpret_cast<const float4 *>(p + 4 * j);
+            w[4 * j] = t.x, w[4 * j + 1] = t.y, w[4 * j + 2] = t.z, w[4 * j + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kFC; k++) w[k] = f0 + k < d ? p[k] : 0.0f;
+    }
+}
+
+// the wave's total of every acc[k]; lane k keeps total k (selected without indexing the array by a register)
+__device__ __forceinline__ float reduce_pick(float (&acc)[kFC], int lane) {
+    float mine = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kFC; k++) {
+        const float t = wave_sum(acc[k]);
+        if (lane == k) mine = t;
+    }
+    return mine;
+}
+
+// pre, h = relu(pre), s = h H and each row's maximum of s
+template <class Rows>
+__device__ __forceinline__ void att_score_body(const AttArgs &a, const Rows &rows) {
+    __shared__ float sh[kBlock / 64][kMaxFactors];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
+    const bool live = r < a.nrows;
+    const bool vec = (a.d & 3) == 0;
+    if (live) {
+        const uint16_t *xr = rows.x(a, r);
+        for (int f0 = 0; f0 < a.d; f0 += kFC) {
+            float acc[kFC];
+#pragma unroll
+            for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
+            for (int c = lane; c < a.D; c += 64) {
+                const float xv = bf16_f32(xr[c]);
+                float wv[kFC];
+                load_w16(a.Wa, c, a.d, f0, vec, wv);
+#pragma unroll
+                for (int k = 0; k < kFC; k++) acc[k] = fmaf(xv, wv[k], acc[k]);
+            }
+            const float mine = reduce_pick(acc, lane);
+            if (lane < kFC && f0 + lane < a.d) {
+                const float hv = fmaxf(mine + a.ba[f0 + lane], 0.0f);
+                sh[w][f0 + lane] = hv;
+                a.h[r * a.d + f0 + lane] = hv;
+            }
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    float *sr = a.s + r * a.D;
+    float mx = -INFINITY;
+    for (int c = lane; c < a.D; c += 64) {
+        float acc = 0.0f;
+        for (int f = 0; f < a.d; f++) acc = fmaf(sh[w][f], a.H[(int64_t)f * a.D + c], acc);  // floats.MM's chain over f
+        sr[c] = acc;
+        mx = fmaxf(mx, acc);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) a.rmax[r] = mx;
+}
+
+// e = exp(s - max[(r D + c) % n]) through fp64 (float32(math.Exp(float64(.))), tensor.go:414-419) and each row's sum of e
+template <class Rows>
+__device__ __forceinline__ void att_exp_body(const AttArgs &a, const Rows &rows) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= a.nrows) return;
+    uint32_t n;
+    int64_t base;
+    const uint32_t m0 = rows.wrap(a, r, n, base);
+    const float *rmax = a.rmax + base;
+    float *sr = a.s + r * a.D;
+    float sum = 0.0f;
+    for (int c = lane; c < a.D; c += 64) {
+        const uint32_t m = (m0 + (uint32_t)c) % n;
+        const float e = (float)exp((double)(sr[c] - rmax[m]));
+        sr[c] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) a.rsum[r] = sum;
+}
+
+// a = e / sum[(r D + c) % n], z = a * x, enc = z We + be, logit += sum_f vx_f enc_f
+template <class Rows>
+__device__ __forceinline__ void att_enc_body(const AttArgs &a, const Rows &rows) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= a.nrows) return;
+    const bool vec = (a.d & 3) == 0;
+    uint32_t n;
+    int64_t base;
+    const uint32_t m0 = rows.wrap(a, r, n, base);
+    const float *rsum = a.rsum + base;
+    const uint16_t *xr = rows.x(a, r);
+    float *sr = a.s + r * a.D;
+    float contrib = 0.0f;
+    for (int f0 = 0; f0 < a.d; f0 += kFC) {
+        float acc[kFC];
+#pragma unroll
+        for (int k = 0; k < kFC; k++) acc[k] = 0.0f;
+        for (int c = lane; c < a.D; c += 64) {
+            float av = sr[c];
+            if (f0 == 0) {  // the first chunk turns e into a in place (this lane owns the element in every chunk)
+                av = av / rsum[(m0 + (uint32_t)c) % n];
+                sr[c] = av;
+            }
+            const float zv = av * bf16_f32(xr[c]);
+            float wv[kFC];
+            load_w16(a.We, c, a.d, f0, vec, wv);
+#pragma unroll
+            for (int k = 0; k < kFC; k++) acc[k] = fmaf(zv, wv[k], acc[k]);
+        }
+        const float mine = reduce_pick(acc, lane);
+        float part = 0.0f;
+        if (lane < kFC && f0 + lane < a.d) {
+            const int64_t o = r * a.d + f0 + lane;
+            const float enc = mine + a.be[f0 + lane];
+            if (a.esum) a.esum[o] = a.first ? enc : a.esum[o] + enc;
+            part = a.vx[o] * enc;
+        }
+        contrib += wave_sum(part);
+    }
+    if (lane == 0) a.logit[r] = a.logit[r] + contrib;
+}
+
+}  // namespace fm
+}  // namespace gorse

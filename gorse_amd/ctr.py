@@ -32,6 +32,8 @@ def host():
         H.gh_fm_params.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
         H.gh_ctr_dataset_set_embeddings.argtypes = [C.c_void_p, C.c_int32, _i32p, C.POINTER(_u16p)]
         H.gh_fm_field_params.argtypes = [C.c_void_p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]
+        H.gh_ctr_fm_set_items.argtypes = [C.c_void_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, C.c_int32, C.POINTER(_u16p)]
+        H.gh_ctr_fm_rank_users.argtypes = [C.c_void_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, _i64p, _i32p, _i32p, _f32p]
         _configured = True
     return H
 
@@ -167,3 +169,40 @@ class FM:
         arrs = [np.zeros(shp, np.float32) for shp in ((d, D), (D, d), (d,), (D, d), (d,))]
         host().gh_fm_field_params(self.p, field, *[a.ctypes.data_as(_f32p) for a in arrs])
         return tuple(arrs)
+
+    @staticmethod
+    def _label_rows(ids, rows):
+        """ids: each entity's own feature index (negative: unknown to the index); rows: per entity [(label index, value)] with a
+        negative index for an unknown label"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        ptr = np.zeros(len(rows) + 1, np.int64)
+        ptr[1:] = np.cumsum([len(r) for r in rows])
+        lab = np.array([l for r in rows for l, _ in r] or [0], np.int32)
+        val = np.array([v for r in rows for _, v in r] or [0], np.float32)
+        if ids.size != len(rows):
+            raise ValueError("one id per label row")
+        return ids, ptr, lab, val
+
+    def SetItems(self, ids, rows, embs=()):
+        """the resident catalogue of RankUsers: items as label rows, one n_items x D uint16 (bf16) table per field"""
+        ids, ptr, lab, val = self._label_rows(ids, rows)
+        embs = [np.ascontiguousarray(e, np.uint16) for e in embs]
+        ptrs = (_u16p * max(1, len(embs)))(*[e.ctypes.data_as(_u16p) for e in embs])
+        rc = host().gh_ctr_fm_set_items(self.p, ids.size, ids.ctypes.data_as(_i32p), ptr.ctypes.data_as(_i64p),
+                                        lab.ctypes.data_as(_i32p), val.ctypes.data_as(_f32p), len(embs), ptrs)
+        if rc != 0:
+            raise cf.HostError(rc)
+
+    def RankUsers(self, ids, rows, cands):
+        """users as label rows and each one's candidates (catalogue rows) -> per user [(item, score)], best first"""
+        ids, ptr, lab, val = self._label_rows(ids, rows)
+        cptr = np.zeros(len(cands) + 1, np.int64)
+        cptr[1:] = np.cumsum([len(c) for c in cands])
+        flat = np.array([c for cl in cands for c in cl] or [0], np.int32)
+        items, scores = np.zeros(max(1, int(cptr[-1])), np.int32), np.zeros(max(1, int(cptr[-1])), np.float32)
+        rc = host().gh_ctr_fm_rank_users(self.p, ids.size, ids.ctypes.data_as(_i32p), ptr.ctypes.data_as(_i64p),
+                                         lab.ctypes.data_as(_i32p), val.ctypes.data_as(_f32p), cptr.ctypes.data_as(_i64p),
+                                         flat.ctypes.data_as(_i32p), items.ctypes.data_as(_i32p), scores.ctypes.data_as(_f32p))
+        if rc != 0:
+            raise cf.HostError(rc)
+        return [[(int(items[j]), scores[j]) for j in range(int(cptr[t]), int(cptr[t + 1]))] for t in range(len(cands))]

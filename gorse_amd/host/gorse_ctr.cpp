@@ -116,6 +116,60 @@ std::vector<float> FM::BatchInternalPredict(const Dataset &ds, const std::vector
     return out;
 }
 
+// BatchPredict's encoding of one side (fm.go:183-206): the id entry with value 1 when the index knows the entity, then the
+// labels it knows, in order; lead = 1 exactly when the id entry is there
+static void encode_rows(const LabelRows &rows, std::vector<int64_t> &ptr, std::vector<int32_t> &idx, std::vector<float> &val,
+                        std::vector<int32_t> &lead) {
+    const int64_t n = rows.Count();
+    if ((int64_t)rows.indptr.size() != n + 1) throw std::invalid_argument("label rows: indptr must hold Count() + 1 entries");
+    ptr.assign(1, 0);
+    idx.clear(), val.clear(), lead.clear();
+    for (int64_t i = 0; i < n; i++) {
+        const bool known = rows.id[(size_t)i] >= 0;
+        if (known) idx.push_back(rows.id[(size_t)i]), val.push_back(1.0f);
+        lead.push_back(known ? 1 : 0);
+        for (int64_t j = rows.indptr[(size_t)i]; j < rows.indptr[(size_t)i + 1]; j++)
+            if (rows.label[(size_t)j] >= 0) idx.push_back(rows.label[(size_t)j]), val.push_back(rows.value[(size_t)j]);
+        ptr.push_back((int64_t)idx.size());
+    }
+}
+
+void FM::SetItems(const LabelRows &items, const std::vector<const uint16_t *> &emb) {
+    if (!h_) throw std::invalid_argument("model is not fitted");
+    if (emb.size() != fields.size()) throw std::invalid_argument("one embedding table per field of the fitted model");
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> idx, lead;
+    std::vector<float> val;
+    encode_rows(items, ptr, idx, val, lead);
+    check(gorse_fm_set_items(h_, items.Count(), ptr.data(), idx.data(), val.data(), lead.data(), emb.empty() ? nullptr : emb.data()));
+}
+
+std::vector<std::vector<Ranked>> FM::RankUsers(const LabelRows &users, const std::vector<std::vector<int32_t>> &cands) {
+    if (!h_) throw std::invalid_argument("model is not fitted");
+    if ((int64_t)cands.size() != users.Count()) throw std::invalid_argument("one candidate list per user");
+    std::vector<int64_t> ptr, cptr(1, 0);
+    std::vector<int32_t> idx, lead, flat;
+    std::vector<float> val;
+    encode_rows(users, ptr, idx, val, lead);
+    for (const auto &c : cands) {
+        flat.insert(flat.end(), c.begin(), c.end());
+        cptr.push_back((int64_t)flat.size());
+    }
+    std::vector<float> scores(flat.size());
+    std::vector<int32_t> order(flat.size());
+    check(gorse_fm_rank_users(h_, users.Count(), ptr.data(), idx.data(), val.data(), lead.data(), cptr.data(), flat.data(), batchSize_,
+                              nullptr, scores.data(), order.data()));
+    std::vector<std::vector<Ranked>> out(cands.size());
+    for (size_t t = 0; t < cands.size(); t++) {
+        const size_t c0 = (size_t)cptr[t];
+        for (size_t r = 0; r < cands[t].size(); r++) {
+            const size_t p = c0 + (size_t)order[c0 + r];
+            out[t].push_back({flat[p], scores[p]});
+        }
+    }
+    return out;
+}
+
 void FM::ReadBack() {
     check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
     for (size_t k = 0; k < fields.size(); k++) {

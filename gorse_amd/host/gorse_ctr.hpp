@@ -38,6 +38,22 @@ float Recall(const std::vector<float> &pos, const std::vector<float> &neg);
 float Accuracy(const std::vector<float> &pos, const std::vector<float> &neg);
 float AUC(std::vector<float> pos, std::vector<float> neg);
 
+// One side of a ranking call as label rows, the form BatchPredict receives it in (fm.go:180-206): row i is the entity's own
+// feature index (negative: the index does not know it, dataset.NotId) and its labels as (feature index, value), a negative
+// index again meaning a label the index does not know.  Values reach this struct scaled.
+struct LabelRows {
+    std::vector<int32_t> id;
+    std::vector<int64_t> indptr{0};
+    std::vector<int32_t> label;
+    std::vector<float> value;
+    int64_t Count() const { return (int64_t)id.size(); }
+};
+
+struct Ranked {
+    int32_t item;  // catalogue row
+    float score;
+};
+
 struct FitConfig {
     int Verbose = 10, Patience = 0;
     const volatile int32_t *cancel = nullptr;  // ctx.Err() != nil
@@ -61,6 +77,12 @@ class FM {
     Score Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg);
     // BatchInternalPredict (fm.go:156-178) of rows [0, ds.Count()) that satisfy keep (or all rows)
     std::vector<float> BatchInternalPredict(const Dataset &ds, const std::vector<int64_t> &rows);
+    // The bulk form of the worker's rankByClickTroughRate (worker/pipeline.go:451-499).  SetItems encodes the catalogue as
+    // BatchPredict would (the id entry when known, then the known labels) and makes it resident on the device with one
+    // n_items x D bf16 table per field (emb; empty for a model without fields); RankUsers encodes the users the same way and
+    // returns, per user, its candidates (catalogue rows) sorted as gorse_fm_rank_users orders them, with their scores.
+    void SetItems(const LabelRows &items, const std::vector<const uint16_t *> &emb);
+    std::vector<std::vector<Ranked>> RankUsers(const LabelRows &users, const std::vector<std::vector<int32_t>> &cands);
     float B = 0;
     std::vector<float> W, V;          // the parameters after Fit (copied back, as into the nn tensors)
     struct Field {                    // one embedding field's tensors in Parameters() order (fm.go:136-146)

@@ -1091,4 +1091,33 @@ void gh_fm_params(void *m, float *B, float *W, float *V) {
     std::copy(f->W.begin(), f->W.end(), W);
     std::copy(f->V.begin(), f->V.end(), V);
 }
+static ctr::LabelRows label_rows(int64_t n, const int32_t *id, const int64_t *indptr, const int32_t *label, const float *value) {
+    ctr::LabelRows r;
+    r.id.assign(id, id + n);
+    r.indptr.assign(indptr, indptr + n + 1);
+    r.label.assign(label, label + indptr[n]);
+    r.value.assign(value, value + indptr[n]);
+    return r;
+}
+// ctr::FM::SetItems: n label rows (id[i] < 0 / label < 0: unknown to the index) and one n x D bf16 table per field of the model
+int32_t gh_ctr_fm_set_items(void *m, int64_t n, const int32_t *id, const int64_t *indptr, const int32_t *label, const float *value,
+                            int32_t n_fields, const uint16_t *const *emb) {
+    return guard([&] {
+        ((ctr::FM *)m)->SetItems(label_rows(n, id, indptr, label, value), std::vector<const uint16_t *>(emb, emb + n_fields));
+    });
+}
+// ctr::FM::RankUsers: items_out / scores_out in cand's layout, every user's list sorted
+int32_t gh_ctr_fm_rank_users(void *m, int64_t n, const int32_t *id, const int64_t *indptr, const int32_t *label, const float *value,
+                             const int64_t *cand_indptr, const int32_t *cand, int32_t *items_out, float *scores_out) {
+    return guard([&] {
+        std::vector<std::vector<int32_t>> cands((size_t)n);
+        for (int64_t t = 0; t < n; t++) cands[(size_t)t].assign(cand + cand_indptr[t], cand + cand_indptr[t + 1]);
+        const auto ranked = ((ctr::FM *)m)->RankUsers(label_rows(n, id, indptr, label, value), cands);
+        for (int64_t t = 0; t < n; t++)
+            for (size_t r = 0; r < ranked[(size_t)t].size(); r++) {
+                items_out[cand_indptr[t] + (int64_t)r] = ranked[(size_t)t][r].item;
+                scores_out[cand_indptr[t] + (int64_t)r] = ranked[(size_t)t][r].score;
+            }
+    });
+}
 }  // extern "C"

@@ -476,6 +476,55 @@ int32_t gorse_fm_predict_embeddings(gorse_fm *h, int64_t n, int32_t width, const
                                     const float *values /*host*/, const uint16_t *const *emb /*host, n_fields pointers*/,
                                     int32_t batch_size, float *logits_out /*host*/);
 
+/* ---- ranking candidates by CTR from a resident item catalogue ---------------------------------------------------------------
+ * The bulk form of the worker's per-user loop (worker/pipeline.go:451-499, rankByClickTroughRate): BatchPredict
+ * (model/ctr/fm.go:180-229) builds one row per candidate, [user id, item id, user labels..., item labels...] plus the item's
+ * embeddings, scores the rows in slices of batch_size, and cache.SortDocuments orders them.  Here the item side stays on the
+ * device, the rows are composed there, many users are scored per launch and every user's list is sorted on the device.
+ *
+ * gorse_fm_set_items makes the item side resident.  Catalogue row i = indices / values [indptr[i], indptr[i + 1]): the item's
+ * feature entries in the order BatchPredict appends them (the item-id entry first when the index knows the item, then the item
+ * labels), values already scaled.  lead[i] = how many of its leading entries precede the user's labels in a composed row (0 or 1
+ * in practice, any 0..len allowed; lead == NULL: 0 for every item).  emb[k] = field k's n_items x D_k bf16 matrix, an all-zero
+ * row where the item has no embedding (convertToTensors, fm.go:555-561); emb may be NULL on a handle without fields.  The tables
+ * stay on the device as bf16 and are indexed with 64-bit offsets.  n_items = 0 drops the catalogue, and so does
+ * gorse_fm_set_embedding_dims (the field set changed); set_params, set_embedding_params, set_train and epoch leave it alone.
+ * indptr[0] != 0, a decreasing indptr or lead[i] beyond row i: GORSE_ERR_INVALID; an index outside [0, n_features):
+ * GORSE_ERR_RANGE; a catalogue that does not fit the device: GORSE_ERR_NOMEM.  Everything is validated before anything is
+ * replaced: an error leaves the previous catalogue in place. */
+int32_t gorse_fm_set_items(gorse_fm *h, int64_t n_items, const int64_t *indptr /*host, n_items+1*/, const int32_t *indices /*host*/,
+                           const float *values /*host*/, const int32_t *lead /*host, n_items, or NULL*/,
+                           const uint16_t *const *emb /*host, n_fields pointers, or NULL without fields*/);
+/* Scores and ranks the candidates of n_users users.  User t's feature row = user_indices / user_values [user_indptr[t],
+ * user_indptr[t + 1]) (user-id entry first when known, then the user labels; user_lead as lead above), its candidates = the
+ * catalogue rows cand[cand_indptr[t] .. cand_indptr[t + 1]) (both pointers start at 0; a list may be empty, repeat an item and
+ * share items with other users).  The composed row of candidate c of user t is, in this order (fm.go:183-206): the first
+ * user_lead[t] entries of the user's row, the first lead[c] entries of the item's row, the rest of the user's row, the rest of
+ * the item's row; entries with value 0 are skipped as the forward kernel skips them, so there is no width.  Its embedding in
+ * field k is row c of table k.
+ * scores_out[cand_indptr[t] + r] holds the BITS gorse_fm_predict_embeddings (without fields: gorse_fm_predict) returns for row r
+ * when called on user t's materialised rows alone with the same batch_size: the same fused-multiply-add chains in the same
+ * order, slices of batch_size rows per user with the reference's Softmax indexing inside each slice, a user's last slice
+ * partial, and no slice shared between users.
+ * order_out[cand_indptr[t] + r] = the position inside user t's list of its r-th ranked candidate: descending score; equal
+ * scores (as floats, -0 == +0) by ascending position; NaN scores last, by ascending position.  cache.SortDocuments is
+ * sort.Slice(score >) (storage/cache/database.go:190-194), which is not stable: this order is one it can produce, and no
+ * reference test pins an order among ties.
+ * Either output may be NULL.  No catalogue, batch_size <= 0, a malformed pointer array or user_lead[t] beyond the row:
+ * GORSE_ERR_INVALID (also more than 2^31 - 1 candidates in one call); a candidate outside [0, n_items) or a user index outside
+ * [0, n_features): GORSE_ERR_RANGE.  Everything is validated before the first launch and an error leaves the outputs untouched.
+ * The cancel flag is read between launch rounds: GORSE_ERR_CANCELLED, outputs unspecified.  Parameters, optimizer state,
+ * training set and training plan are untouched. */
+int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64_t *user_indptr /*host, n_users+1*/,
+                            const int32_t *user_indices /*host*/, const float *user_values /*host*/,
+                            const int32_t *user_lead /*host, n_users, or NULL*/, const int64_t *cand_indptr /*host, n_users+1*/,
+                            const int32_t *cand /*host*/, int32_t batch_size, const volatile int32_t *cancel /*host or NULL*/,
+                            float *scores_out /*host or NULL*/, int32_t *order_out /*host or NULL*/);
+/* the handle's last gorse_fm_rank_users: rows scored, slices, launch rounds, lists longer than the device sort's cap (sorted by
+ * the host with the same comparator), and the device time of its launches (hipEvents on the handle's stream, copies excluded).
+ * Any pointer may be NULL. */
+int32_t gorse_fm_rank_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, int64_t *host_sorted, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,14 @@ int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items /*host*/, int32
  * k + 2 where smaller, the smallest that can hold k + 1 entries and one more: a compaction per survivor; 0 = max(32, 2 (k + 1)));
  * literal_chunk > 0 = candidates materialised per launch of the literal path at most (0 = 2^22).  Results never depend on them. */
 void gorse_hip_test_set_recommend(int32_t slices, int32_t buffer, int64_t literal_chunk);
+/* gorse_fm_rank_users (csrc/fm_rank.hip), calls AFTERWARDS: round_rows > 0 = rows of a launch round at most (raised to the call's
+ * batch_size where smaller: a slice is never split; 0 = by the scratch budget); sort_cap > 0 = entries of the longest list the
+ * device sorts (at most 4096, the default; longer lists are sorted by the host).  Results never depend on them. */
+void gorse_hip_test_set_fm_rank(int64_t round_rows, int32_t sort_cap);
+/* the ranking step of gorse_fm_rank_users alone, on scores the caller supplies (any bit patterns: signed zeros, NaNs of either
+ * sign and any payload, infinities): order_out as that call defines it, lists beyond the cap by the host */
+int32_t gorse_hip_test_fm_rank_sort(gorse_fm *h, int64_t n_users, const int64_t *cand_indptr /*host, n_users+1*/,
+                                    const float *scores /*host*/, int32_t *order_out /*host*/);
 
 #ifdef __cplusplus
 }

@@ -251,3 +251,166 @@ func (fm *AFM) batchPredictHIP(x []lo.Tuple2[[]int32, []float32], e [][][]uint16
 	}
 	return out, true
 }
+
+// RankItem is one catalogue entry of setItemsHIP as BatchPredict would encode it (fm.go:189-206): the item-id entry first when the
+// index knows the item, then the item labels it knows, values already scaled; Embeddings[k] is field k's vector or nil.
+type RankItem struct {
+	Indices    []int32
+	Values     []float32
+	Lead       int32 // 1 when the item-id entry is there, else 0
+	Embeddings [][]uint16
+}
+
+// EncodeRankItem / EncodeRankUser do BatchPredict's encoding (fm.go:183-206) for one side; the scalers are applied here, as
+// BatchInternalPredict applies them (fm.go:160-165), because values reach the library scaled.
+func (fm *AFM) EncodeRankItem(itemId string, labels []Label, embeddings []Embedding) RankItem {
+	var x lo.Tuple2[[]int32, []float32]
+	item := RankItem{Embeddings: make([][]uint16, len(fm.embeddingDim))}
+	if itemIndex := fm.Index.EncodeItem(itemId); itemIndex != dataset.NotId {
+		x.A, x.B = append(x.A, itemIndex), append(x.B, 1)
+		item.Lead = 1
+	}
+	for _, f := range labels {
+		if index := fm.Index.EncodeItemLabel(f.Name); index != dataset.NotId {
+			x.A, x.B = append(x.A, index), append(x.B, f.Value)
+		}
+	}
+	if fm.autoScale {
+		x = fm.applyScalers([]lo.Tuple2[[]int32, []float32]{x})[0]
+	}
+	item.Indices, item.Values = x.A, x.B
+	if fm.embeddingIndex != nil {
+		for _, embedding := range embeddings {
+			k := fm.embeddingIndex.ToNumber(embedding.Name)
+			if k == dataset.NotId || len(embedding.Value) != fm.embeddingDim[int(k)] {
+				continue // unknown embedding or dimension mismatch (fm.go:216-224)
+			}
+			item.Embeddings[int(k)] = embedding.Value
+		}
+	}
+	return item
+}
+
+func (fm *AFM) EncodeRankUser(userId string, labels []Label) (indices []int32, values []float32, lead int32) {
+	var x lo.Tuple2[[]int32, []float32]
+	if userIndex := fm.Index.EncodeUser(userId); userIndex != dataset.NotId {
+		x.A, x.B = append(x.A, userIndex), append(x.B, 1)
+		lead = 1
+	}
+	for _, f := range labels {
+		if index := fm.Index.EncodeUserLabel(f.Name); index != dataset.NotId {
+			x.A, x.B = append(x.A, index), append(x.B, f.Value)
+		}
+	}
+	if fm.autoScale {
+		x = fm.applyScalers([]lo.Tuple2[[]int32, []float32]{x})[0]
+	}
+	return x.A, x.B, lead
+}
+
+// setItemsHIP makes the catalogue resident on the device (gorse_fm_set_items); ok = false when no model is resident or the
+// library refuses the catalogue (it then keeps the previous one).
+func (fm *AFM) setItemsHIP(items []RankItem) bool {
+	if fm.hip == nil || fm.hip.h == nil {
+		return false
+	}
+	n := len(items)
+	indptr := make([]int64, n+1)
+	lead := make([]int32, max(n, 1))
+	var idx []int32
+	var val []float32
+	for i, item := range items {
+		idx = append(idx, item.Indices...)
+		val = append(val, item.Values...)
+		indptr[i+1] = int64(len(idx))
+		lead[i] = item.Lead
+	}
+	if len(idx) == 0 {
+		idx, val = []int32{0}, []float32{0}
+	}
+	var embPtr **C.uint16_t
+	if len(fm.embeddingDim) > 0 && n > 0 {
+		// the tables live in C memory for the call: a Go pointer to Go pointers must not cross cgo
+		ptrs := (*[C.GORSE_FM_MAX_FIELDS]*C.uint16_t)(C.malloc(C.size_t(C.GORSE_FM_MAX_FIELDS) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+		defer C.free(unsafe.Pointer(ptrs))
+		for k, dim := range fm.embeddingDim {
+			table := make([]uint16, n*dim) // an all-zero row where the item has no embedding (fm.go:555-561)
+			for i, item := range items {
+				if len(item.Embeddings) > k && len(item.Embeddings[k]) == dim {
+					copy(table[i*dim:], item.Embeddings[k])
+				}
+			}
+			ptrs[k] = (*C.uint16_t)(C.CBytes(unsafe.Slice((*byte)(unsafe.Pointer(&table[0])), 2*len(table))))
+			defer C.free(unsafe.Pointer(ptrs[k]))
+		}
+		embPtr = &ptrs[0]
+	}
+	rc := C.gorse_fm_set_items(fm.hip.h, C.int64_t(n), (*C.int64_t)(&indptr[0]), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		(*C.int32_t)(&lead[0]), embPtr)
+	return rc == 0
+}
+
+// RankUser is one user of rankUsersHIP: its encoded row and its candidates as catalogue rows.
+type RankUser struct {
+	Indices    []int32
+	Values     []float32
+	Lead       int32
+	Candidates []int32
+}
+
+// rankUsersHIP scores and ranks every user's candidates in one gorse_fm_rank_users call.  scores[t][r] belongs to
+// users[t].Candidates[r]; order[t] lists the positions of user t's candidates best first: descending score, equal scores by
+// position, NaN last -- one of the orders sort.Slice(score >) of cache.SortDocuments can produce (it is not stable).
+func (fm *AFM) rankUsersHIP(ctx context.Context, users []RankUser) (scores [][]float32, order [][]int32, ok bool) {
+	if fm.hip == nil || fm.hip.h == nil || len(users) == 0 {
+		return nil, nil, false
+	}
+	n := len(users)
+	uptr, cptr := make([]int64, n+1), make([]int64, n+1)
+	lead := make([]int32, n)
+	var idx, cand []int32
+	var val []float32
+	for t, u := range users {
+		idx = append(idx, u.Indices...)
+		val = append(val, u.Values...)
+		cand = append(cand, u.Candidates...)
+		uptr[t+1], cptr[t+1] = int64(len(idx)), int64(len(cand))
+		lead[t] = u.Lead
+	}
+	if len(cand) == 0 {
+		return make([][]float32, n), make([][]int32, n), true
+	}
+	if len(idx) == 0 {
+		idx, val = []int32{0}, []float32{0}
+	}
+	flatScores, flatOrder := make([]float32, len(cand)), make([]int32, len(cand))
+	cancel := (*C.int32_t)(C.calloc(1, 4)) // C memory: the watcher writes it while the call runs
+	defer C.free(unsafe.Pointer(cancel))
+	done := make(chan struct{})
+	defer close(done)
+	go func() {
+		select {
+		case <-ctx.Done():
+			atomic.StoreInt32((*int32)(unsafe.Pointer(cancel)), 1)
+		case <-done:
+		}
+	}()
+	rc := C.gorse_fm_rank_users(fm.hip.h, C.int64_t(n), (*C.int64_t)(&uptr[0]), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		(*C.int32_t)(&lead[0]), (*C.int64_t)(&cptr[0]), (*C.int32_t)(&cand[0]), C.int32_t(fm.batchSize), cancel,
+		(*C.float)(&flatScores[0]), (*C.int32_t)(&flatOrder[0]))
+	if rc != 0 {
+		return nil, nil, false
+	}
+	scores, order = make([][]float32, n), make([][]int32, n)
+	for t := range users {
+		scores[t], order[t] = flatScores[cptr[t]:cptr[t+1]], flatOrder[cptr[t]:cptr[t+1]]
+	}
+	return scores, order, true
+}
+
+// SetRankItems / RankUsers are what the worker calls (worker/pipeline_hip.go).
+func (fm *AFM) SetRankItems(items []RankItem) bool { return fm.setItemsHIP(items) }
+
+func (fm *AFM) RankUsers(ctx context.Context, users []RankUser) ([][]float32, [][]int32, bool) {
+	return fm.rankUsersHIP(ctx, users)
+}

@@ -22,3 +22,30 @@ func (fm *AFM) fitHIP(context.Context, dataset.CTRSplit, dataset.CTRSplit, *FitC
 func (fm *AFM) batchPredictHIP([]lo.Tuple2[[]int32, []float32], [][][]uint16) ([]float32, bool) {
 	return nil, false
 }
+
+// Without the library there is no resident catalogue: the worker ranks user by user through BatchPredict.
+type RankItem struct {
+	Indices    []int32
+	Values     []float32
+	Lead       int32
+	Embeddings [][]uint16
+}
+
+type RankUser struct {
+	Indices    []int32
+	Values     []float32
+	Lead       int32
+	Candidates []int32
+}
+
+func (fm *AFM) setItemsHIP([]RankItem) bool { return false }
+
+func (fm *AFM) rankUsersHIP(context.Context, []RankUser) ([][]float32, [][]int32, bool) {
+	return nil, nil, false
+}
+
+func (fm *AFM) SetRankItems(items []RankItem) bool { return fm.setItemsHIP(items) }
+
+func (fm *AFM) RankUsers(ctx context.Context, users []RankUser) ([][]float32, [][]int32, bool) {
+	return fm.rankUsersHIP(ctx, users)
+}

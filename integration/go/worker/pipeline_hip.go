@@ -13,6 +13,8 @@ import (
 
 	mapset "github.com/deckarep/golang-set/v2"
 	"github.com/gorse-io/gorse/common/log"
+	"github.com/gorse-io/gorse/model/ctr"
+	"github.com/gorse-io/gorse/storage/data"
 	"github.com/gorse-io/gorse/storage/cache"
 	"github.com/gorse-io/gorse/storage/vectors"
 	"github.com/pkg/errors"
@@ -122,4 +124,80 @@ func (p *Pipeline) updateCollaborativeRecommendUnseen(ctx context.Context, matri
 		}
 	}
 	return nil
+}
+
+// ctrRanker is what model/ctr/fm_hip.go offers beyond ctr.FactorizationMachines: a resident item catalogue and one ranking call
+// for a block of users (gorse_fm_set_items / gorse_fm_rank_users).
+type ctrRanker interface {
+	EncodeRankItem(itemId string, labels []ctr.Label, embeddings []ctr.Embedding) ctr.RankItem
+	EncodeRankUser(userId string, labels []ctr.Label) ([]int32, []float32, int32)
+	SetRankItems(items []ctr.RankItem) bool
+	RankUsers(ctx context.Context, users []ctr.RankUser) ([][]float32, [][]int32, bool)
+}
+
+// rankCatalogue is the item cache encoded once per model and item-cache generation: the rows of the resident catalogue and
+// each item's row number.
+type rankCatalogue struct {
+	row   map[string]int32
+	items []data.Item
+}
+
+// encodeRankCatalogue encodes every item of the cache the way BatchPredict would and makes the result resident.  Label
+// encoding and the scalers run here, in Go; the library sees indices and scaled values only.
+func (p *Pipeline) encodeRankCatalogue(ranker ctrRanker, items []data.Item) (*rankCatalogue, bool) {
+	catalogue := &rankCatalogue{row: make(map[string]int32, len(items)), items: items}
+	encoded := make([]ctr.RankItem, len(items))
+	for i := range items {
+		catalogue.row[items[i].ItemId] = int32(i)
+		encoded[i] = ranker.EncodeRankItem(items[i].ItemId, ctr.ConvertLabels(items[i].Labels), ctr.ConvertEmbeddings(items[i].Labels))
+	}
+	if !ranker.SetRankItems(encoded) {
+		return nil, false
+	}
+	return catalogue, true
+}
+
+// rankByClickThroughRateBulk is rankByClickTroughRate (worker/pipeline.go:451-499) for a block of users: one call scores and
+// ranks all their candidates against the resident catalogue.  ok = false sends the caller to the per-user path for the whole
+// block: no resident model (the predictor is not a ctrRanker, or Fit did not run in this process), a candidate that is not in
+// the catalogue (the item cache moved on: encode it again), or an error from the library.  Replacement candidates and the
+// decay of read items stay in Go around this call, exactly as around the per-user one.
+// Ties: the library orders equal scores by candidate position and puts NaN scores last; cache.SortDocuments is
+// sort.Slice(score >), which is not stable, so this is one of the orders it can produce.
+func (p *Pipeline) rankByClickThroughRateBulk(ctx context.Context, predictor ctr.FactorizationMachines, catalogue *rankCatalogue,
+	users []*data.User, candidates [][]cache.Score, recommendTime time.Time) (ranked [][]cache.Score, ok bool) {
+	ranker, isRanker := predictor.(ctrRanker)
+	if !isRanker || catalogue == nil || len(users) != len(candidates) {
+		return nil, false
+	}
+	block := make([]ctr.RankUser, len(users))
+	for t, user := range users {
+		indices, values, lead := ranker.EncodeRankUser(user.UserId, ctr.ConvertLabels(user.Labels))
+		block[t] = ctr.RankUser{Indices: indices, Values: values, Lead: lead, Candidates: make([]int32, len(candidates[t]))}
+		for r, candidate := range candidates[t] {
+			row, found := catalogue.row[candidate.Id]
+			if !found {
+				return nil, false
+			}
+			block[t].Candidates[r] = row
+		}
+	}
+	scores, order, done := ranker.RankUsers(ctx, block)
+	if !done {
+		return nil, false
+	}
+	ranked = make([][]cache.Score, len(users))
+	for t := range users {
+		ranked[t] = make([]cache.Score, 0, len(order[t]))
+		for _, position := range order[t] {
+			item := &catalogue.items[block[t].Candidates[position]]
+			ranked[t] = append(ranked[t], cache.Score{
+				Id:         item.ItemId,
+				Score:      float64(scores[t][position]),
+				Categories: item.Categories,
+				Timestamp:  recommendTime,
+			})
+		}
+	}
+	return ranked, true
 }
