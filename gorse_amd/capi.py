@@ -158,6 +158,8 @@ SIGNATURES = {
     "gorse_hip_test_set_als_plan": (None, [C.c_int32, C.c_int32]),
     "gorse_hip_test_set_bpr_chunk": (None, [C.c_int64]),
     "gorse_hip_test_bpr_prepare_chunk": (C.c_int32, [_vp, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, _i32p, _i32p, _i32p]),
+    "gorse_hip_test_bpr_finish_capacities": (None, [_i32p, _i32p]),
+    "gorse_hip_test_bpr_fail_count": (C.c_int32, [_vp, _i32p]),
     "gorse_hip_test_set_bpr_store_mode": (None, [C.c_int32]),
     "gorse_hip_test_set_prep_cu_stride": (None, [C.c_int32]),
     "gorse_hip_test_set_sgemm_valu": (None, [C.c_int32]),
@@ -354,6 +356,12 @@ class MF:
         check(lib().gorse_hip_test_bpr_prepare_chunk(self.h, n, seed, epoch, sample_base, _p(off, _i32p), _p(si, _i32p),
                                                      _p(sj, _i32p)))
         return off, si, sj
+
+    def bpr_fail_count(self):
+        """test hook: samples the BPR samplers of this handle have given up on so far"""
+        n = C.c_int32(0)
+        check(lib().gorse_hip_test_bpr_fail_count(self.h, C.byref(n)))
+        return n.value
 
     def bpr_apply_triplets(self, u, i, j, lr, reg, mode):
         u, i, j = _arr(u, np.int32), _arr(i, np.int32), _arr(j, np.int32)

@@ -281,10 +281,12 @@ __global__ __launch_bounds__(256) void bpr_sample_items_batch_kernel(int32_t U, 
 //   bpr_bin_scatter_kernel : scans the bin totals (every workgroup for itself: < 8192 bins), adds its row of the matrix = its tile's
 //                            place in every bin, and writes (sample id, user) there -- runs of a tile's samples of one bin, written
 //                            by ONE workgroup, merge in its L2;
-//   bpr_bin_sort_kernel    : a workgroup per bin counts the bin's samples per user in LDS, scans, writes the run offsets of its users
-//                            (bucket[] as the update kernel reads it) and places (sample id, user) at the sorted positions -- stores
-//                            inside the bin's own window;
-//   bpr_sample_items_kernel: unchanged.
+//   bpr_bin_finish_kernel  : a workgroup per bin does the rest in LDS -- the bin's pairs by user, the run offsets (bucket[] as the
+//                            update kernel reads it), the item draws, equal positives of a run next to each other -- and writes
+//                            (i, j) once: the form of the shapes whose bins fit it and whose rows sit in the L2s (S-ml1m);
+//   bpr_bin_sort_kernel, bpr_sample_items[_batch]_kernel, bpr_group_positives_kernel: the same three steps through global memory,
+//                            a launch each -- every other shape on the binned route (C3 shapes, the 10M-user set).
+// See launch_prepare_users for which chunk takes which.
 // The order of the samples inside a run is the order of arrival as before (no order is promised: the runs are multisets).
 constexpr int kBinThreads = 512;     // workgroup of the count / scatter kernels
 constexpr int kBinBatch = 8;         // samples of a thread whose loads are in flight together (scatter / sort kernels)
@@ -368,15 +370,27 @@ __global__ __launch_bounds__(kBinThreads) void bpr_bin_count_kernel(int32_t U, c
 // of the binned preparation reserved a tile's share of a bin with a returning atomic on the bin's cursor: a few hundred tiles on
 // one address take ~0.4 us each, one after the other -- 88 us at S-ml1m, the whole gain.  r05_zd_bpr_serial_*.txt)
 constexpr int kOffWaves = 16;
+constexpr int kOffKeep = 16;  // tiles of a thread whose counts stay in registers
 __global__ __launch_bounds__(kOffWaves * 64) void bpr_bin_offsets_kernel(int32_t *__restrict__ H, int tiles, int nbins,
                                                                          int32_t *__restrict__ bin_count) {
     __shared__ int32_t seg[kOffWaves][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + lane;
     const int per = (tiles + kOffWaves - 1) / kOffWaves, t0 = w * per, t1 = t0 + per < tiles ? t0 + per : tiles;
+    // a share of at most kOffKeep tiles (S-ml1m: 243 tiles, 16 a thread) stays in registers between the two passes: one read of
+    // the matrix, its loads in flight together
+    const bool keep = per <= kOffKeep;
+    int32_t held[kOffKeep];
     int32_t sum = 0;
-    if (b < nbins)
+    if (keep) {
+#pragma unroll
+        for (int e = 0; e < kOffKeep; e++) {
+            held[e] = b < nbins && t0 + e < t1 ? H[(int64_t)(t0 + e) * nbins + b] : 0;
+            sum += held[e];
+        }
+    } else if (b < nbins) {
         for (int t = t0; t < t1; t++) sum += H[(int64_t)t * nbins + b];
+    }
     seg[w][lane] = sum;
     __syncthreads();
     int32_t run = 0, total = 0;
@@ -387,10 +401,18 @@ __global__ __launch_bounds__(kOffWaves * 64) void bpr_bin_offsets_kernel(int32_t
         total += v;
     }
     if (b < nbins) {
-        for (int t = t0; t < t1; t++) {
-            const int32_t v = H[(int64_t)t * nbins + b];
-            H[(int64_t)t * nbins + b] = run;
-            run += v;
+        if (keep) {
+#pragma unroll
+            for (int e = 0; e < kOffKeep; e++) {
+                if (t0 + e < t1) H[(int64_t)(t0 + e) * nbins + b] = run;
+                run += held[e];
+            }
+        } else {
+            for (int t = t0; t < t1; t++) {
+                const int32_t v = H[(int64_t)t * nbins + b];
+                H[(int64_t)t * nbins + b] = run;
+                run += v;
+            }
         }
         if (w == 0) bin_count[b] = total;
     }
@@ -443,65 +465,70 @@ __global__ __launch_bounds__(kBinThreads) void bpr_bin_scatter_kernel(int32_t U,
     }
 }
 
+// one bin: cnt[0 .. ub) <- where the runs of its users end (relative to b0), bucket[] <- where they begin, pairs[] <- the bin's
+// (sample id, user) in run order.  The body of bpr_bin_sort_kernel, and of a workgroup of bpr_bin_finish_kernel that meets a bin
+// larger than its LDS holds.
+template <int NT>
+__device__ __forceinline__ void bin_sort_body(int32_t U, int ub, int32_t ulo, int32_t b0, int32_t b1, const int2 *__restrict__ bp,
+                                              int32_t *__restrict__ bucket, int2 *__restrict__ pairs, int32_t *cnt, int32_t *wsum) {
+    for (int k = threadIdx.x; k < ub; k += NT) cnt[k] = 0;
+    __syncthreads();
+    for (int32_t eb = b0 + threadIdx.x; eb < b1; eb += kBinBatch * NT) {
+        int32_t u[kBinBatch];
+#pragma unroll
+        for (int e = 0; e < kBinBatch; e++) u[e] = eb + e * NT < b1 ? bp[eb + e * NT].y : 0;
+#pragma unroll
+        for (int e = 0; e < kBinBatch; e++)
+            if (eb + e * NT < b1) atomicAdd(&cnt[(u[e] < 0 ? U : u[e]) - ulo], 1);
+    }
+    __syncthreads();
+    // exclusive scan of cnt[0 .. ub): eight counters per thread and round
+    int32_t carry = 0;
+    for (int k0 = 0; k0 < ub; k0 += 8 * NT) {
+        int32_t c[8], v = 0;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const int k = k0 + threadIdx.x * 8 + e;
+            c[e] = k < ub ? cnt[k] : 0;
+            v += c[e];
+        }
+        int32_t total;
+        int32_t run = carry + block_exclusive_scan<NT / 64>(v, wsum, &total);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const int k = k0 + threadIdx.x * 8 + e;
+            if (k < ub) {
+                cnt[k] = run;
+                if (ulo + k <= U) bucket[ulo + k] = b0 + run;
+                if (ulo + k == U) bucket[U + 1] = b1;
+            }
+            run += c[e];
+        }
+        carry += total;
+    }
+    __syncthreads();
+    for (int32_t eb = b0 + threadIdx.x; eb < b1; eb += kBinBatch * NT) {
+        int2 pr[kBinBatch];
+#pragma unroll
+        for (int e = 0; e < kBinBatch; e++) pr[e] = eb + e * NT < b1 ? bp[eb + e * NT] : make_int2(0, 0);
+#pragma unroll
+        for (int e = 0; e < kBinBatch; e++) {
+            if (eb + e * NT < b1) {
+                const int32_t p = b0 + atomicAdd(&cnt[(pr[e].y < 0 ? U : pr[e].y) - ulo], 1);
+                pairs[p] = pr[e];
+            }
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(256) void bpr_bin_sort_kernel(int32_t U, int shift, int nbins, const int32_t *__restrict__ bin_start,
                                                            const int2 *__restrict__ bp, int32_t *__restrict__ bucket,
                                                            int2 *__restrict__ pairs) {
     __shared__ int32_t cnt[1 << kMaxBinShift];
     __shared__ int32_t wsum[5];
-    const int ub = 1 << shift;
-    for (int b = blockIdx.x; b < nbins; b += gridDim.x) {
-        const int32_t ulo = b << shift;  // keys ulo .. ulo + ub - 1 (key U = the samples without a user, sorted last)
-        const int32_t b0 = bin_start[b], b1 = bin_start[b + 1];
-        for (int k = threadIdx.x; k < ub; k += 256) cnt[k] = 0;
-        __syncthreads();
-        for (int32_t eb = b0 + threadIdx.x; eb < b1; eb += kBinBatch * 256) {
-            int32_t u[kBinBatch];
-#pragma unroll
-            for (int e = 0; e < kBinBatch; e++) u[e] = eb + e * 256 < b1 ? bp[eb + e * 256].y : 0;
-#pragma unroll
-            for (int e = 0; e < kBinBatch; e++)
-                if (eb + e * 256 < b1) atomicAdd(&cnt[(u[e] < 0 ? U : u[e]) - ulo], 1);
-        }
-        __syncthreads();
-        // exclusive scan of cnt[0 .. ub): eight counters per thread and round
-        int32_t carry = 0;
-        for (int k0 = 0; k0 < ub; k0 += 2048) {
-            int32_t c[8], v = 0;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int k = k0 + threadIdx.x * 8 + e;
-                c[e] = k < ub ? cnt[k] : 0;
-                v += c[e];
-            }
-            int32_t total;
-            int32_t run = carry + block_exclusive_scan<4>(v, wsum, &total);
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int k = k0 + threadIdx.x * 8 + e;
-                if (k < ub) {
-                    cnt[k] = run;
-                    if (ulo + k <= U) bucket[ulo + k] = b0 + run;
-                    if (ulo + k == U) bucket[U + 1] = b1;
-                }
-                run += c[e];
-            }
-            carry += total;
-        }
-        __syncthreads();
-        for (int32_t eb = b0 + threadIdx.x; eb < b1; eb += kBinBatch * 256) {
-            int2 pr[kBinBatch];
-#pragma unroll
-            for (int e = 0; e < kBinBatch; e++) pr[e] = eb + e * 256 < b1 ? bp[eb + e * 256] : make_int2(0, 0);
-#pragma unroll
-            for (int e = 0; e < kBinBatch; e++) {
-                if (eb + e * 256 < b1) {
-                    const int32_t p = b0 + atomicAdd(&cnt[(pr[e].y < 0 ? U : pr[e].y) - ulo], 1);
-                    pairs[p] = pr[e];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    for (int b = blockIdx.x; b < nbins; b += gridDim.x)  // keys ulo .. ulo + ub - 1 (key U = the samples without a user, sorted last)
+        bin_sort_body<256>(U, 1 << shift, b << shift, bin_start[b], bin_start[b + 1], bp, bucket, pairs, cnt, wsum);
 }
 
 // ---- equal positives of a run next to each other ------------------------------------------------
@@ -542,37 +569,242 @@ __device__ __forceinline__ int2 group_unkey(uint64_t k, uint32_t salt) {
     return make_int2((int32_t)((x * kGroupMulInv) ^ salt), j);
 }
 
+// one run of 3 .. kGroupCap samples, by the NT threads of a workgroup: sorted in key[], written back in place
+template <int NT>
+__device__ __forceinline__ void group_run(uint64_t *key, int32_t beg, int32_t len, uint32_t salt, int32_t *si, int32_t *sj) {
+    const int lane = threadIdx.x;
+    int P = 4;
+    while (P < len) P <<= 1;
+    for (int k = lane; k < P; k += NT) key[k] = k < len ? group_key(si[beg + k], sj[beg + k], salt) : ~0ull;
+    __syncthreads();
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+            for (int t = lane; t < (P >> 1); t += NT) {
+                const int lo = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), hi = lo | jj;
+                const uint64_t a = key[lo], b = key[hi];
+                if ((a > b) == ((lo & kk) == 0)) key[lo] = b, key[hi] = a;
+            }
+            __syncthreads();
+        }
+    }
+    // (the padding keys equal the key of a sample without a negative and decode to the same (-1, -1): the first `len` keys
+    // are the run's samples whichever of the equal keys they are)
+    for (int k = lane; k < len; k += NT) {
+        const int2 v = group_unkey(key[k], salt);
+        si[beg + k] = v.x;
+        sj[beg + k] = v.y;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(64) void bpr_group_positives_kernel(int32_t U, const int32_t *__restrict__ off, int32_t *__restrict__ si,
                                                                  int32_t *__restrict__ sj) {
     __shared__ uint64_t key[kGroupCap];
-    const int lane = threadIdx.x;
     for (int32_t u = blockIdx.x; u < U; u += gridDim.x) {
         const int32_t beg = off[u], len = off[u + 1] - beg;
         if (len < 3 || len > kGroupCap) continue;  // (two samples are adjacent anyway)
-        int P = 4;
-        while (P < len) P <<= 1;
-        const uint32_t salt = group_salt(u);
-        for (int k = lane; k < P; k += 64) key[k] = k < len ? group_key(si[beg + k], sj[beg + k], salt) : ~0ull;
-        __syncthreads();
-        for (int kk = 2; kk <= P; kk <<= 1) {
-            for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-                for (int t = lane; t < (P >> 1); t += 64) {
-                    const int lo = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), hi = lo | jj;
-                    const uint64_t a = key[lo], b = key[hi];
-                    if ((a > b) == ((lo & kk) == 0)) key[lo] = b, key[hi] = a;
+        group_run<64>(key, beg, len, group_salt(u), si, sj);
+    }
+}
+
+// ---- the per-bin finish: sort, item draws and grouping of a bin in ONE LDS-resident pass -------------------------------------------
+// After bpr_bin_scatter_kernel every sample of a bin sits in one contiguous window of bp[], and one workgroup owns the bin.  What
+// bpr_bin_sort_kernel, bpr_sample_items_kernel and bpr_group_positives_kernel do to that window through global memory -- pairs read
+// twice and written, read again, (i, j) written, read and written again: 56 bytes per sample, three launches -- this kernel does
+// in LDS: the pairs are read once, counted per user, scanned (bucket[] as before) and placed by run in key[]; a thread per sorted
+// position replays its sample's stream exactly as bpr_sample_items_kernel does and leaves group_key(i, j, salt(u)) in place of the
+// pair; a wave per run sorts the runs of 3 .. kGroupCap samples (in place: the bitonic network whose merges all point upwards, so
+// that positions >= len act as +inf without being there) and decodes them; the window's (i, j) go out once, in whole lines.
+// 16 bytes per sample of global traffic, no global atomic (a workgroup's failed draws: one), no lone store.
+// The rows the draws look into: the bin's users are consecutive, so their rows are ONE range uptr[ulo] .. uptr[ulo + users] of
+// uidx_sorted / uidx.  Where that range has at most kFinStage entries the workgroup copies uidx_sorted's into LDS and row_contains
+// runs there (S-ml1m: 16 users, 2,630 entries on average, 5,426 at most); at half of that or less uidx's too.  Longer ranges (C3
+// shapes: 128 users, ~12,800 entries) are read from global memory as bpr_sample_items_kernel reads them.
+// Capacities: kFinCap samples (48 KB of keys) + kFinStage row entries (24 KB) + two words per user of the bin = 76 KB of LDS, two
+// workgroups per CU.  The host sends a chunk here only where n / nbins <= 3/4 kFinCap (launch_prepare_users); a bin that holds
+// more all the same (users with feedback in a narrow id range) is finished by its workgroup: sorted through global memory
+// (bin_sort_body), drawn a slice of kFinCap positions at a time, its runs grouped in global memory (group_run).
+constexpr int kFinThreads = 512;
+constexpr int kFinCap = 6144;                      // samples of a bin at most
+constexpr int kFinPer = kFinCap / kFinThreads;     // pairs a thread holds in registers between the count and the placement
+constexpr int kFinStage = 6144;                    // row entries staged at most
+constexpr int kFinShift = 9, kFinUsers = 1 << kFinShift;  // user ids per bin at most (one thread each in the scan)
+#ifndef GORSE_BPR_STAGE_ROWS
+#define GORSE_BPR_STAGE_ROWS 1  // A/B: 0 = the rows always from global memory
+#endif
+static_assert(kFinUsers <= kFinThreads && kFinCap >= kGroupCap && kFinCap % kFinThreads == 0, "geometry of bpr_bin_finish_kernel");
+
+__device__ __forceinline__ void wave_lds_sync() {  // LDS written by a wave's lanes, read by others of the SAME wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ascending sort of k[0 .. len), len <= kGroupCap, by one wave
+__device__ __forceinline__ void wave_sort_run(uint64_t *k, int len, int lane) {
+    int P = 4;
+    while (P < len) P <<= 1;
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+            for (int t = lane; t < (P >> 1); t += 64) {
+                const int lo = ((t & ~(jj - 1)) << 1) | (t & (jj - 1));
+                const int hi = jj == (kk >> 1) ? lo ^ (kk - 1) : lo | jj;  // (a merge's first step mirrors: every step sorts upwards)
+                if (hi < len) {
+                    const uint64_t a = k[lo], b = k[hi];
+                    if (a > b) k[lo] = b, k[hi] = a;
                 }
-                __syncthreads();
             }
+            wave_lds_sync();
         }
-        // (the padding keys equal the key of a sample without a negative and decode to the same (-1, -1): the first `len` keys
-        // are the run's samples whichever of the equal keys they are)
-        for (int k = lane; k < len; k += 64) {
-            const int2 v = group_unkey(key[k], salt);
-            si[beg + k] = v.x;
-            sj[beg + k] = v.y;
+    }
+}
+
+// A uniform value as a per-lane one.  Philox's ten round keys are sums of the seed's halves: of a uniform seed the compiler keeps all
+// twenty in scalar registers across the draw loops, which bpr_bin_finish_kernel does not have (it spilled sixteen); of a per-lane
+// seed they are twenty vector adds per block of four draws, next to its forty multiplies.
+__device__ __forceinline__ uint64_t lane_copy(uint64_t x) {
+    uint32_t lo, hi;
+    asm("v_mov_b32 %0, %1" : "=v"(lo) : "s"((uint32_t)x));
+    asm("v_mov_b32 %0, %1" : "=v"(hi) : "s"((uint32_t)(x >> 32)));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// the negative of a sample (model.go:462-468) from the generator behind the positive's draw; ROW: the user's sorted row, LDS or global
+template <typename ROW>
+__device__ __forceinline__ int32_t draw_negative(Philox &g, int32_t I, ROW row, int32_t cnt) {
+    for (int k = 0; k < kMaxDraws; k++) {
+        const int32_t c = g.int31n(I);
+        if (!row_contains(row, cnt, c)) return c;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(kFinThreads) void bpr_bin_finish_kernel(int32_t U, int32_t I, int shift, const int32_t *__restrict__ bin_start,
+                                                                     const int2 *__restrict__ bp, const int64_t *__restrict__ uptr,
+                                                                     const int32_t *__restrict__ uidx,
+                                                                     const int32_t *__restrict__ usorted, uint64_t seed, uint64_t epoch,
+                                                                     int64_t sample_base, int32_t *__restrict__ bucket,
+                                                                     int2 *__restrict__ pairs, int32_t *__restrict__ si,
+                                                                     int32_t *__restrict__ sj, int32_t *__restrict__ fail_count,
+                                                                     int group) {
+    __shared__ uint64_t key[kFinCap];         // (sample id, user) by run, then the group key of the sample's (i, j), then (i, j)
+    __shared__ int32_t cnt[kFinUsers + 1];    // per user of the bin: samples, then where its run begins, then where it ends
+    __shared__ int32_t rowoff[kFinUsers + 1]; // where the user's row begins in the bin's range of rows
+    __shared__ int32_t rows[kFinStage];       // uidx_sorted's entries of the range (and uidx's behind them)
+    __shared__ int32_t wsum[kFinThreads / 64 + 1];
+    __shared__ int32_t nfail;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int ub = 1 << shift;
+    const int32_t ulo = (int32_t)blockIdx.x << shift;  // keys ulo .. ulo + ub - 1 (key U = the samples without a user, sorted last)
+    const int32_t b0 = bin_start[blockIdx.x], b1 = bin_start[blockIdx.x + 1], m = b1 - b0;
+    const bool big = m > kFinCap;  // (the whole workgroup) more samples than key[] holds: see below
+    // 1. the users' rows
+    if (tid == 0) nfail = 0;
+    const int64_t rbase = uptr[ulo];  // (ulo <= U)
+    for (int k = tid; k <= ub; k += kFinThreads) {
+        const int64_t uu = (int64_t)ulo + k < U ? (int64_t)ulo + k : U;
+        rowoff[k] = (int32_t)(uptr[uu] - rbase);
+    }
+    __syncthreads();
+    const int32_t range = rowoff[ub];  // entries of the users' rows together
+    const bool staged = GORSE_BPR_STAGE_ROWS && m > 0 && range <= kFinStage, staged_idx = staged && 2 * range <= kFinStage;
+    if (staged)
+        for (int k = tid; k < range; k += kFinThreads) {
+            rows[k] = usorted[rbase + k];
+            if (staged_idx) rows[range + k] = uidx[rbase + k];
+        }
+    // 2. the samples per user -> the run offsets -> the pairs by run; every counter ends up at its run's end
+    if (big) {
+        bin_sort_body<kFinThreads>(U, ub, ulo, b0, b1, bp, bucket, pairs, cnt, wsum);  // (by run in pairs[], through global memory)
+    } else {
+        if (tid < ub) cnt[tid] = 0;
+        __syncthreads();
+        int2 pr[kFinPer];  // the bin's pairs, read once
+#pragma unroll
+        for (int e = 0; e < kFinPer; e++) {
+            const int p = tid + e * kFinThreads;
+            pr[e] = p < m ? bp[b0 + p] : make_int2(0, 0);
+            if (p < m) atomicAdd(&cnt[(pr[e].y < 0 ? U : pr[e].y) - ulo], 1);
+        }
+        __syncthreads();
+        const int32_t c = tid < ub ? cnt[tid] : 0;
+        const int32_t run = block_exclusive_scan<kFinThreads / 64>(c, wsum, nullptr);
+        if (tid < ub) {
+            cnt[tid] = run;
+            if (ulo + tid <= U) bucket[ulo + tid] = b0 + run;
+            if (ulo + tid == U) bucket[U + 1] = b1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < kFinPer; e++) {
+            if (tid + e * kFinThreads < m) {
+                const int32_t q = atomicAdd(&cnt[(pr[e].y < 0 ? U : pr[e].y) - ulo], 1);
+                key[q] = ((uint64_t)(uint32_t)pr[e].y << 32) | (uint32_t)pr[e].x;
+            }
         }
         __syncthreads();
     }
+    // (a bin within the capacity: one round)
+    for (int32_t s0 = 0; s0 < m; s0 += kFinCap) {
+        const int32_t ms = m - s0 < kFinCap ? m - s0 : kFinCap;
+        if (big) {
+            for (int p = tid; p < ms; p += kFinThreads) {
+                const int2 pr = pairs[b0 + s0 + p];
+                key[p] = ((uint64_t)(uint32_t)pr.y << 32) | (uint32_t)pr.x;
+            }
+            __syncthreads();
+        }
+        // 3. the item draws, a thread per sorted position (bpr_sample_items_kernel); the key of (i, j) takes the pair's place
+        for (int p = tid; p < ms; p += kFinThreads) {
+            const int32_t sid = (int32_t)(uint32_t)key[p], u = (int32_t)(key[p] >> 32);
+            uint64_t out = ~0ull;  // a sample without a negative: what group_key gives it, and (-1, -1)
+            if (u >= 0) {
+                const int32_t ro = rowoff[u - ulo], n_u = rowoff[u - ulo + 1] - ro;
+                Philox g;
+                // (lane_copy: without it this kernel spills scalar registers -- tests/test_bpr_bin_finish_cpu.py is what says so)
+                g.init(lane_copy(seed), epoch, (uint64_t)(sample_base + sid));
+                // the user draw again: rows drawn before u were empty (u is the first non-empty one), no look-up needed
+                for (int k = 0; k < kMaxDraws; k++)
+                    if (g.int31n(U) == u) break;
+                const int32_t r = g.int31n(n_u);
+                const int32_t pi = staged_idx ? rows[range + ro + r] : uidx[rbase + ro + r];
+                const int32_t nj = staged ? draw_negative(g, I, rows + ro, n_u) : draw_negative(g, I, usorted + rbase + ro, n_u);
+                if (nj < 0)
+                    atomicAdd(&nfail, 1);
+                else
+                    out = big ? ((uint64_t)(uint32_t)nj << 32) | (uint32_t)pi : group_key(pi, nj, group_salt(u));
+            }
+            key[p] = out;
+        }
+        __syncthreads();
+        // 4. a wave per run: equal positives next to each other (bpr_group_positives_kernel's order), then (i, j) in the key's place
+        if (!big) {
+            for (int k = wid; k < ub; k += kFinThreads / 64) {
+                const int32_t beg = k ? cnt[k - 1] : 0, len = cnt[k] - beg;
+                const uint32_t salt = group_salt(ulo + k);
+                if (group && len >= 3 && len <= kGroupCap && ulo + k < U) wave_sort_run(key + beg, len, lane);
+                for (int t = lane; t < len; t += 64) {
+                    const int2 v = group_unkey(key[beg + t], salt);
+                    key[beg + t] = ((uint64_t)(uint32_t)v.y << 32) | (uint32_t)v.x;
+                }
+            }
+            __syncthreads();
+        }
+        // 5. the window, once
+        for (int p = tid; p < ms; p += kFinThreads) {
+            si[b0 + s0 + p] = (int32_t)(uint32_t)key[p];
+            sj[b0 + s0 + p] = (int32_t)(key[p] >> 32);
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && nfail > 0) atomicAdd(fail_count, nfail);
+    // a bin over the capacity went through key[] a slice at a time, the slices' (i, j) are in global memory: its runs are grouped
+    // there, as bpr_group_positives_kernel does it, one after the other by the whole workgroup
+    if (big && group)
+        for (int k = 0; k < ub && ulo + k < U; k++) {
+            const int32_t beg = k ? cnt[k - 1] : 0, len = cnt[k] - beg;
+            if (len >= 3 && len <= kGroupCap) group_run<kFinThreads>(key, b0 + beg, len, group_salt(ulo + k), si, sj);
+        }
 }
 
 // ---- memory access flavours ------------------------------------------------------------------
@@ -1373,6 +1605,7 @@ int32_t launch_sampler(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t base,
 // holds the keys and (sample id, user) pairs; `rank` (2 x cap) the ranks or the sorted pairs; `sorted` receives si at cap, sj at
 // 2 cap; bucket[0..U + 1] the run offsets.
 // (PrepBins / prep_bins: csrc/bpr_bins.hpp, shared with the CPU cover test)
+constexpr size_t kItemsBatchFrom = (size_t)8 << 20;  // feedbacks of a handle beyond which the users' rows cannot all sit in the L2s
 int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t base, int64_t n, int32_t *trip, int32_t *sorted,
                              int32_t *bucket, int32_t *rank, size_t cap, hipStream_t st) {
     if (n <= 0) return GORSE_OK;
@@ -1381,7 +1614,7 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
     const PrepBins pb = prep_bins(h->U, n);
     // the item draws: four positions per thread where the users' rows cannot all sit in the L2s (see bpr_sample_items_batch_kernel)
     auto launch_items = [&](const int2 *pairs) {
-        if (h->uidx.n > ((size_t)8 << 20))
+        if (h->uidx.n > kItemsBatchFrom)
             bpr_sample_items_batch_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>((int32_t)h->U, (int32_t)h->I, h->uptr.p, h->uidx.p,
                                                                                         h->uidx_sorted.p, seed, epoch, base, n, pairs,
                                                                                         sorted + cap, sorted + 2 * cap, h->fail_count.p);
@@ -1412,6 +1645,22 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
         bpr_bin_offsets_kernel<<<dim3((unsigned)ceil_div(pb.nbins, 64)), dim3(kOffWaves * 64), 0, st>>>(H, (int)tiles, pb.nbins, bin_count);
         bpr_bin_scatter_kernel<<<dim3(tiles), dim3(kBinThreads), 0, st>>>((int32_t)h->U, key, n, pb.tile, pb.shift, pb.nbins, bin_count,
                                                                           H, bin_start, bp);
+        // the finish of the bins in one LDS-resident pass (bpr_bin_finish_kernel) where a bin's expected samples are safely under
+        // its capacity (the 10M-user set: ~27,500 per bin), a bin's users have a counter each, and the users' rows sit in the L2s:
+        // where they do not (C3 shapes) the item draws are bpr_sample_items_batch_kernel's, four chains of look-ups per thread, which
+        // the finish kernel does not have; variant bit 19 (tests, A/B): the three kernels whatever the shape
+        const bool finish = !(g_variant & (1 << 19)) && pb.shift <= kFinShift && n / pb.nbins <= kFinCap / 4 * 3 &&
+                            h->uidx.n <= kItemsBatchFrom;
+        if (finish) {
+            h->prof.end(tok, st);
+            tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
+            bpr_bin_finish_kernel<<<dim3((unsigned)pb.nbins), dim3(kFinThreads), 0, st>>>(
+                (int32_t)h->U, (int32_t)h->I, pb.shift, bin_start, bp, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, bucket,
+                pairs, sorted + cap, sorted + 2 * cap, h->fail_count.p, (g_variant & (1 << 20)) ? 0 : 1);
+            h->prof.end(tok, st);
+            GORSE_HIP_CHECK(hipGetLastError());
+            return GORSE_OK;
+        }
         bpr_bin_sort_kernel<<<dim3((unsigned)pb.nbins), dim3(256), 0, st>>>((int32_t)h->U, pb.shift, pb.nbins, bin_start, bp, bucket, pairs);
         h->prof.end(tok, st);
         tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
@@ -1636,6 +1885,17 @@ extern "C" int32_t gorse_mf_bpr_schedule(gorse_mf *h, int32_t *user_runs) {
 }
 extern "C" void gorse_hip_test_set_variant(int32_t v) { g_variant = v; }
 extern "C" void gorse_hip_test_set_bpr_chunk(int64_t samples) { g_chunk_override = samples; }
+extern "C" int32_t gorse_hip_test_bpr_fail_count(gorse_mf *h, int32_t *count) {
+    if (!h || !count) return fail(GORSE_ERR_INVALID, "NULL argument");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    GORSE_HIP_CHECK(hipMemcpy(count, h->fail_count.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return GORSE_OK;
+}
+extern "C" void gorse_hip_test_bpr_finish_capacities(int32_t *samples, int32_t *row_entries) {
+    if (samples) *samples = kFinCap;
+    if (row_entries) *row_entries = kFinStage;
+}
 extern "C" void gorse_hip_test_set_bpr_store_mode(int32_t store_mode) {
     // only bit 0 selects a form the library carries (cold negatives by store); the forms bits 1 and 2 asked for were removed
     g_store_mode = store_mode < 0 ? kDefaultStoreMode : (store_mode & 1);

@@ -163,6 +163,16 @@ double gorse_hip_test_sgemm_last_ms(void);
  * gorse_bpr_sample_triplets returns for the same range. */
 int32_t gorse_hip_test_bpr_prepare_chunk(gorse_mf *h, int64_t n, uint64_t seed, uint64_t epoch, int64_t sample_base,
                                          int32_t *off /*U + 2, host*/, int32_t *si /*n, host*/, int32_t *sj /*n, host*/);
+/* the binned preparation finishes a bin in one LDS-resident pass (csrc/bpr.hip bpr_bin_finish_kernel): *samples = the samples of a
+ * bin that pass holds (a larger bin goes through it a slice at a time), *row_entries = the entries of a bin's users' rows it copies
+ * into LDS at most (longer ranges are read from global memory).  Variant bit 19 of gorse_hip_test_set_variant: the three kernels
+ * that pass replaces (sort, item draws, grouping), whatever the shape.  Results never depend on either beyond the order of the
+ * samples in runs of fewer than 3 or more than 1024. */
+void gorse_hip_test_bpr_finish_capacities(int32_t *samples, int32_t *row_entries);
+/* the handle's counter of BPR samples given up on (no user with feedback or no negative within the draw limit), after its streams
+ * drain: every sampler and preparation kernel raises it once per such sample; it is never reset by them (the evaluation's negative
+ * sampler zeroes it), so a test reads it before and after. */
+int32_t gorse_hip_test_bpr_fail_count(gorse_mf *h, int32_t *count /*host*/);
 /* items expected to be touched (as a positive: their share of the feedback; as a negative: 1 / items) less than once per
  * `samples` samples are of class "cold" in handles created AFTERWARDS; 0 = no cold items (every update an atomic). */
 void gorse_hip_test_set_bpr_cold_window(int64_t samples);
