@@ -1496,8 +1496,11 @@ int open_hot(gorse_mf *h, HotRows &hot) {
     return kFolderBlocks;
 }
 
+// start / stop (may be null): events bound to the kernel's own dispatch (hipExtLaunchKernelGGL) -- its timestamps and its completion
+// signal, no marker packet on the stream (epoch_impl)
 int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *bucket, size_t cap, float lr, float reg,
-                            int exp_mode, double *loss, hipStream_t st, bool stores) {
+                            int exp_mode, double *loss, hipStream_t st, bool stores, hipEvent_t start = nullptr,
+                            hipEvent_t stop = nullptr) {
     const int d = h->d;
     int64_t blocks = ceil_div(h->U, (int64_t)kGroupsPerBlock * (d == 8 && GORSE_BPR_D8_PAIRS ? 2 : 1));  // nFactors 8: two runs per group
     const int64_t capb = 256 * 16;
@@ -1512,8 +1515,9 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     // cold items by store only in GORSE_BPR_HOGWILD_STORES and where the handle has any (n_cold) -- the atomics-only instantiation otherwise
     const bool neg_store = stores && h->n_cold > 0 && g_store_mode == 1;
 #define LAUNCH2(NC, NEG_STORE)                                                                                         \
-    bpr_update_user_kernel<(NC == 0 ? 1 : NC), NEG_STORE, NC == 0><<<grid, block, 0, st>>>(                            \
-        h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, folders, neg_rep)
+    hipExtLaunchKernelGGL((bpr_update_user_kernel<(NC == 0 ? 1 : NC), NEG_STORE, NC == 0>), grid, block, 0, st, start, stop, 0,     \
+                          h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, \
+                          folders, neg_rep)
 #define LAUNCH(NC)                                                                                                     \
     do {                                                                                                               \
         if (neg_store)                                                                                                 \
@@ -1540,7 +1544,7 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
 template <int MODE>
 int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, const int32_t *js, const int32_t *order,
                            int64_t begin, int64_t end, float lr, float reg, int exp_mode, double *loss,
-                           hipStream_t st) {
+                           hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     const int64_t n = end - begin;
     if (n <= 0) return GORSE_OK;
     const int d = h->d;
@@ -1552,8 +1556,8 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
     blocks += folders;
     dim3 grid((unsigned)blocks), block(kBlock);
 #define LAUNCH(NC, SH)                                                                                               \
-    bpr_update_kernel<NC, MODE><<<grid, block, SH, st>>>(h->P.p, h->Q.p, us, is, js, order, begin, end, d, lr, reg, \
-                                                         exp_mode, loss, hot, folders)
+    hipExtLaunchKernelGGL((bpr_update_kernel<NC, MODE>), grid, block, SH, st, start, folders > 0 ? nullptr : stop, 0, h->P.p, \
+                          h->Q.p, us, is, js, order, begin, end, d, lr, reg, exp_mode, loss, hot, folders)
     if (d == 16)
         LAUNCH(1, 0);
     else if (d == 32)
@@ -1566,9 +1570,9 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
         LAUNCH(0, (size_t)kGroupsPerBlock * 3 * d * sizeof(float));
 #undef LAUNCH
     GORSE_HIP_CHECK(hipGetLastError());
-    if (folders > 0) {  // (its folders make no last pass: worker_done)
+    if (folders > 0) {  // (its folders make no last pass: worker_done); the launch's stop event is this kernel's
         const int64_t fb = std::min<int64_t>(ceil_div((int64_t)hot.n_hot * d, 256), 512);
-        bpr_fold_kernel<<<dim3((unsigned)fb), dim3(256), 0, st>>>(hot, h->Q.p);
+        hipExtLaunchKernelGGL(bpr_fold_kernel, dim3((unsigned)fb), dim3(256), 0, st, nullptr, stop, 0, hot, h->Q.p);
         GORSE_HIP_CHECK(hipGetLastError());
     }
     return GORSE_OK;
@@ -1576,26 +1580,27 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
 
 int32_t launch_update(gorse_mf *h, int mode, const int32_t *us, const int32_t *is, const int32_t *js,
                       const int32_t *order, int64_t begin, int64_t end, float lr, float reg, int exp_mode, double *loss,
-                      hipStream_t st) {
+                      hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
     switch (mode) {
     case MODE_ATOMIC:
-        return launch_update_mode<MODE_ATOMIC>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st);
+        return launch_update_mode<MODE_ATOMIC>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st, start, stop);
     case MODE_EXACT:
-        return launch_update_mode<MODE_EXACT>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st);
+        return launch_update_mode<MODE_EXACT>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st, start, stop);
     case MODE_RACY:
-        return launch_update_mode<MODE_RACY>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st);
+        return launch_update_mode<MODE_RACY>(h, us, is, js, order, begin, end, lr, reg, exp_mode, loss, st, start, stop);
     }
     return fail(GORSE_ERR_INVALID, "unknown BPR mode %d", mode);
 }
 
 int32_t launch_sampler(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t base, int64_t n, int32_t *trip, size_t cap,
-                       hipStream_t st, int32_t *bucket = nullptr, int32_t *rank = nullptr) {
+                       hipStream_t st, int32_t *bucket = nullptr, int32_t *rank = nullptr, hipEvent_t start = nullptr,
+                       hipEvent_t stop = nullptr) {
     if (n <= 0) return GORSE_OK;
     int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 256 * 8);
     if (bucket) GORSE_HIP_CHECK(hipMemsetAsync(bucket, 0, (size_t)(h->U + 2) * sizeof(int32_t), st));
-    bpr_sample_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>((int32_t)h->U, (int32_t)h->I, h->uptr.p, h->uidx.p,
-                                                                    h->uidx_sorted.p, seed, epoch, base, n, trip,
-                                                                    trip + cap, trip + 2 * cap, h->fail_count.p, bucket, rank);
+    hipExtLaunchKernelGGL(bpr_sample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, start, stop, 0, (int32_t)h->U, (int32_t)h->I,
+                          h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, n, trip, trip + cap, trip + 2 * cap,
+                          h->fail_count.p, bucket, rank);
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
@@ -1612,24 +1617,27 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
     const int64_t m = h->U + 2;
     const int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 256 * 8);
     const PrepBins pb = prep_bins(h->U, n);
+    // the profile's spans of this chain are bound to their kernels (KernelProfile::events): a span of one kernel is that launch's start
+    // and stop event, a span of several the start of its first and the stop of its last -- no marker packet on the preparation stream
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
     // the item draws: four positions per thread where the users' rows cannot all sit in the L2s (see bpr_sample_items_batch_kernel)
     auto launch_items = [&](const int2 *pairs) {
+        h->prof.events(GORSE_PROF_BPR_SAMPLE, &ev_a, &ev_b);
         if (h->uidx.n > kItemsBatchFrom)
-            bpr_sample_items_batch_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>((int32_t)h->U, (int32_t)h->I, h->uptr.p, h->uidx.p,
-                                                                                        h->uidx_sorted.p, seed, epoch, base, n, pairs,
-                                                                                        sorted + cap, sorted + 2 * cap, h->fail_count.p);
+            hipExtLaunchKernelGGL(bpr_sample_items_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ev_a, ev_b, 0, (int32_t)h->U,
+                                  (int32_t)h->I, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, n, pairs, sorted + cap,
+                                  sorted + 2 * cap, h->fail_count.p);
         else
-            bpr_sample_items_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>((int32_t)h->U, (int32_t)h->I, h->uptr.p, h->uidx.p,
-                                                                                  h->uidx_sorted.p, seed, epoch, base, n, pairs,
-                                                                                  sorted + cap, sorted + 2 * cap, h->fail_count.p);
+            hipExtLaunchKernelGGL(bpr_sample_items_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ev_a, ev_b, 0, (int32_t)h->U,
+                                  (int32_t)h->I, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, n, pairs, sorted + cap,
+                                  sorted + 2 * cap, h->fail_count.p);
     };
     // equal positives of a run next to each other (bpr_group_positives_kernel): one wave per run, in place
     auto launch_group = [&]() {
         if (g_variant & (1 << 20)) return;  // variant bit 20 (probes, A/B): the runs stay in arrival order
-        const int tok = h->prof.begin(GORSE_PROF_BPR_SORT, st);
-        bpr_group_positives_kernel<<<dim3((unsigned)std::min<int64_t>(h->U, 256 * 16)), dim3(64), 0, st>>>(
-            (int32_t)h->U, bucket, sorted + cap, sorted + 2 * cap);
-        h->prof.end(tok, st);
+        h->prof.events(GORSE_PROF_BPR_SORT, &ev_a, &ev_b);
+        hipExtLaunchKernelGGL(bpr_group_positives_kernel, dim3((unsigned)std::min<int64_t>(h->U, 256 * 16)), dim3(64), 0, st, ev_a, ev_b, 0,
+                              (int32_t)h->U, bucket, sorted + cap, sorted + 2 * cap);
     };
     if (pb.ok && !(g_variant & (1 << 21))) {  // variant bit 21 (probes, tests): the preparation without bins
         int32_t *key = trip;
@@ -1637,35 +1645,32 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
         int32_t *bin_count = h->ubins.p, *bin_start = h->ubins.p + kMaxBins, *H = h->ubinmat.p;
         const unsigned tiles = (unsigned)ceil_div(n, pb.tile);
         if ((size_t)tiles * pb.nbins > h->ubinmat.n) return fail(GORSE_ERR_INVALID, "tile x bin matrix smaller than %u x %d", tiles, pb.nbins);
-        int tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
-        bpr_bin_count_kernel<<<dim3(tiles), dim3(kBinThreads), 0, st>>>((int32_t)h->U, h->uptr.p, seed, epoch, base, n, pb.tile, pb.shift,
-                                                                        pb.nbins, key, h->fail_count.p, H);
-        h->prof.end(tok, st);
-        tok = h->prof.begin(GORSE_PROF_BPR_SORT, st);
-        bpr_bin_offsets_kernel<<<dim3((unsigned)ceil_div(pb.nbins, 64)), dim3(kOffWaves * 64), 0, st>>>(H, (int)tiles, pb.nbins, bin_count);
-        bpr_bin_scatter_kernel<<<dim3(tiles), dim3(kBinThreads), 0, st>>>((int32_t)h->U, key, n, pb.tile, pb.shift, pb.nbins, bin_count,
-                                                                          H, bin_start, bp);
         // the finish of the bins in one LDS-resident pass (bpr_bin_finish_kernel) where a bin's expected samples are safely under
         // its capacity (the 10M-user set: ~27,500 per bin), a bin's users have a counter each, and the users' rows sit in the L2s:
         // where they do not (C3 shapes) the item draws are bpr_sample_items_batch_kernel's, four chains of look-ups per thread, which
         // the finish kernel does not have; variant bit 19 (tests, A/B): the three kernels whatever the shape
         const bool finish = !(g_variant & (1 << 19)) && pb.shift <= kFinShift && n / pb.nbins <= kFinCap / 4 * 3 &&
                             h->uidx.n <= kItemsBatchFrom;
+        h->prof.events(GORSE_PROF_BPR_SAMPLE, &ev_a, &ev_b);
+        hipExtLaunchKernelGGL(bpr_bin_count_kernel, dim3(tiles), dim3(kBinThreads), 0, st, ev_a, ev_b, 0, (int32_t)h->U, h->uptr.p, seed,
+                              epoch, base, n, pb.tile, pb.shift, pb.nbins, key, h->fail_count.p, H);
+        // the sort's span: offsets, scatter and (without the finish) the bins' sort
+        h->prof.events(GORSE_PROF_BPR_SORT, &ev_a, &ev_b);
+        hipExtLaunchKernelGGL(bpr_bin_offsets_kernel, dim3((unsigned)ceil_div(pb.nbins, 64)), dim3(kOffWaves * 64), 0, st, ev_a, nullptr, 0,
+                              H, (int)tiles, pb.nbins, bin_count);
+        hipExtLaunchKernelGGL(bpr_bin_scatter_kernel, dim3(tiles), dim3(kBinThreads), 0, st, nullptr, finish ? ev_b : nullptr, 0,
+                              (int32_t)h->U, key, n, pb.tile, pb.shift, pb.nbins, bin_count, H, bin_start, bp);
         if (finish) {
-            h->prof.end(tok, st);
-            tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
-            bpr_bin_finish_kernel<<<dim3((unsigned)pb.nbins), dim3(kFinThreads), 0, st>>>(
-                (int32_t)h->U, (int32_t)h->I, pb.shift, bin_start, bp, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, bucket,
-                pairs, sorted + cap, sorted + 2 * cap, h->fail_count.p, (g_variant & (1 << 20)) ? 0 : 1);
-            h->prof.end(tok, st);
+            h->prof.events(GORSE_PROF_BPR_SAMPLE, &ev_a, &ev_b);
+            hipExtLaunchKernelGGL(bpr_bin_finish_kernel, dim3((unsigned)pb.nbins), dim3(kFinThreads), 0, st, ev_a, ev_b, 0, (int32_t)h->U,
+                                  (int32_t)h->I, pb.shift, bin_start, bp, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, bucket,
+                                  pairs, sorted + cap, sorted + 2 * cap, h->fail_count.p, (g_variant & (1 << 20)) ? 0 : 1);
             GORSE_HIP_CHECK(hipGetLastError());
             return GORSE_OK;
         }
-        bpr_bin_sort_kernel<<<dim3((unsigned)pb.nbins), dim3(256), 0, st>>>((int32_t)h->U, pb.shift, pb.nbins, bin_start, bp, bucket, pairs);
-        h->prof.end(tok, st);
-        tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
+        hipExtLaunchKernelGGL(bpr_bin_sort_kernel, dim3((unsigned)pb.nbins), dim3(256), 0, st, nullptr, ev_b, 0, (int32_t)h->U, pb.shift,
+                              pb.nbins, bin_start, bp, bucket, pairs);
         launch_items(pairs);
-        h->prof.end(tok, st);
         launch_group();
         GORSE_HIP_CHECK(hipGetLastError());
         return GORSE_OK;
@@ -1681,9 +1686,7 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
     GORSE_TRY(exclusive_scan_i32(bucket, m, h->scan_tmp2.p, st));
     bpr_scatter_ids_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(key, rank, bucket, n, (int32_t)h->U, pairs);
     h->prof.end(tok, st);
-    tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, st);
     launch_items(pairs);
-    h->prof.end(tok, st);
     launch_group();
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
@@ -1791,8 +1794,17 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
         return GORSE_OK;
     }
     GORSE_TRY(ensure_trip(h, n_samples));
-    GORSE_TRY(mf_epoch_begin(h, chained));  // epoch pacing: the (begin, end) pair gorse_mf_epoch_throttle / _times read (csrc/mf.hip)
     double *d_loss = loss_out ? h->loss.p : nullptr;
+    // Epoch pacing: the (begin, end) pair gorse_mf_epoch_throttle / _times read (csrc/mf.hip).  Between two update kernels the update
+    // stream carries the wait on the chunk's preparation and nothing else: the epoch's end, the chunk's "consumed" event and the
+    // profile's span are the launch's own events (ev_consumed, mf_internal.hpp).  An epoch that does not begin where the one before it
+    // ended takes its begin from its first update launch (ep_begin) -- unless something else of the epoch comes first on the stream (the
+    // loss memset, the sequential schedule's sampler, the sort of variant bits 27 / 29) or the profile needs that launch's start event:
+    // then the begin is recorded where the stream reaches the epoch, as the only marker packet of the epoch.
+    const bool uruns = (mode == MODE_ATOMIC || mode == MODE_STORES) && user_runs_enabled() && user_runs_supported(h);
+    const bool sort_on_update_stream = uruns && ((g_variant & (1 << 29)) || (g_variant & (1 << 27)));
+    hipEvent_t ep_begin = nullptr, ep_end = nullptr;
+    GORSE_TRY(mf_epoch_begin(h, chained, d_loss || mode == MODE_EXACT || sort_on_update_stream || (g_variant & (1 << 22)) || h->prof.on, &ep_begin));
     if (d_loss) GORSE_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), h->stream));
     const int64_t cap = (int64_t)h->trip_cap;
     if (mode == MODE_EXACT) {
@@ -1809,7 +1821,6 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
     } else {
         // two-stream pipeline: stream2 samples (and item-sorts) chunk c+1 while stream applies chunk c; the
         // buffer parity runs on across calls so that back-to-back enqueued epochs overlap as well
-        const bool uruns = (mode == MODE_ATOMIC || mode == MODE_STORES) && user_runs_enabled() && user_runs_supported(h);
         if (uruns) GORSE_TRY(ensure_user_sort(h));
         int64_t c = 0;
         for (int64_t s0 = 0; s0 < n_samples; s0 += cap, c++) {
@@ -1823,8 +1834,8 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
             int32_t *tb = h->trip[b].p;
             // variant bit 22 (probes): the preparation on the update stream, so that a kernel timeline shows every kernel alone
             const hipStream_t prep = (g_variant & (1 << 22)) ? h->stream : h->stream2;
-            // a never-recorded event is complete: the first two chunks of a handle do not wait
-            GORSE_HIP_CHECK(hipStreamWaitEvent(prep, h->ev_consumed[b], 0));
+            // the update launch that last read this buffer (none: the first two chunks of a handle, or the streams were drained since)
+            if (h->ev_consumed[b]) GORSE_HIP_CHECK(hipStreamWaitEvent(prep, h->ev_consumed[b], 0));
             // user runs: the whole preparation of chunk c + 1 (launch_prepare_users) runs on the sampler stream under the update
             // kernel of chunk c.  Variant bit 27: the round-3 preparation (whole triplets sampled per sample, then scattered) with the sort on the
             // update stream; bit 26: the same with the sort on the sampler stream.
@@ -1834,9 +1845,12 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
                 GORSE_TRY(launch_prepare_users(h, seed, epoch, base + s0, m, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p,
                                                (size_t)cap, prep));
             } else {
-                int tok = h->prof.begin(GORSE_PROF_BPR_SAMPLE, prep);
+                // the sampler alone: its span is the launch's own; with the run counters (fused) a memset goes first and the span is recorded
+                int tok = fused ? h->prof.begin(GORSE_PROF_BPR_SAMPLE, prep) : -1;
+                hipEvent_t sa = nullptr, sb = nullptr;
+                if (!fused) h->prof.events(GORSE_PROF_BPR_SAMPLE, &sa, &sb);
                 GORSE_TRY(launch_sampler(h, seed, epoch, base + s0, m, tb, (size_t)cap, prep, fused ? h->ubucket[b].p : nullptr,
-                                         fused ? h->urank[b].p : nullptr));
+                                         fused ? h->urank[b].p : nullptr, sa, sb));
                 h->prof.end(tok, prep);
                 if (fused) {
                     tok = h->prof.begin(GORSE_PROF_BPR_SORT, prep);
@@ -1846,24 +1860,30 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
             }
             GORSE_HIP_CHECK(hipEventRecord(h->ev_sampled[b], prep));
             GORSE_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_sampled[b], 0));
-            int tok;
             if (uruns && !fused) {
-                tok = h->prof.begin(GORSE_PROF_BPR_SORT, h->stream);
+                const int tok = h->prof.begin(GORSE_PROF_BPR_SORT, h->stream);
                 GORSE_TRY(launch_user_sort(h, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p, m, (size_t)cap, h->stream, false));
                 h->prof.end(tok, h->stream);
             }
-            tok = h->prof.begin(GORSE_PROF_BPR_UPDATE, h->stream);
+            // the launch's events: start = the profile's span, or the epoch's begin (first chunk, not chained, profiling off); stop = the
+            // profile's, the epoch's end (last chunk) or a slot of the chunk ring -- whichever it is, it is the chunk's consumed event
+            hipEvent_t start = nullptr, stop = nullptr;
+            h->prof.events(GORSE_PROF_BPR_UPDATE, &start, &stop);
+            const bool last = s0 + cap >= n_samples;
+            if (!start && c == 0) start = ep_begin;
+            if (!stop) stop = last ? mf_epoch_end_event(h) : h->ev_chunk[(h->chunk_seq - 1) % gorse_mf::kChunkRing];
             if (uruns)
                 GORSE_TRY(launch_update_users(h, h->sorted[b].p, h->ubucket[b].p, (size_t)cap, lr, reg, g_exp_mode_exact, d_loss, h->stream,
-                                              mode == MODE_STORES));
+                                              mode == MODE_STORES, start, stop));
             else  // (the per-sample schedule has no store route: mode 3 is mode 0 there)
-                GORSE_TRY(launch_update(h, mode == MODE_STORES ? MODE_ATOMIC : mode, tb, tb + cap, tb + 2 * cap, nullptr, 0, m, lr, reg, 0, d_loss, h->stream));
-            h->prof.end(tok, h->stream);
-            GORSE_HIP_CHECK(hipEventRecord(h->ev_consumed[b], h->stream));
+                GORSE_TRY(launch_update(h, mode == MODE_STORES ? MODE_ATOMIC : mode, tb, tb + cap, tb + 2 * cap, nullptr, 0, m, lr, reg, 0, d_loss,
+                                        h->stream, start, stop));
+            h->ev_consumed[b] = stop;
+            if (last) ep_end = stop;
             if (cancel && (c & 7) == 7) GORSE_TRY(mf_sync_streams(h));
         }
     }
-    GORSE_TRY(mf_epoch_end(h));
+    GORSE_TRY(mf_epoch_end(h, ep_end));  // (the sequential schedule has no launch to bind it to: recorded)
     h->ep_chain = true;
     if (sync || loss_out) {
         if (loss_out)

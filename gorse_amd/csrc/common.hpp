@@ -1,6 +1,7 @@
 // common.hpp -- shared plumbing of libgorse_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <cstdarg>
 #include <cstdint>
@@ -113,6 +114,18 @@ struct KernelProfile {
     }
     void end(int tok, hipStream_t s) {
         if (tok >= 0) (void)hipEventRecord(pending[tok].b, s);
+    }
+    // A span bound to its launches instead of recorded around them: the pair goes to hipExtLaunchKernelGGL (hip/hip_ext.h) as the
+    // startEvent of the span's first kernel and the stopEvent of its last (the same launch when the span is one kernel), so no marker
+    // packet of the profile's stands between two kernels of the stream.  Two nulls while profiling is off.  The events stay the
+    // profile's until resolve(): a caller that hands the stop event on (as a chunk's "consumed" event) drops it before that.
+    void events(int cls, hipEvent_t *start, hipEvent_t *stop) {
+        *start = *stop = nullptr;
+        if (!on) return;
+        Pair p{get(), get(), cls};
+        pending.push_back(p);
+        *start = p.a;
+        *stop = p.b;
     }
     void resolve() {  // caller has synchronised the streams
         for (auto &p : pending) {

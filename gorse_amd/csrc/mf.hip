@@ -172,11 +172,13 @@ int32_t mf_sync_streams(gorse_mf *h) {
 // stream: begin = the stream reaches the epoch (= the end of the previous epoch's last update kernel when epochs follow each other),
 // end = its last update kernel is done.  gorse_mf_epoch_throttle waits on them with the cancel flag in hand, gorse_mf_epoch_times
 // adds up their spans.
-int32_t mf_epoch_begin(gorse_mf *h, bool chained) {
+int32_t mf_epoch_begin(gorse_mf *h, bool chained, bool record, hipEvent_t *attach) {
+    *attach = nullptr;
     if (!h->ep_events) {
         for (int i = 0; i < gorse_mf::kEpochRing; i++) {
             GORSE_HIP_CHECK(hipEventCreate(&h->ev_ep_begin[i]));
-            GORSE_HIP_CHECK(hipEventCreate(&h->ev_ep_end[i]));
+            GORSE_HIP_CHECK(hipEventCreate(&h->ev_ep_end_own[i]));
+            h->ev_ep_end[i] = h->ev_ep_end_own[i];
         }
         h->ep_events = true;
     }
@@ -202,12 +204,35 @@ int32_t mf_epoch_begin(gorse_mf *h, bool chained) {
         }
     }
     h->ep_begin_prev[slot] = from_prev;
-    if (!from_prev) GORSE_HIP_CHECK(hipEventRecord(h->ev_ep_begin[slot], h->stream));
+    // not chained: the begin is the start event of the epoch's first update launch (*attach) unless the caller issues something else
+    // of the epoch in front of that launch (`record`): then it is recorded here, where the stream reaches the epoch
+    if (!from_prev) {
+        if (record)
+            GORSE_HIP_CHECK(hipEventRecord(h->ev_ep_begin[slot], h->stream));
+        else
+            *attach = h->ev_ep_begin[slot];
+    }
     return GORSE_OK;
 }
-int32_t mf_epoch_end(gorse_mf *h) {
-    GORSE_HIP_CHECK(hipEventRecord(h->ev_ep_end[h->ep_seq % gorse_mf::kEpochRing], h->stream));
+hipEvent_t mf_epoch_end_event(gorse_mf *h) { return h->ev_ep_end_own[h->ep_seq % gorse_mf::kEpochRing]; }
+int32_t mf_epoch_end(gorse_mf *h, hipEvent_t attached) {
+    const int slot = (int)(h->ep_seq % gorse_mf::kEpochRing);
+    if (attached) {  // the stop event of the epoch's last update launch: nothing is enqueued
+        h->ev_ep_end[slot] = attached;
+    } else {
+        h->ev_ep_end[slot] = h->ev_ep_end_own[slot];
+        GORSE_HIP_CHECK(hipEventRecord(h->ev_ep_end[slot], h->stream));
+    }
     h->ep_seq++;
+    return GORSE_OK;
+}
+// The profile takes its events back (KernelProfile::resolve; the caller has synchronised the streams): read the epochs that end on one
+// of them first, and let go of every event borrowed from it.
+int32_t mf_prof_resolve(gorse_mf *h) {
+    GORSE_TRY(mf_epoch_harvest(h, true));
+    for (int i = 0; i < gorse_mf::kEpochRing; i++) h->ev_ep_end[i] = h->ev_ep_end_own[i];
+    h->ev_consumed[0] = h->ev_consumed[1] = nullptr;  // (both buffers are consumed: the streams are idle)
+    h->prof.resolve();
     return GORSE_OK;
 }
 int32_t mf_epoch_harvest(gorse_mf *h, bool wait) {
@@ -375,8 +400,8 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
         }
         for (int b = 0; b < 2; b++) {
             GORSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev_sampled[b], hipEventDisableTiming));
-            GORSE_HIP_CHECK(hipEventCreateWithFlags(&h->ev_consumed[b], hipEventDisableTiming));
         }
+        for (int i = 0; i < gorse_mf::kChunkRing; i++) GORSE_HIP_CHECK(hipEventCreate(&h->ev_chunk[i]));
         trace.mark("create: streams, events");
         // one row more than the matrix has, and it stays zero: the ALS gathers send the entries past a row's end there (row id U
         // resp. I) instead of selecting an address per load
@@ -511,12 +536,13 @@ extern "C" int32_t gorse_mf_destroy(gorse_mf *h) {
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     for (int b = 0; b < 2; b++) {
         if (h->ev_sampled[b]) (void)hipEventDestroy(h->ev_sampled[b]);
-        if (h->ev_consumed[b]) (void)hipEventDestroy(h->ev_consumed[b]);
     }
+    for (int i = 0; i < gorse_mf::kChunkRing; i++)
+        if (h->ev_chunk[i]) (void)hipEventDestroy(h->ev_chunk[i]);
     if (h->ep_events)
         for (int i = 0; i < gorse_mf::kEpochRing; i++) {
             (void)hipEventDestroy(h->ev_ep_begin[i]);
-            (void)hipEventDestroy(h->ev_ep_end[i]);
+            (void)hipEventDestroy(h->ev_ep_end_own[i]);
         }
     trace.mark("destroy: sync, events");
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -747,7 +773,7 @@ extern "C" int32_t gorse_mf_set_profiling(gorse_mf *h, int32_t on) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     GORSE_TRY(h->use());
     GORSE_TRY(mf_sync_streams(h));
-    h->prof.resolve();
+    GORSE_TRY(mf_prof_resolve(h));
     h->prof.on = on != 0;
     return GORSE_OK;
 }
@@ -755,7 +781,7 @@ extern "C" int32_t gorse_mf_get_profile(gorse_mf *h, int32_t cls, int64_t *launc
     if (!h || cls < 0 || cls >= GORSE_PROF_NCLASSES) return fail(GORSE_ERR_INVALID, "bad kernel class");
     GORSE_TRY(h->use());
     GORSE_TRY(mf_sync_streams(h));
-    h->prof.resolve();
+    GORSE_TRY(mf_prof_resolve(h));
     if (launches) *launches = h->prof.launches[cls];
     if (total_ms) *total_ms = h->prof.ms[cls];
     return GORSE_OK;
@@ -764,6 +790,7 @@ extern "C" int32_t gorse_mf_reset_profile(gorse_mf *h) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     GORSE_TRY(h->use());
     GORSE_TRY(mf_sync_streams(h));
+    GORSE_TRY(mf_prof_resolve(h));
     h->prof.reset();
     return GORSE_OK;
 }

@@ -23,11 +23,23 @@ struct gorse_mf {
     hipStream_t stream = nullptr;   // update kernels, copies
     hipStream_t stream2 = nullptr;  // sampler running ahead of the update kernels
     hipEvent_t ev_sampled[2] = {nullptr, nullptr};
+    // A chunk's update launch carries ONE stop event, attached to its last kernel's dispatch (hipExtLaunchKernelGGL): the chunk's
+    // "consumed" event the preparation of the chunk after next waits on, the epoch's end event when the chunk is the epoch's last, and
+    // the profile's end of the update span -- no marker packet follows the kernel.  ev_consumed[b] = the stop event of the launch that
+    // last read buffer b (null: nothing to wait for).  It is borrowed: the profile's stop event while profiling is on
+    // (KernelProfile::events; mf_prof_resolve drops it before the profile takes its events back), the epoch's own end event for an
+    // epoch's last chunk, a slot of ev_chunk otherwise.  A waiter is issued two chunks after the launch and a slot of ev_chunk is
+    // attached again four chunks after it, so the wait has always been issued (and has taken hold of that launch) by then.
     hipEvent_t ev_consumed[2] = {nullptr, nullptr};
-    // epoch pacing (gorse_mf_epoch_throttle / gorse_mf_epoch_times): a ring of (begin, end) event pairs, one per BPR epoch, recorded
-    // on the update stream; created with the first epoch.  ep_seq = epochs issued, ep_done = epochs whose events have been read.
+    static constexpr int kChunkRing = 4;
+    hipEvent_t ev_chunk[kChunkRing] = {};
+    // epoch pacing (gorse_mf_epoch_throttle / gorse_mf_epoch_times): a ring of (begin, end) event pairs, one per BPR epoch, on the
+    // update stream; created with the first epoch.  ep_seq = epochs issued, ep_done = epochs whose events have been read.
+    // end = the stop event of the epoch's last update launch: ev_ep_end[slot] is what the readers use, either the ring's own event
+    // (ev_ep_end_own) or, while profiling is on, the profile's.  begin = the start event of the epoch's first update launch, or a
+    // recorded event where something else of the epoch precedes that launch on the stream (epoch_impl, csrc/bpr.hip).
     static constexpr int kEpochRing = 16;
-    hipEvent_t ev_ep_begin[kEpochRing] = {}, ev_ep_end[kEpochRing] = {};
+    hipEvent_t ev_ep_begin[kEpochRing] = {}, ev_ep_end[kEpochRing] = {}, ev_ep_end_own[kEpochRing] = {};
     bool ep_events = false;
     // An epoch that is enqueued while the one before it is still in flight, with nothing else issued on the handle in between (ep_chain:
     // set by the epoch, cleared by every other entry point through use()), begins where that one ended: its begin IS the previous slot's
@@ -119,8 +131,13 @@ namespace gorse {
 // implemented in bpr.hip / als.hip, used across files
 int32_t mf_sync_streams(gorse_mf *h);
 // epoch pacing: mark the begin / end of one epoch on the update stream; read the finished ones (wait = block for all of them)
-int32_t mf_epoch_begin(gorse_mf *h, bool chained);
-int32_t mf_epoch_end(gorse_mf *h);
+// (begin: `record` = the caller issues other work of the epoch in front of its first update launch, *attach = the start event that
+// launch takes otherwise; end: `attached` = the stop event the epoch's last update launch took -- mf_epoch_end_event() or the
+// profile's -- or null to record one)
+int32_t mf_epoch_begin(gorse_mf *h, bool chained, bool record, hipEvent_t *attach);
+hipEvent_t mf_epoch_end_event(gorse_mf *h);
+int32_t mf_epoch_end(gorse_mf *h, hipEvent_t attached);
+int32_t mf_prof_resolve(gorse_mf *h);  // KernelProfile::resolve of the handle's profile, after letting go of the events borrowed from it
 int32_t mf_epoch_harvest(gorse_mf *h, bool wait);
 int32_t mf_delta_export_async(gorse_mf *h, float *dst);        // mf.hip: dst <- Q - Q_sync, enqueued on h->stream
 int32_t mf_delta_import_async(gorse_mf *h, const float *src);  // mf.hip: Q <- Q_sync + src; Q_sync <- Q
