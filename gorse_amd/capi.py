@@ -119,6 +119,9 @@ SIGNATURES = {
     "gorse_fm_rank_users": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, _f32p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p,
                                         _i32p]),
     "gorse_fm_rank_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p, _i64p, _f64p]),
+    "gorse_fm_set_test": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p, C.POINTER(C.POINTER(C.c_uint16))]),
+    "gorse_fm_evaluate": (C.c_int32, [_vp, C.c_int32, _i32p, _i64p, _f32p, _f32p]),
+    "gorse_fm_evaluate_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p, _f64p]),
     "gorse_hip_test_set_exact_exp": (None, [C.c_int32]),
     "gorse_hip_test_set_variant": (None, [C.c_int32]),
     "gorse_hip_test_set_topk_path": (None, [C.c_int32]),
@@ -172,6 +175,9 @@ SIGNATURES = {
     "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
     "gorse_hip_test_set_fm_rank": (None, [C.c_int64, C.c_int32]),
     "gorse_hip_test_fm_rank_sort": (C.c_int32, [_vp, C.c_int64, _i64p, _f32p, _i32p]),
+    "gorse_hip_test_set_fm_evaluate": (None, [C.c_int64, C.c_int32]),
+    "gorse_hip_test_fm_auc": (C.c_int32, [_vp, _f32p, C.c_int64, _f32p, C.c_int64, _i64p, _f32p]),
+    "gorse_hip_test_fm_evaluate_times": (C.c_int32, [_vp, _f64p]),
 }
 
 
@@ -432,6 +438,9 @@ class MF:
         return n.value, ms.value
 
 
+EVAL_COUNTS = ("n_pos", "n_neg", "pos_above", "neg_above", "neg_below", "nan", "pairs_less")
+
+
 class FM:
     """One gorse_fm handle: a factorization machine (ctr.AFM) resident on one GPU, with its item-embedding attention branch when
     embedding_dims names fields.  Rows are n x width matrices of feature indices and values, padded with index 0 / value 0;
@@ -548,6 +557,40 @@ class FM:
         ms = C.c_double(0)
         check(lib().gorse_fm_rank_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
         return dict(rows=v[0].value, slices=v[1].value, rounds=v[2].value, host_sorted=v[3].value, device_ms=ms.value)
+
+    def set_test(self, indices, values, target, embs=()):
+        """the resident test split of evaluate: n x width indices / values, one target per row (> 0: a positive) and one
+        n x D uint16 (bf16) matrix per field.  No rows (n = 0) drops the split."""
+        idx, val = self._rows(indices, values)
+        tgt = _arr(target, np.float32).reshape(-1)
+        n = idx.shape[0]
+        if tgt.size != n:
+            raise GorseHipError(ERR_INVALID, "one target per row")
+        embs = [_arr(e, np.uint16) for e in embs]
+        if n > 0 and (len(embs) != len(self.dims) or any(e.shape != (n, D) for e, D in zip(embs, self.dims))):
+            raise GorseHipError(ERR_INVALID, "one n x D embedding matrix per field")
+        ptrs = (C.POINTER(C.c_uint16) * max(1, len(embs)))(*[_p(e, C.POINTER(C.c_uint16)) for e in embs])
+        check(lib().gorse_fm_set_test(self.h, n, max(1, idx.shape[1]), _p(idx, _i32p), _p(val, _f32p), _p(tgt, _f32p),
+                                      ptrs if embs else None))
+        self._n_test = n
+
+    def evaluate(self, batch_size, cancel=None, logits=False):
+        """(counts, auc_sum) of the resident split, or (counts, auc_sum, logits) with the logits in the rows' given order.
+        counts: dict of n_pos, n_neg, pos_above (positives with logit > 0), neg_above, neg_below, nan, pairs_less."""
+        cnt = np.zeros(7, np.int64)
+        s = np.zeros(1, np.float32)
+        out = np.zeros(max(1, getattr(self, "_n_test", 0)), np.float32) if logits else None
+        check(lib().gorse_fm_evaluate(self.h, int(batch_size), _p(cancel, _i32p) if cancel is not None else None, _p(cnt, _i64p),
+                                      _p(s, _f32p), _p(out, _f32p)))
+        counts = dict(zip(EVAL_COUNTS, (int(x) for x in cnt)))
+        return (counts, s[0], out[:getattr(self, "_n_test", 0)]) if logits else (counts, s[0])
+
+    def evaluate_stats(self):
+        """the last evaluate: rows scored, slices, launch rounds, device milliseconds"""
+        v = [C.c_int64(0) for _ in range(3)]
+        ms = C.c_double(0)
+        check(lib().gorse_fm_evaluate_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
+        return dict(rows=v[0].value, slices=v[1].value, rounds=v[2].value, device_ms=ms.value)
 
     def close(self):
         if getattr(self, "h", None):

@@ -759,6 +759,8 @@ extern "C" int32_t gorse_fm_destroy(gorse_fm *h) {
         if (e) (void)hipEventDestroy(e);
     for (auto e : h->r_ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto e : h->e_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->s) (void)hipStreamDestroy(h->s);
     delete h;
     return GORSE_OK;
@@ -832,6 +834,7 @@ extern "C" int32_t gorse_fm_set_embedding_dims(gorse_fm *h, int32_t n_fields, co
         F.D = 0;
     }
     h->cat.reset();  // the resident item catalogue holds one table per field of the set that is going away
+    h->test.reset();  // and so does the resident test split
     h->n_fields = 0;
     h->dense_blocks = 0;
     std::vector<fm::DenseDesc> descs;

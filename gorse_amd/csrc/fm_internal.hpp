@@ -43,6 +43,23 @@ struct Catalogue {
     DevBuf<float> val;
     DevBuf<uint16_t> emb[kMaxFields];
 };
+
+// The resident test split of gorse_fm_evaluate (gorse_fm_set_test): the rows in EvaluateClassification's order (the n_pos
+// positives first, then the others, each side in dataset order), their padded index / value matrices and one n x D bf16 table per
+// field, gathered once.  Replaced as a whole.  The slice descriptors belong to one (batch size, round rows).
+struct TestSplit {
+    int64_t n = 0, n_pos = 0;
+    int width = 0;
+    std::vector<int32_t> order;  // resident row -> dataset row
+    DevBuf<int32_t> idx;
+    DevBuf<float> val;
+    DevBuf<uint16_t> emb[kMaxFields];
+    int32_t plan_bs = 0;
+    int64_t plan_rows = 0;
+    DevBuf<int32_t> desc;  // row | slice row0 | slice length, n entries each
+    std::vector<int64_t> round_begin;
+    int64_t n_slices = 0, max_round = 0;
+};
 }  // namespace fm
 }  // namespace gorse
 
@@ -90,6 +107,14 @@ struct gorse_fm {
     hipEvent_t r_ev[2] = {nullptr, nullptr};  // timing events of gorse_fm_rank_stats, created by the first rank call
     int64_t rk_rows = 0, rk_slices = 0, rk_rounds = 0, rk_host_sorted = 0;
     double rk_ms = 0.0;
+    // evaluation from a resident test split (fm_eval.hip): again buffers of its own
+    std::unique_ptr<gorse::fm::TestSplit> test;
+    gorse::DevBuf<float> e_vx, e_h, e_s, e_rmax, e_rsum, e_logit;
+    gorse::DevBuf<uint32_t> e_key[2], e_hist, e_cnt;  // the sort's two key arrays, its tile x digit counts, negatives below each positive
+    gorse::DevBuf<uint64_t> e_acc;                    // the tallies, pairs_less and (as bits) auc_sum
+    hipEvent_t e_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | scored | sorted and counted | chain done
+    int64_t ev_rows = 0, ev_slices = 0, ev_rounds = 0;
+    double ev_ms[4] = {0.0, 0.0, 0.0, 0.0};  // all | scoring | keys, sort, count | chain
 };
 
 namespace gorse {

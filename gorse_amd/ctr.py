@@ -34,6 +34,10 @@ def host():
         H.gh_fm_field_params.argtypes = [C.c_void_p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]
         H.gh_ctr_fm_set_items.argtypes = [C.c_void_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, C.c_int32, C.POINTER(_u16p)]
         H.gh_ctr_fm_rank_users.argtypes = [C.c_void_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, _i64p, _i32p, _i32p, _f32p]
+        H.gh_fm_set_test.argtypes = [C.c_void_p, C.c_void_p]
+        H.gh_fm_evaluate_resident.argtypes = [C.c_void_p, _f32p]
+        H.gh_fm_set_host_evaluate.restype = None
+        H.gh_fm_set_host_evaluate.argtypes = [C.c_void_p, C.c_int32]
         _configured = True
     return H
 
@@ -148,6 +152,24 @@ class FM:
         if rc != 0:
             raise cf.HostError(rc)
         return Score(s)
+
+    def SetTest(self, test):
+        """makes the test split resident on the device for EvaluateResident (Fit does it itself for its own test set)"""
+        rc = host().gh_fm_set_test(self.p, test.p)
+        if rc != 0:
+            raise cf.HostError(rc)
+
+    def EvaluateResident(self):
+        """EvaluateClassification of the resident split, scored and counted on the device"""
+        s = np.zeros(4, np.float32)
+        rc = host().gh_fm_evaluate_resident(self.p, s.ctypes.data_as(_f32p))
+        if rc != 0:
+            raise cf.HostError(rc)
+        return Score(s)
+
+    def SetHostEvaluate(self, on):
+        """True: Fit evaluates through Evaluate's route (gather, upload, download, sort on the host) instead of the resident split"""
+        host().gh_fm_set_host_evaluate(self.p, int(bool(on)))
 
     def log(self):
         """[(epoch, cost, AUC)] of every evaluation of the last Fit"""

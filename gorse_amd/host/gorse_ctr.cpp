@@ -170,6 +170,69 @@ std::vector<std::vector<Ranked>> FM::RankUsers(const LabelRows &users, const std
     return out;
 }
 
+void FM::SetTest(const Dataset &test) {
+    if (!h_) throw std::invalid_argument("model is not fitted");
+    const int64_t n = test.Count();
+    testCount_ = -1;
+    testPositive_.assign((size_t)n, 0);
+    for (int64_t i = 0; i < n; i++) testPositive_[(size_t)i] = test.target[(size_t)i] > 0;
+    if (n == 0) {
+        check(gorse_fm_set_test(h_, 0, 1, nullptr, nullptr, nullptr, nullptr));
+        testCount_ = 0;
+        return;
+    }
+    const int width = std::max({1, numDimension_, test.MaxLen()});
+    std::vector<int64_t> all((size_t)n);
+    for (int64_t i = 0; i < n; i++) all[(size_t)i] = i;
+    std::vector<int32_t> idx;
+    std::vector<float> val;
+    pad_rows(test, all, width, idx, val);
+    // a set without embeddings scores with absent (zero) ones, as BatchInternalPredict has it
+    if (!test.emb_dims.empty() && test.emb_dims.size() != fields.size()) throw std::invalid_argument("embedding fields differ from the fitted model's");
+    std::vector<std::vector<uint16_t>> zeros(fields.size());
+    std::vector<const uint16_t *> ptrs(fields.size());
+    for (size_t k = 0; k < fields.size(); k++) {
+        if (!test.emb_dims.empty()) {
+            if (test.emb_dims[k] != fields[k].D) throw std::invalid_argument("embedding dimension differs from the fitted model's");
+            ptrs[k] = test.emb[k].data();
+        } else {
+            zeros[k].assign((size_t)n * (size_t)fields[k].D, 0);
+            ptrs[k] = zeros[k].data();
+        }
+    }
+    check(gorse_fm_set_test(h_, n, width, idx.data(), val.data(), test.target.data(), fields.empty() ? nullptr : ptrs.data()));
+    testCount_ = n;
+}
+
+// the float32 counter `x++` run `count` times from 0: past 2^24 the increment rounds away
+static float counter(int64_t count) { return (float)std::min<int64_t>(count, (int64_t)1 << 24); }
+
+Score FM::EvaluateResident() {
+    if (!h_ || testCount_ < 0) throw std::invalid_argument("no resident test split (SetTest)");
+    if (testCount_ == 0) return Score{};
+    int64_t c[GORSE_FM_EVAL_COUNTS];
+    float aucSum = 0;
+    check(gorse_fm_evaluate(h_, batchSize_, nullptr, c, &aucSum, nullptr));
+    Score s;
+    if (c[5] > 0) {  // a NaN logit: the metrics' own loops decide, on the same logits
+        std::vector<float> logits((size_t)testCount_), pp, np_;
+        check(gorse_fm_evaluate(h_, batchSize_, nullptr, c, &aucSum, logits.data()));
+        for (int64_t i = 0; i < testCount_; i++) (testPositive_[(size_t)i] ? pp : np_).push_back(logits[(size_t)i]);
+        s.Precision = Precision(pp, np_);
+        s.Recall = Recall(pp, np_);
+        s.Accuracy = Accuracy(pp, np_);
+        s.AUC = AUC(pp, np_);
+        return s;
+    }
+    const int64_t nPos = c[0], nNeg = c[1];
+    const float tp = counter(c[2]), fp = counter(c[3]), fn = counter(nPos - c[2]);
+    s.Precision = tp + fp == 0 ? 0 : tp / (tp + fp);
+    s.Recall = tp + fn == 0 ? 0 : tp / (tp + fn);
+    s.Accuracy = counter(c[2] + c[4]) / (float)(size_t)(nPos + nNeg);
+    s.AUC = nPos * nNeg == 0 ? 0 : aucSum / (float)((size_t)nPos * (size_t)nNeg);
+    return s;
+}
+
 void FM::ReadBack() {
     check(gorse_fm_get_params(h_, &B, W.data(), V.data()));
     for (size_t k = 0; k < fields.size(); k++) {
@@ -232,7 +295,10 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
     }
     log.clear();
 
-    Score score = EvaluateClassification(*this, test);
+    testCount_ = -1;  // the handle is new
+    if (!hostEvaluate_) SetTest(test);
+    auto evaluate = [&] { return hostEvaluate_ ? EvaluateClassification(*this, test) : EvaluateResident(); };
+    Score score = evaluate();
     std::vector<std::pair<int, float>> scores{{0, score.AUC}};
     log.push_back({0, 0.0f, score});
 
@@ -256,7 +322,7 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
         }
         check(rc);
         if (epoch % cfg.Verbose == 0 || epoch == nEpochs_) {
-            score = EvaluateClassification(*this, test);
+            score = evaluate();
             scores.push_back({epoch, score.AUC});
             log.push_back({epoch, cost, score});
             if (std::isnan(cost) || std::isnan(score.GetValue())) break;  // model diverged

@@ -83,6 +83,14 @@ class FM {
     // returns, per user, its candidates (catalogue rows) sorted as gorse_fm_rank_users orders them, with their scores.
     void SetItems(const LabelRows &items, const std::vector<const uint16_t *> &emb);
     std::vector<std::vector<Ranked>> RankUsers(const LabelRows &users, const std::vector<std::vector<int32_t>> &cands);
+    // EvaluateClassification from a test split that stays on the device.  SetTest partitions, pads and uploads the set once
+    // (gorse_fm_set_test); EvaluateResident scores it there and forms the Score from the counts that come back exactly as
+    // evaluator.go:85-153 forms it from the logits (its float32 counters stop at 2^24, as tp++ does).  Should a logit be NaN,
+    // the logits are fetched and the metrics' own loops run on them, as the host route's do.  Fit evaluates this way unless
+    // SetHostEvaluate(true) asks for the free function below.
+    void SetTest(const Dataset &test);
+    Score EvaluateResident();
+    void SetHostEvaluate(bool on) { hostEvaluate_ = on; }
     float B = 0;
     std::vector<float> W, V;          // the parameters after Fit (copied back, as into the nn tensors)
     struct Field {                    // one embedding field's tensors in Parameters() order (fm.go:136-146)
@@ -99,6 +107,9 @@ class FM {
     int64_t seed_;
     int device_;
     int numDimension_ = 0;
+    bool hostEvaluate_ = false;
+    int64_t testCount_ = -1;           // rows of the resident split; -1: none
+    std::vector<uint8_t> testPositive_;  // per row of it: target > 0
     void ReadBack();
     int64_t nf_ = 0;
     gorse_fm *h_ = nullptr;

@@ -1078,6 +1078,17 @@ int32_t gh_fm_evaluate(void *m, void *test, float *score4) {
         score4[0] = s.Precision, score4[1] = s.Recall, score4[2] = s.Accuracy, score4[3] = s.AUC;
     });
 }
+// ctr::FM::SetTest / EvaluateResident / SetHostEvaluate: the test split resident on the device
+int32_t gh_fm_set_test(void *m, void *test) {
+    return guard([&] { ((ctr::FM *)m)->SetTest(*(ctr::Dataset *)test); });
+}
+int32_t gh_fm_evaluate_resident(void *m, float *score4) {
+    return guard([&] {
+        const ctr::Score s = ((ctr::FM *)m)->EvaluateResident();
+        score4[0] = s.Precision, score4[1] = s.Recall, score4[2] = s.Accuracy, score4[3] = s.AUC;
+    });
+}
+void gh_fm_set_host_evaluate(void *m, int32_t on) { ((ctr::FM *)m)->SetHostEvaluate(on != 0); }
 // the evaluations of the last Fit: epoch, cost, AUC; returns how many there are (at most cap are written)
 int32_t gh_fm_log(void *m, int32_t *epochs, float *costs, float *aucs, int32_t cap) {
     const auto &lg = ((ctr::FM *)m)->log;

@@ -525,6 +525,42 @@ int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64_t *user_in
  * Any pointer may be NULL. */
 int32_t gorse_fm_rank_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, int64_t *host_sorted, double *device_ms);
 
+/* ---- evaluating the ranker from a resident test split ------------------------------------------------------------------------
+ * EvaluateClassification (model/ctr/evaluator.go:46-153) partitions the test rows into positives and negatives, scores each side
+ * with one BatchInternalPredict call, and forms Precision, Recall, Accuracy and AUC from the logits.  Fit calls it at epoch 0 and
+ * at every Verbose-th epoch on the same rows.  Here the split stays on the device and only counts come back.
+ *
+ * gorse_fm_set_test keeps n rows (n x width indices / values padded with index 0 / value 0, as gorse_fm_predict takes them, and
+ * emb[k] = field k's n x D_k bf16 matrix) in the order the reference scores them: the rows with target > 0 first, in dataset
+ * order, then the others (a target of exactly 0 is a negative), in dataset order.  The partition and the gather of the embedding
+ * rows happen once, here; the embeddings stay bf16 and are indexed with 64-bit offsets.  Everything is validated before
+ * anything is replaced and an error leaves the previous split in place: an index outside [0, n_features) is GORSE_ERR_RANGE,
+ * n >= 2^31 GORSE_ERR_INVALID, a split that does not fit the device GORSE_ERR_NOMEM.  n = 0 drops the split, and so does
+ * gorse_fm_set_embedding_dims; set_params, set_embedding_params, set_train, epoch, set_items and rank_users leave it alone.  It
+ * lives in buffers of its own: training and predict read nothing of it. */
+int32_t gorse_fm_set_test(gorse_fm *h, int64_t n, int32_t width, const int32_t *indices /*host*/, const float *values /*host*/,
+                          const float *target /*host, n*/,
+                          const uint16_t *const *emb /*host, n_fields pointers, or NULL without fields*/);
+/* Scores the resident split and forms the metrics' counts on the device.  The positives are sliced into batches of batch_size
+ * rows from the first positive (the last slice partial), the negatives afresh from the first negative: the reference's Softmax
+ * indexing makes the slice part of the result, and every logit carries the BITS gorse_fm_predict_embeddings (without fields:
+ * gorse_fm_predict) returns for that row when called on the positive rows alone, or on the negative rows alone, with the same
+ * batch_size.
+ * counts[0..GORSE_FM_EVAL_COUNTS): n_pos, n_neg, positives with logit > 0, negatives with logit > 0, negatives with logit < 0,
+ * NaN logits, and pairs_less = the exact sum over the positives of the negatives strictly below it (compared as floats,
+ * -0 == +0).  auc_sum = the reference's own running sum (evaluator.go:139-148): the same per-positive counts added one after the
+ * other in float32, the positives in ascending order of logit.  NaN logits take part in neither.  logits_out (may be NULL): the n
+ * logits in the order the rows were given to gorse_fm_set_test; nothing else travels to the host.
+ * No resident split or batch_size <= 0: GORSE_ERR_INVALID.  The cancel flag is read between launch rounds: GORSE_ERR_CANCELLED,
+ * outputs unspecified.  Parameters, optimizer state, training set, training plan and item catalogue are untouched. */
+#define GORSE_FM_EVAL_COUNTS 7
+int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const volatile int32_t *cancel /*host or NULL*/,
+                          int64_t *counts /*host, GORSE_FM_EVAL_COUNTS entries*/, float *auc_sum /*host*/,
+                          float *logits_out /*host or NULL*/);
+/* the handle's last gorse_fm_evaluate: rows scored, slices, launch rounds, and the device time of its launches (hipEvents on the
+ * handle's stream, copies excluded).  Any pointer may be NULL. */
+int32_t gorse_fm_evaluate_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

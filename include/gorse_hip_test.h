@@ -203,6 +203,16 @@ void gorse_hip_test_set_fm_rank(int64_t round_rows, int32_t sort_cap);
  * sign and any payload, infinities): order_out as that call defines it, lists beyond the cap by the host */
 int32_t gorse_hip_test_fm_rank_sort(gorse_fm *h, int64_t n_users, const int64_t *cand_indptr /*host, n_users+1*/,
                                     const float *scores /*host*/, int32_t *order_out /*host*/);
+/* gorse_fm_evaluate (csrc/fm_eval.hip), calls AFTERWARDS: round_rows > 0 = rows of a launch round at most (raised to the call's
+ * batch_size where smaller: a slice is never split; 0 = by the scratch budget); sort_tile > 0 = keys per workgroup of the radix
+ * sort (0 = 4096).  Results never depend on them. */
+void gorse_hip_test_set_fm_evaluate(int64_t round_rows, int32_t sort_tile);
+/* the metric stage of gorse_fm_evaluate alone, on logits the caller supplies (any bit patterns): counts and auc_sum as that call
+ * defines them */
+int32_t gorse_hip_test_fm_auc(gorse_fm *h, const float *pos /*host*/, int64_t n_pos, const float *neg /*host*/, int64_t n_neg,
+                              int64_t *counts /*host, GORSE_FM_EVAL_COUNTS entries*/, float *auc_sum /*host*/);
+/* device milliseconds of the handle's last gorse_fm_evaluate by stage: scoring | keys, sort and per-positive counts | the chain */
+int32_t gorse_hip_test_fm_evaluate_times(gorse_fm *h, double *ms3 /*host*/);
 
 #ifdef __cplusplus
 }

@@ -147,7 +147,18 @@ func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, c
 	stop := context.AfterFunc(ctx, func() { atomic.StoreInt32((*int32)(unsafe.Pointer(cancel)), 1) })
 	defer stop()
 
-	score = EvaluateClassification(fm, testSet, config.Jobs)
+	// the test split goes to the device once; every evaluation of this Fit then uploads nothing (resident = false: the
+	// reference's EvaluateClassification, which gathers, uploads and sorts per call, stays the route)
+	resident := fm.setTestHIP(testSet)
+	evaluate := func() Score {
+		if resident {
+			if s, ok := fm.evaluateResidentHIP(testSet); ok {
+				return s
+			}
+		}
+		return EvaluateClassification(fm, testSet, config.Jobs)
+	}
+	score = evaluate()
 	scores := []lo.Tuple2[int, float32]{{A: 0, B: score.AUC}}
 	_, span := monitor.Start(ctx, "FM.Fit", fm.nEpochs)
 	defer span.End()
@@ -170,7 +181,7 @@ func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, c
 		fitTime := time.Since(fitStart)
 		if epoch%config.Verbose == 0 || epoch == fm.nEpochs {
 			evalStart := time.Now()
-			score = EvaluateClassification(fm, testSet, config.Jobs) // BatchInternalPredict -> gorse_fm_predict(_embeddings)
+			score = evaluate() // gorse_fm_evaluate on the resident split
 			scores = append(scores, lo.Tuple2[int, float32]{A: epoch, B: score.AUC})
 			log.Logger().Info(fmt.Sprintf("fit AFM %v/%v", epoch, fm.nEpochs), append([]zap.Field{
 				zap.String("fit_time", fitTime.String()),
@@ -194,6 +205,85 @@ func (fm *AFM) fitHIP(ctx context.Context, trainSet, testSet dataset.CTRSplit, c
 	}
 	fm.pullParams()
 	return score, true
+}
+
+// setTestHIP makes the test split resident (gorse_fm_set_test): the rows scaled and padded as BatchInternalPredict has them
+// (applyScalers, convertToTensors), the targets, and every field's embeddings as one n x D bf16 matrix.  The library partitions
+// them into positives (target > 0) and the rest and gathers the embedding rows once.  false: nothing resident (an empty split, or
+// one the device refuses: GORSE_ERR_NOMEM when it does not fit).
+func (fm *AFM) setTestHIP(testSet dataset.CTRSplit) bool {
+	n := testSet.Count()
+	if fm.hip == nil || n == 0 {
+		return false
+	}
+	x := make([]lo.Tuple2[[]int32, []float32], n)
+	y := make([]float32, n)
+	e := make([][][]uint16, n)
+	width := max(fm.numDimension, 1)
+	for i := range x {
+		indices, values, embeddings, target := testSet.Get(i)
+		e[i] = embeddings
+		scaled := make([]float32, len(values))
+		copy(scaled, values)
+		for j, idx := range indices {
+			if scaler, ok := fm.Scalers[idx]; ok {
+				scaled[j] = scaler.Transform(values[j])
+			}
+		}
+		x[i], y[i] = lo.Tuple2[[]int32, []float32]{A: indices, B: scaled}, target
+		width = max(width, len(indices))
+	}
+	idx, val := flatRows(x, width)
+	var embPtr **C.uint16_t
+	if len(fm.embeddingDim) != 0 {
+		// the matrices live in C memory for the call: a Go pointer to Go pointers must not cross cgo
+		ptrs := (*[C.GORSE_FM_MAX_FIELDS]*C.uint16_t)(C.malloc(C.size_t(C.GORSE_FM_MAX_FIELDS) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+		defer C.free(unsafe.Pointer(ptrs))
+		for k, dim := range fm.embeddingDim {
+			emb := flatEmbeddings(e, n, k, dim)
+			ptrs[k] = (*C.uint16_t)(C.CBytes(unsafe.Slice((*byte)(unsafe.Pointer(&emb[0])), 2*len(emb))))
+			defer C.free(unsafe.Pointer(ptrs[k]))
+		}
+		embPtr = &ptrs[0]
+	}
+	if rc := C.gorse_fm_set_test(fm.hip.h, C.int64_t(n), C.int32_t(width), (*C.int32_t)(&idx[0]), (*C.float)(&val[0]),
+		(*C.float)(&y[0]), embPtr); rc != 0 {
+		log.Logger().Warn("fit AFM: gorse_fm_set_test, evaluating through BatchInternalPredict",
+			zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		return false
+	}
+	return true
+}
+
+// evaluateResidentHIP is EvaluateClassification (evaluator.go:46-83) from the resident split: the device scores both sides and
+// returns the counts Precision, Recall, Accuracy and AUC (evaluator.go:85-153) are formed from.  Their float32 counters
+// (tp++, fp++, correct++) stop growing at 2^24, so a count enters as min(count, 2^24); auc_sum is the reference's own running
+// float32 sum.  ok = false (a failure, or a NaN logit: the metrics' own loops then decide) sends the caller to the reference's code.
+func (fm *AFM) evaluateResidentHIP(testSet dataset.CTRSplit) (Score, bool) {
+	var counts [C.GORSE_FM_EVAL_COUNTS]C.int64_t
+	var aucSum C.float
+	if rc := C.gorse_fm_evaluate(fm.hip.h, C.int32_t(fm.batchSize), nil, &counts[0], &aucSum, nil); rc != 0 {
+		log.Logger().Error("evaluate AFM", zap.String("err", C.GoString(C.gorse_hip_last_error())))
+		return Score{}, false
+	}
+	if counts[5] > 0 {
+		return Score{}, false
+	}
+	counter := func(c C.int64_t) float32 { return float32(min(int64(c), 1<<24)) }
+	nPos, nNeg := int(counts[0]), int(counts[1])
+	tp, fp, fn := counter(counts[2]), counter(counts[3]), counter(counts[0]-counts[2])
+	var s Score
+	if tp+fp != 0 {
+		s.Precision = tp / (tp + fp)
+	}
+	if tp+fn != 0 {
+		s.Recall = tp / (tp + fn)
+	}
+	s.Accuracy = counter(counts[2]+counts[4]) / float32(nPos+nNeg)
+	if nPos*nNeg != 0 {
+		s.AUC = float32(aucSum) / float32(nPos*nNeg)
+	}
+	return s, true
 }
 
 // pullParams copies the device's parameters back into the nn tensors; nn.Save (Marshal) then writes them as today.
