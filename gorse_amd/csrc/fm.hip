@@ -5,8 +5,9 @@
 // (common/nn/optimizers.go:70-84, 118-156), plus batch scoring (BatchInternalPredict, fm.go:156-178).
 //
 // One training step = three launches, enqueued for a whole epoch without a host round trip:
-//   fm_forward_kernel  one sample per G-lane group: gathers the row's V / W entries, DPP-reduces the pairwise term, writes the
-//                      sample's loss, its loss gradient g_b = (sigmoid(logit) - y) / n_batch and its vx_f = sum_j V[idx_j,f] x_j;
+//   fm_forward_kernel  (fm_internal.hpp: the one forward kernel, here over PaddedRows) one sample per G-lane group: gathers the
+//                      row's V / W entries, DPP-reduces the pairwise term, writes the sample's loss, its loss gradient
+//                      g_b = (sigmoid(logit) - y) / n_batch and its vx_f = sum_j V[idx_j,f] x_j;
 //   fm_accum_kernel    one wave per feature the batch touches (the batch's (feature, position) list is sorted once per training
 //                      set and batch size): the row's gradient summed over its positions in position order, in a fixed shape,
 //                      no atomics; one extra block reduces dB and the batch's mean loss in a fixed tree;
@@ -21,55 +22,6 @@ namespace gorse {
 namespace fm {
 
 constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kEps = 1e-8f;
-
-struct FwdArgs {
-    const int32_t *idx;  // n x width
-    const float *val;
-    const float *tgt;    // training only
-    const float *V, *W, *B;
-    int64_t row0, nrows;
-    int width, d;
-    float inv_n;         // 1 / rows of the batch (training)
-    float *out;          // scoring: logits; training: NULL, or where the embedding branch wants the FM's logit
-    float *gs, *loss, *vx;  // training: per sample g_b, loss_b, vx (nrows x d)
-};
-
-template <int G, int NF, bool TRAIN>
-__global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs a) {
-    const int lane = threadIdx.x & (G - 1);
-    const int64_t b = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
-    if (b >= a.nrows) return;  // whole groups leave together
-    const int64_t r = a.row0 + b;
-    const int32_t *ri = a.idx + r * a.width;
-    const float *rv = a.val + r * a.width;
-    float vx[NF], sq[NF];
-#pragma unroll
-    for (int k = 0; k < NF; k++) vx[k] = sq[k] = 0.0f;
-    float lin = 0.0f;
-    for (int j = 0; j < a.width; j++) {
-        const float x = rv[j];
-        if (x == 0.0f) continue;  // padding (index 0, value 0) and zero values add only signed zeros
-        fm_entry<G, NF>(a.V, a.W, a.d, lane, ri[j], x, vx, sq, lin);
-    }
-    const float logit = fm_logit<G, NF>(vx, sq, lin, a.B);  // the group's first lane holds it
-    if (TRAIN) {
-#pragma unroll
-        for (int k = 0; k < NF; k++) {
-            const int f = lane + k * G;
-            if (f < a.d) a.vx[b * a.d + f] = vx[k];
-        }
-    }
-    if (lane != 0) return;
-    if (!TRAIN) {
-        a.out[b] = logit;
-        return;
-    }
-    // BCEWithLogits (common/nn/functions.go:218-243) with y = (t + 1) / 2
-    const float y = (a.tgt[r] + 1.0f) * 0.5f;
-    a.loss[b] = fmaxf(logit, 0.0f) - logit * y + logf(1.0f + expf(-fabsf(logit)));
-    a.gs[b] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
-    if (a.out) a.out[b] = logit;  // with embedding fields att_loss_kernel forms loss and g again from the full logit
-}
 
 struct AccArgs {
     const int32_t *uniq, *seg, *pos;  // the batch's slots: uniq[s] = feature, positions pos[seg[s] .. seg[s+1])
@@ -302,16 +254,8 @@ __global__ __launch_bounds__(kBlock) void fm_opt_kernel(OptArgs a) {
 // forward and backward (op.go:760-777).  These kernels reproduce that indexing, so every maximum must exist before any
 // exponential and every sum before any a: three launches forward, two backward plus the parameter-gradient reduction.
 // One wave per row; lanes stride over the D columns; skinny products are formed 16 factors at a time and wave-reduced in
-// a fixed butterfly.  The three forward kernels' bodies are in fm_internal.hpp, shared with fm_rank.hip.
-
-// pre, h = relu(pre), s = h H and each row's maximum of s
-__global__ __launch_bounds__(kBlock) void att_score_kernel(AttArgs a) { att_score_body(a, BatchRows{}); }
-
-// e = exp(s - max[(r D + c) % n]) through fp64 (float32(math.Exp(float64(.))), tensor.go:414-419) and each row's sum of e
-__global__ __launch_bounds__(kBlock) void att_exp_kernel(AttArgs a) { att_exp_body(a, BatchRows{}); }
-
-// a = e / sum[(r D + c) % n], z = a * x, enc = z We + be, logit += sum_f vx_f enc_f
-__global__ __launch_bounds__(kBlock) void att_enc_kernel(AttArgs a) { att_enc_body(a, BatchRows{}); }
+// a fixed butterfly.  The three forward kernels are in fm_internal.hpp (here over BatchRows; fm_resident.hip runs them over
+// the slices of a launch round).
 
 struct LossArgs {
     const float *logit, *tgt;  // tgt: the batch's rows
@@ -557,36 +501,11 @@ int32_t check_rows(const gorse_fm *h, int64_t n, int32_t width, const int32_t *i
     return GORSE_OK;
 }
 
-template <bool TRAIN>
-int32_t launch_forward(gorse_fm *h, const FwdArgs &a) {
-    const int G = lanes_for(h->d);
-    const int64_t grid = ceil_div(a.nrows * G, kBlock);
-    if (grid == 0) return GORSE_OK;
-#define FM_FWD(g, nf) fm_forward_kernel<g, nf, TRAIN><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a)
-    switch (G) {
-        case 8: FM_FWD(8, 1); break;
-        case 16: FM_FWD(16, 1); break;
-        case 32: FM_FWD(32, 1); break;
-        default:
-            if (h->d > 64) FM_FWD(64, 2); else FM_FWD(64, 1);
-    }
-#undef FM_FWD
-    GORSE_HIP_CHECK(hipGetLastError());
-    return GORSE_OK;
-}
-
 int32_t launch_accum(gorse_fm *h, const AccArgs &a) {
-    const int G = lanes_for(h->d);
     const int64_t grid = ceil_div(a.nslots * 64, kBlock) + 1;
-#define FM_ACC(g, nf) fm_accum_kernel<g, nf><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a)
-    switch (G) {
-        case 8: FM_ACC(8, 1); break;
-        case 16: FM_ACC(16, 1); break;
-        case 32: FM_ACC(32, 1); break;
-        default:
-            if (h->d > 64) FM_ACC(64, 2); else FM_ACC(64, 1);
-    }
-#undef FM_ACC
+    with_lanes(h->d, [&](auto G, auto NF) {
+        fm_accum_kernel<decltype(G)::value, decltype(NF)::value><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a);
+    });
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
@@ -644,8 +563,7 @@ int32_t build_plan(gorse_fm *h, int32_t bs) {
 
 // per-batch buffers of the branch for batches of up to `rows` rows; train: also what the backward needs
 int32_t ensure_branch(gorse_fm *h, int64_t rows, bool train) {
-    int maxD = 1;
-    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
+    const int maxD = std::max(1, max_emb_dim(h));
     GORSE_TRY(h->a_rmax.ensure((size_t)rows));
     GORSE_TRY(h->a_rsum.ensure((size_t)rows));
     GORSE_TRY(h->a_logit.ensure((size_t)rows));
@@ -664,12 +582,12 @@ int32_t ensure_branch(gorse_fm *h, int64_t rows, bool train) {
     return GORSE_OK;
 }
 
+// field k on a batch of nrows rows with embeddings x: scoring keeps nothing per field, every field works in field 0's buffers
 AttArgs branch_args(gorse_fm *h, int k, const uint16_t *x, int64_t nrows, const float *vx, bool train) {
     Field &F = h->fld[k], &S = h->fld[train ? k : 0];
-    AttArgs a{};
+    AttArgs a = field_args(h, k);
     a.x = x;
-    a.H = F.p.p + F.off[0], a.Wa = F.p.p + F.off[1], a.ba = F.p.p + F.off[2], a.We = F.p.p + F.off[3], a.be = F.p.p + F.off[4];
-    a.nrows = nrows, a.D = F.D, a.d = h->d;
+    a.nrows = nrows;
     a.h = S.h.p, a.s = S.a.p;
     a.rmax = h->a_rmax.p, a.rsum = h->a_rsum.p;
     a.vx = vx;
@@ -679,16 +597,6 @@ AttArgs branch_args(gorse_fm *h, int k, const uint16_t *x, int64_t nrows, const 
     a.gs = h->gs.p, a.gx = h->a_gx.p, a.sumdx = h->a_sumdx.p, a.dpre = h->a_dpre.p;
     a.gpart = F.gpart.p, a.gstride = (int64_t)F.gstride();
     return a;
-}
-
-// the three forward launches of one field on the batch
-int32_t branch_forward(gorse_fm *h, const AttArgs &a) {
-    const unsigned grid = row_grid(a.nrows);
-    att_score_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
-    att_exp_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
-    att_enc_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
-    GORSE_HIP_CHECK(hipGetLastError());
-    return GORSE_OK;
 }
 
 int32_t branch_backward(gorse_fm *h, const AttArgs &a) {
@@ -954,18 +862,20 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
         }
         const int64_t r0 = k * batch_size, nr = std::min<int64_t>(h->n, r0 + batch_size) - r0;
         const int64_t tag_hi = (h->step + 1) << 32;
-        fm::FwdArgs f{};
-        f.idx = h->idx.p, f.val = h->val.p, f.tgt = h->tgt.p;
+        fm::FwdArgs<fm::PaddedRows> f{};
+        f.src = {h->idx.p, h->val.p, r0, h->width};
+        f.tgt = h->tgt.p + r0;
         f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
-        f.row0 = r0, f.nrows = nr, f.width = h->width, f.d = h->d;
+        f.nrows = nr, f.d = h->d;
         f.inv_n = 1.0f / (float)nr;
         f.gs = h->gs.p, f.loss = h->loss.p, f.vx = h->vx.p;
         if (h->n_fields > 0) f.out = h->a_logit.p;
-        GORSE_TRY(fm::launch_forward<true>(h, f));
+        GORSE_TRY(fm::launch_forward<fm::kTrain>(h->s, f));
         if (h->n_fields > 0) {
             // the branch's contribution joins the logit before loss and g are formed (fm.go:127-132)
             for (int e = 0; e < h->n_fields; e++)
-                GORSE_TRY(fm::branch_forward(h, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true)));
+                GORSE_TRY(fm::branch_forward(h->s, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true),
+                                             fm::BatchRows{}));
             fm::LossArgs l{};
             l.logit = h->a_logit.p, l.tgt = h->tgt.p + r0;
             l.vx = h->vx.p, l.esum = h->a_esum.p;
@@ -1028,12 +938,12 @@ extern "C" int32_t gorse_fm_predict(gorse_fm *h, int64_t n, int32_t width, const
     GORSE_TRY(h->p_out.ensure((size_t)n));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->p_idx.p, indices, ne * 4, hipMemcpyHostToDevice, h->s));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->p_val.p, values, ne * 4, hipMemcpyHostToDevice, h->s));
-    fm::FwdArgs f{};
-    f.idx = h->p_idx.p, f.val = h->p_val.p;
+    fm::FwdArgs<fm::PaddedRows> f{};
+    f.src = {h->p_idx.p, h->p_val.p, 0, width};
     f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
-    f.row0 = 0, f.nrows = n, f.width = width, f.d = h->d;
+    f.nrows = n, f.d = h->d;
     f.out = h->p_out.p;
-    GORSE_TRY(fm::launch_forward<false>(h, f));
+    GORSE_TRY(fm::launch_forward<fm::kLogit>(h->s, f));
     GORSE_HIP_CHECK(hipMemcpyAsync(logits_out, h->p_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->s));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
     return GORSE_OK;
@@ -1047,42 +957,30 @@ extern "C" int32_t gorse_fm_predict_embeddings(gorse_fm *h, int64_t n, int32_t w
     GORSE_TRY(fm::check_rows(h, n, width, indices, values, false));
     if (n == 0) return GORSE_OK;
     if (!logits_out) return fail(GORSE_ERR_INVALID, "logits_out is NULL");
-    if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
-    for (int k = 0; k < h->n_fields; k++)
-        if (!emb[k]) return fail(GORSE_ERR_INVALID, "emb[%d] is NULL", k);
+    GORSE_TRY(fm::check_emb(h, emb));
     GORSE_HIP_CHECK(hipSetDevice(h->device));
     const int64_t bs = std::min<int64_t>(n, batch_size);
     const size_t ne = (size_t)n * width;
-    int maxD = 1;
-    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
     GORSE_TRY(h->p_idx.ensure(ne));
     GORSE_TRY(h->p_val.ensure(ne));
-    GORSE_TRY(h->p_x.ensure((size_t)bs * maxD));
+    GORSE_TRY(h->p_x.ensure((size_t)bs * fm::max_emb_dim(h)));
     GORSE_TRY(h->p_vx.ensure((size_t)bs * h->d));
-    GORSE_TRY(h->p_gs.ensure((size_t)bs));
-    GORSE_TRY(h->p_loss.ensure((size_t)bs));
-    if ((size_t)bs > h->p_zero.n) {
-        GORSE_TRY(h->p_zero.alloc((size_t)bs));
-        GORSE_HIP_CHECK(hipMemsetAsync(h->p_zero.p, 0, (size_t)bs * sizeof(float), h->s));
-    }
     GORSE_TRY(fm::ensure_branch(h, bs, false));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->p_idx.p, indices, ne * 4, hipMemcpyHostToDevice, h->s));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->p_val.p, values, ne * 4, hipMemcpyHostToDevice, h->s));
     // BatchInternalPredict's slices (fm.go:168-176): the softmax's indexing makes the slice length part of the result
     for (int64_t r0 = 0; r0 < n; r0 += bs) {
         const int64_t nr = std::min<int64_t>(n, r0 + bs) - r0;
-        fm::FwdArgs f{};
-        // the training instantiation writes vx; its loss and g (against zero targets) go to buffers nobody reads
-        f.idx = h->p_idx.p + r0 * width, f.val = h->p_val.p + r0 * width, f.tgt = h->p_zero.p;
+        fm::FwdArgs<fm::PaddedRows> f{};
+        f.src = {h->p_idx.p, h->p_val.p, r0, width};
         f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
-        f.row0 = 0, f.nrows = nr, f.width = width, f.d = h->d;
-        f.inv_n = 1.0f;
-        f.out = h->a_logit.p, f.gs = h->p_gs.p, f.loss = h->p_loss.p, f.vx = h->p_vx.p;
-        GORSE_TRY(fm::launch_forward<true>(h, f));
+        f.nrows = nr, f.d = h->d;
+        f.out = h->a_logit.p, f.vx = h->p_vx.p;
+        GORSE_TRY(fm::launch_forward<fm::kLogitVx>(h->s, f));
         for (int k = 0; k < h->n_fields; k++) {
             const int64_t D = h->fld[k].D;
             GORSE_HIP_CHECK(hipMemcpyAsync(h->p_x.p, emb[k] + r0 * D, (size_t)(nr * D) * sizeof(uint16_t), hipMemcpyHostToDevice, h->s));
-            GORSE_TRY(fm::branch_forward(h, fm::branch_args(h, k, h->p_x.p, nr, h->p_vx.p, false)));
+            GORSE_TRY(fm::branch_forward(h->s, fm::branch_args(h, k, h->p_x.p, nr, h->p_vx.p, false), fm::BatchRows{}));
         }
         GORSE_HIP_CHECK(hipMemcpyAsync(logits_out + r0, h->a_logit.p, (size_t)nr * 4, hipMemcpyDeviceToHost, h->s));
     }

@@ -2,11 +2,9 @@
 //
 // gorse_fm_set_test partitions the test rows once (positives first, then the others, each side in dataset order), gathers their
 // embeddings once and keeps all of it resident.  gorse_fm_evaluate scores the two sides as BatchInternalPredict would score them
-// (fm.go:156-178: slices of batch_size rows, each side sliced on its own) with fm_entry / fm_logit and the attention branch's
-// kernel bodies (fm_internal.hpp: the same code as gorse_fm_predict_embeddings, so the same bits), many slices per launch, and
-// forms the metrics' raw counts on the device:
-//   fm_eval_forward_kernel   one G-lane group per resident row: the FM logit, and vx when the model has fields
-//   att_*_eval_kernel        the branch's three forward launches over many slices (SliceRows: the split's table, item[r] = r)
+// (fm.go:156-178: slices of batch_size rows, each side sliced on its own) through score_rounds (fm_resident.hip: the kernels of
+// gorse_fm_predict_embeddings, so the same bits, many slices per launch; the rows are the split's padded rows, and a row's
+// embedding is its own row of the split's tables), and forms the metrics' raw counts on the device:
 //   fm_eval_keys_kernel      order-preserving keys of the logits (-0 folded onto +0, NaN = 0xffffffff: sorts last), and the
 //                            threshold tallies (positives > 0, negatives > 0, negatives < 0, NaNs per side) in the same pass
 //   fm_eval_sort_*_kernel    an LSD radix sort of the two sides' keys, 8 bits a pass: per-tile digit counts into a digit x tile
@@ -23,9 +21,8 @@
 namespace gorse {
 namespace fm {
 
-constexpr int64_t kEvalRoundBytes = (int64_t)256 << 20;  // scratch of one launch round at most (unless one slice alone needs more)
-constexpr int64_t kEvalSortTile = 4096;                  // keys per sort workgroup
-constexpr int64_t kEvalMaxTiles = 65536;                 // tiles per side at most: beyond, the tile grows
+constexpr int64_t kEvalSortTile = 4096;   // keys per sort workgroup
+constexpr int64_t kEvalMaxTiles = 65536;  // tiles per side at most: beyond, the tile grows
 constexpr uint32_t kNanKey = 0xffffffffu;
 // slots of gorse_fm::e_acc
 enum { kAccPosAbove = 0, kAccNegAbove, kAccNegBelow, kAccNanPos, kAccNanNeg, kAccPairs, kAccAuc, kAccSlots };
@@ -33,49 +30,6 @@ enum { kAccPosAbove = 0, kAccNegAbove, kAccNegBelow, kAccNanPos, kAccNanNeg, kAc
 // test hooks (gorse_hip_test_set_fm_evaluate): 0 = the library's choice
 static int64_t g_eval_round_rows = 0;
 static int64_t g_eval_sort_tile = 0;
-
-struct EvalFwdArgs {
-    const int32_t *idx;  // the split's n x width
-    const float *val;
-    const float *V, *W, *B;
-    int64_t row0, nrows;  // the round's first resident row and its rows
-    int width, d;
-    float *logit;  // nrows
-    float *vx;     // nrows x d (VX only)
-};
-
-// fm_forward_kernel's walk over a padded row, on the resident split
-template <int G, int NF, bool VX>
-__global__ __launch_bounds__(kBlock) void fm_eval_forward_kernel(EvalFwdArgs a) {
-    const int lane = threadIdx.x & (G - 1);
-    const int64_t b = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
-    if (b >= a.nrows) return;  // whole groups leave together
-    const int64_t r = a.row0 + b;
-    const int32_t *ri = a.idx + r * a.width;
-    const float *rv = a.val + r * a.width;
-    float vx[NF], sq[NF];
-#pragma unroll
-    for (int k = 0; k < NF; k++) vx[k] = sq[k] = 0.0f;
-    float lin = 0.0f;
-    for (int j = 0; j < a.width; j++) {
-        const float x = rv[j];
-        if (x == 0.0f) continue;
-        fm_entry<G, NF>(a.V, a.W, a.d, lane, ri[j], x, vx, sq, lin);
-    }
-    const float logit = fm_logit<G, NF>(vx, sq, lin, a.B);
-    if (VX) {
-#pragma unroll
-        for (int k = 0; k < NF; k++) {
-            const int f = lane + k * G;
-            if (f < a.d) a.vx[b * a.d + f] = vx[k];
-        }
-    }
-    if (lane == 0) a.logit[b] = logit;
-}
-
-__global__ __launch_bounds__(kBlock) void att_score_eval_kernel(AttArgs a, SliceRows rows) { att_score_body(a, rows); }
-__global__ __launch_bounds__(kBlock) void att_exp_eval_kernel(AttArgs a, SliceRows rows) { att_exp_body(a, rows); }
-__global__ __launch_bounds__(kBlock) void att_enc_eval_kernel(AttArgs a, SliceRows rows) { att_enc_body(a, rows); }
 
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
@@ -293,37 +247,6 @@ __global__ __launch_bounds__(64) void fm_eval_chain_kernel(const uint32_t *cnt, 
     if (lane == 0) acc[kAccAuc] = (unsigned long long)__float_as_uint(s);
 }
 
-template <bool VX>
-int32_t launch_eval_forward(gorse_fm *h, const EvalFwdArgs &a) {
-    const int G = lanes_for(h->d);
-    const int64_t grid = ceil_div(a.nrows * G, kBlock);
-    if (grid == 0) return GORSE_OK;
-#define FM_EVAL_FWD(g, nf) fm_eval_forward_kernel<g, nf, VX><<<dim3((unsigned)grid), dim3(kBlock), 0, h->s>>>(a)
-    switch (G) {
-        case 8: FM_EVAL_FWD(8, 1); break;
-        case 16: FM_EVAL_FWD(16, 1); break;
-        case 32: FM_EVAL_FWD(32, 1); break;
-        default:
-            if (h->d > 64) FM_EVAL_FWD(64, 2); else FM_EVAL_FWD(64, 1);
-    }
-#undef FM_EVAL_FWD
-    GORSE_HIP_CHECK(hipGetLastError());
-    return GORSE_OK;
-}
-
-template <typename T>
-int32_t put(DevBuf<T> &dst, const T *src, size_t n) {
-    GORSE_TRY(dst.ensure(n));
-    if (n) GORSE_HIP_CHECK(hipMemcpy(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return GORSE_OK;
-}
-
-int32_t ensure_events(gorse_fm *h) {
-    for (auto &e : h->e_ev)
-        if (!e) GORSE_HIP_CHECK(hipEventCreate(&e));
-    return GORSE_OK;
-}
-
 int64_t sort_tile_for(int64_t n) {
     int64_t tile = g_eval_sort_tile > 0 ? g_eval_sort_tile : kEvalSortTile;
     if (ceil_div(n, tile) > kEvalMaxTiles) tile = ceil_div(ceil_div(n, kEvalMaxTiles), kBlock) * kBlock;
@@ -421,18 +344,10 @@ extern "C" int32_t gorse_fm_set_test(gorse_fm *h, int64_t n, int32_t width, cons
         if (indices[e] < 0 || indices[e] >= h->nf)
             return fail(GORSE_ERR_RANGE, "feature index %d at position %lld out of range [0,%lld)", indices[e], (long long)e,
                         (long long)h->nf);
-    if (h->n_fields > 0) {
-        if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
-        for (int k = 0; k < h->n_fields; k++)
-            if (!emb[k]) return fail(GORSE_ERR_INVALID, "emb[%d] is NULL", k);
-    }
-    // a split larger than the device's memory is refused before anything is allocated
+    GORSE_TRY(fm::check_emb(h, emb));
     double bytes = (double)ne * 8 + (double)n * 12;
     for (int k = 0; k < h->n_fields; k++) bytes += (double)n * h->fld[k].D * 2;
-    size_t mem_free = 0, mem_total = 0;
-    GORSE_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
-    if (bytes > (double)mem_total)
-        return fail(GORSE_ERR_NOMEM, "a test split of %.3g bytes does not fit the device's %zu", bytes, mem_total);
+    GORSE_TRY(fm::check_fits(bytes, "test split"));
     // built beside the resident one, which stays until the new one is complete
     std::unique_ptr<fm::TestSplit> t(new (std::nothrow) fm::TestSplit());
     if (!t) return fail(GORSE_ERR_NOMEM, "out of host memory");
@@ -446,8 +361,8 @@ extern "C" int32_t gorse_fm_set_test(gorse_fm *h, int64_t n, int32_t width, cons
             std::copy(indices + src, indices + src + width, pi.begin() + r * width);
             std::copy(values + src, values + src + width, pv.begin() + r * width);
         }
-        GORSE_TRY(fm::put(t->idx, pi.data(), (size_t)ne));
-        GORSE_TRY(fm::put(t->val, pv.data(), (size_t)ne));
+        GORSE_TRY(fm::upload(t->idx, pi.data(), (size_t)ne));
+        GORSE_TRY(fm::upload(t->val, pv.data(), (size_t)ne));
     }
     // the embedding rows gathered through a bounded staging buffer
     for (int k = 0; k < h->n_fields; k++) {
@@ -480,71 +395,23 @@ extern "C" int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const vola
     const int64_t n = t.n, n_pos = t.n_pos;
 
     // slices and launch rounds: built once per (split, batch size, rows of a round)
-    int maxD = 0;
-    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
-    const int64_t row_floats = (int64_t)maxD + 2 * h->d + 2;
-    const int64_t R = std::max<int64_t>(batch_size,
-                                        fm::g_eval_round_rows > 0 ? fm::g_eval_round_rows
-                                                                  : fm::kEvalRoundBytes / (row_floats * (int64_t)sizeof(float)));
+    const int maxD = fm::max_emb_dim(h);
+    const int64_t R = fm::round_rows_for(maxD, h->d, batch_size, fm::g_eval_round_rows);
     if (t.plan_bs != batch_size || t.plan_rows != R) {
-        fm::EvalSlices sl;
-        fm::eval_slices(n_pos, n - n_pos, batch_size, R, sl);
+        const int64_t sides[3] = {0, n_pos, n};
+        fm::SlicePlan plan;
+        fm::plan_slices(sides, 2, nullptr, batch_size, R, plan);
         GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
         t.plan_bs = 0;
-        GORSE_TRY(fm::put(t.desc, sl.desc.data(), sl.desc.size()));
-        t.round_begin = std::move(sl.round_begin);
-        t.n_slices = sl.n_slices, t.max_round = sl.max_round;
+        GORSE_TRY(fm::upload_plan(t.plan, plan, n));
         t.plan_bs = batch_size, t.plan_rows = R;
     }
     GORSE_TRY(h->e_logit.ensure((size_t)n));
-    if (h->n_fields > 0) {
-        GORSE_TRY(h->e_vx.ensure((size_t)t.max_round * h->d));
-        GORSE_TRY(h->e_h.ensure((size_t)t.max_round * h->d));
-        GORSE_TRY(h->e_s.ensure((size_t)t.max_round * maxD));
-        GORSE_TRY(h->e_rmax.ensure((size_t)t.max_round));
-        GORSE_TRY(h->e_rsum.ensure((size_t)t.max_round));
-    }
-    GORSE_TRY(fm::ensure_events(h));
+    if (h->n_fields > 0) GORSE_TRY(h->rs.ensure(t.plan.max_round, h->d, maxD));
+    GORSE_TRY(fm::ensure_events(h->e_ev));
 
-    const int64_t n_rounds = (int64_t)t.round_begin.size() - 1;
-    const int32_t *v_row = t.desc.p, *v_row0 = v_row + n, *v_len = v_row0 + n;
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[0], h->s));
-    for (int64_t k = 0; k < n_rounds; k++) {
-        if (cancel && *cancel) {
-            GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
-            return fail(GORSE_ERR_CANCELLED, "cancelled");
-        }
-        const int64_t r0 = t.round_begin[(size_t)k], nr = t.round_begin[(size_t)k + 1] - r0;
-        fm::EvalFwdArgs f{};
-        f.idx = t.idx.p, f.val = t.val.p;
-        f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
-        f.row0 = r0, f.nrows = nr, f.width = t.width, f.d = h->d;
-        f.logit = h->e_logit.p + r0, f.vx = h->e_vx.p;
-        if (h->n_fields == 0) {
-            GORSE_TRY(fm::launch_eval_forward<false>(h, f));
-            continue;
-        }
-        GORSE_TRY(fm::launch_eval_forward<true>(h, f));
-        const fm::SliceRows rows{v_row + r0, v_row0 + r0, v_len + r0};
-        const unsigned grid = fm::row_grid(nr);
-        for (int e = 0; e < h->n_fields; e++) {
-            const fm::Field &F = h->fld[e];
-            fm::AttArgs a{};
-            a.x = t.emb[e].p;
-            a.H = F.p.p + F.off[0], a.Wa = F.p.p + F.off[1], a.ba = F.p.p + F.off[2], a.We = F.p.p + F.off[3], a.be = F.p.p + F.off[4];
-            a.nrows = nr, a.D = F.D, a.d = h->d;
-            a.h = h->e_h.p, a.s = h->e_s.p, a.rmax = h->e_rmax.p, a.rsum = h->e_rsum.p;
-            a.vx = h->e_vx.p, a.logit = h->e_logit.p + r0;
-            fm::att_score_eval_kernel<<<dim3(grid), dim3(fm::kBlock), 0, h->s>>>(a, rows);
-            fm::att_exp_eval_kernel<<<dim3(grid), dim3(fm::kBlock), 0, h->s>>>(a, rows);
-            fm::att_enc_eval_kernel<<<dim3(grid), dim3(fm::kBlock), 0, h->s>>>(a, rows);
-            GORSE_HIP_CHECK(hipGetLastError());
-        }
-    }
-    if (cancel && *cancel) {
-        GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
-        return fail(GORSE_ERR_CANCELLED, "cancelled");
-    }
+    GORSE_TRY(fm::score_rounds(h, t.plan, fm::PaddedRows{t.idx.p, t.val.p, 0, t.width}, t.emb, cancel, h->rs, h->e_logit.p));
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[1], h->s));
     GORSE_TRY(fm::enqueue_metrics(h, n_pos, n - n_pos));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
@@ -554,7 +421,7 @@ extern "C" int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const vola
         GORSE_HIP_CHECK(hipMemcpy(tmp.data(), h->e_logit.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < n; r++) logits_out[t.order[(size_t)r]] = tmp[(size_t)r];
     }
-    h->ev_rows = n, h->ev_slices = t.n_slices, h->ev_rounds = n_rounds;
+    h->ev_rows = n, h->ev_slices = t.plan.n_slices, h->ev_rounds = t.plan.rounds();
     return GORSE_OK;
 }
 
@@ -583,7 +450,7 @@ extern "C" int32_t gorse_hip_test_fm_auc(gorse_fm *h, const float *pos, int64_t 
     GORSE_TRY(h->e_logit.ensure((size_t)(n_pos + n_neg)));
     if (n_pos) GORSE_HIP_CHECK(hipMemcpy(h->e_logit.p, pos, (size_t)n_pos * sizeof(float), hipMemcpyHostToDevice));
     if (n_neg) GORSE_HIP_CHECK(hipMemcpy(h->e_logit.p + n_pos, neg, (size_t)n_neg * sizeof(float), hipMemcpyHostToDevice));
-    GORSE_TRY(fm::ensure_events(h));
+    GORSE_TRY(fm::ensure_events(h->e_ev));
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[0], h->s));
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[1], h->s));
     GORSE_TRY(fm::enqueue_metrics(h, n_pos, n_neg));

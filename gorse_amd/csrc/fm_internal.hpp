@@ -1,12 +1,16 @@
-// fm_internal.hpp -- what fm.hip (training, batch scoring) and fm_rank.hip (ranking from a resident item catalogue) share: the
-// handle, the per-entry body of the factorization machine's forward pass, and the bodies of the attention branch's three
-// forward kernels.  The bodies are written once and instantiated by both files' kernels, so the scores of the two agree in
-// every bit by construction.
+// fm_internal.hpp -- what the factorization machine's sources share.  fm.hip trains and scores batches handed over by the host;
+// fm_rank.hip and fm_eval.hip score rows that stay on the device (an item catalogue, a test split) through the one resident
+// path of fm_resident.hip.  In here: the handle; the ONE forward kernel (a template over the lane shape, where a row's entries
+// come from and what is written) with the helper that picks the lane shape; the attention branch's three forward kernels (a
+// template over where a launch's rows come from) with the function that launches them for a field; and the small host helpers
+// every entry point uses.  Each is written once, so the scores of all routes agree in every bit by construction.
 #pragma once
 #include <memory>
+#include <type_traits>
 
 #include "common.hpp"
 #include "cf_device.hpp"
+#include "fm_eval_plan.hpp"
 
 namespace gorse {
 namespace fm {
@@ -44,9 +48,17 @@ struct Catalogue {
     DevBuf<uint16_t> emb[kMaxFields];
 };
 
+// a SlicePlan (fm_eval_plan.hpp) whose per-row descriptors are on the device
+struct RoundPlan {
+    DevBuf<int32_t> desc;  // segment | item | slice row0 | slice length, n entries each
+    std::vector<int64_t> round_begin;
+    int64_t n = 0, n_slices = 0, max_round = 0;
+    int64_t rounds() const { return (int64_t)round_begin.size() - 1; }
+};
+
 // The resident test split of gorse_fm_evaluate (gorse_fm_set_test): the rows in EvaluateClassification's order (the n_pos
 // positives first, then the others, each side in dataset order), their padded index / value matrices and one n x D bf16 table per
-// field, gathered once.  Replaced as a whole.  The slice descriptors belong to one (batch size, round rows).
+// field, gathered once.  Replaced as a whole.  The plan belongs to one (batch size, round rows).
 struct TestSplit {
     int64_t n = 0, n_pos = 0;
     int width = 0;
@@ -56,9 +68,21 @@ struct TestSplit {
     DevBuf<uint16_t> emb[kMaxFields];
     int32_t plan_bs = 0;
     int64_t plan_rows = 0;
-    DevBuf<int32_t> desc;  // row | slice row0 | slice length, n entries each
-    std::vector<int64_t> round_begin;
-    int64_t n_slices = 0, max_round = 0;
+    RoundPlan plan;
+};
+
+// What one launch round of score_rounds works in (the model has fields): vx and h (rows x d), s (rows x maxD), the Softmax's
+// maxima and sums.  One instance per handle: gorse_fm_rank_users and gorse_fm_evaluate run on the handle's one stream and
+// drain it before they return, and every round writes each of these before it reads it.
+struct RoundScratch {
+    DevBuf<float> vx, h, s, rmax, rsum;
+    int32_t ensure(int64_t rows, int d, int maxD) {
+        GORSE_TRY(vx.ensure((size_t)rows * d));
+        GORSE_TRY(h.ensure((size_t)rows * d));
+        GORSE_TRY(s.ensure((size_t)rows * maxD));
+        GORSE_TRY(rmax.ensure((size_t)rows));
+        return rsum.ensure((size_t)rows);
+    }
 };
 }  // namespace fm
 }  // namespace gorse
@@ -96,20 +120,23 @@ struct gorse_fm {
     int64_t dense_blocks = 0;  // blocks of the longest dense tensor
     gorse::DevBuf<float> a_rmax, a_rsum, a_sumdx, a_gx, a_dpre, a_esum, a_vxe, a_logit;
     gorse::DevBuf<uint16_t> p_x;
-    gorse::DevBuf<float> p_zero, p_gs, p_loss, p_vx;
-    // ranking from a resident catalogue (fm_rank.hip): buffers of its own, nothing here is read by training or by predict
+    gorse::DevBuf<float> p_vx;
+    // scoring resident rows (fm_resident.hip): the round scratch both calls below work in.  Nothing from here on is read or
+    // written by training or by gorse_fm_predict*, and the two calls touch none of the buffers above but the parameters.
+    gorse::fm::RoundScratch rs;
+    // ranking from a resident catalogue (fm_rank.hip)
     std::unique_ptr<gorse::fm::Catalogue> cat;
-    gorse::DevBuf<int64_t> r_uptr, r_cptr;          // the call's user CSR pointer and candidate pointer
-    gorse::DevBuf<int32_t> r_uidx, r_ulead, r_desc;  // r_desc: user | item | slice row0 | slice length, each one entry per row
-    gorse::DevBuf<float> r_uval;
-    gorse::DevBuf<float> r_vx, r_h, r_s, r_rmax, r_rsum, r_scores;
+    gorse::DevBuf<int64_t> r_uptr, r_cptr;  // the call's user CSR pointer and candidate pointer
+    gorse::DevBuf<int32_t> r_uidx, r_ulead;
+    gorse::DevBuf<float> r_uval, r_scores;
+    gorse::fm::RoundPlan r_plan;            // the call's slices: segment = user, item = candidate
     gorse::DevBuf<int32_t> r_order;
     hipEvent_t r_ev[2] = {nullptr, nullptr};  // timing events of gorse_fm_rank_stats, created by the first rank call
     int64_t rk_rows = 0, rk_slices = 0, rk_rounds = 0, rk_host_sorted = 0;
     double rk_ms = 0.0;
-    // evaluation from a resident test split (fm_eval.hip): again buffers of its own
+    // evaluation from a resident test split (fm_eval.hip)
     std::unique_ptr<gorse::fm::TestSplit> test;
-    gorse::DevBuf<float> e_vx, e_h, e_s, e_rmax, e_rsum, e_logit;
+    gorse::DevBuf<float> e_logit;
     gorse::DevBuf<uint32_t> e_key[2], e_hist, e_cnt;  // the sort's two key arrays, its tile x digit counts, negatives below each positive
     gorse::DevBuf<uint64_t> e_acc;                    // the tallies, pairs_less and (as bits) auc_sum
     hipEvent_t e_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | scored | sorted and counted | chain done
@@ -128,6 +155,21 @@ inline int lanes_for(int d) {
     int g = 8;
     while (g < d && g < 64) g *= 2;
     return g;
+}
+
+// fn(G, NF) with d's lane shape as compile-time constants (std::integral_constant): the one statement of that mapping
+template <class F>
+inline void with_lanes(int d, F &&fn) {
+    using std::integral_constant;
+    const int G = lanes_for(d);
+    switch (G) {
+        case 8: fn(integral_constant<int, 8>{}, integral_constant<int, 1>{}); break;
+        case 16: fn(integral_constant<int, 16>{}, integral_constant<int, 1>{}); break;
+        case 32: fn(integral_constant<int, 32>{}, integral_constant<int, 1>{}); break;
+        default:
+            if (d > 64) fn(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+            else fn(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    }
 }
 
 inline unsigned row_grid(int64_t nrows) { return (unsigned)ceil_div(nrows, kBlock / 64); }
@@ -174,12 +216,151 @@ __device__ __forceinline__ float fm_logit(const float (&vx)[NF], const float (&s
     return (lin + 0.5f * part) + B[0];
 }
 
-// ---- the item-embedding branch: forward bodies -----------------------------------------------------------------------------
+// ---- the forward kernel ---------------------------------------------------------------------------------------------------
+// Where a row's entries come from.  Both sources hand the nonzero entries to fm_entry one after the other; zero values (the
+// padding: index 0, value 0) are skipped, they would add only signed zeros.  round() points a source at the launch round that
+// begins at row r0 of a plan's per-row segment and item descriptors.
+
+// row0 + b of a padded n x width index / value matrix (training, gorse_fm_predict*, the resident test split)
+struct PaddedRows {
+    const int32_t *idx;
+    const float *val;
+    int64_t row0;
+    int width;
+    void round(const int32_t *, const int32_t *, int64_t r0) { row0 = r0; }
+    template <int G, int NF>
+    __device__ __forceinline__ void walk(int64_t b, const float *V, const float *W, int d, int lane, float (&vx)[NF],
+                                         float (&sq)[NF], float &lin) const {
+        const int64_t r = row0 + b;
+        const int32_t *ri = idx + r * width;
+        const float *rv = val + r * width;
+        for (int j = 0; j < width; j++) {
+            const float x = rv[j];
+            if (x == 0.0f) continue;
+            fm_entry<G, NF>(V, W, d, lane, ri[j], x, vx, sq, lin);
+        }
+    }
+};
+
+__device__ __forceinline__ int64_t first_lane64(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The row gorse_fm_rank_users composes in BatchPredict's order (fm.go:183-206): user lead | item lead | user rest | item rest,
+// through the row's (user, item) descriptor into the call's user CSR and the resident catalogue.
+struct ComposedRows {
+    const int64_t *uptr;  // the call's users: CSR pointer, entries, leading entries per user
+    const int32_t *uidx;
+    const float *uval;
+    const int32_t *ulead;
+    const int64_t *iptr;  // the catalogue
+    const int32_t *iidx;
+    const float *ival;
+    const int32_t *ilead;
+    const int32_t *user, *item;  // per row of the round
+    void round(const int32_t *seg, const int32_t *it, int64_t r0) { user = seg + r0, item = it + r0; }
+    // entries [j0, j1) of a CSR in order.  UNIFORM: the range is the same in every lane of the wave (the caller checked), so
+    // index and value come through scalar loads.
+    template <int G, int NF, bool UNIFORM>
+    __device__ __forceinline__ static void span(const int32_t *idx, const float *val, int64_t j0, int64_t j1, const float *V,
+                                                const float *W, int d, int lane, float (&vx)[NF], float (&sq)[NF], float &lin) {
+        if (UNIFORM) {
+            j0 = first_lane64(j0);
+            j1 = first_lane64(j1);
+        }
+        for (int64_t j = j0; j < j1; j++) {
+            const float x = val[j];
+            if (x == 0.0f) continue;
+            fm_entry<G, NF>(V, W, d, lane, idx[j], x, vx, sq, lin);
+        }
+    }
+    template <int G, int NF>
+    __device__ __forceinline__ void walk(int64_t b, const float *V, const float *W, int d, int lane, float (&vx)[NF],
+                                         float (&sq)[NF], float &lin) const {
+        const int32_t u = user[b], c = item[b];
+        const int64_t u0 = uptr[u], u1 = uptr[u + 1], um = u0 + ulead[u];
+        const int64_t i0 = iptr[c], i1 = iptr[c + 1], im = i0 + ilead[c];
+        // a user's rows are consecutive: most waves hold one user only
+        const bool one_user = __all(u == __builtin_amdgcn_readfirstlane(u));
+        if (one_user)
+            span<G, NF, true>(uidx, uval, u0, um, V, W, d, lane, vx, sq, lin);
+        else
+            span<G, NF, false>(uidx, uval, u0, um, V, W, d, lane, vx, sq, lin);
+        span<G, NF, false>(iidx, ival, i0, im, V, W, d, lane, vx, sq, lin);
+        if (one_user)
+            span<G, NF, true>(uidx, uval, um, u1, V, W, d, lane, vx, sq, lin);
+        else
+            span<G, NF, false>(uidx, uval, um, u1, V, W, d, lane, vx, sq, lin);
+        span<G, NF, false>(iidx, ival, im, i1, V, W, d, lane, vx, sq, lin);
+    }
+};
+
+// what a forward launch writes: the logit; the logit and vx (scoring a model with fields); or what a training step needs
+enum { kLogit = 0, kLogitVx = 1, kTrain = 2 };
+
+template <class Src>
+struct FwdArgs {
+    Src src;
+    const float *V, *W, *B;
+    int64_t nrows;
+    int d;
+    float *out;          // nrows logits (kTrain: NULL, or where the embedding branch wants the FM's logit)
+    float *vx;           // nrows x d: vx_f = sum_j V[idx_j, f] x_j (kLogitVx, kTrain)
+    const float *tgt;    // kTrain: the launch's rows' targets
+    float inv_n;         // kTrain: 1 / rows of the batch
+    float *gs, *loss;    // kTrain: per sample g_b and loss_b
+};
+
+// one sample per G-lane group: the row's chains, the DPP-reduced pairwise term, the logit in the group's first lane
+template <int G, int NF, class Src, int OUT>
+__global__ __launch_bounds__(kBlock) void fm_forward_kernel(FwdArgs<Src> a) {
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t b = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
+    if (b >= a.nrows) return;  // whole groups leave together
+    float vx[NF], sq[NF];
+#pragma unroll
+    for (int k = 0; k < NF; k++) vx[k] = sq[k] = 0.0f;
+    float lin = 0.0f;
+    a.src.template walk<G, NF>(b, a.V, a.W, a.d, lane, vx, sq, lin);
+    const float logit = fm_logit<G, NF>(vx, sq, lin, a.B);
+    if (OUT != kLogit) {
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+            const int f = lane + k * G;
+            if (f < a.d) a.vx[b * a.d + f] = vx[k];
+        }
+    }
+    if (lane != 0) return;
+    if (OUT != kTrain) {
+        a.out[b] = logit;
+        return;
+    }
+    // BCEWithLogits (common/nn/functions.go:218-243) with y = (t + 1) / 2
+    const float y = (a.tgt[b] + 1.0f) * 0.5f;
+    a.loss[b] = fmaxf(logit, 0.0f) - logit * y + logf(1.0f + expf(-fabsf(logit)));
+    a.gs[b] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
+    if (a.out) a.out[b] = logit;  // with embedding fields att_loss_kernel forms loss and g again from the full logit
+}
+
+template <int OUT, class Src>
+inline int32_t launch_forward(hipStream_t s, const FwdArgs<Src> &a) {
+    const int64_t grid = ceil_div(a.nrows * lanes_for(a.d), kBlock);
+    if (grid == 0) return GORSE_OK;
+    with_lanes(a.d, [&](auto G, auto NF) {
+        fm_forward_kernel<decltype(G)::value, decltype(NF)::value, Src, OUT><<<dim3((unsigned)grid), dim3(kBlock), 0, s>>>(a);
+    });
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+// ---- the item-embedding branch: forward kernels ----------------------------------------------------------------------------
 
 constexpr int kFC = 16;  // factors per accumulator chunk
 
 struct AttArgs {
-    const uint16_t *x;  // the batch rows' embeddings, nrows x D bf16 (ranking: the field's item table)
+    const uint16_t *x;  // the batch rows' embeddings, nrows x D bf16 (SliceRows: the field's resident table)
     const float *H, *Wa, *ba, *We, *be;
     int64_t nrows;
     int D, d;
@@ -200,8 +381,9 @@ struct AttArgs {
 };
 
 // Where a launch's rows come from.  BatchRows: the launch is one batch, row r's embedding is row r of x, and the Softmax's
-// maxima and sums are indexed over the whole launch.  SliceRows (ranking): the launch holds many slices, each a batch of its
-// own; row r's embedding is row item[r] of the field's table, read in place, and r carries its slice's first row and length.
+// maxima and sums are indexed over the whole launch.  SliceRows (a launch round of score_rounds): the launch holds many
+// slices, each a batch of its own; row r's embedding is row item[r] of the field's resident table, read in place, and r
+// carries its slice's first row and length.
 struct BatchRows {
     __device__ __forceinline__ const uint16_t *x(const AttArgs &a, int64_t r) const { return a.x + r * a.D; }
     // n = the slice's rows, base = its first row, returns (local row x D) % n
@@ -265,7 +447,7 @@ __device__ __forceinline__ float reduce_pick(float (&acc)[kFC], int lane) {
 
 // pre, h = relu(pre), s = h H and each row's maximum of s
 template <class Rows>
-__device__ __forceinline__ void att_score_body(const AttArgs &a, const Rows &rows) {
+__global__ __launch_bounds__(kBlock) void att_score_kernel(AttArgs a, Rows rows) {
     __shared__ float sh[kBlock / 64][kMaxFactors];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
@@ -308,7 +490,7 @@ __device__ __forceinline__ void att_score_body(const AttArgs &a, const Rows &row
 
 // e = exp(s - max[(r D + c) % n]) through fp64 (float32(math.Exp(float64(.))), tensor.go:414-419) and each row's sum of e
 template <class Rows>
-__device__ __forceinline__ void att_exp_body(const AttArgs &a, const Rows &rows) {
+__global__ __launch_bounds__(kBlock) void att_exp_kernel(AttArgs a, Rows rows) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (r >= a.nrows) return;
@@ -330,7 +512,7 @@ __device__ __forceinline__ void att_exp_body(const AttArgs &a, const Rows &rows)
 
 // a = e / sum[(r D + c) % n], z = a * x, enc = z We + be, logit += sum_f vx_f enc_f
 template <class Rows>
-__device__ __forceinline__ void att_enc_body(const AttArgs &a, const Rows &rows) {
+__global__ __launch_bounds__(kBlock) void att_enc_kernel(AttArgs a, Rows rows) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (r >= a.nrows) return;
@@ -370,6 +552,81 @@ __device__ __forceinline__ void att_enc_body(const AttArgs &a, const Rows &rows)
     }
     if (lane == 0) a.logit[r] = a.logit[r] + contrib;
 }
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+// field k's parameters and shape; the caller adds the rows and the buffers
+inline AttArgs field_args(const gorse_fm *h, int k) {
+    const Field &F = h->fld[k];
+    AttArgs a{};
+    a.H = F.p.p + F.off[0], a.Wa = F.p.p + F.off[1], a.ba = F.p.p + F.off[2], a.We = F.p.p + F.off[3], a.be = F.p.p + F.off[4];
+    a.D = F.D, a.d = h->d;
+    return a;
+}
+
+// the three forward launches of one field on the launch's rows
+template <class Rows>
+inline int32_t branch_forward(hipStream_t s, const AttArgs &a, const Rows &rows) {
+    const unsigned grid = row_grid(a.nrows);
+    att_score_kernel<<<dim3(grid), dim3(kBlock), 0, s>>>(a, rows);
+    att_exp_kernel<<<dim3(grid), dim3(kBlock), 0, s>>>(a, rows);
+    att_enc_kernel<<<dim3(grid), dim3(kBlock), 0, s>>>(a, rows);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
+inline int max_emb_dim(const gorse_fm *h) {
+    int maxD = 0;
+    for (int k = 0; k < h->n_fields; k++) maxD = std::max(maxD, h->fld[k].D);
+    return maxD;
+}
+
+// one table per field, where the model has fields
+inline int32_t check_emb(const gorse_fm *h, const uint16_t *const *emb) {
+    if (h->n_fields == 0) return GORSE_OK;
+    if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
+    for (int k = 0; k < h->n_fields; k++)
+        if (!emb[k]) return fail(GORSE_ERR_INVALID, "emb[%d] is NULL", k);
+    return GORSE_OK;
+}
+
+// what is to become resident is refused before anything is allocated where it is larger than the device's memory
+inline int32_t check_fits(double bytes, const char *what) {
+    size_t mem_free = 0, mem_total = 0;
+    GORSE_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+    if (bytes > (double)mem_total) return fail(GORSE_ERR_NOMEM, "a %s of %.3g bytes does not fit the device's %zu", what, bytes, mem_total);
+    return GORSE_OK;
+}
+
+template <typename T>
+inline int32_t upload(DevBuf<T> &dst, const T *src, size_t n) {
+    GORSE_TRY(dst.ensure(n));
+    if (n) GORSE_HIP_CHECK(hipMemcpy(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return GORSE_OK;
+}
+
+inline int32_t upload_plan(RoundPlan &dst, SlicePlan &src, int64_t n) {
+    GORSE_TRY(upload(dst.desc, src.desc.data(), src.desc.size()));
+    dst.round_begin = std::move(src.round_begin);
+    dst.n = n, dst.n_slices = src.n_slices, dst.max_round = src.max_round;
+    return GORSE_OK;
+}
+
+// timing events created by the first call that records them
+template <size_t N>
+inline int32_t ensure_events(hipEvent_t (&ev)[N]) {
+    for (auto &e : ev)
+        if (!e) GORSE_HIP_CHECK(hipEventCreate(&e));
+    return GORSE_OK;
+}
+
+// fm_resident.hip: the rows of every round of `plan` scored into logit (plan.n entries): src's entries through the forward
+// kernel and, where the model has fields, the branch on the rows' embeddings in tables[field] (row plan item[r]), in `rs`
+// (ensured by the caller for plan.max_round rows).  Enqueued on the handle's stream; the cancel flag is read before every round
+// and once after the last.
+template <class Src>
+int32_t score_rounds(gorse_fm *h, const RoundPlan &plan, Src src, const DevBuf<uint16_t> *tables, const volatile int32_t *cancel,
+                     RoundScratch &rs, float *logit);
 
 }  // namespace fm
 }  // namespace gorse

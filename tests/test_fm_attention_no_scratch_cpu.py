@@ -11,13 +11,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-KERNELS = ("gorse::fm::att_score_kernel", "gorse::fm::att_exp_kernel", "gorse::fm::att_enc_kernel", "gorse::fm::att_loss_kernel",
+SHAPES = ((8, 1), (16, 1), (32, 1), (64, 1), (64, 2))
+KERNELS = ("gorse::fm::att_score_kernel<gorse::fm::BatchRows>", "gorse::fm::att_exp_kernel<gorse::fm::BatchRows>",
+           "gorse::fm::att_enc_kernel<gorse::fm::BatchRows>", "gorse::fm::att_loss_kernel",
            "gorse::fm::att_bwd_gx_kernel", "gorse::fm::att_bwd_ds_kernel", "gorse::fm::att_grad_kernel",
-           "gorse::fm::fm_dense_opt_kernel<true>", "gorse::fm::fm_dense_opt_kernel<false>",
-           # scoring with fields runs the training instantiations of the forward kernel (they write vx)
-           "gorse::fm::fm_forward_kernel<8, 1, true>", "gorse::fm::fm_forward_kernel<16, 1, true>",
-           "gorse::fm::fm_forward_kernel<32, 1, true>", "gorse::fm::fm_forward_kernel<64, 1, true>",
-           "gorse::fm::fm_forward_kernel<64, 2, true>")
+           "gorse::fm::fm_dense_opt_kernel<true>", "gorse::fm::fm_dense_opt_kernel<false>") + tuple(
+    # with fields, scoring runs the logit + vx form (1) of the forward kernel and training its training form (2)
+    "gorse::fm::fm_forward_kernel<%d, %d, gorse::fm::PaddedRows, %d>" % (g, nf, out) for g, nf in SHAPES for out in (1, 2))
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")

@@ -1,6 +1,7 @@
-"""gorse_fm_set_test / gorse_fm_evaluate without a device: the register budget of every kernel of fm_eval.hip on the gfx950
-assembly, the partition and slice-descriptor header in a stand-alone C++ program under AddressSanitizer and UBSan, the numpy
-restatement the GPU test compares with (fm_eval_ref) against the host library's metrics, and the new symbols."""
+"""gorse_fm_set_test / gorse_fm_evaluate without a device: the register budget of every kernel of fm_eval.hip, and of what
+score_rounds launches for it from fm_resident.hip, on the gfx950 assembly, the partition and slice-planner header (the test
+split's two sides and gorse_fm_rank_users' candidate lists) in a stand-alone C++ program under AddressSanitizer and UBSan, the
+numpy restatement the GPU test compares with (fm_eval_ref) against the host library's metrics, and the new symbols."""
 import os
 import re
 import shutil
@@ -15,26 +16,33 @@ import fm_eval_ref as E
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
-KERNELS = ("gorse::fm::att_score_eval_kernel", "gorse::fm::att_exp_eval_kernel", "gorse::fm::att_enc_eval_kernel",
-           "gorse::fm::fm_eval_keys_kernel", "gorse::fm::fm_eval_sort_count_kernel", "gorse::fm::fm_eval_sort_scan_kernel",
-           "gorse::fm::fm_eval_sort_scatter_kernel", "gorse::fm::fm_eval_count_kernel", "gorse::fm::fm_eval_chain_kernel") + tuple(
-    "gorse::fm::fm_eval_forward_kernel<%d, %d, %s>" % (g, nf, vx)
-    for g, nf in ((8, 1), (16, 1), (32, 1), (64, 1), (64, 2)) for vx in ("false", "true"))
+KERNELS = {
+    "fm_eval.hip": ("gorse::fm::fm_eval_keys_kernel", "gorse::fm::fm_eval_sort_count_kernel", "gorse::fm::fm_eval_sort_scan_kernel",
+                    "gorse::fm::fm_eval_sort_scatter_kernel", "gorse::fm::fm_eval_count_kernel", "gorse::fm::fm_eval_chain_kernel"),
+    # scoring: the forward kernel over the split's padded rows and the branch's kernels over slices (test_fm_rank_no_scratch_cpu.py
+    # names every kernel of this file)
+    "fm_resident.hip": ("gorse::fm::att_score_kernel<gorse::fm::SliceRows>", "gorse::fm::att_exp_kernel<gorse::fm::SliceRows>",
+                        "gorse::fm::att_enc_kernel<gorse::fm::SliceRows>") + tuple(
+        "gorse::fm::fm_forward_kernel<%d, %d, gorse::fm::PaddedRows, %d>" % (g, nf, out)
+        for g, nf in ((8, 1), (16, 1), (32, 1), (64, 1), (64, 2)) for out in (0, 1)),
+}
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_no_evaluate_kernel_spills_or_scratch():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa_census.py"),
-                          os.path.join(ROOT, "gorse_amd", "csrc", "fm_eval.hip")], capture_output=True, text=True, check=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        m = re.match(r"^(?:void )?(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+spills: vgpr (\d+) sgpr (\d+)\s+scratch (\d+) B", line)
-        if m:
-            seen[m.group(1)] = tuple(int(m.group(i)) for i in (5, 6, 7))
-    for name in KERNELS:
-        assert name in seen, (name, sorted(seen))
-        assert seen[name] == (0, 0, 0), (name, seen[name])
-    assert set(seen) == set(KERNELS), sorted(set(seen) - set(KERNELS))  # no kernel of the file goes unnamed
+    for src, kernels in KERNELS.items():
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa_census.py"),
+                              os.path.join(ROOT, "gorse_amd", "csrc", src)], capture_output=True, text=True, check=True).stdout
+        seen = {}
+        for line in out.splitlines():
+            m = re.match(r"^(?:void )?(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+spills: vgpr (\d+) sgpr (\d+)\s+scratch (\d+) B", line)
+            if m:
+                seen[m.group(1)] = tuple(int(m.group(i)) for i in (5, 6, 7))
+        for name in kernels:
+            assert name in seen, (name, sorted(seen))
+            assert seen[name] == (0, 0, 0), (name, seen[name])
+        if src == "fm_eval.hip":
+            assert set(seen) == set(kernels), sorted(set(seen) - set(kernels))  # no kernel of the file goes unnamed
 
 
 @pytest.mark.skipif(shutil.which("g++") is None and shutil.which("clang++") is None, reason="no host C++ compiler")

@@ -22,8 +22,8 @@ def test_no_fm_kernel_spills_or_scratch():
         if m:
             seen[m.group(1)] = tuple(int(m.group(i)) for i in (5, 6, 7))
     for name in ("gorse::fm::fm_opt_kernel<true>", "gorse::fm::fm_opt_kernel<false>", "gorse::fm::fm_accum_kernel<16, 1>",
-                 "gorse::fm::fm_accum_kernel<64, 2>", "gorse::fm::fm_forward_kernel<64, 2, true>",
-                 "gorse::fm::fm_forward_kernel<8, 1, false>"):
+                 "gorse::fm::fm_accum_kernel<64, 2>", "gorse::fm::fm_forward_kernel<64, 2, gorse::fm::PaddedRows, 2>",
+                 "gorse::fm::fm_forward_kernel<8, 1, gorse::fm::PaddedRows, 0>"):
         assert name in seen, (name, sorted(seen))
     for name, (vspill, sspill, scratch) in seen.items():
         assert vspill == 0 and sspill == 0 and scratch == 0, (name, vspill, sspill, scratch)
