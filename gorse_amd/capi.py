@@ -122,6 +122,8 @@ SIGNATURES = {
     "gorse_fm_set_test": (C.c_int32, [_vp, C.c_int64, C.c_int32, _i32p, _f32p, _f32p, C.POINTER(C.POINTER(C.c_uint16))]),
     "gorse_fm_evaluate": (C.c_int32, [_vp, C.c_int32, _i32p, _i64p, _f32p, _f32p]),
     "gorse_fm_evaluate_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p, _f64p]),
+    "gorse_fm_set_train_samples": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, _f32p, _i32p, C.c_int64, _i32p, _i32p, _f32p]),
+    "gorse_fm_set_test_samples": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, _f32p, _i32p, C.c_int64, _i32p, _i32p, _f32p]),
     "gorse_hip_test_set_exact_exp": (None, [C.c_int32]),
     "gorse_hip_test_set_variant": (None, [C.c_int32]),
     "gorse_hip_test_set_topk_path": (None, [C.c_int32]),
@@ -573,6 +575,40 @@ class FM:
         check(lib().gorse_fm_set_test(self.h, n, max(1, idx.shape[1]), _p(idx, _i32p), _p(val, _f32p), _p(tgt, _f32p),
                                       ptrs if embs else None))
         self._n_test = n
+
+    @staticmethod
+    def _samples(user_indptr, user_indices, user_values, user_lead, user, item, target):
+        uptr = _arr(user_indptr, np.int64).reshape(-1)
+        nu = uptr.size - 1
+        uidx, uval = _arr(user_indices, np.int32).reshape(-1), _arr(user_values, np.float32).reshape(-1)
+        if nu < 0 or uidx.size != uval.size:
+            raise GorseHipError(ERR_INVALID, "user_indptr holds n_users + 1 entries, user_indices and user_values one per entry")
+        # the library reads indptr[-1] entries: only a well-formed pointer array may be trusted with that
+        if nu > 0 and np.all(np.diff(uptr) >= 0) and uptr[0] == 0 and uidx.size < uptr[-1]:
+            raise GorseHipError(ERR_INVALID, "fewer entries than the pointer array names")
+        ul = _arr(user_lead, np.int32).reshape(-1) if user_lead is not None else None
+        if ul is not None and ul.size != nu:
+            raise GorseHipError(ERR_INVALID, "one lead per user")
+        us, it = _arr(user, np.int32).reshape(-1), _arr(item, np.int32).reshape(-1)
+        tgt = _arr(target, np.float32).reshape(-1)
+        if us.size != it.size or us.size != tgt.size:
+            raise GorseHipError(ERR_INVALID, "one user, one item and one target per sample")
+        keep = (uptr, uidx, uval, ul, us, it, tgt)
+        return keep, (max(nu, 0), _p(uptr, _i64p), _p(uidx, _i32p), _p(uval, _f32p), _p(ul, _i32p), us.size, _p(us, _i32p),
+                      _p(it, _i32p), _p(tgt, _f32p))
+
+    def set_train_samples(self, user_indptr, user_indices, user_values, user, item, target, user_lead=None):
+        """the training set in sample form: the users' feature rows as a CSR (as rank_users takes them) and per sample
+        (user, item, target); sample i is the row rank_users composes for user[i] and catalogue row item[i] (set_items), its
+        embeddings are the catalogue's.  Replaces a set_train set, and the other way round."""
+        keep, args = self._samples(user_indptr, user_indices, user_values, user_lead, user, item, target)
+        check(lib().gorse_fm_set_train_samples(self.h, *args))
+
+    def set_test_samples(self, user_indptr, user_indices, user_values, user, item, target, user_lead=None):
+        """the resident test split of evaluate in sample form (see set_train_samples).  No samples drops the split."""
+        keep, args = self._samples(user_indptr, user_indices, user_values, user_lead, user, item, target)
+        check(lib().gorse_fm_set_test_samples(self.h, *args))
+        self._n_test = args[5]
 
     def evaluate(self, batch_size, cancel=None, logits=False):
         """(counts, auc_sum) of the resident split, or (counts, auc_sum, logits) with the logits in the rows' given order.

@@ -16,116 +16,17 @@
 // Every floats.* call of the reference runs the AVX512 kernels of common/floats/src/floats_avx512.c: a 16-lane FMA body and
 // unfused 8-lane / scalar tails, and partitionAligned(.., 32) leaves the tail at the tensor's last len % 16 elements; the
 // optimizer kernel applies the same rule by element position (fmaf vs. mul then add; the library builds with -ffp-contract=off).
-#include "fm_internal.hpp"
+#include "fm_train.hpp"
 
 namespace gorse {
 namespace fm {
 
 constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kEps = 1e-8f;
 
-struct AccArgs {
-    const int32_t *uniq, *seg, *pos;  // the batch's slots: uniq[s] = feature, positions pos[seg[s] .. seg[s+1])
-    int64_t slot0, nslots;
-    const float *val;  // batch rows' values (row0 * width applied)
-    const float *V;
-    const float *gs, *loss, *vx;
-    int64_t nrows;
-    int width, d;
-    int64_t tag_hi;  // (step + 1) << 32
-    int64_t *tag;
-    float *gV, *gW, *gB, *cost;
-};
-
-// One wave per touched feature.  The wave's 64 / G groups take every (64 / G)-th position of the feature's list in order, each
-// group's lanes hold the row's factors; the groups' partial sums are then added in a fixed butterfly.  The last block instead
-// sums dB and the batch's loss over the samples (one thread per stride, then an LDS tree) and adds the mean to the epoch's cost.
+// One wave per touched feature over the batch's (feature, position) lists: fm_accum_body (fm_train.hpp) over PaddedEntries.
 template <int G, int NF>
 __global__ __launch_bounds__(kBlock) void fm_accum_kernel(AccArgs a) {
-    if (blockIdx.x == gridDim.x - 1) {
-        __shared__ float sg[kBlock], sl[kBlock];
-        float g = 0.0f, l = 0.0f;
-        for (int64_t b = threadIdx.x; b < a.nrows; b += kBlock) {
-            g += a.gs[b];
-            l += a.loss[b];
-        }
-        sg[threadIdx.x] = g;
-        sl[threadIdx.x] = l;
-        __syncthreads();
-        for (int o = kBlock / 2; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) {
-                sg[threadIdx.x] += sg[threadIdx.x + o];
-                sl[threadIdx.x] += sl[threadIdx.x + o];
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            a.gB[0] = sg[0];
-            a.cost[0] = a.cost[0] + sl[0] / (float)a.nrows;
-        }
-        return;
-    }
-    constexpr int NG = 64 / G;
-    const int64_t s = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 64;
-    if (s >= a.nslots) return;
-    const int lane = threadIdx.x & (G - 1);
-    const int grp = (threadIdx.x & 63) / G;
-    const int64_t gslot = a.slot0 + s;
-    const int32_t feat = a.uniq[gslot];
-    const int32_t beg = a.seg[gslot], end = a.seg[gslot + 1];
-    float vr[NF], acc[NF];
-#pragma unroll
-    for (int k = 0; k < NF; k++) {
-        const int f = lane + k * G;
-        vr[k] = f < a.d ? a.V[(int64_t)feat * a.d + f] : 0.0f;
-        acc[k] = 0.0f;
-    }
-    float accw = 0.0f;
-    constexpr int U = 4;  // positions whose loads are issued together; the sum still runs in position order
-    for (int q0 = beg + grp; q0 < end; q0 += U * NG) {
-        float gx[U], xx[U], x2[U];
-        int64_t bb[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int q = q0 + u * NG;
-            const int p = q < end ? a.pos[q] : 0;
-            const int64_t b = p / a.width;
-            const float x = q < end ? a.val[p] : 0.0f;
-            const float g = q < end ? a.gs[b] : 0.0f;
-            bb[u] = b;
-            xx[u] = x;
-            gx[u] = g;
-            x2[u] = x * x;
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (q0 + u * NG >= end) break;
-            accw += gx[u] * xx[u];
-#pragma unroll
-            for (int k = 0; k < NF; k++) {
-                const int f = lane + k * G;
-                if (f < a.d) {
-                    const float t = xx[u] * a.vx[bb[u] * a.d + f] - vr[k] * x2[u];
-                    acc[k] += gx[u] * t;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-#pragma unroll
-        for (int k = 0; k < NF; k++) acc[k] = acc[k] + __shfl_xor(acc[k], o, 64);
-        accw = accw + __shfl_xor(accw, o, 64);
-    }
-    if (grp != 0) return;
-#pragma unroll
-    for (int k = 0; k < NF; k++) {
-        const int f = lane + k * G;
-        if (f < a.d) a.gV[s * a.d + f] = acc[k];
-    }
-    if (lane == 0) {
-        a.gW[s] = accw;
-        a.tag[feat] = a.tag_hi | s;
-    }
+    fm_accum_body<G, NF>(a, PaddedEntries{a.pos, a.val, a.width});
 }
 
 struct OptArgs {  // tensor t = 0 (V), 1 (W), 2 (B); the kernel selects by constant index only (no private copy of the block)
@@ -278,35 +179,8 @@ __global__ __launch_bounds__(kBlock) void att_loss_kernel(LossArgs a) {
     a.gs[i] = (1.0f / (1.0f + expf(-logit)) - y) * a.inv_n;
 }
 
-// denc = g vx, dz = denc We^T, da = dz * x, gx = a * da and each row's sum of gx
-__global__ __launch_bounds__(kBlock) void att_bwd_gx_kernel(AttArgs a) {
-    __shared__ float sh[kBlock / 64][kMaxFactors];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + w;
-    const bool live = r < a.nrows;
-    for (int f = lane; f < kMaxFactors; f += 64) sh[w][f] = live && f < a.d ? a.gs[r] * a.vx[r * a.d + f] : 0.0f;
-    __syncthreads();
-    if (!live) return;
-    const bool vec = (a.d & 3) == 0;
-    const uint16_t *xr = a.x + r * a.D;
-    const float *ar = a.s + r * a.D;
-    float *gr = a.gx + r * a.D;
-    float sum = 0.0f;
-    for (int c = lane; c < a.D; c += 64) {
-        float dz = 0.0f;
-        for (int f0 = 0; f0 < a.d; f0 += kFC) {
-            float wv[kFC];
-            load_w16(a.We, c, a.d, f0, vec, wv);
-#pragma unroll
-            for (int k = 0; k < kFC; k++) dz = fmaf(sh[w][f0 + k], wv[k], dz);
-        }
-        const float g = ar[c] * (dz * bf16_f32(xr[c]));
-        gr[c] = g;
-        sum += g;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) a.sumdx[r] = sum;
-}
+// denc = g vx, dz = denc We^T, da = dz * x, gx = a * da and each row's sum of gx: att_bwd_gx_body (fm_train.hpp) over BatchRows
+__global__ __launch_bounds__(kBlock) void att_bwd_gx_kernel(AttArgs a) { att_bwd_gx_body(a, BatchRows{}); }
 
 // ds = gx - a * sumdx[(r D + c) % n], dh = ds H^T, dpre = (pre > 0) dh
 __global__ __launch_bounds__(kBlock) void att_bwd_ds_kernel(AttArgs a) {
@@ -340,63 +214,8 @@ __global__ __launch_bounds__(kBlock) void att_bwd_ds_kernel(AttArgs a) {
     }
 }
 
-// The parameter gradients that reduce over the batch: dWe = z^T denc, dWa = x^T dpre, dH = h^T ds, and the bias sums as one
-// more column (c = D) whose z and x are 1.  Block (column tile of 64, factor chunk of 16, row segment): wave w takes every
-// fourth row of the segment in ascending order, the four waves' sums are added in wave order, and the kGradSegs segment sums
-// are added in segment order by the optimizer pass: the order depends on the shapes alone, no atomics.
-__global__ __launch_bounds__(kBlock) void att_grad_kernel(AttArgs a) {
-    __shared__ float sh[kBlock / 64][kFC][64];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int c = blockIdx.x * 64 + lane;
-    const int f0 = blockIdx.y * kFC;
-    const int seg = blockIdx.z;
-    const int64_t rps = (a.nrows + kGradSegs - 1) / kGradSegs;
-    const int64_t r_lo = seg * rps, r_hi = r_lo + rps < a.nrows ? r_lo + rps : a.nrows;
-    float aWe[kFC], aWa[kFC], aH[kFC];
-#pragma unroll
-    for (int k = 0; k < kFC; k++) aWe[k] = aWa[k] = aH[k] = 0.0f;
-    for (int64_t r = r_lo + w; r < r_hi; r += kBlock / 64) {
-        float xv = 0.0f, zv = 0.0f, dsv = 0.0f;
-        if (c < a.D) {
-            xv = bf16_f32(a.x[r * a.D + c]);
-            zv = a.s[r * a.D + c] * xv;
-            dsv = a.gx[r * a.D + c];
-        } else if (c == a.D) {
-            xv = zv = 1.0f;
-        }
-        const float g = a.gs[r];
-#pragma unroll
-        for (int k = 0; k < kFC; k++) {
-            if (f0 + k < a.d) {
-                const int64_t o = r * a.d + f0 + k;
-                aWe[k] = fmaf(zv, g * a.vx[o], aWe[k]);
-                aWa[k] = fmaf(xv, a.dpre[o], aWa[k]);
-                aH[k] = fmaf(dsv, a.h[o], aH[k]);
-            }
-        }
-    }
-    const int64_t nH = (int64_t)a.d * a.D, nW = (int64_t)(a.D + 1) * a.d;
-    float *gH = a.gpart + seg * a.gstride, *gWa = gH + nH, *gWe = gWa + nW;
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        if (t) __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kFC; k++) sh[w][k][lane] = t == 0 ? aH[k] : t == 1 ? aWa[k] : aWe[k];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < kFC / (kBlock / 64); j++) {
-            const int k = w + j * (kBlock / 64);
-            const float v = ((sh[0][k][lane] + sh[1][k][lane]) + sh[2][k][lane]) + sh[3][k][lane];
-            if (f0 + k >= a.d) continue;
-            if (t == 0) {
-                if (c < a.D) gH[(int64_t)(f0 + k) * a.D + c] = v;
-            } else if (c <= a.D) {
-                (t == 1 ? gWa : gWe)[(int64_t)c * a.d + f0 + k] = v;
-            }
-        }
-    }
-}
+// the parameter gradients that reduce over the batch: att_grad_body (fm_train.hpp) over BatchRows
+__global__ __launch_bounds__(kBlock) void att_grad_kernel(AttArgs a) { att_grad_body(a, BatchRows{}); }
 
 // The dense step of the branch's tensors (blockIdx.y = tensor number in Parameters() order: per field H, Wa, ba, We, be), each
 // as its own tensor: the FMA body / unfused tail split lies at its own last len % 16 elements.  The descriptors are read
@@ -550,13 +369,17 @@ int32_t build_plan(gorse_fm *h, int32_t bs) {
     if (!uniq.empty()) GORSE_HIP_CHECK(hipMemcpy(h->uniq.p, uniq.data(), uniq.size() * 4, hipMemcpyHostToDevice));
     GORSE_HIP_CHECK(hipMemcpy(h->seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice));
     if (!pos.empty()) GORSE_HIP_CHECK(hipMemcpy(h->pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
-    GORSE_TRY(h->gV.ensure((size_t)std::max<int64_t>(1, h->max_slots) * h->d));
-    GORSE_TRY(h->gW.ensure((size_t)std::max<int64_t>(1, h->max_slots)));
-    GORSE_TRY(h->gs.ensure((size_t)bs));
-    GORSE_TRY(h->loss.ensure((size_t)bs));
-    GORSE_TRY(h->vx.ensure((size_t)bs * h->d));
     h->plan_bs = bs;
     return GORSE_OK;
+}
+
+// what a step works in whatever the source: the touched rows' gradient sums and the batch's g, loss and vx
+int32_t ensure_step(gorse_fm *h, int32_t bs, int64_t max_slots) {
+    GORSE_TRY(h->gV.ensure((size_t)std::max<int64_t>(1, max_slots) * h->d));
+    GORSE_TRY(h->gW.ensure((size_t)std::max<int64_t>(1, max_slots)));
+    GORSE_TRY(h->gs.ensure((size_t)bs));
+    GORSE_TRY(h->loss.ensure((size_t)bs));
+    return h->vx.ensure((size_t)bs * h->d);
 }
 
 // ---- the embedding branch: host side -----------------------------------------------------
@@ -599,14 +422,49 @@ AttArgs branch_args(gorse_fm *h, int k, const uint16_t *x, int64_t nrows, const 
     return a;
 }
 
-int32_t branch_backward(gorse_fm *h, const AttArgs &a) {
-    const unsigned grid = row_grid(a.nrows);
-    att_bwd_gx_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
-    att_bwd_ds_kernel<<<dim3(grid), dim3(kBlock), 0, h->s>>>(a);
-    att_grad_kernel<<<dim3((unsigned)ceil_div(a.D + 1, 64), (unsigned)ceil_div(a.d, kFC), kGradSegs), dim3(kBlock), 0, h->s>>>(a);
-    GORSE_HIP_CHECK(hipGetLastError());
-    return GORSE_OK;
-}
+// the training set of gorse_fm_set_train (+ gorse_fm_set_train_embeddings): padded rows, one embedding row per sample
+struct PaddedTrain final : TrainSource {
+    const float *targets(const gorse_fm *h) const override { return h->tgt.p; }
+    int32_t ready(const gorse_fm *h) const override {
+        for (int k = 0; k < h->n_fields; k++)
+            if (!h->fld[k].have_x)
+                return fail(GORSE_ERR_INVALID, "embedding field %d has no training embeddings (gorse_fm_set_train_embeddings)", k);
+        return GORSE_OK;
+    }
+    int32_t plan(gorse_fm *h, int32_t bs, int64_t *max_slots) const override {
+        if (h->plan_bs != bs) GORSE_TRY(build_plan(h, bs));
+        *max_slots = h->max_slots;
+        return GORSE_OK;
+    }
+    int32_t forward(gorse_fm *h, int64_t r0, int64_t nr) const override {
+        return train_forward(h, PaddedRows{h->idx.p, h->val.p, r0, h->width}, h->tgt.p + r0, nr);
+    }
+    AttArgs args(gorse_fm *h, int e, int64_t r0, int64_t nr) const {
+        return branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true);
+    }
+    int32_t branch_forward(gorse_fm *h, int e, int64_t r0, int64_t nr) const override {
+        return fm::branch_forward(h->s, args(h, e, r0, nr), BatchRows{});
+    }
+    int32_t branch_gx(gorse_fm *h, int e, int64_t r0, int64_t nr) const override {
+        att_bwd_gx_kernel<<<dim3(row_grid(nr)), dim3(kBlock), 0, h->s>>>(args(h, e, r0, nr));
+        GORSE_HIP_CHECK(hipGetLastError());
+        return GORSE_OK;
+    }
+    int32_t branch_grad(gorse_fm *h, int e, int64_t r0, int64_t nr) const override {
+        const AttArgs a = args(h, e, r0, nr);
+        att_grad_kernel<<<grad_grid(a), dim3(kBlock), 0, h->s>>>(a);
+        GORSE_HIP_CHECK(hipGetLastError());
+        return GORSE_OK;
+    }
+    int32_t accum(gorse_fm *h, int64_t k, int64_t r0, int64_t nr, int64_t tag_hi) const override {
+        AccArgs a = accum_args(h, nr, tag_hi);
+        a.uniq = h->uniq.p, a.seg = h->seg.p, a.pos = h->pos.p;
+        a.slot0 = h->uoff[(size_t)k], a.nslots = h->uoff[(size_t)k + 1] - h->uoff[(size_t)k];
+        a.val = h->val.p + r0 * h->width;
+        a.width = h->width;
+        return launch_accum(h, a);
+    }
+};
 
 int32_t check_field(const gorse_fm *h, int32_t field) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
@@ -707,6 +565,8 @@ extern "C" int32_t gorse_fm_set_train(gorse_fm *h, int64_t n, int32_t width, con
     GORSE_HIP_CHECK(hipSetDevice(h->device));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
     const size_t ne = (size_t)n * width;
+    h->smp.reset();  // a padded set replaces one in sample form
+    h->smp_dropped = false;
     h->h_idx.assign(indices, indices + ne);
     h->h_val.assign(values, values + ne);
     GORSE_TRY(h->idx.alloc(ne));
@@ -741,6 +601,7 @@ extern "C" int32_t gorse_fm_set_embedding_dims(gorse_fm *h, int32_t n_fields, co
         F.have_x = false;
         F.D = 0;
     }
+    fm::drop_sample_sets(h);  // they index the catalogue
     h->cat.reset();  // the resident item catalogue holds one table per field of the set that is going away
     h->test.reset();  // and so does the resident test split
     h->n_fields = 0;
@@ -808,6 +669,8 @@ extern "C" int32_t gorse_fm_get_embedding_params(gorse_fm *h, int32_t field, flo
 
 extern "C" int32_t gorse_fm_set_train_embeddings(gorse_fm *h, int32_t field, const uint16_t *emb) {
     GORSE_TRY(fm::check_field(h, field));
+    if (h->smp)
+        return fail(GORSE_ERR_INVALID, "the training set is in sample form: its embeddings are the item catalogue's (gorse_fm_set_items)");
     if (h->n <= 0) return fail(GORSE_ERR_INVALID, "no training set (gorse_fm_set_train)");
     if (!emb) return fail(GORSE_ERR_INVALID, "emb is NULL");
     fm::Field &F = h->fld[field];
@@ -828,13 +691,20 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
     if (optimizer != GORSE_OPT_SGD && optimizer != GORSE_OPT_ADAM) return fail(GORSE_ERR_INVALID, "unknown optimizer %d", optimizer);
+    if (h->n <= 0 && h->smp_dropped)
+        return fail(GORSE_ERR_INVALID, "the sample-form training set was dropped when the item catalogue it indexed was replaced or "
+                                       "dropped (gorse_fm_set_items, gorse_fm_set_embedding_dims): set it again");
     if (h->n <= 0) return fail(GORSE_ERR_INVALID, "no training set (gorse_fm_set_train)");
-    for (int k = 0; k < h->n_fields; k++)
-        if (!h->fld[k].have_x)
-            return fail(GORSE_ERR_INVALID, "embedding field %d has no training embeddings (gorse_fm_set_train_embeddings)", k);
+    // one loop over two training sources: whichever set was set last
+    static const fm::PaddedTrain padded;
+    const fm::TrainSource &src = h->smp ? fm::samples_source() : static_cast<const fm::TrainSource &>(padded);
+    GORSE_TRY(src.ready(h));
     GORSE_HIP_CHECK(hipSetDevice(h->device));
-    if (h->plan_bs != batch_size) GORSE_TRY(fm::build_plan(h, batch_size));
+    int64_t max_slots = 0;
+    GORSE_TRY(src.plan(h, batch_size, &max_slots));
+    GORSE_TRY(fm::ensure_step(h, batch_size, max_slots));
     if (h->n_fields > 0) GORSE_TRY(fm::ensure_branch(h, std::min<int64_t>(h->n, batch_size), true));
+    const float *tgt = src.targets(h);
     GORSE_HIP_CHECK(hipMemsetAsync(h->cost.p, 0, sizeof(float), h->s));
     const int64_t nb = ceil_div(h->n, batch_size);
     const bool adam = optimizer == GORSE_OPT_ADAM;
@@ -862,40 +732,25 @@ extern "C" int32_t gorse_fm_epoch(gorse_fm *h, int32_t batch_size, int32_t optim
         }
         const int64_t r0 = k * batch_size, nr = std::min<int64_t>(h->n, r0 + batch_size) - r0;
         const int64_t tag_hi = (h->step + 1) << 32;
-        fm::FwdArgs<fm::PaddedRows> f{};
-        f.src = {h->idx.p, h->val.p, r0, h->width};
-        f.tgt = h->tgt.p + r0;
-        f.V = h->V.p, f.W = h->W.p, f.B = h->B.p;
-        f.nrows = nr, f.d = h->d;
-        f.inv_n = 1.0f / (float)nr;
-        f.gs = h->gs.p, f.loss = h->loss.p, f.vx = h->vx.p;
-        if (h->n_fields > 0) f.out = h->a_logit.p;
-        GORSE_TRY(fm::launch_forward<fm::kTrain>(h->s, f));
+        GORSE_TRY(src.forward(h, r0, nr));
         if (h->n_fields > 0) {
             // the branch's contribution joins the logit before loss and g are formed (fm.go:127-132)
-            for (int e = 0; e < h->n_fields; e++)
-                GORSE_TRY(fm::branch_forward(h->s, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true),
-                                             fm::BatchRows{}));
+            for (int e = 0; e < h->n_fields; e++) GORSE_TRY(src.branch_forward(h, e, r0, nr));
             fm::LossArgs l{};
-            l.logit = h->a_logit.p, l.tgt = h->tgt.p + r0;
+            l.logit = h->a_logit.p, l.tgt = tgt + r0;
             l.vx = h->vx.p, l.esum = h->a_esum.p;
-            l.nrows = nr, l.d = h->d, l.inv_n = f.inv_n;
+            l.nrows = nr, l.d = h->d, l.inv_n = 1.0f / (float)nr;
             l.gs = h->gs.p, l.loss = h->loss.p, l.vxe = h->a_vxe.p;
             fm::att_loss_kernel<<<dim3((unsigned)ceil_div(nr * h->d, fm::kBlock)), dim3(fm::kBlock), 0, h->s>>>(l);
-            for (int e = 0; e < h->n_fields; e++)
-                GORSE_TRY(fm::branch_backward(h, fm::branch_args(h, e, h->fld[e].x.p + r0 * h->fld[e].D, nr, h->vx.p, true)));
+            for (int e = 0; e < h->n_fields; e++) {
+                GORSE_TRY(src.branch_gx(h, e, r0, nr));
+                // reads no embedding: the same launch for either source (x is not dereferenced)
+                fm::att_bwd_ds_kernel<<<dim3(fm::row_grid(nr)), dim3(fm::kBlock), 0, h->s>>>(
+                    fm::branch_args(h, e, nullptr, nr, h->vx.p, true));
+                GORSE_TRY(src.branch_grad(h, e, r0, nr));
+            }
         }
-        fm::AccArgs a{};
-        a.uniq = h->uniq.p, a.seg = h->seg.p, a.pos = h->pos.p;
-        a.slot0 = h->uoff[(size_t)k], a.nslots = h->uoff[(size_t)k + 1] - h->uoff[(size_t)k];
-        a.val = h->val.p + r0 * h->width;
-        a.V = h->V.p;
-        a.gs = h->gs.p, a.loss = h->loss.p;
-        a.vx = h->n_fields > 0 ? h->a_vxe.p : h->vx.p;  // with fields: vx + sum of enc, so that dV carries g * enc
-        a.nrows = nr, a.width = h->width, a.d = h->d;
-        a.tag_hi = tag_hi, a.tag = h->tag.p;
-        a.gV = h->gV.p, a.gW = h->gW.p, a.gB = h->gB.p, a.cost = h->cost.p;
-        GORSE_TRY(fm::launch_accum(h, a));
+        GORSE_TRY(src.accum(h, k, r0, nr, tag_hi));
         o.tag_hi = tag_hi;
         if (adam) {
             h->adam_t++;

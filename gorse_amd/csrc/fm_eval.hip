@@ -335,6 +335,7 @@ extern "C" int32_t gorse_fm_set_test(gorse_fm *h, int64_t n, int32_t width, cons
     if (n == 0) {
         GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
         h->test.reset();
+        h->test_dropped = false;
         return GORSE_OK;
     }
     if (width <= 0) return fail(GORSE_ERR_INVALID, "width must be positive (got %d)", width);
@@ -382,13 +383,18 @@ extern "C" int32_t gorse_fm_set_test(gorse_fm *h, int64_t n, int32_t width, cons
     }
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
     h->test = std::move(t);
+    h->test_dropped = false;
     return GORSE_OK;
 }
 
 extern "C" int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const volatile int32_t *cancel, int64_t *counts,
                                      float *auc_sum, float *logits_out) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (!h->test && h->test_dropped)
+        return fail(GORSE_ERR_INVALID, "the sample-form test split was dropped when the item catalogue it indexed was replaced or "
+                                       "dropped (gorse_fm_set_items, gorse_fm_set_embedding_dims): set it again");
     if (!h->test) return fail(GORSE_ERR_INVALID, "no resident test split (gorse_fm_set_test)");
+    if (h->test->samples && !h->cat) return fail(GORSE_ERR_INVALID, "the sample-form test split has no item catalogue");
     if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
     GORSE_HIP_CHECK(hipSetDevice(h->device));
     fm::TestSplit &t = *h->test;
@@ -400,7 +406,9 @@ extern "C" int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const vola
     if (t.plan_bs != batch_size || t.plan_rows != R) {
         const int64_t sides[3] = {0, n_pos, n};
         fm::SlicePlan plan;
-        fm::plan_slices(sides, 2, nullptr, batch_size, R, plan);
+        // sample form: a row's descriptor is (its user, its item) instead of (its side, its own number)
+        fm::plan_slices(sides, 2, t.samples ? t.s_item.data() : nullptr, batch_size, R, plan);
+        if (t.samples) std::copy(t.s_user.begin(), t.s_user.end(), plan.desc.begin());
         GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
         t.plan_bs = 0;
         GORSE_TRY(fm::upload_plan(t.plan, plan, n));
@@ -411,7 +419,15 @@ extern "C" int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const vola
     GORSE_TRY(fm::ensure_events(h->e_ev));
 
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[0], h->s));
-    GORSE_TRY(fm::score_rounds(h, t.plan, fm::PaddedRows{t.idx.p, t.val.p, 0, t.width}, t.emb, cancel, h->rs, h->e_logit.p));
+    if (t.samples) {
+        const fm::Catalogue &cat = *h->cat;
+        fm::ComposedRows src{};
+        src.uptr = t.users.ptr.p, src.uidx = t.users.idx.p, src.uval = t.users.val.p, src.ulead = t.users.lead.p;
+        src.iptr = cat.ptr.p, src.iidx = cat.idx.p, src.ival = cat.val.p, src.ilead = cat.lead.p;
+        GORSE_TRY(fm::score_rounds(h, t.plan, src, cat.emb, cancel, h->rs, h->e_logit.p));
+    } else {
+        GORSE_TRY(fm::score_rounds(h, t.plan, fm::PaddedRows{t.idx.p, t.val.p, 0, t.width}, t.emb, cancel, h->rs, h->e_logit.p));
+    }
     GORSE_HIP_CHECK(hipEventRecord(h->e_ev[1], h->s));
     GORSE_TRY(fm::enqueue_metrics(h, n_pos, n - n_pos));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));

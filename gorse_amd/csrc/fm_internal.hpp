@@ -46,6 +46,38 @@ struct Catalogue {
     DevBuf<int32_t> idx, lead;
     DevBuf<float> val;
     DevBuf<uint16_t> emb[kMaxFields];
+    // the CSR and the lead array once more on the host (never the embedding tables): a sample-form training set's per-batch
+    // plan is built from composed rows (fm_samples_plan.hpp)
+    std::vector<int64_t> h_ptr;
+    std::vector<int32_t> h_idx, h_lead;
+    std::vector<float> h_val;
+};
+
+// The user side a sample-form set keeps (gorse_fm_set_train_samples, gorse_fm_set_test_samples): the users' CSR in the form
+// gorse_fm_rank_users takes, on the device, and for a training set on the host as well.
+struct UserSide {
+    int64_t n_users = 0;
+    DevBuf<int64_t> ptr;
+    DevBuf<int32_t> idx, lead;
+    DevBuf<float> val;
+};
+
+// A training set in sample form: per sample (user, item, target); sample i is the row gorse_fm_rank_users composes for user[i]
+// and catalogue row item[i], and its embedding in field k is row item[i] of the catalogue's table k.  The per-batch plan
+// (fm_samples_plan.hpp) belongs to one batch size.
+struct SampleSet {
+    int64_t n = 0;
+    UserSide users;
+    std::vector<int64_t> h_uptr;
+    std::vector<int32_t> h_uidx, h_ulead, h_user, h_item;
+    std::vector<float> h_uval;
+    DevBuf<int32_t> user, item;
+    DevBuf<float> tgt;
+    int32_t plan_bs = 0;
+    int64_t max_slots = 0;
+    std::vector<int64_t> uoff, eoff;  // n_batches + 1 each: batch k's slots and entries
+    DevBuf<int32_t> uniq, seg, row;   // seg: per batch its slots + 1 batch-local entry offsets, at uoff[k] + k
+    DevBuf<float> val;
 };
 
 // a SlicePlan (fm_eval_plan.hpp) whose per-row descriptors are on the device
@@ -66,6 +98,11 @@ struct TestSplit {
     DevBuf<int32_t> idx;
     DevBuf<float> val;
     DevBuf<uint16_t> emb[kMaxFields];
+    // sample form (gorse_fm_set_test_samples): no rows and no embeddings of its own; resident row r is composed from user
+    // s_user[r] of `users` and catalogue row s_item[r], whose embeddings are read in place from the catalogue's tables
+    bool samples = false;
+    UserSide users;
+    std::vector<int32_t> s_user, s_item;
     int32_t plan_bs = 0;
     int64_t plan_rows = 0;
     RoundPlan plan;
@@ -108,6 +145,9 @@ struct gorse_fm {
     std::vector<int64_t> uoff;  // n_batches + 1: slots of batch k = [uoff[k], uoff[k+1])
     int64_t max_slots = 0;
     gorse::DevBuf<int32_t> uniq, seg, pos;
+    // the training set in sample form (fm_samples.hip): set means it is what gorse_fm_epoch trains, and n above is its rows
+    std::unique_ptr<gorse::fm::SampleSet> smp;
+    bool smp_dropped = false, test_dropped = false;  // a sample-form set went away with the catalogue it indexed
     // scratch
     gorse::DevBuf<float> gs, loss, vx, gV, gW, gB, cost;
     gorse::DevBuf<int32_t> p_idx;
@@ -392,6 +432,7 @@ struct BatchRows {
         base = 0;
         return (uint32_t)((r * a.D) % a.nrows);
     }
+    __device__ __forceinline__ const uint16_t *xu(const AttArgs &a, int64_t r) const { return x(a, r); }
 };
 struct SliceRows {
     const int32_t *item, *row0, *len;  // per row of the launch
@@ -401,6 +442,20 @@ struct SliceRows {
         n = (uint32_t)sn;
         base = row0[r];
         return (uint32_t)(((r - base) * a.D) % sn);
+    }
+};
+
+// A batch of a sample-form training set: one batch as BatchRows has it (the Softmax indexes over the whole launch), but row r's
+// embedding is row item[r] of the field's resident table, read in place.  xu: r is the same in every lane of the wave, so
+// item[r] comes through a scalar load.
+struct ItemRows {
+    const int32_t *item;  // per row of the batch
+    __device__ __forceinline__ const uint16_t *x(const AttArgs &a, int64_t r) const { return a.x + (int64_t)item[r] * a.D; }
+    __device__ __forceinline__ const uint16_t *xu(const AttArgs &a, int64_t r) const {
+        return a.x + (int64_t)__builtin_amdgcn_readfirstlane(item[r]) * a.D;
+    }
+    __device__ __forceinline__ uint32_t wrap(const AttArgs &a, int64_t r, uint32_t &n, int64_t &base) const {
+        return BatchRows{}.wrap(a, r, n, base);
     }
 };
 
@@ -612,6 +667,20 @@ inline int32_t upload_plan(RoundPlan &dst, SlicePlan &src, int64_t n) {
     return GORSE_OK;
 }
 
+// a sample-form training set or test split goes away with the catalogue it indexes (gorse_fm_set_items,
+// gorse_fm_set_embedding_dims); the flags let gorse_fm_epoch / gorse_fm_evaluate say why there is none
+inline void drop_sample_sets(gorse_fm *h) {
+    if (h->smp) {
+        h->smp.reset();
+        h->n = 0;
+        h->smp_dropped = true;
+    }
+    if (h->test && h->test->samples) {
+        h->test.reset();
+        h->test_dropped = true;
+    }
+}
+
 // timing events created by the first call that records them
 template <size_t N>
 inline int32_t ensure_events(hipEvent_t (&ev)[N]) {
@@ -619,6 +688,10 @@ inline int32_t ensure_events(hipEvent_t (&ev)[N]) {
         if (!e) GORSE_HIP_CHECK(hipEventCreate(&e));
     return GORSE_OK;
 }
+
+// fm_rank.hip: the feature rows of one side: a well-formed pointer, entries in range, lead[i] within row i
+int32_t check_side(const gorse_fm *h, int64_t n, const int64_t *ptr, const int32_t *idx, const float *val, const int32_t *lead,
+                   const char *what);
 
 // fm_resident.hip: the rows of every round of `plan` scored into logit (plan.n entries): src's entries through the forward
 // kernel and, where the model has fields, the branch on the rows' embeddings in tables[field] (row plan item[r]), in `rs`

@@ -112,6 +112,7 @@ extern "C" int32_t gorse_fm_set_items(gorse_fm *h, int64_t n_items, const int64_
     GORSE_HIP_CHECK(hipSetDevice(h->device));
     if (n_items == 0) {
         GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+        fm::drop_sample_sets(h);  // they index the catalogue that goes away
         h->cat.reset();
         return GORSE_OK;
     }
@@ -135,7 +136,14 @@ extern "C" int32_t gorse_fm_set_items(gorse_fm *h, int64_t n_items, const int64_
         GORSE_HIP_CHECK(hipMemset(c->lead.p, 0, (size_t)n_items * sizeof(int32_t)));
     }
     for (int k = 0; k < h->n_fields; k++) GORSE_TRY(fm::upload(c->emb[k], emb[k], (size_t)n_items * (size_t)h->fld[k].D));
+    // the host's copy of the rows (not of the tables): what a sample-form training set's plan is built from
+    c->h_ptr.assign(indptr, indptr + n_items + 1);
+    c->h_idx.assign(indices, indices + nnz);
+    c->h_val.assign(values, values + nnz);
+    if (lead) c->h_lead.assign(lead, lead + n_items);
+    else c->h_lead.assign((size_t)n_items, 0);
     GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    fm::drop_sample_sets(h);  // they index the catalogue that is replaced
     h->cat = std::move(c);
     return GORSE_OK;
 }

@@ -38,6 +38,23 @@ def host():
         H.gh_fm_evaluate_resident.argtypes = [C.c_void_p, _f32p]
         H.gh_fm_set_host_evaluate.restype = None
         H.gh_fm_set_host_evaluate.argtypes = [C.c_void_p, C.c_int32]
+        H.gh_ctr_samples_new.restype = C.c_void_p
+        H.gh_ctr_samples_new.argtypes = [C.c_int64]
+        H.gh_ctr_samples_free.argtypes = [C.c_void_p]
+        H.gh_ctr_samples_set_side.restype = None
+        H.gh_ctr_samples_set_side.argtypes = [C.c_void_p, C.c_int32, C.c_int64, _i32p, _i64p, _i32p, _f32p]
+        H.gh_ctr_samples_set_embeddings.restype = None
+        H.gh_ctr_samples_set_embeddings.argtypes = [C.c_void_p, C.c_int32, _i32p, C.POINTER(_u16p)]
+        H.gh_ctr_samples_add.restype = None
+        H.gh_ctr_samples_add.argtypes = [C.c_void_p, C.c_int64, _i32p, _i32p, _f32p]
+        H.gh_ctr_samples_materialise.restype = C.c_void_p
+        H.gh_ctr_samples_materialise.argtypes = [C.c_void_p]
+        H.gh_ctr_dataset_shape.restype = None
+        H.gh_ctr_dataset_shape.argtypes = [C.c_void_p, _i64p]
+        H.gh_ctr_dataset_read.restype = None
+        H.gh_ctr_dataset_read.argtypes = [C.c_void_p, _i64p, _i32p, _f32p, _f32p]
+        H.gh_ctr_dataset_read_embeddings.argtypes = [C.c_void_p, C.c_int32, _u16p]
+        H.gh_fm_fit_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _i32p, _f32p]
         _configured = True
     return H
 
@@ -120,6 +137,74 @@ class Dataset:
     def Count(self):
         return self.n
 
+    def rows(self):
+        """(indptr, indices, values, target, [one Count() x D uint16 matrix per field]) as the set holds them"""
+        shape = np.zeros(3, np.int64)
+        host().gh_ctr_dataset_shape(self.p, shape.ctypes.data_as(_i64p))
+        n, nnz, nf = (int(x) for x in shape)
+        ptr, idx = np.zeros(n + 1, np.int64), np.zeros(max(1, nnz), np.int32)
+        val, tgt = np.zeros(max(1, nnz), np.float32), np.zeros(max(1, n), np.float32)
+        host().gh_ctr_dataset_read(self.p, ptr.ctypes.data_as(_i64p), idx.ctypes.data_as(_i32p), val.ctypes.data_as(_f32p),
+                                   tgt.ctypes.data_as(_f32p))
+        embs = []
+        for k in range(nf):
+            D = host().gh_ctr_dataset_read_embeddings(self.p, k, None)
+            e = np.zeros((max(1, n), D), np.uint16)
+            host().gh_ctr_dataset_read_embeddings(self.p, k, e.ctypes.data_as(_u16p))
+            embs.append(e[:n])
+        return ptr, idx[:nnz], val[:nnz], tgt[:n], embs
+
+
+class SampleDataset:
+    """The reference's own form of a CTR data set (model/ctr/data.go:152-267) without context labels: users and items as label
+    rows (ids and labels are feature indices, negative = unknown to the index, as FM.SetItems takes them), one n_items x D
+    uint16 (bf16) table per embedding field, and per sample (user row, item row, target).  A training set and its test set
+    share one item side."""
+
+    def __init__(self, n_features, user_ids, user_rows, item_ids, item_rows, embs=(), samples=None):
+        self.n_features = int(n_features)
+        self.p = C.c_void_p(host().gh_ctr_samples_new(self.n_features))
+        self.n = 0
+        for side, (ids, rows) in enumerate(((user_ids, user_rows), (item_ids, item_rows))):
+            ids, ptr, lab, val = FM._label_rows(ids, rows)
+            host().gh_ctr_samples_set_side(self.p, side, ids.size, ids.ctypes.data_as(_i32p), ptr.ctypes.data_as(_i64p),
+                                           lab.ctypes.data_as(_i32p), val.ctypes.data_as(_f32p))
+        embs = [np.ascontiguousarray(e, np.uint16) for e in embs]
+        if any(e.ndim != 2 or e.shape[0] != len(item_rows) for e in embs):
+            raise ValueError("one n_items x D table per field")
+        dims = np.array([e.shape[1] for e in embs] or [0], np.int32)
+        ptrs = (_u16p * max(1, len(embs)))(*[e.ctypes.data_as(_u16p) for e in embs])
+        host().gh_ctr_samples_set_embeddings(self.p, len(embs), dims.ctypes.data_as(_i32p), ptrs)
+        self.dims = tuple(int(e.shape[1]) for e in embs)
+        if samples is not None:
+            self.add_samples(*samples)
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            host().gh_ctr_samples_free(self.p)
+            self.p = None
+
+    def add_samples(self, user, item, target):
+        u, i = np.ascontiguousarray(user, np.int32), np.ascontiguousarray(item, np.int32)
+        t = np.ascontiguousarray(target, np.float32)
+        if u.size != t.size or i.size != t.size:
+            raise ValueError("one user, one item and one target per sample")
+        if t.size:
+            host().gh_ctr_samples_add(self.p, t.size, u.ctypes.data_as(_i32p), i.ctypes.data_as(_i32p), t.ctypes.data_as(_f32p))
+        self.n += t.size
+
+    def Count(self):
+        return self.n
+
+    def Materialise(self):
+        """Dataset.Get for every sample: the Dataset the padded route takes"""
+        p = host().gh_ctr_samples_materialise(self.p)
+        if not p:
+            raise ValueError("malformed samples")
+        d = Dataset.__new__(Dataset)
+        d.n_features, d.p, d.n, d.dims = self.n_features, C.c_void_p(p), self.n, self.dims
+        return d
+
 
 class FM:
     """ctr.AFM (model/ctr/fm.go), trained and scored on the device; a training set with item embeddings (Dataset.set_embeddings)
@@ -140,6 +225,18 @@ class FM:
         s = np.zeros(4, np.float32)
         cp = cancel.ctypes.data_as(_i32p) if cancel is not None else None
         rc = host().gh_fm_fit(self.p, train.p, test.p, Verbose, Patience, cp, s.ctypes.data_as(_f32p))
+        if rc != 0:
+            raise cf.HostError(rc)
+        self.nf = train.n_features
+        self.dims = train.dims
+        return Score(s)
+
+    def FitSamples(self, train, test, Verbose=10, Patience=0, cancel=None):
+        """Fit from SampleDatasets: the item side goes to the device once and stays resident (RankUsers works afterwards
+        without SetItems), per sample three numbers; every bit of the result is Fit's on the Materialise()d sets"""
+        s = np.zeros(4, np.float32)
+        cp = cancel.ctypes.data_as(_i32p) if cancel is not None else None
+        rc = host().gh_fm_fit_samples(self.p, train.p, test.p, Verbose, Patience, cp, s.ctypes.data_as(_f32p))
         if rc != 0:
             raise cf.HostError(rc)
         self.nf = train.n_features

@@ -254,10 +254,9 @@ Score EvaluateClassification(FM &m, const Dataset &test) {
     return s;
 }
 
-Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
+void FM::Init(int64_t nFeatures, const std::vector<int32_t> &embDims) {
     // Init (fm.go:247-270): B = 0, W and V from N(0, 0.01) (layers.go:82-87), W drawn first
-    nf_ = train.n_features;
-    numDimension_ = train.MaxLen();
+    nf_ = nFeatures;
     if (h_) gorse_fm_destroy(h_), h_ = nullptr;
     check(gorse_fm_create(&h_, device_, nf_, nFactors_));
     util::RandomGenerator rng(seed_);
@@ -266,21 +265,15 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
     rng.NormalMatrix(nf_, nFactors_, 0, 0.01f, V);
     // the embedding fields (fm.go:257-264): nn.NewAttention draws its Linear (Wa ~ Uniform(+-1/sqrt(D)), ba = 0), then
     // H ~ Normal(0, 0.01); nn.NewLinear draws We the same way, be = 0 (layers.go:42-48, 166-171)
-    fields.assign(train.emb_dims.size(), Field{});
-    if (!train.emb_dims.empty()) {
-        if (train.emb.size() != train.emb_dims.size()) throw std::invalid_argument("one embedding matrix per field");
-        for (size_t k = 0; k < fields.size(); k++)
-            if (train.emb[k].size() != (size_t)train.Count() * (size_t)train.emb_dims[k])
-                throw std::invalid_argument("an embedding matrix must hold Count() x D values");
-    }
-    check(gorse_fm_set_embedding_dims(h_, (int32_t)train.emb_dims.size(), train.emb_dims.data()));
+    fields.assign(embDims.size(), Field{});
+    check(gorse_fm_set_embedding_dims(h_, (int32_t)embDims.size(), embDims.data()));
     auto uniform = [&](size_t n, float bound, std::vector<float> &out) {
         out.resize(n);
         for (auto &x : out) x = (float)rng.Float64() * (2 * bound) - bound;
     };
     for (size_t k = 0; k < fields.size(); k++) {
         Field &f = fields[k];
-        f.D = train.emb_dims[k];
+        f.D = embDims[k];
         const float bound = 1.0f / std::sqrt((float)f.D);
         uniform((size_t)f.D * nFactors_, bound, f.Wa);
         f.ba.assign((size_t)nFactors_, 0.0f);
@@ -294,23 +287,14 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
         check(gorse_fm_set_embedding_params(h_, (int32_t)k, f.H.data(), f.Wa.data(), f.ba.data(), f.We.data(), f.be.data()));
     }
     log.clear();
-
     testCount_ = -1;  // the handle is new
-    if (!hostEvaluate_) SetTest(test);
-    auto evaluate = [&] { return hostEvaluate_ ? EvaluateClassification(*this, test) : EvaluateResident(); };
+}
+
+template <class Evaluate>
+Score FM::Train(const FitConfig &cfg, Evaluate evaluate) {
     Score score = evaluate();
     std::vector<std::pair<int, float>> scores{{0, score.AUC}};
     log.push_back({0, 0.0f, score});
-
-    const int width = std::max(1, numDimension_);
-    std::vector<int64_t> all((size_t)train.Count());
-    for (int64_t i = 0; i < train.Count(); i++) all[(size_t)i] = i;
-    std::vector<int32_t> idx;
-    std::vector<float> val;
-    pad_rows(train, all, width, idx, val);
-    check(gorse_fm_set_train(h_, train.Count(), width, idx.data(), val.data(), train.target.data()));
-    for (size_t k = 0; k < fields.size(); k++) check(gorse_fm_set_train_embeddings(h_, (int32_t)k, train.emb[k].data()));
-
     const int32_t opt = optimizer_ == 0 ? GORSE_OPT_SGD : GORSE_OPT_ADAM;
     for (int epoch = 1; epoch <= nEpochs_; epoch++) {
         float cost = 0;
@@ -337,6 +321,120 @@ Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
     }
     ReadBack();  // in Parameters() order: B, V, W, then per field H, Wa, ba, We, be
     return score;
+}
+
+Score FM::Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg) {
+    numDimension_ = train.MaxLen();
+    if (!train.emb_dims.empty()) {
+        if (train.emb.size() != train.emb_dims.size()) throw std::invalid_argument("one embedding matrix per field");
+        for (size_t k = 0; k < train.emb_dims.size(); k++)
+            if (train.emb[k].size() != (size_t)train.Count() * (size_t)train.emb_dims[k])
+                throw std::invalid_argument("an embedding matrix must hold Count() x D values");
+    }
+    Init(train.n_features, train.emb_dims);
+    if (!hostEvaluate_) SetTest(test);
+    const int width = std::max(1, numDimension_);
+    std::vector<int64_t> all((size_t)train.Count());
+    for (int64_t i = 0; i < train.Count(); i++) all[(size_t)i] = i;
+    {
+        std::vector<int32_t> idx;
+        std::vector<float> val;
+        pad_rows(train, all, width, idx, val);
+        check(gorse_fm_set_train(h_, train.Count(), width, idx.data(), val.data(), train.target.data()));
+    }
+    for (size_t k = 0; k < fields.size(); k++) check(gorse_fm_set_train_embeddings(h_, (int32_t)k, train.emb[k].data()));
+    return Train(cfg, [&] { return hostEvaluate_ ? EvaluateClassification(*this, test) : EvaluateResident(); });
+}
+
+// sample i's row (Dataset.Get, data.go:221-267): user id | item id | user labels | item labels, from the sides as encode_rows
+// leaves them
+template <class F>
+static void sample_row(const std::vector<int64_t> &uptr, const std::vector<int32_t> &uidx, const std::vector<float> &uval,
+                       const std::vector<int32_t> &ulead, const std::vector<int64_t> &iptr, const std::vector<int32_t> &iidx,
+                       const std::vector<float> &ival, const std::vector<int32_t> &ilead, int32_t u, int32_t c, F fn) {
+    const int64_t u0 = uptr[(size_t)u], u1 = uptr[(size_t)u + 1], um = u0 + ulead[(size_t)u];
+    const int64_t i0 = iptr[(size_t)c], i1 = iptr[(size_t)c + 1], im = i0 + ilead[(size_t)c];
+    for (int64_t j = u0; j < um; j++) fn(uidx[(size_t)j], uval[(size_t)j]);
+    for (int64_t j = i0; j < im; j++) fn(iidx[(size_t)j], ival[(size_t)j]);
+    for (int64_t j = um; j < u1; j++) fn(uidx[(size_t)j], uval[(size_t)j]);
+    for (int64_t j = im; j < i1; j++) fn(iidx[(size_t)j], ival[(size_t)j]);
+}
+
+static void check_samples(const SampleDataset &s) {
+    if (s.user.size() != s.target.size() || s.item.size() != s.target.size())
+        throw std::invalid_argument("one user, one item and one target per sample");
+    for (size_t i = 0; i < s.target.size(); i++)
+        if (s.user[i] < 0 || s.user[i] >= s.users.Count() || s.item[i] < 0 || s.item[i] >= s.items.Count())
+            throw std::invalid_argument("a sample names a user or an item outside its side");
+    if (s.emb.size() != s.emb_dims.size()) throw std::invalid_argument("one embedding table per field");
+    for (size_t k = 0; k < s.emb_dims.size(); k++)
+        if (s.emb[k].size() != (size_t)s.items.Count() * (size_t)s.emb_dims[k])
+            throw std::invalid_argument("an embedding table must hold items.Count() x D values");
+}
+
+Dataset Materialise(const SampleDataset &s) {
+    check_samples(s);
+    std::vector<int64_t> uptr, iptr;
+    std::vector<int32_t> uidx, ulead, iidx, ilead;
+    std::vector<float> uval, ival;
+    encode_rows(s.users, uptr, uidx, uval, ulead);
+    encode_rows(s.items, iptr, iidx, ival, ilead);
+    Dataset d;
+    d.n_features = s.n_features;
+    for (int64_t i = 0; i < s.Count(); i++) {
+        sample_row(uptr, uidx, uval, ulead, iptr, iidx, ival, ilead, s.user[(size_t)i], s.item[(size_t)i], [&](int32_t f, float x) {
+            d.indices.push_back(f);
+            d.values.push_back(x);
+        });
+        d.indptr.push_back((int64_t)d.indices.size());
+        d.target.push_back(s.target[(size_t)i]);
+    }
+    d.emb_dims = s.emb_dims;
+    d.emb.assign(s.emb_dims.size(), {});
+    for (size_t k = 0; k < s.emb_dims.size(); k++) {
+        const size_t D = (size_t)s.emb_dims[k];
+        d.emb[k].resize((size_t)s.Count() * D);
+        for (int64_t i = 0; i < s.Count(); i++)
+            std::copy(s.emb[k].begin() + (size_t)s.item[(size_t)i] * D, s.emb[k].begin() + ((size_t)s.item[(size_t)i] + 1) * D,
+                      d.emb[k].begin() + (size_t)i * D);
+    }
+    return d;
+}
+
+Score FM::Fit(const SampleDataset &train, const SampleDataset &test, const FitConfig &cfg) {
+    check_samples(train);
+    check_samples(test);
+    if (test.emb_dims != train.emb_dims || test.items.Count() != train.items.Count())
+        throw std::invalid_argument("the test set must share the training set's item side");
+    std::vector<int64_t> uptr, iptr;
+    std::vector<int32_t> uidx, ulead, iidx, ilead;
+    std::vector<float> uval, ival;
+    encode_rows(train.users, uptr, uidx, uval, ulead);
+    encode_rows(train.items, iptr, iidx, ival, ilead);
+    numDimension_ = 0;  // the longest composed row
+    for (int64_t i = 0; i < train.Count(); i++) {
+        const int32_t u = train.user[(size_t)i], c = train.item[(size_t)i];
+        numDimension_ = std::max(numDimension_, (int)(uptr[(size_t)u + 1] - uptr[(size_t)u] + iptr[(size_t)c + 1] - iptr[(size_t)c]));
+    }
+    Init(train.n_features, train.emb_dims);
+    std::vector<const uint16_t *> tables;
+    for (const auto &e : train.emb) tables.push_back(e.data());
+    SetItems(train.items, tables);  // once: training, evaluation and ranking all read it in place
+    check(gorse_fm_set_train_samples(h_, train.users.Count(), uptr.data(), uidx.data(), uval.data(), ulead.data(), train.Count(),
+                                     train.user.data(), train.item.data(), train.target.data()));
+    Dataset hostTest;
+    if (hostEvaluate_) {
+        hostTest = Materialise(test);
+    } else {
+        const int64_t n = test.Count();
+        testPositive_.assign((size_t)n, 0);
+        for (int64_t i = 0; i < n; i++) testPositive_[(size_t)i] = test.target[(size_t)i] > 0;
+        encode_rows(test.users, uptr, uidx, uval, ulead);
+        check(gorse_fm_set_test_samples(h_, test.users.Count(), uptr.data(), uidx.data(), uval.data(), ulead.data(), n,
+                                        test.user.data(), test.item.data(), test.target.data()));
+        testCount_ = n;
+    }
+    return Train(cfg, [&] { return hostEvaluate_ ? EvaluateClassification(*this, hostTest) : EvaluateResident(); });
 }
 
 }  // namespace ctr

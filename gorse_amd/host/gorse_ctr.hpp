@@ -49,6 +49,24 @@ struct LabelRows {
     int64_t Count() const { return (int64_t)id.size(); }
 };
 
+// The reference's own form of a CTR data set (model/ctr/data.go:152-267) without context labels: one label row per user and
+// per item, one embedding per item and field, and per sample only (Users[i], Items[i], Target[i]).  Row ids and labels are
+// feature indices, as in LabelRows; emb[k] is an items.Count() x emb_dims[k] matrix of bf16 bit patterns (an all-zero row for
+// an item without one).  A training set and its test set share one item side, as Dataset.Split leaves them.
+struct SampleDataset {
+    int64_t n_features = 0;
+    LabelRows users, items;
+    std::vector<int32_t> emb_dims;
+    std::vector<std::vector<uint16_t>> emb;
+    std::vector<int32_t> user, item;
+    std::vector<float> target;
+    int64_t Count() const { return (int64_t)target.size(); }
+};
+
+// Dataset.Get (data.go:221-267) for every sample: the user-id entry, the item-id entry, the user's labels, the item's labels
+// (entries the index does not know are left out, as BatchPredict leaves them out), and the item's embedding per field
+Dataset Materialise(const SampleDataset &s);
+
 struct Ranked {
     int32_t item;  // catalogue row
     float score;
@@ -75,6 +93,12 @@ class FM {
     FM &operator=(const FM &) = delete;
     // AFM.Fit (fm.go:307-417); a training set with item embeddings trains the attention branch as well
     Score Fit(const Dataset &train, const Dataset &test, const FitConfig &cfg);
+    // The same Fit from samples: the item side goes to the device once (SetItems: it stays resident, so RankUsers works
+    // afterwards without another SetItems), per sample three numbers (gorse_fm_set_train_samples, gorse_fm_set_test_samples).
+    // Initial parameters, evaluation schedule, NaN stop, patience and cancel are Fit's, and so is every bit of the result
+    // Fit(Materialise(train), Materialise(test)) gives.  With SetHostEvaluate(true) the test set is materialised once and
+    // evaluated through EvaluateClassification.
+    Score Fit(const SampleDataset &train, const SampleDataset &test, const FitConfig &cfg);
     // BatchInternalPredict (fm.go:156-178) of rows [0, ds.Count()) that satisfy keep (or all rows)
     std::vector<float> BatchInternalPredict(const Dataset &ds, const std::vector<int64_t> &rows);
     // The bulk form of the worker's rankByClickTroughRate (worker/pipeline.go:451-499).  SetItems encodes the catalogue as
@@ -111,6 +135,10 @@ class FM {
     int64_t testCount_ = -1;           // rows of the resident split; -1: none
     std::vector<uint8_t> testPositive_;  // per row of it: target > 0
     void ReadBack();
+    // Init (fm.go:247-270) on a new handle; Train: the epoch-0 evaluation, the epochs and what stops them, the read-back
+    void Init(int64_t nFeatures, const std::vector<int32_t> &embDims);
+    template <class Evaluate>
+    Score Train(const FitConfig &cfg, Evaluate evaluate);
     int64_t nf_ = 0;
     gorse_fm *h_ = nullptr;
 };

@@ -1131,4 +1131,64 @@ int32_t gh_ctr_fm_rank_users(void *m, int64_t n, const int32_t *id, const int64_
             }
     });
 }
+// ---- model/ctr in sample form: ctr::SampleDataset, Materialise and the Fit that trains from it ---------------------------------
+void *gh_ctr_samples_new(int64_t n_features) {
+    auto *d = new ctr::SampleDataset();
+    d->n_features = n_features;
+    return d;
+}
+void gh_ctr_samples_free(void *d) { delete (ctr::SampleDataset *)d; }
+// one side as label rows (side 0: users, 1: items), replacing it
+void gh_ctr_samples_set_side(void *d, int32_t side, int64_t n, const int32_t *id, const int64_t *indptr, const int32_t *label,
+                             const float *value) {
+    auto *s = (ctr::SampleDataset *)d;
+    (side == 0 ? s->users : s->items) = label_rows(n, id, indptr, label, value);
+}
+// the items' embeddings: per field its dimension and an items.Count() x D matrix of bf16 bit patterns (after the item side)
+void gh_ctr_samples_set_embeddings(void *d, int32_t n_fields, const int32_t *dims, const uint16_t *const *emb) {
+    auto *s = (ctr::SampleDataset *)d;
+    s->emb_dims.assign(dims, dims + n_fields);
+    s->emb.assign((size_t)n_fields, {});
+    for (int32_t k = 0; k < n_fields; k++) s->emb[(size_t)k].assign(emb[k], emb[k] + (size_t)s->items.Count() * (size_t)dims[k]);
+}
+void gh_ctr_samples_add(void *d, int64_t n, const int32_t *user, const int32_t *item, const float *target) {
+    auto *s = (ctr::SampleDataset *)d;
+    s->user.insert(s->user.end(), user, user + n);
+    s->item.insert(s->item.end(), item, item + n);
+    s->target.insert(s->target.end(), target, target + n);
+}
+// ctr::Materialise: a new ctr::Dataset (gh_ctr_dataset_free), or NULL where the samples are malformed
+void *gh_ctr_samples_materialise(void *d) {
+    ctr::Dataset *out = nullptr;
+    guard([&] { out = new ctr::Dataset(ctr::Materialise(*(ctr::SampleDataset *)d)); });
+    return out;
+}
+// a ctr::Dataset's contents: out3 = rows, entries, embedding fields; then the rows; then one field's matrix (returns its D)
+void gh_ctr_dataset_shape(void *d, int64_t *out3) {
+    const auto *ds = (ctr::Dataset *)d;
+    out3[0] = ds->Count(), out3[1] = (int64_t)ds->indices.size(), out3[2] = (int64_t)ds->emb_dims.size();
+}
+void gh_ctr_dataset_read(void *d, int64_t *indptr, int32_t *idx, float *val, float *target) {
+    const auto *ds = (ctr::Dataset *)d;
+    std::copy(ds->indptr.begin(), ds->indptr.end(), indptr);
+    std::copy(ds->indices.begin(), ds->indices.end(), idx);
+    std::copy(ds->values.begin(), ds->values.end(), val);
+    std::copy(ds->target.begin(), ds->target.end(), target);
+}
+int32_t gh_ctr_dataset_read_embeddings(void *d, int32_t field, uint16_t *out) {
+    const auto *ds = (ctr::Dataset *)d;
+    if (field < 0 || field >= (int32_t)ds->emb_dims.size()) return 0;
+    if (out) std::copy(ds->emb[(size_t)field].begin(), ds->emb[(size_t)field].end(), out);
+    return ds->emb_dims[(size_t)field];
+}
+int32_t gh_fm_fit_samples(void *m, void *train, void *test, int32_t verbose, int32_t patience, const int32_t *cancel, float *score4) {
+    return guard([&] {
+        ctr::FitConfig cfg;
+        cfg.Verbose = verbose;
+        cfg.Patience = patience;
+        cfg.cancel = cancel;
+        const ctr::Score s = ((ctr::FM *)m)->Fit(*(ctr::SampleDataset *)train, *(ctr::SampleDataset *)test, cfg);
+        score4[0] = s.Precision, score4[1] = s.Recall, score4[2] = s.Accuracy, score4[3] = s.AUC;
+    });
+}
 }  // extern "C"

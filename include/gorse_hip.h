@@ -561,6 +561,42 @@ int32_t gorse_fm_evaluate(gorse_fm *h, int32_t batch_size, const volatile int32_
  * handle's stream, copies excluded).  Any pointer may be NULL. */
 int32_t gorse_fm_evaluate_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, double *device_ms);
 
+/* ---- training and evaluating from (user, item) samples -------------------------------------------------------------------------
+ * The reference keeps a CTR data set in sample form (model/ctr/data.go:152-267): one label row per user and per item, one
+ * embedding per item, and per sample only (Users[i], Items[i], Target[i]); Dataset.Get composes the feature row and looks the
+ * embedding up by item.  These two calls take that form.  The item side is the resident catalogue of gorse_fm_set_items;
+ * the user side (a CSR in the form gorse_fm_rank_users takes; user_lead NULL = 0) is copied to the device and kept with the set.
+ * Sample i is the row gorse_fm_rank_users composes for user user[i] and catalogue row item[i] -- user lead | item lead |
+ * user rest | item rest, zero-valued entries skipped -- and its embedding in field k is row item[i] of catalogue table k, read
+ * in place.  Per sample three numbers travel; no n x width rows and no n x D embeddings are built anywhere.
+ *
+ * gorse_fm_epoch trains whichever training set was set last (this one or gorse_fm_set_train's, each replaces the other) and
+ * gorse_fm_evaluate scores whichever test split was set last; signatures, stats and cancel behaviour are theirs.  Every bit --
+ * each epoch's cost, B, W, V and every field tensor after any number of SGD or Adam steps, the seven counts, auc_sum and
+ * logits_out -- equals what gorse_fm_set_train + gorse_fm_set_train_embeddings / gorse_fm_set_test produce from the
+ * materialised rows: the composed rows zero-padded to any width, the embeddings gathered per sample.  gorse_fm_set_test_samples
+ * keeps EvaluateClassification's order (target > 0 first, then the rest, each side in sample order); logits_out comes back in
+ * the order given.
+ *
+ * Both sets index the catalogue: gorse_fm_set_items (replacing or dropping it) and gorse_fm_set_embedding_dims drop a
+ * sample-form training set and test split, and gorse_fm_epoch / gorse_fm_evaluate then return GORSE_ERR_INVALID saying so.
+ * gorse_fm_set_train_embeddings on a sample-form set is GORSE_ERR_INVALID.  set_params, set_embedding_params, rank_users and
+ * evaluate leave the training set alone.
+ * Everything is validated before anything is replaced and an error leaves the previous set in place.  GORSE_ERR_INVALID: no
+ * catalogue, n <= 0 for training (n = 0 drops the test split), a malformed user_indptr, user_lead[t] beyond its row, n >= 2^31;
+ * a batch whose nonzero entries exceed 2^31 - 1 is refused by gorse_fm_epoch.  GORSE_ERR_RANGE: user[i] outside [0, n_users),
+ * item[i] outside [0, n_items), a user feature outside [0, n_features).  GORSE_ERR_NOMEM: it does not fit the device.
+ * Per-sample context labels (Dataset.ContextLabels) are out of scope: a set that has them keeps the padded route
+ * (gorse_fm_set_train / gorse_fm_set_test on materialised rows). */
+int32_t gorse_fm_set_train_samples(gorse_fm *h, int64_t n_users, const int64_t *user_indptr /*host, n_users+1*/,
+                                   const int32_t *user_indices /*host*/, const float *user_values /*host*/,
+                                   const int32_t *user_lead /*host, n_users, or NULL*/, int64_t n, const int32_t *user /*host, n*/,
+                                   const int32_t *item /*host, n*/, const float *target /*host, n*/);
+int32_t gorse_fm_set_test_samples(gorse_fm *h, int64_t n_users, const int64_t *user_indptr /*host, n_users+1*/,
+                                  const int32_t *user_indices /*host*/, const float *user_values /*host*/,
+                                  const int32_t *user_lead /*host, n_users, or NULL*/, int64_t n, const int32_t *user /*host, n*/,
+                                  const int32_t *item /*host, n*/, const float *target /*host, n*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -504,3 +504,68 @@ func (fm *AFM) SetRankItems(items []RankItem) bool { return fm.setItemsHIP(items
 func (fm *AFM) RankUsers(ctx context.Context, users []RankUser) ([][]float32, [][]int32, bool) {
 	return fm.rankUsersHIP(ctx, users)
 }
+
+// SampleSide is the user side of a set in sample form: one encoded row per user (EncodeRankUser), as rankUsersHIP takes them.
+type SampleSide struct {
+	Indices [][]int32
+	Values  [][]float32
+	Lead    []int32
+}
+
+// setSamplesHIP hands a data set over in the reference's own form (Dataset.Users / Items / Target, model/ctr/data.go:152-267):
+// the users' encoded rows and per sample (user row, catalogue row, target).  The item side is the catalogue of setItemsHIP,
+// which must be resident; sample i is the row BatchPredict composes for (user[i], item[i]) and its embeddings are the
+// catalogue's.  train selects gorse_fm_set_train_samples (what the next gorse_fm_epoch trains) or gorse_fm_set_test_samples
+// (what gorse_fm_evaluate scores).  A set with context labels keeps the padded route (fitHIP).  ok = false when no model is
+// resident or the library refuses the set (it then keeps the previous one).
+func (fm *AFM) setSamplesHIP(train bool, users SampleSide, user, item []int32, target []float32) bool {
+	if fm.hip == nil || fm.hip.h == nil || len(user) != len(item) || len(user) != len(target) {
+		return false
+	}
+	nUsers, n := len(users.Indices), len(user)
+	if n == 0 && train {
+		return false
+	}
+	uptr := make([]int64, nUsers+1)
+	lead := make([]int32, max(nUsers, 1))
+	var idx []int32
+	var val []float32
+	for t := range users.Indices {
+		idx = append(idx, users.Indices[t]...)
+		val = append(val, users.Values[t]...)
+		uptr[t+1] = int64(len(idx))
+		lead[t] = users.Lead[t]
+	}
+	if len(idx) == 0 {
+		idx, val = []int32{0}, []float32{0}
+	}
+	if n == 0 { // no samples: drops the resident test split
+		user, item, target = []int32{0}, []int32{0}, []float32{0}
+	}
+	var rc C.int32_t
+	if train {
+		rc = C.gorse_fm_set_train_samples(fm.hip.h, C.int64_t(nUsers), (*C.int64_t)(&uptr[0]), (*C.int32_t)(&idx[0]),
+			(*C.float)(&val[0]), (*C.int32_t)(&lead[0]), C.int64_t(n), (*C.int32_t)(&user[0]), (*C.int32_t)(&item[0]),
+			(*C.float)(&target[0]))
+	} else {
+		rc = C.gorse_fm_set_test_samples(fm.hip.h, C.int64_t(nUsers), (*C.int64_t)(&uptr[0]), (*C.int32_t)(&idx[0]),
+			(*C.float)(&val[0]), (*C.int32_t)(&lead[0]), C.int64_t(n), (*C.int32_t)(&user[0]), (*C.int32_t)(&item[0]),
+			(*C.float)(&target[0]))
+	}
+	if rc != 0 {
+		log.Logger().Warn("fit AFM: the sample-form set was refused, keeping the padded route",
+			zap.Bool("train", train), zap.Int("samples", n), zap.String("error", C.GoString(C.gorse_hip_last_error())))
+		return false
+	}
+	return true
+}
+
+// SetTrainSamples / SetTestSamples: a Fit in sample form calls SetRankItems once, then these two, and trains and evaluates
+// with the calls fitHIP uses (gorse_fm_epoch, evaluateResidentHIP); the catalogue stays resident for RankUsers.
+func (fm *AFM) SetTrainSamples(users SampleSide, user, item []int32, target []float32) bool {
+	return fm.setSamplesHIP(true, users, user, item, target)
+}
+
+func (fm *AFM) SetTestSamples(users SampleSide, user, item []int32, target []float32) bool {
+	return fm.setSamplesHIP(false, users, user, item, target)
+}
