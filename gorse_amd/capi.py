@@ -155,7 +155,6 @@ SIGNATURES = {
     "gorse_hip_test_sparse_sym_stats": (None, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gorse_hip_test_set_sparse_tile": (None, [C.c_int32]),
     "gorse_hip_test_set_scan_literal": (None, [C.c_int32]),
-    "gorse_hip_test_set_stream_priorities": (None, [C.c_int32]),
     "gorse_hip_test_set_sparse_split": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_heavy": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_atomic": (None, [C.c_int32]),
@@ -166,7 +165,6 @@ SIGNATURES = {
     "gorse_hip_test_bpr_finish_capacities": (None, [_i32p, _i32p]),
     "gorse_hip_test_bpr_fail_count": (C.c_int32, [_vp, _i32p]),
     "gorse_hip_test_set_bpr_store_mode": (None, [C.c_int32]),
-    "gorse_hip_test_set_prep_cu_stride": (None, [C.c_int32]),
     "gorse_hip_test_set_sgemm_valu": (None, [C.c_int32]),
     "gorse_hip_test_sgemm_last_ms": (C.c_double, []),
     "gorse_hip_test_set_bpr_cold_window": (None, [C.c_int64]),

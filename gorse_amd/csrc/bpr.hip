@@ -1,8 +1,12 @@
 // bpr.hip -- BPR training step on gfx950.  Reference: model/cf/model.go:446-494.
 //
-// Kernels per chunk of samples (the user-run schedule: the production Hogwild form for >= 4096 users and nFactors 8/16/32/64/128):
+// The sample stream itself -- which draws make sample s, in which order -- is stated once, in bpr_stream.hpp; every sampling and
+// preparation kernel below composes its functions.
+// Kernels per chunk of samples (the user-run schedule: the production Hogwild form for >= 4096 users and nFactors 8/16/32/64/128;
+// launch_prepare_users runs the preparation AHEAD on its own stream, by user bins where the shape has them: see "the preparation
+// by user BINS" below -- the form without bins is):
 //   bpr_sample_user_kernel : model.go:452-458 -- sample s draws its USER from the counter-based Philox stream of sample s and
-//                            takes its rank in that user's run; runs AHEAD on its own stream, like the rest of the preparation.
+//                            takes its rank in that user's run.
 //   scan + bpr_scatter_ids : counting sort of the chunk's SAMPLE IDS by user (the order in which a Hogwild epoch applies its
 //                            samples is free: parallel.go:44-68).
 //   bpr_sample_items_kernel: model.go:459-468 -- one thread per sorted position replays its sample's stream and draws the
@@ -18,6 +22,8 @@
 //                            sequential parity schedule, the racy diagnostic, and the Hogwild schedule of shapes
 //                            with few users or another factor width.
 // HBM-bound: algorithmic bytes per sample = 6*d*4 (three rows read + three written) + 12 (indices).
+// Test switches: the six GORSE_TEST_BPR_* bits of include/gorse_hip_test.h choose between equivalent schedules and preparations;
+// the chunk loop of epoch_impl has two forms, the product's and GORSE_TEST_BPR_STABLE_RANK's.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -30,58 +36,28 @@ using namespace gorse;
 
 namespace {
 
-int g_variant = 0;  // schedule switches of the tests and probes (gorse_hip_test_set_variant); nothing of it reaches a kernel
+int g_variant = 0;  // GORSE_TEST_BPR_* switches of the tests (gorse_hip_test_set_variant); nothing of it reaches a kernel
 constexpr int MODE_ATOMIC = GORSE_BPR_HOGWILD_ATOMIC;
 constexpr int MODE_EXACT = GORSE_BPR_SEQUENTIAL;
 constexpr int MODE_RACY = GORSE_BPR_HOGWILD_RACY;
 constexpr int MODE_STORES = GORSE_BPR_HOGWILD_STORES;  // MODE_ATOMIC with the cold negatives by store (user-run schedule only)
 
-// ---- sampling ------------------------------------------------------------------------------
-__device__ __forceinline__ bool row_contains(const int32_t *__restrict__ row, int64_t n, int32_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        int64_t mid = (lo + hi) >> 1;
-        if (row[mid] < x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo < n && row[lo] == x;
-}
-
+// ---- sampling (the draws themselves: bpr_stream.hpp) ------------------------------------------
 __global__ __launch_bounds__(256) void bpr_sample_kernel(int32_t U, int32_t I, const int64_t *__restrict__ uptr,
                                                          const int32_t *__restrict__ uidx,
                                                          const int32_t *__restrict__ usorted, uint64_t seed,
                                                          uint64_t epoch, int64_t sample_base, int64_t n,
                                                          int32_t *__restrict__ us, int32_t *__restrict__ is,
-                                                         int32_t *__restrict__ js, int32_t *__restrict__ fail_count,
-                                                         int32_t *__restrict__ bucket, int32_t *__restrict__ rank) {
-    // bucket != null (user-run schedule): the sample also draws its arrival rank inside its user's run -- the first pass of
-    // the counting sort by user, done here so that no separate pass over the triplets is needed (skipped samples: key U)
+                                                         int32_t *__restrict__ js, int32_t *__restrict__ fail_count) {
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         Philox g;
         g.init(seed, epoch, (uint64_t)(sample_base + s));
-        int32_t u = -1;
-        int64_t beg = 0, cnt = 0;
-        for (int t = 0; t < kMaxDraws; t++) {
-            int32_t cu = g.int31n(U);
-            beg = uptr[cu];
-            cnt = uptr[cu + 1] - beg;
-            if (cnt > 0) {
-                u = cu;
-                break;
-            }
-        }
+        int32_t u = draw_user(g, U, uptr);
         int32_t pi = -1, nj = -1;
         if (u >= 0) {
+            const int64_t beg = uptr[u], cnt = uptr[u + 1] - beg;
             pi = uidx[beg + g.int31n((int32_t)cnt)];
-            for (int t = 0; t < kMaxDraws; t++) {
-                int32_t c = g.int31n(I);
-                if (!row_contains(usorted + beg, cnt, c)) {
-                    nj = c;
-                    break;
-                }
-            }
+            nj = draw_negative(g, I, usorted + beg, cnt);
         }
         if (u < 0 || nj < 0) {
             atomicAdd(fail_count, 1);
@@ -90,7 +66,6 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(int32_t U, int32_t I, c
         us[s] = u;
         is[s] = pi;
         js[s] = nj;
-        if (bucket) rank[s] = atomicAdd(&bucket[u < 0 ? U : u], 1);
     }
 }
 
@@ -112,16 +87,7 @@ __global__ __launch_bounds__(256) void bpr_sample_user_kernel(int32_t U, const i
                                                               int32_t *__restrict__ key, int32_t *__restrict__ fail_count,
                                                               int32_t *__restrict__ bucket, int32_t *__restrict__ rank) {
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        Philox g;
-        g.init(seed, epoch, (uint64_t)(sample_base + s));
-        int32_t u = -1;
-        for (int t = 0; t < kMaxDraws; t++) {
-            const int32_t cu = g.int31n(U);
-            if (uptr[cu + 1] > uptr[cu]) {
-                u = cu;
-                break;
-            }
-        }
+        const int32_t u = redraw_user(seed, epoch, (uint64_t)(sample_base + s), U, uptr);
         if (u < 0) atomicAdd(fail_count, 1);
         key[s] = u;
         rank[s] = atomicAdd(&bucket[u < 0 ? U : u], 1);
@@ -136,22 +102,6 @@ __global__ __launch_bounds__(256) void bpr_scatter_ids_kernel(const int32_t *__r
         const int64_t pos = (int64_t)bucket[k] + rank[s];
         pairs[pos] = make_int2((int32_t)s, key[s]);  // (sample id, user) at the sorted position: one 8-byte store
     }
-}
-
-// the item draws of one sample from the start of its stream (model.go:452-468): the path of a sample whose first negative candidate
-// was one of the user's own items -- the batch in bpr_sample_items_kernel only carries the first candidate
-__device__ __forceinline__ int32_t draw_negative_again(int32_t U, int32_t I, const int32_t *__restrict__ row, int64_t cnt, int32_t u,
-                                                    uint64_t seed, uint64_t epoch, uint64_t sample) {
-    Philox g;
-    g.init(seed, epoch, sample);
-    for (int k = 0; k < kMaxDraws; k++)
-        if (g.int31n(U) == u) break;
-    (void)g.int31n((int32_t)cnt);  // the positive's draw
-    for (int k = 0; k < kMaxDraws; k++) {
-        const int32_t c = g.int31n(I);
-        if (!row_contains(row, cnt, c)) return c;
-    }
-    return -1;
 }
 
 __global__ __launch_bounds__(256) void bpr_sample_items_kernel(int32_t U, int32_t I, const int64_t *__restrict__ uptr,
@@ -170,17 +120,9 @@ __global__ __launch_bounds__(256) void bpr_sample_items_kernel(int32_t U, int32_
         const int64_t cnt = uptr[u + 1] - rbeg;
         Philox g;
         g.init(seed, epoch, (uint64_t)(sample_base + pr.x));
-        // the user draw again: rows drawn before u were empty (u is the first non-empty one), no look-up needed
-        for (int k = 0; k < kMaxDraws; k++)
-            if (g.int31n(U) == u) break;
-        int32_t pi = uidx[rbeg + g.int31n((int32_t)cnt)], nj = -1;
-        for (int k = 0; k < kMaxDraws; k++) {
-            const int32_t c = g.int31n(I);
-            if (!row_contains(usorted + rbeg, cnt, c)) {
-                nj = c;
-                break;
-            }
-        }
+        replay_user(g, U, u);
+        int32_t pi = uidx[rbeg + g.int31n((int32_t)cnt)];
+        const int32_t nj = draw_negative(g, I, usorted + rbeg, cnt);
         if (nj < 0) {
             atomicAdd(fail_count, 1);
             pi = -1;
@@ -226,7 +168,7 @@ __global__ __launch_bounds__(256) void bpr_sample_items_batch_kernel(int32_t U, 
         for (int e = 0; e < B; e++) {
             Philox g;
             g.init(seed, epoch, (uint64_t)(sample_base + sid[e]));
-            // the user draw again: rows drawn before u were empty (u is the first non-empty one), no look-up needed
+            // replay_user, inline: four independent chains per thread (and no draw at all for a position without a user)
             for (int k = 0; k < kMaxDraws; k++)
                 if (cnt[e] == 0 || g.int31n(U) == u[e]) break;
             const int32_t r = g.int31n(cnt[e] > 0 ? cnt[e] : 1);
@@ -262,7 +204,7 @@ __global__ __launch_bounds__(256) void bpr_sample_items_batch_kernel(int32_t U, 
             if (t >= n || u[e] < 0) continue;
             int32_t nj = c[e];
             if (at[e] == c[e])  // the candidate is one of the user's items: the rest of the draws, one at a time
-                nj = draw_negative_again(U, I, usorted + rbeg[e], cnt[e], u[e], seed, epoch, (uint64_t)(sample_base + sid[e]));
+                nj = redraw_negative(seed, epoch, (uint64_t)(sample_base + sid[e]), U, I, u[e], usorted + rbeg[e], cnt[e]);
             if (nj < 0) atomicAdd(fail_count, 1);
             si[t] = nj < 0 ? -1 : pi[e];
             sj[t] = nj;
@@ -314,19 +256,6 @@ __device__ __forceinline__ int32_t block_exclusive_scan(int32_t v, int32_t *lds 
     return base + x - v;
 }
 
-// the user draw of a sample whose FIRST draw met a user without feedback: the stream again from its start (model.go:452-458)
-__device__ __forceinline__ int32_t draw_user_again(int32_t U, const int64_t *__restrict__ uptr, uint64_t seed, uint64_t epoch,
-                                                uint64_t sample, int32_t *__restrict__ fail_count) {
-    Philox g;
-    g.init(seed, epoch, sample);
-    for (int t = 0; t < kMaxDraws; t++) {
-        const int32_t cu = g.int31n(U);
-        if (uptr[cu + 1] > uptr[cu]) return cu;
-    }
-    atomicAdd(fail_count, 1);
-    return -1;
-}
-
 __global__ __launch_bounds__(kBinThreads) void bpr_bin_count_kernel(int32_t U, const int64_t *__restrict__ uptr, uint64_t seed,
                                                                     uint64_t epoch, int64_t sample_base, int64_t n, int64_t tile,
                                                                     int shift, int nbins, int32_t *__restrict__ key,
@@ -356,7 +285,10 @@ __global__ __launch_bounds__(kBinThreads) void bpr_bin_count_kernel(int32_t U, c
             const int64_t s = sb + (int64_t)e * kBinThreads;
             if (s < s1) {
                 int32_t u = r1[e] > r0[e] ? cu[e] : -1;
-                if (u < 0) u = draw_user_again(U, uptr, seed, epoch, (uint64_t)(sample_base + s), fail_count);
+                if (u < 0) {  // the first draw met a user without feedback: the stream again from its start
+                    u = redraw_user(seed, epoch, (uint64_t)(sample_base + s), U, uptr);
+                    if (u < 0) atomicAdd(fail_count, 1);
+                }
                 key[s] = u;
                 atomicAdd(&hist[(u < 0 ? U : u) >> shift], 1);
             }
@@ -669,16 +601,6 @@ __device__ __forceinline__ uint64_t lane_copy(uint64_t x) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// the negative of a sample (model.go:462-468) from the generator behind the positive's draw; ROW: the user's sorted row, LDS or global
-template <typename ROW>
-__device__ __forceinline__ int32_t draw_negative(Philox &g, int32_t I, ROW row, int32_t cnt) {
-    for (int k = 0; k < kMaxDraws; k++) {
-        const int32_t c = g.int31n(I);
-        if (!row_contains(row, cnt, c)) return c;
-    }
-    return -1;
-}
-
 __global__ __launch_bounds__(kFinThreads) void bpr_bin_finish_kernel(int32_t U, int32_t I, int shift, const int32_t *__restrict__ bin_start,
                                                                      const int2 *__restrict__ bp, const int64_t *__restrict__ uptr,
                                                                      const int32_t *__restrict__ uidx,
@@ -763,9 +685,7 @@ __global__ __launch_bounds__(kFinThreads) void bpr_bin_finish_kernel(int32_t U, 
                 Philox g;
                 // (lane_copy: without it this kernel spills scalar registers -- tests/test_bpr_bin_finish_cpu.py is what says so)
                 g.init(lane_copy(seed), epoch, (uint64_t)(sample_base + sid));
-                // the user draw again: rows drawn before u were empty (u is the first non-empty one), no look-up needed
-                for (int k = 0; k < kMaxDraws; k++)
-                    if (g.int31n(U) == u) break;
+                replay_user(g, U, u);
                 const int32_t r = g.int31n(n_u);
                 const int32_t pi = staged_idx ? rows[range + ro + r] : uidx[rbase + ro + r];
                 const int32_t nj = staged ? draw_negative(g, I, rows + ro, n_u) : draw_negative(g, I, usorted + rbase + ro, n_u);
@@ -1093,7 +1013,7 @@ __global__ __launch_bounds__(256) void bpr_fold_kernel(HotRows hot, float *Q) {
 // ---- counting sort by user ---------------------------------------------------------------------
 constexpr int kScanTile = 2048;  // elements per workgroup of the scan (256 threads x 8)
 
-// first pass of the counting sort for callers whose sampler did not rank (gorse_bpr_apply_triplets, the stable-rank test hook):
+// first pass of the counting sort of whole triplets (launch_user_sort: gorse_bpr_apply_triplets, GORSE_TEST_BPR_STABLE_RANK):
 // rank[s] = arrival rank of sample s among the samples of its key; keys < 0 (skipped samples) count under key K
 __global__ __launch_bounds__(256) void bpr_rank_kernel(const int32_t *__restrict__ key, int64_t n, int32_t K,
                                                        int32_t *__restrict__ bucket, int32_t *__restrict__ rank) {
@@ -1429,21 +1349,17 @@ int32_t exclusive_scan_i32(int32_t *data, int64_t m, int32_t *tmp, hipStream_t s
 }
 
 
-// counting sort of the chunk by user: `sorted` receives su | si | sj, bucket[0..U] the run offsets
-// ranked: the sampler already counted the runs into `bucket` and wrote every sample's rank (launch_sampler with a bucket)
+// counting sort of the chunk's triplets by user: `sorted` receives su | si | sj, bucket[0..U] the run offsets
 int32_t launch_user_sort(gorse_mf *h, const int32_t *trip, int32_t *sorted, int32_t *bucket, int32_t *rank, int64_t n, size_t cap,
-                         hipStream_t st, bool ranked) {
+                         hipStream_t st) {
     const int64_t m = h->U + 2;  // one counter per user + one for skipped samples (sorted last) + the end offset
     const int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 256 * 8);
-    if (!ranked) {
-        GORSE_HIP_CHECK(hipMemsetAsync(bucket, 0, (size_t)m * sizeof(int32_t), st));
-        // key = user, skipped samples (u < 0) get key U
-        // test hook (variant bit 29): one thread ranks the samples in stream order -> every run keeps the stream's order
-        if (g_variant & (1 << 29))
-            bpr_rank_kernel<<<dim3(1), dim3(1), 0, st>>>(trip, n, (int32_t)h->U, bucket, rank);
-        else
-            bpr_rank_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(trip, n, (int32_t)h->U, bucket, rank);
-    }
+    GORSE_HIP_CHECK(hipMemsetAsync(bucket, 0, (size_t)m * sizeof(int32_t), st));
+    // key = user, skipped samples (u < 0) get key U; GORSE_TEST_BPR_STABLE_RANK: one thread ranks the samples in stream order
+    if (g_variant & GORSE_TEST_BPR_STABLE_RANK)
+        bpr_rank_kernel<<<dim3(1), dim3(1), 0, st>>>(trip, n, (int32_t)h->U, bucket, rank);
+    else
+        bpr_rank_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(trip, n, (int32_t)h->U, bucket, rank);
     GORSE_TRY(exclusive_scan_i32(bucket, m, h->scan_tmp2.p, st));
     bpr_scatter_by_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(trip, trip, trip + cap, trip + 2 * cap, n,
                                                                        (int32_t)h->U, bucket, rank, sorted,
@@ -1473,7 +1389,7 @@ int32_t ensure_user_sort(gorse_mf *h) {
 // user runs need enough users to fill the chip with one 16-lane group each (4096 groups = one wave per SIMD) and a
 // register-resident factor width; otherwise the per-sample schedule is the faster one (S-ml100k: 943 users)
 bool user_runs_supported(const gorse_mf *h) {
-    return (h->d == 8 || h->d == 16 || h->d == 32 || h->d == 64 || h->d == 128) && (h->U >= 4096 || (g_variant & 128));
+    return (h->d == 8 || h->d == 16 || h->d == 32 || h->d == 64 || h->d == 128) && (h->U >= 4096 || (g_variant & GORSE_TEST_BPR_USER_RUNS));
 }
 
 // which item updates may take the store route (gorse_hip_test_set_bpr_store_mode)
@@ -1506,11 +1422,11 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     const int64_t capb = 256 * 16;
     if (blocks > capb) blocks = capb;
     HotRows hot = make_hot(h);
-    const int folders = h->n_hot > 0 && !(g_variant & 32) ? open_hot(h, hot) : 0;
+    const int folders = h->n_hot > 0 ? open_hot(h, hot) : 0;
     blocks += folders;
     // the negative's slot look-up is one more gather per sample: where a draw has a fair chance of meeting a hot item (hot_rows.hpp;
     // gorse_mf_create counted the negatives into the replica counts by the same rule)
-    const int neg_rep = !(g_variant & (1 << 25)) && hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I) ? 1 : 0;
+    const int neg_rep = hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I) ? 1 : 0;
     dim3 grid((unsigned)blocks), block(kBlock);
     // cold items by store only in GORSE_BPR_HOGWILD_STORES and where the handle has any (n_cold) -- the atomics-only instantiation otherwise
     const bool neg_store = stores && h->n_cold > 0 && g_store_mode == 1;
@@ -1552,7 +1468,7 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
     const int64_t cap = 256 * 16;  // 16 workgroups of 4 waves per CU: grid-stride beyond that
     if (blocks > cap) blocks = cap;
     HotRows hot = make_hot(h);
-    const int folders = MODE == MODE_ATOMIC && h->n_hot > 0 && !(g_variant & 32) ? open_hot(h, hot) : 0;
+    const int folders = MODE == MODE_ATOMIC && h->n_hot > 0 ? open_hot(h, hot) : 0;
     blocks += folders;
     dim3 grid((unsigned)blocks), block(kBlock);
 #define LAUNCH(NC, SH)                                                                                               \
@@ -1593,14 +1509,12 @@ int32_t launch_update(gorse_mf *h, int mode, const int32_t *us, const int32_t *i
 }
 
 int32_t launch_sampler(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t base, int64_t n, int32_t *trip, size_t cap,
-                       hipStream_t st, int32_t *bucket = nullptr, int32_t *rank = nullptr, hipEvent_t start = nullptr,
-                       hipEvent_t stop = nullptr) {
+                       hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
     if (n <= 0) return GORSE_OK;
     int64_t blocks = std::min<int64_t>(ceil_div(n, 256), 256 * 8);
-    if (bucket) GORSE_HIP_CHECK(hipMemsetAsync(bucket, 0, (size_t)(h->U + 2) * sizeof(int32_t), st));
     hipExtLaunchKernelGGL(bpr_sample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, start, stop, 0, (int32_t)h->U, (int32_t)h->I,
                           h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, n, trip, trip + cap, trip + 2 * cap,
-                          h->fail_count.p, bucket, rank);
+                          h->fail_count.p);
     GORSE_HIP_CHECK(hipGetLastError());
     return GORSE_OK;
 }
@@ -1634,12 +1548,12 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
     };
     // equal positives of a run next to each other (bpr_group_positives_kernel): one wave per run, in place
     auto launch_group = [&]() {
-        if (g_variant & (1 << 20)) return;  // variant bit 20 (probes, A/B): the runs stay in arrival order
+        if (g_variant & GORSE_TEST_BPR_ARRIVAL_ORDER) return;
         h->prof.events(GORSE_PROF_BPR_SORT, &ev_a, &ev_b);
         hipExtLaunchKernelGGL(bpr_group_positives_kernel, dim3((unsigned)std::min<int64_t>(h->U, 256 * 16)), dim3(64), 0, st, ev_a, ev_b, 0,
                               (int32_t)h->U, bucket, sorted + cap, sorted + 2 * cap);
     };
-    if (pb.ok && !(g_variant & (1 << 21))) {  // variant bit 21 (probes, tests): the preparation without bins
+    if (pb.ok && !(g_variant & GORSE_TEST_BPR_NO_BINS)) {
         int32_t *key = trip;
         int2 *bp = reinterpret_cast<int2 *>(trip + cap), *pairs = reinterpret_cast<int2 *>(rank);  // (rank: 2 x cap words, ensure_user_sort)
         int32_t *bin_count = h->ubins.p, *bin_start = h->ubins.p + kMaxBins, *H = h->ubinmat.p;
@@ -1648,8 +1562,8 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
         // the finish of the bins in one LDS-resident pass (bpr_bin_finish_kernel) where a bin's expected samples are safely under
         // its capacity (the 10M-user set: ~27,500 per bin), a bin's users have a counter each, and the users' rows sit in the L2s:
         // where they do not (C3 shapes) the item draws are bpr_sample_items_batch_kernel's, four chains of look-ups per thread, which
-        // the finish kernel does not have; variant bit 19 (tests, A/B): the three kernels whatever the shape
-        const bool finish = !(g_variant & (1 << 19)) && pb.shift <= kFinShift && n / pb.nbins <= kFinCap / 4 * 3 &&
+        // the finish kernel does not have; GORSE_TEST_BPR_THREE_KERNELS: the three kernels whatever the shape
+        const bool finish = !(g_variant & GORSE_TEST_BPR_THREE_KERNELS) && pb.shift <= kFinShift && n / pb.nbins <= kFinCap / 4 * 3 &&
                             h->uidx.n <= kItemsBatchFrom;
         h->prof.events(GORSE_PROF_BPR_SAMPLE, &ev_a, &ev_b);
         hipExtLaunchKernelGGL(bpr_bin_count_kernel, dim3(tiles), dim3(kBinThreads), 0, st, ev_a, ev_b, 0, (int32_t)h->U, h->uptr.p, seed,
@@ -1664,7 +1578,7 @@ int32_t launch_prepare_users(gorse_mf *h, uint64_t seed, uint64_t epoch, int64_t
             h->prof.events(GORSE_PROF_BPR_SAMPLE, &ev_a, &ev_b);
             hipExtLaunchKernelGGL(bpr_bin_finish_kernel, dim3((unsigned)pb.nbins), dim3(kFinThreads), 0, st, ev_a, ev_b, 0, (int32_t)h->U,
                                   (int32_t)h->I, pb.shift, bin_start, bp, h->uptr.p, h->uidx.p, h->uidx_sorted.p, seed, epoch, base, bucket,
-                                  pairs, sorted + cap, sorted + 2 * cap, h->fail_count.p, (g_variant & (1 << 20)) ? 0 : 1);
+                                  pairs, sorted + cap, sorted + 2 * cap, h->fail_count.p, (g_variant & GORSE_TEST_BPR_ARRIVAL_ORDER) ? 0 : 1);
             GORSE_HIP_CHECK(hipGetLastError());
             return GORSE_OK;
         }
@@ -1762,7 +1676,7 @@ int32_t run_sequential(gorse_mf *h, const int32_t *d_us, const int32_t *d_is, co
 
 // Hogwild schedule: 1 = user runs (bpr_update_user_kernel), 0 = per-sample groups (bpr_update_kernel).  The
 // environment variable GORSE_BPR_SCHEDULE = "users" | "samples" overrides the compiled default (read once);
-// the probe bits of gorse_hip_test_set_variant override both.
+// GORSE_TEST_BPR_USER_RUNS / _PER_SAMPLE of gorse_hip_test_set_variant override both.
 int g_user_runs = 1;
 bool user_runs_default() {
     static const int v = [] {
@@ -1773,7 +1687,9 @@ bool user_runs_default() {
     }();
     return v != 0;
 }
-bool user_runs_enabled() { return (g_variant & 128) ? true : ((g_variant & (1 << 28)) ? false : user_runs_default()); }
+bool user_runs_enabled() {
+    return (g_variant & GORSE_TEST_BPR_USER_RUNS) ? true : ((g_variant & GORSE_TEST_BPR_PER_SAMPLE) ? false : user_runs_default());
+}
 int g_exp_mode_exact = 0;  // exp flavour of the sequential schedule; tests flip it to 1 for bit parity
 
 int32_t check_mode(int mode) {
@@ -1799,12 +1715,12 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
     // stream carries the wait on the chunk's preparation and nothing else: the epoch's end, the chunk's "consumed" event and the
     // profile's span are the launch's own events (ev_consumed, mf_internal.hpp).  An epoch that does not begin where the one before it
     // ended takes its begin from its first update launch (ep_begin) -- unless something else of the epoch comes first on the stream (the
-    // loss memset, the sequential schedule's sampler, the sort of variant bits 27 / 29) or the profile needs that launch's start event:
-    // then the begin is recorded where the stream reaches the epoch, as the only marker packet of the epoch.
+    // loss memset, the sequential schedule's sampler, the sort of GORSE_TEST_BPR_STABLE_RANK) or the profile needs that launch's start
+    // event: then the begin is recorded where the stream reaches the epoch, as the only marker packet of the epoch.
     const bool uruns = (mode == MODE_ATOMIC || mode == MODE_STORES) && user_runs_enabled() && user_runs_supported(h);
-    const bool sort_on_update_stream = uruns && ((g_variant & (1 << 29)) || (g_variant & (1 << 27)));
+    const bool stable_rank = uruns && (g_variant & GORSE_TEST_BPR_STABLE_RANK);  // the sort on the update stream, by one thread
     hipEvent_t ep_begin = nullptr, ep_end = nullptr;
-    GORSE_TRY(mf_epoch_begin(h, chained, d_loss || mode == MODE_EXACT || sort_on_update_stream || (g_variant & (1 << 22)) || h->prof.on, &ep_begin));
+    GORSE_TRY(mf_epoch_begin(h, chained, d_loss || mode == MODE_EXACT || stable_rank || h->prof.on, &ep_begin));
     if (d_loss) GORSE_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), h->stream));
     const int64_t cap = (int64_t)h->trip_cap;
     if (mode == MODE_EXACT) {
@@ -1832,37 +1748,24 @@ int32_t epoch_impl(gorse_mf *h, int64_t n_samples, float lr, float reg, uint64_t
                 return fail(GORSE_ERR_CANCELLED, "cancelled");
             }
             int32_t *tb = h->trip[b].p;
-            // variant bit 22 (probes): the preparation on the update stream, so that a kernel timeline shows every kernel alone
-            const hipStream_t prep = (g_variant & (1 << 22)) ? h->stream : h->stream2;
+            const hipStream_t prep = h->stream2;
             // the update launch that last read this buffer (none: the first two chunks of a handle, or the streams were drained since)
             if (h->ev_consumed[b]) GORSE_HIP_CHECK(hipStreamWaitEvent(prep, h->ev_consumed[b], 0));
-            // user runs: the whole preparation of chunk c + 1 (launch_prepare_users) runs on the sampler stream under the update
-            // kernel of chunk c.  Variant bit 27: the round-3 preparation (whole triplets sampled per sample, then scattered) with the sort on the
-            // update stream; bit 26: the same with the sort on the sampler stream.
-            const bool fused = uruns && !(g_variant & (1 << 29)) && !(g_variant & (1 << 27));
-            const bool by_run = fused && !(g_variant & (1 << 26));
-            if (by_run) {
+            // user runs: the whole preparation of chunk c + 1 (launch_prepare_users) runs on the preparation stream under the update
+            // kernel of chunk c; otherwise (the per-sample schedule, GORSE_TEST_BPR_STABLE_RANK) the sampler alone, its span the launch's own
+            if (uruns && !stable_rank) {
                 GORSE_TRY(launch_prepare_users(h, seed, epoch, base + s0, m, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p,
                                                (size_t)cap, prep));
             } else {
-                // the sampler alone: its span is the launch's own; with the run counters (fused) a memset goes first and the span is recorded
-                int tok = fused ? h->prof.begin(GORSE_PROF_BPR_SAMPLE, prep) : -1;
                 hipEvent_t sa = nullptr, sb = nullptr;
-                if (!fused) h->prof.events(GORSE_PROF_BPR_SAMPLE, &sa, &sb);
-                GORSE_TRY(launch_sampler(h, seed, epoch, base + s0, m, tb, (size_t)cap, prep, fused ? h->ubucket[b].p : nullptr,
-                                         fused ? h->urank[b].p : nullptr, sa, sb));
-                h->prof.end(tok, prep);
-                if (fused) {
-                    tok = h->prof.begin(GORSE_PROF_BPR_SORT, prep);
-                    GORSE_TRY(launch_user_sort(h, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p, m, (size_t)cap, prep, true));
-                    h->prof.end(tok, prep);
-                }
+                h->prof.events(GORSE_PROF_BPR_SAMPLE, &sa, &sb);
+                GORSE_TRY(launch_sampler(h, seed, epoch, base + s0, m, tb, (size_t)cap, prep, sa, sb));
             }
             GORSE_HIP_CHECK(hipEventRecord(h->ev_sampled[b], prep));
             GORSE_HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_sampled[b], 0));
-            if (uruns && !fused) {
+            if (stable_rank) {  // the triplets ranked by one thread and scattered, on the update stream
                 const int tok = h->prof.begin(GORSE_PROF_BPR_SORT, h->stream);
-                GORSE_TRY(launch_user_sort(h, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p, m, (size_t)cap, h->stream, false));
+                GORSE_TRY(launch_user_sort(h, tb, h->sorted[b].p, h->ubucket[b].p, h->urank[b].p, m, (size_t)cap, h->stream));
                 h->prof.end(tok, h->stream);
             }
             // the launch's events: start = the profile's span, or the epoch's begin (first chunk, not chained, profiling off); stop = the
@@ -1903,7 +1806,10 @@ extern "C" int32_t gorse_mf_bpr_schedule(gorse_mf *h, int32_t *user_runs) {
     *user_runs = (user_runs_enabled() && user_runs_supported(h)) ? 1 : 0;
     return GORSE_OK;
 }
-extern "C" void gorse_hip_test_set_variant(int32_t v) { g_variant = v; }
+extern "C" void gorse_hip_test_set_variant(int32_t v) {
+    g_variant = v & (GORSE_TEST_BPR_USER_RUNS | GORSE_TEST_BPR_PER_SAMPLE | GORSE_TEST_BPR_STABLE_RANK | GORSE_TEST_BPR_THREE_KERNELS |
+                     GORSE_TEST_BPR_ARRIVAL_ORDER | GORSE_TEST_BPR_NO_BINS);
+}
 extern "C" void gorse_hip_test_set_bpr_chunk(int64_t samples) { g_chunk_override = samples; }
 extern "C" int32_t gorse_hip_test_bpr_fail_count(gorse_mf *h, int32_t *count) {
     if (!h || !count) return fail(GORSE_ERR_INVALID, "NULL argument");
@@ -2023,7 +1929,7 @@ extern "C" int32_t gorse_bpr_apply_triplets(gorse_mf *h, const int32_t *u, const
                                      nullptr, nullptr));
         } else if ((mode == MODE_ATOMIC || mode == MODE_STORES) && user_runs_enabled() && user_runs_supported(h)) {
             GORSE_TRY(ensure_user_sort(h));
-            GORSE_TRY(launch_user_sort(h, tb, h->sorted[0].p, h->ubucket[0].p, h->urank[0].p, m, (size_t)cap, h->stream, false));
+            GORSE_TRY(launch_user_sort(h, tb, h->sorted[0].p, h->ubucket[0].p, h->urank[0].p, m, (size_t)cap, h->stream));
             GORSE_TRY(launch_update_users(h, h->sorted[0].p, h->ubucket[0].p, (size_t)cap, lr, reg, g_exp_mode_exact, nullptr,
                                           h->stream, mode == MODE_STORES));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));

@@ -15,6 +15,7 @@
 
 #include "../../include/gorse_hip.h"
 #include "../../include/gorse_hip_test.h"
+#include "bpr_stream.hpp"  // Philox, kMaxDraws and the BPR sample stream
 
 namespace gorse {
 
@@ -145,63 +146,6 @@ struct KernelProfile {
         for (auto &x : ms) x = 0;
     }
 };
-
-// ---- Philox4x32-10 (Salmon et al., SC'11) + Go math/rand Int31n -------------------------
-struct Philox {
-    uint32_t c0, c1, c2, c3, k0, k1;
-    uint32_t buf[4];
-    int pos;
-    __host__ __device__ inline void init(uint64_t seed, uint64_t epoch, uint64_t sample) {
-        c0 = (uint32_t)sample;
-        c1 = (uint32_t)(sample >> 32);
-        c2 = 0;  // block counter
-        c3 = (uint32_t)epoch;
-        k0 = (uint32_t)seed;
-        k1 = (uint32_t)(seed >> 32);
-        pos = 4;
-    }
-    __host__ __device__ inline void block() {
-        uint32_t a0 = c0, a1 = c1, a2 = c2, a3 = c3, x0 = k0, x1 = k1;
-#pragma unroll
-        for (int r = 0; r < 10; r++) {
-            uint64_t p0 = (uint64_t)0xD2511F53u * a0;
-            uint64_t p1 = (uint64_t)0xCD9E8D57u * a2;
-            uint32_t n0 = (uint32_t)(p1 >> 32) ^ a1 ^ x0;
-            uint32_t n1 = (uint32_t)p1;
-            uint32_t n2 = (uint32_t)(p0 >> 32) ^ a3 ^ x1;
-            uint32_t n3 = (uint32_t)p0;
-            a0 = n0;
-            a1 = n1;
-            a2 = n2;
-            a3 = n3;
-            x0 += 0x9E3779B9u;
-            x1 += 0xBB67AE85u;
-        }
-        buf[0] = a0;
-        buf[1] = a1;
-        buf[2] = a2;
-        buf[3] = a3;
-        c2++;
-        pos = 0;
-    }
-    __host__ __device__ inline uint32_t int31() {
-        if (pos == 4) block();
-        // static indexing keeps buf in registers on the device
-        uint32_t v = pos == 0 ? buf[0] : pos == 1 ? buf[1] : pos == 2 ? buf[2] : buf[3];
-        pos++;
-        return v >> 1;
-    }
-    // Go math/rand (*Rand).Int31n
-    __host__ __device__ inline int32_t int31n(int32_t n) {
-        if ((n & (n - 1)) == 0) return (int32_t)(int31() & (uint32_t)(n - 1));
-        uint32_t mx = (uint32_t)((1u << 31) - 1 - (1u << 31) % (uint32_t)n);
-        uint32_t v = int31();
-        while (v > mx) v = int31();
-        return (int32_t)(v % (uint32_t)n);
-    }
-};
-
-constexpr int kMaxDraws = 4096;  // per-sample retry cap (the reference spins forever)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

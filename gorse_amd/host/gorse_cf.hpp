@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/gorse_hip.h"
+#include "../csrc/bpr_stream.hpp"
 #include "../csrc/goheap.hpp"
 #include "tpe.hpp"
 
@@ -51,7 +52,7 @@ namespace util {
 class RandomGenerator {
    public:
     explicit RandomGenerator(int64_t seed = 0) { g_.init((uint64_t)seed, 0, 0); }
-    // a generator on one of the library's counter-based streams (csrc/common.hpp Philox: seed, epoch word, sample word)
+    // a generator on one of the library's counter-based streams (csrc/bpr_stream.hpp Philox: seed, epoch word, sample word)
     RandomGenerator(int64_t seed, uint64_t epoch, uint64_t sample) { g_.init((uint64_t)seed, epoch, sample); }
     int32_t Int31n(int32_t n) { return g_.int31n(n); }
     int Intn(int n) { return (int)g_.int31n((int32_t)n); }
@@ -100,34 +101,7 @@ class RandomGenerator {
     }
 
    private:
-    struct Px {  // host copy of csrc/common.hpp's Philox (kept header-only here)
-        uint32_t c0, c1, c2, c3, k0, k1, buf[4];
-        int pos;
-        void init(uint64_t seed, uint64_t epoch, uint64_t sample) {
-            c0 = (uint32_t)sample, c1 = (uint32_t)(sample >> 32), c2 = 0, c3 = (uint32_t)epoch;
-            k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), pos = 4;
-        }
-        void block() {
-            uint32_t a0 = c0, a1 = c1, a2 = c2, a3 = c3, x0 = k0, x1 = k1;
-            for (int r = 0; r < 10; r++) {
-                uint64_t p0 = (uint64_t)0xD2511F53u * a0, p1 = (uint64_t)0xCD9E8D57u * a2;
-                uint32_t n0 = (uint32_t)(p1 >> 32) ^ a1 ^ x0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ a3 ^ x1,
-                         n3 = (uint32_t)p0;
-                a0 = n0, a1 = n1, a2 = n2, a3 = n3, x0 += 0x9E3779B9u, x1 += 0xBB67AE85u;
-            }
-            buf[0] = a0, buf[1] = a1, buf[2] = a2, buf[3] = a3, c2++, pos = 0;
-        }
-        uint32_t int31() {
-            if (pos == 4) block();
-            return buf[pos++] >> 1;
-        }
-        int32_t int31n(int32_t n) {
-            if ((n & (n - 1)) == 0) return (int32_t)(int31() & (uint32_t)(n - 1));
-            uint32_t mx = (uint32_t)((1u << 31) - 1 - (1u << 31) % (uint32_t)n), v = int31();
-            while (v > mx) v = int31();
-            return (int32_t)(v % (uint32_t)n);
-        }
-    } g_;
+    Philox g_;  // csrc/bpr_stream.hpp: the generator the device sampler uses
     bool have_ = false;
     double spare_ = 0;
 };

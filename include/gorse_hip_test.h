@@ -17,13 +17,14 @@ extern "C" {
  * 1 = the float32 FreeBSD/math32 scheme restated in oracle/gorse_oracle.c (orc_exp_restated),
  * which makes device and oracle factors comparable bit for bit. */
 void gorse_hip_test_set_exact_exp(int32_t mode);
-/* schedule switches of the Hogwild update path (bit 5: no hot-row replicas = the round-1 kernel; bit 7: force the user-run schedule (triplets counting-sorted by user, p_u
- * register-resident over a user's samples), bit 25: the user-run schedule sends only the POSITIVE item's update of a hot item
- * through the replicas (round 2), bit 28: force the per-sample schedule, bit 29: the user sort ranks
- * samples in stream order (single thread; makes a run's order deterministic for the parity test), bit 21: the user-run
- * schedule's chunk preparation WITHOUT user bins (round 4's form: a returning atomic per sample on its user's run counter),
- * bit 22: the chunk preparation on the update stream instead of beside it (kernel timelines: every kernel alone).  Used by
- * scripts/gpu_probe_*.py and the tests; 0 (the default) is the only value the product ever runs with. */
+/* Switches of the BPR Hogwild path, for the parity tests: OR of the six bits below.  Every other bit is ignored; 0 (the default)
+ * is the only value the product ever runs with. */
+#define GORSE_TEST_BPR_USER_RUNS (1 << 7)       /* the user-run schedule whatever the number of users (product: from 4096 users on) */
+#define GORSE_TEST_BPR_PER_SAMPLE (1 << 28)     /* the per-sample schedule whatever the shape (USER_RUNS wins where both are set) */
+#define GORSE_TEST_BPR_STABLE_RANK (1 << 29)    /* one thread ranks a chunk's samples in stream order: every run keeps the stream's order */
+#define GORSE_TEST_BPR_THREE_KERNELS (1 << 19)  /* the bins' sort, item draws and grouping as three kernels, not bpr_bin_finish_kernel */
+#define GORSE_TEST_BPR_ARRIVAL_ORDER (1 << 20)  /* a run's samples stay in arrival order: equal positives are not brought together */
+#define GORSE_TEST_BPR_NO_BINS (1 << 21)        /* the chunk preparation without user bins: an atomic per sample on its user's counter */
 void gorse_hip_test_set_variant(int32_t variant);
 /* top-k path choice: 0 = automatic (MFMA sweep for >= 768 queries, any of the three metrics, k <= 255), 1 = always the
  * literal scan (path A), 2 = the MFMA sweep whenever its operands exist.  Both paths return identical results;
@@ -75,12 +76,6 @@ int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out16 /*host*/
 /* 1 = every query of the literal scan (path A) goes through the one-thread-per-query heap kernel; 0 (default) = the queries whose
  * k + 1 smallest distances are pairwise distinct are answered by select_fast_kernel (same results). */
 void gorse_hip_test_set_scan_literal(int32_t on);
-/* probe: 1 = a gorse_mf handle created afterwards runs its update stream at the device's highest stream priority and its
- * sampler / sort stream at the lowest; 0 (default) = both at the same priority (measured no better: r02_ak). */
-void gorse_hip_test_set_stream_priorities(int32_t on);
-/* probe: n > 1 = the sampler / sort stream of a gorse_mf handle created afterwards is confined to every n-th CU
- * (hipExtStreamCreateWithCUMask); 0 / 1 = the whole chip (default). */
-void gorse_hip_test_set_prep_cu_stride(int32_t n);
 /* sparse top-k (csrc/sparse*.h*).  Results never depend on any of these.
  * slots: at most this many single-wave workgroups per launch of sparse_tile_kernel (0 = the library's 16 per CU). */
 void gorse_hip_test_set_sparse_slots(int64_t max_slots);
@@ -165,8 +160,8 @@ int32_t gorse_hip_test_bpr_prepare_chunk(gorse_mf *h, int64_t n, uint64_t seed, 
                                          int32_t *off /*U + 2, host*/, int32_t *si /*n, host*/, int32_t *sj /*n, host*/);
 /* the binned preparation finishes a bin in one LDS-resident pass (csrc/bpr.hip bpr_bin_finish_kernel): *samples = the samples of a
  * bin that pass holds (a larger bin goes through it a slice at a time), *row_entries = the entries of a bin's users' rows it copies
- * into LDS at most (longer ranges are read from global memory).  Variant bit 19 of gorse_hip_test_set_variant: the three kernels
- * that pass replaces (sort, item draws, grouping), whatever the shape.  Results never depend on either beyond the order of the
+ * into LDS at most (longer ranges are read from global memory).  GORSE_TEST_BPR_THREE_KERNELS of gorse_hip_test_set_variant: the three
+ * kernels that pass replaces (sort, item draws, grouping), whatever the shape.  Results never depend on either beyond the order of the
  * samples in runs of fewer than 3 or more than 1024. */
 void gorse_hip_test_bpr_finish_capacities(int32_t *samples, int32_t *row_entries);
 /* the handle's counter of BPR samples given up on (no user with feedback or no negative within the draw limit), after its streams

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU probe: where the time of the C2 epoch (S-ml1m, 6040 user runs) goes -- update-kernel ms against the number of samples of the
-epoch (fixed cost against per-sample cost), with and without the hot-row replicas + folder workgroups, at d = 64 and 16.
+epoch (fixed cost against per-sample cost), at d = 64 and 16.
 
 usage: gpu_probe_bpr_c2_scaling.py      Output -> profiles/rNN_*_probe_bpr_c2_scaling.txt"""
 import os
@@ -16,7 +16,7 @@ L = capi.lib()
 data = synth.s_ml1m()
 for d in (64, 16):
     P0, Q0 = synth.init_factors(data.U, data.I, d, 0.0, 0.001, 1)
-    for variant, label in ((128, "replicas"), (128 | 32, "no replicas")):
+    for variant, label in ((1 << 7, "user runs"),):  # GORSE_TEST_BPR_USER_RUNS (include/gorse_hip_test.h)
         L.gorse_hip_test_set_variant(variant)
         mf = capi.MF(data.U, data.I, d, data.uptr, data.uidx)
         for n in (62_500, 125_000, 250_000, 500_000, 994_169, 2_000_000, 4_000_000):

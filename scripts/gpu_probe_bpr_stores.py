@@ -51,10 +51,10 @@ def run_case(name, data, d, epochs, ref_ndcg, variants, n_loss):
     U, I = data.U, data.I
     P0, Q0 = synth.init_factors(U, I, d, 0.0, 0.001, 1)
     share = np.bincount(data.uidx, minlength=I) / float(data.n_train)
-    for label, window, store, extra_variant in variants:
+    for label, window, store in variants:
         L.gorse_hip_test_set_bpr_cold_window(window)
         L.gorse_hip_test_set_bpr_store_mode(store)
-        L.gorse_hip_test_set_variant(128 | extra_variant)
+        L.gorse_hip_test_set_variant(1 << 7)  # GORSE_TEST_BPR_USER_RUNS (include/gorse_hip_test.h)
         mf = capi.MF(U, I, d, data.uptr, data.uidx)
         cold = (share + 1.0 / I) * window < 1.0 if window > 0 else np.zeros(I, bool)
         mf.set_factors(P0, Q0)
@@ -94,9 +94,9 @@ def run_case(name, data, d, epochs, ref_ndcg, variants, n_loss):
 
 
 def store_variants(windows):
-    v = [("atomics only", 0, 0, 0), ("atomics only, round-3 preparation", 0, 0, 1 << 26)]
+    v = [("atomics only", 0, 0)]
     for w in windows:
-        v += [("W=%d stores: negatives" % w, w, 1, 0)]
+        v += [("W=%d stores: negatives" % w, w, 1)]
     return v
 
 

@@ -1,0 +1,85 @@
+"""The BPR sample stream (gorse_amd/csrc/bpr_stream.hpp) without a device: tests/cpp/bpr_stream_main.cpp, built with AddressSanitizer
+and UBSan, draws every sample the three ways the kernels of csrc/bpr.hip compose the header's functions and requires the same
+triplets and the same given-up samples; route 1's triplets are compared here with the oracle's orc_bpr_sample
+(model/cf/model.go:449-468), on every world."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+SEEDS = (1, 0xDEADBEEFCAFE)
+BASES = (0, (1 << 40) + 12345)  # the second one exercises the high counter word
+EPOCHS = (0, 7)
+
+
+def _rows(U, I, lens, seed):
+    rng = np.random.default_rng(seed)
+    uptr = np.zeros(U + 1, np.int64)
+    np.cumsum(lens, out=uptr[1:])
+    rows = [rng.permutation(I)[:n] for n in lens if n > 0]
+    uidx = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
+    return U, I, uptr, uidx
+
+
+def _worlds():
+    """name -> (U, I, uptr, uidx, samples per run)"""
+    w = {}
+    w["1x2"] = _rows(1, 2, np.array([1]), 0) + (1500,)                 # half of the negative candidates are the user's one item
+    w["3x4"] = _rows(3, 4, np.array([0, 2, 4]), 1) + (200,)            # a user without feedback, and one that holds every item
+    rng = np.random.default_rng(2)
+    lens = rng.integers(0, 65, 64)
+    lens[[5, 6, 7]] = 0
+    lens[9] = 64                                                       # (given up on after 4096 draws)
+    lens[10] = 63
+    w["64x64"] = _rows(64, 64, lens, 2) + (1500,)
+    lens = np.where(rng.random(1000) < 0.6, 0, rng.integers(1, 38, 1000))  # most first user draws meet an empty row
+    w["1000x37"] = _rows(1000, 37, lens, 3) + (1500,)
+    # the ragged world of test_prepared_chunk_holds_the_sampled_triplets (tests/test_gpu_cf_parity.py)
+    lens = np.zeros(60, np.int64)
+    lens[::3] = 5
+    lens[3] = 40
+    w["ragged"] = _rows(60, 40, lens, 3) + (1500,)
+    w["no feedback"] = _rows(5, 3, np.zeros(5, np.int64), 4) + (100,)  # every user draw fails
+    return w
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    out = str(tmp_path_factory.mktemp("bpr_stream") / "bpr_stream")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "cpp", "bpr_stream_main.cpp"), "-o", out], check=True)
+    return out
+
+
+@pytest.mark.parametrize("name", list(_worlds()))
+def test_three_compositions_draw_the_oracles_triplets(oracle, exe, tmp_path, name):
+    from oracle import oracle as orc
+    U, I, uptr, uidx, n = _worlds()[name]
+    usorted = orc.sort_rows(uptr, uidx)
+    runs = [(seed, epoch, base) for seed in SEEDS for base in BASES for epoch in EPOCHS]
+    world, out = str(tmp_path / "world.txt"), str(tmp_path / "triplets.txt")
+    with open(world, "w") as f:
+        f.write("%d %d\n%s\n%s\n%s\n%d\n" % (U, I, " ".join(map(str, uptr)), " ".join(map(str, uidx)), " ".join(map(str, usorted)), len(runs)))
+        for seed, epoch, base in runs:
+            f.write("%d %d %d %d\n" % (seed, epoch, base, n))
+    res = subprocess.run([exe, world, out], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "bpr_stream ok" in res.stdout
+    got = np.loadtxt(out, dtype=np.int64).reshape(len(runs), n, 3)
+    given_up = 0
+    for k, (seed, epoch, base) in enumerate(runs):
+        eu, ei, ej = oracle.bpr_sample(U, I, uptr, uidx if len(uidx) else np.zeros(1, np.int32), n, seed, epoch, base,
+                                       sorted_indices=usorted if len(usorted) else np.zeros(1, np.int32))
+        want = np.stack([eu, ei, ej], axis=1).astype(np.int64)
+        want[(want < 0).any(axis=1)] = -1  # a sample given up on is (-1, -1, -1) on both sides (the oracle keeps u and i beside j = -1)
+        assert np.array_equal(got[k], want), (name, seed, epoch, base)
+        given_up += int((want[:, 0] < 0).sum())
+    lens = np.diff(uptr)
+    assert (given_up > 0) == bool((lens == I).any() or not lens.any()), name  # the worlds that must give up do, the others never

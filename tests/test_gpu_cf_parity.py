@@ -556,6 +556,42 @@ def test_prepared_chunk_at_a_size_the_product_takes_the_path(oracle):
         mf.close()
 
 
+def test_prepared_chunk_above_the_item_batch_threshold(oracle):
+    """A handle of 8,396,000 feedbacks, just over the 8 Mi beyond which the item draws of a prepared chunk are
+    bpr_sample_items_batch_kernel's (csrc/bpr.hip kItemsBatchFrom: four positions per thread, the first negative candidate inline, the
+    rest by a restart of the sample's stream) -- the route of every C3 shape.  No test switch.  Three users without feedback, one
+    holding every item (its samples are given up on), every other user half of the items: half of the first candidates are
+    rejected, so the restart is taken throughout.  Asserts what test_prepared_chunk_holds_the_sampled_triplets asserts."""
+    U, I = 4200, 4000
+    lens = np.full(U, I // 2, np.int64)
+    lens[[0, 1777, U - 1]] = 0
+    lens[5] = I
+    uptr = np.zeros(U + 1, np.int64)
+    np.cumsum(lens, out=uptr[1:])
+    assert uptr[-1] == 8_396_000 > 8 << 20
+    rng = np.random.default_rng(19)
+    perm = rng.permuted(np.tile(np.arange(I, dtype=np.int32), (U, 1)), axis=1)  # a user's row: the first lens[u] of its permutation
+    uidx = perm[np.arange(I)[None, :] < lens[:, None]]
+    mf = capi.MF(U, I, 16, uptr, uidx)
+    try:
+        assert mf.bpr_user_runs()
+        n, seed, epoch, base = 200_000, 0x1234_5678_9ABC, 3, (1 << 40) + 12345
+        off, si, sj = mf.bpr_prepare_chunk(n, seed, epoch, base)
+        gu, gi, gj = mf.bpr_sample_triplets(n, seed, epoch, base)
+        assert off[0] == 0 and off[U + 1] == n and (np.diff(off) >= 0).all()
+        su = np.repeat(np.arange(U + 1, dtype=np.int32), np.diff(off))
+        ok = sj[:off[U]] >= 0  # positions past off[U]: samples whose user draw failed (never written)
+        failed = gu < 0
+        assert failed.any() and (gu[~failed] != 5).all()  # the samples of the user that holds every item
+        # a sample the per-sample sampler gave up on (-1, -1, -1) is, here, either without a user or a (-1, -1) in its run
+        assert int(failed.sum()) == int((~ok).sum()) + int(n - off[U])
+        assert np.array_equal(_sorted_triples(su[:off[U]][ok], si[:off[U]][ok], sj[:off[U]][ok]),
+                              _sorted_triples(gu[~failed], gi[~failed], gj[~failed]))
+        assert (si[:off[U]][~ok] == -1).all()
+    finally:
+        mf.close()
+
+
 def test_prepared_chunk_binned_and_unbinned_on_many_users(oracle):
     """The binned preparation (csrc/bpr.hip, bpr_bin_count / _scatter / _sort kernels: bins of 2^shift user ids, here 1024 ids per bin
     and several tiles) and the preparation without bins (variant bit 21) hold the same runs: the triplets of the per-sample sampler,
