@@ -792,8 +792,25 @@ __device__ __forceinline__ void update_elem(float *pu, float *qi, float *qj, int
 // only source of truth for every reader; a hot row's update becomes visible one folder pass (a fold period) late, the same order as the
 // latency of the atomics themselves.  Once every worker workgroup has finished, the folders make a last pass: the launch leaves every
 // replica zero and Q complete, so nothing outside bpr.hip ever sees them.
+// The ACCUMULATED tier (hot_rows.hpp acc_rows_layout; handles whose whole Q fits one XCD's L2): every WARM item has one accumulator
+// row behind the replica rows, and its hot_slot word is that row's code -- to the workers it is a hot item with one replica, so on
+// such a handle no worker atomic lands on a row that anybody gathers (atomics onto rows under agent-scope loads run at 241 G dwords/s
+// on a table of that size, onto rows nobody reads at 311: profiles/r04_s_probe_atomics3.txt).  The tier's slots follow the hot ones in
+// items / meta (n_hot .. n_hot + n_acc) and have folder workgroups of their own, kFolderBlocksAcc of them behind the hot tier's, which
+// pass every kDefaultAccFoldEvery-th fold period; the hot tier's folders and their period are what they are without the tier.  In the last
+// pass all folder workgroups share the rows of both tiers.
 constexpr int kHotReplicas = GORSE_HOT_REPLICAS;
 constexpr int kFolderBlocks = 32;
+// the tier's folders: 2,780 rows x 64 elements at C2 are 178 K (slot, element) pairs, 22 per thread of 32 workgroups and pass -- on
+// the hot tier's 8,192 threads (11 pairs each today) they would not fit the period
+constexpr int kFolderBlocksAcc = 32;
+// Fold periods between two passes of the tier's folders.  A warm item takes at most 1/8192 + 1/I of the updates (3.9e-4 at C2), the
+// hottest item 1.5e-2 and is folded every period: at 4 a warm row's window holds 3.9e-4 x 4 / 1.5e-2 ~ 1/10 of the stale updates the
+// hottest item's window holds, and at nFactors 16 about 50 where the 32 us window that diverged (kDefaultFoldPeriod below) held ~1800.
+// Swept on C2 (profiles/bpr_acc_rows_sweep.txt): 2 / 4 / 8 -> 0.393 / 0.389 / 0.384 ms per epoch at nFactors 64, 0.202 / 0.202 / 0.201
+// at 16; NDCG@10 after 30 epochs stays within 0.006 of the sequential oracle at 2 and 4 and leaves the +-0.01 bar at 8 (nFactors 8, 16).
+constexpr int kDefaultAccFoldEvery = 4;
+int g_acc_fold_every = kDefaultAccFoldEvery;  // gorse_hip_test_set_bpr_acc_fold_every
 // Wall-clock ticks (100 MHz) from the start of one folder pass to the next: how late a hot row's update reaches Q.  Swept on C2
 // (profiles/r07_hr_sweep_replica_unit.txt, replica unit 0.001): 8 / 16 / 32 us -> 0.545 / 0.544 / 0.538 ms per epoch at nFactors 64,
 // 0.295 / 0.293 ms at 16 -- where 32 us DIVERGED (non-finite factors within 23 epochs, three handles of three): the hottest item takes
@@ -806,15 +823,18 @@ uint32_t g_fold_period = kDefaultFoldPeriod;  // gorse_hip_test_set_bpr_fold_per
 constexpr uint64_t kFolderTimeout = 1000000000ull;
 
 struct HotRows {
-    const int32_t *slot;   // I entries: class of an item -- hot_code(first replica row, log2 R_s) of a HOT item, -1 warm, -2 cold
-    const int32_t *items;  // n_hot entries: item of a slot
-    const int32_t *meta;   // n_hot entries: hot_code of a slot
-    float *rep;            // replica rows of d floats, all zero outside an update launch
+    const int32_t *slot;   // I entries: class of an item -- hot_code(first replica row, log2 R_s) of a HOT item, hot_code(its row, 0)
+                           // of an item of the accumulated tier, -1 warm, -2 cold
+    const int32_t *items;  // n_hot + n_acc entries: item of a slot (the hot slots first)
+    const int32_t *meta;   // n_hot + n_acc entries: hot_code of a slot
+    float *rep;            // replica rows, then the tier's rows, of d floats: all zero outside an update launch
     int32_t *done;         // two sets of arrival stripes (worker workgroups that have finished) + the folders' pass count
     int n_hot;
     int d;
     int set;               // the set of stripes this launch counts in (launch parity: the launch zeroes the other one for the next)
     uint32_t period;       // wall-clock ticks between two folder passes
+    int n_acc;             // slots of the accumulated tier (0: the handle has none)
+    int acc_every;         // fold periods between two passes of the tier's folders
 };
 
 // the replica row that group `group` adds a hot item's update to (code: the item's hot_slot word)
@@ -857,12 +877,13 @@ __device__ __forceinline__ bool workers_done(const HotRows &hot, int workers) { 
 }
 
 // one folder pass: (slot, element) pairs strided over the folder threads; each exchanges the slot's R_s rows and adds their sum once
-__device__ __forceinline__ void fold_pass(const HotRows &hot, float *Q, int64_t tid, int64_t nthreads) {
+// (slots [s0, s1): the hot tier's are [0, n_hot))
+__device__ __forceinline__ void fold_pass(const HotRows &hot, float *Q, int s0, int s1, int64_t tid, int64_t nthreads) {
     const int d = hot.d;
-    const int64_t work = (int64_t)hot.n_hot * d;
+    const int64_t work = (int64_t)(s1 - s0) * d;
     for (int64_t w = tid; w < work; w += nthreads) {
-        const int64_t slot = w / d;
-        const int e = (int)(w - slot * d);
+        const int64_t slot = s0 + w / d;
+        const int e = (int)(w - (slot - s0) * d);
         const int32_t code = hot.meta[slot];
         const int nr = 1 << hot_lg(code);
         float *r0 = hot.rep + hot_base(code) * d + e;
@@ -878,19 +899,52 @@ __device__ __forceinline__ void fold_pass(const HotRows &hot, float *Q, int64_t 
     }
 }
 
-// The folder workgroups (blockIdx.x < folders) of an update launch.  Wave 0 polls the workers' arrival count at the grain of one
-// load round trip and decides for the workgroup: a pass when the fold period has run out, and once every worker has finished,
-// with LAST, the last pass (an agent-scope acquire behind the count the workers released into).  So the end of the launch never
-// waits for a folder's sleep, and with LAST no fold kernel follows the launch.
+// one pass over slots [s0, s1) of the accumulated tier (one row each): kAccBatch exchanges of a thread are in flight before the first
+// add that depends on one -- the tier's pass is a few times the hot tier's, and a chain of exchange -> add round trips per pair is
+// what its last pass, at the end of the launch, cannot afford
+constexpr int kAccBatch = 4;
+__device__ __forceinline__ void fold_acc_pass(const HotRows &hot, float *Q, int s0, int s1, int tid, int nthreads) {
+    const int d = hot.d;
+    const int work = (s1 - s0) * d;  // (at most 4 MiB / 4 pairs: hot_rows.hpp kAccTableBytes)
+    for (int wb = tid; wb < work; wb += kAccBatch * nthreads) {
+        float v[kAccBatch];
+        float *q[kAccBatch];
+#pragma unroll
+        for (int b = 0; b < kAccBatch; b++) {
+            const int w = wb + b * nthreads;
+            v[b] = 0.0f;
+            q[b] = Q;
+            if (w < work) {
+                const int slot = s0 + w / d;
+                const int e = w - (slot - s0) * d;
+                q[b] = Q + (int64_t)hot.items[slot] * d + e;
+                v[b] = __hip_atomic_exchange(hot.rep + hot_base(hot.meta[slot]) * d + e, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kAccBatch; b++)
+            if (v[b] != 0.0f) __hip_atomic_fetch_add(q[b], v[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The folder workgroups (blockIdx.x < folders) of an update launch: the hot tier's kFolderBlocks first, then -- on a handle with the
+// accumulated tier -- the tier's own.  Wave 0 polls the workers' arrival count at the grain of one load round trip and decides for the
+// workgroup: a pass over its tier when its period has run out (the hot tier's: the fold period; the accumulated tier's: acc_every of
+// them), and once every worker has finished, with LAST, the last pass (an agent-scope acquire behind the count the workers released
+// into), in which all folder workgroups share the rows of both tiers.  So the end of the launch never waits for a folder's sleep, and
+// with LAST no fold kernel follows the launch.  Both kinds wait in the same loop, under the same bound (kFolderTimeout).
 template <bool LAST>
 __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
     __shared__ int go;
     const int workers = (int)gridDim.x - folders;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)folders * blockDim.x;
+    const int hotf = folders < kFolderBlocks ? folders : kFolderBlocks;  // the hot tier's workgroups
+    const bool acc = (int)blockIdx.x >= hotf;                            // this workgroup serves the accumulated tier
+    const int n_all = hot.n_hot + hot.n_acc;
+    const uint64_t period = acc ? (uint64_t)hot.period * (uint64_t)hot.acc_every : hot.period;
     if (blockIdx.x == 0 && threadIdx.x < kDoneStripes)  // the stripes the launch before this one counted in: zero for the next launch
         __hip_atomic_store(done_set(hot, hot.set ^ 1) + threadIdx.x * kDoneStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t t0 = wall_clock64();
-    uint64_t next = t0 + hot.period;
+    uint64_t next = t0 + period;
     int passes = 0;
     for (;;) {
         if (threadIdx.x < 64) {
@@ -905,7 +959,7 @@ __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
                     }
                     g = 2;
                 } else if (now >= next) {
-                    next = now + hot.period;
+                    next = now + period;
                     g = 1;
                 }
                 go = g;
@@ -914,15 +968,16 @@ __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
         __syncthreads();
         const int g = go;
         __syncthreads();
-        if (g == 2) break;
-        if (g == 1) {
-            fold_pass(hot, Q, tid, nthreads);
-            passes++;
-        }
-    }
-    if constexpr (LAST) {
-        fold_pass(hot, Q, tid, nthreads);
+        if (g == 0) continue;
+        if (g == 2 && !LAST) break;
+        // a periodic pass (g == 1): this workgroup's tier among the workgroups of its kind; the last pass (g == 2): both tiers among all
+        const bool last = g == 2;
+        const int first = last || !acc ? 0 : hotf, among = last ? folders : (acc ? folders - hotf : hotf);
+        const int tid = ((int)blockIdx.x - first) * (int)blockDim.x + (int)threadIdx.x, nthreads = among * (int)blockDim.x;
+        if (last || !acc) fold_pass(hot, Q, 0, hot.n_hot, tid, nthreads);
+        if (last || acc) fold_acc_pass(hot, Q, hot.n_hot, n_all, tid, nthreads);
         passes++;
+        if (last) break;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) hot.done[kFoldPassesWord] = passes;
 }
@@ -952,7 +1007,7 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(float *P, float *Q, 
         if ((u | i | j) < 0) continue;
         float *pu = P + (int64_t)u * d, *qi = Q + (int64_t)i * d, *qj = Q + (int64_t)j * d;
         float *qiw = qi;  // where the positive item's update lands
-        if (MODE == MODE_ATOMIC && hot.n_hot > 0) {
+        if (MODE == MODE_ATOMIC && folders > 0) {  // (a launch has folders where it has rows that take an item's updates: open_hot)
             const int32_t code = hot.slot[i];
             if (code >= 0) qiw = hot_row(hot, code, group);
         }
@@ -992,10 +1047,11 @@ __global__ __launch_bounds__(kBlock) void bpr_update_kernel(float *P, float *Q, 
     if (MODE == MODE_ATOMIC && folders > 0) worker_done<false>(hot);
 }
 
-// after a per-sample update launch: Q[item] += the sum of its replicas, replicas <- 0 (nothing else runs on the stream)
+// after a per-sample update launch: Q[item] += the sum of its replicas, replicas <- 0 (nothing else runs on the stream); the slots
+// of both tiers
 __global__ __launch_bounds__(256) void bpr_fold_kernel(HotRows hot, float *Q) {
     const int d = hot.d;
-    const int64_t work = (int64_t)hot.n_hot * d;
+    const int64_t work = (int64_t)(hot.n_hot + hot.n_acc) * d;
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < work; w += (int64_t)gridDim.x * blockDim.x) {
         const int64_t slot = w / d;
         const int e = (int)(w - slot * d);
@@ -1124,7 +1180,8 @@ __global__ __launch_bounds__(256) void bpr_scatter_by_kernel(const int32_t *__re
 // the other groups' updates keep arriving and only the series' own group reads past them, for the length of the series (<= the
 // run; 2 samples on average at C2, ~9 for a user of 19 feedbacks).  tests/test_gpu_bpr_positive_series.py runs 30 epochs at
 // nFactors 8 and 16.
-// Item classes (hot.slot): >= 0 = replica slot of a HOT item, kWarm = fp32 atomics straight onto the row, kCold = an item whose
+// Item classes (hot.slot): >= 0 = the replica rows of a HOT item or the accumulator row of an item of the accumulated tier,
+// kWarm = fp32 atomics straight onto the row, kCold = an item whose
 // row is touched so rarely (expected touches per `cold window` samples < 1, gorse_mf_create) that the reference's own unlocked
 // load / fma / store (model.go:473-488 under parallel.go:44-81) loses next to nothing: its update is ONE write-through store of
 // fma(t, lr, row) instead of d atomic dwords.  NEG_STORE opens that route for the NEGATIVE item of a sample; the positive's update is
@@ -1169,8 +1226,9 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
     double my_loss = 0.0;
     // which class look-ups this launch needs (every path issues the same loads from a valid address: a look-up nobody needs
     // reads a word that is in cache anyway)
-    const bool look_i = hot.n_hot > 0;
-    const bool look_j = (hot.n_hot > 0 && neg_replicas) || NEG_STORE;
+    const bool open = folders > 0;  // the launch has rows that take an item's updates, of either tier (open_hot)
+    const bool look_i = open;
+    const bool look_j = (open && neg_replicas) || NEG_STORE;
     const int32_t *slot_of = (look_i || look_j) ? hot.slot : si;
     // the items of this group's last two samples: a row one of them wrote is NOT in the snapshot of the current sample (gathered
     // two samples ago), so its update goes through an atomic whatever its class -- a store would overwrite the group's own work
@@ -1239,8 +1297,8 @@ __global__ __launch_bounds__(kBlock) void bpr_update_user_kernel(float *P, float
             const bool more = s < last && continues(i, j, ii[1], jj[1]);  // the next sample continues this one's series
             const bool valid = j >= 0;  // j < 0: the sampler found no negative for this sample (bpr_sample_items_kernel)
             float *qi = Q + (int64_t)cl(i) * d, *qj = Q + (int64_t)cl(j) * d;
-            if (hot.n_hot > 0 && slot >= 0) qi = hot_row(hot, slot, group);
-            if (hot.n_hot > 0 && neg_replicas && slotj >= 0) qj = hot_row(hot, slotj, group);
+            if (open && slot >= 0) qi = hot_row(hot, slot, group);
+            if (open && neg_replicas && slotj >= 0) qj = hot_row(hot, slotj, group);
             bool st_j = false;
             if constexpr (NEG_STORE) {
                 const bool own_j = i == j || j == im1 || j == jm1 || j == im2 || j == jm2;
@@ -1402,14 +1460,16 @@ int g_store_mode = kDefaultStoreMode;  // 1 = NEG_STORE of bpr_update_user_kerne
 // the replica rows of a slot lie next to each other (r04_a: 4 KB apart or n_hot rows apart makes no difference); n_hot stays 0 (no
 // replicas, no folders) until the launch opens them: open_hot
 HotRows make_hot(const gorse_mf *h) {
-    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_meta.p, h->hot_rep.p, h->hot_done.p, 0, h->d, 0, g_fold_period};
+    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_meta.p, h->hot_rep.p, h->hot_done.p, 0, h->d, 0, g_fold_period, 0, g_acc_fold_every};
 }
+bool has_hot(const gorse_mf *h) { return h->n_hot > 0 || h->n_acc > 0; }  // any row that takes an item's updates for it
 // an update launch with folders: the replicas open, the launch's set of arrival stripes by launch parity (the set of the launch before
 // is zeroed by this one's folders; gorse_mf_create zeroed both)
 int open_hot(gorse_mf *h, HotRows &hot) {
     hot.n_hot = h->n_hot;
+    hot.n_acc = h->n_acc;
     hot.set = (int)(h->hot_launches++ & 1);
-    return kFolderBlocks;
+    return kFolderBlocks + (h->n_acc > 0 ? kFolderBlocksAcc : 0);
 }
 
 // start / stop (may be null): events bound to the kernel's own dispatch (hipExtLaunchKernelGGL) -- its timestamps and its completion
@@ -1422,11 +1482,12 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     const int64_t capb = 256 * 16;
     if (blocks > capb) blocks = capb;
     HotRows hot = make_hot(h);
-    const int folders = h->n_hot > 0 ? open_hot(h, hot) : 0;
+    const int folders = has_hot(h) ? open_hot(h, hot) : 0;
     blocks += folders;
     // the negative's slot look-up is one more gather per sample: where a draw has a fair chance of meeting a hot item (hot_rows.hpp;
     // gorse_mf_create counted the negatives into the replica counts by the same rule)
-    const int neg_rep = hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I) ? 1 : 0;
+    // -- and always with the accumulated tier, where every item has a row
+    const int neg_rep = hot.n_acc > 0 || (hot.n_hot > 0 && hot_neg_replicas(hot.n_hot, h->I)) ? 1 : 0;
     dim3 grid((unsigned)blocks), block(kBlock);
     // cold items by store only in GORSE_BPR_HOGWILD_STORES and where the handle has any (n_cold) -- the atomics-only instantiation otherwise
     const bool neg_store = stores && h->n_cold > 0 && g_store_mode == 1;
@@ -1468,7 +1529,7 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
     const int64_t cap = 256 * 16;  // 16 workgroups of 4 waves per CU: grid-stride beyond that
     if (blocks > cap) blocks = cap;
     HotRows hot = make_hot(h);
-    const int folders = MODE == MODE_ATOMIC && h->n_hot > 0 ? open_hot(h, hot) : 0;
+    const int folders = MODE == MODE_ATOMIC && has_hot(h) ? open_hot(h, hot) : 0;
     blocks += folders;
     dim3 grid((unsigned)blocks), block(kBlock);
 #define LAUNCH(NC, SH)                                                                                               \
@@ -1487,7 +1548,7 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
 #undef LAUNCH
     GORSE_HIP_CHECK(hipGetLastError());
     if (folders > 0) {  // (its folders make no last pass: worker_done); the launch's stop event is this kernel's
-        const int64_t fb = std::min<int64_t>(ceil_div((int64_t)hot.n_hot * d, 256), 512);
+        const int64_t fb = std::min<int64_t>(ceil_div((int64_t)(hot.n_hot + hot.n_acc) * d, 256), 512);
         hipExtLaunchKernelGGL(bpr_fold_kernel, dim3((unsigned)fb), dim3(256), 0, st, nullptr, stop, 0, hot, h->Q.p);
         GORSE_HIP_CHECK(hipGetLastError());
     }
@@ -1827,6 +1888,7 @@ extern "C" void gorse_hip_test_set_bpr_store_mode(int32_t store_mode) {
     g_store_mode = store_mode < 0 ? kDefaultStoreMode : (store_mode & 1);
 }
 extern "C" void gorse_hip_test_set_bpr_fold_period(int32_t ticks) { g_fold_period = ticks > 0 ? (uint32_t)ticks : kDefaultFoldPeriod; }
+extern "C" void gorse_hip_test_set_bpr_acc_fold_every(int32_t periods) { g_acc_fold_every = periods > 0 ? periods : kDefaultAccFoldEvery; }
 extern "C" int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3) {
     if (!h || !out3) return fail(GORSE_ERR_INVALID, "NULL argument");
     GORSE_TRY(h->use());
@@ -1851,6 +1913,26 @@ extern "C" int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items, int
         for (size_t s = 0; s < n; s++) replicas[s] = 1 << hot_lg(meta[s]);
     if (rep && h->hot_rows > 0)
         GORSE_HIP_CHECK(hipMemcpy(rep, h->hot_rep.p, (size_t)h->hot_rows * h->d * sizeof(float), hipMemcpyDeviceToHost));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_hip_test_bpr_acc_state(gorse_mf *h, int32_t *items, float *rows) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    const size_t n = (size_t)h->n_acc;
+    if (n == 0) return GORSE_OK;
+    if (items) GORSE_HIP_CHECK(hipMemcpy(items, h->hot_items.p + h->n_hot, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (rows)
+        GORSE_HIP_CHECK(hipMemcpy(rows, h->hot_rep.p + (size_t)h->hot_rows * h->d, n * h->d * sizeof(float), hipMemcpyDeviceToHost));
+    return GORSE_OK;
+}
+extern "C" int32_t gorse_hip_test_bpr_item_classes(gorse_mf *h, int32_t *slot, int64_t *out2) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    if (slot && h->hot_slot.p) GORSE_HIP_CHECK(hipMemcpy(slot, h->hot_slot.p, (size_t)h->I * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out2) out2[0] = h->n_acc, out2[1] = h->n_cold;
     return GORSE_OK;
 }
 

@@ -11,7 +11,8 @@
 namespace gorse {
 
 // A hot item's word (hot_slot[item] and hot_meta[slot]): its first replica row << 4 | log2 of its replica count.  Every other class
-// of hot_slot is negative (-1 warm, -2 cold), so `word >= 0` still means "hot".
+// of hot_slot is negative (-1 warm, -2 cold), so `word >= 0` means "add to that row" -- a hot item's replica or, on a handle with the
+// accumulated tier (below), a warm item's one accumulator row (log2 = 0).
 constexpr int32_t hot_code(int64_t base, int lg) { return (int32_t)((base << 4) | lg); }
 constexpr int64_t hot_base(int32_t code) { return (int64_t)(code >> 4); }
 constexpr int hot_lg(int32_t code) { return code & 15; }
@@ -74,6 +75,47 @@ inline int64_t hot_replica_layout(const std::vector<uint64_t> &acc, int64_t user
         rows += (int64_t)1 << lg;
     }
     return rows;
+}
+
+// class "cold" (-2): an item expected to be touched -- its share of the feedback as a positive, 1 / I as a negative -- less than once
+// per `window` samples (0 = no item is cold)
+inline bool item_is_cold(int64_t cnt, int64_t nnz, int64_t I, int64_t window) {
+    return window > 0 && nnz > 0 && ((double)cnt / (double)nnz + 1.0 / (double)I) * (double)window < 1.0;
+}
+
+// ---- the ACCUMULATED tier: one accumulator row for every warm item of a small catalogue ------------------------------------------
+// Atomics onto rows that the same launch gathers run slower than atomics onto rows nobody reads, and the penalty belongs to small
+// tables: 24 % at 0.9 MB, 6 % at 7.6 MB, 3 % at 268 MB (profiles/r04_s_probe_atomics3.txt: 318 G dwords/s alone, 241 with agent-scope
+// loads of the same rows, 311 with the loads from another table).  Where the whole of Q fits one XCD's L2 (4 MiB) the warm items'
+// updates therefore go to a row of their own too, which the tier's folders add to Q every few fold periods (csrc/bpr.hip).
+constexpr int64_t kAccTableBytes = (int64_t)4 << 20;  // I x nFactors x 4 at most: one XCD's L2, between the probe's 0.9 MB and 7.6 MB
+constexpr int64_t kUserRunUsers = 4096;               // users from which a handle takes the user-run schedule (bpr.hip user_runs_supported)
+inline bool user_run_width(int d) { return d == 8 || d == 16 || d == 32 || d == 64 || d == 128; }
+
+// whether a handle gets the tier: the user-run schedule natively, no cold item at create (a cold row's update is a store: the store
+// route and the tier exclude each other), and a catalogue within kAccTableBytes
+inline bool acc_rows_eligible(int64_t U, int64_t I, int d, int64_t n_cold) {
+    return U >= kUserRunUsers && user_run_width(d) && n_cold == 0 && I * (int64_t)d * 4 <= kAccTableBytes;
+}
+
+// The tier's layout.  slot: the class of every item after the hot layout (hot_code of a hot item, -1 warm, -2 cold); first_row: the
+// replica rows in front (hot_replica_layout's return).  Every warm item, ids ascending, takes ONE row behind them: slot[item] and
+// meta[k] become hot_code(row, 0), items[k] the item.  Returns the tier's rows (0 and nothing changed where the handle is not
+// eligible).
+inline int64_t acc_rows_layout(std::vector<int32_t> &slot, int64_t first_row, int64_t U, int d, int64_t n_cold, std::vector<int32_t> &items,
+                               std::vector<int32_t> &meta) {
+    items.clear();
+    meta.clear();
+    const int64_t I = (int64_t)slot.size();
+    if (!acc_rows_eligible(U, I, d, n_cold)) return 0;
+    for (int64_t i = 0; i < I; i++)
+        if (slot[(size_t)i] == -1) {
+            const int32_t code = hot_code(first_row + (int64_t)items.size(), 0);
+            slot[(size_t)i] = code;
+            items.push_back((int32_t)i);
+            meta.push_back(code);
+        }
+    return (int64_t)items.size();
 }
 
 }  // namespace gorse

@@ -296,7 +296,18 @@ constexpr double kDefaultReplicaUnit = 0.001;
 double g_mf_replica_unit = kDefaultReplicaUnit;
 extern "C" void gorse_hip_test_set_bpr_replica_unit(double unit) { g_mf_replica_unit = unit > 0 ? unit : kDefaultReplicaUnit; }
 
-// the cold classes of one handle for another window: warm <-> cold only, the hot slots stay (include/gorse_hip.h)
+// The accumulated tier of handles created AFTERWARDS (hot_rows.hpp acc_rows_layout): 1 = eligible handles get it, 0 = no handle does
+// (the classes and launches of the library without the tier: A/B and the tests).  On by default: S-ml1m's epoch 0.4276 -> 0.4021 ms at
+// nFactors 64, every run ahead of every run of the parent (profiles/bpr_acc_rows_ab.txt).
+#ifndef GORSE_BPR_ACC_ROWS
+#define GORSE_BPR_ACC_ROWS 1  // A/B (make ab AB_SRC=mf AB_FLAGS=-DGORSE_BPR_ACC_ROWS=0): the library's default
+#endif
+constexpr int kDefaultAccRows = GORSE_BPR_ACC_ROWS;
+int g_mf_acc_rows = kDefaultAccRows;
+extern "C" void gorse_hip_test_set_bpr_acc_rows(int32_t on) { g_mf_acc_rows = on < 0 ? kDefaultAccRows : (on != 0); }
+
+// the cold classes of one handle for another window: warm <-> cold only; the hot slots and, on a handle with the accumulated tier, the
+// tier's items (code >= 0 as well) stay -- such a handle had no cold item at create and keeps none (include/gorse_hip.h)
 extern "C" int32_t gorse_mf_set_bpr_cold_window(gorse_mf *h, int64_t samples, int64_t *n_cold) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     if (samples < 0) return fail(GORSE_ERR_INVALID, "cold window < 0");
@@ -307,7 +318,7 @@ extern "C" int32_t gorse_mf_set_bpr_cold_window(gorse_mf *h, int64_t samples, in
     h->n_cold = 0;
     for (int64_t i = 0; i < h->I; i++) {
         int32_t &s = h->h_hot_slot[(size_t)i];
-        if (s >= 0) continue;  // hot: its replica rows stay as they are
+        if (s >= 0) continue;  // hot, or a row of the accumulated tier: its rows stay as they are
         const bool cold = samples > 0 && h->nnz > 0 &&
                           ((double)h->h_item_count[(size_t)i] / (double)h->nnz + 1.0 / (double)h->I) * (double)samples < 1.0;
         s = cold ? -2 : -1;
@@ -443,14 +454,11 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
             for (int64_t i = 0; i < I; i++) h->h_item_count[(size_t)i] = (int32_t)std::min<int64_t>(cnt[(size_t)i], INT32_MAX);
             h->cold_window = g_mf_cold_window;
             h->n_cold = 0;
-            if (h->cold_window > 0 && h->nnz > 0) {
-                const double w = (double)h->cold_window;
-                for (int64_t i = 0; i < I; i++)
-                    if (((double)cnt[(size_t)i] / (double)h->nnz + 1.0 / (double)I) * w < 1.0) {
-                        slot[(size_t)i] = -2;
-                        h->n_cold++;
-                    }
-            }
+            for (int64_t i = 0; i < I; i++)
+                if (item_is_cold(cnt[(size_t)i], h->nnz, I, h->cold_window)) {  // (hot_rows.hpp)
+                    slot[(size_t)i] = -2;
+                    h->n_cold++;
+                }
             // replica rows per hot item, by its expected updates per sample (hot_rows.hpp hot_replica_layout): what a slot needs so that
             // its replicas do not queue, instead of the eight rows every slot had until round 6 -- a folder pass exchanges every row, and
             // at C2 the median hot item took ~18 updates per pass against 8 x 64 exchanged dwords
@@ -471,12 +479,18 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
                                                  GORSE_HOT_REPLICAS, meta);
                 for (size_t k = 0; k < hot.size(); k++) slot[hot[k]] = meta[k];
             }
+            // the accumulated tier (hot_rows.hpp): on an eligible handle every warm item takes one row behind the replica rows, its
+            // slot behind the hot slots; the hot tier above is what it is without it
+            std::vector<int32_t> acc_items, acc_meta;
+            if (g_mf_acc_rows) acc_rows_layout(slot, h->hot_rows, U, d, h->n_cold, acc_items, acc_meta);
+            h->n_acc = (int)acc_items.size();
+            const size_t rep_rows = (size_t)h->hot_rows + acc_items.size();
             h->h_hot_slot = slot;
             h->n_hot = (int)hot.size();
             GORSE_TRY(h->hot_slot.alloc((size_t)I));
-            GORSE_TRY(h->hot_items.alloc(hot.size()));
-            GORSE_TRY(h->hot_meta.alloc(hot.size()));
-            GORSE_TRY(h->hot_rep.alloc((size_t)h->hot_rows * (size_t)d));
+            GORSE_TRY(h->hot_items.alloc(hot.size() + acc_items.size()));
+            GORSE_TRY(h->hot_meta.alloc(hot.size() + acc_items.size()));
+            GORSE_TRY(h->hot_rep.alloc(rep_rows * (size_t)d));
             GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_WORDS));  // (bpr.hip worker_done)
             GORSE_HIP_CHECK(hipMemsetAsync(h->hot_done.p, 0, (size_t)GORSE_HOT_DONE_WORDS * sizeof(int32_t), h->stream));
             GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_slot.p, slot.data(), (size_t)I * sizeof(int32_t), hipMemcpyHostToDevice,
@@ -486,8 +500,13 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
                                                hipMemcpyHostToDevice, h->stream));
                 GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_meta.p, meta.data(), hot.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             }
-            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_rep.p, 0, std::max<size_t>(1, (size_t)h->hot_rows * (size_t)d) * sizeof(float),
-                                           h->stream));
+            if (!acc_items.empty()) {
+                GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_items.p + hot.size(), acc_items.data(), acc_items.size() * sizeof(int32_t),
+                                               hipMemcpyHostToDevice, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_meta.p + hot.size(), acc_meta.data(), acc_meta.size() * sizeof(int32_t),
+                                               hipMemcpyHostToDevice, h->stream));
+            }
+            GORSE_HIP_CHECK(hipMemsetAsync(h->hot_rep.p, 0, std::max<size_t>(1, rep_rows * (size_t)d) * sizeof(float), h->stream));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));  // slot / hot are host temporaries
         }
         trace.mark("create: item classes");

@@ -72,6 +72,9 @@ struct gorse_mf {
     gorse::DevBuf<float> hot_rep;
     int n_hot = 0;
     int64_t hot_rows = 0;       // replica rows in all (the sum of the slots' counts)
+    // the accumulated tier (hot_rows.hpp acc_rows_layout): n_acc warm items with one row each behind the hot_rows replica rows of
+    // hot_rep; their slots are entries n_hot .. n_hot + n_acc of hot_items / hot_meta
+    int n_acc = 0;
     uint64_t hot_launches = 0;  // update launches with folders so far: the parity picks the launch's set of arrival stripes
     int64_t n_cold = 0;  // items of class "cold" in hot_slot (-2): updates by write-through store (bpr.hip)
     int64_t cold_window = 0;               // what n_cold was computed for (gorse_mf_set_bpr_cold_window)

@@ -987,6 +987,32 @@ int32_t gh_test_bpr_hot_layout(int64_t U, int64_t I, const int64_t *uptr, const 
     std::copy(m.begin(), m.end(), meta);
     return (int32_t)hot.size();
 }
+// the accumulated tier of a BPR handle (csrc/hot_rows.hpp acc_rows_layout) on top of the hot layout above, for nFactors d and cold window
+// `window`: slot[I] = the class of every item as gorse_mf_create uploads it, acc_items[k] = the item of the tier's k-th row (at most I);
+// out3 = {replica rows of the hot tier, hot items, cold items}; returns the tier's rows
+int32_t gh_test_bpr_acc_layout(int64_t U, int64_t I, int32_t d, const int64_t *uptr, const int32_t *uidx, double unit, int32_t max_r,
+                               int64_t window, int32_t *slot_out, int32_t *acc_items, int64_t *out3) {
+    std::vector<int64_t> cnt((size_t)I, 0);
+    for (int64_t t = 0; t < uptr[U]; t++) cnt[(size_t)uidx[t]]++;
+    const std::vector<int32_t> hot = gorse::hot_items_select(cnt, uptr[U]);
+    std::vector<int32_t> slot((size_t)I, -1);
+    int64_t n_cold = 0;
+    for (int64_t i = 0; i < I; i++)
+        if (gorse::item_is_cold(cnt[(size_t)i], uptr[U], I, window)) slot[(size_t)i] = -2, n_cold++;
+    for (size_t k = 0; k < hot.size(); k++) slot[(size_t)hot[k]] = (int32_t)k;
+    std::vector<uint64_t> acc(hot.size(), 0);
+    gorse::hot_shares_rows(uptr, uidx, slot.data(), 0, U, acc.data());
+    int64_t users = 0;
+    for (int64_t r = 0; r < U; r++) users += uptr[r + 1] > uptr[r];
+    std::vector<int32_t> m, ai, am;
+    const int64_t rows = gorse::hot_replica_layout(acc, users, I, gorse::hot_neg_replicas((int64_t)hot.size(), I), unit, max_r, m);
+    for (size_t k = 0; k < hot.size(); k++) slot[(size_t)hot[k]] = m[k];
+    const int64_t n_acc = gorse::acc_rows_layout(slot, rows, U, d, n_cold, ai, am);
+    std::copy(slot.begin(), slot.end(), slot_out);
+    std::copy(ai.begin(), ai.end(), acc_items);
+    out3[0] = rows, out3[1] = (int64_t)hot.size(), out3[2] = n_cold;
+    return (int32_t)n_acc;
+}
 // the ALS row plan's long-row threshold for a side of `side_entries` feedbacks (csrc/als_plan.hpp, the header als_build_plan includes)
 int64_t gh_test_als_long_row(int64_t side_entries, int32_t d) { return gorse::als_long_row_threshold(side_entries, d); }
 // the 64-bit sparse ranking key itself, and the number of results the reference returns (xvec.go:379-446)

@@ -185,6 +185,21 @@ int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3 /*host*/);
  * follow those of slot s - 1), rep = every replica row (sum of R x nFactors floats; all zero between two update launches).  Any of the
  * three may be NULL. */
 int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items /*host*/, int32_t *replicas /*host*/, float *rep /*host*/);
+/* The accumulated tier (csrc/hot_rows.hpp acc_rows_layout, csrc/bpr.hip): on a handle that takes the user-run schedule natively, has
+ * no cold item at create and whose item factors fit 4 MiB, every warm item has ONE accumulator row behind the replica rows; the
+ * workers add its updates there and folder workgroups of the tier's own add the rows to Q every `periods` fold periods.  The two hooks
+ * above keep reporting the hot tier only.
+ * set_bpr_acc_rows: handles created AFTERWARDS get the tier where eligible (1) or never (0: the classes and launches of the library
+ * without it); < 0 = the library's default.  set_bpr_acc_fold_every: fold periods between two passes of the tier's folders in the
+ * update launches that follow; <= 0 = the library's default.
+ * acc_state, after the handle's streams drain: items[k] = the item of the tier's k-th row (ascending), rows = the rows (their number
+ * x nFactors floats; all zero between two update launches).  Either may be NULL.
+ * item_classes, after the handle's streams drain: slot[item] = the class word of every item (hot_code(row, log2 R) of an item whose
+ * updates go to replica or accumulator rows, -1 warm, -2 cold); out2 = {rows of the tier, cold items}.  Either may be NULL. */
+void gorse_hip_test_set_bpr_acc_rows(int32_t on);
+void gorse_hip_test_set_bpr_acc_fold_every(int32_t periods);
+int32_t gorse_hip_test_bpr_acc_state(gorse_mf *h, int32_t *items /*host*/, float *rows /*host*/);
+int32_t gorse_hip_test_bpr_item_classes(gorse_mf *h, int32_t *slot /*host, items*/, int64_t *out2 /*host*/);
 /* gorse_mf_recommend (csrc/recommend.hip).  slices > 0 = the threshold kernel cuts the items into this many slices across workgroups
  * (at most 8 and at most one per item; 0 = by the number of query blocks); buffer > 0 = entries of a query's survivor buffer (raised to
  * k + 2 where smaller, the smallest that can hold k + 1 entries and one more: a compaction per survivor; 0 = max(32, 2 (k + 1)));
