@@ -749,11 +749,15 @@ __global__ __launch_bounds__(256, 2) void als_wide_kernel(float *__restrict__ A,
                                                        int64_t n_items, int d, float w, float reg, float *__restrict__ partial,
                                                        int probe, unsigned long long *prof) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // probe only (prof != null, MFMA rows): s_memtime ticks of the workgroup's first wave in [0] G, [1] M to LDS + S, [2] sweep;
-    // [3] rows, [4] entries, [5] kernel ticks, [6] workgroups
+    // NOT LIVE: `probe` is always 0 and `prof` always null (the timing probes that set them are gone from the host side), and every
+    // `if (prof)` below folds away.  The body stays as measured because the MFMA forms compile differently without it: with these
+    // blocks and the two arguments taken out (as in als_row_kernel, where it cost nothing) als_wide_kernel<false, 1> went from 2 to 4
+    // scalar spills and its half-sweeps at nFactors 96 / 128 were 0.8 % slower, outside the untouched build's range
+    // (profiles/als_dispatch_ab.txt); keeping only the arguments did not bring the old instruction stream back.
+    // (prof != null, MFMA rows: s_memtime ticks of the workgroup's first wave in [0] G, [1] M to LDS + S, [2] sweep; [3] rows,
+    // [4] entries, [5] kernel ticks, [6] workgroups)
     unsigned long long c_acc = 0, c_m = 0, c_solve = 0, c_rows = 0, c_ent = 0, t_begin = 0;
-    prof = nullptr;  // nothing fills the phase counters any more (every `if (prof)` folds away); the blocks stay because taking them
-                     // out changed the kernel's register allocation and branch layout
+    prof = nullptr;
     if (prof) t_begin = __builtin_amdgcn_s_memtime();
     float *sM = smem;                           // 128 x 129
     float *sq = sM + 128 * kWideLd;             // 16 x 128: one batch of gathered rows
@@ -915,15 +919,11 @@ __global__ __launch_bounds__(256) void als_wide_long_kernel(float *__restrict__ 
 int g_als_long_row = 0;  // rows longer than this are cut into chunks; 0 = by the side's size (als_build_plan); test hook: gorse_hip_test_set_als_plan
 int g_als_chunk = 0;     // feedback entries per chunk of a long row; 0 = the threshold
 bool g_als_solve_adds = false;  // tests (path | 2048): no als_partial_reduce_kernel in front of the long-row solve
-int g_als_path = 0;         // 0 auto (Gram form: MFMA kernels for d <= 64, als_wide_kernel for d <= 128; else the residual
-                            // sweep), 1 force the residual sweep, 2 force the MFMA Gram form (d <= 64)
+int g_als_path = 0;         // which family a half-sweep runs (als_form): 0 by nFactors, 1 the residual sweep, 2 the MFMA tiles (d <= 64)
 int g_als_wide_fma = 0;     // als_wide_kernel: G by fused multiply-adds (round 2) instead of the fp32 MFMA (probe: path | 8)
 int g_als_slow_gather = 0;  // als_row_kernel / als_chunk_kernel: the first form of the gather stage whatever the shape (probe: path | 64)
-int g_als_wide_probe = 0;   // timing probes of als_wide_kernel (results are garbage): path | 16 = no sweep, path | 32 = S not added
 int g_als_nob3 = 0;         // no bf16 x 3 Gram: d = 32 / 64 take the fp32 16 x 16 tiles (probe: path | 1024)
-int g_als_waves8 = 0;       // als_row_kernel in 16 x 16 tiles: 8 waves per workgroup even where 12 fit (probe: path | 256)
 int g_als_tile32 = 0;       // als_row_kernel / als_chunk_kernel: 32 x 32 MFMA tiles even where d = 16 NB takes 16 x 16 ones (probe: path | 128)
-int g_als_phased = 0;       // als_row_kernel: the waves of a workgroup accumulate together and solve together (probe: path | 4)
 constexpr int kAlsDP = 65;          // LDS row stride of the per-wave M matrix
 constexpr int kAlsWaves = 4;        // waves per workgroup of the chunk kernels
 constexpr int kAlsRowWaves = 8;     // waves per workgroup of als_row_kernel: ONE workgroup per CU (2 waves per SIMD) so that its LDS
@@ -959,12 +959,6 @@ struct GramAcc {
 // against 80 for the fp32 tiles.  Fragment: lane l holds column (l & 31) of the EIGHT entries 8 (l >> 5) .. + 7 of a 16-entry stage
 // (the MFMA's k index), two values per register; the accumulators and their D layout are those of the fp32 32 x 32 form.
 constexpr int kAlsOct = 8;  // entries per lane and stage
-#ifndef GORSE_ALS_ROW_DEEP
-#define GORSE_ALS_ROW_DEEP 1
-#endif
-constexpr bool kAlsRowDeep = GORSE_ALS_ROW_DEEP != 0;  // the row kernel's bf16 form: four gather stages and no pairing of sweeps (the registers of
-                                                       // one or the other): C5 5.69-5.71 against 5.78 ms (profiles/r04_zq_ab_row_ring.txt)
-constexpr bool kAlsRowPair = !kAlsRowDeep;
 
 template <int NB>
 __device__ __forceinline__ void gram_load_stage_b3(const float *__restrict__ B, uint32_t rowbytes, int idx, int first, int lane,
@@ -981,7 +975,7 @@ __device__ __forceinline__ void gram_load_stage_b3(const float *__restrict__ B, 
     }
 }
 
-template <int NB, bool DEEP = true>  // DEEP: four gather stages in the ring (long runs of stages: the chunk kernel), else two
+template <int NB>
 __device__ __forceinline__ void gram_accumulate_b3(const float *__restrict__ B, const int32_t *__restrict__ fb, int n, int d, int lane,
                                                    GramAcc<NB> &g, int idx0, int idx1, int zero_row) {
 #pragma unroll
@@ -1035,42 +1029,28 @@ __device__ __forceinline__ void gram_accumulate_b3(const float *__restrict__ B, 
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, c, acc, 0, 0, 0);
                 }
     };
-    // DEEP: three stages in flight, a fourth being consumed (a ring of four buffers, unrolled: nothing moves) -- for the chunk kernel,
-    // whose wave walks 256 stages on end: the S Gram 0.27 -> 0.22 ms and the long rows' share of the sweeps with it (C5 6.1 -> 5.8 ms,
-    // profiles/r04_zo_probe_als_tiles.txt).  In the row kernel (a 100-entry row is seven stages) the deeper ring is worth 1.5 %, and only
-    // in place of the pairing of two rows' sweeps -- with both the registers spill (kAlsRowDeep).
-    if constexpr (DEEP) {
-        float f0[kAlsOct][NB], f1[kAlsOct][NB], f2[kAlsOct][NB], f3[kAlsOct][NB];
-        issue(f0);
-        issue(f1);
-        issue(f2);
-        int s = 0;
-        for (; s + 4 <= nstages; s += 4) {
-            issue(f3);
-            consume(f0);
-            issue(f0);
-            consume(f1);
-            issue(f1);
-            consume(f2);
-            issue(f2);
-            consume(f3);
-        }
-        if (s < nstages) consume(f0);
-        if (s + 1 < nstages) consume(f1);
-        if (s + 2 < nstages) consume(f2);
-        return;
-    } else {
-    float f0[kAlsOct][NB], f1[kAlsOct][NB];
+    // Three stages in flight, a fourth being consumed (a ring of four buffers, unrolled: nothing moves) -- for the chunk kernel, whose
+    // wave walks 256 stages on end: the S Gram 0.27 -> 0.22 ms and the long rows' share of the sweeps with it (C5 6.1 -> 5.8 ms,
+    // profiles/r04_zo_probe_als_tiles.txt).  In the row kernel (a 100-entry row is seven stages) a ring of two stages with the sweeps
+    // of two rows paired was 1.5 % slower, and both together spill (profiles/r04_zq_ab_row_ring.txt).
+    float f0[kAlsOct][NB], f1[kAlsOct][NB], f2[kAlsOct][NB], f3[kAlsOct][NB];
     issue(f0);
+    issue(f1);
+    issue(f2);
     int s = 0;
-    for (; s + 2 <= nstages; s += 2) {
-        issue(f1);
+    for (; s + 4 <= nstages; s += 4) {
+        issue(f3);
         consume(f0);
         issue(f0);
         consume(f1);
+        issue(f1);
+        consume(f2);
+        issue(f2);
+        consume(f3);
     }
     if (s < nstages) consume(f0);
-    }
+    if (s + 1 < nstages) consume(f1);
+    if (s + 2 < nstages) consume(f2);
 }
 
 // ---- the same accumulation in 16 x 16 tiles (d = 16 NB with the fast gather stage) -------------------------------------------------
@@ -1129,8 +1109,8 @@ __device__ __forceinline__ void gram_load_stage16(const float *__restrict__ B, u
 }
 
 // idx0 / idx1: lane l's entries l and 64 + l of the row as loaded by the caller (any value past the row's end); zero_row: the row id of
-// the zero row behind B (what an entry past the row's end reads); DEEP: as gram_accumulate_b3
-template <int NB, bool DEEP = false, bool FULL = true, bool O64 = false>
+// the zero row behind B (what an entry past the row's end reads); the ring of four gather stages is gram_accumulate_b3's
+template <int NB, bool FULL = true, bool O64 = false>
 __device__ __forceinline__ void gram_accumulate16(const float *__restrict__ B, const int32_t *__restrict__ fb, int n, int d, int lane,
                                                   GramAcc16<NB> &g, int idx0, int idx1, int zero_row) {
 #pragma unroll
@@ -1171,39 +1151,26 @@ __device__ __forceinline__ void gram_accumulate16(const float *__restrict__ B, c
                         fr[j][bi], fr[j][bj], g.t[GramAcc16<NB>::tile(bi, bj)], 0, 0, 0);
         }
     };
-    // ping-pong over pairs of stages; an odd last stage (already gathered into f0) is consumed behind the loop instead of being
-    // paired with sixteen zero rows (C5: 7.24-7.26 against 7.46-7.49 ms in one session, profiles/r04_u_probe_als_tiles_peel.txt)
-    if constexpr (DEEP) {
-        float f0[kAlsQuads][NB], f1[kAlsQuads][NB], f2[kAlsQuads][NB], f3[kAlsQuads][NB];
+    // the last stages (already gathered) are consumed behind the loop instead of being filled up with sixteen zero rows each (C5:
+    // 7.24-7.26 against 7.46-7.49 ms in one session, profiles/r04_u_probe_als_tiles_peel.txt)
+    float f0[kAlsQuads][NB], f1[kAlsQuads][NB], f2[kAlsQuads][NB], f3[kAlsQuads][NB];
+    issue(f0);
+    issue(f1);
+    issue(f2);
+    int s = 0;
+    for (; s + 4 <= nstages; s += 4) {
+        issue(f3);
+        consume(f0);
         issue(f0);
+        consume(f1);
         issue(f1);
+        consume(f2);
         issue(f2);
-        int s = 0;
-        for (; s + 4 <= nstages; s += 4) {
-            issue(f3);
-            consume(f0);
-            issue(f0);
-            consume(f1);
-            issue(f1);
-            consume(f2);
-            issue(f2);
-            consume(f3);
-        }
-        if (s < nstages) consume(f0);
-        if (s + 1 < nstages) consume(f1);
-        if (s + 2 < nstages) consume(f2);
-    } else {
-        float f0[kAlsQuads][NB], f1[kAlsQuads][NB];
-        issue(f0);
-        int s = 0;
-        for (; s + 2 <= nstages; s += 2) {
-            issue(f1);
-            consume(f0);
-            issue(f0);
-            consume(f1);
-        }
-        if (s < nstages) consume(f0);
+        consume(f3);
     }
+    if (s < nstages) consume(f0);
+    if (s + 1 < nstages) consume(f1);
+    if (s + 2 < nstages) consume(f2);
 }
 
 // the callback gets the compile-time parts of the coordinates: i = ci + 4 * (lane >> 4), j = cj + (lane & 15)
@@ -1297,26 +1264,10 @@ struct SolveSteps {
         }
         SolveSteps<F + 1, DMAX, FULL>::run(x, d);
     }
-    // two rows' sweeps, step by step: each chain is three dependent operations per step and every link waits ~45 cycles next to the
-    // sibling wave's MFMA stream -- two independent chains take the same slots twice as well
-    static __device__ __forceinline__ void run2(SolveState<DMAX> &x, SolveState<DMAX> &z, int d) {
-        if (FULL || F < d) {
-            const float dkx = fmaf(-x.y, x.inv, x.gk);
-            const float dkz = fmaf(-z.y, z.inv, z.gk);
-            const int dx = __builtin_amdgcn_readlane(__float_as_int(dkx), F);
-            const int dz = __builtin_amdgcn_readlane(__float_as_int(dkz), F);
-            x.y = fmaf(__int_as_float(dx), x.mcol[F], x.y);
-            z.y = fmaf(__int_as_float(dz), z.mcol[F], z.y);
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(x.steps) : "s"(dx), "n"(F));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(z.steps) : "s"(dz), "n"(F));
-        }
-        SolveSteps<F + 1, DMAX, FULL>::run2(x, z, d);
-    }
 };
 template <int DMAX, bool FULL>
 struct SolveSteps<DMAX, DMAX, FULL> {
     static __device__ __forceinline__ void run(SolveState<DMAX> &, int) {}
-    static __device__ __forceinline__ void run2(SolveState<DMAX> &, SolveState<DMAX> &, int) {}
 };
 // everything in front of the chain: the columns of M into registers, the diagonal, y = M p
 // PAD (with FULL): the system is DMAX x DMAX with zeros past dvalid -- M, S (stride DMAX) and the sums are zero there -- so the DMAX
@@ -1325,10 +1276,8 @@ struct SolveSteps<DMAX, DMAX, FULL> {
 template <int DMAX, bool FORM, bool FULL = false, int DP = kAlsDP, bool PAD = false>  // DP: row stride of sM
 __device__ __forceinline__ void als_solve_prepare(SolveState<DMAX> &x, float *__restrict__ a, const float *sM, const float *ss,
                                                   const float *__restrict__ S, int d, float one_w, float w, float reg, int lane,
-                                                  unsigned long long *c_load = nullptr, int dvalid = 0) {
+                                                  int dvalid = 0) {
     static_assert(!PAD || FULL, "a padded system is solved with all DMAX steps");
-    unsigned long long t_in = 0;
-    if (c_load) t_in = __builtin_amdgcn_s_memtime();
     if (FULL) d = DMAX;
     float (&mcol)[DMAX] = x.mcol;
     if (FORM) {  // an opaque zero offset per call: keeps the 64 loads of S inside the row loop instead of 64 registers
@@ -1357,7 +1306,6 @@ __device__ __forceinline__ void als_solve_prepare(SolveState<DMAX> &x, float *__
     // (the wave sum took ~650 cycles per step next to a sibling wave's MFMAs: 42K cycles per row against 27K for the Gram
     // accumulation, profiles/r01_p_probe_als_prof.txt).  Same recurrence, products summed in a different order; agreement
     // with the float64 recurrence 6e-7 of the row's scale on random systems (well inside the 1e-4 bar).
-    if (c_load) *c_load += __builtin_amdgcn_s_memtime() + (__float_as_int(mcol[DMAX - 1]) & 0) - t_in;  // probe: columns of M in registers
     const float p0_raw = a[lane_c], sv_raw = ss[lane_c];
     float diag = sM[lane_c * DP + lane_c];
     if (FORM) diag = one_w * diag + w * S[lane_c * d + lane_c];
@@ -1399,9 +1347,9 @@ __device__ __forceinline__ void als_solve_finish(const SolveState<DMAX> &x, int 
 template <int DMAX, bool FORM, bool FULL = false, int DP = kAlsDP>
 __device__ __forceinline__ void als_solve_row(float *__restrict__ a, const float *sM, const float *ss,
                                               const float *__restrict__ S, int d, float one_w, float w, float reg,
-                                              int lane, unsigned long long *c_load = nullptr) {
+                                              int lane) {
     SolveState<DMAX> x;
-    als_solve_prepare<DMAX, FORM, FULL, DP>(x, a, sM, ss, S, d, one_w, w, reg, lane, c_load);
+    als_solve_prepare<DMAX, FORM, FULL, DP>(x, a, sM, ss, S, d, one_w, w, reg, lane);
     SolveSteps<0, DMAX, FULL>::run(x, FULL ? DMAX : d);
     als_solve_finish<DMAX>(x, lane);
 }
@@ -1412,24 +1360,17 @@ __device__ __forceinline__ void als_solve_row(float *__restrict__ a, const float
 // zero row, M is 16 NB x (16 NB + 1) with zeros past d, the sweep runs d steps -- which is what the reference's test width 8 and
 // every nFactors that is not a multiple of 16 take.  MODE 4: mode 3 with 64-bit gather addresses (factor matrices of 4 GB and
 // more, or 2^24 rows).  (The 32 x 32 fp32 tile form of rounds 1-4, MODE 0, served those shapes with 124 registers + 175 scalar spills
-// for d = 8; it is gone.)  All modes gather through the zero row behind the matrix (zero_row), keep M per wave in LDS and pair the
-// rows' sweeps.  WAVES: waves per workgroup (one workgroup per CU).
+// for d = 8; it is gone.)  All modes gather through the zero row behind the matrix (zero_row) and keep M per wave in LDS.
+// WAVES: waves per workgroup (one workgroup per CU).
 template <int NB, int MODE = 1, int WAVES = kAlsRowWaves>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4, WAVES / 4))) void als_row_kernel(float *__restrict__ A, const float *__restrict__ B,
                                                                  const int64_t *__restrict__ ptr,
                                                                  const int32_t *__restrict__ idx,
                                                                  const float *__restrict__ S,
                                                                  const int32_t *__restrict__ rows, int64_t n_rows, int d,
-                                                                 float w, float reg, const float *__restrict__ zeros,
-                                                                 unsigned long long *prof, int phased, int zero_row) {
+                                                                 float w, float reg, int zero_row) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // probe only (prof != null): s_memtime ticks per wave in [0] Gram accumulation, [1] M to LDS, [2] solve; [3] rows,
-    // [4] feedback entries, [5] kernel ticks, [6] waves
-    unsigned long long c_acc = 0, c_m = 0, c_solve = 0, c_rows = 0, c_ent = 0, t_begin = 0, c_load = 0;
-    prof = nullptr;  // nothing fills the phase counters any more (every `if (prof)` folds away); the blocks stay because taking them
-                     // out changed the kernel's register allocation and branch layout
-    if (prof) t_begin = __builtin_amdgcn_s_memtime();
     // S (d x d, the same for every row of the half-sweep) is copied to LDS once: read from global memory inside the solve, its
     // 64 loads per row queued behind the sibling waves' gathers -- 24.6K of the solve's 40.5K cycles per row
     // (profiles/r02_i_probe_als_prof.txt)
@@ -1468,34 +1409,15 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
         n = (int)(ptr[u + 1] - beg);
         first_indices(beg, n, idx0, idx1);
     }
-    // phased: the eight waves of the workgroup accumulate together and solve together (a barrier in between and one after): a
-    // solving wave then never shares its SIMD with a wave that streams 64-cycle fp32 MFMAs.  Every wave runs the same number of
-    // iterations; one without a row of its own (the tail) only keeps the barriers.
-    const int64_t t_end = phased ? (n_rows + nwaves - 1) / nwaves * nwaves : n_rows;
-    SolveState<DD> held;  // the first row of a pair, waiting for the second
-    bool have_held = false;
-    for (int64_t t = wave; t < t_end; t += nwaves) {
-        if (t >= n_rows) {
-            __syncthreads();
-            __syncthreads();
-            continue;
-        }
+    for (int64_t t = wave; t < n_rows; t += nwaves) {
         const int64_t u_next = rows[t + nwaves < n_rows ? t + nwaves : t];
         std::conditional_t<T16, GramAcc16<NB>, GramAcc<NB>> g;
-        unsigned long long t0 = 0;
-        if (prof) t0 = __builtin_amdgcn_s_memtime();
         if constexpr (T16)
-            gram_accumulate16<NB, true, FULLD, MODE == 4>(B, idx + beg, n, d, lane, g, idx0, idx1, zero_row);
+            gram_accumulate16<NB, FULLD, MODE == 4>(B, idx + beg, n, d, lane, g, idx0, idx1, zero_row);
         else
-            gram_accumulate_b3<NB, kAlsRowDeep>(B, idx + beg, n, d, lane, g, idx0, idx1, zero_row);
+            gram_accumulate_b3<NB>(B, idx + beg, n, d, lane, g, idx0, idx1, zero_row);
         const int64_t beg_next = ptr[u_next];
         const int64_t end_next = ptr[u_next + 1];
-        if (prof) {
-            // the accumulators are only complete once they are read: touch one so that the stamp waits for the MFMAs
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime() + (__float_as_int(g.t[0][0]) & 0);
-            c_acc += t1 - t0;
-            t0 = t1;
-        }
         {   // rows / columns past d are zeros of the padded gathers: stored unconditionally (sM is DD x DP), with
             // immediate offsets from two lane-dependent bases
             auto put = [&](float *direct, float *mirror) {
@@ -1517,11 +1439,6 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
             gram_store_sums<NB>(g, d, lane, ss);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (prof) {
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-            c_m += t1 - t0;
-            t0 = t1;
-        }
         // The solve is a chain of ~1100 dependent VALU operations; the sibling wave of this SIMD is meanwhile streaming fp32
         // MFMAs, and at equal priority the arbiter lets one VALU operation through per 64-cycle MFMA (840 cycles per solve
         // step, profiles/r02_g_probe_als_prof.txt).  At raised priority the chain issues at its own pace and the MFMA stream
@@ -1529,45 +1446,16 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
         const int n_next = (int)(end_next - beg_next);
         int idx0_next, idx1_next;
         first_indices(beg_next, n_next, idx0_next, idx1_next);
-        if (phased) __syncthreads();
         __builtin_amdgcn_s_setprio(3);
         {
-            // two rows' sweeps run together: the first row of a pair is taken as far as the chain (its M in registers, the LDS
-            // buffer free for the second row's), the chains of both then advance step by step (SolveSteps::run2)
             SolveState<DD> cur;
-            als_solve_prepare<DD, true, true, DP, !FULLD>(cur, A + u * d, sM, ss, sS, DD, one_w, w, reg, lane, prof ? &c_load : nullptr, d);
-            if (have_held) {
-                SolveSteps<0, DD, true>::run2(held, cur, d);
-                als_solve_finish<DD>(held, lane);
-                als_solve_finish<DD>(cur, lane);
-                have_held = false;
-            } else if (kAlsRowPair && !phased && t + nwaves < n_rows) {
-                held = cur;
-                have_held = true;
-            } else {
-                SolveSteps<0, DD, true>::run(cur, d);
-                als_solve_finish<DD>(cur, lane);
-            }
+            als_solve_prepare<DD, true, true, DP, !FULLD>(cur, A + u * d, sM, ss, sS, DD, one_w, w, reg, lane, d);
+            SolveSteps<0, DD, true>::run(cur, d);
+            als_solve_finish<DD>(cur, lane);
         }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_wave_barrier();
-        if (prof) {
-            c_solve += __builtin_amdgcn_s_memtime() - t0;
-            c_rows++;
-            c_ent += n;
-        }
-        if (phased) __syncthreads();
         u = u_next, beg = beg_next, n = n_next, idx0 = idx0_next, idx1 = idx1_next;
-    }
-    if (prof && lane == 0) {
-        atomicAdd(prof + 0, c_acc);
-        atomicAdd(prof + 1, c_m);
-        atomicAdd(prof + 2, c_solve);
-        atomicAdd(prof + 3, c_rows);
-        atomicAdd(prof + 4, c_ent);
-        atomicAdd(prof + 5, (unsigned long long)__builtin_amdgcn_s_memtime() - t_begin);
-        atomicAdd(prof + 6, 1ull);
-        atomicAdd(prof + 7, c_load);
     }
 }
 
@@ -1578,8 +1466,7 @@ __global__ __launch_bounds__(64 * kAlsWaves, 2) void als_chunk_kernel(const floa
                                                                    const int64_t *__restrict__ chunk_beg,
                                                                    const int32_t *__restrict__ chunk_cnt,
                                                                    int64_t n_chunks, int d, float *__restrict__ partial,
-                                                                   const float *__restrict__ zeros, int zero_row,
-                                                                   const int32_t *__restrict__ order) {
+                                                                   int zero_row, const int32_t *__restrict__ order) {
     static_assert(MODE >= 1 && MODE <= 4, "als_chunk_kernel modes");
     constexpr bool T16 = MODE != 2;
     constexpr bool FULLD = MODE == 1 || MODE == 2;
@@ -1594,7 +1481,7 @@ __global__ __launch_bounds__(64 * kAlsWaves, 2) void als_chunk_kernel(const floa
         const int32_t *fb = idx + chunk_beg[c];
         const int cn = chunk_cnt[c];
         if constexpr (T16)
-            gram_accumulate16<NB, true, FULLD, MODE == 4>(B, fb, cn, d, lane, g, fb[lane < cn ? lane : 0], fb[64 + lane < cn ? 64 + lane : 0], zero_row);
+            gram_accumulate16<NB, FULLD, MODE == 4>(B, fb, cn, d, lane, g, fb[lane < cn ? lane : 0], fb[64 + lane < cn ? 64 + lane : 0], zero_row);
         else
             gram_accumulate_b3<NB>(B, fb, cn, d, lane, g, fb[lane < cn ? lane : 0], fb[64 + lane < cn ? 64 + lane : 0], zero_row);
         float *dst = partial + c * stride;
@@ -1671,7 +1558,7 @@ __global__ __launch_bounds__(256) void als_long_solve_kernel(float *__restrict__
         __syncthreads();
         if (threadIdx.x < 64) {
             SolveState<DMAX> x;
-            als_solve_prepare<DMAX, false, true, kAlsDP, true>(x, A + (int64_t)rows[t] * d, sM, ss, S, DMAX, one_w, w, reg, threadIdx.x, nullptr, d);
+            als_solve_prepare<DMAX, false, true, kAlsDP, true>(x, A + (int64_t)rows[t] * d, sM, ss, S, DMAX, one_w, w, reg, threadIdx.x, d);
             SolveSteps<0, DMAX, true>::run(x, DMAX);
             als_solve_finish<DMAX>(x, threadIdx.x);
         }
@@ -1699,45 +1586,18 @@ int32_t run_gram(gorse_mf *h, const float *F, const int64_t *ptr, int64_t rows, 
     return GORSE_OK;
 }
 
-int als_zero_row(const gorse_mf *h, const float *F);
-bool als_split_products();
+// a kernel's dynamic LDS above the 64 KB default is allowed per device (one process drives handles on several): asked for in front
+// of every launch that needs it, for the kernel about to be launched
+template <typename K>
+int32_t allow_lds(K kernel, size_t bytes) {
+    GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return GORSE_OK;
+}
+
+// the residual sweep of rows [row_begin, row_end): the reference's own recurrence, any nFactors
 int32_t run_sweep(gorse_mf *h, float *A, const float *B, const int64_t *ptr, const int32_t *idx, int64_t row_begin,
                   int64_t row_end, int64_t max_row, float w, float reg) {
     const int d = h->d;
-    // 64 < nFactors <= 128, the product's choice: the Gram form of als_wide_kernel over the row plan (short rows whole, long rows
-    // by chunks + als_wide_long_kernel); the residual sweep below stays as the forced path 1
-    if (d > 64 && d <= 128 && g_als_path == 0) {
-        gorse_mf::AlsPlan &pl = h->als_plan[A == h->P.p ? 0 : 1];
-        const size_t wlds = ((size_t)128 * kWideLd + (size_t)kWideBatch * 128 + 128) * sizeof(float);
-        // G by fused multiply-adds / the fp32 MFMA / the bf16 MFMA over split values (32-bit gather offsets: als_zero_row's condition)
-        const int form = g_als_wide_fma ? 0 : ((!als_split_products() || als_zero_row(h, B) < 0) ? 1 : 2);
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_wide_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        const int tokw = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
-        if (pl.n_short > 0) {
-            auto k = form == 2 ? als_wide_kernel<false, 2> : (form == 1 ? als_wide_kernel<false, 1> : als_wide_kernel<false, 0>);
-            k<<<dim3((unsigned)std::min<int64_t>(pl.n_short, 512)), dim3(256), wlds, h->stream>>>(
-                A, B, ptr, idx, h->gram.p, pl.short_rows.p, nullptr, nullptr, pl.n_short, d, w, reg, nullptr, g_als_wide_probe, nullptr);
-            GORSE_HIP_CHECK(hipGetLastError());
-        }
-        if (pl.n_long > 0) {
-            GORSE_TRY(h->als_partial.ensure((size_t)pl.n_chunks * kWidePartial));
-            auto k = form == 2 ? als_wide_kernel<true, 2> : (form == 1 ? als_wide_kernel<true, 1> : als_wide_kernel<true, 0>);
-            k<<<dim3((unsigned)std::min<int64_t>(pl.n_chunks, 2048)), dim3(256), wlds, h->stream>>>(
-                A, B, ptr, idx, h->gram.p, nullptr, pl.chunk_beg.p, pl.chunk_cnt.p, pl.n_chunks, d, w, reg, h->als_partial.p, 0, nullptr);
-            GORSE_HIP_CHECK(hipGetLastError());
-            als_wide_long_kernel<<<dim3((unsigned)std::min<int64_t>(pl.n_long, 512)), dim3(256), wlds, h->stream>>>(
-                A, h->gram.p, pl.long_rows.p, pl.long_first.p, pl.long_nch.p, pl.n_long, d, w, reg, h->als_partial.p);
-            GORSE_HIP_CHECK(hipGetLastError());
-        }
-        h->prof.end(tokw, h->stream);
-        return GORSE_OK;
-    }
     const size_t fixed = ((size_t)((d + 3) & ~3) + 12 + 2 * (size_t)kGroupsPerBlock * d) * sizeof(float);
     const size_t budget = 64 * 1024;
     if (fixed + 1024 > 150 * 1024) return fail(GORSE_ERR_INVALID, "nFactors %d too large for the ALS kernel", d);
@@ -1749,8 +1609,7 @@ int32_t run_sweep(gorse_mf *h, float *A, const float *B, const int64_t *ptr, con
     int blocks = (int)std::min<int64_t>(row_end - row_begin, 256 * 8);
     const int64_t stride = max_row > pred_cap ? max_row : 1;
     GORSE_TRY(h->als_scratch.ensure((size_t)blocks * stride));
-    GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)shmem));
+    GORSE_TRY(allow_lds(als_sweep_kernel, shmem));
     int tok = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
     als_sweep_kernel<<<dim3(blocks), dim3(256), shmem, h->stream>>>(A, B, ptr, idx, h->gram.p, row_begin, row_end, d, w, reg,
                                                                    pred_cap, q_cap, h->als_scratch.p, stride, 0);
@@ -1792,28 +1651,38 @@ int als_gram_mode(int d, int zrow) {
     return 3;
 }
 
-void launch_chunks(const float *B, const int32_t *idx, const int64_t *chunk_beg, const int32_t *chunk_cnt, int64_t n_chunks, int d,
-                   float *partial, const float *zeros, int zrow, int pad_row, unsigned grid, hipStream_t st, const int32_t *order = nullptr) {
-#define CHUNK_LAUNCH(...) \
-    als_chunk_kernel<__VA_ARGS__><<<dim3(grid), dim3(64 * kAlsWaves), 0, st>>>(B, idx, chunk_beg, chunk_cnt, n_chunks, d, partial, zeros, pad_row, order)
-    const int mode = als_gram_mode(d, zrow);
-    switch (mode * 10 + (mode == 2 ? d / 32 : (d + 15) / 16)) {
-    case 11: CHUNK_LAUNCH(1, 1); break;
-    case 12: CHUNK_LAUNCH(2, 1); break;
-    case 13: CHUNK_LAUNCH(3, 1); break;
-    case 14: CHUNK_LAUNCH(4, 1); break;
-    case 21: CHUNK_LAUNCH(1, 2); break;
-    case 22: CHUNK_LAUNCH(2, 2); break;
-    case 31: CHUNK_LAUNCH(1, 3); break;
-    case 32: CHUNK_LAUNCH(2, 3); break;
-    case 33: CHUNK_LAUNCH(3, 3); break;
-    case 34: CHUNK_LAUNCH(4, 3); break;
-    case 41: CHUNK_LAUNCH(1, 4); break;
-    case 42: CHUNK_LAUNCH(2, 4); break;
-    case 43: CHUNK_LAUNCH(3, 4); break;
-    default: CHUNK_LAUNCH(4, 4); break;
-    }
-#undef CHUNK_LAUNCH
+// The kernels of the Tiles form, one line per (mode, NB): NB = d / 32 in mode 2, else d rounded up to 16-column blocks.  Twelve waves
+// per CU where they fit and pay (DD <= 32, 32-bit gathers): d = 16 0.86 -> 0.77 ms, d = 32 1.30 -> 1.26 (C5 shard / 4); d = 48 is no
+// faster with twelve, and d = 64 (M packed as the block rows of its upper triangle so that twelve buffers fit) was slower: 3.06
+// against 2.89 ms (profiles/r04_t_probe_als_tiles*.txt)
+struct TileKernels {
+    int mode, nb, waves;  // waves per workgroup of the row kernel
+    decltype(&als_row_kernel<1, 1, 12>) row;
+    decltype(&als_chunk_kernel<1, 1>) chunk;
+};
+const TileKernels *tile_kernels(int d, int zrow) {
+#define TILES(MODE, NB, WAVES) {MODE, NB, WAVES, als_row_kernel<NB, MODE, WAVES>, als_chunk_kernel<NB, MODE>}
+    static const TileKernels table[] = {
+        TILES(1, 1, 12), TILES(1, 2, 12), TILES(1, 3, 8), TILES(1, 4, 8),  // d = 16 NB on fp32 16 x 16 tiles
+        TILES(2, 1, 12), TILES(2, 2, 8),                                   // d = 32 NB on the bf16 MFMA
+        TILES(3, 1, 12), TILES(3, 2, 12), TILES(3, 3, 8), TILES(3, 4, 8),  // any d <= 16 NB
+        TILES(4, 1, 8),  TILES(4, 2, 8),  TILES(4, 3, 8), TILES(4, 4, 8),  // the same with 64-bit gather addresses
+    };
+#undef TILES
+    const int mode = als_gram_mode(d, zrow), nb = mode == 2 ? d / 32 : (d + 15) / 16;
+    for (const TileKernels &k : table)
+        if (k.mode == mode && k.nb == nb) return &k;
+    fail(GORSE_ERR_INVALID, "no ALS row kernel for nFactors %d (mode %d)", d, mode);
+    return nullptr;
+}
+
+int32_t launch_chunks(const float *B, const int32_t *idx, const int64_t *chunk_beg, const int32_t *chunk_cnt, int64_t n_chunks, int d,
+                      float *partial, int zrow, int pad_row, unsigned grid, hipStream_t st, const int32_t *order = nullptr) {
+    const TileKernels *k = tile_kernels(d, zrow);
+    if (!k) return GORSE_ERR_INVALID;
+    k->chunk<<<dim3(grid), dim3(64 * kAlsWaves), 0, st>>>(B, idx, chunk_beg, chunk_cnt, n_chunks, d, partial, pad_row, order);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
 }
 
 // long rows, stage 1 1/2: the partials of a row added up by ONE THREAD PER ELEMENT, for rows with many chunks.  als_long_solve_kernel
@@ -1854,15 +1723,10 @@ __global__ __launch_bounds__(256) void als_partial_reduce_kernel(const float *__
 
 void launch_long_solve(float *A, const float *S, const int32_t *rows, const int32_t *first, const int32_t *nch, int64_t n_rows, int d,
                        float w, float reg, const float *partial, hipStream_t st) {
-#define LONG_LAUNCH(DMAX_) \
-    als_long_solve_kernel<DMAX_><<<dim3((unsigned)std::min<int64_t>(n_rows, 1024)), dim3(256), 0, st>>>(A, S, rows, first, nch, n_rows, d, w, reg, partial)
-    switch ((d + 15) / 16) {
-    case 1: LONG_LAUNCH(16); break;
-    case 2: LONG_LAUNCH(32); break;
-    case 3: LONG_LAUNCH(48); break;
-    default: LONG_LAUNCH(64); break;
-    }
-#undef LONG_LAUNCH
+    static const decltype(&als_long_solve_kernel<16>) by_blocks[] = {  // DMAX = d rounded up to whole 16-column blocks
+        als_long_solve_kernel<16>, als_long_solve_kernel<32>, als_long_solve_kernel<48>, als_long_solve_kernel<64>};
+    by_blocks[std::min((d + 15) / 16, 4) - 1]<<<dim3((unsigned)std::min<int64_t>(n_rows, 1024)), dim3(256), 0, st>>>(
+        A, S, rows, first, nch, n_rows, d, w, reg, partial);
 }
 
 int32_t run_side_gram(gorse_mf *h, int side, float *A, const float *B, const int64_t *ptr, const int32_t *idx, float w,
@@ -1872,56 +1736,22 @@ int32_t run_side_gram(gorse_mf *h, int side, float *A, const float *B, const int
     gorse_mf::AlsPlan &pl = h->als_plan[side];
     int tok = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
     if (pl.n_short > 0) {
-#define ROW_LAUNCH(WAVES_, LDS_, ...)                                                                                  \
-    do {                                                                                                               \
-        const unsigned grid_ = (unsigned)std::min<int64_t>(ceil_div(pl.n_short, WAVES_), 256); /* one workgroup per CU */ \
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)als_row_kernel<__VA_ARGS__, WAVES_>,                         \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)));                 \
-        als_row_kernel<__VA_ARGS__, WAVES_><<<dim3(grid_), dim3(64 * WAVES_), (LDS_), h->stream>>>(                    \
-            A, B, ptr, idx, h->gram.p, pl.short_rows.p, pl.n_short, d, w, reg, h->als_zeros.p, nullptr,                \
-            g_als_phased, pad_row);                                                                                    \
-    } while (0)
-        const int mode = als_gram_mode(d, zrow);
-        {
-            // DD x (DD + 1) + DD words of M and sums per wave next to S (DD = d, or d rounded up to whole 16-column blocks in modes 3, 4).
-            // Twelve waves per CU where they fit and pay: d = 16 0.86 -> 0.77 ms, d = 32 1.30 -> 1.26 (C5 shard / 4); d = 48 is no
-            // faster with twelve, and d = 64 (M packed as the block rows of its upper triangle so that twelve buffers fit) was slower:
-            // 3.06 against 2.89 ms (profiles/r04_t_probe_als_tiles*.txt)
-            const int dd = mode == 2 ? d : (d + 15) / 16 * 16;
-            const int wv16 = (dd <= 32 && !g_als_waves8 && mode != 4) ? 12 : 8;
-            const size_t lds16 = ((size_t)dd * dd + (size_t)wv16 * ((size_t)dd * (dd + 1) + dd)) * sizeof(float);
-            switch (mode * 1000 + (mode == 2 ? d / 32 * 2 : dd / 16) * 100 + wv16) {
-            case 1108: ROW_LAUNCH(8, lds16, 1, 1); break;
-            case 1112: ROW_LAUNCH(12, lds16, 1, 1); break;
-            case 1208: ROW_LAUNCH(8, lds16, 2, 1); break;
-            case 1212: ROW_LAUNCH(12, lds16, 2, 1); break;
-            case 1308: ROW_LAUNCH(8, lds16, 3, 1); break;
-            case 1408: ROW_LAUNCH(8, lds16, 4, 1); break;
-            case 2208: ROW_LAUNCH(8, lds16, 1, 2); break;
-            case 2212: ROW_LAUNCH(12, lds16, 1, 2); break;
-            case 2408: ROW_LAUNCH(8, lds16, 2, 2); break;
-            case 3108: ROW_LAUNCH(8, lds16, 1, 3); break;
-            case 3112: ROW_LAUNCH(12, lds16, 1, 3); break;
-            case 3208: ROW_LAUNCH(8, lds16, 2, 3); break;
-            case 3212: ROW_LAUNCH(12, lds16, 2, 3); break;
-            case 3308: ROW_LAUNCH(8, lds16, 3, 3); break;
-            case 3408: ROW_LAUNCH(8, lds16, 4, 3); break;
-            case 4108: ROW_LAUNCH(8, lds16, 1, 4); break;
-            case 4208: ROW_LAUNCH(8, lds16, 2, 4); break;
-            case 4308: ROW_LAUNCH(8, lds16, 3, 4); break;
-            case 4408: ROW_LAUNCH(8, lds16, 4, 4); break;
-            default: return fail(GORSE_ERR_INVALID, "no ALS row kernel for nFactors %d (mode %d)", d, mode);
-            }
-        }
-#undef ROW_LAUNCH
+        const TileKernels *k = tile_kernels(d, zrow);
+        if (!k) return GORSE_ERR_INVALID;
+        // DD x (DD + 1) + DD words of M and sums per wave next to S (DD = d, or d rounded up to whole 16-column blocks in modes 3, 4)
+        const int dd = k->mode == 2 ? d : 16 * k->nb;
+        const size_t lds = ((size_t)dd * dd + (size_t)k->waves * ((size_t)dd * (dd + 1) + dd)) * sizeof(float);
+        const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(pl.n_short, k->waves), 256);  // one workgroup per CU
+        GORSE_TRY(allow_lds(k->row, lds));
+        k->row<<<dim3(grid), dim3(64 * k->waves), lds, h->stream>>>(A, B, ptr, idx, h->gram.p, pl.short_rows.p, pl.n_short, d, w, reg,
+                                                                  pad_row);
         GORSE_HIP_CHECK(hipGetLastError());
     }
     if (pl.n_long > 0) {
         GORSE_TRY(h->als_partial.ensure((size_t)pl.n_chunks * ((size_t)d * d + d)));
         const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(pl.n_chunks, kAlsWaves), 2048);
-        launch_chunks(B, idx, pl.chunk_beg.p, pl.chunk_cnt.p, pl.n_chunks, d, h->als_partial.p, h->als_zeros.p, zrow, pad_row, grid, h->stream,
-                      pl.chunk_order.p);
-        GORSE_HIP_CHECK(hipGetLastError());
+        GORSE_TRY(launch_chunks(B, idx, pl.chunk_beg.p, pl.chunk_cnt.p, pl.n_chunks, d, h->als_partial.p, zrow, pad_row, grid, h->stream,
+                                pl.chunk_order.p));
         if (pl.max_nch > 8 && !g_als_solve_adds) {  // (path | 2048: the solve kernel adds the partials itself whatever their number -- tests)
             const int stride = d * d + d;
             GORSE_TRY(h->als_reduced.ensure((size_t)pl.n_long * stride));
@@ -1953,8 +1783,7 @@ int32_t run_gram_mfma(gorse_mf *h, const float *F, int side) {
         const int64_t stride = (int64_t)dd + d;
         GORSE_TRY(h->gram_partial.ensure((size_t)pl.n_gchunks * stride));
         const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(pl.n_gchunks, kAlsWaves), 2048);
-        launch_chunks(F, pl.fb_rows.p, pl.g_beg.p, pl.g_cnt.p, pl.n_gchunks, d, h->gram_partial.p, h->als_zeros.p, zrow, pad_row, grid, h->stream);
-        GORSE_HIP_CHECK(hipGetLastError());
+        GORSE_TRY(launch_chunks(F, pl.fb_rows.p, pl.g_beg.p, pl.g_cnt.p, pl.n_gchunks, d, h->gram_partial.p, zrow, pad_row, grid, h->stream));
         als_gram_reduce_kernel<<<dim3((unsigned)ceil_div(dd, 256)), dim3(256), 0, h->stream>>>(
             h->gram_partial.p, (int)pl.n_gchunks, dd, h->gram.p, stride);
         GORSE_HIP_CHECK(hipGetLastError());
@@ -1973,6 +1802,19 @@ __global__ void als_gram_reduce_wide_kernel(const float *__restrict__ partial, i
     for (int c = 0; c < nparts; c++) acc += partial[(int64_t)c * kWidePartial + i * 128 + j];
     S[e] = acc;
 }
+// the kernels of the Wide form share one LDS layout: M (128 x kWideLd), one batch of gathered rows, the column sums
+constexpr size_t kWideLdsBytes = ((size_t)128 * kWideLd + (size_t)kWideBatch * 128 + 128) * sizeof(float);
+// how a Wide kernel reading matrix F forms G: 0 = fused multiply-adds (path | 8), 1 = the fp32 MFMA, 2 = the bf16 MFMA over split values
+// (32-bit gather offsets: als_zero_row's condition)
+int wide_mfma(const gorse_mf *h, const float *F) {
+    return g_als_wide_fma ? 0 : ((!als_split_products() || als_zero_row(h, F) < 0) ? 1 : 2);
+}
+decltype(&als_wide_kernel<false, 0>) wide_kernel(bool chunks, int mfma) {
+    static const decltype(&als_wide_kernel<false, 0>) table[2][3] = {
+        {als_wide_kernel<false, 0>, als_wide_kernel<false, 1>, als_wide_kernel<false, 2>},
+        {als_wide_kernel<true, 0>, als_wide_kernel<true, 1>, als_wide_kernel<true, 2>}};
+    return table[chunks][mfma];
+}
 int32_t run_gram_mfma_wide(gorse_mf *h, const float *F, int side) {
     const int d = h->d, dd = d * d;
     gorse_mf::AlsPlan &pl = h->als_plan[side];
@@ -1982,12 +1824,10 @@ int32_t run_gram_mfma_wide(gorse_mf *h, const float *F, int side) {
         GORSE_HIP_CHECK(hipMemsetAsync(h->gram.p, 0, (size_t)dd * sizeof(float), h->stream));
     } else {
         GORSE_TRY(h->gram_partial.ensure((size_t)pl.n_gchunks * kWidePartial));
-        const size_t wlds = ((size_t)128 * kWideLd + (size_t)kWideBatch * 128 + 128) * sizeof(float);
-        auto gk = (!als_split_products() || als_zero_row(h, F) < 0) ? als_wide_kernel<true, 1> : als_wide_kernel<true, 2>;
-        GORSE_HIP_CHECK(hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-        gk<<<dim3((unsigned)std::min<int64_t>(pl.n_gchunks, 2048)), dim3(256), wlds, h->stream>>>(
-            nullptr, F, nullptr, pl.fb_rows.p, nullptr, nullptr, pl.g_beg.p, pl.g_cnt.p, pl.n_gchunks, d, 0.0f, 0.0f, h->gram_partial.p, 0,
-            nullptr);
+        const auto gk = wide_kernel(true, wide_mfma(h, F));
+        GORSE_TRY(allow_lds(gk, kWideLdsBytes));
+        gk<<<dim3((unsigned)std::min<int64_t>(pl.n_gchunks, 2048)), dim3(256), kWideLdsBytes, h->stream>>>(
+            nullptr, F, nullptr, pl.fb_rows.p, nullptr, nullptr, pl.g_beg.p, pl.g_cnt.p, pl.n_gchunks, d, 0.0f, 0.0f, h->gram_partial.p, 0, nullptr);
         GORSE_HIP_CHECK(hipGetLastError());
         als_gram_reduce_wide_kernel<<<dim3((unsigned)ceil_div(dd, 256)), dim3(256), 0, h->stream>>>(h->gram_partial.p, (int)pl.n_gchunks,
                                                                                                    d, h->gram.p);
@@ -1997,38 +1837,82 @@ int32_t run_gram_mfma_wide(gorse_mf *h, const float *F, int side) {
     return GORSE_OK;
 }
 
-bool use_gram_form(const gorse_mf *h) { return g_als_path == 2 || (g_als_path == 0 && h->d <= 64); }
-bool use_wide_mfma(const gorse_mf *h) { return g_als_path == 0 && h->d > 64 && h->d <= 128 && !g_als_wide_fma; }
+// the rows of `side` for 64 < nFactors <= 128: als_wide_kernel over the row plan (short rows whole, long rows by chunks +
+// als_wide_long_kernel)
+int32_t run_side_wide(gorse_mf *h, int side, float *A, const float *B, const int64_t *ptr, const int32_t *idx, float w, float reg) {
+    const int d = h->d, mfma = wide_mfma(h, B);
+    gorse_mf::AlsPlan &pl = h->als_plan[side];
+    const int tok = h->prof.begin(GORSE_PROF_ALS_SWEEP, h->stream);
+    if (pl.n_short > 0) {
+        const auto k = wide_kernel(false, mfma);
+        GORSE_TRY(allow_lds(k, kWideLdsBytes));
+        k<<<dim3((unsigned)std::min<int64_t>(pl.n_short, 512)), dim3(256), kWideLdsBytes, h->stream>>>(
+            A, B, ptr, idx, h->gram.p, pl.short_rows.p, nullptr, nullptr, pl.n_short, d, w, reg, nullptr, 0, nullptr);
+        GORSE_HIP_CHECK(hipGetLastError());
+    }
+    if (pl.n_long > 0) {
+        GORSE_TRY(h->als_partial.ensure((size_t)pl.n_chunks * kWidePartial));
+        const auto k = wide_kernel(true, mfma);
+        GORSE_TRY(allow_lds(k, kWideLdsBytes));
+        k<<<dim3((unsigned)std::min<int64_t>(pl.n_chunks, 2048)), dim3(256), kWideLdsBytes, h->stream>>>(
+            A, B, ptr, idx, h->gram.p, nullptr, pl.chunk_beg.p, pl.chunk_cnt.p, pl.n_chunks, d, w, reg, h->als_partial.p, 0, nullptr);
+        GORSE_HIP_CHECK(hipGetLastError());
+        GORSE_TRY(allow_lds(als_wide_long_kernel, kWideLdsBytes));
+        als_wide_long_kernel<<<dim3((unsigned)std::min<int64_t>(pl.n_long, 512)), dim3(256), kWideLdsBytes, h->stream>>>(
+            A, h->gram.p, pl.long_rows.p, pl.long_first.p, pl.long_nch.p, pl.n_long, d, w, reg, h->als_partial.p);
+        GORSE_HIP_CHECK(hipGetLastError());
+    }
+    h->prof.end(tok, h->stream);
+    return GORSE_OK;
+}
 
-}  // namespace
-
-namespace {
-// one half of model.go:641-738: S over ALL rows (with feedback) of the other side, then the coordinate sweep of this
-// handle's row range of `side` (0: user factors from item factors, 1: item factors from user factors)
-int32_t half_epoch(gorse_mf *h, int side, float weight, float reg) {
-    const bool gram_form = use_gram_form(h);
-    float *A = side == 0 ? h->P.p : h->Q.p;
-    const float *B = side == 0 ? h->Q.p : h->P.p;
-    const int64_t *ptr = side == 0 ? h->uptr.p : h->iptr.p;
-    const int32_t *idx = side == 0 ? h->uidx.p : h->iidx.p;
-    if (gram_form) {
-        GORSE_TRY(run_gram_mfma(h, B, 1 - side));
-        GORSE_TRY(run_side_gram(h, side, A, B, ptr, idx, weight, reg));
-    } else {
-        if (use_wide_mfma(h))
-            GORSE_TRY(run_gram_mfma_wide(h, B, 1 - side));
-        else
-            GORSE_TRY(run_gram(h, B, side == 0 ? h->iptr.p : h->uptr.p, side == 0 ? h->I : h->U, GORSE_PROF_ALS_GRAM));
-        GORSE_TRY(run_sweep(h, A, B, ptr, idx, h->als_lo[side], h->als_hi[side],
-                            side == 0 ? h->max_user_row : h->max_item_row, weight, reg));
+// Which kernel family a half-sweep of this handle runs -- the whole rule, asked once per call:
+//   Residual  run_gram + run_sweep: the reference's own recurrence, any nFactors
+//   Tiles     run_gram_mfma + run_side_gram: the Gram form on MFMA tiles held by one wave, nFactors <= 64
+//   Wide      run_gram_mfma_wide + run_side_wide: the Gram form of als_wide_kernel, 64 < nFactors <= 128
+enum class AlsForm { Residual, Tiles, Wide };
+int32_t als_form(const gorse_mf *h, AlsForm &form) {
+    const int d = h->d;
+    form = AlsForm::Residual;  // path 1, and nFactors > 128
+    if (g_als_path == 2) {
+        if (d > 64) return fail(GORSE_ERR_INVALID, "the Gram-form ALS kernels cover nFactors <= 64 (got %d)", d);
+        form = AlsForm::Tiles;
+    } else if (g_als_path == 0 && d <= 128) {
+        form = d <= 64 ? AlsForm::Tiles : AlsForm::Wide;
     }
     return GORSE_OK;
+}
+
+// one half of model.go:641-738: S over ALL rows (with feedback) of the other side, then the rows of this handle's range of `side`
+// (0: user factors from item factors, 1: item factors from user factors)
+int32_t half_epoch(gorse_mf *h, int side, float weight, float reg) {
+    float *A = side == 0 ? h->P.p : h->Q.p;
+    const float *B = side == 0 ? h->Q.p : h->P.p;
+    const int64_t *ptr = side == 0 ? h->uptr.p : h->iptr.p, *optr = side == 0 ? h->iptr.p : h->uptr.p;
+    const int32_t *idx = side == 0 ? h->uidx.p : h->iidx.p;
+    AlsForm form;
+    GORSE_TRY(als_form(h, form));
+    switch (form) {
+    case AlsForm::Tiles:
+        GORSE_TRY(run_gram_mfma(h, B, 1 - side));
+        return run_side_gram(h, side, A, B, ptr, idx, weight, reg);
+    case AlsForm::Wide:
+        if (g_als_wide_fma)  // (path | 8 is round 2 as it was: S by that round's kernel too)
+            GORSE_TRY(run_gram(h, B, optr, side == 0 ? h->I : h->U, GORSE_PROF_ALS_GRAM));
+        else
+            GORSE_TRY(run_gram_mfma_wide(h, B, 1 - side));
+        return run_side_wide(h, side, A, B, ptr, idx, weight, reg);
+    case AlsForm::Residual:
+        break;
+    }
+    GORSE_TRY(run_gram(h, B, optr, side == 0 ? h->I : h->U, GORSE_PROF_ALS_GRAM));
+    return run_sweep(h, A, B, ptr, idx, h->als_lo[side], h->als_hi[side], side == 0 ? h->max_user_row : h->max_item_row, weight, reg);
 }
 int32_t als_check(gorse_mf *h) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     if (!h->has_item_csr) return fail(GORSE_ERR_INVALID, "ALS needs the item feedback CSR (item_indptr/item_indices)");
-    if (g_als_path == 2 && h->d > 64) return fail(GORSE_ERR_INVALID, "the Gram-form ALS kernels cover nFactors <= 64 (got %d)", h->d);
-    return GORSE_OK;
+    AlsForm form;
+    return als_form(h, form);
 }
 }  // namespace
 
@@ -2106,13 +1990,10 @@ extern "C" int32_t gorse_mf_rows_import(gorse_mf *h, int32_t side, int64_t begin
 }
 
 extern "C" void gorse_hip_test_set_als_path(int32_t path) {
-    g_als_path = path & 3;
-    g_als_phased = (path & 4) != 0;
+    g_als_path = path & 3;  // (bits 4, 16, 32 and 256 asked for probes that are gone: ignored)
     g_als_wide_fma = (path & 8) != 0;
-    g_als_wide_probe = (path >> 4) & 3;
     g_als_slow_gather = (path & 64) != 0;
     g_als_tile32 = (path & 128) != 0;
-    g_als_waves8 = (path & 256) != 0;
     g_als_nob3 = (path & 1024) != 0;
     g_als_solve_adds = (path & 2048) != 0;
 }
@@ -2126,10 +2007,6 @@ namespace gorse {
 // rows of one side -> short-row list (longest first) + chunks of the long rows; host CSR pointers only
 int32_t als_build_plan(gorse_mf *h, int side, const int64_t *ptr, int64_t rows, int64_t lo, int64_t hi) {
     gorse_mf::AlsPlan &pl = h->als_plan[side];
-    if (h->als_zeros.n < 64) {
-        GORSE_TRY(h->als_zeros.alloc(64));
-        GORSE_HIP_CHECK(hipMemsetAsync(h->als_zeros.p, 0, 64 * sizeof(float), h->stream));
-    }
     std::vector<int32_t> shorts, lrows, lfirst, lnch, crow, ccnt;
     std::vector<int64_t> cbeg;
     // the threshold follows the side's size (csrc/als_plan.hpp, shared with the CPU test), taken from the WHOLE side, not from [lo, hi)

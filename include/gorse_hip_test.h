@@ -117,19 +117,18 @@ void gorse_hip_test_set_sparse_heavy(int64_t entries);
  * wave, -1 = the library's choice (ds_add_f32 unless a product of a stored and a query value could fall below 2^-100,
  * where partial sums may be subnormal and the LDS adder's handling of those is not relied upon). */
 void gorse_hip_test_set_sparse_atomic(int32_t mode);
-/* ALS row-solve choice: 0 = automatic (Gram form: on the fp32 MFMA for nFactors <= 64, als_wide_kernel for 65..128; the residual
- * sweep beyond), 1 = always the residual sweep (the reference's own recurrence), 2 = always the MFMA Gram form (nFactors <= 64).
- * Both meet the 1e-4 relative bar; the hook lets the parity tests drive each one.  Probe bits on top of the choice: 4 = the
- * waves of als_row_kernel's workgroup accumulate and solve in lockstep, 8 = als_wide_kernel builds G by fused multiply-adds
- * (round 2) instead of the fp32 MFMA, 16 / 32 = timing probes of als_wide_kernel (no sweep / S not added: results undefined),
- * 64 = the first form of the Gram kernels' gather stage whatever the shape (the product takes it for factor matrices of
- * >= 4 GB or >= 2^24 rows; otherwise 32-bit offsets from a scalar base, see csrc/als.hip gram_load_stage32).
- * Which MFMA form the Gram of a row takes (csrc/als.hip als_gram_mode; default: nFactors 32 / 64 on the bf16 MFMA over three-way
- * split values, 16 / 48 on the fp32 MFMA in 16 x 16 tiles, anything else or without the fast gather stage fp32 32 x 32 tiles):
- * 1024 = no bf16 form (32 / 64 take the 16 x 16 fp32 tiles), 128 = no 16 x 16 tiles either (1024 | 128: everything in 32 x 32
- * fp32 tiles, the form of rounds 1-3); 256 = eight waves per workgroup where twelve are the default (nFactors <= 32);
+/* Which kernel family an ALS half-sweep runs (csrc/als.hip als_form), the low two bits: 0 = by nFactors (the Gram form on MFMA
+ * tiles up to 64, als_wide_kernel for 65..128, the residual sweep beyond), 1 = always the residual sweep (the reference's own
+ * recurrence), 2 = always the MFMA tiles (nFactors <= 64; an error beyond).  All meet the 1e-4 relative bar; the hook lets the
+ * parity tests drive each one.  Bits on top of the choice -- these and no others; any other bit is ignored:
+ *    8 = als_wide_kernel builds G by fused multiply-adds instead of the MFMA, and S comes from als_gram_partial_kernel;
+ *   64 = 64-bit gather addresses in the Gram kernels whatever the shape (the product takes them for factor matrices of >= 4 GB
+ *        or >= 2^24 rows; otherwise 32-bit offsets from a scalar base): als_gram_mode 4, the fp32 form of als_wide_kernel;
+ *  128 = every nFactors <= 64 takes the padded 16 x 16 fp32 tiles (als_gram_mode 3) instead of the forms specialised for
+ *        nFactors 16 / 32 / 48 / 64;
+ * 1024 = no bf16 MFMA over three-way split values: nFactors 32 / 64 take the fp32 16 x 16 tiles, 65..128 the fp32 MFMA;
  * 2048 = als_long_solve_kernel adds a long row's partial Gram matrices itself however many there are (default: rows of more
- * than eight chunks go through als_partial_reduce_kernel first; the two are equal in every bit). */
+ *        than eight chunks go through als_partial_reduce_kernel first; the two are equal in every bit). */
 void gorse_hip_test_set_als_path(int32_t path);
 /* thresholds of the Gram-form row plan, for handles created AFTERWARDS: rows longer than long_row feedbacks
  * are cut into chunks of `chunk` entries; <= 0 restores the library's choice (round 5: by the side's size -- the even
