@@ -167,6 +167,7 @@ SIGNATURES = {
     "gorse_hip_test_set_bpr_store_mode": (None, [C.c_int32]),
     "gorse_hip_test_set_sgemm_valu": (None, [C.c_int32]),
     "gorse_hip_test_sgemm_last_ms": (C.c_double, []),
+    "gorse_hip_test_sgemm_last_form": (C.c_int32, []),
     "gorse_hip_test_set_bpr_cold_window": (None, [C.c_int64]),
     "gorse_hip_test_set_bpr_replica_unit": (None, [C.c_double]),
     "gorse_hip_test_set_bpr_fold_period": (None, [C.c_int32]),
@@ -1075,6 +1076,11 @@ class Sparse:
         out = (C.c_int64 * 4)()
         lib().gorse_hip_test_sparse_sym_stats(self.h, out)
         return tuple(int(x) for x in out)
+
+
+# gorse_hip_test_sgemm_last_form (include/gorse_hip_test.h, GORSE_TEST_SGEMM_*)
+SGEMM_NONE, SGEMM_NT, SGEMM_VALU, SGEMM_MFMA64, SGEMM_MFMA128 = range(5)
+SGEMM_IN_PLACE, SGEMM_NT_LONG = 0x100, 0x200
 
 
 def sgemm(transA, transB, m, n, k, a, lda, b, ldb, c, ldc, device=0):

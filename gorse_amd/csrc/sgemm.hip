@@ -200,13 +200,33 @@ __global__ __launch_bounds__(kBlock) void sgemm_nt_kernel(int m, int n, int k, c
     }
 }
 
+// NT with rows too long for the staging above: it takes 2 k floats of LDS per group, 128 k bytes per workgroup -- the 64 KB a kernel
+// gets without asking at k = 512, more than a CU has from k = 1281 on.  Here a group reads its two rows where they lie: the 16
+// lanes' step is 64 contiguous bytes of each row, every element is read once, and the sums are dot512_lds's own (it only indexes
+// its rows: the same lane chains, the same trees, the same tails), so the result has the bits the staged form would give.
+constexpr int kNtStagedK = 64 * 1024 / (kGroupsPerBlock * 2 * (int)sizeof(float));  // 512
+__global__ __launch_bounds__(kBlock) void sgemm_nt_long_kernel(int m, int n, int k, const float *__restrict__ a, int lda,
+                                                               const float *__restrict__ b, int ldb, float *__restrict__ c,
+                                                               int ldc) {
+    const int lane = threadIdx.x & (kGroup - 1), gib = threadIdx.x / kGroup;
+    const VecShape vs(k);
+    const int64_t total = (int64_t)m * n;
+    for (int64_t t = (int64_t)blockIdx.x * kGroupsPerBlock + gib; t < total; t += (int64_t)gridDim.x * kGroupsPerBlock) {
+        const int i = (int)(t / n), j = (int)(t % n);
+        const float r = dot512_lds(a + (int64_t)i * lda, b + (int64_t)j * ldb, vs, lane);
+        if (lane == 0) c[(int64_t)i * ldc + j] = r;
+    }
+}
+
 int g_sgemm_valu = 0;  // test hook: 1 = the vector-ALU chain whatever the shape (gorse_hip_test_set_sgemm_valu)
 double g_sgemm_last_ms = 0.0;  // kernel time of the last call (hipEvents around the launch): gorse_hip_test_sgemm_last_ms
+int32_t g_sgemm_last_form = 0;  // what the last call launched (GORSE_TEST_SGEMM_*, set on the host): gorse_hip_test_sgemm_last_form
 
 }  // namespace
 
 extern "C" void gorse_hip_test_set_sgemm_valu(int32_t on) { g_sgemm_valu = on; }
 extern "C" double gorse_hip_test_sgemm_last_ms(void) { return g_sgemm_last_ms; }
+extern "C" int32_t gorse_hip_test_sgemm_last_form(void) { return g_sgemm_last_form; }
 
 namespace {
 // the pair of events around the kernel(s) of one call: released on every path out of it
@@ -226,6 +246,7 @@ struct EventPair {
 
 int32_t sgemm_check(int32_t device, int32_t transA, int32_t transB, int32_t m, int32_t n, int32_t k, const void *a, int32_t lda,
                     const void *b, int32_t ldb, const void *c, int32_t ldc) {
+    g_sgemm_last_form = GORSE_TEST_SGEMM_NONE;  // (until sgemm_on_device launches something)
     if (m < 0 || n < 0 || k < 0) return fail(GORSE_ERR_INVALID, "negative dimension");
     if (m == 0 || n == 0) return GORSE_OK;
     if (!a || !b || !c) return fail(GORSE_ERR_INVALID, "NULL matrix");
@@ -248,8 +269,14 @@ int32_t sgemm_on_device(hipStream_t st, EventPair &ev, int32_t transA, int32_t t
     (void)hipEventRecord(ev.ev0, st);
     if (!transA && transB) {
         int64_t blocks = std::min<int64_t>(ceil_div((int64_t)m * n, kGroupsPerBlock), 8192);
-        sgemm_nt_kernel<<<dim3((unsigned)blocks), dim3(kBlock), (size_t)kGroupsPerBlock * 2 * std::max(k, 1) * 4, st>>>(
-            m, n, k, da, lda, db, ldb, dc, ldc);
+        if (k <= kNtStagedK) {
+            g_sgemm_last_form = GORSE_TEST_SGEMM_NT;
+            sgemm_nt_kernel<<<dim3((unsigned)blocks), dim3(kBlock), (size_t)kGroupsPerBlock * 2 * std::max(k, 1) * 4, st>>>(
+                m, n, k, da, lda, db, ldb, dc, ldc);
+        } else {
+            g_sgemm_last_form = GORSE_TEST_SGEMM_NT | GORSE_TEST_SGEMM_NT_LONG;
+            sgemm_nt_long_kernel<<<dim3((unsigned)blocks), dim3(kBlock), 0, st>>>(m, n, k, da, lda, db, ldb, dc, ldc);
+        }
     } else if (k > 0 && (int64_t)m * n >= 64 * 64 && (int64_t)(m + 128) * (n + 128) * 4 < ((int64_t)1 << 32) && !g_sgemm_valu) {
         // the matrix cores (a tile is 128 x 128: below 64 x 64 the vector ALU form; C below 4 GB: the kernel addresses it by 32-bit offsets)
         // 128 x 128 tiles where they give every CU work (>= 512 of them: two per CU), 64 x 64 tiles otherwise.  The kernel has no edge
@@ -278,6 +305,7 @@ int32_t sgemm_on_device(hipStream_t st, EventPair &ev, int32_t transA, int32_t t
             ka = pa.p, kb = pb.p, kc = pc.p, klda = pa_cols, kldb = pb_cols, kldc = np;
         }
         (void)hipEventRecord(ev.ev0, st);  // (the figure of gorse_hip_test_sgemm_last_ms: the kernel alone)
+        g_sgemm_last_form = (big ? GORSE_TEST_SGEMM_MFMA128 : GORSE_TEST_SGEMM_MFMA64) | (whole ? GORSE_TEST_SGEMM_IN_PLACE : 0);
         dim3 grid((unsigned)(np / T), (unsigned)(mp / T)), block(256);
 #define MM(TA_, TB_)                                                                                                   \
     do {                                                                                                               \
@@ -311,6 +339,7 @@ int32_t sgemm_on_device(hipStream_t st, EventPair &ev, int32_t transA, int32_t t
         return GORSE_OK;
     } else if (k > 0) {
         dim3 grid((unsigned)ceil_div(n, TS), (unsigned)ceil_div(m, TS)), block(TS * TS);
+        g_sgemm_last_form = GORSE_TEST_SGEMM_VALU;
         if (!transA && !transB)
             sgemm_chain_kernel<false, false><<<grid, block, 0, st>>>(m, n, k, da, lda, db, ldb, dc, ldc);
         else if (transA && !transB)

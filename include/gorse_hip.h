@@ -404,7 +404,9 @@ int32_t gorse_sparse_last_stats(gorse_sparse *h, int64_t *postings, int64_t *hit
 
 /* ---- floats.MM / blas.SGEMM, common/floats/floats.go:241, mm.go:19-49 ------------------------
  * Row-major C(m x n) = op(A) op(B) with the reference's own semantics: the NN, TN and TT
- * cases ACCUMULATE into C, the NT case overwrites it (mm.go:20-48, floats_avx512.c:443-480). */
+ * cases ACCUMULATE into C, the NT case overwrites it (mm.go:20-48, floats_avx512.c:443-480).
+ * The NT case takes k <= 8192 (every such k gives floats.Dot's bits; k = 0 writes +0); a larger
+ * k is GORSE_ERR_INVALID and leaves C alone.  The other three cases have no bound on k. */
 int32_t gorse_hip_sgemm(int32_t device, int32_t transA, int32_t transB, int32_t m, int32_t n, int32_t k,
                         const float *a /*host*/, int32_t lda, const float *b /*host*/, int32_t ldb, float *c /*host*/,
                         int32_t ldc);

@@ -150,6 +150,20 @@ void gorse_hip_test_set_bpr_store_mode(int32_t store_mode);
  * gorse_hip_sgemm call in milliseconds (hipEvents around the launch, copies excluded): bench.py's `mm` object. */
 void gorse_hip_test_set_sgemm_valu(int32_t on);
 double gorse_hip_test_sgemm_last_ms(void);
+/* which kernel family the last gorse_hip_sgemm / gorse_hip_sgemm_device call of this process launched, recorded on the host where
+ * sgemm_on_device chooses it (no device code): one of NONE (m or n == 0, k == 0 outside the NT case, or the call was refused), NT
+ * (one AVX512-order dot per element), VALU (sgemm_chain_kernel), MFMA64 / MFMA128 (sgemm_mfma_kernel on 64 x 64 / 128 x 128 tiles),
+ * or'ed with IN_PLACE when the MFMA kernel ran on the caller's operands where they lie (whole tiles, k a multiple of 16) and with
+ * NT_LONG when the NT rows were longer than the LDS staging takes (k > 512) and were read from global memory.  A test asserts the
+ * form it was written for, so that a moved threshold cannot leave it testing another kernel. */
+#define GORSE_TEST_SGEMM_NONE 0
+#define GORSE_TEST_SGEMM_NT 1
+#define GORSE_TEST_SGEMM_VALU 2
+#define GORSE_TEST_SGEMM_MFMA64 3
+#define GORSE_TEST_SGEMM_MFMA128 4
+#define GORSE_TEST_SGEMM_IN_PLACE 0x100
+#define GORSE_TEST_SGEMM_NT_LONG 0x200
+int32_t gorse_hip_test_sgemm_last_form(void);
 /* test hook: runs the user-run schedule's preparation of ONE chunk (user draws, counting sort of the sample ids by user, item
  * draws by run: csrc/bpr.hip launch_prepare_users) for samples [sample_base, sample_base + n) and returns the run offsets
  * (off[u] .. off[u + 1] = the positions of user u's samples; off[U] .. off[U + 1] = samples whose user draw failed) and the
