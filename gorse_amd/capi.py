@@ -19,6 +19,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_NEG_DOT, METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_EUCLIDEAN_BF16 = 0, 1, 2, 3
 PROF_BPR_UPDATE, PROF_BPR_SAMPLE, PROF_ALS_SWEEP, PROF_ALS_GRAM, PROF_BPR_SORT, PROF_COMM = 0, 1, 2, 3, 4, 5
 COMM_ID_BYTES = 128
+MF_EVAL_MAX_TOPK = 128  # GORSE_MF_EVAL_MAX_TOPK
 OPT_SGD, OPT_ADAM = 0, 1
 PROF_TOPK_SCORE, PROF_TOPK_RESCORE, PROF_TOPK_SWEEP, PROF_TOPK_SELECT, PROF_TOPK_HIST, PROF_TOPK_REPLAY = 0, 1, 2, 3, 4, 5
 
@@ -45,6 +46,9 @@ SIGNATURES = {
     "gorse_mf_resident_candidates": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_mf_resident_generation": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     "gorse_mf_rank_resident": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p, _i32p]),
+    "gorse_mf_evaluate_resident": (C.c_int32, [_vp, C.c_int32, _f32p, _f32p, _f32p, _i32p, _i32p]),
+    "gorse_mf_evaluate": (C.c_int32, [_vp, C.c_int64, _i32p, _i64p, _i32p, _i64p, _i32p, C.c_int32, _f32p, _f32p, _f32p]),
+    "gorse_mf_evaluate_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
     "gorse_bpr_epoch": (C.c_int32, [_vp, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32,
                                     _i32p, _f64p]),
     "gorse_bpr_epoch_enqueue": (C.c_int32, [_vp, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int64,
@@ -183,6 +187,8 @@ SIGNATURES = {
     "gorse_hip_test_set_fm_evaluate": (None, [C.c_int64, C.c_int32]),
     "gorse_hip_test_fm_auc": (C.c_int32, [_vp, _f32p, C.c_int64, _f32p, C.c_int64, _i64p, _f32p]),
     "gorse_hip_test_fm_evaluate_times": (C.c_int32, [_vp, _f64p]),
+    "gorse_hip_test_mf_evaluate_times": (C.c_int32, [_vp, _f64p]),
+    "gorse_hip_test_mf_evaluate_tables": (C.c_int32, [_f32p, _f32p, C.c_int32]),
 }
 
 
@@ -220,6 +226,13 @@ def device_count():
     n = C.c_int32(0)
     rc = lib().gorse_hip_device_count(C.byref(n))
     return n.value if rc == OK else 0
+
+
+def mf_evaluate_tables(n=MF_EVAL_MAX_TOPK):
+    """the evaluation kernel's two tables as the library fills them: (1 / log2f(i + 2) for i < n, IDCG prefix sums for k <= n)"""
+    inv_log, idcg = np.zeros(n, np.float32), np.zeros(n + 1, np.float32)
+    check(lib().gorse_hip_test_mf_evaluate_tables(inv_log.ctypes.data_as(_f32p), idcg.ctypes.data_as(_f32p), n))
+    return inv_log, idcg
 
 
 def _arr(a, dtype):
@@ -333,6 +346,46 @@ class MF:
         if nu.value:
             check(lib().gorse_mf_rank_resident(self.h, topk, _p(users, _i32p), _p(rank, _i32p), _p(rlen, _i32p)))
         return users, rank, rlen
+
+    def evaluate_resident(self, topk, per_user=False, ranks=False):
+        """cf.Evaluate's ranking and metrics over the resident lists (gorse_mf_evaluate_resident): (sums 6, count), the metrics
+        in the order NDCG, Precision, Recall, HR, MAP, MRR; then per_user 6 x n_users when asked for, then (rank n_users x topk
+        padded with -1, lengths) when asked for"""
+        nu, nc = C.c_int64(0), C.c_int64(0)
+        check(lib().gorse_mf_resident_candidates(self.h, C.byref(nu), C.byref(nc)))
+        sums, count = np.full(6, np.nan, np.float32), C.c_float(0)
+        pu = np.full((6, nu.value), np.nan, np.float32) if per_user else None
+        rank = np.full((nu.value, max(int(topk), 0)), -2, np.int32) if ranks else None
+        rlen = np.full(nu.value, -2, np.int32) if ranks else None
+        check(lib().gorse_mf_evaluate_resident(self.h, topk, _p(sums, _f32p), C.byref(count), _p(pu, _f32p), _p(rank, _i32p),
+                                               _p(rlen, _i32p)))
+        return (sums, np.float32(count.value)) + ((pu,) if per_user else ()) + ((rank, rlen) if ranks else ())
+
+    def evaluate(self, users, target_indptr, targets, cand_indptr, cand, topk, per_user=False):
+        """the same over lists given here (gorse_mf_evaluate): targets and candidates as CSRs with one row per entry of users"""
+        users, tp, cp = _arr(users, np.int32), _arr(target_indptr, np.int64), _arr(cand_indptr, np.int64)
+        tg, cd = _arr(targets, np.int32), _arr(cand, np.int32)
+        if tp.size != users.size + 1 or cp.size != users.size + 1:
+            raise GorseHipError(ERR_INVALID, "target_indptr and cand_indptr must have n_users + 1 entries")
+        tg = tg if tg.size else np.zeros(1, np.int32)
+        cd = cd if cd.size else np.zeros(1, np.int32)
+        sums, count = np.full(6, np.nan, np.float32), C.c_float(0)
+        pu = np.full((6, users.size), np.nan, np.float32) if per_user else None
+        check(lib().gorse_mf_evaluate(self.h, users.size, _p(users, _i32p), _p(tp, _i64p), _p(tg, _i32p), _p(cp, _i64p),
+                                      _p(cd, _i32p), topk, _p(sums, _f32p), C.byref(count), _p(pu, _f32p)))
+        return (sums, np.float32(count.value)) + ((pu,) if per_user else ())
+
+    def evaluate_stats(self):
+        """the last evaluate / evaluate_resident: (users counted, candidates scored, device milliseconds)"""
+        nu, nc, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        check(lib().gorse_mf_evaluate_stats(self.h, C.byref(nu), C.byref(nc), C.byref(ms)))
+        return nu.value, nc.value, ms.value
+
+    def evaluate_stage_times(self):
+        """device milliseconds of the last evaluation by stage: (per-user kernel, sum chain)"""
+        ms = np.zeros(2, np.float64)
+        check(lib().gorse_hip_test_mf_evaluate_times(self.h, _p(ms, _f64p)))
+        return float(ms[0]), float(ms[1])
 
     def set_bpr_cold_window(self, samples):
         """the cold window of THIS handle (GORSE_BPR_HOGWILD_STORES); returns the number of cold items"""

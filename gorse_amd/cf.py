@@ -223,6 +223,11 @@ class _Model:
         self.epochs_done = done.value
         return Score(score[0], score[1], score[2])
 
+    def SetHostEvaluate(self, on):
+        """True: Evaluate (Fit's included) ranks on the device and walks the metrics on the host, the route before
+        gorse_mf_evaluate; the default computes the metrics and their sums on the device.  Both give the same bits."""
+        host().gh_model_set_host_evaluate(self.p, int(bool(on)))
+
     def Predict(self, user_id, item_id):
         out = C.c_float(0)
         _ck(host().gh_model_predict(self.p, str(user_id).encode(), str(item_id).encode(), C.byref(out)))

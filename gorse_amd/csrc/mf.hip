@@ -538,6 +538,8 @@ extern "C" int32_t gorse_mf_destroy(gorse_mf *h) {
     }
     for (int i = 0; i < gorse_mf::kChunkRing; i++)
         if (h->ev_chunk[i]) (void)hipEventDestroy(h->ev_chunk[i]);
+    for (hipEvent_t e : h->mfe_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->ep_events)
         for (int i = 0; i < gorse_mf::kEpochRing; i++) {
             (void)hipEventDestroy(h->ev_ep_begin[i]);

@@ -113,6 +113,12 @@ struct gorse_mf {
     int64_t ev_users_n = 0, ev_cand_n = 0;
     bool ev_valid = false;
     uint64_t ev_generation = 0;  // bumped by every gorse_mf_sample_user_negatives (gorse_mf_resident_generation)
+    // gorse_mf_evaluate / _resident (mf_eval.hip): the 1 / log2 and IDCG tables, the stage events (both made by the first call), and
+    // the last call's users counted, candidates scored and device milliseconds (per-user kernel | sum chain)
+    gorse::DevBuf<float> mfe_tab;
+    hipEvent_t mfe_ev[3] = {nullptr, nullptr, nullptr};
+    int64_t mfe_users = 0, mfe_cands = 0;
+    double mfe_ms[2] = {0.0, 0.0};
     // generic staging
     gorse::DevBuf<char> stage, rank_in;
     // gorse_mf_recommend (recommend.hip): its inputs, the fast path's buffers, the literal path's candidate lists; the last call's split

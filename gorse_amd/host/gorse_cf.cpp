@@ -248,13 +248,40 @@ std::vector<std::vector<MatrixFactorization::Recommended>> MatrixFactorization::
     return out;
 }
 
+// which of the C ABI's six metrics a scorer is (gorse_mf_evaluate's order); -1: a function of the caller's own
+static int metric_id(Metric m) {
+    static const Metric table[] = {NDCG, Precision, Recall, HR, MAP, MRR};
+    for (int k = 0; k < 6; k++)
+        if (m == table[k]) return k;
+    return -1;
+}
+
 std::vector<float> Evaluate(MatrixFactorization &estimator, dataset::Dataset &testSet, dataset::Dataset &trainSet, int topK,
                             int numCandidates, int nJobs, const std::vector<Metric> &scorers) {
     (void)nJobs;  // the device ranks every user at once; sums are taken in user order (== nJobs 1)
     // a production split has no preloaded negatives: sample them on the device when the handle of this Fit holds trainSet
     // (the host loop of Dataset::SampleUserNegatives draws the same lists, only user after user)
     if (!testSet.HasNegatives()) estimator.SampleNegativesOnDevice(testSet, trainSet, numCandidates);
-    if (estimator.HasResidentCandidates(testSet, numCandidates)) {  // every later Evaluate of the Fit: no upload, rank lists only
+    // The device route (csrc/mf_eval.hip): rank lists and metrics there, six user-order sums back -- whenever every scorer is one
+    // of the six metrics and the heap of topK + 1 slots fits the kernel's LDS.  What it returns equals the host route below in
+    // every bit (tests/test_gpu_mf_evaluate.py); the host route stays as the yardstick and for a caller's own scorers.
+    std::vector<int> ids;
+    for (Metric m : scorers) ids.push_back(metric_id(m));
+    const bool onDevice = !estimator.HostEvaluate() && topK > 0 && topK <= GORSE_MF_EVAL_MAX_TOPK &&
+                          std::find(ids.begin(), ids.end(), -1) == ids.end();
+    auto fromDevice = [&](const float sums[6], float count) {
+        std::vector<float> sum(scorers.size());
+        for (size_t m = 0; m < scorers.size(); m++) sum[m] = sums[ids[m]];
+        const float inv = 1 / count;
+        for (auto &x : sum) x *= inv;  // floats.MulConst(sum, 1/count)
+        return sum;
+    };
+    if (onDevice && estimator.HasResidentCandidates(testSet, numCandidates)) {  // every Evaluate of a Fit: no upload, six sums back
+        float sums[6], count = 0;
+        estimator.EvaluateResident(topK, sums, count);
+        return fromDevice(sums, count);
+    }
+    if (estimator.HasResidentCandidates(testSet, numCandidates)) {  // no upload, rank lists only
         const auto &tf = testSet.GetUserFeedback();
         std::vector<int32_t> users;
         auto ranks = estimator.RankResident(users, topK);
@@ -284,6 +311,13 @@ std::vector<float> Evaluate(MatrixFactorization &estimator, dataset::Dataset &te
         users.push_back(u);
         cands.push_back(std::move(c));
         targets.push_back(std::move(t));
+    }
+    if (onDevice && !users.empty()) {  // preloaded negatives: the lists go up, six sums come back
+        std::vector<std::vector<int32_t>> rows;
+        for (int32_t u : users) rows.push_back(tf[(size_t)u]);  // the rows as stored: the kernel counts the distinct items
+        float sums[6], count = 0;
+        estimator.EvaluateMany(users, rows, cands, topK, sums, count);
+        return fromDevice(sums, count);
     }
     std::vector<float> sum(scorers.size(), 0.0f);
     float count = 0;

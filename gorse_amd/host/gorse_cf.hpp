@@ -684,6 +684,23 @@ class MatrixFactorization {
         return out;
     }
 
+    // Evaluate on the device (gorse_mf_evaluate_resident / gorse_mf_evaluate, csrc/mf_eval.hip): rank lists AND the six metrics
+    // there, six float32 user-order sums and the count back.  sums are indexed NDCG, Precision, Recall, HR, MAP, MRR.
+    // SetHostEvaluate(true) keeps Evaluate on the route above (rank lists to the host, metrics here), as ctr::FM spells it.
+    void SetHostEvaluate(bool on) { hostEvaluate_ = on; }
+    bool HostEvaluate() const { return hostEvaluate_; }
+    void EvaluateResident(int topK, float sums[6], float &count) { check(gorse_mf_evaluate_resident(h_, topK, sums, &count, nullptr, nullptr, nullptr)); }
+    void EvaluateMany(const std::vector<int32_t> &users, const std::vector<std::vector<int32_t>> &targets,
+                      const std::vector<std::vector<int32_t>> &cands, int topK, float sums[6], float &count) {
+        ensure_resident();
+        std::vector<int64_t> tptr, cptr;
+        std::vector<int32_t> tflat, cflat;
+        flatten_rows(targets, tptr, tflat);
+        flatten_rows(cands, cptr, cflat);
+        check(gorse_mf_evaluate(h_, (int64_t)users.size(), users.data(), tptr.data(), tflat.data(), cptr.data(), cflat.data(), topK, sums,
+                                &count, nullptr));
+    }
+
     // Every user's n best unseen items on a fitted model (gorse_mf_recommend): the bulk form of the worker's per-user loop
     // (worker/pipeline.go:403-448), for CacheSize = n the prefix of length n of the reference's list.  Excluded are the user's
     // training row WHEN the resident handle holds the training set (HandleHoldsTrainingRows: true from Fit on, until the model is
@@ -723,6 +740,12 @@ class MatrixFactorization {
         resident_gen_ = 0;
     }
     util::RandomGenerator &GetRandomGenerator() { return rng_; }
+    static void flatten_rows(const std::vector<std::vector<int32_t>> &rows, std::vector<int64_t> &ptr, std::vector<int32_t> &flat) {
+        ptr.assign(rows.size() + 1, 0);
+        for (size_t t = 0; t < rows.size(); t++) ptr[t + 1] = ptr[t] + (int64_t)rows[t].size();
+        flat.resize((size_t)ptr.back() + 1);  // (never empty: the C ABI wants a pointer)
+        for (size_t t = 0; t < rows.size(); t++) std::copy(rows[t].begin(), rows[t].end(), flat.begin() + ptr[t]);
+    }
     // the shared evaluate / early-stopping epoch loop of BPR.Fit and ALS.Fit (model.go:432-440, 496-518)
     Score fit_loop(const char *tag, int nEpochs, dataset::Dataset &trainSet, dataset::Dataset &valSet, const FitConfig &config,
                    const std::function<int32_t(int)> &run_epoch);
@@ -732,6 +755,7 @@ class MatrixFactorization {
     util::RandomGenerator rng_{0};
     gorse_mf *h_ = nullptr;
     bool borrowed_ = false;
+    bool hostEvaluate_ = false;
     int epochs_done_ = 0;  // fit_loop
     int device_ = 0;
     const void *handle_train_ = nullptr;   // the training set the resident handle was created from (a Fit in progress)

@@ -244,6 +244,8 @@ int32_t gh_evaluate(void *m, void *test, void *train, int32_t topk, int32_t cand
         for (int32_t k = 0; k < n_metrics; k++) out[k] = r[(size_t)k];
     });
 }
+// MatrixFactorization::SetHostEvaluate: Evaluate (Fit's included) ranks on the device and walks the metrics on the host
+void gh_model_set_host_evaluate(void *m, int32_t on) { ((cf::MatrixFactorization *)m)->SetHostEvaluate(on != 0); }
 float gh_metric(int32_t id, const int32_t *target, int32_t nt, const int32_t *rank, int32_t nr) {
     static const cf::Metric table[] = {cf::NDCG, cf::Precision, cf::Recall, cf::HR, cf::MAP, cf::MRR};
     return table[id](cf::TargetSet(target, target + nt), std::vector<int32_t>(rank, rank + nr));

@@ -160,6 +160,30 @@ int32_t gorse_mf_resident_generation(gorse_mf *h, uint64_t *generation /*out*/);
 int32_t gorse_mf_rank_resident(gorse_mf *h, int32_t topk, int32_t *users_out /*host or NULL*/, int32_t *rank_out /*host*/,
                                int32_t *rank_len /*host*/);
 
+/* cf.Evaluate's ranking and metrics on the device (model/cf/evaluator.go:35-160; csrc/mf_eval.hip): per evaluated user the rank
+ * list of gorse_mf_rank (every index, ties as container/heap leaves them) and from it the six metrics NDCG, Precision, Recall, HR,
+ * MAP, MRR -- in this order everywhere below -- against the user's target row: membership is targetSet.Contains(item), the
+ * denominators use the number of DISTINCT targets, every operation is the reference's float32 one in its order.  sums[m] is metric
+ * m's float32 running sum over the users in user order (nJobs = 1), *count the float32 number of users counted; the caller forms
+ * sums[m] * (1 / count) as floats.MulConst does.  per_user (host or NULL) receives 6 x n_users values, metric-major.
+ * topk outside 1 .. GORSE_MF_EVAL_MAX_TOPK: GORSE_ERR_INVALID (the heap's topk + 1 slots live in LDS) -- rank on the device and
+ * walk the metrics on the host then. */
+#define GORSE_MF_EVAL_MAX_TOPK 128
+/* ... over the resident candidate lists gorse_mf_sample_user_negatives left, against the resident test rows: nothing is uploaded,
+ * and unless per_user / rank_out / rank_len (gorse_mf_rank_resident's outputs, host or NULL) are asked for, six sums come back.
+ * Nothing resident: GORSE_ERR_INVALID, as gorse_mf_rank_resident. */
+int32_t gorse_mf_evaluate_resident(gorse_mf *h, int32_t topk, float *sums /*host, 6*/, float *count /*host*/,
+                                   float *per_user /*host 6 x n_users, or NULL*/, int32_t *rank_out /*host or NULL*/,
+                                   int32_t *rank_len /*host or NULL*/);
+/* ... over lists the caller uploads (a test set with preloaded negatives): users, candidate CSR and validation as gorse_mf_rank,
+ * targets as a CSR with one row per entry of users.  A user with an empty target row is skipped and not counted
+ * (evaluator.go:47); its per_user column holds zeros.  A counted user with no candidates yields the reference's 0 / 0 = NaN. */
+int32_t gorse_mf_evaluate(gorse_mf *h, int64_t n_users, const int32_t *users /*host*/, const int64_t *target_indptr /*host*/,
+                          const int32_t *targets /*host*/, const int64_t *cand_indptr /*host*/, const int32_t *cand /*host*/,
+                          int32_t topk, float *sums /*host, 6*/, float *count /*host*/, float *per_user /*host 6 x n_users, or NULL*/);
+/* the handle's last evaluation: users counted, candidates scored, device time of its two kernels (events on the handle's stream) */
+int32_t gorse_mf_evaluate_stats(gorse_mf *h, int64_t *users, int64_t *candidates, double *device_ms);
+
 /* ---- BPR, model/cf/model.go:446-494 ------------------------------------------------------
  * One call = n_samples SGD steps (the reference does CountFeedback() per epoch).
  * Sampling (model.go:449-468) runs on the device from a counter-based Philox4x32-10 stream

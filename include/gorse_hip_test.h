@@ -236,6 +236,11 @@ int32_t gorse_hip_test_fm_auc(gorse_fm *h, const float *pos /*host*/, int64_t n_
                               int64_t *counts /*host, GORSE_FM_EVAL_COUNTS entries*/, float *auc_sum /*host*/);
 /* device milliseconds of the handle's last gorse_fm_evaluate by stage: scoring | keys, sort and per-positive counts | the chain */
 int32_t gorse_hip_test_fm_evaluate_times(gorse_fm *h, double *ms3 /*host*/);
+/* device milliseconds of the handle's last gorse_mf_evaluate / _resident by stage: the per-user kernel | the sum chain */
+int32_t gorse_hip_test_mf_evaluate_times(gorse_mf *h, double *ms2 /*host*/);
+/* the two tables the evaluation kernel reads, filled as the library fills them (no device needed): inv_log[i] = 1 / log2f(i + 2)
+ * for i < n, idcg[k] = inv_log[0] + ... + inv_log[k - 1] for k <= n (n + 1 entries); n <= GORSE_MF_EVAL_MAX_TOPK */
+int32_t gorse_hip_test_mf_evaluate_tables(float *inv_log /*host, n*/, float *idcg /*host, n + 1*/, int32_t n);
 
 #ifdef __cplusplus
 }

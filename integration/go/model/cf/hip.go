@@ -187,6 +187,44 @@ func (m *hipModel) evaluateResident(testSet, trainSet dataset.CFSplit, topK, num
 	return sum
 }
 
+// The six metrics of evaluator.go:75-160 in the order of gorse_mf_evaluate's sums.
+const (
+	MetricNDCG = iota
+	MetricPrecision
+	MetricRecall
+	MetricHR
+	MetricMAP
+	MetricMRR
+)
+
+// evaluateDevice is evaluateResident with the metrics and their sums computed on the device too (gorse_mf_evaluate_resident): per
+// user the rank list of gorse_mf_rank_resident and from it the six metrics in the reference's float32 operations, then the running
+// sums over the users in user order (Evaluate with nJobs = 1).  Six sums and the count come back; the result equals
+// evaluateResident's in every bit.  Go cannot compare function values, so the scorers are named by the constants above; a caller
+// with a Metric of its own, or a topK above GORSE_MF_EVAL_MAX_TOPK, calls evaluateResident.
+func (m *hipModel) evaluateDevice(testSet, trainSet dataset.CFSplit, topK, numCandidates int, seed uint64, metrics ...int) []float32 {
+	if !m.negativesResident {
+		indptr, indices := flatten(testSet.GetUserFeedback())
+		if rc := C.gorse_mf_sample_user_negatives(m.h, (*C.int64_t)(unsafe.Pointer(&indptr[0])), (*C.int32_t)(unsafe.Pointer(&indices[0])),
+			C.int32_t(numCandidates), C.uint64_t(seed), nil, nil); rc != 0 {
+			panic(hipError("gorse_mf_sample_user_negatives", rc))
+		}
+		m.negativesResident = true
+	}
+	var sums [6]C.float
+	var count C.float
+	if rc := C.gorse_mf_evaluate_resident(m.h, C.int32_t(topK), &sums[0], &count, nil, nil, nil); rc != 0 {
+		panic(hipError("gorse_mf_evaluate_resident", rc))
+	}
+	sum := make([]float32, len(metrics))
+	for i, id := range metrics {
+		sum[i] = float32(sums[id])
+	}
+	// count = 0 (a validation split without feedback): 0 * +Inf = NaN, as in the reference (evaluator.go:69-70)
+	floats.MulConst(sum, 1/float32(count))
+	return sum
+}
+
 // earlyStop is the patience rule of model.go:508-517 on the recorded (epoch, NDCG) pairs.
 func earlyStop(scores []lo.Tuple2[int, float32], epoch, patience int) (lo.Tuple2[int, float32], bool) {
 	if patience <= 0 || epoch <= patience {
