@@ -157,6 +157,7 @@ SIGNATURES = {
     "gorse_hip_test_set_sparse_sym": (None, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gorse_hip_test_set_sparse_front": (None, [C.c_int32]),
     "gorse_hip_test_sparse_sym_stats": (None, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "gorse_hip_test_sparse_path_stats": (None, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gorse_hip_test_set_sparse_tile": (None, [C.c_int32]),
     "gorse_hip_test_set_scan_literal": (None, [C.c_int32]),
     "gorse_hip_test_set_sparse_split": (None, [C.c_int64]),
@@ -1128,6 +1129,12 @@ class Sparse:
         """the last call: (ran in symmetric form, rows redone after a foreign list overflowed, foreign entries ranked, longest foreign list)"""
         out = (C.c_int64 * 4)()
         lib().gorse_hip_test_sparse_sym_stats(self.h, out)
+        return tuple(int(x) for x in out)
+
+    def path_stats(self):
+        """the last call: (launch rounds, heavy queries over the rounds); the handle: (row ranges of the heavy-query kernel, directory cells)"""
+        out = (C.c_int64 * 4)()
+        lib().gorse_hip_test_sparse_path_stats(self.h, out)
         return tuple(int(x) for x in out)
 
 

@@ -59,6 +59,7 @@ struct gorse_sparse {
         std::vector<sparse::Work> work;
     } plan;
     int64_t last_sym[4] = {0, 0, 0, 0};  // the last call: ran symmetric, rows redone, foreign entries ranked, longest foreign list
+    int64_t last_path[2] = {0, 0};  // the last call: launch rounds, heavy queries over the rounds (gorse_hip_test_sparse_path_stats)
     KernelProfile prof{1};
     int64_t last_postings = 0, last_hits = 0;
     int32_t use() const {
@@ -304,6 +305,7 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
     std::vector<sparse::Work> &work = plan.work;
     std::vector<int32_t> &heavy_t = plan.heavy_t, &heavy_pslot = plan.heavy_pslot, &nparts = plan.nparts;
     const bool one_launch = longs.size() <= per_launch;  // (a plan is kept across calls only then)
+    h->last_path[0] = h->last_path[1] = 0;
     for (size_t l0 = 0; l0 == 0 || l0 < longs.size(); l0 += per_launch) {
         const size_t l1 = std::min(longs.size(), l0 + per_launch);
         if (!(plan_hit && one_launch)) {
@@ -328,6 +330,7 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
                 for (int32_t t : shorts) work.push_back(sparse::Work{t, -1, 0, 0});
         }
         if (work.empty() && heavy_t.empty()) break;
+        h->last_path[0]++, h->last_path[1] += (int64_t)heavy_t.size();
         const size_t n_long = l1 - l0;
         const bool upload = !(plan_hit && one_launch && plan.on_device);
         GORSE_TRY(h->work.ensure(work.size()));
@@ -763,6 +766,10 @@ extern "C" void gorse_hip_test_set_sparse_sym(int32_t mode, int32_t c1, int32_t 
 }
 extern "C" void gorse_hip_test_sparse_sym_stats(const gorse_sparse *h, int64_t out[4]) {
     for (int i = 0; i < 4; i++) out[i] = h ? h->last_sym[i] : 0;
+}
+extern "C" void gorse_hip_test_sparse_path_stats(const gorse_sparse *h, int64_t out[4]) {
+    out[0] = h ? h->last_path[0] : 0, out[1] = h ? h->last_path[1] : 0;
+    out[2] = h ? h->n_ranges : 0, out[3] = h ? h->Dc * h->ngroups : 0;
 }
 extern "C" void gorse_hip_test_set_sparse_table(int32_t cap_shift) { g_sparse_cap_shift = cap_shift >= 2 && cap_shift <= 6 ? cap_shift : 2; }
 extern "C" void gorse_hip_test_set_sparse_tile(int32_t rows) { g_sparse_tile = rows; }

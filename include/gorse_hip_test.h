@@ -104,6 +104,10 @@ void gorse_hip_test_set_sparse_front(int32_t front);
 /* the last call of the handle: out[0] = it ran in symmetric form, [1] = rows redone after an overflow, [2] = foreign entries ranked,
  * [3] = the longest foreign list */
 void gorse_hip_test_sparse_sym_stats(const gorse_sparse *h, int64_t out[4]);
+/* which paths the last search / all-pairs call of the handle took (read only): out[0] = launch rounds (a call with more long queries
+ * than its partial rankings and dense copies may hold takes several), [1] = heavy queries (sparse_rows_kernel), summed over the rounds,
+ * [2] = the handle's row ranges of sparse_rows_kernel, [3] = its directory cells (distinct indices x row groups). */
+void gorse_hip_test_sparse_path_stats(const gorse_sparse *h, int64_t out[4]);
 /* rows per group of a handle created AFTERWARDS (the posting lists are cut by row group, csrc/sparse_kernels.hpp): a power of two
  * in 256 .. 16384; 0 = 2048.  A workgroup holds a group's accumulators: 5.5 bytes of LDS per row. */
 void gorse_hip_test_set_sparse_tile(int32_t rows);
