@@ -160,6 +160,8 @@ SIGNATURES = {
     "gorse_hip_test_sparse_path_stats": (None, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gorse_hip_test_set_sparse_tile": (None, [C.c_int32]),
     "gorse_hip_test_set_scan_literal": (None, [C.c_int32]),
+    "gorse_hip_test_topk_scan_flags": (C.c_int32, [_vp, _i32p, C.c_int64]),
+    "gorse_hip_test_set_scan_block": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_split": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_heavy": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_atomic": (None, [C.c_int32]),
@@ -871,6 +873,12 @@ class TopK:
         """per-query flags of the last MFMA search's last chunk behind the rescoring (non-zero: the query took the tie path)"""
         f = np.empty(n, np.uint8)
         check(lib().gorse_hip_test_topk_get_flags(self.h, f.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return f
+
+    def scan_flags(self, n):
+        """flags of the last scan block of the last call (1: select_fast_kernel left the query to the literal kernel or the reroute)"""
+        f = np.empty(n, np.int32)
+        check(lib().gorse_hip_test_topk_scan_flags(self.h, _p(f, _i32p), n))
         return f
 
     def foreign_counts(self, n):

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void dist_kernel(const float *__restrict__ 
             if (metric == GORSE_METRIC_NEG_DOT)
                 r = -ab;
             else
-                r = 1.0f - ab / (sqrtf(qq) * sqrtf(norm2[i]));
+                r = cosine_distance(ab, qq, norm2[i]);
         }
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) dist[q * N + i] = r;
@@ -131,10 +131,6 @@ __device__ inline uint32_t ascending_key(float w) {  // smaller distance <=> sma
     uint32_t u = __float_as_uint(w);
     if ((u << 1) == 0) u = 0;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float key_distance(uint32_t key) {
-    const uint32_t u = (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
-    return __uint_as_float(u);
 }
 __global__ __launch_bounds__(kSelThreads) void select_fast_kernel(const float *__restrict__ dist, const int64_t *__restrict__ qidx,
                                                                   int64_t N, int k, int prune0, int32_t *__restrict__ out_idx,
@@ -222,13 +218,20 @@ __global__ __launch_bounds__(kSelThreads) void select_fast_kernel(const float *_
         if (tid == 0) literal[q] = 1;
         return;
     }
+    // what is returned is the STORED distance: the key has folded -0 (-floats.Dot of an orthogonal pair) onto +0
+    const int take = min(k, A);
+    for (int i = tid; i < take; i += kSelThreads) {
+        const uint32_t row = (uint32_t)s_sel[i];
+        s_sel[i] = ((unsigned long long)__float_as_uint(dq[row]) << 32) | (unsigned long long)row;
+    }
+    __syncthreads();
     if (tid == 0) {
-        const int take = min(k, A);
         int n = 0;
         for (int i = 0; i < take; i++) {
-            const float w = key_distance((uint32_t)(s_sel[i] >> 32));
+            const int32_t row = (int32_t)(uint32_t)s_sel[i];
+            const float w = __uint_as_float((uint32_t)(s_sel[i] >> 32));
             if (!prune0 || w > 0) {
-                out_idx[q * k + n] = (int32_t)(uint32_t)s_sel[i];
+                out_idx[q * k + n] = row;
                 out_dist[q * k + n] = w;
                 n++;
             }
@@ -250,6 +253,7 @@ int scan_groups(int d) {
 }
 constexpr int64_t kDistBudget = (int64_t)1 << 28;  // floats in the distance slab (1 GiB)
 int g_scan_literal_only = 0;  // test hook: every query of the scan through the literal heap kernel
+int64_t g_scan_block = 0;      // test hook: > 0 = queries per scan block instead of the budget's (topk_scan_block_queries)
 constexpr int64_t kMinRerouteQueries = (int64_t)1 << 40;  // "enough queries": asks topk_mfma_usable about the index and k only
 
 }  // namespace
@@ -298,7 +302,10 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
         GORSE_HIP_CHECK(hipGetLastError());
     }
     h->prof.end(tok, h->stream);
-    std::vector<int32_t> flags;
+    h->scan_last_nq = nq;
+    h->scan_last_literal_only = g_scan_literal_only != 0;
+    h->scan_flags_on_host = false;
+    std::vector<int32_t> &flags = h->scan_flags_host;
     if (reroute) {
         flags.resize((size_t)nq);
         GORSE_HIP_CHECK(hipMemcpyAsync(flags.data(), literal, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
@@ -328,6 +335,9 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
     GORSE_TRY(topk_mfma_search(h, qidx_host ? ids.data() : nullptr, -1, qidx_host ? nullptr : qf.p, (int64_t)nf, k, prune0, ti.data(),
                                td.data(), tc.data()));
     h->n_fallback += keep_fallback;
+    h->scan_last_nq = nq;  // the replay may have scanned what it left undecided: the hook reports this block
+    h->scan_last_literal_only = false;
+    h->scan_flags_on_host = true;
     for (size_t r = 0; r < nf; r++) {
         const int64_t t = todo[r];
         if (idx_out) memcpy(idx_out + t * k, ti.data() + r * k, (size_t)k * 4);
@@ -338,7 +348,7 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
 }
 
 int64_t topk_scan_block_queries(const gorse_topk *h) {
-    int64_t b = kDistBudget / std::max<int64_t>(h->N, 1);
+    int64_t b = g_scan_block > 0 ? g_scan_block : kDistBudget / std::max<int64_t>(h->N, 1);
     return std::max<int64_t>(1, std::min<int64_t>(b, 65535));
 }
 
@@ -429,6 +439,7 @@ extern "C" int32_t gorse_topk_search_index(gorse_topk *h, const int64_t *q, int6
     if (nq == 0) return GORSE_OK;
     GORSE_TRY(h->use());
     h->n_fallback = 0;
+    h->scan_last_nq = 0;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, q, -1, nullptr, nq, k, prune0, idx_out, dist_out, count_out);
     const int64_t bq = topk_scan_block_queries(h);
     GORSE_TRY(h->qidx.ensure((size_t)std::min(bq, nq)));
@@ -453,6 +464,7 @@ extern "C" int32_t gorse_topk_search_vector(gorse_topk *h, const void *qv, int64
     if (nq == 0) return GORSE_OK;
     GORSE_TRY(h->use());
     h->n_fallback = 0;
+    h->scan_last_nq = 0;
     if (topk_mfma_usable(h, nq, k)) {  // all query vectors to the device as fp32, then path B
         GORSE_TRY(h->qf32.ensure((size_t)nq * h->d));
         if (h->dtype == GORSE_DTYPE_BF16) {
@@ -499,6 +511,7 @@ extern "C" int32_t gorse_topk_all_pairs(gorse_topk *h, int64_t q_begin, int64_t 
     if (nq == 0) return GORSE_OK;
     GORSE_TRY(h->use());
     h->n_fallback = 0;
+    h->scan_last_nq = 0;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, nullptr, q_begin, nullptr, nq, k, 0, idx_out, dist_out, nullptr);
     const int64_t bq = topk_scan_block_queries(h);
     const int64_t mb = std::min(bq, nq);
@@ -659,3 +672,23 @@ extern "C" int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out
 }
 
 extern "C" void gorse_hip_test_set_scan_literal(int32_t on) { g_scan_literal_only = on != 0; }
+// test hook: > 0 = queries per block of the scan (still at most 65535, the grid's y limit), 0 = by the distance slab's budget
+extern "C" void gorse_hip_test_set_scan_block(int64_t queries) { g_scan_block = queries > 0 ? queries : 0; }
+
+// test hook: the scan_literal flags of the last scan block of the handle's last call (1 = select_fast_kernel left the query to the
+// literal kernel or to the reroute); all 1 when the literal-only switch was on
+extern "C" int32_t gorse_hip_test_topk_scan_flags(gorse_topk *h, int32_t *flags, int64_t n) {
+    if (!h || !flags || n < 0) return fail(GORSE_ERR_INVALID, "NULL argument");
+    if (h->scan_last_nq <= 0) return fail(GORSE_ERR_INVALID, "the handle's last call did not scan");
+    if (n > h->scan_last_nq) return fail(GORSE_ERR_INVALID, "the last scan block had %lld queries", (long long)h->scan_last_nq);
+    if (h->scan_last_literal_only) {
+        std::fill(flags, flags + n, 1);
+    } else if (h->scan_flags_on_host) {
+        std::copy(h->scan_flags_host.begin(), h->scan_flags_host.begin() + n, flags);
+    } else {
+        GORSE_TRY(h->use());
+        GORSE_HIP_CHECK(hipMemcpyAsync(flags, h->scan_literal.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+        GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+    return GORSE_OK;
+}

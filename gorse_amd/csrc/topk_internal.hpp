@@ -80,6 +80,12 @@ struct gorse_topk {
     int64_t tri_packed_counts = 0, tri_packed_entries = 0;
     std::vector<uint8_t> dbg_flags;   // probe (variant bit 24): the pilot's flags and list lengths of the last chunk
     std::vector<int32_t> dbg_counts;
+    // test hook (gorse_hip_test_topk_scan_flags): the last block of the last call's scan -- its queries (0: the call did not scan),
+    // whether the literal-only switch was on, and, where the host read the flags for the reroute (whose replay may scan again
+    // and overwrite scan_literal), the flags as it read them
+    int64_t scan_last_nq = 0;
+    bool scan_last_literal_only = false, scan_flags_on_host = false;
+    std::vector<int32_t> scan_flags_host;
     int32_t use() const {
         hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) return gorse::fail(GORSE_ERR_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
@@ -89,22 +95,40 @@ struct gorse_topk {
 
 namespace gorse {
 constexpr int64_t kTopkRowPad = 256;  // NaN entries behind the last row value: one tile of the sweep reaches at most 127 rows past N
+// A NaN operand of a subtraction: the reference's vsubps / subss return it as it is (the first operand's when both are NaN);
+// v_sub_f32 computes a + (-b) and hands back a NaN b with its sign flipped (measured on an MI355X: 1.0f - NaN(7fc00000) =
+// ffc00000; sqrtf, products and quotients keep the sign).  NAN_SUB = true restores the operand.  The distance functions below run
+// their plain form and, only when the result is a NaN, once more in this form: a finite pair pays one comparison.
+template <bool NAN_SUB>
+__device__ __forceinline__ float ref_sub(float a, float b) {
+    const float v = a - b;
+    if (NAN_SUB && v != v) return a != a ? a : (b != b ? b : v);
+    return v;
+}
+// 1 - ab / (|q| |x|) of the cosine distance: a NaN quotient is the result
+__device__ __forceinline__ float cosine_distance(float ab, float qq, float n2) {
+    const float t = ab / (sqrtf(qq) * sqrtf(n2));
+    const float r = 1.0f - t;
+    return t != t ? t : r;
+}
+
 // floats.Euclidean (squared part) in AVX512 order for rows staged in LDS: floats_avx512.c:374-441
+template <bool NAN_SUB = false>
 __device__ __forceinline__ float euclid512_lds(const float *a, const float *b, const VecShape &vs, int lane) {
     float acc = 0.0f;
     for (int c = 0; c < vs.nfull; c++) {
-        float v = a[16 * c + lane] - b[16 * c + lane];
+        float v = ref_sub<NAN_SUB>(a[16 * c + lane], b[16 * c + lane]);
         v = v * v;
         acc = c == 0 ? v : v + acc;
     }
     float sum = group_tree16(acc);
     if (vs.has8) {
         int e = vs.nfull * 16 + (lane & 7);
-        float v = a[e] - b[e];
+        float v = ref_sub<NAN_SUB>(a[e], b[e]);
         sum += group_tree8(v * v);
     }
     for (int e = vs.tail0; e < vs.d; e++) {
-        float v = a[e] - b[e];
+        float v = ref_sub<NAN_SUB>(a[e], b[e]);
         sum = fmaf(v, v, sum);
     }
     return sqrtf(sum);
@@ -114,11 +138,12 @@ __device__ __forceinline__ float euclid512_lds(const float *a, const float *b, c
 // shipped in bfloats_avx512.s, restated by the oracle's orc_bf16_euclidean): rows are the bf16 values expanded by << 16;
 // sixteen partial sums with UNFUSED multiply + add, the partials added SEQUENTIALLY (a vaddss chain, not the shuffle tree of
 // floats.Euclidean), the n % 16 tail one element at a time with a fused multiply-add.
+template <bool NAN_SUB = false>
 __device__ __forceinline__ float euclid_bf16_lds(const float *a, const float *b, int d, int lane) {
     const int nfull = d / 16;
     float acc = 0.0f;
     for (int c = 0; c < nfull; c++) {
-        const float v = a[16 * c + lane] - b[16 * c + lane];
+        const float v = ref_sub<NAN_SUB>(a[16 * c + lane], b[16 * c + lane]);
         acc = acc + v * v;  // -ffp-contract=off: two roundings, as vmulps + vaddps
     }
     float sum = 0.0f;
@@ -126,7 +151,7 @@ __device__ __forceinline__ float euclid_bf16_lds(const float *a, const float *b,
 #pragma unroll
     for (int l = 0; l < 16; l++) sum = sum + __shfl(acc, (base & 63) + l, 64);
     for (int e = 16 * nfull; e < d; e++) {
-        const float v = a[e] - b[e];
+        const float v = ref_sub<NAN_SUB>(a[e], b[e]);
         sum = fmaf(v, v, sum);
     }
     return sqrtf(sum);
@@ -134,7 +159,9 @@ __device__ __forceinline__ float euclid_bf16_lds(const float *a, const float *b,
 // the distance of `metric` (GORSE_METRIC_EUCLIDEAN or the kernels' own id 3 = bfloats order) for rows staged in LDS
 constexpr int kMetricEuclidBf16 = 3;
 __device__ __forceinline__ float euclid_any_lds(int metric, const float *a, const float *b, const VecShape &vs, int lane) {
-    return metric == kMetricEuclidBf16 ? euclid_bf16_lds(a, b, vs.d, lane) : euclid512_lds(a, b, vs, lane);
+    const float r = metric == kMetricEuclidBf16 ? euclid_bf16_lds(a, b, vs.d, lane) : euclid512_lds(a, b, vs, lane);
+    if (r == r) return r;  // every lane of the 16-lane group holds the same total: the group takes the second run together
+    return metric == kMetricEuclidBf16 ? euclid_bf16_lds<true>(a, b, vs.d, lane) : euclid512_lds<true>(a, b, vs, lane);
 }
 
 // topk.hip

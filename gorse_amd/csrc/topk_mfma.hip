@@ -1158,7 +1158,7 @@ __global__ __launch_bounds__(kBlock) void topk_rescore_kernel(RescoreParams p) {
                 if (p.metric == GORSE_METRIC_NEG_DOT)
                     r[u] = -ab;
                 else
-                    r[u] = 1.0f - ab / (sqrtf(qq) * sqrtf(p.norm2[i]));
+                    r[u] = cosine_distance(ab, qq, p.norm2[i]);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -1374,7 +1374,7 @@ __global__ __launch_bounds__(kBlock) void topk_tie_sort_kernel(ReplayParams p) {
             if (p.metric == GORSE_METRIC_NEG_DOT)
                 r = -ab;
             else
-                r = 1.0f - ab / (sqrtf(qq) * sqrtf(p.norm2[i]));
+                r = cosine_distance(ab, qq, p.norm2[i]);
         }
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) {

@@ -76,6 +76,14 @@ int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out16 /*host*/
 /* 1 = every query of the literal scan (path A) goes through the one-thread-per-query heap kernel; 0 (default) = the queries whose
  * k + 1 smallest distances are pairwise distinct are answered by select_fast_kernel (same results). */
 void gorse_hip_test_set_scan_literal(int32_t on);
+/* the scan_literal flags of the LAST scan block of the handle's last call (the first n queries of that block): 1 = select_fast_kernel
+ * left the query to the literal kernel or to the reroute through the MFMA path's tie replay (ties among its k + 1 smallest
+ * distances, a NaN, k + 1 > 1024, more than 2048 rows at the bound), 0 = it answered; all 1 when gorse_hip_test_set_scan_literal
+ * was on.  GORSE_ERR_INVALID when that call did not scan or n exceeds the block's queries. */
+int32_t gorse_hip_test_topk_scan_flags(gorse_topk *h, int32_t *flags /*host*/, int64_t n);
+/* queries per block of the scan: > 0 replaces min(2^28 / N, 65535) (still at most 65535), 0 restores the rule.  Lets small inputs
+ * run the block loop of the three calls.  Results never depend on it. */
+void gorse_hip_test_set_scan_block(int64_t queries);
 /* sparse top-k (csrc/sparse*.h*).  Results never depend on any of these.
  * slots: at most this many single-wave workgroups per launch of sparse_tile_kernel (0 = the library's 16 per CU). */
 void gorse_hip_test_set_sparse_slots(int64_t max_slots);
