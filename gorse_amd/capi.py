@@ -22,6 +22,17 @@ COMM_ID_BYTES = 128
 MF_EVAL_MAX_TOPK = 128  # GORSE_MF_EVAL_MAX_TOPK
 OPT_SGD, OPT_ADAM = 0, 1
 PROF_TOPK_SCORE, PROF_TOPK_RESCORE, PROF_TOPK_SWEEP, PROF_TOPK_SELECT, PROF_TOPK_HIST, PROF_TOPK_REPLAY = 0, 1, 2, 3, 4, 5
+# gorse_hip_test_set_topk_variant (include/gorse_hip_test.h, GORSE_TEST_TOPK_*)
+TOPK_TILE64, TOPK_COARSE_OFF, TOPK_COARSE_ON, TOPK_REPLAY_COUNTERS = 1 << 0, 1 << 2, 1 << 3, 1 << 4
+TOPK_WARM_OFF, TOPK_WARM_ALWAYS, TOPK_PILOT_KTH2, TOPK_COLD_SLICES = 1 << 8, 1 << 9, 1 << 10, 1 << 11
+TOPK_SLICES8, TOPK_SLICE1, TOPK_SYM_OFF, TOPK_REPLAY_WAVE64 = 1 << 14, 1 << 15, 1 << 23, 1 << 28
+TOPK_VARIANT_MASK = (TOPK_TILE64 | TOPK_COARSE_OFF | TOPK_COARSE_ON | TOPK_REPLAY_COUNTERS | TOPK_WARM_OFF | TOPK_WARM_ALWAYS | TOPK_PILOT_KTH2 |
+                     TOPK_COLD_SLICES | TOPK_SLICES8 | TOPK_SLICE1 | TOPK_SYM_OFF | TOPK_REPLAY_WAVE64 | (3 << 29))
+
+
+def TOPK_TRI_SLICES(n):
+    """GORSE_TEST_TOPK_TRI_SLICES(n): n = 1 / 2 / 3 -> one / two / four row slices per query block of a triangle-sharded sweep"""
+    return (n & 3) << 29
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -147,13 +158,10 @@ SIGNATURES = {
     "gorse_hip_test_topk_last_symmetric": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "gorse_hip_test_topk_sym_stats": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
     "gorse_hip_test_topk_get_thresholds": (C.c_int32, [_vp, _f32p, C.c_int64]),
-    "gorse_hip_test_topk_get_pilot_state": (C.c_int32, [_vp, C.POINTER(C.c_uint8), _i32p, C.c_int64]),
     "gorse_hip_test_topk_get_flags": (C.c_int32, [_vp, C.POINTER(C.c_uint8), C.c_int64]),
     "gorse_hip_test_topk_get_foreign_counts": (C.c_int32, [_vp, _i32p, C.c_int64]),
     "gorse_hip_test_set_sparse_slots": (None, [C.c_int64]),
     "gorse_hip_test_set_sparse_head": (None, [C.c_int32]),
-    "gorse_hip_test_set_sparse_table": (None, [C.c_int32]),
-    "gorse_hip_test_set_sparse_probe": (None, [C.c_int32]),
     "gorse_hip_test_set_sparse_sym": (None, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gorse_hip_test_set_sparse_front": (None, [C.c_int32]),
     "gorse_hip_test_sparse_sym_stats": (None, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -859,11 +867,6 @@ class TopK:
         check(lib().gorse_hip_test_topk_resweeps(self.h, C.byref(n)))
         return n.value
 
-    def pilot_state(self, n):
-        f, c = np.empty(n, np.uint8), np.empty(n, np.int32)
-        check(lib().gorse_hip_test_topk_get_pilot_state(self.h, f.ctypes.data_as(C.POINTER(C.c_uint8)), c.ctypes.data_as(_i32p), n))
-        return f, c
-
     def warm_thresholds(self, n):
         out = np.empty(n, np.float32)
         check(lib().gorse_hip_test_topk_get_thresholds(self.h, out.ctypes.data_as(_f32p), n))
@@ -1023,72 +1026,6 @@ class Sparse:
             self.h = None
 
     __del__ = close
-
-    # ---- the triangle-sharded all-pairs search (include/gorse_hip.h, gorse_topk_tri_*): host-memory forms of the messages ----
-    def tri_begin(self, k, rank, world, q_begin=0, q_end=None):
-        q_end = self.N if q_end is None else q_end
-        self._tri = (k, q_end - q_begin)
-        check(lib().gorse_topk_tri_begin(self.h, q_begin, q_end, k, rank, world))
-
-    def tri_slice(self, rank):
-        """(lo, hi, owned): the queries whose pilots `rank` runs, and how many queries it owns"""
-        lo, hi, ow = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(lib().gorse_topk_tri_slice(self.h, rank, C.byref(lo), C.byref(hi), C.byref(ow)))
-        return lo.value, hi.value, ow.value
-
-    def tri_thresholds_get(self, lo, hi):
-        out = np.empty(hi - lo, np.float32)
-        check(lib().gorse_topk_tri_thresholds_get(self.h, lo, hi, out.ctypes.data_as(_vp)))
-        return out
-
-    def tri_thresholds_put(self, lo, hi, thr):
-        thr = _arr(thr, np.float32)
-        assert thr.size == hi - lo
-        check(lib().gorse_topk_tri_thresholds_put(self.h, lo, hi, thr.ctypes.data_as(_vp)))
-
-    def tri_sweep(self):
-        check(lib().gorse_topk_tri_sweep(self.h))
-
-    def tri_pack_device(self, dest):
-        """builds the message for `dest` in the handle's device buffers; returns (number of counts, number of entries)"""
-        nc, ne = C.c_int64(0), C.c_int64(0)
-        check(lib().gorse_topk_tri_pack(self.h, dest, C.byref(nc), C.byref(ne)))
-        return nc.value, ne.value
-
-    def tri_pack_fetch(self, nc, ne):
-        counts, entries = np.empty(nc, np.int32), np.empty(ne, np.uint64)
-        check(lib().gorse_topk_tri_pack_read(self.h, counts.ctypes.data_as(_vp), entries.ctypes.data_as(_vp)))
-        return counts, entries
-
-    def tri_pack(self, dest):
-        """the message for `dest`: (counts int32 per query dest owns, entries uint64 = (key, row) pairs end to end)"""
-        return self.tri_pack_fetch(*self.tri_pack_device(dest))
-
-    def tri_unpack(self, src, counts, entries):
-        counts, entries = _arr(counts, np.int32), _arr(entries, np.uint64)
-        check(lib().gorse_topk_tri_unpack(self.h, src, counts.ctypes.data_as(_vp), counts.size, entries.ctypes.data_as(_vp), entries.size))
-
-    # device-pointer forms (the messages stay on the GPU: torch tensors' data_ptr(); gorse_amd.dist.HipTriEngine(device="cuda"))
-    def tri_thresholds_get_ptr(self, lo, hi, ptr):
-        check(lib().gorse_topk_tri_thresholds_get(self.h, lo, hi, _vp(ptr)))
-
-    def tri_thresholds_put_ptr(self, lo, hi, ptr):
-        check(lib().gorse_topk_tri_thresholds_put(self.h, lo, hi, _vp(ptr)))
-
-    def tri_pack_read_ptr(self, counts_ptr, entries_ptr):
-        check(lib().gorse_topk_tri_pack_read(self.h, _vp(counts_ptr), _vp(entries_ptr)))
-
-    def tri_unpack_ptr(self, src, counts_ptr, n_counts, entries_ptr, n_entries):
-        check(lib().gorse_topk_tri_unpack(self.h, src, _vp(counts_ptr), n_counts, _vp(entries_ptr), n_entries))
-
-    def tri_finish(self, idx=None, dist=None, fetch=True):
-        """rescoring + tie path of the queries this rank owns; with fetch their rows are written into idx / dist (nq x k, allocated
-        here when not given: the rows of other ranks' queries are then -1 / +inf)"""
-        k, nq = self._tri
-        if fetch and idx is None:
-            idx, dist = np.full((nq, k), -1, np.int32), np.full((nq, k), np.inf, np.float32)
-        check(lib().gorse_topk_tri_finish(self.h, _p(idx, _i32p) if fetch else None, _p(dist, _f32p) if fetch else None))
-        return idx, dist
 
     def set_mask(self, admissible=None):
         m = None if admissible is None else _arr(admissible, np.uint8)

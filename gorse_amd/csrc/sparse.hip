@@ -81,11 +81,8 @@ int64_t g_sparse_max_slots = 0;  // workgroups per launch (0 = 16 per CU)
 int g_sparse_sym = -1;            // an eligible all-pairs pass walks its whole-query pairs once (SymArgs): -1 / 1 = yes, 0 = never,
                                   // 2 = yes, but the front (the long rows in a group of their own) does not deliver
 int g_sparse_sym_caps[3] = {0, 0, 0};  // foreign list capacities of the three tiers (0 = the defaults): tests overflow them on purpose
-int64_t g_sparse_rows_wgs = 1024;  // most workgroups of sparse_rows_kernel (probe: bits 8.. of gorse_hip_test_set_sparse_probe x 256)
 int g_sparse_front = 1;           // handles created afterwards give their longest rows a row group of their own (RowOrder): 0 = no, 1 = the rows
                                   // longer than 1 .. 2 x the split threshold (gorse_sparse_create), > 1 = the rows longer than this
-int g_sparse_tri_probe = 0;      // timing probe: whole-query items stop at their own group (gorse_hip_test_set_sparse_probe)
-int g_sparse_cap_shift = 2;      // postings a super-visit's table takes: accumulators >> this (gorse_hip_test_set_sparse_table)
 int g_sparse_head = -1;          // groups a whole-query item visits one by one (the rest in hashed super-visits); -1 = head_groups_of()
 
 // The head: the leading groups (rows come longest first, so the groups' shares of the stored entries fall) that hold more than
@@ -258,8 +255,6 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
     }
     a.off = h->off.p, a.post = h->post.p, a.ngroups = h->ngroups, a.logG = h->logG, a.part_stride = (int32_t)ng;
     a.head_groups = head_groups_of(h);
-    a.cap_shift = g_sparse_cap_shift;
-    a.tri_probe = g_sparse_tri_probe;
     a.N = h->N, a.Np = h->Np;
     a.orig_of = h->orig_of.p, a.new_of = h->new_of.p;
     a.q_ptr = qp, a.q_cid = qc, a.q_val = qv, a.q_first = q_first;
@@ -382,8 +377,9 @@ int32_t run_queries(gorse_sparse *h, const int64_t *qp, const int32_t *qc, const
             r.part_keys = h->part_keys.p, r.part_cnt = h->part_cnt.p, r.stat = h->stat.p;
             r.fm = sym && a.sym.front ? a.sym.fm : nullptr, r.Ns = a.sym.Ns, r.first = a.sym.first, r.new_of = h->new_of.p;
             // at most four of its waves per CU: the kernel is bound by its longest row, not by throughput, and at 170 VGPRs a full
-            // grid of it would take the register files from the list walk it runs next to
-            const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)nh * h->n_ranges, std::min<int64_t>(slots, g_sparse_rows_wgs)));
+            // grid of it would take the register files from the list walk it runs next to (1024 workgroups; 2048 and 4096
+            // gain nothing at the heavy threshold in force: 21.99 / 22.12 ms against 22.0, profiles/r06_zr_probe_gpu_probe_sparse_knobs.txt)
+            const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)nh * h->n_ranges, std::min<int64_t>(slots, 1024)));
             switch (kp) {
                 case 128: sparse::sparse_rows_kernel<128><<<dim3(rgrid), dim3(sparse::kBlock), 0, h->stream2>>>(r); break;
                 case 256: sparse::sparse_rows_kernel<256><<<dim3(rgrid), dim3(sparse::kBlock), 0, h->stream2>>>(r); break;
@@ -755,10 +751,6 @@ extern "C" int32_t gorse_sparse_last_stats(gorse_sparse *h, int64_t *postings, i
 
 extern "C" void gorse_hip_test_set_sparse_slots(int64_t max_slots) { g_sparse_max_slots = max_slots; }
 extern "C" void gorse_hip_test_set_sparse_head(int32_t groups) { g_sparse_head = groups; }
-extern "C" void gorse_hip_test_set_sparse_probe(int32_t probe) {
-    g_sparse_tri_probe = probe & 0xff;
-    g_sparse_rows_wgs = (probe >> 8) > 0 ? (int64_t)(probe >> 8) * 256 : 1024;
-}
 extern "C" void gorse_hip_test_set_sparse_front(int32_t front) { g_sparse_front = front; }
 extern "C" void gorse_hip_test_set_sparse_sym(int32_t mode, int32_t c1, int32_t c2, int32_t c3) {
     g_sparse_sym = mode;
@@ -771,7 +763,6 @@ extern "C" void gorse_hip_test_sparse_path_stats(const gorse_sparse *h, int64_t 
     out[0] = h ? h->last_path[0] : 0, out[1] = h ? h->last_path[1] : 0;
     out[2] = h ? h->n_ranges : 0, out[3] = h ? h->Dc * h->ngroups : 0;
 }
-extern "C" void gorse_hip_test_set_sparse_table(int32_t cap_shift) { g_sparse_cap_shift = cap_shift >= 2 && cap_shift <= 6 ? cap_shift : 2; }
 extern "C" void gorse_hip_test_set_sparse_tile(int32_t rows) { g_sparse_tile = rows; }
 extern "C" void gorse_hip_test_set_sparse_split(int64_t entries) { g_sparse_split = entries; }
 extern "C" void gorse_hip_test_set_sparse_heavy(int64_t entries) { g_sparse_heavy = entries; }

@@ -161,9 +161,6 @@ struct TileArgs {
     const uint32_t *off;
     const Posting *post;
     int32_t ngroups, logG;
-    int32_t tri_probe;    // timing probe (results are garbage): a whole-query item visits only the groups up to its own row's -- what a
-                          // symmetric walk of the whole-query items would leave of the list walk (gorse_hip_test_set_sparse_probe)
-    int32_t cap_shift;    // the hashed table of a super-visit takes at most (accumulators >> cap_shift) postings (2: half full at most)
     int32_t head_groups;  // a whole-query item visits the groups [0, head_groups) one by one with directly indexed accumulators and
                           // the rest in SUPER-VISITS of several groups with hashed accumulators (see sparse_tile_kernel); = ngroups: never
     int32_t part_stride;  // partial rankings per block of part_keys / part_cnt
@@ -716,10 +713,10 @@ __global__ __launch_bounds__(kBlock) void sparse_tile_kernel(TileArgs a) {
         const uint32_t *off = a.off;
         const Posting *post = a.post;
         const int dir_stride = a.ngroups;
-        // SYM: a whole-query item takes the rows in front of its own (and the timing probe stops there too)
+        // SYM: a whole-query item takes the rows in front of its own
         const bool symw = SYM && whole;
-        const int32_t sid_q = SYM || (whole && a.tri_probe && qr < a.N) ? a.new_of[qr] : 0;
-        const int glim = symw || (whole && a.tri_probe && qr < a.N) ? (sid_q >> a.logG) + 1 : a.ngroups;
+        const int32_t sid_q = SYM ? a.new_of[qr] : 0;
+        const int glim = symw ? (sid_q >> a.logG) + 1 : a.ngroups;
         const int gfirst = FRONT && symw ? 1 : 0;  // SYM with a front: group 0 is the front's, which delivers (SymArgs)
         uint32_t pub = 0;  // SYM: the bound this item has published for its row
         // (a part of a front row: where its scores go, indexed by the other row's scratch id)
@@ -975,7 +972,9 @@ __global__ __launch_bounds__(kBlock) void sparse_tile_kernel(TileArgs a) {
         // software pipeline as the head groups: index / value pairs two visits ahead, directory entries one visit ahead.
         if (whole && ghead < glim) {
             const int S = nacc >> 1;
-            const uint32_t cap_t = (uint32_t)(nacc >> a.cap_shift);
+            // the table of S slots takes at most half as many postings (a quarter / an eighth full instead of half: 49.0 / 50.6 ms against
+            // 48.2, profiles/r04_zc_probe_sparse_table.txt)
+            const uint32_t cap_t = (uint32_t)(nacc >> 2);
             lds_key *hkey = reinterpret_cast<lds_key *>(acc);
             float *hval = acc + S;
             for (int g0 = ghead; g0 < glim; g0 += kBlock - 1) {

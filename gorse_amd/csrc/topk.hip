@@ -649,22 +649,14 @@ extern "C" int32_t gorse_hip_test_topk_get_foreign_counts(gorse_topk *h, int32_t
     return GORSE_OK;
 }
 
-// probe (variant bit 24): the pilot's per-query flags and list lengths
-extern "C" int32_t gorse_hip_test_topk_get_pilot_state(gorse_topk *h, uint8_t *flags, int32_t *counts, int64_t n) {
-    if (!h || !flags || !counts) return fail(GORSE_ERR_INVALID, "NULL argument");
-    if ((int64_t)h->dbg_flags.size() < n) return fail(GORSE_ERR_INVALID, "no pilot-only search of that size has run on this handle");
-    memcpy(flags, h->dbg_flags.data(), (size_t)n);
-    memcpy(counts, h->dbg_counts.data(), (size_t)n * 4);
-    return GORSE_OK;
-}
-
 // test hook: 0 = automatic path choice, 1 = path A only (literal scan), 2 = path B whenever its operands exist
 extern "C" void gorse_hip_test_set_topk_path(int32_t path) { gorse::g_topk_force_path = path; }
-extern "C" void gorse_hip_test_set_topk_variant(int32_t v) { gorse::g_topk_variant = v; }
-// probe: the counters of the last tie replay that ran with variant bit 4 on this handle
+// test hook: the GORSE_TEST_TOPK_* switches of the MFMA path (include/gorse_hip_test.h); any other bit is ignored
+extern "C" void gorse_hip_test_set_topk_variant(int32_t v) { gorse::g_topk_variant = v & GORSE_TEST_TOPK_MASK; }
+// probe: the counters of the last tie replay that ran with GORSE_TEST_TOPK_REPLAY_COUNTERS on this handle
 extern "C" int32_t gorse_hip_test_get_sweep_profile(gorse_topk *h, uint64_t *out16) {
     if (!h || !out16) return fail(GORSE_ERR_INVALID, "NULL argument");
-    if (h->sweep_prof.n < 16) return fail(GORSE_ERR_INVALID, "no search with variant bit 4 has run on this handle");
+    if (h->sweep_prof.n < 16) return fail(GORSE_ERR_INVALID, "no search with GORSE_TEST_TOPK_REPLAY_COUNTERS has run on this handle");
     GORSE_TRY(h->use());
     GORSE_HIP_CHECK(hipMemcpyAsync(out16, h->sweep_prof.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));

@@ -52,7 +52,7 @@ struct gorse_topk {
     gorse::DevBuf<uint8_t> rp_flag;
     gorse::DevBuf<int32_t> rp_sidx, rp_scount;
     gorse::DevBuf<float> rp_sdst;
-    gorse::DevBuf<unsigned long long> sweep_prof;  // probe: counters of the tie replay (variant bit 4, gorse_hip_test_get_sweep_profile)
+    gorse::DevBuf<unsigned long long> sweep_prof;  // counters of the tie replay (GORSE_TEST_TOPK_REPLAY_COUNTERS, gorse_hip_test_get_sweep_profile)
     gorse::KernelProfile prof{GORSE_PROF_TOPK_NCLASSES};
     // gorse_topk_set_mask: rows with mask == 0 take no part in any search (as if they had never been added)
     gorse::DevBuf<uint8_t> mask;
@@ -78,8 +78,6 @@ struct gorse_topk {
     gorse::DevBuf<long long> tri_offsets;
     gorse::DevBuf<uint2> tri_entries, tri_in_entries;
     int64_t tri_packed_counts = 0, tri_packed_entries = 0;
-    std::vector<uint8_t> dbg_flags;   // probe (variant bit 24): the pilot's flags and list lengths of the last chunk
-    std::vector<int32_t> dbg_counts;
     // test hook (gorse_hip_test_topk_scan_flags): the last block of the last call's scan -- its queries (0: the call did not scan),
     // whether the literal-only switch was on, and, where the host read the flags for the reroute (whose replay may scan again
     // and overwrite scan_literal), the flags as it read them
@@ -181,6 +179,6 @@ int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_conti
                          int64_t nq, int k, int prune0, int32_t *idx_out, float *dist_out, int32_t *cnt_out);
 bool topk_mfma_usable(const gorse_topk *h, int64_t nq, int k);
 void topk_mfma_release(gorse_topk *h);  // at destroy: the search state
-extern int g_topk_variant;     // probe switches of the sweep (tile rows, coarse scale test)
+extern int g_topk_variant;     // OR of the GORSE_TEST_TOPK_* switches (include/gorse_hip_test.h): every read names one; 0 in the product
 extern int g_topk_force_path;  // 0 auto, 1 path A only, 2 path B whenever it is usable, 3 = 2 without the tie replay
 }  // namespace gorse

@@ -28,7 +28,7 @@ using namespace gorse;
 
 namespace gorse {
 int g_topk_force_path = 0;
-int g_topk_variant = 0;  // probe switches: bit 0 = 64-row tiles, bit 1 = 128-row tiles, bit 2 / 3 = coarse scale test off / on
+int g_topk_variant = 0;  // OR of the GORSE_TEST_TOPK_* switches (include/gorse_hip_test.h)
 }
 
 namespace {
@@ -85,7 +85,13 @@ constexpr int64_t kMinSweepQueries = 768;  // fewer queries in a call take the s
 constexpr int kCap = 512;      // candidate-list capacity per query
 constexpr int kCapF = 512;     // SYM: capacity of a query's FOREIGN list (candidates other workgroups found for it)
 constexpr int kEPL = kCap / 64;
-constexpr int kCompactAt = kCap - 64;   // compact a list once it holds more than this (a block adds <= 32)
+constexpr int kCompactAt = kCap - 64;   // a list must be compacted once it holds more than this (a block adds <= 32)
+// The sweep compacts a list (threshold raised to its K-th best) as soon as one of its two sub-lists holds more than kCompactSubAt:
+// 4.7 ms of the C4 pass less than at kCompactAt / 2 = 224 (fewer rows accepted late in the sweep), 96 no better
+// (profiles/r03_p_probe_c4_floor.txt)
+constexpr int kCompactSubAt = 128;
+static_assert(kCompactSubAt <= kCompactAt / 2, "a sub-list holds half of the list");
+constexpr int kPilotStride = 16;        // the warm start's pilot sweeps every 16th row tile (chunk_prepare)
 constexpr int kOverflowAt = kCap - 128; // a compaction that keeps more than this cannot make progress
 constexpr int kMaxKth = 256;
 constexpr int kHistCap = 4096;          // history entries per query of the tie-replay sweep (see ReplayParams)
@@ -101,8 +107,8 @@ __device__ __forceinline__ int lane_rank(uint64_t m) {  // set bits of m below t
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
 }
 
-constexpr int kDefaultRowsPerTile = 128;  // one barrier per four MFMA row blocks: 8 % faster than 64 at C4 (profiles/r02_d_probe_topk_warm.txt)
-inline int topk_rows_per_tile() { return (g_topk_variant & 1) ? 64 : ((g_topk_variant & 2) ? 128 : kDefaultRowsPerTile); }
+// 128: one barrier per four MFMA row blocks, 8 % faster than 64 at C4 (profiles/r02_d_probe_topk_warm.txt)
+inline int topk_rows_per_tile() { return (g_topk_variant & GORSE_TEST_TOPK_TILE64) ? 64 : 128; }
 
 struct SweepParams {
     const uint16_t *A;     // candidate operands, N x KPAD bf16
@@ -116,9 +122,9 @@ struct SweepParams {
     int32_t *hcnt;         // HIST sweeps: nq
     int64_t N, nq;
     int kth;
-    int compact_at;        // a sub-list longer than this triggers the compaction of its query (<= kCompactAt / 2)
+    int compact_at;        // a sub-list longer than this triggers the compaction of its query: kCompactSubAt
     int ep;                // EP_SCALE / EP_BIAS / EP_COARSE: what the epilogue does with the per-row values (host side: picks the kernel)
-    unsigned long long *prof;  // host side only: the handle's counters when variant bit 4 asks the tie replay to count (ReplayParams::prof);
+    unsigned long long *prof;  // host side only: the handle's counters when GORSE_TEST_TOPK_REPLAY_COUNTERS asks the tie replay to count (ReplayParams::prof);
                                // the main sweep then keeps its square form.  No sweep reads it.
     // warm start (see topk_mfma_search): a PILOT sweep walks every tile_stride-th tile with kth = a small j and writes the
     // threshold it ends with to f_out; the main sweep starts from f0 and verifies it (compact_query: a threshold that a later
@@ -126,8 +132,6 @@ struct SweepParams {
     const float *f0;   // nq initial thresholds or null (-inf)
     float *f_out;      // pilot: nq final thresholds; null otherwise
     int tile_stride;   // 1, or the pilot's sampling stride over the row tiles
-    int probe;         // timing probes of the MAIN sweep (results are garbage): 1 = every threshold +inf (no block ever qualifies: the
-                       // sweep's floor), 2 = a qualifying block does nothing, 3 = it tests and counts its candidates without storing them
     int nslices;       // HIST: row slices (grid.y); the per-query outputs are then nslices x nq long, slice-major
     const float *fwarm;  // HIST: nslices x nq starting thresholds of the slices (tie_warm_kernel: each a valid lower bound of the K-th
                          // best score among the rows IN FRONT of the slice, so nothing the reference's heap can have accepted is
@@ -141,8 +145,6 @@ struct SweepParams {
     int32_t *fcnt;         // nq entries appended to them (may exceed kCapF: the list then overflowed)
     unsigned long long *sym_stats;  // [0] queries without a pilot threshold, [1] warm starts the rescoring could not verify, [2] foreign
                                     // lists that overflowed, [3] (query, block) hits beyond a wave's staging area
-    int sym_probe;         // timing probes of the symmetric sweep (results are garbage): 1 = no tile is read along its rows, 2 = the
-                           // block and row tests run but a hit does nothing, 3 = hits are staged but never flushed
     // SYM, triangle sharding over GPUs (gorse_topk_tri_*): this launch sweeps the query blocks C with C % sym_world == sym_rank only --
     // their own lists, and what they find for the rows of EVERY earlier block (foreign lists of queries other ranks own included);
     // 0 of 1 = the whole triangle
@@ -336,8 +338,8 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
         s_cnt[2 * t] = 0;
         s_cnt[2 * t + 1] = 0;
         s_hc[t] = 0;
-        s_f[t] = q < p.nq && p.probe != 1 ? (p.f0 ? p.f0[q] : (HIST && p.fwarm ? p.fwarm[(int64_t)blockIdx.y * p.nq + q] : -__builtin_inff()))
-                                            : __builtin_inff();
+        s_f[t] = q < p.nq ? (p.f0 ? p.f0[q] : (HIST && p.fwarm ? p.fwarm[(int64_t)blockIdx.y * p.nq + q] : -__builtin_inff()))
+                          : __builtin_inff();
         s_mg[t] = q < p.nq ? p.qmargin[q] : 0.0f;
     }
     if (tid < 2 * NBUF) s_sync[tid] = 0;
@@ -679,7 +681,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
         }
         const int64_t base_row = tile_index(t) * stride_rows;
         // SYM: a tile of an earlier query block is read along its rows too (wave-uniform)
-        const bool trans = SYM && sched.transposed(tile_index(t)) && p.sym_probe != 1;
+        const bool trans = SYM && sched.transposed(tile_index(t));
         // register staging zero-fills the rows past N; their scores are set to NaN below.  The DMA sweeps need nothing: the
         // row values of those rows are NaN
         const int valid = DMA ? kTR : (int)std::min<int64_t>(kTR, p.N - base_row);
@@ -769,7 +771,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                             qd[g] = max2f(max3f(a0 - th.x, a1 - th.y, a2 - th.z), a3 - th.w);
                         }
                         const float dm = max2f(max3f(qd[0], qd[1], qd[2]), qd[3]);
-                        if (__builtin_amdgcn_ballot_w64(dm >= 0.0f) != 0 && p.sym_probe != 2) {
+                        if (__builtin_amdgcn_ballot_w64(dm >= 0.0f) != 0) {
                             const float4 *f4 = reinterpret_cast<const float4 *>(s_fq + buf * kTR + rb * 32);
                             const uint32_t colw = (uint32_t)(w * QW + cb * 32 + (lane & 31)) << 20;  // the column inside the workgroup's block
                             uint2 *stg = s_stage + w * kStageCap;
@@ -797,12 +799,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                                     }
                                 }
                             }
-                            if (stage_n >= kStageFlushAt) {
-                                if (p.sym_probe == 3)
-                                    stage_n = 0;
-                                else
-                                    flush_stage();
-                            }
+                            if (stage_n >= kStageFlushAt) flush_stage();
                         }
                         }
                     }
@@ -866,7 +863,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                     // maximum skips NaN operands, and a quad of four NaNs holds no candidate).
 #pragma unroll
                     for (int g = 0; g < 4; g++) {
-                        if (gm[g] >= fq && p.probe != 2) {
+                        if (gm[g] >= fq) {
                             if (RAWF) {
                                 const float4 sc = rs4[RAWF ? g : 0];
                                 acc[cb][4 * g + 0] *= sc.x;
@@ -879,7 +876,7 @@ __global__ __launch_bounds__(64 * sweep_waves(HIST, KP), (sweep_waves(HIST, KP) 
                                 const int r = 4 * g + e;
                                 if (acc[cb][r] >= f) {
                                     const uint32_t row = (uint32_t)(base_row + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5));
-                                    if (p.probe != 3) mine[cb][2 * cnt[cb]] = make_uint2(fkey(acc[cb][r]), row);
+                                    mine[cb][2 * cnt[cb]] = make_uint2(fkey(acc[cb][r]), row);
                                     cnt[cb]++;
                                 }
                             }
@@ -1293,7 +1290,7 @@ struct ReplayParams {
     const int32_t *hcnt;
     const float *fslice;   // nslices x nq: the threshold every slice of the history sweep ended with (-inf: none)
     int nslices;           // cbuf / ccnt / hbuf / hcnt / cflag / fslice hold nslices x nq entries, slice-major
-    unsigned long long *prof;  // probe (variant bit 4): the replay's counters, see gorse_hip_test_get_sweep_profile; else null
+    unsigned long long *prof;  // GORSE_TEST_TOPK_REPLAY_COUNTERS: the replay's counters, see gorse_hip_test_get_sweep_profile; else null
     int64_t nq;
     uint8_t *cflag;        // in: flags of the history sweep (non-zero: undecidable); out [0, nq): 2 = undecided here
     int64_t N;
@@ -1855,11 +1852,7 @@ int32_t dispatch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym 
         case 3: return launch_sweep<3, kNcbMain>(h, p, hist);
         case 4: return launch_sweep<4, kNcbMain>(h, p, hist, sym);
         case 6: return launch_sweep<6, kNcbMain>(h, p, hist);
-        case 8:
-            // variant bit 27 (probe): the history sweep of the tie path with ONE column block per wave -- 64 queries per two-wave
-            // workgroup instead of 128: twice the workgroups, each with half the acceptances of a cold start
-            if (hist && (g_topk_variant & (1 << 27))) return launch_sweep<8, 1>(h, p, true);
-            return launch_sweep<8, kNcbMain>(h, p, hist, sym);
+        case 8: return launch_sweep<8, kNcbMain>(h, p, hist, sym);
         case 12: return launch_sweep<12, 1>(h, p, hist);  // 2 column blocks would spill
         case 16: return launch_sweep<16, 1>(h, p, hist);
         case 24: return launch_sweep<24, 1>(h, p, hist);
@@ -2140,7 +2133,7 @@ struct TopkChunkState {
     const int64_t *qid_host = nullptr;
     const float *qv_dev = nullptr;
     bool by_vector = false, contiguous = false, euclid = false, warm = false, sym = false;
-    int k = 0, kth = 0, prune0 = 0, pilot_stride = 16;
+    int k = 0, kth = 0, prune0 = 0;
     int64_t expect = 0;
     float other = 0.0f;
     const uint16_t *Bop = nullptr;
@@ -2256,15 +2249,13 @@ int32_t chunk_prepare(gorse_topk *h, ChunkState &cs) {
     sp.hcnt = nullptr;
     // epilogue: Euclidean adds its bias to every score; cosine multiplies every score by the row scale unless the scales
     // lie within 2 % of each other (then the block's largest raw score times the extreme scale bounds the block and
-    // rows are scaled only behind that test; variant bit 2 / 3: off / on whatever the norms); -dot has the value 1
+    // rows are scaled only behind that test; COARSE_OFF / COARSE_ON: off / on whatever the norms); -dot has the value 1
     // (NaN for a masked row), which the block test never needs
-    const bool cos_coarse = (g_topk_variant & 4) ? false : ((g_topk_variant & 8) ? true : h->coarse_ok);
+    const bool cos_coarse = (g_topk_variant & GORSE_TEST_TOPK_COARSE_OFF) ? false : ((g_topk_variant & GORSE_TEST_TOPK_COARSE_ON) ? true : h->coarse_ok);
     sp.ep = euclid ? EP_BIAS : (h->metric == GORSE_METRIC_COSINE ? (cos_coarse ? EP_COARSE : EP_SCALE) : EP_COARSE);
-    // a list is compacted (threshold raised to its K-th best) once a sub-list holds 128: 4.7 ms of the C4 pass less than at
-    // kCompactAt / 2 = 224 (fewer rows accepted late in the sweep; profiles/r03_p_probe_c4_floor.txt)
-    sp.compact_at = (g_topk_variant & 32) ? kCompactAt / 2 : ((g_topk_variant & 64) ? 96 : 128);
+    sp.compact_at = kCompactSubAt;
     sp.prof = nullptr;
-    if (g_topk_variant & 16) {
+    if (g_topk_variant & GORSE_TEST_TOPK_REPLAY_COUNTERS) {
         GORSE_TRY(h->sweep_prof.ensure(16));
         GORSE_HIP_CHECK(hipMemsetAsync(h->sweep_prof.p, 0, 16 * sizeof(unsigned long long), h->stream));
         sp.prof = h->sweep_prof.p;
@@ -2274,7 +2265,6 @@ int32_t chunk_prepare(gorse_topk *h, ChunkState &cs) {
     sp.kth = kth;
     sp.f0 = nullptr, sp.f_out = nullptr, sp.tile_stride = 1;
     sp.nslices = 1;
-    sp.probe = (g_topk_variant >> 17) & 3;  // variant bits 17-18: timing probes of the main sweep (the call then returns garbage)
     // bounds of the per-row value for the DMA sweeps' block test: the cosine scales; without them (a masked -dot index:
     // the value is 1 or NaN) the bound is the score itself
     sp.rs_min = h->metric == GORSE_METRIC_COSINE ? h->rs_min : 1.0f;
@@ -2286,18 +2276,17 @@ int32_t chunk_prepare(gorse_topk *h, ChunkState &cs) {
     sp.sym_stats = nullptr;
     sp.sym_rank = 0, sp.sym_world = 1, sp.sym_slices = 1;
     sp.fwarm = nullptr;
-    sp.sym_probe = (g_topk_variant >> 25) & 3;  // variant bits 25-26: timing probes of the symmetric sweep (the call returns garbage)
     // Warm start.  A streaming threshold that begins at -inf accepts ~kth * ln(N / kth) * (its lag) rows per query (1800
     // at C4) and every accepted row costs its 32 x 32 block the slow epilogue.  A pilot sweep over every 16th row tile
     // with kth_pilot = j yields the j-th best score of a 1/16 sample: with X ~ Binomial(kth - 1, 1/16) sample members
     // among the true kth - 1 best, that score is below the kth best of ALL rows unless X >= j -- j is chosen for a
     // tail of ~1e-3 -- and about 16 j rows lie above it.  The main sweep starts there and VERIFIES it (compact_query
     // flags a query whose K-th-best bound does not reach its threshold); those few queries join the tie queries' stage.
-    // (probe: variant bit 20 = every 8th row tile, bit 21 = every 32nd, bit 22 = without the 1/256 pilot in front)
-    cs.pilot_stride = (g_topk_variant & (1 << 20)) ? 8 : ((g_topk_variant & (1 << 21)) ? 32 : 16);
-    // probe / test switches: bit 8 = no warm start, bit 9 = warm start whatever N, bit 10 = a pilot kth of 2 (thresholds
+    // (Every 8th and every 32nd tile, and the 1/16 pilot without the 1/256 one in front, were measured at C4 and lost by
+    // 6 to 28 ms of the 224 ms pass: profiles/r06_a_probe_gpu_probe_topk_c4_pilot.txt.)
+    // Test switches: WARM_OFF = no warm start, WARM_ALWAYS = warm start whatever N, PILOT_KTH2 = a pilot kth of 2 (thresholds
     // far too high: most queries fail the verification and are swept again)
-    cs.warm = !(g_topk_variant & 256) && kth >= 8 && (h->N >= (int64_t)1 << 17 || (g_topk_variant & 512));
+    cs.warm = !(g_topk_variant & GORSE_TEST_TOPK_WARM_OFF) && kth >= 8 && (h->N >= (int64_t)1 << 17 || (g_topk_variant & GORSE_TEST_TOPK_WARM_ALWAYS));
     cs.Bop = Bop, cs.qn2 = qn2, cs.Qf = Qf;
     return GORSE_OK;
 }
@@ -2314,14 +2303,13 @@ int32_t chunk_pilots(gorse_topk *h, ChunkState &cs, int64_t lo, int64_t hi) {
         return (int)std::ceil(lam + 3.3 * std::sqrt(lam) + 1.5);
     };
     SweepParams p2 = slice_params(cs.sp, lo, hi - lo, h->kp * 16);
-    p2.kth = (g_topk_variant & 1024) ? 2 : pilot_kth(cs.kth, cs.pilot_stride);
-    p2.tile_stride = cs.pilot_stride;
+    p2.kth = (g_topk_variant & GORSE_TEST_TOPK_PILOT_KTH2) ? 2 : pilot_kth(cs.kth, kPilotStride);
+    p2.tile_stride = kPilotStride;
     p2.f_out = h->f0.p + lo;
-    p2.probe = 0;
-    if ((h->N >= (int64_t)1 << 18 || (g_topk_variant & 512)) && !(g_topk_variant & (1 << 22))) {
+    if (h->N >= (int64_t)1 << 18 || (g_topk_variant & GORSE_TEST_TOPK_WARM_ALWAYS)) {
         SweepParams p1 = p2;
         p1.kth = pilot_kth(p2.kth, 16);
-        p1.tile_stride = cs.pilot_stride * 16;
+        p1.tile_stride = kPilotStride * 16;
         p1.f_out = h->f1.p + lo;
         GORSE_TRY(dispatch_sweep(h, p1, false));
         GORSE_HIP_CHECK(hipMemsetAsync(h->cflag.p + lo, 0, (size_t)(hi - lo), h->stream));
@@ -2339,10 +2327,10 @@ int32_t chunk_main(gorse_topk *h, ChunkState &cs) {
     if (cs.warm) sp.f0 = h->f0.p;
     // The symmetric form (topk_sweep_kernel, SYM): the queries are a contiguous range of the stored rows that starts on a tile
     // boundary, the sweep is warm-started (a foreign workgroup cannot tighten a threshold: it needs a good one from the start)
-    // and there are at least two query blocks.  Variant bit 23 switches it off (the square sweep: tests, ablation).
+    // and there are at least two query blocks.  SYM_OFF switches it off (the square sweep: tests, ablation).
     const int64_t sym_q0 = cs.q_contig_begin + cs.c0;
-    bool sym = cs.warm && cs.contiguous && !(g_topk_variant & (1 << 23)) && sweep_sym_kp(h->kp) && topk_rows_per_tile() == 128 &&
-               sym_q0 % 128 == 0 && m >= 2 * 32 * kNcbMain * kWavesMain && sp.probe <= 1 && !sp.prof;
+    bool sym = cs.warm && cs.contiguous && !(g_topk_variant & GORSE_TEST_TOPK_SYM_OFF) && sweep_sym_kp(h->kp) && topk_rows_per_tile() == 128 &&
+               sym_q0 % 128 == 0 && m >= 2 * 32 * kNcbMain * kWavesMain && !sp.prof;
     if (cs.warm) {
         // sym_stats[0..3]: the counters of the whole search (every chunk adds to them); [4]: THIS chunk's queries without a pilot
         // threshold -- cleared per chunk, so that a chunk that was not eligible for the symmetric form leaves nothing behind for the
@@ -2476,7 +2464,7 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
             // Row slices: a history sweep serves few queries (1 % of a chunk), so its workgroups are few, and each would walk
             // all N rows on its own -- 56 ms for 10,000 queries at C4, three quarters of the tie path.  Cut into slices of
             // rows, slices x as many workgroups each walk 1 / slices of the rows; topk_tie_sort_kernel joins the slices.
-            // Variant bit 14: eight slices whatever N (lets small test inputs take the path); bit 15: one slice.
+            // SLICES8: eight slices whatever N (lets small test inputs take the path); SLICE1: one slice.
             int nsl = (int)std::min<int64_t>(kMaxSlices, std::max<int64_t>(1, h->N / 32768));
             // Few flagged queries -- a rank of a sharded search holds 1 / world of them, and the history sweep's time does not
             // shrink with their number: every workgroup (128 queries) walks its slice of the rows whatever else runs -- take more,
@@ -2490,8 +2478,8 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
                 const int64_t wgs = ceil_div(m2, (int64_t)64 * kNcbMain);
                 while (nsl >= kMaxSlices && nsl < kMaxSlicesFew && wgs * nsl < 512 && h->N / (2 * (int64_t)nsl) >= 16384) nsl *= 2;
             }
-            if (g_topk_variant & 16384) nsl = kMaxSlices;
-            if (g_topk_variant & 32768) nsl = 1;
+            if (g_topk_variant & GORSE_TEST_TOPK_SLICES8) nsl = kMaxSlices;
+            if (g_topk_variant & GORSE_TEST_TOPK_SLICE1) nsl = 1;
             const size_t sm2 = (size_t)nsl * (size_t)m2;
             GORSE_TRY(h->rp_cbuf.ensure(sm2 * kCap));
             GORSE_TRY(h->rp_hbuf.ensure(sm2 * kHistCap));
@@ -2509,8 +2497,8 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
             hp.f0 = nullptr;  // the history sweep records what a threshold that starts at -inf would have kept
             hp.fwarm = nullptr;
             // ... or, slice by slice, what a threshold that starts at a bound the main sweep's lists prove would have kept
-            // (tie_warm_kernel; variant bit 11: every slice cold, the form of rounds 2-5)
-            if (nsl > 1 && !(g_topk_variant & 2048)) {
+            // (tie_warm_kernel; COLD_SLICES: every slice cold, the form of rounds 2-5)
+            if (nsl > 1 && !(g_topk_variant & GORSE_TEST_TOPK_COLD_SLICES)) {
                 GORSE_TRY(h->rp_fwarm.ensure(sm2));
                 WarmParams wp;
                 wp.pos = pos_dev, wp.m2 = m2, wp.N = h->N, wp.nsl = nsl, wp.tile_rows = 64 /* the history sweep's tiles: launch_sweep */,
@@ -2551,7 +2539,7 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
             pp.hcnt = h->rp_hcnt.p;
             pp.fslice = h->rp_fslice.p;
             pp.nslices = nsl;
-            pp.prof = (g_topk_variant & 16) && h->sweep_prof.n >= 16 ? h->sweep_prof.p : nullptr;
+            pp.prof = (g_topk_variant & GORSE_TEST_TOPK_REPLAY_COUNTERS) && h->sweep_prof.n >= 16 ? h->sweep_prof.p : nullptr;
             if (pp.prof) GORSE_HIP_CHECK(hipMemsetAsync(pp.prof, 0, 16 * sizeof(unsigned long long), h->stream));
             pp.nq = m2;
             pp.cflag = h->rp_flag.p;
@@ -2582,8 +2570,8 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
                 // The lanes of a wave replay their queries in step: a wave takes as long as its lanes' branches laid end to end, and
                 // the launch as long as its slowest wave, however few queries there are (1,250 queries of one rank of eight: 11.9 ms,
                 // the 10,136 of a whole C4 pass: 11.5).  Fewer queries per wave while the launch has fewer waves than the chip has CUs
-                // (variant bit 28: 64 whatever the size).
-                while (qpw > 16 && !(g_topk_variant & (1 << 28)) && ceil_div(m2, (int64_t)qpw) < 256) qpw >>= 1;
+                // (REPLAY_WAVE64: 64 whatever the size).
+                while (qpw > 16 && !(g_topk_variant & GORSE_TEST_TOPK_REPLAY_WAVE64) && ceil_div(m2, (int64_t)qpw) < 256) qpw >>= 1;
                 const size_t llds = (size_t)(3 * slots + 2 * kLaneLog) * qpw * 4;
                 auto launch_lanes = [&](auto tag) -> int32_t {
                     constexpr int Q = decltype(tag)::value;
@@ -2670,23 +2658,9 @@ int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_conti
             GORSE_TRY(h->f0.ensure((size_t)cs.mb));
             GORSE_TRY(h->f1.ensure((size_t)cs.mb));
             GORSE_TRY(chunk_pilots(h, cs, 0, m));
-            if (g_topk_variant & (1 << 24)) {  // probe: stop behind the pilot, keep its flags and list lengths (results are garbage)
-                h->dbg_flags.resize((size_t)m);
-                h->dbg_counts.resize((size_t)m);
-                GORSE_HIP_CHECK(hipMemcpyAsync(h->dbg_flags.data(), h->cflag.p, (size_t)m, hipMemcpyDeviceToHost, h->stream));
-                GORSE_HIP_CHECK(hipMemcpyAsync(h->dbg_counts.data(), h->ccnt.p, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
-                GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-                h->prof.end(tok, h->stream);
-                return GORSE_OK;
-            }
         }
         GORSE_TRY(chunk_main(h, cs));
         h->last_sym = cs.sym;
-        if (cs.sp.probe || cs.sp.sym_probe) {  // timing probe: nothing behind the sweep is meaningful
-            h->prof.end(tok, h->stream);
-            GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
-            continue;
-        }
         // The queries whose warm start failed its verification carry flag 2: topk_rescore_kernel leaves flagged queries alone
         // and stage 2 of chunk_finish (history sweep from -inf + literal replay) answers them together with the tie queries -- a sweep
         // of their own would cost one workgroup a full pass over the rows (48 ms for 86 queries, profiles/r02_h_*).
@@ -2828,7 +2802,7 @@ extern "C" int32_t gorse_topk_tri_begin(gorse_topk *h, int64_t q_begin, int64_t 
     GORSE_TRY(h->use());
     // what the symmetric sweep needs (chunk_main): a warm-started MFMA search over one chunk that starts on a tile boundary
     const bool ok = topk_mfma_usable(h, nq, k) && nq <= kChunkQ && sweep_sym_kp(h->kp) && topk_rows_per_tile() == 128 && q_begin % 128 == 0 &&
-                    nq >= 2 * kSymBQ && k + 1 >= 8 && h->N >= (int64_t)1 << 17 && !(g_topk_variant & ((1 << 23) | 256));
+                    nq >= 2 * kSymBQ && k + 1 >= 8 && h->N >= (int64_t)1 << 17 && !(g_topk_variant & (GORSE_TEST_TOPK_SYM_OFF | GORSE_TEST_TOPK_WARM_OFF));
     if (!ok)
         return fail(GORSE_ERR_INVALID, "this search has no symmetric form (operand depth, a range that does not start on a 128-row boundary, fewer than "
                                        "%d queries or more than %lld, an index of fewer than 2^17 rows): shard its query rows instead", 2 * kSymBQ, (long long)kChunkQ);
@@ -2839,12 +2813,12 @@ extern "C" int32_t gorse_topk_tri_begin(gorse_topk *h, int64_t q_begin, int64_t 
     // CU: 40 ms at C4, whatever the number of ranks (a rank of eight holds 244 workgroups for 256 CUs: its main sweep took those 40 ms
     // where its share of the work is 19).  Few, long workgroups are therefore cut by ROWS: slice y of a block takes an even share of
     // its tiles, with own lists of its own (slice-major, like a history sweep's: topk_rescore_kernel takes them together); 1, 2 or 4
-    // slices, the fewest that give the launch ~768 workgroups.  (Variant bits 29-30 force 1 / 2 / 4: tests, ablation.)
+    // slices, the fewest that give the launch ~768 workgroups.  (TRI_SLICES(n) forces 1 / 2 / 4: tests, ablation.)
     {
         const int64_t blocks = tri_geom(cs).blocks_of(rank);
         int S = 1;
         while (S < kMaxOwnSlices && blocks * S < 768) S *= 2;
-        const int forced = (g_topk_variant >> 29) & 3;
+        const int forced = (g_topk_variant & GORSE_TEST_TOPK_TRI_SLICES(3)) / GORSE_TEST_TOPK_TRI_SLICES(1);
         if (forced) S = forced == 1 ? 1 : (forced == 2 ? 2 : 4);
         cs.sym_slices = world > 1 || forced ? S : 1;
         if (cs.sym_slices > 1) {

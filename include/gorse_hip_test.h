@@ -30,28 +30,32 @@ void gorse_hip_test_set_variant(int32_t variant);
  * literal scan (path A), 2 = the MFMA sweep whenever its operands exist.  Both paths return identical results;
  * the hook exists so the parity tests can drive each one. */
 void gorse_hip_test_set_topk_path(int32_t path);
-/* probe switches of the MFMA sweep: bit 0 = 64 candidate rows per LDS tile, bit 1 = 128 (default: what the library
- * ships with), bit 2 / bit 3 = block-level row-scale bound of the cosine sweep off / on (default: on when all norms
- * are within 2 % of each other), bit 4 = the tie replay counts its work (see gorse_hip_test_get_sweep_profile; the main
- * sweep then keeps its square form), bit 5 / bit 6 = compact a candidate list
- * when one of its two sub-lists exceeds 224 / 96 entries (default 128), bit 14 = the history
- * sweep of the tie path in eight row slices whatever the index size (default: one slice per 32768 rows, at most eight),
- * bit 15 = in one slice, bits 17-18 = timing probes of the main sweep (1: no block ever qualifies, 2: a qualifying
- * block does nothing, 3: it counts its candidates without storing them; the search then returns after the sweep, results
- * undefined), bits 20-22 = the warm start's pilot sample: every 8th / every 32nd row tile instead of every 16th, and without the
- * 1/256 pilot in front (scripts/gpu_probe_topk_c4.py pilot).  Results never depend on the others. */
+/* Switches of the MFMA sweep and its tie path, for the parity tests: OR of the bits below.  Every other bit is ignored; 0 (the default)
+ * is the only value the product ever runs with.  Each drives one of two equivalent code paths or lets a small input reach a path
+ * that only a large one takes; results never depend on them. */
+#define GORSE_TEST_TOPK_TILE64 (1 << 0)           /* 64 candidate rows per LDS tile of the main sweep instead of 128 (then never symmetric) */
+#define GORSE_TEST_TOPK_COARSE_OFF (1 << 2)       /* cosine: every score times its row scale, whatever the norms ... */
+#define GORSE_TEST_TOPK_COARSE_ON (1 << 3)        /* ... or the block-level bound first (default: when all norms lie within 2 % of each other) */
+#define GORSE_TEST_TOPK_REPLAY_COUNTERS (1 << 4)  /* the tie replay counts its work; the main sweep keeps its square form */
+#define GORSE_TEST_TOPK_WARM_OFF (1 << 8)         /* no warm start: no pilot sweeps, every threshold starts at -inf */
+#define GORSE_TEST_TOPK_WARM_ALWAYS (1 << 9)      /* warm start, with both pilots, below its size limits of 2^17 / 2^18 rows */
+#define GORSE_TEST_TOPK_PILOT_KTH2 (1 << 10)      /* the pilot takes a kth of 2: most warm starts fail their verification */
+#define GORSE_TEST_TOPK_COLD_SLICES (1 << 11)     /* every row slice of the tie path's history sweep starts cold */
+#define GORSE_TEST_TOPK_SLICES8 (1 << 14)         /* that sweep in eight row slices whatever the index size ... */
+#define GORSE_TEST_TOPK_SLICE1 (1 << 15)          /* ... or in one (wins where both are set) */
+#define GORSE_TEST_TOPK_SYM_OFF (1 << 23)         /* the square form of an all-pairs sweep where the symmetric one is eligible */
+#define GORSE_TEST_TOPK_REPLAY_WAVE64 (1 << 28)   /* the tie replay with 64 queries per wave whatever the launch's size */
+/* bits 29-30, row slices per query block of a triangle-sharded sweep (gorse_topk_tri_*): n = 1 / 2 / 3 = one / two / four */
+#define GORSE_TEST_TOPK_TRI_SLICES(n) (((n) & 3) << 29)
+#define GORSE_TEST_TOPK_MASK                                                                                                     \
+    (GORSE_TEST_TOPK_TILE64 | GORSE_TEST_TOPK_COARSE_OFF | GORSE_TEST_TOPK_COARSE_ON | GORSE_TEST_TOPK_REPLAY_COUNTERS |          \
+     GORSE_TEST_TOPK_WARM_OFF | GORSE_TEST_TOPK_WARM_ALWAYS | GORSE_TEST_TOPK_PILOT_KTH2 | GORSE_TEST_TOPK_COLD_SLICES |          \
+     GORSE_TEST_TOPK_SLICES8 | GORSE_TEST_TOPK_SLICE1 | GORSE_TEST_TOPK_SYM_OFF | GORSE_TEST_TOPK_REPLAY_WAVE64 | GORSE_TEST_TOPK_TRI_SLICES(3))
 void gorse_hip_test_set_topk_variant(int32_t variant);
-/* (round 6) bit 27 = the tie path's history sweep with 64 instead of 128 queries per workgroup, bit 28 = the tie replay with 64 queries
- * per wave whatever the launch's size, bits 29-30 = the row slices per query block of a triangle-sharded sweep (gorse_topk_tri_*):
- * 1 = one, 2 = two, 3 = four (0: by the launch's size).  Results never depend on them. */
-/* variant bit 8 (256) switches the warm start of the sweep off (pilot sweep over every 16th row tile -> initial thresholds,
- * verified by the main sweep; csrc/topk_mfma.hip topk_mfma_search), bit 9 (512) switches it on below its size limit of 2^17
- * rows, bit 10 (1024) gives the pilot a kth of 2 so that most warm starts fail their verification.  This returns how many
- * queries of the last search failed it and were swept again from -inf. */
+/* how many queries of the last search failed the verification of their warm start and were swept again from -inf */
 int32_t gorse_hip_test_topk_resweeps(gorse_topk *h, int64_t *n /*out*/);
-/* variant bit 23 (1 << 23) switches the symmetric form of an all-pairs sweep off (the square sweep of rounds 1-4; the symmetric
- * form is taken when the queries are a contiguous range of the stored rows that starts on a 128-row boundary, the sweep is
- * warm-started, and the operands are 32 / 64 / 128 bf16 values deep).  This returns whether the last search's main sweep took it. */
+/* whether the last search's main sweep took the symmetric form: the queries are a contiguous range of the stored rows that starts on a
+ * 128-row boundary, the sweep is warm-started, and the operands are 32 / 64 / 128 bf16 values deep (GORSE_TEST_TOPK_SYM_OFF: never) */
 int32_t gorse_hip_test_topk_last_symmetric(gorse_topk *h, int32_t *sym /*out*/);
 /* counters of the last symmetric search: [0] queries the pilot left without a threshold (they take the tie path's sweep), [1] warm
  * starts the rescoring could not verify over both lists, [2] foreign lists that overflowed, [3] hits beyond a wave's staging area */
@@ -62,11 +66,9 @@ int32_t gorse_hip_test_topk_sym_stats(gorse_topk *h, uint64_t *out4 /*host*/);
 int32_t gorse_hip_test_topk_get_flags(gorse_topk *h, uint8_t *flags /*host*/, int64_t n);
 /* after a symmetric sweep: the entries other workgroups appended to each query's foreign list (more than 512 = the list overflowed) */
 int32_t gorse_hip_test_topk_get_foreign_counts(gorse_topk *h, int32_t *counts /*host*/, int64_t n);
-/* variant bit 24: the search stops behind the pilot sweep (results undefined); this returns the pilot's flags and list lengths */
-int32_t gorse_hip_test_topk_get_pilot_state(gorse_topk *h, uint8_t *flags /*host*/, int32_t *counts /*host*/, int64_t n);
 /* the warm-start thresholds of the last search's last chunk (the first n queries) */
 int32_t gorse_hip_test_topk_get_thresholds(gorse_topk *h, float *out /*host*/, int64_t n);
-/* with variant bit 4 set, the tie replay (csrc/topk_mfma.hip topk_tie_replay_lane_kernel) of a search counts its work; this
+/* with GORSE_TEST_TOPK_REPLAY_COUNTERS set, the tie replay (csrc/topk_mfma.hip topk_tie_replay_lane_kernel) of a search counts its work; this
  * returns the sixteen counters of the handle's last such replay, over its queries: [0] s_memtime ticks summed, [1] the most of one
  * query, [2] recorded entries summed, [3] queries, [4] heap pushes, [5] gaps evaluated (T^gap), [6] those where T was not the
  * identity, [7] literal applications of T summed, [8] the most of one query, [9] the most recorded entries of one query,
@@ -92,14 +94,6 @@ void gorse_hip_test_set_sparse_slots(int64_t max_slots);
  * more than their even share of the stored entries; 0 = none (every group through the super-visit loop, which falls back to the
  * direct accumulators where one group alone has too many postings); a value >= the number of groups = no super-visits. */
 void gorse_hip_test_set_sparse_head(int32_t groups);
-/* probe: a hashed super-visit of the sparse list walk takes at most (accumulators >> cap_shift) postings into its table of
- * (accumulators / 2) slots: 2 (default) = half full at most, 3 = a quarter, ...; outside 2..6 = the default. */
-void gorse_hip_test_set_sparse_table(int32_t cap_shift);
-/* timing probe (results are garbage): low byte 1 = a whole-query item of the UNSYMMETRIC sparse list walk visits only the row groups up to
- * its own row's -- the postings a symmetric walk of the whole-query items would still meet (sparse); 0 = off
- * (default).  Bits 8..: most workgroups of the dense-vector kernel of the heavy queries, in units of 256 (0 = 1024, the default; results
- * unaffected). */
-void gorse_hip_test_set_sparse_probe(int32_t probe);
 /* The symmetric form of gorse_sparse_all_pairs over all rows (csrc/sparse_kernels.hpp, SymArgs): mode 0 = never (the walk every other
  * call takes), -1 / 1 = when the call is eligible (default), 2 = likewise, but the front (gorse_hip_test_set_sparse_front) does not deliver.  c1 / c2 / c3 > 0 replace the capacities of the three tiers of foreign lists
  * (tests overflow them on purpose: the rows then take the unsymmetric walk in a second launch); 0 = the defaults.  Results never differ. */

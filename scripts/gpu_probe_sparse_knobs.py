@@ -19,14 +19,13 @@ ref = None
 lens = np.diff(ptr)
 
 
-def run(split, heavy, tile, head=-1, slots=0, rows_wgs=0):
+def run(split, heavy, tile, head=-1, slots=0):
     global ref
     L.gorse_hip_test_set_sparse_tile(tile)
     L.gorse_hip_test_set_sparse_split(split)
     L.gorse_hip_test_set_sparse_heavy(heavy)
     L.gorse_hip_test_set_sparse_head(head)
     L.gorse_hip_test_set_sparse_slots(slots)
-    L.gorse_hip_test_set_sparse_probe(rows_wgs << 8)
     sp = capi.Sparse(ptr, idx, val)
     out = sp.all_pairs(k, 0, N)
     if ref is None:
@@ -38,9 +37,8 @@ def run(split, heavy, tile, head=-1, slots=0, rows_wgs=0):
         sp.all_pairs(k, 0, N, fetch=False)
     sp.synchronize()
     dt = (time.perf_counter() - t0) / 5
-    print("split %5d (> split: %4d rows) heavy %6d (%3d rows) tile %5d head %2d slots %5d rows-kernel wgs %5d: %7.2f ms  postings %.3e  sym %s  equal %s"
-          % (split, int((lens > split).sum()), heavy, int((lens > heavy).sum()), tile or 2048, head, slots or 4096, rows_wgs * 256 or 1024,
-             dt * 1e3, sp.last_stats()[0], sp.sym_stats(), same), flush=True)
+    print("split %5d (> split: %4d rows) heavy %6d (%3d rows) tile %5d head %2d slots %5d: %7.2f ms  postings %.3e  sym %s  equal %s"
+          % (split, int((lens > split).sum()), heavy, int((lens > heavy).sum()), tile or 2048, head, slots or 4096, dt * 1e3, sp.last_stats()[0], sp.sym_stats(), same), flush=True)
     sp.close()
     return same
 
@@ -50,8 +48,8 @@ if len(sys.argv) > 3 and sys.argv[1] == "one":  # one configuration (split, heav
     sys.exit(0)
 ok = run(2048, 16384, 0)
 if len(sys.argv) > 1 and sys.argv[1] == "balance":  # list walk against dense-vector kernel at the default front
-    for heavy, wgs in itertools.product((8192, 10240, 12288, 16384, 20480, 24576), (0, 8)):
-        ok &= run(2048, heavy, 0, rows_wgs=wgs)
+    for heavy in (8192, 10240, 12288, 16384, 20480, 24576):
+        ok &= run(2048, heavy, 0)
     ok &= run(2048, 16384, 0)
 elif len(sys.argv) > 1 and sys.argv[1] == "split":
     for split in (2560, 3072, 3584, 4096, 5120, 6144, 8192, 12288, 16384):
@@ -74,6 +72,6 @@ else:
         ok &= run(2048, 16384, 0, slots=slots)
     ok &= run(2048, 16384, 0)
 for fn, v in ((L.gorse_hip_test_set_sparse_tile, 0), (L.gorse_hip_test_set_sparse_split, 2048), (L.gorse_hip_test_set_sparse_heavy, 16384),
-              (L.gorse_hip_test_set_sparse_head, -1), (L.gorse_hip_test_set_sparse_slots, 0), (L.gorse_hip_test_set_sparse_probe, 0)):
+              (L.gorse_hip_test_set_sparse_head, -1), (L.gorse_hip_test_set_sparse_slots, 0)):
     fn(v)
 sys.exit(0 if ok else 1)

@@ -16,9 +16,8 @@ L = capi.lib()
 N, k = ptr.size - 1, 100
 caps = [int(x) for x in sys.argv[1:4]] if len(sys.argv) >= 4 else [0, 0, 0]
 res = {}
-if len(sys.argv) == 2:  # `<mode> [+ 256 x (workgroups of the heavy-query kernel / 256)]`: that form alone, for a timeline
-    L.gorse_hip_test_set_sparse_sym(int(sys.argv[1]) & 0xff, 0, 0, 0)
-    L.gorse_hip_test_set_sparse_probe(int(sys.argv[1]) & ~0xff)
+if len(sys.argv) == 2:  # `<mode>`: that form alone, for a timeline
+    L.gorse_hip_test_set_sparse_sym(int(sys.argv[1]), 0, 0, 0)
     for _ in range(4):
         sp.all_pairs(k, 0, N, fetch=False)
     sp.synchronize()

@@ -42,40 +42,28 @@ def main():
         run("C4 S-emb bf16 cosine", Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 1_000_000, reps=1)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "tiles":  # 128- and 64-row tiles (run once per library build: GORSE_HIP_LIB)
-        for v, label in [(2, "128-row tiles"), (1, "64-row tiles")]:
+        for v, label in [(0, "128-row tiles"), (capi.TOPK_TILE64, "64-row tiles")]:
             capi.lib().gorse_hip_test_set_topk_variant(v)
             run("C4 256K q: " + label, Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=2)
         capi.lib().gorse_hip_test_set_topk_variant(0)
         return
     if len(sys.argv) > 1 and sys.argv[1] in ("onewarm", "onecold"):  # one configuration, for a kernel trace
-        capi.lib().gorse_hip_test_set_topk_variant(0 if sys.argv[1] == "onewarm" else 256)
+        capi.lib().gorse_hip_test_set_topk_variant(0 if sys.argv[1] == "onewarm" else capi.TOPK_WARM_OFF)
         run("C4 256K q: " + sys.argv[1], Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=1)
         capi.lib().gorse_hip_test_set_topk_variant(0)
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "prio":  # wave priority of the candidate path / the epilogue, cold and warm
-        for v, label in [(256 | 2048, "cold, default priority"), (256, "cold, candidate path prio 3"), (256 | 8192, "cold, + epilogue prio 1"),
-                         (0, "warm, candidate path prio 3"), (8192, "warm, + epilogue prio 1"), (2048, "warm, default priority")]:
-            capi.lib().gorse_hip_test_set_topk_variant(v)
-            run("C4 256K q: " + label, Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=2)
-        capi.lib().gorse_hip_test_set_topk_variant(0)
-        return
     if len(sys.argv) > 1 and sys.argv[1] == "warm":  # the warm-started sweep against the cold one, with the re-sweep counts
-        for v, label in [(256, "cold start"), (0, "warm start"), (2, "warm start, 128-row tiles"), (2 | 256, "cold start, 128-row tiles")]:
+        for v, label in [(capi.TOPK_WARM_OFF, "cold start"), (0, "warm start")]:
             capi.lib().gorse_hip_test_set_topk_variant(v)
             run("C4 256K q: " + label, Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=1)
             run("C4 1M q: " + label, Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 1_000_000, reps=1)
         capi.lib().gorse_hip_test_set_topk_variant(0)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "variants":  # tile height x block-level scale bound, C4 shape
-        for v, label in [(1 | 4, "64 rows, exact scale"), (1 | 8, "64 rows, block bound"), (2 | 8, "128 rows, block bound"),
-                         (1 | 8 | 32, "64 rows, compact at 2x128"), (1 | 8 | 64, "64 rows, compact at 2x96")]:
+        for v, label in [(capi.TOPK_TILE64 | capi.TOPK_COARSE_OFF, "64 rows, exact scale"), (capi.TOPK_TILE64 | capi.TOPK_COARSE_ON, "64 rows, block bound"),
+                         (capi.TOPK_COARSE_ON, "128 rows, block bound")]:
             capi.lib().gorse_hip_test_set_topk_variant(v)
             run("C4 256K q: " + label, Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=1)
-        capi.lib().gorse_hip_test_set_topk_variant(1 | 8 | 32)
-        run("C4 1M q: 64 rows, compact at 2x128", Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 1_000_000, reps=1)
-        capi.lib().gorse_hip_test_set_topk_variant(128)
-        run("C4 256K q: per-row wave vote in the candidate path", Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 262144, reps=1)
-        run("C4 1M q: per-row wave vote in the candidate path", Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 1_000_000, reps=1)
         capi.lib().gorse_hip_test_set_topk_variant(0)
         run("C4 1M q: library default", Xb, capi.METRIC_COSINE, capi.DTYPE_BF16, 100, 0, 1_000_000, reps=1)
         return

@@ -47,9 +47,9 @@ def main():
     if "quick" in sys.argv[1:]:
         return
     if "sym" in sys.argv[1:]:  # the symmetric form of the sweep against the square one: stage times, then EVERY row of both passes
-        SYM_OFF = 1 << 23
+        SYM_OFF = capi.TOPK_SYM_OFF
         for rep in range(2):
-            for v, label in ((0, "symmetric sweep (default)"), (SYM_OFF, "square sweep (variant bit 23)")):
+            for v, label in ((0, "symmetric sweep (default)"), (SYM_OFF, "square sweep (TOPK_SYM_OFF)")):
                 L.gorse_hip_test_set_topk_variant(v)
                 run(t, k, 0, nq, label, reps=2)
                 print("   main sweep symmetric: %s" % t.last_symmetric(), flush=True)
@@ -83,18 +83,8 @@ def main():
             run(t, k, a, b, "range [%d, %d) square" % (a, b), reps=2)
         L.gorse_hip_test_set_topk_variant(0)
         return
-    if "symfloor" in sys.argv[1:]:  # what the parts of the symmetric sweep cost (results are garbage: timing only)
-        run(t, k, 0, nq, "symmetric sweep", reps=2)
-        print("   counters [no pilot threshold, unverified, foreign overflow, staging overflow]: %s" % t.sym_stats(), flush=True)
-        for v, label in ((1 << 25, "no tile read along its rows"), (2 << 25, "block + row tests, a hit does nothing"), (3 << 25, "hits staged, never flushed"),
-                         (1 << 17, "no block qualifies on the column side (own thresholds +inf)"), ((1 << 17) | (1 << 25), "neither side: the symmetric floor"),
-                         ((1 << 23) | (1 << 17), "square sweep, no block qualifies")):
-            L.gorse_hip_test_set_topk_variant(v)
-            run(t, k, 0, nq, label, reps=2)
-        L.gorse_hip_test_set_topk_variant(0)
-        return
-    if "replay" in sys.argv[1:]:  # the tie replay's counters (variant bit 4)
-        L.gorse_hip_test_set_topk_variant(16)
+    if "replay" in sys.argv[1:]:  # the tie replay's counters
+        L.gorse_hip_test_set_topk_variant(capi.TOPK_REPLAY_COUNTERS)
         run(t, k, 0, nq, "instrumented", reps=1)
         c = t.sweep_profile()
         q = max(c[3], 1)
@@ -102,17 +92,17 @@ def main():
               % (c[3], c[0] / q, c[1], c[2] / q, c[9], c[4] / q, c[5] / q, c[6] / q, c[7] / q, c[8], c[10]), flush=True)
         L.gorse_hip_test_set_topk_variant(0)
         return
-    if "lanes" in sys.argv[1:]:  # the tie replay: queries per wave chosen by the launch's size (default) against always 64 (variant bit 28)
-        for v, label in ((0, "queries per replay wave by launch size"), (1 << 28, "64 queries per replay wave"),
-                         (0, "by launch size again"), (1 << 28, "64 again")):
+    if "lanes" in sys.argv[1:]:  # the tie replay: queries per wave chosen by the launch's size (default) against always 64
+        for v, label in ((0, "queries per replay wave by launch size"), (capi.TOPK_REPLAY_WAVE64, "64 queries per replay wave"),
+                         (0, "by launch size again"), (capi.TOPK_REPLAY_WAVE64, "64 again")):
             L.gorse_hip_test_set_topk_variant(v)
             run(t, k, 0, nq, label, reps=2)
         L.gorse_hip_test_set_topk_variant(0)
         return
-    if "warm" in sys.argv[1:]:  # round 6: the history sweep's slices started from the bounds the main sweep's lists prove (default) against cold (bit 11)
-        COLD = 1 << 11
+    if "warm" in sys.argv[1:]:  # round 6: the history sweep's slices started from the bounds the main sweep's lists prove (default) against cold
+        COLD = capi.TOPK_COLD_SLICES
         for rep in range(2):
-            for v, label in ((0, "history slices warm (default)"), (COLD, "history slices cold (bit 11)")):
+            for v, label in ((0, "history slices warm (default)"), (COLD, "history slices cold (TOPK_COLD_SLICES)")):
                 L.gorse_hip_test_set_topk_variant(v)
                 run(t, k, 0, nq, label, reps=2)
         L.gorse_hip_test_set_topk_variant(0)
@@ -127,30 +117,7 @@ def main():
         print("all %d rows with warm-started history slices equal the cold form's: %s" % (nq, same), flush=True)
         assert same
         return
-    if "hist" in sys.argv[1:]:  # the tie path's history sweep: workgroups of 64 queries (variant bit 27) against 128, 8 / 1 row slices
-        for v, label in ((0, "default (128 queries per history workgroup, 8 slices)"), (1 << 27, "64 queries per history workgroup"),
-                         (0, "default again"), (1 << 27, "64 queries again")):
-            L.gorse_hip_test_set_topk_variant(v)
-            run(t, k, 0, nq, label, reps=2)
-        L.gorse_hip_test_set_topk_variant(0)
-        return
-    if "pilot" in sys.argv[1:]:  # the warm start: stride of the pilot sample, with and without the 1/256 pilot in front of it
-        for v, label in ((0, "pilots 1/256 + 1/16 (default)"), (1 << 20, "pilots 1/128 + 1/8"), (1 << 21, "pilots 1/512 + 1/32"),
-                         (1 << 22, "pilot 1/16 alone"), ((1 << 21) | (1 << 22), "pilot 1/32 alone"), (256, "no warm start")):
-            L.gorse_hip_test_set_topk_variant(v)
-            run(t, k, 0, nq, label, reps=2)
-        L.gorse_hip_test_set_topk_variant(0)
-        return
-    if "floor" in sys.argv[1:]:  # what the sweep costs without its candidate path (results are garbage: timing only)
-        for v, label in ((256, "cold sweep alone"), (256 | (1 << 17), "cold sweep, no block ever qualifies"),
-                         (1 << 17, "main: no block qualifies"), (2 << 17, "main: qualifying blocks do nothing"),
-                         (3 << 17, "main: candidates counted, not stored"), (32, "compaction at 224"), (64, "compaction at 96")):
-            L.gorse_hip_test_set_topk_variant(v)
-            run(t, k, 0, nq, label, reps=1)
-        L.gorse_hip_test_set_topk_variant(0)
-        return
-    for v, label in ((1 << 15, "history sweep in one slice"), (1 << 16, "replay: literal T"), ((1 << 15) | (1 << 16), "one slice + literal T (round 2)"),
-                     (256, "no warm start"), (4, "no block-level scale bound")):
+    for v, label in ((capi.TOPK_SLICE1, "history sweep in one slice"), (capi.TOPK_WARM_OFF, "no warm start"), (capi.TOPK_COARSE_OFF, "no block-level scale bound")):
         L.gorse_hip_test_set_topk_variant(v)
         run(t, k, 0, nq, label, reps=1)
     L.gorse_hip_test_set_topk_variant(0)

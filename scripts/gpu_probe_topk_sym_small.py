@@ -8,7 +8,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from gorse_amd import capi  # noqa: E402
 
-WARM_ALWAYS, SYM_OFF = 512, 1 << 23
+WARM_ALWAYS, SYM_OFF = capi.TOPK_WARM_ALWAYS, capi.TOPK_SYM_OFF
 N, d, k = 40000, 128, 100
 rng = np.random.default_rng(N + d)
 Xf = rng.standard_normal((N, d)).astype(np.float32)
@@ -24,15 +24,6 @@ for metric, name in ((capi.METRIC_COSINE, "cosine"), (capi.METRIC_NEG_DOT, "-dot
         print("%-10s %-10s symmetric %s: re-sweeps %d, tie/scan %s, stats [no pilot threshold, unverified, foreign overflow, staging overflow] %s"
               % (name, label, t.last_symmetric(), t.resweeps(), t.last_stats(), t.sym_stats()), flush=True)
         if v & SYM_OFF:
-            capi.lib().gorse_hip_test_set_topk_variant(v | (1 << 24))
-            t.all_pairs(k, fetch=False)
-            fl, cn = t.pilot_state(N)
-            print("   pilot alone: flags 0/1/2: %s; list lengths of the flagged: %s; of the others: min %d median %d max %d"
-                  % (np.bincount(fl, minlength=3).tolist(), np.unique(cn[fl != 0])[:10].tolist(), cn[fl == 0].min(), np.median(cn[fl == 0]), cn[fl == 0].max()), flush=True)
-            ft = t.warm_thresholds(N)
-            print("   thresholds of the flagged: %s, unset without a flag: %d" % (np.unique(ft[fl != 0])[:5].tolist(), int((np.isinf(ft) & (fl == 0)).sum())), flush=True)
-            capi.lib().gorse_hip_test_set_topk_variant(v)
-            t.all_pairs(k, fetch=False)
             f = t.warm_thresholds(N)
             unset = np.isinf(f)
             print("   queries without a pilot threshold: %d; by index decile: %s; thresholds min %.3f max %.3f"

@@ -19,7 +19,7 @@ from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-V_TILE64, V_SLICES8 = 1, 1 << 14
+V_TILE64, V_SLICES8 = capi.TOPK_TILE64, capi.TOPK_SLICES8
 
 
 def bits(a):
@@ -110,7 +110,7 @@ def test_deep_operands_with_k_100(oracle, case, metric):
 @pytest.mark.parametrize("metric", tc.METRICS)
 @pytest.mark.parametrize("case", tc.TILE64_CASES, ids=case_id)
 def test_64_row_tiles_of_the_register_staged_sweep(oracle, case, metric):
-    """variant bit 0: KP 3 and KP 6 stage their tiles through registers; with 64-row tiles (RB = 2) the same rows"""
+    """TOPK_TILE64: KP 3 and KP 6 stage their tiles through registers; with 64-row tiles (RB = 2) the same rows"""
     capi.lib().gorse_hip_test_set_topk_variant(V_TILE64)
     sweep_all_calls(oracle, case[0], case[1], metric, tc.DEPTH_K)
 

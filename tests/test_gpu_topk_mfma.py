@@ -34,7 +34,9 @@ def _paths(oracle):
     capi.lib().gorse_hip_test_set_topk_variant(0)
 
 
-@pytest.mark.parametrize("variant", [1, 2, 1 | 4, 1 | 8, 2 | 4, 2 | 8])
+# (the ids are the values these six cases had while a bit of its own selected the 128-row tiles, today's default)
+@pytest.mark.parametrize("variant", [capi.TOPK_TILE64, 0, capi.TOPK_TILE64 | capi.TOPK_COARSE_OFF, capi.TOPK_TILE64 | capi.TOPK_COARSE_ON,
+                                     capi.TOPK_COARSE_OFF, capi.TOPK_COARSE_ON], ids=["1", "2", "5", "9", "6", "10"])
 @pytest.mark.parametrize("dtype,d,N", [(capi.DTYPE_BF16, 128, 4321), (capi.DTYPE_F32, 40, 3000), (capi.DTYPE_BF16, 64, 130)])
 def test_sweep_variants_return_the_same_rows(oracle, variant, dtype, d, N):
     # tile height (64 / 128 candidate rows per barrier) and the block-level row-scale bound of the cosine sweep are
@@ -150,7 +152,7 @@ def test_tie_replay_long_history(oracle, N, d, k, lo, hi, metric):
         assert c2[r] == ei.size and np.array_equal(i2[r, :c2[r]], ei) and np.array_equal(bits(d2[r, :c2[r]]), bits(ed))
 
 
-V_SLICES8, V_SLICE1, V_INSTRUMENTED = 1 << 14, 1 << 15, 16
+V_SLICES8, V_SLICE1, V_INSTRUMENTED = capi.TOPK_SLICES8, capi.TOPK_SLICE1, capi.TOPK_REPLAY_COUNTERS
 
 
 @pytest.mark.parametrize("variant", [V_SLICES8, V_SLICE1, V_SLICES8 | V_INSTRUMENTED])
@@ -192,15 +194,15 @@ def test_history_sweep_in_row_slices_and_the_replay_shortcut(oracle, variant, me
         assert c2[q] == ei.size and np.array_equal(i2[q, :c2[q]], ei) and np.array_equal(bits(d2[q, :c2[q]]), bits(ed))
 
 
-V_COLD_SLICES = 1 << 11
+V_COLD_SLICES = capi.TOPK_COLD_SLICES
 
 
 @pytest.mark.parametrize("metric", [capi.METRIC_COSINE, capi.METRIC_NEG_DOT, capi.METRIC_EUCLIDEAN])
 def test_history_slices_started_from_the_main_sweeps_lists(oracle, metric):
     """Round 6 (csrc/topk_mfma.hip: tie_warm_kernel, sweep_hist_dma).  A bf16 index of d = 128 (eight k-steps: the history sweep takes the
     main sweep's eight-wave LDS-DMA form) with planted duplicates, eight row slices forced on a small index: every slice but the first
-    starts from the bound the main sweep's list entries in front of it prove (default) -- against the slices that start cold (variant
-    bit 11), every row of the two forms compared, and a sample of tie rows and plain rows against the oracle."""
+    starts from the bound the main sweep's list entries in front of it prove (default) -- against the slices that start cold
+    (TOPK_COLD_SLICES), every row of the two forms compared, and a sample of tie rows and plain rows against the oracle."""
     rng = np.random.default_rng(4100 + metric)
     N, d, k, nq = 24000, 128, 30, 2048
     Xf = rng.standard_normal((N, d)).astype(np.float32)
@@ -214,7 +216,7 @@ def test_history_slices_started_from_the_main_sweeps_lists(oracle, metric):
     Xe = from_bf16(X)
     out = {}
     for v in (V_SLICES8, V_SLICES8 | V_COLD_SLICES):
-        capi.lib().gorse_hip_test_set_topk_variant(v | 512)  # (bit 9: the warm-started main sweep on an index this small)
+        capi.lib().gorse_hip_test_set_topk_variant(v | capi.TOPK_WARM_ALWAYS)  # (the warm-started main sweep on an index this small)
         t = capi.TopK(X, metric, dtype=capi.DTYPE_BF16)
         idx, dist, cnt = t.search_index(np.arange(nq), k)
         out[v] = (idx.copy(), dist.copy(), cnt.copy(), t.last_stats())
@@ -337,7 +339,7 @@ def test_large_index_against_the_scan():
     assert np.array_equal(ia, idx[sample - q0]) and np.array_equal(bits(da), bits(dist[sample - q0]))
 
 
-WARM_OFF, WARM_ALWAYS, WARM_SABOTAGE = 256, 512, 512 | 1024
+WARM_OFF, WARM_ALWAYS, WARM_SABOTAGE = capi.TOPK_WARM_OFF, capi.TOPK_WARM_ALWAYS, capi.TOPK_WARM_ALWAYS | capi.TOPK_PILOT_KTH2
 
 
 @pytest.mark.parametrize("metric", [capi.METRIC_COSINE, capi.METRIC_NEG_DOT, capi.METRIC_EUCLIDEAN])
@@ -403,7 +405,7 @@ def test_admissibility_mask(oracle, metric, path):
     assert np.array_equal(again[0], plain[0]) and np.array_equal(bits(again[1]), bits(plain[1]))
 
 
-SYM_OFF = 1 << 23
+SYM_OFF = capi.TOPK_SYM_OFF
 
 
 @pytest.mark.parametrize("metric", [capi.METRIC_COSINE, capi.METRIC_NEG_DOT, capi.METRIC_EUCLIDEAN])
@@ -412,7 +414,7 @@ SYM_OFF = 1 << 23
 def test_symmetric_sweep_equals_the_square_sweep(oracle, metric, dtype, d, norms):
     """An all-pairs search whose queries are a contiguous range of the stored rows takes the symmetric form of the sweep
     (topk_sweep_kernel<..., SYM>: a workgroup skips the row tiles of later query blocks and reads the tiles of earlier ones along
-    their rows, for those rows' foreign lists).  Rows, distance bits and counts must equal the square sweep's (variant bit 23) for
+    their rows, for those rows' foreign lists).  Rows, distance bits and counts must equal the square sweep's (TOPK_SYM_OFF) for
     every query range -- all rows, a range that starts and ends inside the index, one that ends inside a tile -- with every
     epilogue (cosine with equal norms: raw-score thresholds; skewed norms: scaled scores; Euclidean: biased scores), duplicates
     (ties: the history sweep answers them) and a mask; and equal the oracle's on a sample."""
@@ -473,3 +475,55 @@ def test_symmetric_sweep_with_overflowing_foreign_lists(oracle):
     assert t.last_symmetric()
     qs = np.array([0, 17, 18, 4999, 5000, 5450, 5899, 5900, 12345, N - 1])
     check_rows(oracle, Xe, capi.METRIC_NEG_DOT, qs, k, idx[qs], dist[qs])
+
+
+def test_retired_variant_bits_are_ignored():
+    """gorse_hip_test_set_topk_variant keeps the named switches only (capi.TOPK_VARIANT_MASK): every other bit -- the retired timing
+    probes and tuning alternatives among them, which made a search return garbage or stop behind its pilot -- changes nothing.
+    A bf16 index of operand depth 2 whose 2048 queries are four symmetric query blocks.  An index of sixteen row tiles gives both pilots
+    (every 256th and every 16th tile) the same sample, tile 0, and the second one -- started at the first one's 4th best, looking for
+    a 5th -- then leaves nearly every query without a threshold (1947 of 2048 with plain Gaussian rows), which sends the search to the
+    square sweep.  So tile 0 holds sixteen vectors eight times each: the best scores of the sample come eight at a time, both pilots
+    agree, and the main sweep takes the symmetric form (with ~155 warm starts swept again, the same in both runs)."""
+    rng = np.random.default_rng(2048)
+    N, d, k = 2048, 32, 10
+    Xf = rng.standard_normal((N, d)).astype(np.float32)
+    Xf[:128] = np.repeat(Xf[:16], 8, axis=0)
+    X = to_bf16(Xf)
+    t = capi.TopK(X, capi.METRIC_COSINE, dtype=capi.DTYPE_BF16)
+    retired = ~capi.TOPK_VARIANT_MASK & 0xffffffff
+    assert retired & (1 << 17) and retired & (1 << 24) and retired & (1 << 25)
+    out = []
+    for v in (capi.TOPK_WARM_ALWAYS, capi.TOPK_WARM_ALWAYS | retired):
+        capi.lib().gorse_hip_test_set_topk_variant(v - (1 << 32) if v >> 31 else v)  # (as the int32 the hook takes)
+        idx, dist = t.all_pairs(k)
+        out.append((idx, dist, t.last_symmetric(), t.resweeps()))
+    (i_a, d_a, sym_a, re_a), (i_b, d_b, sym_b, re_b) = out
+    assert np.array_equal(i_a, i_b) and np.array_equal(bits(d_a), bits(d_b))
+    assert sym_a and sym_b
+    assert re_a == re_b
+
+
+def test_tie_replay_with_64_queries_per_wave(oracle):
+    """topk_tie_replay_lane_kernel<64>.  The replay halves its queries per wave while the launch has fewer than 256 waves, so only a
+    chunk of 16384 tie queries reaches the 64-lane form by itself; TOPK_REPLAY_WAVE64 keeps 64 whatever the launch's size.  The LDS rule
+    in front of it (chunk_finish) must leave 64 too: (3 (k + 1) + 2 kLaneLog) * 64 * 4 <= 144 KiB with kLaneLog = 24 is
+    3 (k + 1) + 48 <= 576, k <= 175; k = 130 takes (393 + 48) * 256 = 112,896 bytes.  96 queries: one full wave and one half full.
+    Small-integer vectors as in test_tie_replay_with_large_k make nearly every query a tie query."""
+    k = 130
+    rng = np.random.default_rng(500 + k)
+    N, d = 9000, 6
+    X = rng.integers(-4, 5, (N, d)).astype(np.float32)
+    qs = rng.choice(N, 96, replace=False)
+    t = capi.TopK(X, capi.METRIC_NEG_DOT)
+    out = []
+    for v in (V_SLICES8 | capi.TOPK_REPLAY_WAVE64, V_SLICES8):
+        capi.lib().gorse_hip_test_set_topk_variant(v)
+        out.append(t.search_index(qs, k) + (t.last_stats(),))
+    (i_w, d_w, c_w, st_w), (i_s, d_s, c_s, st_s) = out
+    assert np.array_equal(c_w, c_s) and np.array_equal(i_w, i_s) and np.array_equal(bits(d_w), bits(d_s))
+    for r, q in enumerate(qs):
+        ei, ed = oracle.search_index(X, capi.METRIC_NEG_DOT, int(q), k)
+        assert c_w[r] == ei.size and np.array_equal(i_w[r, :c_w[r]], ei), (q, st_w)
+        assert np.array_equal(bits(d_w[r, :c_w[r]]), bits(ed)), q
+    assert st_w[1] > 50 and st_s[1] > 50, (st_w, st_s)

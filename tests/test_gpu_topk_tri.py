@@ -53,7 +53,7 @@ def test_triangle_shards_equal_the_single_rank_pass(oracle, metric, dtype, d):
     L = capi.lib()
     try:
         for forced, world in ((2, 1), (3, 2), (2, 3)):
-            L.gorse_hip_test_set_topk_variant(forced << 29)
+            L.gorse_hip_test_set_topk_variant(capi.TOPK_TRI_SLICES(forced))
             idx, dist, _ = run_world(handles, k, world)
             assert np.array_equal(idx, ref_i) and np.array_equal(bits(dist), bits(ref_d)), "slices forced (%d), world %d" % (forced, world)
     finally:
