@@ -7,6 +7,8 @@
 // the rotate-add butterfly below reproduces `_mm512_dot` bit for bit, while every global
 // access of a group is one contiguous 64-byte segment.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace gorse {
@@ -88,6 +90,38 @@ __device__ __forceinline__ float dot512_regs(const float (&a)[NC], const float (
 #pragma unroll
     for (int c = 1; c < NC; c++) acc = fmaf(a[c], b[c], acc);
     return group_tree16(acc);
+}
+
+// ---- the factor width's kernel form, stated once --------------------------------------------------------------------------
+// A kernel that scores (user, item) pairs comes in two forms: for nFactors = 16 NC <= 128 a group holds a factor row in NC registers
+// per lane and reduces with dot512_regs<NC>; for every other width the row is staged in LDS and reduced with dot512_lds (NC = 0).
+// The two forms give the same bits wherever both could run: at d = 16 NC VecShape has no 8-lane tail and no scalar tail, and both
+// are a[0] * b[0], the fmaf chain over chunks 1 .. NC - 1 in order, group_tree16.  So which widths take the register form is a
+// matter of speed alone, and every launcher (score, evaluate, recommend) may share this one mapping.
+constexpr int kMaxRegisterChunks = 8;
+constexpr bool factor_row_in_registers(int d) { return d % 16 == 0 && d <= 16 * kMaxRegisterChunks; }
+// fn(std::integral_constant<int, NC>{}): NC = d / 16 where the row is held in registers, 0 (the LDS form) otherwise
+template <class F>
+inline void with_factor_chunks(int d, F &&fn) {
+    using std::integral_constant;
+    switch (factor_row_in_registers(d) ? d / 16 : 0) {
+        case 1: fn(integral_constant<int, 1>{}); break;
+        case 2: fn(integral_constant<int, 2>{}); break;
+        case 3: fn(integral_constant<int, 3>{}); break;
+        case 4: fn(integral_constant<int, 4>{}); break;
+        case 5: fn(integral_constant<int, 5>{}); break;
+        case 6: fn(integral_constant<int, 6>{}); break;
+        case 7: fn(integral_constant<int, 7>{}); break;
+        case 8: fn(integral_constant<int, 8>{}); break;
+        default: fn(integral_constant<int, 0>{}); break;
+    }
+}
+
+// x in row[0 .. n), a row in no particular order (a sorted row: row_contains, bpr_stream.hpp)
+__device__ __forceinline__ bool row_has_linear(const int32_t *__restrict__ row, int64_t n, int32_t x) {
+    for (int64_t t = 0; t < n; t++)
+        if (row[t] == x) return true;
+    return false;
 }
 
 // math32.Exp restated (see oracle/gorse_oracle.c orc_exp_restated; chewxy/math32 exp.go states

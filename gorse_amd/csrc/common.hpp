@@ -74,6 +74,17 @@ struct DevBuf {
     int32_t ensure(size_t count) { return count <= n ? GORSE_OK : alloc(count); }
 };
 
+// ---- staging layout -----------------------------------------------------------------
+// Consecutive pieces of one staging buffer, each 256-byte aligned: take() returns a piece's offset, off is what to ensure() at the end.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
 // ---- per-kernel-class event profiling --------------------------------------------------
 // Each profiled launch is bracketed by an event pair recorded on the stream the kernel
 // runs on; pairs are resolved lazily (hipEventElapsedTime) when the profile is read.

@@ -6,8 +6,7 @@
 // negatives (master/tasks.go:232: SplitCF + SampleUserNegatives), so every Fit paid this as a host loop before epoch 0; here one
 // thread per user draws from the user's own Philox stream (seed, "neg", user) through Go's Int31n -- the reference's ONE
 // sequential math/rand stream cannot be reproduced anyway -- and the candidate CSR stays resident for
-// gorse_mf_rank_resident, so an Evaluate between epochs uploads nothing.
-#include "goheap.hpp"
+// gorse_mf_rank_resident (mf_rank.hip) and gorse_mf_evaluate_resident (mf_eval.hip), so an Evaluate between epochs uploads nothing.
 #include "mf_internal.hpp"
 
 using namespace gorse;
@@ -16,23 +15,6 @@ namespace {
 
 constexpr uint64_t kNegStream = 0x6e6567ull;  // "neg": the epoch word of the negatives' streams (the oracle's ORC_NEG_STREAM)
 constexpr int64_t kNegMaxDraws = (int64_t)1 << 24;  // per user; the reference spins forever
-
-__device__ __forceinline__ bool sorted_has(const int32_t *__restrict__ row, int64_t n, int32_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (row[mid] < x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo < n && row[lo] == x;
-}
-__device__ __forceinline__ bool linear_has(const int32_t *__restrict__ row, int64_t n, int32_t x) {
-    for (int64_t t = 0; t < n; t++)
-        if (row[t] == x) return true;
-    return false;
-}
 
 // one thread per user: SampleInt32(0, I, n, test row, train row)
 __global__ __launch_bounds__(128) void sample_negatives_kernel(int64_t U, int32_t I, const int64_t *__restrict__ train_ptr,
@@ -49,12 +31,12 @@ __global__ __launch_bounds__(128) void sample_negatives_kernel(int64_t U, int32_
     const int64_t nte = test_ptr[u + 1] - test_ptr[u];
     int64_t card = 0;  // |test set U train set|, duplicates once (mapset semantics)
     for (int64_t t = 0; t < ntr; t++) card += t == 0 || tr[t] != tr[t - 1];
-    for (int64_t t = 0; t < nte; t++) card += !sorted_has(tr, ntr, te[t]) && !linear_has(te, t, te[t]);
+    for (int64_t t = 0; t < nte; t++) card += !row_contains(tr, ntr, te[t]) && !row_has_linear(te, t, te[t]);
     int32_t *o = out + u * (int64_t)n;
     int32_t got = 0;
     if ((int64_t)n >= (int64_t)I - card) {  // random.go:115-121: everything that is left, ascending
         for (int32_t i = 0; i < I && got < n; i++)
-            if (!sorted_has(tr, ntr, i) && !linear_has(te, nte, i)) o[got++] = i;
+            if (!row_contains(tr, ntr, i) && !row_has_linear(te, nte, i)) o[got++] = i;
     } else {
         Philox g;
         g.init(seed, kNegStream, (uint64_t)u);
@@ -62,7 +44,7 @@ __global__ __launch_bounds__(128) void sample_negatives_kernel(int64_t U, int32_
         while (got < n && draws < kNegMaxDraws) {
             const int32_t v = g.int31n(I);
             draws++;
-            if (!sorted_has(tr, ntr, v) && !linear_has(te, nte, v) && !linear_has(o, got, v)) o[got++] = v;
+            if (!row_contains(tr, ntr, v) && !row_has_linear(te, nte, v) && !row_has_linear(o, got, v)) o[got++] = v;
         }
         if (got < n) atomicAdd(fail_count, 1);
     }
@@ -171,29 +153,15 @@ extern "C" int32_t gorse_mf_sample_user_negatives(gorse_mf *h, const int64_t *te
 
 extern "C" int32_t gorse_mf_resident_candidates(gorse_mf *h, int64_t *n_users, int64_t *n_candidates) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
-    if (!h->ev_valid) return fail(GORSE_ERR_INVALID, "no resident candidate lists (gorse_mf_sample_user_negatives first)");
-    if (n_users) *n_users = h->ev_users_n;
-    if (n_candidates) *n_candidates = h->ev_cand_n;
+    UserLists lists;
+    GORSE_TRY(resident_user_lists(h, &lists));
+    if (n_users) *n_users = lists.n_users;
+    if (n_candidates) *n_candidates = lists.n_cand;
     return GORSE_OK;
 }
 
 extern "C" int32_t gorse_mf_resident_generation(gorse_mf *h, uint64_t *generation) {
     if (!h || !generation) return fail(GORSE_ERR_INVALID, "NULL argument");
     *generation = h->ev_valid ? h->ev_generation : 0;
-    return GORSE_OK;
-}
-
-extern "C" int32_t gorse_mf_rank_resident(gorse_mf *h, int32_t topk, int32_t *users_out, int32_t *rank_out, int32_t *rank_len) {
-    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
-    if (!h->ev_valid) return fail(GORSE_ERR_INVALID, "no resident candidate lists (gorse_mf_sample_user_negatives first)");
-    if (topk <= 0) return fail(GORSE_ERR_INVALID, "topk <= 0");
-    if (h->ev_users_n == 0) return GORSE_OK;
-    if (!rank_out || !rank_len) return fail(GORSE_ERR_INVALID, "NULL argument");
-    GORSE_TRY(h->use());
-    GORSE_TRY(mf_sync_streams(h));
-    GORSE_TRY(mf_rank_device(h, h->ev_users_n, h->ev_users.p, h->ev_cptr.p, h->ev_cand.p, h->ev_cand_n, topk, rank_out, rank_len));
-    if (users_out)
-        GORSE_HIP_CHECK(hipMemcpyAsync(users_out, h->ev_users.p, (size_t)h->ev_users_n * 4, hipMemcpyDeviceToHost, h->stream));
-    GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
     return GORSE_OK;
 }

@@ -1,9 +1,9 @@
 // mf_eval.hip -- cf.Evaluate's ranking AND metrics on the device (model/cf/evaluator.go:35-160).
-// The route of mf.hip (gorse_mf_rank / gorse_mf_rank_resident) writes one (user, item) pair per candidate, scores the pairs,
+// The route of mf_rank.hip (gorse_mf_rank / gorse_mf_rank_resident) writes one (user, item) pair per candidate, scores the pairs,
 // ranks one user per thread over a heap in global memory and sends n_users x topK ranks to the host, which builds a set per
 // user and walks the metrics.  Here one launch does all of it per user, and what crosses PCIe is six sums:
-//   mf_eval_user_kernel<NC>  one 16-lane group per evaluated user (the layout of mf_score_kernel / cf_device.hpp, so every score has
-//                            gorse_mf_score's bits): p_u is loaded once (registers for nFactors = 16 NC, LDS otherwise), the
+//   mf_eval_user_kernel<NC>  one 16-lane group per evaluated user (mf_score_kernel's layout and width dispatch, cf_device.hpp
+//                            with_factor_chunks, so every score has gorse_mf_score's bits): p_u is loaded once, the
 //                            candidates are scored a slice at a time into LDS, lane 0 pushes the slice in candidate order into the
 //                            literal GoHeap<false> whose topK + 1 slots live in LDS (mf_rank_kernel's push / pop sequence, so ties
 //                            fall as container/heap lets them), pops the rank list in place, the group marks the list's hits
@@ -47,12 +47,6 @@ struct MfEvalArgs {
 
 // floats per 16-lane group of the kernel's LDS: heap items | heap weights | slice scores | slice items | (LDS form) p_u | q_i
 __host__ __device__ inline int group_floats(int topk, int d, bool lds_form) { return 2 * (topk + 1) + 2 * kSlice + (lds_form ? 2 * d : 0); }
-
-__device__ __forceinline__ bool row_has(const int32_t *__restrict__ row, int64_t n, int32_t x) {
-    for (int64_t t = 0; t < n; t++)
-        if (row[t] == x) return true;
-    return false;
-}
 
 // the group's lanes wrote LDS that other lanes of the group read next (one wave: its LDS operations complete in order)
 __device__ __forceinline__ void group_sync() {
@@ -152,13 +146,13 @@ __global__ __launch_bounds__(kBlock) void mf_eval_user_kernel(const MfEvalArgs A
     // ---- hits (targetSet.Contains), the target set's cardinality
     for (int r = lane; r < cnt; r += kGroup) {
         const int32_t item = hv[r];
-        hw[r] = row_has(te, nte, item) ? 1.0f : 0.0f;
+        hw[r] = row_has_linear(te, nte, item) ? 1.0f : 0.0f;
         if (A.rank_out) A.rank_out[t * topk + r] = item;
     }
     if (A.rank_out)
         for (int r = cnt + lane; r < topk; r += kGroup) A.rank_out[t * topk + r] = -1;
     int card = 0;
-    for (int64_t k = lane; k < nte; k += kGroup) card += !row_has(te, k, te[k]);
+    for (int64_t k = lane; k < nte; k += kGroup) card += !row_has_linear(te, k, te[k]);
     card += __shfl_xor(card, 8, kGroup);
     card += __shfl_xor(card, 4, kGroup);
     card += __shfl_xor(card, 2, kGroup);
@@ -218,11 +212,6 @@ __global__ __launch_bounds__(64) void mf_eval_chain_kernel(const float *__restri
     if (lane < kMetrics) sums[lane] = s;
 }
 
-template <int NC>
-void launch_user(const MfEvalArgs &A, dim3 grid, size_t lds, hipStream_t s) {
-    mf_eval_user_kernel<NC><<<grid, dim3(kBlock), lds, s>>>(A);
-}
-
 // the two tables, as the host mirror computes their entries (math32.Log2 -> log2f; evaluator.go:80-92)
 void fill_tables(float *inv_log, float *idcg, int n) {
     volatile float two = 2.0f;  // (a run-time call of libm's log2f, never the compiler's own evaluation)
@@ -237,11 +226,11 @@ void fill_tables(float *inv_log, float *idcg, int n) {
 float float_count(int64_t n) { return (float)std::min<int64_t>(n, (int64_t)1 << 24); }
 
 // Both entry points end here: lists on the device, everything validated.  n_counted = users with a target row.
-int32_t evaluate_device(gorse_mf *h, int64_t n_users, int64_t n_counted, const int32_t *d_users, const int64_t *d_cptr,
-                        const int32_t *d_cand, int64_t nc, const int64_t *d_tptr, const int32_t *d_tgt, bool tgt_by_user,
-                        int32_t topk, float *sums, float *count, float *per_user, int32_t *rank_out, int32_t *rank_len) {
+int32_t evaluate_device(gorse_mf *h, const UserLists &L, int64_t n_counted, int32_t topk, float *sums, float *count, float *per_user,
+                        int32_t *rank_out, int32_t *rank_len) {
+    const int64_t n_users = L.n_users;
     h->mfe_users = n_counted;
-    h->mfe_cands = nc;
+    h->mfe_cands = L.n_cand;
     h->mfe_ms[0] = h->mfe_ms[1] = 0.0;
     if (n_users == 0) {
         for (int m = 0; m < kMetrics; m++) sums[m] = 0.0f;
@@ -257,42 +246,26 @@ int32_t evaluate_device(gorse_mf *h, int64_t n_users, int64_t n_counted, const i
         for (auto &e : h->mfe_ev) GORSE_HIP_CHECK(hipEventCreate(&e));
     }
     // stage scratch (shared with score / rank / recommend; nothing of it outlives the call): per_user | sums | rank | len
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_pu = carve((size_t)n_users * kMetrics * 4), o_sums = carve(kMetrics * 4),
-                 o_rank = carve(rank_out ? (size_t)n_users * topk * 4 : 0), o_len = carve(rank_len ? (size_t)n_users * 4 : 0);
-    GORSE_TRY(h->stage.ensure(off));
+    Carver sc;
+    const size_t o_pu = sc.take((size_t)n_users * kMetrics * 4), o_sums = sc.take(kMetrics * 4),
+                 o_rank = sc.take(rank_out ? (size_t)n_users * topk * 4 : 0), o_len = sc.take(rank_len ? (size_t)n_users * 4 : 0);
+    GORSE_TRY(h->stage.ensure(sc.off));
     char *base = h->stage.p;
     float *d_pu = (float *)(base + o_pu), *d_sums = (float *)(base + o_sums);
     MfEvalArgs A;
     A.P = h->P.p, A.Q = h->Q.p;
-    A.users = d_users, A.cand_ptr = d_cptr, A.cand = d_cand, A.tgt_ptr = d_tptr, A.tgt = d_tgt;
+    A.users = L.users, A.cand_ptr = L.cand_ptr, A.cand = L.cand, A.tgt_ptr = L.tgt_ptr, A.tgt = L.tgt;
     A.inv_log = h->mfe_tab.p, A.idcg = h->mfe_tab.p + kMaxK;
     A.per_user = d_pu;
     A.rank_out = rank_out ? (int32_t *)(base + o_rank) : nullptr;
     A.rank_len = rank_len ? (int32_t *)(base + o_len) : nullptr;
-    A.n_users = n_users, A.d = h->d, A.topk = topk, A.tgt_by_user = tgt_by_user;
+    A.n_users = n_users, A.d = h->d, A.topk = topk, A.tgt_by_user = L.tgt_by_user;
     const int d = h->d;
-    const int nc16 = (d % 16 == 0 && d <= 128) ? d / 16 : 0;
-    const size_t lds = (size_t)kGroupsPerBlock * group_floats(topk, d, nc16 == 0) * sizeof(float);
+    const size_t lds = (size_t)kGroupsPerBlock * group_floats(topk, d, !factor_row_in_registers(d)) * sizeof(float);
     if (lds > 64 * 1024) return fail(GORSE_ERR_INVALID, "evaluate: %zu bytes of LDS for nFactors %d, topk %d", lds, d, topk);
     const dim3 grid((unsigned)ceil_div(n_users, kGroupsPerBlock));
     GORSE_HIP_CHECK(hipEventRecord(h->mfe_ev[0], h->stream));
-    switch (nc16) {
-        case 1: launch_user<1>(A, grid, lds, h->stream); break;
-        case 2: launch_user<2>(A, grid, lds, h->stream); break;
-        case 3: launch_user<3>(A, grid, lds, h->stream); break;
-        case 4: launch_user<4>(A, grid, lds, h->stream); break;
-        case 5: launch_user<5>(A, grid, lds, h->stream); break;
-        case 6: launch_user<6>(A, grid, lds, h->stream); break;
-        case 7: launch_user<7>(A, grid, lds, h->stream); break;
-        case 8: launch_user<8>(A, grid, lds, h->stream); break;
-        default: launch_user<0>(A, grid, lds, h->stream); break;
-    }
+    with_factor_chunks(d, [&](auto nc) { mf_eval_user_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds, h->stream>>>(A); });
     GORSE_HIP_CHECK(hipGetLastError());
     GORSE_HIP_CHECK(hipEventRecord(h->mfe_ev[1], h->stream));
     mf_eval_chain_kernel<<<dim3(1), dim3(64), 0, h->stream>>>(d_pu, n_users, d_sums);
@@ -323,13 +296,13 @@ int32_t check_topk(int32_t topk) {
 extern "C" int32_t gorse_mf_evaluate_resident(gorse_mf *h, int32_t topk, float *sums, float *count, float *per_user,
                                               int32_t *rank_out, int32_t *rank_len) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
-    if (!h->ev_valid) return fail(GORSE_ERR_INVALID, "no resident candidate lists (gorse_mf_sample_user_negatives first)");
+    UserLists lists;
+    GORSE_TRY(resident_user_lists(h, &lists));
     GORSE_TRY(check_topk(topk));
     if (!sums || !count) return fail(GORSE_ERR_INVALID, "NULL argument");
     GORSE_TRY(h->use());
     GORSE_TRY(mf_sync_streams(h));
-    return evaluate_device(h, h->ev_users_n, h->ev_users_n, h->ev_users.p, h->ev_cptr.p, h->ev_cand.p, h->ev_cand_n, h->ev_tptr.p,
-                           h->ev_tidx.p, true, topk, sums, count, per_user, rank_out, rank_len);
+    return evaluate_device(h, lists, lists.n_users, topk, sums, count, per_user, rank_out, rank_len);
 }
 
 extern "C" int32_t gorse_mf_evaluate(gorse_mf *h, int64_t n_users, const int32_t *users, const int64_t *target_indptr,
@@ -339,42 +312,11 @@ extern "C" int32_t gorse_mf_evaluate(gorse_mf *h, int64_t n_users, const int32_t
     if (n_users < 0) return fail(GORSE_ERR_INVALID, "n_users < 0");
     GORSE_TRY(check_topk(topk));
     if (!sums || !count) return fail(GORSE_ERR_INVALID, "NULL argument");
-    if (n_users > 0 && (!users || !cand_indptr || !target_indptr)) return fail(GORSE_ERR_INVALID, "NULL argument");
-    const int64_t nc = n_users > 0 ? cand_indptr[n_users] : 0, nt = n_users > 0 ? target_indptr[n_users] : 0;
-    if (n_users > 0 && (cand_indptr[0] != 0 || nc < 0 || (nc > 0 && !cand))) return fail(GORSE_ERR_INVALID, "bad candidate CSR");
-    if (n_users > 0 && (target_indptr[0] != 0 || nt < 0 || (nt > 0 && !targets))) return fail(GORSE_ERR_INVALID, "bad target CSR");
+    if (n_users > 0 && !target_indptr) return fail(GORSE_ERR_INVALID, "NULL argument");
+    UserLists lists;
     int64_t counted = 0;
-    for (int64_t t = 0; t < n_users; t++) {
-        if (users[t] < 0 || users[t] >= h->U) return fail(GORSE_ERR_RANGE, "user %d out of range", users[t]);
-        if (cand_indptr[t + 1] < cand_indptr[t]) return fail(GORSE_ERR_INVALID, "cand_indptr not monotone");
-        if (target_indptr[t + 1] < target_indptr[t]) return fail(GORSE_ERR_INVALID, "target_indptr not monotone");
-        counted += target_indptr[t + 1] > target_indptr[t];
-    }
-    for (int64_t c = 0; c < nc; c++)
-        if (cand[c] < 0 || cand[c] >= h->I) return fail(GORSE_ERR_RANGE, "candidate %d out of range", cand[c]);
-    GORSE_TRY(h->use());
-    GORSE_TRY(mf_sync_streams(h));
-    if (n_users == 0) return evaluate_device(h, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, false, topk, sums, count, per_user, nullptr, nullptr);
-    // inputs to the device (their own buffer, as gorse_mf_rank's: the evaluation carves h->stage for its scratch)
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_cptr = carve((size_t)(n_users + 1) * 8), o_tptr = carve((size_t)(n_users + 1) * 8), o_users = carve((size_t)n_users * 4),
-                 o_cand = carve((size_t)std::max<int64_t>(nc, 1) * 4), o_tgt = carve((size_t)std::max<int64_t>(nt, 1) * 4);
-    GORSE_TRY(h->rank_in.ensure(off));
-    char *base = h->rank_in.p;
-    int64_t *d_cptr = (int64_t *)(base + o_cptr), *d_tptr = (int64_t *)(base + o_tptr);
-    int32_t *d_users = (int32_t *)(base + o_users), *d_cand = (int32_t *)(base + o_cand), *d_tgt = (int32_t *)(base + o_tgt);
-    GORSE_HIP_CHECK(hipMemcpyAsync(d_cptr, cand_indptr, (size_t)(n_users + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    GORSE_HIP_CHECK(hipMemcpyAsync(d_tptr, target_indptr, (size_t)(n_users + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    GORSE_HIP_CHECK(hipMemcpyAsync(d_users, users, (size_t)n_users * 4, hipMemcpyHostToDevice, h->stream));
-    if (nc > 0) GORSE_HIP_CHECK(hipMemcpyAsync(d_cand, cand, (size_t)nc * 4, hipMemcpyHostToDevice, h->stream));
-    if (nt > 0) GORSE_HIP_CHECK(hipMemcpyAsync(d_tgt, targets, (size_t)nt * 4, hipMemcpyHostToDevice, h->stream));
-    return evaluate_device(h, n_users, counted, d_users, d_cptr, d_cand, nc, d_tptr, d_tgt, false, topk, sums, count, per_user, nullptr,
-                           nullptr);
+    GORSE_TRY(upload_user_lists(h, n_users, users, cand_indptr, cand, target_indptr, targets, &lists, &counted));
+    return evaluate_device(h, lists, counted, topk, sums, count, per_user, nullptr, nullptr);
 }
 
 extern "C" int32_t gorse_mf_evaluate_stats(gorse_mf *h, int64_t *users, int64_t *candidates, double *device_ms) {

@@ -150,9 +150,28 @@ int32_t mf_epoch_harvest(gorse_mf *h, bool wait);
 int32_t mf_delta_export_async(gorse_mf *h, float *dst);        // mf.hip: dst <- Q - Q_sync, enqueued on h->stream
 int32_t mf_delta_import_async(gorse_mf *h, const float *src);  // mf.hip: Q <- Q_sync + src; Q_sync <- Q
 int32_t als_build_plan(gorse_mf *h, int side, const int64_t *ptr, int64_t rows, int64_t lo, int64_t hi);
-int32_t mf_score_device(gorse_mf *h, const int32_t *us, const int32_t *is, int64_t n, float *out);  // mf.hip: internalPredict, device pointers
-// mf.hip: Rank + TopKFilter for n_users users over candidate lists ALREADY on the device (nc entries in all); the rank lists go
-// to the host arrays (n_users * topk padded with -1, lengths), enqueued on h->stream -- the caller synchronises
-int32_t mf_rank_device(gorse_mf *h, int64_t n_users, const int32_t *d_users, const int64_t *d_cand_ptr, const int32_t *d_cand,
-                       int64_t nc, int32_t topk, int32_t *rank_out, int32_t *rank_len);
+int32_t mf_score_device(gorse_mf *h, const int32_t *us, const int32_t *is, int64_t n, float *out);  // mf_rank.hip: internalPredict, device pointers
+
+// Users' lists ON THE DEVICE, as Rank and Evaluate take them: n_users user ids, their candidate CSR (n_cand entries in all) and, for
+// an evaluation, the target rows -- row users[t] of the CSR (tgt_by_user) or row t.
+struct UserLists {
+    int64_t n_users = 0;
+    const int32_t *users = nullptr;
+    const int64_t *cand_ptr = nullptr;
+    const int32_t *cand = nullptr;
+    int64_t n_cand = 0;
+    const int64_t *tgt_ptr = nullptr;
+    const int32_t *tgt = nullptr;
+    bool tgt_by_user = false;
+};
+// mf_rank.hip: a caller's host lists, validated (ids in range, row pointers from 0 and monotone; the target CSR only when
+// target_indptr is given) and copied to h->rank_in behind everything enqueued on the handle; *n_counted (may be null) = users with
+// a target.  n_users == 0: empty lists.
+int32_t upload_user_lists(gorse_mf *h, int64_t n_users, const int32_t *users, const int64_t *cand_indptr, const int32_t *cand,
+                          const int64_t *target_indptr, const int32_t *targets, UserLists *lists, int64_t *n_counted);
+// mf_rank.hip: the lists gorse_mf_sample_user_negatives left on the handle (eval.hip), with its test split as the target rows
+int32_t resident_user_lists(gorse_mf *h, UserLists *lists);
+// mf_rank.hip: Rank + TopKFilter over the lists; the rank lists go to the host arrays (n_users * topk padded with -1, lengths),
+// enqueued on h->stream -- the caller synchronises
+int32_t mf_rank_device(gorse_mf *h, const UserLists &L, int32_t topk, int32_t *rank_out, int32_t *rank_len);
 }

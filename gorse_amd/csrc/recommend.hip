@@ -53,21 +53,9 @@ struct RecArgs {
     int32_t *nan_flag;  // nq
 };
 
-__device__ __forceinline__ bool row_has(const int32_t *__restrict__ row, int64_t n, int32_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t m = (lo + hi) >> 1;
-        if (row[m] < x)
-            lo = m + 1;
-        else
-            hi = m;
-    }
-    return lo < n && row[lo] == x;
-}
-
 __device__ __forceinline__ bool rec_candidate(const uint8_t *__restrict__ item_ok, const int32_t *trow, int64_t tn, const int32_t *srow,
                                               int64_t sn, int32_t item) {
-    return item_ok[item] != 0 && !row_has(trow, tn, item) && !(sn > 0 && row_has(srow, sn, item));
+    return item_ok[item] != 0 && !row_contains(trow, tn, item) && !(sn > 0 && row_contains(srow, sn, item));
 }
 
 // One 16-lane group: the kk best of cnt buffered entries to dst, sorted by score descending (equal scores in buffer order).  Every
@@ -290,15 +278,6 @@ __global__ __launch_bounds__(kBlock) void rec_candidates_kernel(const int32_t *_
     if (!cand && tid == 0) cnt_out[q] = base;
 }
 
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 // device time of what runs between begin() and end() on one stream, added up
 struct RecTimer {
     hipEvent_t a = nullptr, b = nullptr;
@@ -325,11 +304,6 @@ struct RecTimer {
         return GORSE_OK;
     }
 };
-
-template <int NC>
-void rec_launch(const RecArgs &A, dim3 grid, size_t lds, hipStream_t s) {
-    rec_fast_kernel<NC><<<grid, dim3(kBlock), lds, s>>>(A);
-}
 
 }  // namespace
 
@@ -456,8 +430,7 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
         A.slices = slices;
         A.slice_len = (int32_t)ceil_div(I, slices);
         A.tile_items = std::max(1, std::min({kRecTileFloats / d, kRecMaxTileItems, (int)A.slice_len}));
-        const bool regs = d % 16 == 0 && d <= 128;
-        const size_t lds_fast = ((size_t)A.tile_items * d + (regs ? 0 : (size_t)kGroupsPerBlock * d)) * sizeof(float);
+        const size_t lds_fast = ((size_t)A.tile_items * d + (factor_row_in_registers(d) ? 0 : (size_t)kGroupsPerBlock * d)) * sizeof(float);
         const size_t lds_fin = ((size_t)2 * slices * A.kk + (size_t)2 * A.kk) * 4;
         const size_t per_query = (size_t)slices * ((size_t)2 * A.cap * 8 + (size_t)A.kk * 8 + 4) + (size_t)k * 8 + 16;
         int64_t chunk = (int64_t)(kRecScratchBytes / per_query) / kGroupsPerBlock * kGroupsPerBlock;
@@ -486,17 +459,7 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
             GORSE_TRY(timer.begin(h->stream));
             GORSE_HIP_CHECK(hipMemsetAsync(A.nan_flag, 0, (size_t)nq * 4, h->stream));
             const dim3 grid((unsigned)ceil_div(nq, kGroupsPerBlock), (unsigned)slices);
-            if (!regs) rec_launch<0>(A, grid, lds_fast, h->stream);
-            else switch (d / 16) {
-                case 1: rec_launch<1>(A, grid, lds_fast, h->stream); break;
-                case 2: rec_launch<2>(A, grid, lds_fast, h->stream); break;
-                case 3: rec_launch<3>(A, grid, lds_fast, h->stream); break;
-                case 4: rec_launch<4>(A, grid, lds_fast, h->stream); break;
-                case 5: rec_launch<5>(A, grid, lds_fast, h->stream); break;
-                case 6: rec_launch<6>(A, grid, lds_fast, h->stream); break;
-                case 7: rec_launch<7>(A, grid, lds_fast, h->stream); break;
-                default: rec_launch<8>(A, grid, lds_fast, h->stream); break;
-            }
+            with_factor_chunks(d, [&](auto nc) { rec_fast_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds_fast, h->stream>>>(A); });
             GORSE_HIP_CHECK(hipGetLastError());
             rec_finish_kernel<<<dim3((unsigned)nq), dim3(kBlock), lds_fin, h->stream>>>(A, d_ri, d_rs, d_rc, d_lit);
             GORSE_HIP_CHECK(hipGetLastError());
@@ -562,7 +525,9 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
             rec_candidates_kernel<<<dim3((unsigned)(b - a)), dim3(kBlock), 0, h->stream>>>(d_lu + a, d_lq + a, h->uptr.p, h->uidx_sorted.p, d_sptr,
                                                                                           d_seen, d_ok, (int32_t)I, d_cp, d_cd, nullptr);
             GORSE_HIP_CHECK(hipGetLastError());
-            GORSE_TRY(mf_rank_device(h, b - a, d_lu + a, d_cp, d_cd, nc, k, rank.data() + a * k, rlen.data() + a));
+            UserLists lists;
+            lists.n_users = b - a, lists.users = d_lu + a, lists.cand_ptr = d_cp, lists.cand = d_cd, lists.n_cand = nc;
+            GORSE_TRY(mf_rank_device(h, lists, k, rank.data() + a * k, rlen.data() + a));
             GORSE_TRY(timer.end(h->stream));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
             a = b;

@@ -662,26 +662,19 @@ class MatrixFactorization {
         users.resize((size_t)nu);
         std::vector<int32_t> rank((size_t)nu * (size_t)topN), len((size_t)nu);
         if (nu > 0) check(gorse_mf_rank_resident(h_, topN, users.data(), rank.data(), len.data()));
-        std::vector<std::vector<int32_t>> out((size_t)nu);
-        for (size_t t = 0; t < (size_t)nu; t++)
-            out[t].assign(rank.begin() + (ptrdiff_t)(t * (size_t)topN), rank.begin() + (ptrdiff_t)(t * (size_t)topN) + len[t]);
-        return out;
+        return unflatten_ranks(rank, len, topN);
     }
 
     // Rank lists for Evaluate: user -> candidates, on the device (evaluator.go:162-169)
     std::vector<std::vector<int32_t>> RankMany(const std::vector<int32_t> &users,
                                                const std::vector<std::vector<int32_t>> &cands, int topN) {
         ensure_resident();
-        std::vector<int64_t> ptr(users.size() + 1, 0);
-        for (size_t t = 0; t < users.size(); t++) ptr[t + 1] = ptr[t] + (int64_t)cands[t].size();
-        std::vector<int32_t> flat((size_t)ptr.back());
-        for (size_t t = 0; t < users.size(); t++) std::copy(cands[t].begin(), cands[t].end(), flat.begin() + ptr[t]);
+        std::vector<int64_t> ptr;
+        std::vector<int32_t> flat;
+        flatten_rows(cands, ptr, flat);
         std::vector<int32_t> rank(users.size() * (size_t)topN), len(users.size());
         check(gorse_mf_rank(h_, (int64_t)users.size(), users.data(), ptr.data(), flat.data(), topN, rank.data(), len.data()));
-        std::vector<std::vector<int32_t>> out(users.size());
-        for (size_t t = 0; t < users.size(); t++)
-            out[t].assign(rank.begin() + (ptrdiff_t)(t * (size_t)topN), rank.begin() + (ptrdiff_t)(t * (size_t)topN) + len[t]);
-        return out;
+        return unflatten_ranks(rank, len, topN);
     }
 
     // Evaluate on the device (gorse_mf_evaluate_resident / gorse_mf_evaluate, csrc/mf_eval.hip): rank lists AND the six metrics
@@ -745,6 +738,13 @@ class MatrixFactorization {
         for (size_t t = 0; t < rows.size(); t++) ptr[t + 1] = ptr[t] + (int64_t)rows[t].size();
         flat.resize((size_t)ptr.back() + 1);  // (never empty: the C ABI wants a pointer)
         for (size_t t = 0; t < rows.size(); t++) std::copy(rows[t].begin(), rows[t].end(), flat.begin() + ptr[t]);
+    }
+    // the rank lists of the C ABI (len.size() rows of topN, row t holding len[t] ranks) as one vector per user
+    static std::vector<std::vector<int32_t>> unflatten_ranks(const std::vector<int32_t> &rank, const std::vector<int32_t> &len, int topN) {
+        std::vector<std::vector<int32_t>> out(len.size());
+        for (size_t t = 0; t < len.size(); t++)
+            out[t].assign(rank.begin() + (ptrdiff_t)(t * (size_t)topN), rank.begin() + (ptrdiff_t)(t * (size_t)topN) + len[t]);
+        return out;
     }
     // the shared evaluate / early-stopping epoch loop of BPR.Fit and ALS.Fit (model.go:432-440, 496-518)
     Score fit_loop(const char *tag, int nEpochs, dataset::Dataset &trainSet, dataset::Dataset &valSet, const FitConfig &config,

@@ -63,6 +63,24 @@ def test_score_bit_exact_at_wide_factors(oracle, small, d):
     mf.close()
 
 
+@pytest.mark.parametrize("d", [48, 80, 96, 112, 128, 144])
+def test_score_bit_exact_at_every_register_chunk_count(oracle, small, d):
+    """mf_score_kernel<3 | 5 | 6 | 7> (nFactors 48, 80, 96, 112: the register form for every multiple of 16 up to 128, the widths
+    with_factor_chunks sends there besides 16, 32, 64, 128) and either side of the edge: 112 and 128 in registers, 144 = nine
+    chunks staged in LDS.  Bit-equal to floats.Dot in the reference's AVX512 order, unknown users and items scoring 0."""
+    mf, P, Q = make_mf(small, d)
+    rng = np.random.default_rng(2)
+    u = rng.integers(0, small.U, 5000).astype(np.int32)
+    i = rng.integers(0, small.I, 5000).astype(np.int32)
+    u[:3] = -1
+    i[3:5] = -1
+    got = mf.score(u, i)
+    exp = oracle.mf_score(P, Q, u, i)
+    assert np.array_equal(bits(got), bits(exp))
+    assert (got[:5] == 0).all() and (got[5:] != 0).any()
+    mf.close()
+
+
 @pytest.mark.parametrize("d", [200, 16])
 def test_rank_topk_past_the_list_and_an_empty_list(oracle, small, d):
     """mf_rank_kernel where the heap never fills (topk 100 > every candidate list: rank_len = the list's length, the row padded

@@ -88,7 +88,8 @@ def general_lists():
     return np.asarray(users, np.int32), targets, cands
 
 
-@pytest.mark.parametrize("d", [8, 16, 24, 64, 128, 129, 200])
+# every form of the width dispatch (cf_device.hpp with_factor_chunks): 16 .. 128 in registers, the others staged in LDS
+@pytest.mark.parametrize("d", [8, 16, 24, 32, 48, 64, 80, 96, 112, 128, 129, 200])
 def test_per_user_metrics_and_sums_equal_the_host_route(d):
     users, targets, cands = general_lists()
     P, Q = synth.init_factors(40, N_ITEMS, d, 0.0, 0.5, 100 + d)
