@@ -200,6 +200,12 @@ SIGNATURES = {
     "gorse_hip_test_fm_evaluate_times": (C.c_int32, [_vp, _f64p]),
     "gorse_hip_test_mf_evaluate_times": (C.c_int32, [_vp, _f64p]),
     "gorse_hip_test_mf_evaluate_tables": (C.c_int32, [_f32p, _f32p, C.c_int32]),
+    "gorse_nbr_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64]),
+    "gorse_nbr_destroy": (C.c_int32, [_vp]),
+    "gorse_nbr_set_table": (C.c_int32, [_vp, C.c_int32, C.c_int64, _i64p, _i32p, _f32p, C.c_int32, C.c_double]),
+    "gorse_nbr_recommend": (C.c_int32, [_vp, C.c_int64, _i32p, C.c_int32, _i64p, _i32p, _i32p, _f64p, _i32p]),
+    "gorse_nbr_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
+    "gorse_hip_test_set_nbr": (None, [C.c_int32, C.c_int64]),
 }
 
 
@@ -1081,6 +1087,73 @@ class Sparse:
         out = (C.c_int64 * 4)()
         lib().gorse_hip_test_sparse_path_stats(self.h, out)
         return tuple(int(x) for x in out)
+
+
+NBR_HOP1, NBR_HOP2 = 0, 1
+NBR_RAW, NBR_RECIP = 0, 1
+NBR_MAX_K = 256  # GORSE_NBR_MAX_K
+
+
+def set_nbr(lds_slots=0, query_chunk=0):
+    """gorse_hip_test_set_nbr: slots of the largest LDS table and queries per launch of the calls that follow (0 = the library's)"""
+    lib().gorse_hip_test_set_nbr(int(lds_slots), int(query_chunk))
+
+
+class NbrRecommender:
+    """One gorse_nbr handle: the two neighbour tables of an item-to-item or user-to-user recommender resident on one GPU."""
+
+    def __init__(self, n_items, device=0):
+        self.n_items = int(n_items)
+        self.h = _vp()
+        check(lib().gorse_nbr_create(C.byref(self.h), device, self.n_items))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gorse_nbr_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_table(self, which, indptr, indices, weights=None, transform=NBR_RAW, scale=1.0):
+        """a CSR of len(indptr) - 1 rows; weights = None: every weight is 1.0"""
+        ip, ix = _arr(indptr, np.int64), _arr(indices, np.int32)
+        w = _arr(weights, np.float32) if weights is not None else None
+        if ip.size < 1 or (w is not None and w.size != ix.size):
+            raise GorseHipError(ERR_INVALID, "indptr must have n_rows + 1 entries and weights one per index")
+        if ix.size == 0:
+            ix = np.zeros(1, np.int32)
+            w = np.zeros(1, np.float32) if w is not None else None
+        check(lib().gorse_nbr_set_table(self.h, which, ip.size - 1, _p(ip, _i64p), _p(ix, _i32p), _p(w, _f32p), transform, scale))
+
+    def recommend(self, rows, k, seen_indptr=None, seen_items=None, out=None):
+        """every query's k best candidates (gorse_nbr_recommend): (items n x k padded with -1, float64 sums n x k padded with 0,
+        counts n).  rows = an int n: the first n hop-1 rows; seen rows are per QUERY.  out = the three arrays to fill."""
+        if isinstance(rows, (int, np.integer)):
+            n, rp = int(rows), None
+        else:
+            rp = _arr(rows, np.int32)
+            n = rp.size
+        sp = _arr(seen_indptr, np.int64) if seen_indptr is not None else None
+        if sp is not None and sp.size != n + 1:
+            raise GorseHipError(ERR_INVALID, "seen_indptr must have n_queries + 1 entries")
+        si = _arr(seen_items, np.int32) if seen_items is not None else None
+        if si is not None and si.size == 0:
+            si = np.zeros(1, np.int32)
+        kk = max(int(k), 0)
+        if out is None:
+            out = (np.full((n, kk), -2, np.int32), np.full((n, kk), np.nan, np.float64), np.full(n, -2, np.int32))
+        items, sums, counts = out
+        assert items.dtype == np.int32 and sums.dtype == np.float64 and counts.dtype == np.int32
+        assert items.size >= n * kk and sums.size >= n * kk and counts.size >= n
+        check(lib().gorse_nbr_recommend(self.h, n, _p(rp, _i32p), k, _p(sp, _i64p), _p(si, _i32p), _p(items, _i32p), _p(sums, _f64p),
+                                        _p(counts, _i32p)))
+        return items, sums, counts
+
+    def recommend_stats(self):
+        """the last recommend(): (queries answered over an LDS table, over a table in global scratch, device milliseconds)"""
+        nl, ng, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        check(lib().gorse_nbr_recommend_stats(self.h, C.byref(nl), C.byref(ng), C.byref(ms)))
+        return nl.value, ng.value, ms.value
 
 
 # gorse_hip_test_sgemm_last_form (include/gorse_hip_test.h, GORSE_TEST_SGEMM_*)

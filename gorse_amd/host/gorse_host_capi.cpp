@@ -884,6 +884,53 @@ int32_t gh_logics_cf_recommend_unseen(void *h, const char *collection, const flo
                                       const char *excludes, int32_t cache_size) {
     return guard([&] { stage_scores(logics::CollaborativeRecommendUnseen(vdb(h), collection, parse_user_queries(Q, n_users, d, excludes), cache_size)); });
 }
+// The neighbourhood recommenders (logics::ItemToItemRecommend / UserToUserRecommend and their Bulk forms).  Lists of lists travel as
+// '\n'-joined ids per record, records separated by '\x1e'.  user_to_user = 0: positives = one record per user; user_to_user = 1:
+// user_ids = one id per user, feedback_users / feedback_items = the data store's positive feedback (one record per feedback user).
+namespace {
+std::vector<std::vector<std::string>> split_records(const char *s) {
+    std::vector<std::vector<std::string>> out;
+    std::string cur;
+    for (const char *p = s ? s : "";; p++) {
+        if (*p == '\x1e' || *p == 0) {
+            out.push_back(split_lines(cur.c_str()));
+            cur.clear();
+            if (*p == 0) break;
+        } else {
+            cur.push_back(*p);
+        }
+    }
+    return out;
+}
+}  // namespace
+int32_t gh_logics_nbr_recommend(void *h, int32_t user_to_user, int32_t bulk, const char *collection, const char *type, int64_t n_users,
+                                const char *user_ids, const char *positives, const char *excludes, const char *feedback_users,
+                                const char *feedback_items, const char *categories, int32_t cache_size) {
+    return guard([&] {
+        std::vector<logics::NbrUser> users((size_t)n_users);
+        const auto ids = split_lines(user_ids);
+        const auto pos = split_records(positives), exc = split_records(excludes), fbi = split_records(feedback_items);
+        for (size_t t = 0; t < users.size(); t++) {
+            if (t < ids.size()) users[t].Id = ids[t];
+            if (t < pos.size()) users[t].Positives = pos[t];
+            if (t < exc.size()) users[t].Exclude = exc[t];
+        }
+        logics::FeedbackMap feedback;
+        const auto fbu = split_lines(feedback_users);
+        for (size_t r = 0; r < fbu.size(); r++) feedback[fbu[r]] = r < fbi.size() ? fbi[r] : std::vector<std::string>();
+        const auto cats = split_lines(categories);
+        if (bulk) {
+            stage_scores(user_to_user ? logics::UserToUserRecommendBulk(vdb(h), collection, type, users, feedback, cache_size)
+                                      : logics::ItemToItemRecommendBulk(vdb(h), collection, type, users, cats, cache_size));
+            return;
+        }
+        std::vector<std::vector<logics::Score>> res;
+        for (const auto &u : users)
+            res.push_back(user_to_user ? logics::UserToUserRecommend(vdb(h), collection, type, u, feedback, cache_size)
+                                       : logics::ItemToItemRecommend(vdb(h), collection, type, u, cats, cache_size));
+        stage_scores(res);
+    });
+}
 // master/tasks.go:925-969: items of model `m` into collaborative_filtering_<model_id> of database `h`, users into a new
 // MatrixFactorizationUsers (returned; free with gh_mfusers_free).  hidden: one byte per item or NULL; categories: one
 // '\n'-joined list per item, items separated by '\x1e', or NULL

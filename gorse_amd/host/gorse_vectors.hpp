@@ -848,6 +848,227 @@ inline std::vector<std::vector<Score>> CollaborativeRecommendUnseen(vectors::Hip
     return out;
 }
 
+// ---- the neighbourhood recommenders: recommendItemToItem and recommendUserToUser (logics/recommend.go:244-283, :285-316) ----------
+// Both add, per user, the scores of the lists that QueryItemToItem / QueryUserToUser return into a map, drop the exclude set and keep
+// TopKFilter(CacheSize).  The reference pushes the map in Go's map iteration order and so pins nothing among equal sums (its own
+// test uses ElementsMatch, recommend_test.go:391-394); the order here is gorse_nbr_recommend's: larger sum first, equal sums by
+// ascending id, a NaN sum last.  The data-store filter that follows in recommendUserToUser (:317-345: hidden items, ItemTTL,
+// categories) stays the caller's.
+struct NbrUser {
+    std::string Id;                      // user-to-user: the user whose neighbours are asked for
+    std::vector<std::string> Positives;  // item-to-item: the user's positive feedback, newest first (recommend.go:250-259)
+    std::vector<std::string> Exclude;    // r.excludeSet
+};
+using FeedbackMap = std::map<std::string, std::vector<std::string>>;  // user id -> GetUserFeedback's item ids, in stored order
+
+inline std::vector<Score> nbr_top(const std::map<std::string, double> &scores, const std::map<std::string, std::vector<std::string>> &cats,
+                                  int cacheSize) {
+    std::vector<Score> all;
+    for (const auto &kv : scores) {  // ascending id: the stable sort keeps it among equal sums
+        Score s;
+        s.Id = kv.first;
+        s.Value = kv.second;
+        auto it = cats.find(kv.first);
+        if (it != cats.end()) s.Categories = it->second;
+        all.push_back(std::move(s));
+    }
+    std::stable_sort(all.begin(), all.end(), [](const Score &a, const Score &b) {
+        const bool an = std::isnan(a.Value), bn = std::isnan(b.Value);
+        return an != bn ? bn : (!an && a.Value > b.Value);
+    });
+    if ((int)all.size() > cacheSize) all.resize((size_t)std::max(cacheSize, 0));
+    return all;
+}
+inline bool nbr_excluded(const NbrUser &u, const std::string &id) { return std::find(u.Exclude.begin(), u.Exclude.end(), id) != u.Exclude.end(); }
+
+// recommend.go:260-281 for one user: one QueryItemToItem per positive feedback
+inline std::vector<Score> ItemToItemRecommend(vectors::HipDatabase &client, const std::string &collection, const std::string &type,
+                                              const NbrUser &u, const std::vector<std::string> &categories, int cacheSize) {
+    std::map<std::string, double> scores;
+    std::map<std::string, std::vector<std::string>> cats;
+    for (const std::string &item : u.Positives)
+        for (const Score &nb : QuerySimilarTyped(client, collection, type, item, categories, cacheSize))
+            if (!nbr_excluded(u, nb.Id)) {
+                scores[nb.Id] += nb.Value;
+                cats[nb.Id] = nb.Categories;
+            }
+    return nbr_top(scores, cats, cacheSize);
+}
+// recommend.go:291-316 for one user: QueryUserToUser, then every similar user's positive feedback
+inline std::vector<Score> UserToUserRecommend(vectors::HipDatabase &client, const std::string &collection, const std::string &type,
+                                              const NbrUser &u, const FeedbackMap &feedback, int cacheSize) {
+    std::map<std::string, double> scores;
+    for (const Score &user : QuerySimilarTyped(client, collection, type, u.Id, {}, cacheSize)) {
+        auto it = feedback.find(user.Id);
+        if (it == feedback.end()) continue;
+        for (const std::string &item : it->second)
+            if (!nbr_excluded(u, item)) scores[item] += user.Value;
+    }
+    return nbr_top(scores, {}, cacheSize);
+}
+
+// The lists of QuerySimilarBulk / QuerySimilarTypedBulk with the vector database's own float32 score instead of the cache score
+// (gorse_nbr_recommend turns it into the cache score on the device): the loop of item_to_item.go:72-86 without its arithmetic.
+inline std::vector<std::vector<vectors::ScoredVector>> similar_raw_bulk(vectors::HipDatabase &client, const std::string &collection,
+                                                                       const std::string &type, const std::vector<std::string> &ids,
+                                                                       const std::vector<std::string> &categories, int n) {
+    std::vector<std::vector<vectors::ScoredVector>> out(ids.size());
+    std::vector<vectors::Vector> sparse;
+    std::vector<float> dense;
+    std::vector<size_t> which;
+    for (size_t t = 0; t < ids.size(); t++) {
+        auto v = client.GetVectors(collection, {ids[t]});
+        if (v.empty()) continue;
+        if (type == "embedding")
+            dense.insert(dense.end(), v[0].Values.begin(), v[0].Values.end());
+        else
+            sparse.push_back(std::move(v[0]));
+        which.push_back(t);
+    }
+    if (which.empty()) return out;
+    auto res = type == "embedding" ? client.QueryVectorsBatch(collection, dense, (int64_t)which.size(), categories, n + 1)
+                                   : client.QuerySparseBatch(collection, sparse, categories, n + 1);
+    for (size_t r = 0; r < which.size(); r++)
+        for (auto &nb : res[r]) {
+            if (nb.Id == ids[which[r]] || (type != "embedding" && nb.Score <= 0)) continue;
+            out[which[r]].push_back(std::move(nb));
+            if ((int)out[which[r]].size() == n) break;
+        }
+    return out;
+}
+
+namespace nbr_detail {
+struct Csr {
+    std::vector<int64_t> ptr{0};
+    std::vector<int32_t> idx;
+    std::vector<float> w;
+    void close_row() { ptr.push_back((int64_t)idx.size()); }
+};
+inline std::vector<std::string> sorted_unique(std::vector<std::string> v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+inline int32_t index_of(const std::vector<std::string> &sorted, const std::string &id) {  // -1: absent
+    auto it = std::lower_bound(sorted.begin(), sorted.end(), id);
+    return it != sorted.end() && *it == id ? (int32_t)(it - sorted.begin()) : -1;
+}
+// one gorse_nbr_recommend for all users: items are numbered in ascending id order, so that the call's tie order is the per-user one
+inline std::vector<std::vector<Score>> run(const std::vector<NbrUser> &users, const std::vector<std::string> &items, Csr &hop1, Csr &hop2,
+                                           const std::string &type, bool hop2_weighted,
+                                           const std::map<std::string, std::vector<std::string>> &cats, int cacheSize, int device) {
+    std::vector<std::vector<Score>> out(users.size());
+    if (users.empty() || items.empty() || cacheSize <= 0) return out;
+    if (cacheSize > GORSE_NBR_MAX_K) throw std::invalid_argument("the bulk neighbourhood recommenders serve CacheSize <= 256");
+    Csr seen;
+    for (const NbrUser &u : users) {
+        for (const std::string &id : u.Exclude) {
+            const int32_t j = index_of(items, id);
+            if (j >= 0) seen.idx.push_back(j);
+        }
+        seen.close_row();
+    }
+    for (Csr *c : {&hop1, &hop2, &seen})
+        if (c->idx.empty()) c->idx.push_back(0), c->w.push_back(0.0f);
+    struct Handle {
+        gorse_nbr *h = nullptr;
+        ~Handle() {
+            if (h) gorse_nbr_destroy(h);
+        }
+    } nb;
+    auto check = [](int32_t rc) {
+        if (rc != GORSE_OK) throw std::runtime_error(gorse_hip_last_error());
+    };
+    const int32_t transform = type == "embedding" ? GORSE_NBR_RECIP : GORSE_NBR_RAW;
+    const double scale = type == "auto" ? .5 : 1.0;
+    check(gorse_nbr_create(&nb.h, device, (int64_t)items.size()));
+    check(gorse_nbr_set_table(nb.h, GORSE_NBR_HOP1, (int64_t)hop1.ptr.size() - 1, hop1.ptr.data(), hop1.idx.data(),
+                              hop2_weighted ? nullptr : hop1.w.data(), transform, scale));
+    check(gorse_nbr_set_table(nb.h, GORSE_NBR_HOP2, (int64_t)hop2.ptr.size() - 1, hop2.ptr.data(), hop2.idx.data(),
+                              hop2_weighted ? hop2.w.data() : nullptr, transform, scale));
+    const int64_t n = (int64_t)users.size();
+    std::vector<int32_t> got((size_t)n * (size_t)cacheSize), count((size_t)n);
+    std::vector<double> sums((size_t)n * (size_t)cacheSize);
+    check(gorse_nbr_recommend(nb.h, n, nullptr, cacheSize, seen.ptr.data(), seen.idx.data(), got.data(), sums.data(), count.data()));
+    for (int64_t t = 0; t < n; t++)
+        for (int32_t e = 0; e < count[(size_t)t]; e++) {
+            Score s;
+            s.Id = items[(size_t)got[(size_t)(t * cacheSize + e)]];
+            s.Value = sums[(size_t)(t * cacheSize + e)];
+            auto it = cats.find(s.Id);
+            if (it != cats.end()) s.Categories = it->second;
+            out[(size_t)t].push_back(std::move(s));
+        }
+    return out;
+}
+}  // namespace nbr_detail
+
+// ItemToItemRecommend for many users: ONE bulk search for the neighbour lists of every distinct positive item, one
+// gorse_nbr_recommend for all users (hop 1 = the users' positives, hop 2 = the lists).  List for list and bit for bit the per-user call.
+inline std::vector<std::vector<Score>> ItemToItemRecommendBulk(vectors::HipDatabase &client, const std::string &collection,
+                                                               const std::string &type, const std::vector<NbrUser> &users,
+                                                               const std::vector<std::string> &categories, int cacheSize, int device = 0) {
+    using namespace nbr_detail;
+    std::vector<std::string> sources;
+    for (const NbrUser &u : users) sources.insert(sources.end(), u.Positives.begin(), u.Positives.end());
+    sources = sorted_unique(std::move(sources));
+    const auto lists = similar_raw_bulk(client, collection, type, sources, categories, cacheSize);
+    std::vector<std::string> items;
+    std::map<std::string, std::vector<std::string>> cats;
+    for (const auto &l : lists)
+        for (const auto &nb : l) {
+            items.push_back(nb.Id);
+            cats[nb.Id] = nb.Categories;
+        }
+    items = sorted_unique(std::move(items));
+    Csr hop1, hop2;
+    for (const auto &l : lists) {
+        for (const auto &nb : l) {
+            hop2.idx.push_back(index_of(items, nb.Id));
+            hop2.w.push_back(nb.Score);
+        }
+        hop2.close_row();
+    }
+    for (const NbrUser &u : users) {
+        for (const std::string &id : u.Positives) hop1.idx.push_back(index_of(sources, id));
+        hop1.close_row();
+    }
+    return run(users, items, hop1, hop2, type, true, cats, cacheSize, device);
+}
+
+// UserToUserRecommend for many users: ONE bulk search for every user's neighbours, one gorse_nbr_recommend (hop 1 = the neighbour
+// lists, hop 2 = the neighbours' feedback rows).
+inline std::vector<std::vector<Score>> UserToUserRecommendBulk(vectors::HipDatabase &client, const std::string &collection,
+                                                               const std::string &type, const std::vector<NbrUser> &users,
+                                                               const FeedbackMap &feedback, int cacheSize, int device = 0) {
+    using namespace nbr_detail;
+    std::vector<std::string> ids;
+    for (const NbrUser &u : users) ids.push_back(u.Id);
+    const auto lists = similar_raw_bulk(client, collection, type, ids, {}, cacheSize);
+    std::vector<std::string> neighbours, items;
+    for (const auto &l : lists)
+        for (const auto &nb : l)
+            if (feedback.count(nb.Id)) neighbours.push_back(nb.Id);
+    neighbours = sorted_unique(std::move(neighbours));
+    for (const std::string &nb : neighbours) items.insert(items.end(), feedback.at(nb).begin(), feedback.at(nb).end());
+    items = sorted_unique(std::move(items));
+    Csr hop1, hop2;
+    for (const std::string &nb : neighbours) {
+        for (const std::string &item : feedback.at(nb)) hop2.idx.push_back(index_of(items, item));
+        hop2.close_row();
+    }
+    for (const auto &l : lists) {
+        for (const auto &nb : l) {
+            const int32_t r = index_of(neighbours, nb.Id);
+            if (r < 0) continue;  // a neighbour without feedback adds nothing
+            hop1.idx.push_back(r);
+            hop1.w.push_back(nb.Score);
+        }
+        hop1.close_row();
+    }
+    return run(users, items, hop1, hop2, type, false, {}, cacheSize, device);
+}
+
 // MatrixFactorizationUsers (logics/cf.go:122-179): user id -> embedding, and its blob: WriteGob(int64 count), then per
 // user WriteString(id) (little-endian int32 length + bytes) + WriteSlice(embedding) (int32 length + little-endian float32s).
 // The reference iterates a Go map (any order); here ids go out sorted.

@@ -439,6 +439,43 @@ def CollaborativeRecommendUnseen(client, collection, embeddings, excludes, cache
     return [flat[cuts[t]:cuts[t + 1]] for t in range(Q.shape[0])]
 
 
+def _nbr_recommend(client, user_to_user, bulk, collection, kind, user_ids, positives, excludes, feedback, categories, cache_size):
+    H = _logics_host()
+    H.gh_logics_nbr_recommend.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64] + [C.c_char_p] * 6 + [C.c_int32]
+    n = len(user_ids) if user_to_user else len(positives)
+    rec = lambda lists: "\x1e".join("\n".join(map(str, e)) for e in lists).encode()  # noqa: E731
+    fb_users = list(feedback or {})
+    _ck(H.gh_logics_nbr_recommend(client.h, user_to_user, bulk, collection.encode(), kind.encode(), n, "\n".join(map(str, user_ids)).encode(),
+                                  rec(positives), rec(excludes or [[]] * n), "\n".join(fb_users).encode(),
+                                  rec([feedback[u] for u in fb_users]), "\n".join(categories or []).encode(), cache_size))
+    flat = _scores()
+    cuts = [int(H.gh_vdb_result_split(t)) for t in range(n + 1)]
+    return [flat[cuts[t]:cuts[t + 1]] for t in range(n)]
+
+
+def ItemToItemRecommend(client, collection, kind, positives, exclude, categories, cache_size):
+    """recommendItemToItem (logics/recommend.go:244-283) for one user: positives = the user's positive feedback, newest first; one
+    QueryItemToItem each, the scores added per item, the exclude set dropped, the cache_size best (larger sum first, equal sums by
+    ascending id)"""
+    return _nbr_recommend(client, 0, 0, collection, kind, [], [positives], [exclude], None, categories, cache_size)[0]
+
+
+def UserToUserRecommend(client, collection, kind, user_id, exclude, feedback, cache_size):
+    """recommendUserToUser (logics/recommend.go:285-316) for one user: feedback = {user id: positive item ids in stored order}; the
+    data-store filter of :317-345 stays the caller's"""
+    return _nbr_recommend(client, 1, 0, collection, kind, [user_id], [], [exclude], feedback, None, cache_size)[0]
+
+
+def ItemToItemRecommendBulk(client, collection, kind, positives, excludes, categories, cache_size):
+    """ItemToItemRecommend for many users: one bulk search for the neighbour lists, one gorse_nbr_recommend for all users"""
+    return _nbr_recommend(client, 0, 1, collection, kind, [], positives, excludes, None, categories, cache_size)
+
+
+def UserToUserRecommendBulk(client, collection, kind, user_ids, excludes, feedback, cache_size):
+    """UserToUserRecommend for many users: one bulk search for the neighbour lists, one gorse_nbr_recommend for all users"""
+    return _nbr_recommend(client, 1, 1, collection, kind, user_ids, [], excludes, feedback, None, cache_size)
+
+
 class MatrixFactorizationItems:
     """logics.MatrixFactorizationItems (logics/cf.go:36-128): item id -> embedding, nearest items by -dot on the exact index, and
     its blob: reads the reference's HNSW-based stream (keeping the vectors and ids) and this library's own versioned framing,

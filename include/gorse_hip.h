@@ -623,6 +623,56 @@ int32_t gorse_fm_set_test_samples(gorse_fm *h, int64_t n_users, const int64_t *u
                                   const int32_t *user_lead /*host, n_users, or NULL*/, int64_t n, const int32_t *user /*host, n*/,
                                   const int32_t *item /*host, n*/, const float *target /*host, n*/);
 
+/* ---- neighbourhood recommenders (logics/recommend.go:244-348) --------------------------
+ * recommendItemToItem and recommendUserToUser for many users at once.  Both are a two-hop weighted walk over two tables the handle
+ * holds on the device:
+ *     item-to-item: hop 1 = the user's positive feedback, newest first, unweighted; hop 2 = each item's neighbour list, weighted
+ *     user-to-user: hop 1 = the user's neighbour list, weighted;                   hop 2 = each neighbour's positive feedback, unweighted
+ * which: GORSE_NBR_HOP1 or GORSE_NBR_HOP2.  A table is a CSR of n_rows rows: indices[] and, when weights != NULL, one float32
+ * raw similarity per entry.  The entry's weight as a double is
+ *     w = (double)raw * scale;   if (transform == GORSE_NBR_RECIP) w = 1.0 / (1.0 - w);        (item_to_item.go:64-87, user_to_user.go:63-80)
+ * weights == NULL: every w is exactly 1.0 (transform and scale ignored).  Hop-1 indices name hop-2 rows, hop-2 indices items of
+ * [0, n_items).  gorse_nbr_set_table on a slot replaces the previous table.  indptr[0] != 0, a decreasing indptr, a non-finite raw
+ * weight or scale, a weighted hop-2 table that repeats an index inside one row: GORSE_ERR_INVALID (an unweighted table may repeat,
+ * as feedback rows do, and so may a weighted hop-1 table: those are successive lists); a negative index or a hop-2 index outside
+ * [0, n_items): GORSE_ERR_RANGE.  An error leaves the previous table in place. */
+#define GORSE_NBR_HOP1 0
+#define GORSE_NBR_HOP2 1
+#define GORSE_NBR_RAW 0
+#define GORSE_NBR_RECIP 1
+#define GORSE_NBR_MAX_K 256
+typedef struct gorse_nbr gorse_nbr; /* one pair of neighbour tables resident on one GPU */
+int32_t gorse_nbr_create(gorse_nbr **h, int32_t device, int64_t n_items);
+int32_t gorse_nbr_destroy(gorse_nbr *h);
+int32_t gorse_nbr_set_table(gorse_nbr *h, int32_t which, int64_t n_rows, const int64_t *indptr /*host, n_rows+1*/,
+                            const int32_t *indices /*host*/, const float *weights /*host or NULL*/, int32_t transform, double scale);
+/* For query t with hop-1 row r = rows[t] (rows == NULL: r = t, and n_queries must not exceed the hop-1 rows) the sum of item j is
+ * formed exactly as the reference forms scores[id] += score (recommend.go:268-272, :334-339): s_j starts absent; for each position p
+ * of row r in stored order, with entry (src, w1), and for each position q of hop-2 row src in stored order, with entry (j, w2):
+ *     s_j = (s_j absent ? 0.0 : s_j) + w1 * w2
+ * in IEEE double, the product a separate multiply, never fused.  (One of w1 and w2 is 1.0 in both of the reference's uses, so the
+ * product is exact there; the general case is defined as written.)
+ * An item is a candidate when it was reached at least once and is not in seen_items[seen_indptr[t] .. seen_indptr[t + 1])
+ * (seen_indptr == NULL: no such rows; a row may be unsorted, repeat an item and name items that are never reached).  A sum of zero
+ * or below is still a candidate.  The result row holds the min(k, candidates) candidates that come first in the total order:
+ * larger sum first, equal sums (-0 == +0) by ascending item index, a NaN sum after every number (NaN sums among themselves by
+ * ascending item index).  The reference pushes its map into TopKFilter in Go's map iteration order and so pins nothing among equal
+ * sums (its own test uses ElementsMatch, logics/recommend_test.go:391-394); this call fixes the order.
+ * items_out is n_queries * k padded with -1, scores_out n_queries * k padded with 0 and holds the sums' bits, count_out[t] =
+ * min(k, candidates); each may be NULL.  rows[t] < 0 gives count 0.
+ * GORSE_ERR_RANGE: a hop-1 index outside the hop-2 table's rows, a seen item outside [0, n_items), rows[t] beyond the hop-1 table.
+ * GORSE_ERR_INVALID: k outside 1 .. GORSE_NBR_MAX_K, a table that is not set, a malformed seen_indptr.  Everything is validated
+ * before anything is launched, and an error leaves the outputs untouched.
+ * A query whose accumulator (the items it can reach, at most n_items, plus its seen row) fits an open-addressing table in LDS is
+ * answered there; the others by the same code over a table in global scratch sized by that bound. */
+int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const int32_t *rows /*host, hop-1 row per query, or NULL: rows[t] = t*/,
+                            int32_t k, const int64_t *seen_indptr /*host, n_queries+1, or NULL*/, const int32_t *seen_items /*host*/,
+                            int32_t *items_out /*host or NULL, n_queries*k, padded with -1*/,
+                            double *scores_out /*host or NULL, n_queries*k, padded with 0*/, int32_t *count_out /*host or NULL*/);
+/* the handle's last gorse_nbr_recommend: queries answered over an LDS table (queries with rows[t] < 0 are counted here) / over a
+ * table in global scratch, and the device time of its launches (hipEvents around them, copies excluded) */
+int32_t gorse_nbr_recommend_stats(gorse_nbr *h, int64_t *n_lds, int64_t *n_global, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,10 @@ int32_t gorse_hip_test_mf_evaluate_times(gorse_mf *h, double *ms2 /*host*/);
 /* the two tables the evaluation kernel reads, filled as the library fills them (no device needed): inv_log[i] = 1 / log2f(i + 2)
  * for i < n, idcg[k] = inv_log[0] + ... + inv_log[k - 1] for k <= n (n + 1 entries); n <= GORSE_MF_EVAL_MAX_TOPK */
 int32_t gorse_hip_test_mf_evaluate_tables(float *inv_log /*host, n*/, float *idcg /*host, n + 1*/, int32_t n);
+/* gorse_nbr_recommend (csrc/nbr_recommend.hip), calls AFTERWARDS: lds_slots > 0 = slots of the largest LDS table (at most the
+ * library's 13056; a query takes the LDS path when its bound + 1 fits), so that small inputs reach the global path; query_chunk > 0 =
+ * queries per launch at most, so that they run the launch loop.  0 restores the library's choice.  Results never depend on them. */
+void gorse_hip_test_set_nbr(int32_t lds_slots, int64_t query_chunk);
 
 #ifdef __cplusplus
 }
