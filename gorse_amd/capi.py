@@ -205,6 +205,10 @@ SIGNATURES = {
     "gorse_nbr_set_table": (C.c_int32, [_vp, C.c_int32, C.c_int64, _i64p, _i32p, _f32p, C.c_int32, C.c_double]),
     "gorse_nbr_recommend": (C.c_int32, [_vp, C.c_int64, _i32p, C.c_int32, _i64p, _i32p, _i32p, _f64p, _i32p]),
     "gorse_nbr_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
+    "gorse_nbr_set_table_from_topk": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _i64p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    "gorse_nbr_set_table_from_sparse": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _i64p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    "gorse_nbr_table_info": (C.c_int32, [_vp, C.c_int32, _i64p, _i64p, _i32p]),
+    "gorse_nbr_get_table": (C.c_int32, [_vp, C.c_int32, _i64p, _i32p, _f32p]),
     "gorse_hip_test_set_nbr": (None, [C.c_int32, C.c_int64]),
 }
 
@@ -1124,6 +1128,41 @@ class NbrRecommender:
             ix = np.zeros(1, np.int32)
             w = np.zeros(1, np.float32) if w is not None else None
         check(lib().gorse_nbr_set_table(self.h, which, ip.size - 1, _p(ip, _i64p), _p(ix, _i32p), _p(w, _f32p), transform, scale))
+
+    def _set_table_from(self, fn, which, index, sources, n_rows, n, positive_only, transform, scale):
+        src = _arr(sources, np.int64) if sources is not None else None
+        if src is not None:
+            n_rows = src.size
+            if src.size == 0:
+                src = np.zeros(1, np.int64)
+        check(fn(self.h, which, getattr(index, "h", index), int(n_rows), _p(src, _i64p), int(n), int(bool(positive_only)), transform, scale))
+
+    def set_table_from_topk(self, which, index, n, sources=None, n_rows=None, positive_only=False, transform=NBR_RAW, scale=1.0):
+        """the neighbour lists of a TopK index's rows, built on the device (gorse_nbr_set_table_from_topk): row r = the list of
+        stored row sources[r] (None: the index's first n_rows rows, all of them by default)"""
+        if sources is None and n_rows is None:
+            n_rows = index.N
+        self._set_table_from(lib().gorse_nbr_set_table_from_topk, which, index, sources, n_rows, n, positive_only, transform, scale)
+
+    def set_table_from_sparse(self, which, index, n, sources=None, n_rows=None, positive_only=False, transform=NBR_RAW, scale=1.0):
+        """the same from a Sparse index (gorse_nbr_set_table_from_sparse)"""
+        if sources is None and n_rows is None:
+            n_rows = index.N
+        self._set_table_from(lib().gorse_nbr_set_table_from_sparse, which, index, sources, n_rows, n, positive_only, transform, scale)
+
+    def table_info(self, which):
+        """(rows, entries, weighted) of the table a slot holds (gorse_nbr_table_info)"""
+        nr, nz, w = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(lib().gorse_nbr_table_info(self.h, which, C.byref(nr), C.byref(nz), C.byref(w)))
+        return nr.value, nz.value, bool(w.value)
+
+    def get_table(self, which):
+        """(indptr, indices, weights or None) of the table a slot holds, host-built or device-built (gorse_nbr_get_table)"""
+        nr, nz, weighted = self.table_info(which)
+        ip, ix = np.zeros(nr + 1, np.int64), np.zeros(max(nz, 1), np.int32)
+        w = np.zeros(max(nz, 1), np.float32) if weighted else None
+        check(lib().gorse_nbr_get_table(self.h, which, _p(ip, _i64p), _p(ix, _i32p), _p(w, _f32p)))
+        return ip, ix[:nz], (w[:nz] if weighted else None)
 
     def recommend(self, rows, k, seen_indptr=None, seen_items=None, out=None):
         """every query's k best candidates (gorse_nbr_recommend): (items n x k padded with -1, float64 sums n x k padded with 0,

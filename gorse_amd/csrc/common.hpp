@@ -65,6 +65,7 @@ struct DevBuf {
         if (count == 0) count = 1;
         hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
         if (e != hipSuccess) {
+            (void)hipGetLastError();  // reported here: the next launch's hipGetLastError must not find it
             p = nullptr;
             return fail(GORSE_ERR_NOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
         }

@@ -1,7 +1,8 @@
 // nbr_plan.hpp -- the host side of gorse_nbr_recommend that needs no device: validation of a neighbour table and of a call's
 // arguments, the per-row and per-query bounds on the accumulator's entries, and the launch plan that sorts the queries into
-// LDS-table classes and the global-table path and cuts each into launches.  No HIP in here: tests/cpp/nbr_plan_main.cpp runs it
-// under AddressSanitizer and UBSan without a device.
+// LDS-table classes and the global-table path and cuts each into launches; the validation of gorse_nbr_set_table_from_topk /
+// _from_sparse's arguments.  No HIP in here: tests/cpp/nbr_plan_main.cpp and tests/cpp/nbr_build_main.cpp run it under
+// AddressSanitizer and UBSan without a device.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -62,6 +63,30 @@ inline int32_t validate_table(int32_t which, int64_t n_rows, const int64_t *indp
         }
     }
     if (max_index) *max_index = mx;
+    return GORSE_OK;
+}
+
+// The arguments of gorse_nbr_set_table_from_topk / _from_sparse against the index's rows (index_n) and the handle's n_items.
+// The valid sources, in row order, go to `rows` (the table row) and `src` (the stored row searched): a source < 0 is an empty row.
+inline int32_t validate_from_search(int32_t which, int64_t n_rows, const int64_t *sources, int32_t n, int32_t transform, double scale,
+                                    int64_t index_n, int64_t n_items, std::vector<int64_t> *rows, std::vector<int64_t> *src,
+                                    std::string *msg) {
+    if (which != GORSE_NBR_HOP1 && which != GORSE_NBR_HOP2) return *msg = fmt("which = %lld is neither hop", which), GORSE_ERR_INVALID;
+    if (n_rows < 0 || n_rows > INT32_MAX) return *msg = fmt("n_rows = %lld", n_rows), GORSE_ERR_INVALID;
+    if (n < 1 || n > GORSE_NBR_MAX_LIST) return *msg = fmt("n = %lld outside 1 .. %lld", n, GORSE_NBR_MAX_LIST), GORSE_ERR_INVALID;
+    if (!std::isfinite(scale)) return *msg = "scale is not finite", GORSE_ERR_INVALID;
+    if (transform != GORSE_NBR_RAW && transform != GORSE_NBR_RECIP) return *msg = fmt("transform = %lld", transform), GORSE_ERR_INVALID;
+    if (which == GORSE_NBR_HOP2 && index_n > n_items)
+        return *msg = fmt("the index has %lld rows, the handle %lld items", index_n, n_items), GORSE_ERR_RANGE;
+    if (!sources && n_rows > index_n) return *msg = fmt("sources is NULL and n_rows %lld > %lld index rows", n_rows, index_n), GORSE_ERR_RANGE;
+    rows->clear(), src->clear();
+    for (int64_t r = 0; r < n_rows; r++) {
+        const int64_t s = sources ? sources[r] : r;
+        if (s >= index_n) return *msg = fmt("sources[%lld] = %lld beyond the index's %lld rows", r, s, index_n), GORSE_ERR_RANGE;
+        if (s < 0) continue;
+        rows->push_back(r);
+        src->push_back(s);
+    }
     return GORSE_OK;
 }
 

@@ -16,7 +16,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "nbr_internal.hpp"
 #include "nbr_plan.hpp"
 
 using namespace gorse;
@@ -285,35 +285,7 @@ __global__ __launch_bounds__(T) void nbr_walk_kernel(const NbrArgs A) {
     if (tid == 0) A.out_cnt[t] = m;
 }
 
-struct NbrTable {
-    bool set = false, weighted = false;
-    int64_t n_rows = 0, nnz = 0, max_index = -1;
-    int32_t transform = GORSE_NBR_RAW;
-    double scale = 1.0;
-    std::vector<int64_t> ptr;  // host copies: the bounds are one pass over hop 1's indices and hop 2's row pointer
-    std::vector<int32_t> idx;
-    DevBuf<int64_t> d_ptr;
-    DevBuf<int32_t> d_idx;
-    DevBuf<float> d_w;
-};
-
 }  // namespace
-
-struct gorse_nbr {
-    int device = 0;
-    int64_t n_items = 0;
-    hipStream_t stream = nullptr;
-    NbrTable tab[2];
-    std::vector<int64_t> src_sum;  // per hop-1 row, valid while bounds_valid
-    bool bounds_valid = false;
-    DevBuf<char> in, out, scratch;
-    int64_t n_lds = 0, n_global = 0;
-    double ms = 0.0;
-    int32_t use() {
-        GORSE_HIP_CHECK(hipSetDevice(device));
-        return GORSE_OK;
-    }
-};
 
 extern "C" void gorse_hip_test_set_nbr(int32_t lds_slots, int64_t query_chunk) {
     g_nbr_lds_slots = lds_slots > 0 ? std::min(lds_slots, nbr::kMaxLdsSlots) : 0;
@@ -381,6 +353,7 @@ extern "C" int32_t gorse_nbr_set_table(gorse_nbr *h, int32_t which, int64_t n_ro
     T.max_index = max_index;
     T.transform = weights ? transform : GORSE_NBR_RAW;
     T.scale = weights ? scale : 1.0;
+    T.on_device_only = false;
     T.ptr.assign(indptr, indptr + n_rows + 1);
     if (which == GORSE_NBR_HOP1)
         T.idx.assign(indices, indices + nnz);
@@ -429,7 +402,10 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
     h->ms = 0.0;
     if (n_queries == 0) return GORSE_OK;
     if (!h->bounds_valid) {
-        nbr::row_bounds(T1.n_rows, T1.ptr.data(), T1.idx.data(), T2.ptr.data(), &h->src_sum);
+        if (T1.on_device_only)  // its indices never crossed to the host: the same sums, formed where they lie
+            GORSE_TRY(nbr_device_row_bounds(h, &h->src_sum));
+        else
+            nbr::row_bounds(T1.n_rows, T1.ptr.data(), T1.idx.data(), T2.ptr.data(), &h->src_sum);
         h->bounds_valid = true;
     }
     const bool has_seen = seen_indptr && seen_indptr[n_queries] > seen_indptr[0];

@@ -718,6 +718,28 @@ extern "C" int32_t gorse_sparse_all_pairs(gorse_sparse *h, int64_t q_begin, int6
                        exclude_self != 0, k, atomic_ok(h->stored_small, h->stored_small), idx_out, score_out, count_out);
 }
 
+namespace gorse {
+namespace sparse {
+
+int64_t index_rows(const gorse_sparse *h) { return h->N; }
+int index_device(const gorse_sparse *h) { return h->device; }
+
+// A covering range of stored rows, self included: the stored CSR already holds the queries as directory entries, so nothing is
+// uploaded or translated (gorse_nbr_set_table_from_sparse keeps the rows it asked for).
+int32_t search_stored_rows(gorse_sparse *h, int64_t q_begin, int64_t q_end, int k, StoredRowsResult *out) {
+    if (q_begin < 0 || q_end > h->N || q_begin >= q_end || k <= 0) return fail(GORSE_ERR_RANGE, "bad query range");
+    GORSE_TRY(h->use());
+    GORSE_TRY(run_queries(h, h->r_ptr.p, h->r_cid.p, h->r_val.p, q_begin, q_end - q_begin, h->r_ptr_host.data() + q_begin, nullptr, 0, k,
+                          atomic_ok(h->stored_small, h->stored_small), nullptr, nullptr, nullptr));
+    out->idx = h->out_idx.p, out->score = h->out_score.p, out->cnt = h->out_cnt.p;
+    out->stream = (void *)h->stream;
+    out->device = h->device;
+    return GORSE_OK;
+}
+
+}  // namespace sparse
+}  // namespace gorse
+
 extern "C" int32_t gorse_sparse_synchronize(gorse_sparse *h) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     GORSE_TRY(h->use());

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+struct gorse_sparse;
+
 namespace gorse {
 namespace sparse {
 
@@ -103,6 +105,20 @@ inline int pick_kp(int k) {
         if (k <= kp) return kp;
     return 0;
 }
+
+// sparse.hip: the stored rows [q_begin, q_end) as queries, the row itself NOT excluded, under the current mask -- what
+// gorse_sparse_search returns for those rows' vectors with exclude == NULL.  The results stay on the device: row q - q_begin of
+// idx / score (stride k) and cnt, the handle's buffers, complete when the call returns and valid until the handle's next search.
+struct StoredRowsResult {
+    const int32_t *idx = nullptr;
+    const float *score = nullptr;
+    const int32_t *cnt = nullptr;
+    void *stream = nullptr;  // the handle's hipStream_t
+    int device = 0;
+};
+int64_t index_rows(const ::gorse_sparse *h);
+int index_device(const ::gorse_sparse *h);
+int32_t search_stored_rows(::gorse_sparse *h, int64_t q_begin, int64_t q_end, int k, StoredRowsResult *out);
 
 }  // namespace sparse
 }  // namespace gorse

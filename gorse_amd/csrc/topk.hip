@@ -262,7 +262,7 @@ namespace gorse {
 
 // queries already on the device in h->qbuf (nq x d, fp32) [+ h->qnorm]; qidx_dev = exclude list or null
 int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, const int64_t *qidx_host, int k, int prune0,
-                        int32_t *idx_out, float *dist_out, int32_t *cnt_out, bool reroute) {
+                        int32_t *idx_out, float *dist_out, int32_t *cnt_out, bool reroute, bool keep_on_device) {
     const int d = h->d;
     GORSE_TRY(h->dist.ensure((size_t)nq * h->N));
     GORSE_TRY(h->heap_v.ensure((size_t)nq * 2 * (k + 1)));
@@ -331,6 +331,15 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
     }
     std::vector<int32_t> ti(nf * (size_t)k), tc(nf);
     std::vector<float> td(nf * (size_t)k);
+    std::vector<int32_t> bi, bc;  // keep_on_device: the block as the selection left it -- the replay may scan again over h->out_*
+    std::vector<float> bd;
+    if (keep_on_device) {
+        bi.resize((size_t)nq * k), bd.resize((size_t)nq * k), bc.resize((size_t)nq);
+        GORSE_HIP_CHECK(hipMemcpyAsync(bi.data(), h->out_idx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(bd.data(), h->out_dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(bc.data(), h->out_cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+        GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
     const int64_t keep_fallback = h->n_fallback;
     GORSE_TRY(topk_mfma_search(h, qidx_host ? ids.data() : nullptr, -1, qidx_host ? nullptr : qf.p, (int64_t)nf, k, prune0, ti.data(),
                                td.data(), tc.data()));
@@ -343,6 +352,49 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
         if (idx_out) memcpy(idx_out + t * k, ti.data() + r * k, (size_t)k * 4);
         if (dist_out) memcpy(dist_out + t * k, td.data() + r * k, (size_t)k * 4);
         if (cnt_out) cnt_out[t] = tc[r];
+        if (keep_on_device) {
+            memcpy(bi.data() + t * k, ti.data() + r * k, (size_t)k * 4);
+            memcpy(bd.data() + t * k, td.data() + r * k, (size_t)k * 4);
+            bc[(size_t)t] = tc[r];
+        }
+    }
+    if (keep_on_device) {
+        GORSE_TRY(h->out_idx.ensure((size_t)nq * k));
+        GORSE_TRY(h->out_dist.ensure((size_t)nq * k));
+        GORSE_TRY(h->out_cnt.ensure((size_t)nq));
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->out_idx.p, bi.data(), (size_t)nq * k * 4, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->out_dist.p, bd.data(), (size_t)nq * k * 4, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->out_cnt.p, bc.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+    return GORSE_OK;
+}
+
+int32_t topk_search_stored(gorse_topk *h, const int64_t *src_host, int64_t nq, int k, TopkBlockConsumer *consumer) {
+    if (nq <= 0) return GORSE_OK;
+    GORSE_TRY(h->use());
+    h->n_fallback = 0;
+    h->scan_last_nq = 0;
+    const int d = h->d;
+    const bool mfma = topk_mfma_usable(h, nq, k);
+    const int64_t bq = mfma ? nq : std::min(topk_scan_block_queries(h), nq);  // path B takes its query vectors all at once
+    GORSE_TRY(h->qidx.ensure((size_t)bq));
+    DevBuf<float> &Q = mfma ? h->qf32 : h->qbuf;
+    GORSE_TRY(Q.ensure((size_t)bq * d));
+    GORSE_TRY(h->qnorm.ensure((size_t)bq));
+    for (int64_t q0 = 0; q0 < nq; q0 += bq) {
+        const int64_t m = std::min(bq, nq - q0);
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->qidx.p, src_host + q0, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+        gather_rows_kernel<<<dim3((unsigned)m), dim3(64), 0, h->stream>>>(h->X.p, nullptr, h->qidx.p, d, Q.p, nullptr);
+        GORSE_HIP_CHECK(hipGetLastError());
+        if (mfma) {
+            GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));  // src_host is the caller's
+            return topk_mfma_search(h, nullptr, -1, Q.p, nq, k, 0, nullptr, nullptr, nullptr, consumer);
+        }
+        if (h->metric == GORSE_METRIC_COSINE) GORSE_TRY(topk_compute_norms(h, Q.p, m, h->qnorm.p));
+        GORSE_TRY(topk_scan_block(h, m, nullptr, nullptr, k, 0, nullptr, nullptr, nullptr, true, /*keep_on_device=*/true));
+        GORSE_TRY(consumer->block(q0, m, h->out_idx.p, h->out_dist.p, h->out_cnt.p, h->stream));
+        // (the next block's selection writes h->out_* on the same stream, behind what the consumer launched)
     }
     return GORSE_OK;
 }

@@ -162,21 +162,38 @@ __device__ __forceinline__ float euclid_any_lds(int metric, const float *a, cons
     return metric == kMetricEuclidBf16 ? euclid_bf16_lds<true>(a, b, vs.d, lane) : euclid512_lds<true>(a, b, vs, lane);
 }
 
+// Whoever takes a search's results where they lie: after each finished block (a chunk of the MFMA path, a block of the scan) the
+// search hands over the block's device result arrays (m rows of stride k, and m counts) instead of copying them out.  q0 = the
+// block's first query in the call's list.  The arrays are the handle's and are overwritten by the next block: what block() launches
+// goes on `stream`, the search's own.
+struct TopkBlockConsumer {
+    virtual int32_t block(int64_t q0, int64_t m, const int32_t *idx, const float *dist, const int32_t *cnt, hipStream_t stream) = 0;
+
+protected:
+    ~TopkBlockConsumer() = default;
+};
+
 // topk.hip
 int32_t topk_compute_norms(gorse_topk *h, const float *V, int64_t n, float *out);
+// Stored rows src_host[0 .. nq) as query VECTORS (the row itself is not excluded, as gorse_topk_search_vector does not exclude it),
+// prune0 = 0, under the current mask: the same search as the public call on those rows' vectors, gathered on the device from the
+// index's fp32 image, every block's results handed to `consumer`.
+int32_t topk_search_stored(gorse_topk *h, const int64_t *src_host, int64_t nq, int k, TopkBlockConsumer *consumer);
 // path A on queries whose fp32 rows sit in h->qbuf (nq x d) [+ h->qnorm]; qidx_dev = exclusion ids or null (qidx_host: the same
 // ids on the host).  Results land in h->out_idx / out_dist / out_cnt and, where given, in the host arrays.  Queries whose answer
 // depends on the heap's history (ties among the k + 1 smallest distances, NaN) go to the MFMA path's tie replay where that is
 // usable and `reroute` allows it, else to the literal heap kernel.
 int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, const int64_t *qidx_host, int k, int prune0,
-                        int32_t *idx_out, float *dist_out, int32_t *cnt_out, bool reroute = true);
+                        int32_t *idx_out, float *dist_out, int32_t *cnt_out, bool reroute = true, bool keep_on_device = false);
+// keep_on_device: the rows a reroute answered are written back, so that h->out_* hold the whole block when the call returns
 int64_t topk_scan_block_queries(const gorse_topk *h);
 // topk_mfma.hip
 int32_t topk_mfma_prepare(gorse_topk *h);  // at create: operands, scales, error bound
 // Queries: stored vectors qid_host[0..nq) (exclude_self) or, when qid_host is NULL and qv_dev is given, nq fp32
 // query vectors already on the device.  Host outputs may be NULL.
 int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_contig_begin, const float *qv_dev,
-                         int64_t nq, int k, int prune0, int32_t *idx_out, float *dist_out, int32_t *cnt_out);
+                         int64_t nq, int k, int prune0, int32_t *idx_out, float *dist_out, int32_t *cnt_out,
+                         TopkBlockConsumer *consumer = nullptr);
 bool topk_mfma_usable(const gorse_topk *h, int64_t nq, int k);
 void topk_mfma_release(gorse_topk *h);  // at destroy: the search state
 extern int g_topk_variant;     // OR of the GORSE_TEST_TOPK_* switches (include/gorse_hip_test.h): every read names one; 0 in the product

@@ -2646,7 +2646,8 @@ int32_t chunk_finish(gorse_topk *h, ChunkState &cs) {
 namespace gorse {
 
 int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_contig_begin, const float *qv_dev,
-                         int64_t nq, int k, int prune0, int32_t *idx_out, float *dist_out, int32_t *cnt_out) {
+                         int64_t nq, int k, int prune0, int32_t *idx_out, float *dist_out, int32_t *cnt_out,
+                         TopkBlockConsumer *consumer) {
     ChunkState &cs = *h->chunk_state();
     GORSE_TRY(search_setup(h, cs, qid_host, q_contig_begin, qv_dev, nq, k, prune0));
     for (int64_t c0 = 0; c0 < nq; c0 += kChunkQ) {
@@ -2666,6 +2667,7 @@ int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_conti
         // of their own would cost one workgroup a full pass over the rows (48 ms for 86 queries, profiles/r02_h_*).
         h->prof.end(tok, h->stream);
         GORSE_TRY(chunk_finish(h, cs));
+        if (consumer) GORSE_TRY(consumer->block(c0, m, h->res_idx.p, h->res_dist.p, h->res_cnt.p, h->stream));
         if (idx_out)
             GORSE_HIP_CHECK(hipMemcpyAsync(idx_out + c0 * k, h->res_idx.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, h->stream));
         if (dist_out)

@@ -931,6 +931,21 @@ int32_t gh_logics_nbr_recommend(void *h, int32_t user_to_user, int32_t bulk, con
         stage_scores(res);
     });
 }
+// HipDatabase::SetNbrTableFromIndex: slot `which` of the gorse_nbr handle `nbr` from the collection's resident index; the row
+// numbering (ids in row order) is staged like a query's results
+int32_t gh_vdb_set_nbr_table_from_index(void *h, const char *collection, void *nbr, int32_t which, const char *type, const char *categories,
+                                        int32_t n) {
+    return guard([&] {
+        const auto ids = vdb(h).SetNbrTableFromIndex(collection, (gorse_nbr *)nbr, which, type, split_lines(categories), n);
+        g_stage.clear();
+        g_stage_split.clear();
+        for (const std::string &id : ids) {
+            vectors::ScoredVector v;
+            v.Id = id;
+            g_stage.push_back(std::move(v));
+        }
+    });
+}
 // master/tasks.go:925-969: items of model `m` into collaborative_filtering_<model_id> of database `h`, users into a new
 // MatrixFactorizationUsers (returned; free with gh_mfusers_free).  hidden: one byte per item or NULL; categories: one
 // '\n'-joined list per item, items separated by '\x1e', or NULL

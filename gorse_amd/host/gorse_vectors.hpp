@@ -89,6 +89,8 @@ struct Searcher {
                                int32_t *, float *, int32_t *) {
         return false;
     }
+    // the collection's index resident on the device, built when it is not there yet; NULL = this searcher keeps none
+    virtual gorse_topk *resident(const std::string &, const float *, int64_t, int, int) { return nullptr; }
 };
 
 // One gorse_topk handle per collection, rebuilt lazily after a change (like BruteforceHIP.sync in INTEGRATION.md).
@@ -105,8 +107,7 @@ public:
             handles_.erase(it);
         }
     }
-    void search(const std::string &collection, const float *X, int64_t n, int d, int metric, const float *Q, int64_t nq,
-                int k, int32_t *idx, float *dist, int32_t *cnt) override {
+    gorse_topk *resident(const std::string &collection, const float *X, int64_t n, int d, int metric) override {
         gorse_topk *&h = handles_[collection];
         if (!h) {
             if (gorse_topk_create(&h, device_, n, d, GORSE_DTYPE_F32, metric, X) != GORSE_OK) {
@@ -114,6 +115,11 @@ public:
                 throw std::runtime_error(std::string("gorse_topk_create: ") + gorse_hip_last_error());
             }
         }
+        return h;
+    }
+    void search(const std::string &collection, const float *X, int64_t n, int d, int metric, const float *Q, int64_t nq,
+                int k, int32_t *idx, float *dist, int32_t *cnt) override {
+        gorse_topk *h = resident(collection, X, n, d, metric);
         // one call for all queries: >= 768 of them run on the MFMA path of the library, fewer on its scan
         if (gorse_topk_search_vector(h, Q, nq, k, 0, idx, dist, cnt) != GORSE_OK)
             throw std::runtime_error(std::string("gorse_topk_search_vector: ") + gorse_hip_last_error());
@@ -121,13 +127,7 @@ public:
     // the filter as a device mask (gorse_topk_set_mask): the sweep never sees an inadmissible row, k stays topK
     bool search_masked(const std::string &collection, const float *X, int64_t n, int d, int metric, const uint8_t *admissible,
                        const float *Q, int64_t nq, int k, int32_t *idx, float *dist, int32_t *cnt) override {
-        gorse_topk *&h = handles_[collection];
-        if (!h) {
-            if (gorse_topk_create(&h, device_, n, d, GORSE_DTYPE_F32, metric, X) != GORSE_OK) {
-                handles_.erase(collection);
-                throw std::runtime_error(std::string("gorse_topk_create: ") + gorse_hip_last_error());
-            }
-        }
+        gorse_topk *h = resident(collection, X, n, d, metric);
         if (gorse_topk_set_mask(h, admissible) != GORSE_OK)
             throw std::runtime_error(std::string("gorse_topk_set_mask: ") + gorse_hip_last_error());
         const int32_t rc = gorse_topk_search_vector(h, Q, nq, k, 0, idx, dist, cnt);
@@ -150,6 +150,8 @@ struct SparseSearcher {
                         const float *values, const uint8_t *admissible, int64_t nq, const int64_t *q_indptr,
                         const uint32_t *q_indices, const float *q_values, int k, int32_t *idx, float *score,
                         int32_t *cnt) = 0;
+    // the collection's index resident on the device, built when it is not there yet; NULL = this searcher keeps none
+    virtual gorse_sparse *resident(const std::string &, int64_t, const int64_t *, const uint32_t *, const float *) { return nullptr; }
 };
 
 class HipSparseSearcher : public SparseSearcher {  // one gorse_sparse handle per collection, rebuilt after a change
@@ -165,9 +167,8 @@ public:
             handles_.erase(it);
         }
     }
-    void search(const std::string &collection, int64_t n, const int64_t *indptr, const uint32_t *indices, const float *values,
-                const uint8_t *admissible, int64_t nq, const int64_t *q_indptr, const uint32_t *q_indices,
-                const float *q_values, int k, int32_t *idx, float *score, int32_t *cnt) override {
+    gorse_sparse *resident(const std::string &collection, int64_t n, const int64_t *indptr, const uint32_t *indices,
+                           const float *values) override {
         gorse_sparse *&h = handles_[collection];
         if (!h) {
             if (gorse_sparse_create(&h, device_, n, indptr, indices, values) != GORSE_OK) {
@@ -175,6 +176,12 @@ public:
                 throw std::runtime_error(std::string("gorse_sparse_create: ") + gorse_hip_last_error());
             }
         }
+        return h;
+    }
+    void search(const std::string &collection, int64_t n, const int64_t *indptr, const uint32_t *indices, const float *values,
+                const uint8_t *admissible, int64_t nq, const int64_t *q_indptr, const uint32_t *q_indices,
+                const float *q_values, int k, int32_t *idx, float *score, int32_t *cnt) override {
+        gorse_sparse *h = resident(collection, n, indptr, indices, values);
         if (gorse_sparse_set_mask(h, admissible) != GORSE_OK)
             throw std::runtime_error(std::string("gorse_sparse_set_mask: ") + gorse_hip_last_error());
         if (gorse_sparse_search(h, nq, q_indptr, q_indices, q_values, nullptr, k, idx, score, cnt) != GORSE_OK)
@@ -335,16 +342,7 @@ public:
         }
         const int64_t n = (int64_t)c.rows.size();
         if (n == 0) return out;
-        if (!c.csr_valid) {
-            c.indptr.assign(1, 0);
-            c.indices.clear();
-            c.values.clear();
-            for (const Vector &v : c.rows) {
-                append_sorted(v, c.indices, c.values);
-                c.indptr.push_back((int64_t)c.indices.size());
-            }
-            c.csr_valid = true;
-        }
+        ensure_csr(c);
         std::vector<uint8_t> ok((size_t)n);
         for (int64_t r = 0; r < n; r++) ok[(size_t)r] = admissible(c.rows[(size_t)r], categories);
         const int64_t nq = (int64_t)queries.size();
@@ -497,6 +495,51 @@ public:
         return out;
     }
 
+    // One slot of a gorse_nbr handle filled from the collection's RESIDENT index, on the device (gorse_nbr_set_table_from_topk /
+    // _from_sparse): row r of the table is the list QueryItemToItem / QueryUserToUser (logics::similar_scores) form for the
+    // collection's row r with n entries at most, under the hidden / categories mask; its indices are collection rows.  type
+    // "embedding" = a dense collection, the weight 1 / (1 - score); any other type = a sparse one, scores <= 0 skipped, "auto"
+    // halved.  Returns the row numbering: the ids in row order.  gorse_nbr_recommend breaks equal sums by ascending row, so a
+    // collection filled in ascending id order keeps the per-user calls' tie order.  The lists never cross to the host.
+    std::vector<std::string> SetNbrTableFromIndex(const std::string &name, gorse_nbr *nbr, int32_t which, const std::string &type,
+                                                  const std::vector<std::string> &categories, int n) {
+        std::lock_guard<std::mutex> g(mu_);
+        Collection &c = coll(name);
+        const bool dense = type == "embedding";
+        if (dense != (c.info.Dimension != 0))
+            throw std::invalid_argument("type " + type + " against the " + (c.info.Dimension ? "dense" : "sparse") + " collection " + name);
+        const int64_t rows = (int64_t)c.rows.size();
+        if (rows == 0) throw std::invalid_argument("collection " + name + " is empty");
+        std::vector<std::string> ids((size_t)rows);
+        std::vector<uint8_t> ok((size_t)rows);
+        bool filtered = false;
+        for (int64_t r = 0; r < rows; r++) {
+            ids[(size_t)r] = c.rows[(size_t)r].Id;
+            ok[(size_t)r] = admissible(c.rows[(size_t)r], categories);
+            filtered = filtered || !ok[(size_t)r];
+        }
+        auto check = [](int32_t rc) {
+            if (rc != GORSE_OK) throw std::runtime_error(gorse_hip_last_error());
+        };
+        if (dense) {
+            const int metric = c.info.Dist == Dot ? GORSE_METRIC_NEG_DOT : (c.info.Dist == Euclidean ? GORSE_METRIC_EUCLIDEAN : GORSE_METRIC_COSINE);
+            gorse_topk *h = searcher_->resident(name, c.data.data(), rows, c.info.Dimension, metric);
+            if (!h) throw storage::ErrNotSupported("the searcher of " + name + " keeps no index on the device");
+            check(gorse_topk_set_mask(h, filtered ? ok.data() : nullptr));
+            const int32_t rc = gorse_nbr_set_table_from_topk(nbr, which, h, rows, nullptr, n, 0, GORSE_NBR_RECIP, 1.0);
+            const std::string why = rc != GORSE_OK ? gorse_hip_last_error() : "";
+            (void)gorse_topk_set_mask(h, nullptr);
+            if (rc != GORSE_OK) throw std::runtime_error(why);
+        } else {
+            ensure_csr(c);
+            gorse_sparse *h = sparse_->resident(name, rows, c.indptr.data(), c.indices.data(), c.values.data());
+            if (!h) throw storage::ErrNotSupported("the searcher of " + name + " keeps no index on the device");
+            check(gorse_sparse_set_mask(h, ok.data()));
+            check(gorse_nbr_set_table_from_sparse(nbr, which, h, rows, nullptr, n, 1, GORSE_NBR_RAW, type == "auto" ? .5 : 1.0));
+        }
+        return ids;
+    }
+
 private:
     struct Collection {
         CollectionInfo info;
@@ -525,6 +568,17 @@ private:
             indices.push_back(v.Indices[t]);
             values.push_back(v.Values[t]);
         }
+    }
+    static void ensure_csr(Collection &c) {
+        if (c.csr_valid) return;
+        c.indptr.assign(1, 0);
+        c.indices.clear();
+        c.values.clear();
+        for (const Vector &v : c.rows) {
+            append_sorted(v, c.indices, c.values);
+            c.indptr.push_back((int64_t)c.indices.size());
+        }
+        c.csr_valid = true;
     }
     void drop_index(const std::string &name) {
         searcher_->invalidate(name);

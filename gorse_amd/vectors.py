@@ -476,6 +476,16 @@ def UserToUserRecommendBulk(client, collection, kind, user_ids, excludes, feedba
     return _nbr_recommend(client, 1, 1, collection, kind, user_ids, [], excludes, feedback, None, cache_size)
 
 
+def SetNbrTableFromIndex(client, collection, kind, nbr, which, categories, n):
+    """One slot of a capi.NbrRecommender filled on the device from the collection's resident index (HipDatabase::SetNbrTableFromIndex):
+    row r = the QueryItemToItem / QueryUserToUser list of the collection's row r, n entries at most, under the hidden / categories
+    mask, its indices collection rows.  Returns the row numbering: the ids in row order."""
+    H = _logics_host()
+    H.gh_vdb_set_nbr_table_from_index.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32]
+    _ck(H.gh_vdb_set_nbr_table_from_index(client.h, collection.encode(), nbr.h, which, kind.encode(), "\n".join(categories or []).encode(), n))
+    return [v.Id for v in Database._results(False)]
+
+
 class MatrixFactorizationItems:
     """logics.MatrixFactorizationItems (logics/cf.go:36-128): item id -> embedding, nearest items by -dot on the exact index, and
     its blob: reads the reference's HNSW-based stream (keeping the vectors and ids) and this library's own versioned framing,

@@ -672,6 +672,32 @@ int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const int32_t *rows
 /* the handle's last gorse_nbr_recommend: queries answered over an LDS table (queries with rows[t] < 0 are counted here) / over a
  * table in global scratch, and the device time of its launches (hipEvents around them, copies excluded) */
 int32_t gorse_nbr_recommend_stats(gorse_nbr *h, int64_t *n_lds, int64_t *n_global, double *device_ms);
+/* A neighbour table built on the device from a similarity search's device-resident results: what QueryItemToItem / QueryUserToUser
+ * (item_to_item.go:72-86, user_to_user.go:63-80) make of a search, for every row at once, without the lists crossing to the host.
+ * Row r of the new table belongs to source s = sources[r] (sources == NULL: s = r); s < 0 gives an empty row, a source may repeat.
+ * The list L of source s:
+ *     from_topk:   what gorse_topk_search_vector returns for stored row s as a query vector with k = n + 1 and prune0 = 0, under the
+ *                  index's current mask (the row itself is not excluded by the search); an entry's raw weight is -dist as a float
+ *     from_sparse: what gorse_sparse_search returns for stored row s as the query with exclude == NULL and k = n + 1; raw = the score
+ * Walk L in order; skip the entry whose index is s; when positive_only != 0 skip entries with raw <= 0 (a NaN is kept); stop after n
+ * kept entries.  The kept (index, raw) pairs in that order are row r; the table is weighted, transform and scale are stored as
+ * gorse_nbr_set_table stores them.  The table equals, bit for bit, the one a caller builds from those public searches on the host.
+ * GORSE_ERR_INVALID: a NULL handle, an unknown which or transform, n_rows < 0, n outside 1 .. GORSE_NBR_MAX_LIST, a non-finite
+ * scale, handles on different devices, a kept raw weight that is not finite.  GORSE_ERR_RANGE: sources[r] >= the index's rows;
+ * which == GORSE_NBR_HOP2 and more index rows than the handle's n_items.  GORSE_ERR_NOMEM: the staging (n_rows * n pairs) does not
+ * fit.  An error leaves the previous table in place. */
+#define GORSE_NBR_MAX_LIST 1023 /* n + 1 is the k of the search: the sparse search serves k <= 1024 */
+int32_t gorse_nbr_set_table_from_topk(gorse_nbr *h, int32_t which, gorse_topk *index, int64_t n_rows,
+                                      const int64_t *sources /*host, n_rows, or NULL: sources[r] = r*/, int32_t n,
+                                      int32_t positive_only, int32_t transform, double scale);
+int32_t gorse_nbr_set_table_from_sparse(gorse_nbr *h, int32_t which, gorse_sparse *index, int64_t n_rows,
+                                        const int64_t *sources /*host or NULL*/, int32_t n,
+                                        int32_t positive_only, int32_t transform, double scale);
+/* the table a slot holds, host-built or device-built; an unset slot: GORSE_ERR_INVALID.  Outputs may be NULL; weights must be NULL
+ * for an unweighted table. */
+int32_t gorse_nbr_table_info(gorse_nbr *h, int32_t which, int64_t *n_rows, int64_t *nnz, int32_t *weighted);
+int32_t gorse_nbr_get_table(gorse_nbr *h, int32_t which, int64_t *indptr /*host, n_rows+1*/,
+                            int32_t *indices /*host, nnz, or NULL*/, float *weights /*host, nnz, or NULL*/);
 
 #ifdef __cplusplus
 }

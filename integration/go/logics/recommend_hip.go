@@ -84,6 +84,51 @@ func (r *NeighbourRecommender) SetTable(which int, t NeighbourTable) error {
 	return nil
 }
 
+// NeighbourIndex is a similarity index resident on the device: exactly one of Dense (gorse_topk, the embedding kinds) and Sparse
+// (gorse_sparse, the tags / users / items / auto kinds) is set.
+type NeighbourIndex struct {
+	Dense  *C.gorse_topk
+	Sparse *C.gorse_sparse
+}
+
+// SetTableFromIndex replaces hop 1 (which = 0) or hop 2 (which = 1) by the neighbour lists of the index's stored rows, built on the
+// device (gorse_nbr_set_table_from_topk / _from_sparse): row r is the list QueryItemToItem / QueryUserToUser form for stored row
+// sources[r] (nil: the index's first numRows rows; a negative source: an empty row) -- QueryVectors(n + 1) under the index's current
+// mask, the row itself skipped, scores <= 0 skipped for the Dot kinds (positiveOnly), cut at n -- with the index's row numbers as
+// indices and the vector database's float32 score as raw weight.  recip and scale as in NeighbourTable.  The lists never cross to
+// the host; the table equals the one SetTable is given after the same searches on the host, bit for bit.
+func (r *NeighbourRecommender) SetTableFromIndex(which int, index NeighbourIndex, numRows int, sources []int64, n int, positiveOnly,
+	recip bool, scale float64) error {
+	var src *C.int64_t
+	if sources != nil {
+		numRows = len(sources)
+		if numRows == 0 {
+			sources = []int64{-1} // a table without rows: the pointer only has to be non-nil
+		}
+		src = (*C.int64_t)(unsafe.Pointer(&sources[0]))
+	}
+	transform := C.int32_t(C.GORSE_NBR_RAW)
+	if recip {
+		transform = C.GORSE_NBR_RECIP
+	}
+	positive := C.int32_t(0)
+	if positiveOnly {
+		positive = 1
+	}
+	var rc C.int32_t
+	if index.Dense != nil {
+		rc = C.gorse_nbr_set_table_from_topk(r.h, C.int32_t(which), index.Dense, C.int64_t(numRows), src, C.int32_t(n), positive, transform,
+			C.double(scale))
+	} else {
+		rc = C.gorse_nbr_set_table_from_sparse(r.h, C.int32_t(which), index.Sparse, C.int64_t(numRows), src, C.int32_t(n), positive,
+			transform, C.double(scale))
+	}
+	if rc != C.GORSE_OK {
+		return nbrError("gorse_nbr_set_table_from_index", rc)
+	}
+	return nil
+}
+
 // Recommend returns for query t the n best candidates of a walk from hop-1 row rows[t] (negative: empty list) that are not in
 // seen[t] (nil: no such rows).  RecommendSequential (recommend.go:135-156) adds every earlier recommender's results to the exclude
 // set: the caller appends them to seen[t] before the next recommender's call.
