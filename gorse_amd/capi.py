@@ -39,6 +39,7 @@ _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
+_u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); mirrors include/gorse_hip.h (the boundary) and include/gorse_hip_test.h (test hooks) one to one
 SIGNATURES = {
@@ -210,6 +211,19 @@ SIGNATURES = {
     "gorse_nbr_table_info": (C.c_int32, [_vp, C.c_int32, _i64p, _i64p, _i32p]),
     "gorse_nbr_get_table": (C.c_int32, [_vp, C.c_int32, _i64p, _i32p, _f32p]),
     "gorse_hip_test_set_nbr": (None, [C.c_int32, C.c_int64]),
+    "gorse_cand_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64]),
+    "gorse_cand_destroy": (C.c_int32, [_vp]),
+    "gorse_cand_begin": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, C.c_int32]),
+    "gorse_cand_add_mf": (C.c_int32, [_vp, _vp, _i32p, C.c_int32, _u8p, _u8p]),
+    "gorse_cand_add_nbr": (C.c_int32, [_vp, _vp, _i32p, C.c_int32, _u8p]),
+    "gorse_cand_add_shared": (C.c_int32, [_vp, C.c_int64, _i32p, _f64p, C.c_int32, _u8p]),
+    "gorse_cand_add_lists": (C.c_int32, [_vp, _i64p, _i32p, _f64p, C.c_int32, _u8p]),
+    "gorse_cand_finish": (C.c_int32, [_vp, _u8p]),
+    "gorse_cand_info": (C.c_int32, [_vp, _i64p, _i32p, _i64p, _i64p]),
+    "gorse_cand_get": (C.c_int32, [_vp, _i64p, _i32p, _f64p, _u8p]),
+    "gorse_cand_get_exclusion": (C.c_int32, [_vp, _i64p, _i32p]),
+    "gorse_cand_stats": (C.c_int32, [_vp, C.c_int32, _f64p, _f64p]),
+    "gorse_fm_rank_cand": (C.c_int32, [_vp, _vp, _i64p, _i32p, _f32p, _i32p, C.c_int32, _i32p, _f32p, _i32p]),
 }
 
 
@@ -630,8 +644,28 @@ class FM:
                                         _p(cancel, _i32p) if cancel is not None else None, _p(outs[0], _f32p), _p(outs[1], _i32p)))
         return outs[0], outs[1]
 
+    def rank_cand(self, chain, user_indptr, user_indices, user_values, batch_size, user_lead=None, cancel=None, scores=True,
+                  order=True):
+        """rank_users with every user's candidates taken on the device from a finished CandidateChain (gorse_fm_rank_cand):
+        (scores, order) flat in the layout of chain.get()'s row pointer.  scores / order: True or False."""
+        uptr = _arr(user_indptr, np.int64).reshape(-1)
+        uidx, uval = _arr(user_indices, np.int32).reshape(-1), _arr(user_values, np.float32).reshape(-1)
+        n, _, total, _ = chain.info()
+        if uptr.size != n + 1 or uidx.size != uval.size:
+            raise GorseHipError(ERR_INVALID, "user_indptr holds one entry per query of the chain and one more")
+        if n > 0 and np.all(np.diff(uptr) >= 0) and uptr[0] == 0 and uidx.size < uptr[-1]:
+            raise GorseHipError(ERR_INVALID, "fewer entries than the pointer array names")
+        ul = _arr(user_lead, np.int32).reshape(-1) if user_lead is not None else None
+        if ul is not None and ul.size != n:
+            raise GorseHipError(ERR_INVALID, "one lead per user")
+        sc = np.zeros(total, np.float32) if scores else None
+        od = np.zeros(total, np.int32) if order else None
+        check(lib().gorse_fm_rank_cand(self.h, chain.h, _p(uptr, _i64p), _p(uidx, _i32p), _p(uval, _f32p), _p(ul, _i32p), int(batch_size),
+                                       _p(cancel, _i32p) if cancel is not None else None, _p(sc, _f32p), _p(od, _i32p)))
+        return sc, od
+
     def rank_stats(self):
-        """the last rank_users: rows scored, slices, launch rounds, lists sorted by the host, device milliseconds"""
+        """the last rank_users / rank_cand: rows scored, slices, launch rounds, lists sorted by the host, device milliseconds"""
         v = [C.c_int64(0) for _ in range(4)]
         ms = C.c_double(0)
         check(lib().gorse_fm_rank_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
@@ -1193,6 +1227,124 @@ class NbrRecommender:
         nl, ng, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
         check(lib().gorse_nbr_recommend_stats(self.h, C.byref(nl), C.byref(ng), C.byref(ms)))
         return nl.value, ng.value, ms.value
+
+
+CAND_MAX_K, CAND_MAX_STAGES = 256, 255  # GORSE_CAND_MAX_K, GORSE_CAND_MAX_STAGES
+
+
+class CandidateChain:
+    """One gorse_cand handle: the exclusion rows and candidate rows of one offline pass (RecommendSequential for many users)
+    resident on one GPU.  begin, then add_* in the recommenders' order, then finish; get / FM.rank_cand need a finished pass."""
+
+    def __init__(self, n_items, device=0):
+        self.n_items = int(n_items)
+        self.h = _vp()
+        check(lib().gorse_cand_create(C.byref(self.h), device, self.n_items))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gorse_cand_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _keep(self, keep):
+        if keep is None:
+            return None
+        kp = _arr(keep, np.uint8).reshape(-1)
+        if kp.size != self.n_items:
+            raise GorseHipError(ERR_INVALID, "keep must have n_items entries")
+        return kp
+
+    @staticmethod
+    def _csr(indptr, n, *arrays):
+        """a host CSR the library may read to indptr[-1]: only a well-formed pointer array is trusted with that"""
+        ip = _arr(indptr, np.int64).reshape(-1)
+        if ip.size != n + 1:
+            raise GorseHipError(ERR_INVALID, "a row pointer must have n_queries + 1 entries")
+        if ip[0] == 0 and np.all(np.diff(ip) >= 0) and any(a.size < ip[-1] for a in arrays):
+            raise GorseHipError(ERR_INVALID, "fewer entries than the pointer array names")
+        return ip
+
+    def begin(self, n_queries, capacity, excl_indptr=None, excl_items=None):
+        """starts a pass of n_queries queries whose candidate rows hold `capacity` entries; the base exclusion rows as a CSR"""
+        n = int(n_queries)
+        it = _arr(excl_items if excl_items is not None else [], np.int32).reshape(-1)
+        ip = self._csr(excl_indptr, n, it) if excl_indptr is not None and n >= 0 else None
+        if it.size == 0:
+            it = np.zeros(1, np.int32)
+        check(lib().gorse_cand_begin(self.h, n, _p(ip, _i64p), _p(it, _i32p), int(capacity)))
+
+    def _queries(self, ids):
+        if ids is None:
+            return None
+        a = _arr(ids, np.int32).reshape(-1)
+        if a.size != self.info()[0]:
+            raise GorseHipError(ERR_INVALID, "one user / row per query of the pass")
+        return a if a.size else np.zeros(1, np.int32)
+
+    def add_mf(self, mf, users, k, item_ok=None, keep=None):
+        """MF.recommend(users, k, item_ok, seen = the BASE rows) as a stage (users = None: query t is user t)"""
+        ok = _arr(item_ok, np.uint8).reshape(-1) if item_ok is not None else None
+        if ok is not None and ok.size != self.n_items:
+            raise GorseHipError(ERR_INVALID, "item_ok must have n_items entries")
+        check(lib().gorse_cand_add_mf(self.h, mf.h, _p(self._queries(users), _i32p), int(k), _p(ok, _u8p), _p(self._keep(keep), _u8p)))
+
+    def add_nbr(self, nbr, rows, k, keep=None):
+        """NbrRecommender.recommend(rows, k, seen = the CURRENT rows) as a stage (rows = None: query t walks hop-1 row t)"""
+        check(lib().gorse_cand_add_nbr(self.h, nbr.h, _p(self._queries(rows), _i32p), int(k), _p(self._keep(keep), _u8p)))
+
+    def add_shared(self, items, scores, k, keep=None):
+        """one list for every query (latest, non-personalized)"""
+        it, sc = _arr(items, np.int32).reshape(-1), _arr(scores, np.float64).reshape(-1)
+        if it.size != sc.size:
+            raise GorseHipError(ERR_INVALID, "one score per item")
+        n = it.size
+        if n == 0:
+            it, sc = np.zeros(1, np.int32), np.zeros(1, np.float64)
+        check(lib().gorse_cand_add_shared(self.h, n, _p(it, _i32p), _p(sc, _f64p), int(k), _p(self._keep(keep), _u8p)))
+
+    def add_lists(self, indptr, items, scores, k, keep=None):
+        """one list per query, as a CSR"""
+        it, sc = _arr(items, np.int32).reshape(-1), _arr(scores, np.float64).reshape(-1)
+        if it.size != sc.size:
+            raise GorseHipError(ERR_INVALID, "one score per item")
+        ip = self._csr(indptr, self.info()[0], it)
+        if it.size == 0:
+            it, sc = np.zeros(1, np.int32), np.zeros(1, np.float64)
+        check(lib().gorse_cand_add_lists(self.h, _p(ip, _i64p), _p(it, _i32p), _p(sc, _f64p), int(k), _p(self._keep(keep), _u8p)))
+
+    def finish(self, keep=None):
+        """compacts the candidates (dropping items with keep == 0) and closes the pass"""
+        check(lib().gorse_cand_finish(self.h, _p(self._keep(keep), _u8p)))
+
+    def info(self):
+        """(queries, stages so far, candidates, current exclusion entries)"""
+        nq, ns, nc, nx = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gorse_cand_info(self.h, C.byref(nq), C.byref(ns), C.byref(nc), C.byref(nx)))
+        return nq.value, ns.value, nc.value, nx.value
+
+    def get(self):
+        """the finished pass as a CSR: (indptr, items, float64 scores, uint8 stage numbers)"""
+        nq, _, nc, _ = self.info()
+        ip = np.zeros(nq + 1, np.int64)
+        it, sc, sg = np.zeros(max(nc, 1), np.int32), np.zeros(max(nc, 1), np.float64), np.zeros(max(nc, 1), np.uint8)
+        check(lib().gorse_cand_get(self.h, _p(ip, _i64p), _p(it, _i32p), _p(sc, _f64p), _p(sg, _u8p)))
+        n = int(ip[-1])
+        return ip, it[:n], sc[:n], sg[:n]
+
+    def exclusion(self):
+        """the current exclusion rows as a CSR with ascending rows: (indptr, items)"""
+        nq, _, _, nx = self.info()
+        ip, it = np.zeros(nq + 1, np.int64), np.zeros(max(nx, 1), np.int32)
+        check(lib().gorse_cand_get_exclusion(self.h, _p(ip, _i64p), _p(it, _i32p)))
+        return ip, it[:nx]
+
+    def stats(self, stage):
+        """(device milliseconds of the stage's own search, of the chain's filter / scan / append / merge)"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().gorse_cand_stats(self.h, int(stage), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 # gorse_hip_test_sgemm_last_form (include/gorse_hip_test.h, GORSE_TEST_SGEMM_*)

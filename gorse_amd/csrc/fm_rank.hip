@@ -7,6 +7,7 @@
 // score every (user, candidate) row on the device in BatchPredict's order (fm.go:183-206), and sorts every user's list there:
 //   fm_rank_sort_kernel     one workgroup per user list of up to kSortCap entries: a bitonic sort of (key << 32 | position) in
 //                           LDS.  The keys are unique, so the network's instability cannot show.
+#include "cand_internal.hpp"
 #include "fm_internal.hpp"
 #include "fm_rank_order.hpp"
 
@@ -148,29 +149,13 @@ extern "C" int32_t gorse_fm_set_items(gorse_fm *h, int64_t n_items, const int64_
     return GORSE_OK;
 }
 
-extern "C" int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64_t *user_indptr, const int32_t *user_indices,
-                                       const float *user_values, const int32_t *user_lead, const int64_t *cand_indptr,
-                                       const int32_t *cand, int32_t batch_size, const volatile int32_t *cancel, float *scores_out,
-                                       int32_t *order_out) {
-    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
-    if (!h->cat) return fail(GORSE_ERR_INVALID, "no item catalogue (gorse_fm_set_items)");
-    if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
-    if (n_users < 0 || n_users > INT32_MAX) return fail(GORSE_ERR_INVALID, "n_users must be in [0, 2^31)");
-    if (n_users == 0) {
-        h->rk_rows = h->rk_slices = h->rk_rounds = h->rk_host_sorted = 0;
-        h->rk_ms = 0.0;
-        return GORSE_OK;
-    }
-    GORSE_TRY(fm::check_side(h, n_users, user_indptr, user_indices, user_values, user_lead, "users"));
-    GORSE_TRY(fm::check_pointer(cand_indptr, n_users, "cand_indptr"));
-    const int64_t total = cand_indptr[n_users];
-    if (total > INT32_MAX) return fail(GORSE_ERR_INVALID, "more than 2^31 - 1 candidates in one call: split the users");
-    if (total > 0 && !cand) return fail(GORSE_ERR_INVALID, "cand is NULL");
+// The validated call: user t's candidates are cand[cand_indptr[t] ..) on the host, or, with cand == NULL, d_cand[cand_indptr[t] ..)
+// on the device (a finished candidate chain's items).
+static int32_t rank_lists(gorse_fm *h, int64_t n_users, const int64_t *user_indptr, const int32_t *user_indices, const float *user_values,
+                          const int32_t *user_lead, const int64_t *cand_indptr, const int32_t *cand, const int32_t *d_cand,
+                          int32_t batch_size, const volatile int32_t *cancel, float *scores_out, int32_t *order_out) {
     const fm::Catalogue &cat = *h->cat;
-    for (int64_t e = 0; e < total; e++)
-        if (cand[e] < 0 || cand[e] >= cat.n_items)
-            return fail(GORSE_ERR_RANGE, "candidate %d at position %lld is outside the catalogue's [0,%lld)", cand[e], (long long)e,
-                        (long long)cat.n_items);
+    const int64_t total = cand_indptr[n_users];
     GORSE_HIP_CHECK(hipSetDevice(h->device));
 
     // rows, slices (per user, batch_size rows each, the last one partial) and launch rounds (whole slices, at most R rows)
@@ -190,6 +175,8 @@ extern "C" int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64
     GORSE_TRY(fm::upload(h->r_ulead, user_lead ? user_lead : zero_lead.data(), (size_t)n_users));
     GORSE_TRY(fm::upload(h->r_cptr, cand_indptr, (size_t)n_users + 1));
     GORSE_TRY(fm::upload_plan(h->r_plan, plan, total));
+    if (!cand && total > 0)  // the plan's item column (segment | item | ...) from the lists on the device, on the stream of its readers
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->r_plan.desc.p + total, d_cand, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToDevice, h->s));
     GORSE_TRY(h->r_scores.ensure((size_t)total));
     if (order_out) GORSE_TRY(h->r_order.ensure((size_t)total));
     if (h->n_fields > 0) GORSE_TRY(h->rs.ensure(h->r_plan.max_round, h->d, maxD));
@@ -226,6 +213,57 @@ extern "C" int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64
     h->rk_host_sorted = order_out ? n_long : 0;
     h->rk_ms = ms;
     return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64_t *user_indptr, const int32_t *user_indices,
+                                       const float *user_values, const int32_t *user_lead, const int64_t *cand_indptr,
+                                       const int32_t *cand, int32_t batch_size, const volatile int32_t *cancel, float *scores_out,
+                                       int32_t *order_out) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (!h->cat) return fail(GORSE_ERR_INVALID, "no item catalogue (gorse_fm_set_items)");
+    if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
+    if (n_users < 0 || n_users > INT32_MAX) return fail(GORSE_ERR_INVALID, "n_users must be in [0, 2^31)");
+    if (n_users == 0) {
+        h->rk_rows = h->rk_slices = h->rk_rounds = h->rk_host_sorted = 0;
+        h->rk_ms = 0.0;
+        return GORSE_OK;
+    }
+    GORSE_TRY(fm::check_side(h, n_users, user_indptr, user_indices, user_values, user_lead, "users"));
+    GORSE_TRY(fm::check_pointer(cand_indptr, n_users, "cand_indptr"));
+    const int64_t total = cand_indptr[n_users];
+    if (total > INT32_MAX) return fail(GORSE_ERR_INVALID, "more than 2^31 - 1 candidates in one call: split the users");
+    if (total > 0 && !cand) return fail(GORSE_ERR_INVALID, "cand is NULL");
+    const fm::Catalogue &cat = *h->cat;
+    for (int64_t e = 0; e < total; e++)
+        if (cand[e] < 0 || cand[e] >= cat.n_items)
+            return fail(GORSE_ERR_RANGE, "candidate %d at position %lld is outside the catalogue's [0,%lld)", cand[e], (long long)e,
+                        (long long)cat.n_items);
+    return rank_lists(h, n_users, user_indptr, user_indices, user_values, user_lead, cand_indptr, cand, nullptr, batch_size, cancel,
+                      scores_out, order_out);
+}
+
+extern "C" int32_t gorse_fm_rank_cand(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr, const int32_t *user_indices,
+                                      const float *user_values, const int32_t *user_lead, int32_t batch_size,
+                                      const volatile int32_t *cancel, float *scores_out, int32_t *order_out) {
+    if (!h || !c) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (!h->cat) return fail(GORSE_ERR_INVALID, "no item catalogue (gorse_fm_set_items)");
+    if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
+    if (!c->pass.begun || !c->pass.finished) return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain has no finished pass (gorse_cand_finish)");
+    if (c->device != h->device) return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain is on device %d, the ranker on device %d", c->device, h->device);
+    if (c->n_items != h->cat->n_items)
+        return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain has %lld items, the catalogue %lld", (long long)c->n_items,
+                    (long long)h->cat->n_items);
+    const int64_t n_users = c->pass.n_queries;
+    if (n_users == 0) {
+        h->rk_rows = h->rk_slices = h->rk_rounds = h->rk_host_sorted = 0;
+        h->rk_ms = 0.0;
+        return GORSE_OK;
+    }
+    GORSE_TRY(fm::check_side(h, n_users, user_indptr, user_indices, user_values, user_lead, "users"));
+    if (c->f_ptr_h.back() > INT32_MAX) return fail(GORSE_ERR_INVALID, "more than 2^31 - 1 candidates in one call: split the users");
+    // (the chain's items lie in [0, n_items): every stage's input was held against it)
+    return rank_lists(h, n_users, user_indptr, user_indices, user_values, user_lead, c->f_ptr_h.data(), nullptr, c->f_item.p, batch_size, cancel,
+                      scores_out, order_out);
 }
 
 extern "C" int32_t gorse_fm_rank_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, int64_t *host_sorted,

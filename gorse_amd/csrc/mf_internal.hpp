@@ -123,6 +123,7 @@ struct gorse_mf {
     gorse::DevBuf<char> stage, rank_in;
     // gorse_mf_recommend (recommend.hip): its inputs, the fast path's buffers, the literal path's candidate lists; the last call's split
     gorse::DevBuf<char> rec_in, rec_buf, rec_lit;
+    gorse::DevBuf<char> rec_seen;  // gorse_mf_recommend's seen rows, sorted (row pointer | items); the candidate chain brings its own
     int64_t rec_fast = 0, rec_literal = 0;
     double rec_ms = 0.0;
     gorse::KernelProfile prof{GORSE_PROF_NCLASSES};
@@ -174,4 +175,19 @@ int32_t resident_user_lists(gorse_mf *h, UserLists *lists);
 // mf_rank.hip: Rank + TopKFilter over the lists; the rank lists go to the host arrays (n_users * topk padded with -1, lengths),
 // enqueued on h->stream -- the caller synchronises
 int32_t mf_rank_device(gorse_mf *h, const UserLists &L, int32_t topk, int32_t *rank_out, int32_t *rank_len);
+
+// recommend.hip, in two halves so that the candidate chain (cand.hip) searches under its own device-resident exclusion rows.
+// check: gorse_mf_recommend's validation of everything but the seen rows.
+// core: the search.  The seen rows are a CSR on the device with ASCENDING rows (d_sptr from 0; NULL: no seen rows).  dev == NULL: the
+// result rows go to the host arrays (each may be NULL), as gorse_mf_recommend returns them.  dev != NULL (k <= 256): the n_users * k
+// rows and the counts are left in the caller's device buffers instead -- the threshold path's chunks copied device to device, the
+// literal path's few rows uploaded at the end -- and the host arrays are not written.  Returns with the handle's stream idle.
+struct MfDeviceRows {
+    int32_t *items = nullptr;
+    float *scores = nullptr;
+    int32_t *cnt = nullptr;
+};
+int32_t mf_recommend_check(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k);
+int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k, const uint8_t *item_ok, const int64_t *d_sptr,
+                          const int32_t *d_seen, int32_t *items_out, float *scores_out, int32_t *count_out, const MfDeviceRows *dev);
 }

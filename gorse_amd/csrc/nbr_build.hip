@@ -10,6 +10,7 @@
 // largest kept index and, for a hop-1 table, the per-row bounds nbr::row_bounds forms on the host for a host-built table.
 #include <cmath>
 
+#include "csr_scan.hpp"
 #include "nbr_internal.hpp"
 #include "nbr_plan.hpp"
 #include "sparse_host.hpp"
@@ -20,7 +21,6 @@ using namespace gorse;
 namespace {
 
 constexpr int kRuleWaves = 4;                      // result rows per workgroup of the row kernels (one wave each)
-constexpr int kScanThreads = 256, kScanPer = 8;    // the scan: 2048 counts per workgroup
 constexpr int64_t kMaxGrid = (int64_t)1 << 20;
 
 struct RuleArgs {
@@ -80,65 +80,6 @@ __global__ __launch_bounds__(kRuleWaves * 64) void nbr_rule_kernel(const RuleArg
     if (lane == 0) {
         if (bad) atomicOr(A.flags, 1);
         if (mx >= 0) atomicMax(A.flags + 1, mx);
-    }
-}
-
-// exclusive scan of v over the workgroup's 256 threads; *total = the workgroup's sum.  Ends behind a barrier: sh may be used again.
-__device__ __forceinline__ long long block_exclusive(long long v, long long *sh, long long *total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kScanThreads; off <<= 1) {
-        const long long t = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const long long incl = sh[tid];
-    *total = sh[kScanThreads - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// The row pointer: x[0 .. n) exclusive-scanned in place, 64 bits wide (a million rows of a hundred entries pass 2^31 at twenty
-// times that).  sums[b] = the sum of workgroup b's 2048 entries; one workgroup scans the sums; every workgroup scans its own.
-__global__ __launch_bounds__(kScanThreads) void nbr_scan_sums_kernel(const long long *__restrict__ x, int64_t n, long long *__restrict__ sums) {
-    __shared__ long long sh[kScanThreads];
-    const int64_t first = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanPer;
-    long long v = 0;
-    for (int e = 0; e < kScanPer; e++)
-        if (first + e < n) v += x[first + e];
-    long long total;
-    (void)block_exclusive(v, sh, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(kScanThreads) void nbr_scan_top_kernel(long long *sums, int64_t nb) {
-    __shared__ long long sh[kScanThreads];
-    long long carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += kScanThreads) {
-        const int64_t b = b0 + threadIdx.x;
-        const long long v = b < nb ? sums[b] : 0;
-        long long total;
-        const long long ex = block_exclusive(v, sh, &total);
-        if (b < nb) sums[b] = carry + ex;
-        carry += total;
-    }
-}
-__global__ __launch_bounds__(kScanThreads) void nbr_scan_apply_kernel(long long *x, int64_t n, const long long *__restrict__ sums) {
-    __shared__ long long sh[kScanThreads];
-    const int64_t first = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanPer;
-    long long own[kScanPer], v = 0;
-#pragma unroll
-    for (int e = 0; e < kScanPer; e++) {
-        own[e] = first + e < n ? x[first + e] : 0;
-        v += own[e];
-    }
-    long long total;
-    long long run = sums[blockIdx.x] + block_exclusive(v, sh, &total);
-#pragma unroll
-    for (int e = 0; e < kScanPer; e++) {
-        if (first + e < n) x[first + e] = run;
-        run += own[e];
     }
 }
 
@@ -232,12 +173,8 @@ struct Build {
         if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
         (void)hipEventDestroy(ev);  // (released once the wait has passed)
         if (e != hipSuccess) return fail(GORSE_ERR_HIP, "%s: ordering the two streams: %s", who, hipGetErrorString(e));
-        const int64_t ns = n_rows + 1, per = (int64_t)kScanThreads * kScanPer, nb = ceil_div(ns, per);
-        GORSE_TRY(sums.alloc((size_t)nb));
-        nbr_scan_sums_kernel<<<dim3((unsigned)nb), dim3(kScanThreads), 0, st>>>((long long *)ptr.p, ns, sums.p);
-        nbr_scan_top_kernel<<<dim3(1), dim3(kScanThreads), 0, st>>>(sums.p, nb);
-        nbr_scan_apply_kernel<<<dim3((unsigned)nb), dim3(kScanThreads), 0, st>>>((long long *)ptr.p, ns, sums.p);
-        GORSE_HIP_CHECK(hipGetLastError());
+        const int64_t ns = n_rows + 1;
+        GORSE_TRY(csr_exclusive_scan((long long *)ptr.p, ns, sums, st));
         int32_t fl[2] = {0, -1};
         std::vector<int64_t> ptr_host((size_t)ns);
         GORSE_HIP_CHECK(hipMemcpyAsync(fl, flags.p, 8, hipMemcpyDeviceToHost, st));

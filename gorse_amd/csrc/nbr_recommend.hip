@@ -386,20 +386,28 @@ int32_t nbr_launch(const NbrArgs &A, int64_t nq, size_t lds, hipStream_t stream)
 
 }  // namespace
 
-extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const int32_t *rows, int32_t k, const int64_t *seen_indptr,
-                                       const int32_t *seen_items, int32_t *items_out, double *scores_out, int32_t *count_out) {
-    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+namespace gorse {
+
+int32_t nbr_recommend_check(gorse_nbr *h, const char *who, int64_t n_queries, const int32_t *rows, int32_t k, const int64_t *seen_indptr,
+                            const int32_t *seen_items) {
     NbrTable &T1 = h->tab[GORSE_NBR_HOP1], &T2 = h->tab[GORSE_NBR_HOP2];
-    if (!T1.set || !T2.set) return fail(GORSE_ERR_INVALID, "gorse_nbr_recommend: the hop-%d table is not set", T1.set ? 2 : 1);
+    if (!T1.set || !T2.set) return fail(GORSE_ERR_INVALID, "%s: the hop-%d table is not set", who, T1.set ? 2 : 1);
     std::string msg;
     const int32_t rc = nbr::validate_call(n_queries, rows, k, seen_indptr, seen_items, T1.n_rows, h->n_items, &msg);
-    if (rc != GORSE_OK) return fail(rc, "gorse_nbr_recommend: %s", msg.c_str());
+    if (rc != GORSE_OK) return fail(rc, "%s: %s", who, msg.c_str());
     if (T1.max_index >= T2.n_rows)
-        return fail(GORSE_ERR_RANGE, "gorse_nbr_recommend: hop-1 index %lld outside the hop-2 table's %lld rows", (long long)T1.max_index,
+        return fail(GORSE_ERR_RANGE, "%s: hop-1 index %lld outside the hop-2 table's %lld rows", who, (long long)T1.max_index,
                     (long long)T2.n_rows);
+    return GORSE_OK;
+}
+
+int32_t nbr_recommend_core(gorse_nbr *h, int64_t n_queries, const int32_t *rows, int32_t k, const int64_t *sptr_host,
+                           const int64_t *d_sptr, const int32_t *d_seen, NbrDeviceRows *res) {
+    NbrTable &T1 = h->tab[GORSE_NBR_HOP1], &T2 = h->tab[GORSE_NBR_HOP2];
     GORSE_TRY(h->use());
     h->n_lds = h->n_global = 0;
     h->ms = 0.0;
+    *res = NbrDeviceRows();
     if (n_queries == 0) return GORSE_OK;
     if (!h->bounds_valid) {
         if (T1.on_device_only)  // its indices never crossed to the host: the same sums, formed where they lie
@@ -408,12 +416,11 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
             nbr::row_bounds(T1.n_rows, T1.ptr.data(), T1.idx.data(), T2.ptr.data(), &h->src_sum);
         h->bounds_valid = true;
     }
-    const bool has_seen = seen_indptr && seen_indptr[n_queries] > seen_indptr[0];
-    const int64_t n_seen = has_seen ? seen_indptr[n_queries] - seen_indptr[0] : 0;
-    std::vector<int64_t> bound((size_t)n_queries), sptr_host;
+    const bool has_seen = sptr_host != nullptr;
+    std::vector<int64_t> bound((size_t)n_queries);
     for (int64_t t = 0; t < n_queries; t++) {
         const int64_t r = rows ? rows[t] : t;
-        bound[(size_t)t] = r < 0 ? 0 : nbr::query_bound(h->n_items, h->src_sum[(size_t)r], has_seen ? seen_indptr[t + 1] - seen_indptr[t] : 0);
+        bound[(size_t)t] = r < 0 ? 0 : nbr::query_bound(h->n_items, h->src_sum[(size_t)r], has_seen ? sptr_host[t + 1] - sptr_host[t] : 0);
     }
     nbr::Plan plan;
     if (!nbr::make_plan(n_queries, bound.data(), g_nbr_lds_slots > 0 ? g_nbr_lds_slots : nbr::kMaxLdsSlots, g_nbr_query_chunk,
@@ -423,11 +430,10 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
     for (const nbr::Launch &L : plan.launches)
         if (L.slots == 0) scratch_slots = std::max(scratch_slots, plan.off[(size_t)L.q1 - 1] + plan.cap[(size_t)L.q1 - 1]);
 
-    // ---- inputs to the device
+    // ---- the rows asked for and the plan to the device
     Carver in;
-    const size_t o_rows = in.take((size_t)n_queries * 4), o_sptr = in.take((size_t)(n_queries + 1) * 8),
-                 o_seen = in.take((size_t)std::max<int64_t>(n_seen, 1) * 4), o_order = in.take((size_t)n_queries * 4),
-                 o_cap = in.take((size_t)n_queries * 4), o_off = in.take((size_t)n_queries * 8);
+    const size_t o_rows = in.take((size_t)n_queries * 4), o_order = in.take((size_t)n_queries * 4), o_cap = in.take((size_t)n_queries * 4),
+                 o_off = in.take((size_t)n_queries * 8);
     GORSE_TRY(h->in.ensure(in.off));
     Carver oc;
     const size_t o_items = oc.take((size_t)n_queries * k * 4), o_sums = oc.take((size_t)n_queries * k * 8), o_cnt = oc.take((size_t)n_queries * 4);
@@ -437,12 +443,6 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
     GORSE_TRY(h->scratch.ensure(sc.off));
     hipStream_t st = h->stream;
     if (rows) GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_rows, rows, (size_t)n_queries * 4, hipMemcpyHostToDevice, st));
-    if (has_seen) {
-        sptr_host.resize((size_t)n_queries + 1);
-        for (int64_t t = 0; t <= n_queries; t++) sptr_host[(size_t)t] = seen_indptr[t] - seen_indptr[0];
-        GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_sptr, sptr_host.data(), (size_t)(n_queries + 1) * 8, hipMemcpyHostToDevice, st));
-        GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_seen, seen_items + seen_indptr[0], (size_t)n_seen * 4, hipMemcpyHostToDevice, st));
-    }
     GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_order, plan.order.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, st));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_cap, plan.cap.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice, st));
     GORSE_HIP_CHECK(hipMemcpyAsync(h->in.p + o_off, plan.off.data(), (size_t)n_queries * 8, hipMemcpyHostToDevice, st));
@@ -451,8 +451,8 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
     A.ptr1 = T1.d_ptr.p, A.idx1 = T1.d_idx.p, A.w1 = T1.weighted ? T1.d_w.p : nullptr, A.tr1 = T1.transform, A.sc1 = T1.scale;
     A.ptr2 = T2.d_ptr.p, A.idx2 = T2.d_idx.p, A.w2 = T2.weighted ? T2.d_w.p : nullptr, A.tr2 = T2.transform, A.sc2 = T2.scale;
     A.rows = rows ? (const int32_t *)(h->in.p + o_rows) : nullptr;
-    A.sptr = has_seen ? (const int64_t *)(h->in.p + o_sptr) : nullptr;
-    A.seen = (const int32_t *)(h->in.p + o_seen);
+    A.sptr = has_seen ? d_sptr : nullptr;
+    A.seen = d_seen;
     A.k = k;
     A.gsums = (unsigned long long *)(h->scratch.p + o_gsums);
     A.gkeys = (int32_t *)(h->scratch.p + o_gkeys);
@@ -466,7 +466,7 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
         (void)hipEventDestroy(ev_a);
         return fail(GORSE_ERR_HIP, "gorse_nbr_recommend: hipEventCreate");
     }
-    int32_t res = [&]() -> int32_t {
+    int32_t rc = [&]() -> int32_t {
         GORSE_HIP_CHECK(hipEventRecord(ev_a, st));
         for (const nbr::Launch &L : plan.launches) {
             A.order = (const int32_t *)(h->in.p + o_order) + L.q0;
@@ -490,12 +490,42 @@ extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const in
     }();
     (void)hipEventDestroy(ev_a);
     (void)hipEventDestroy(ev_b);
-    GORSE_TRY(res);
-    if (items_out) GORSE_HIP_CHECK(hipMemcpyAsync(items_out, h->out.p + o_items, (size_t)n_queries * k * 4, hipMemcpyDeviceToHost, st));
-    if (scores_out) GORSE_HIP_CHECK(hipMemcpyAsync(scores_out, h->out.p + o_sums, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, st));
-    if (count_out) GORSE_HIP_CHECK(hipMemcpyAsync(count_out, h->out.p + o_cnt, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
-    GORSE_HIP_CHECK(hipStreamSynchronize(st));
+    GORSE_TRY(rc);
+    res->items = A.out_items, res->sums = A.out_sums, res->cnt = A.out_cnt;
     h->n_lds = plan.n_lds;
     h->n_global = plan.n_global;
+    return GORSE_OK;
+}
+
+}  // namespace gorse
+
+extern "C" int32_t gorse_nbr_recommend(gorse_nbr *h, int64_t n_queries, const int32_t *rows, int32_t k, const int64_t *seen_indptr,
+                                       const int32_t *seen_items, int32_t *items_out, double *scores_out, int32_t *count_out) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    GORSE_TRY(nbr_recommend_check(h, "gorse_nbr_recommend", n_queries, rows, k, seen_indptr, seen_items));
+    GORSE_TRY(h->use());
+    // ---- the seen rows to the device; the core walks from device rows (the candidate chain hands it its own)
+    const bool has_seen = n_queries > 0 && seen_indptr && seen_indptr[n_queries] > seen_indptr[0];
+    const int64_t n_seen = has_seen ? seen_indptr[n_queries] - seen_indptr[0] : 0;
+    std::vector<int64_t> sptr_host;
+    Carver in;
+    const size_t o_sptr = in.take((size_t)(n_queries + 1) * 8), o_seen = in.take((size_t)std::max<int64_t>(n_seen, 1) * 4);
+    hipStream_t st = h->stream;
+    if (has_seen) {
+        GORSE_TRY(h->seen_in.ensure(in.off));
+        sptr_host.resize((size_t)n_queries + 1);
+        for (int64_t t = 0; t <= n_queries; t++) sptr_host[(size_t)t] = seen_indptr[t] - seen_indptr[0];
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->seen_in.p + o_sptr, sptr_host.data(), (size_t)(n_queries + 1) * 8, hipMemcpyHostToDevice, st));
+        GORSE_HIP_CHECK(hipMemcpyAsync(h->seen_in.p + o_seen, seen_items + seen_indptr[0], (size_t)n_seen * 4, hipMemcpyHostToDevice, st));
+    }
+    NbrDeviceRows R;
+    GORSE_TRY(nbr_recommend_core(h, n_queries, rows, k, has_seen ? sptr_host.data() : nullptr,
+                                 has_seen ? (const int64_t *)(h->seen_in.p + o_sptr) : nullptr,
+                                 has_seen ? (const int32_t *)(h->seen_in.p + o_seen) : nullptr, &R));
+    if (n_queries == 0) return GORSE_OK;
+    if (items_out) GORSE_HIP_CHECK(hipMemcpyAsync(items_out, R.items, (size_t)n_queries * k * 4, hipMemcpyDeviceToHost, st));
+    if (scores_out) GORSE_HIP_CHECK(hipMemcpyAsync(scores_out, R.sums, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, st));
+    if (count_out) GORSE_HIP_CHECK(hipMemcpyAsync(count_out, R.cnt, (size_t)n_queries * 4, hipMemcpyDeviceToHost, st));
+    GORSE_HIP_CHECK(hipStreamSynchronize(st));
     return GORSE_OK;
 }

@@ -321,9 +321,9 @@ extern "C" int32_t gorse_mf_recommend_stats(gorse_mf *h, int64_t *n_fast, int64_
     return GORSE_OK;
 }
 
-extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k, const uint8_t *item_ok,
-                                      const int64_t *seen_indptr, const int32_t *seen_items, int32_t *items_out, float *scores_out,
-                                      int32_t *count_out) {
+namespace gorse {
+
+int32_t mf_recommend_check(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     if (k <= 0) return fail(GORSE_ERR_INVALID, "k <= 0");
     if (n_users < 0) return fail(GORSE_ERR_INVALID, "n_users < 0");
@@ -332,73 +332,49 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
     if (users)
         for (int64_t t = 0; t < n_users; t++)
             if (users[t] >= h->U) return fail(GORSE_ERR_RANGE, "user %d out of range [0,%lld)", users[t], (long long)h->U);
-    const int64_t I = h->I;
-    int64_t n_seen = 0;
-    if (seen_indptr && n_users > 0) {
-        if (seen_indptr[0] < 0) return fail(GORSE_ERR_INVALID, "seen_indptr[0] < 0");
-        for (int64_t t = 0; t < n_users; t++)
-            if (seen_indptr[t + 1] < seen_indptr[t]) return fail(GORSE_ERR_INVALID, "seen_indptr not monotone at row %lld", (long long)t);
-        n_seen = seen_indptr[n_users] - seen_indptr[0];
-        if (n_seen > 0 && !seen_items) return fail(GORSE_ERR_INVALID, "seen_items is NULL");
-        for (int64_t e = seen_indptr[0]; e < seen_indptr[n_users]; e++)
-            if (seen_items[e] < 0 || seen_items[e] >= I)
-                return fail(GORSE_ERR_RANGE, "seen_items[%lld] = %d out of range [0,%lld)", (long long)e, seen_items[e], (long long)I);
-    }
+    return GORSE_OK;
+}
+
+int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k, const uint8_t *item_ok, const int64_t *d_sptr,
+                          const int32_t *d_seen, int32_t *items_out, float *scores_out, int32_t *count_out, const MfDeviceRows *dev) {
     GORSE_TRY(h->use());
     GORSE_TRY(mf_sync_streams(h));  // behind every epoch still enqueued on the handle
     h->rec_fast = h->rec_literal = 0;
     h->rec_ms = 0.0;
     if (n_users == 0) return GORSE_OK;
+    if (dev && k > kRecMaxK) return fail(GORSE_ERR_INVALID, "device rows are served for k <= %d", kRecMaxK);
 
-    // ---- inputs to the device: users, the item filter, the seen rows sorted
+    // ---- inputs to the device: users, the item filter
+    const int64_t I = h->I;
     std::vector<uint8_t> ok_host;
     if (!item_ok) {
         ok_host.resize((size_t)I);
         for (int64_t i = 0; i < I; i++) ok_host[(size_t)i] = h->h_item_count[(size_t)i] > 0;  // IsItemPredictable
         item_ok = ok_host.data();
     }
-    std::vector<int64_t> sptr_host;
-    std::vector<int32_t> seen_host;
-    const bool has_seen = seen_indptr && n_seen > 0;
-    if (has_seen) {
-        sptr_host.resize((size_t)n_users + 1);
-        for (int64_t t = 0; t <= n_users; t++) sptr_host[(size_t)t] = seen_indptr[t] - seen_indptr[0];
-        seen_host.assign(seen_items + seen_indptr[0], seen_items + seen_indptr[n_users]);
-        parallel_rows(n_users, sptr_host.data(), [&](int, int64_t r0, int64_t r1) {
-            for (int64_t r = r0; r < r1; r++) {
-                int32_t *b = seen_host.data() + sptr_host[(size_t)r], *e = seen_host.data() + sptr_host[(size_t)r + 1];
-                if (e - b > 1 && !std::is_sorted(b, e)) std::sort(b, e);
-            }
-        });
-    }
     Carver in;
-    const size_t o_users = in.take((size_t)n_users * 4), o_ok = in.take((size_t)I), o_sptr = in.take((size_t)(n_users + 1) * 8),
-                 o_seen = in.take((size_t)std::max<int64_t>(n_seen, 1) * 4);
+    const size_t o_users = in.take((size_t)n_users * 4), o_ok = in.take((size_t)I);
     GORSE_TRY(h->rec_in.ensure(in.off));
     int32_t *d_users = users ? (int32_t *)(h->rec_in.p + o_users) : nullptr;
     uint8_t *d_ok = (uint8_t *)(h->rec_in.p + o_ok);
-    int64_t *d_sptr = has_seen ? (int64_t *)(h->rec_in.p + o_sptr) : nullptr;
-    int32_t *d_seen = (int32_t *)(h->rec_in.p + o_seen);
     if (users) GORSE_HIP_CHECK(hipMemcpyAsync(d_users, users, (size_t)n_users * 4, hipMemcpyHostToDevice, h->stream));
     GORSE_HIP_CHECK(hipMemcpyAsync(d_ok, item_ok, (size_t)I, hipMemcpyHostToDevice, h->stream));
-    if (has_seen) {
-        GORSE_HIP_CHECK(hipMemcpyAsync(d_sptr, sptr_host.data(), (size_t)(n_users + 1) * 8, hipMemcpyHostToDevice, h->stream));
-        GORSE_HIP_CHECK(hipMemcpyAsync(d_seen, seen_host.data(), (size_t)n_seen * 4, hipMemcpyHostToDevice, h->stream));
-    }
 
     std::vector<int32_t> items_tmp, count_tmp;
     std::vector<float> scores_tmp;
-    if (!items_out) {
-        items_tmp.resize((size_t)n_users * k);
-        items_out = items_tmp.data();
-    }
-    if (!scores_out) {
-        scores_tmp.resize((size_t)n_users * k);
-        scores_out = scores_tmp.data();
-    }
-    if (!count_out) {
-        count_tmp.resize((size_t)n_users);
-        count_out = count_tmp.data();
+    if (!dev) {  // (the device route keeps no host rows: its few literal rows are assembled in buffers of their own below)
+        if (!items_out) {
+            items_tmp.resize((size_t)n_users * k);
+            items_out = items_tmp.data();
+        }
+        if (!scores_out) {
+            scores_tmp.resize((size_t)n_users * k);
+            scores_out = scores_tmp.data();
+        }
+        if (!count_out) {
+            count_tmp.resize((size_t)n_users);
+            count_out = count_tmp.data();
+        }
     }
     RecTimer timer;
     GORSE_TRY(timer.init());
@@ -464,9 +440,15 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
             rec_finish_kernel<<<dim3((unsigned)nq), dim3(kBlock), lds_fin, h->stream>>>(A, d_ri, d_rs, d_rc, d_lit);
             GORSE_HIP_CHECK(hipGetLastError());
             GORSE_TRY(timer.end(h->stream));
-            GORSE_HIP_CHECK(hipMemcpyAsync(items_out + q0 * k, d_ri, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
-            GORSE_HIP_CHECK(hipMemcpyAsync(scores_out + q0 * k, d_rs, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
-            GORSE_HIP_CHECK(hipMemcpyAsync(count_out + q0, d_rc, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+            if (dev) {  // the chunk's rows stay on the device
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->items + q0 * k, d_ri, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->scores + q0 * k, d_rs, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->cnt + q0, d_rc, (size_t)nq * 4, hipMemcpyDeviceToDevice, h->stream));
+            } else {
+                GORSE_HIP_CHECK(hipMemcpyAsync(items_out + q0 * k, d_ri, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(scores_out + q0 * k, d_rs, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(count_out + q0, d_rc, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+            }
             GORSE_HIP_CHECK(hipMemcpyAsync(lit_host.data(), d_lit, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
             for (int64_t t = 0; t < nq; t++)
@@ -555,20 +537,83 @@ extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_
             GORSE_HIP_CHECK(hipMemcpyAsync(ps.data(), d_ps, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
             GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         }
+        if (dev) {  // the literal rows, row after row in one buffer each, follow the threshold path's rows to the device
+            items_tmp.resize((size_t)nl * k);
+            scores_tmp.resize((size_t)nl * k);
+        }
         int64_t p = 0;
         for (int64_t q = 0; q < nl; q++) {
             const int64_t t = lit_query[(size_t)q];
             const int32_t n = rlen[(size_t)q];
-            count_out[t] = n;
+            int32_t *ri = dev ? items_tmp.data() + q * k : items_out + t * k;
+            float *rs = dev ? scores_tmp.data() + q * k : scores_out + t * k;
+            if (!dev) count_out[t] = n;
             for (int32_t r = 0; r < k; r++) {
-                items_out[t * k + r] = r < n ? rank[(size_t)q * k + r] : -1;
-                scores_out[t * k + r] = r < n ? ps[(size_t)(p + r)] : 0.0f;
+                ri[r] = r < n ? rank[(size_t)q * k + r] : -1;
+                rs[r] = r < n ? ps[(size_t)(p + r)] : 0.0f;
             }
             p += n;
+        }
+        if (dev) {
+            for (int64_t q = 0; q < nl; q++) {
+                const int64_t t = lit_query[(size_t)q];
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->items + t * k, items_tmp.data() + q * k, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->scores + t * k, scores_tmp.data() + q * k, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(dev->cnt + t, rlen.data() + q, 4, hipMemcpyHostToDevice, h->stream));
+            }
+            GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
         }
     }
     h->rec_literal = nl;
     h->rec_fast = n_users - nl;
     h->rec_ms = timer.ms;
     return GORSE_OK;
+}
+
+}  // namespace gorse
+
+extern "C" int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k, const uint8_t *item_ok,
+                                      const int64_t *seen_indptr, const int32_t *seen_items, int32_t *items_out, float *scores_out,
+                                      int32_t *count_out) {
+    GORSE_TRY(mf_recommend_check(h, n_users, users, k));
+    const int64_t I = h->I;
+    int64_t n_seen = 0;
+    if (seen_indptr && n_users > 0) {
+        if (seen_indptr[0] < 0) return fail(GORSE_ERR_INVALID, "seen_indptr[0] < 0");
+        for (int64_t t = 0; t < n_users; t++)
+            if (seen_indptr[t + 1] < seen_indptr[t]) return fail(GORSE_ERR_INVALID, "seen_indptr not monotone at row %lld", (long long)t);
+        n_seen = seen_indptr[n_users] - seen_indptr[0];
+        if (n_seen > 0 && !seen_items) return fail(GORSE_ERR_INVALID, "seen_items is NULL");
+        for (int64_t e = seen_indptr[0]; e < seen_indptr[n_users]; e++)
+            if (seen_items[e] < 0 || seen_items[e] >= I)
+                return fail(GORSE_ERR_RANGE, "seen_items[%lld] = %d out of range [0,%lld)", (long long)e, seen_items[e], (long long)I);
+    }
+    if (n_users == 0) return mf_recommend_core(h, 0, users, k, item_ok, nullptr, nullptr, items_out, scores_out, count_out, nullptr);
+
+    // ---- the seen rows sorted, to the device; the core reads a sorted device CSR (the candidate chain hands it its own)
+    std::vector<int64_t> sptr_host;
+    std::vector<int32_t> seen_host;
+    const bool has_seen = seen_indptr && n_seen > 0;
+    int64_t *d_sptr = nullptr;
+    int32_t *d_seen = nullptr;
+    if (has_seen) {
+        GORSE_TRY(h->use());
+        sptr_host.resize((size_t)n_users + 1);
+        for (int64_t t = 0; t <= n_users; t++) sptr_host[(size_t)t] = seen_indptr[t] - seen_indptr[0];
+        seen_host.assign(seen_items + seen_indptr[0], seen_items + seen_indptr[n_users]);
+        parallel_rows(n_users, sptr_host.data(), [&](int, int64_t r0, int64_t r1) {
+            for (int64_t r = r0; r < r1; r++) {
+                int32_t *b = seen_host.data() + sptr_host[(size_t)r], *e = seen_host.data() + sptr_host[(size_t)r + 1];
+                if (e - b > 1 && !std::is_sorted(b, e)) std::sort(b, e);
+            }
+        });
+        Carver in;
+        const size_t o_sptr = in.take((size_t)(n_users + 1) * 8), o_seen = in.take((size_t)n_seen * 4);
+        GORSE_TRY(h->rec_seen.ensure(in.off));
+        d_sptr = (int64_t *)(h->rec_seen.p + o_sptr);
+        d_seen = (int32_t *)(h->rec_seen.p + o_seen);
+        GORSE_HIP_CHECK(hipMemcpyAsync(d_sptr, sptr_host.data(), (size_t)(n_users + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(d_seen, seen_host.data(), (size_t)n_seen * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    return mf_recommend_core(h, n_users, users, k, item_ok, d_sptr, d_seen, items_out, scores_out, count_out, nullptr);
 }

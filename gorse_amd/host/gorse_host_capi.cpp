@@ -931,6 +931,75 @@ int32_t gh_logics_nbr_recommend(void *h, int32_t user_to_user, int32_t bulk, con
         stage_scores(res);
     });
 }
+// logics::RecommendSequential / RecommendSequentialBulk.  The stages are staged one call each, in the recommenders' order, then run:
+//   gh_logics_seq_add_lists  shared = 0: one record of ids per user (recommendCollaborative / recommendExternal), shared = 1: one record for
+//                            everybody (recommendLatest / recommendNonPersonalized); scores = one double per id, in record order
+//   gh_logics_seq_add_nbr    recommendItemToItem (user_to_user = 0) / recommendUserToUser over a collection; feedback as in gh_logics_nbr_recommend
+//   gh_logics_seq_run        bulk = 0: the per-user loop, bulk = 1: one candidate chain for all users; results staged like every logics call
+namespace {
+thread_local std::vector<logics::SeqStage> g_seq;
+}
+void gh_logics_seq_clear() { g_seq.clear(); }
+int32_t gh_logics_seq_add_lists(int32_t shared, int32_t cache_size, const char *ids, const double *scores, int64_t n_scores) {
+    return guard([&] {
+        logics::SeqStage st;
+        st.kind = shared ? logics::SeqStage::Shared : logics::SeqStage::Lists;
+        st.CacheSize = cache_size;
+        int64_t e = 0;
+        for (const auto &rec : split_records(ids)) {
+            std::vector<logics::Score> l;
+            for (const std::string &id : rec) {
+                if (e >= n_scores) throw std::invalid_argument("fewer scores than ids");
+                logics::Score sc;
+                sc.Id = id;
+                sc.Value = scores[e++];
+                l.push_back(std::move(sc));
+            }
+            if (shared) {
+                st.shared = std::move(l);
+                break;
+            }
+            st.lists.push_back(std::move(l));
+        }
+        g_seq.push_back(std::move(st));
+    });
+}
+int32_t gh_logics_seq_add_nbr(int32_t user_to_user, int32_t cache_size, const char *collection, const char *type, const char *categories,
+                              const char *feedback_users, const char *feedback_items) {
+    return guard([&] {
+        logics::SeqStage st;
+        st.kind = user_to_user ? logics::SeqStage::UserToUser : logics::SeqStage::ItemToItem;
+        st.CacheSize = cache_size;
+        st.collection = collection;
+        st.type = type;
+        st.categories = split_lines(categories);
+        const auto fbu = split_lines(feedback_users);
+        const auto fbi = split_records(feedback_items);
+        for (size_t r = 0; r < fbu.size(); r++) st.feedback[fbu[r]] = r < fbi.size() ? fbi[r] : std::vector<std::string>();
+        g_seq.push_back(std::move(st));
+    });
+}
+int32_t gh_logics_seq_run(void *h, int32_t bulk, int64_t n_users, const char *user_ids, const char *positives, const char *excludes) {
+    return guard([&] {
+        std::vector<logics::NbrUser> users((size_t)n_users);
+        const auto ids = split_lines(user_ids);
+        const auto pos = split_records(positives), exc = split_records(excludes);
+        for (size_t t = 0; t < users.size(); t++) {
+            if (t < ids.size()) users[t].Id = ids[t];
+            if (t < pos.size()) users[t].Positives = pos[t];
+            if (t < exc.size()) users[t].Exclude = exc[t];
+        }
+        for (auto &st : g_seq)
+            if (st.kind == logics::SeqStage::Lists) st.lists.resize(users.size());
+        if (bulk) {
+            stage_scores(logics::RecommendSequentialBulk(vdb(h), users, g_seq));
+            return;
+        }
+        std::vector<std::vector<logics::Score>> res;
+        for (size_t t = 0; t < users.size(); t++) res.push_back(logics::RecommendSequential(vdb(h), users[t], g_seq, t));
+        stage_scores(res);
+    });
+}
 // HipDatabase::SetNbrTableFromIndex: slot `which` of the gorse_nbr handle `nbr` from the collection's resident index; the row
 // numbering (ids in row order) is staged like a query's results
 int32_t gh_vdb_set_nbr_table_from_index(void *h, const char *collection, void *nbr, int32_t which, const char *type, const char *categories,

@@ -1123,6 +1123,217 @@ inline std::vector<std::vector<Score>> UserToUserRecommendBulk(vectors::HipDatab
     return run(users, items, hop1, hop2, type, false, {}, cacheSize, device);
 }
 
+// ---- RecommendSequential (logics/recommend.go:135-156) with limit = 0, the offline pass's form ---------------------------------
+// One configured recommender.  Lists: a list per user that exists on the host already -- recommendCollaborative's and
+// recommendExternal's cached lists as SearchScores returns them (:227-242).  Shared: one list for every user -- recommendLatest's
+// items (:180-200), recommendNonPersonalized's cached list (:202-225).  ItemToItem / UserToUser: the neighbourhood recommenders
+// over a collection of the vector database (:244-348).  Every one is filtered by the user's exclude set and cut at CacheSize, and
+// its results join the exclude set before the next one runs.
+struct SeqStage {
+    enum Kind { Lists, Shared, ItemToItem, UserToUser } kind = Lists;
+    int CacheSize = 0;
+    std::vector<std::vector<Score>> lists;  // Lists: one per user
+    std::vector<Score> shared;              // Shared
+    std::string collection, type;           // ItemToItem / UserToUser
+    std::vector<std::string> categories;    // ItemToItem
+    FeedbackMap feedback;                   // UserToUser
+};
+
+// The per-user restatement, maps and sets as the reference has them: the yardstick of RecommendSequentialBulk.
+inline std::vector<Score> RecommendSequential(vectors::HipDatabase &client, const NbrUser &user, const std::vector<SeqStage> &stages,
+                                              size_t user_pos = 0) {
+    std::vector<std::string> excluded = user.Exclude;  // r.excludeSet, kept as the list NbrUser carries
+    auto contains = [&](const std::string &id) { return std::find(excluded.begin(), excluded.end(), id) != excluded.end(); };
+    std::vector<Score> result;
+    for (const SeqStage &st : stages) {
+        std::vector<Score> scores;  // recommenderFunc(ctx)
+        if (st.kind == SeqStage::Lists || st.kind == SeqStage::Shared) {
+            static const std::vector<Score> none;
+            const std::vector<Score> &items = st.kind == SeqStage::Shared ? st.shared : user_pos < st.lists.size() ? st.lists[user_pos] : none;
+            for (const Score &item : items)  // lo.Filter: no deduplication, the set is updated after the list
+                if (!contains(item.Id) && (int)scores.size() < st.CacheSize) scores.push_back(item);
+        } else {
+            NbrUser u = user;
+            u.Exclude = excluded;
+            scores = st.kind == SeqStage::ItemToItem ? ItemToItemRecommend(client, st.collection, st.type, u, st.categories, st.CacheSize)
+                                                     : UserToUserRecommend(client, st.collection, st.type, u, st.feedback, st.CacheSize);
+        }
+        for (const Score &sc : scores) excluded.push_back(sc.Id);  // r.excludeSet.Add(score.Id)
+        result.insert(result.end(), scores.begin(), scores.end());
+    }
+    return result;
+}
+
+// The bulk twin: one candidate chain (gorse_cand) for all users.  Every id any stage can name is numbered in ascending id order --
+// one numbering for the chain and for every neighbourhood handle, so that the walk's tie order is the per-user one --, the
+// neighbourhood stages' tables come from one bulk search each, and the exclude sets and the merged lists stay on the device from
+// the first stage to the last.  List for list and bit for bit the per-user loop.
+inline std::vector<std::vector<Score>> RecommendSequentialBulk(vectors::HipDatabase &client, const std::vector<NbrUser> &users,
+                                                               const std::vector<SeqStage> &stages, int device = 0) {
+    using namespace nbr_detail;
+    const size_t nu = users.size(), ns = stages.size();
+    std::vector<std::vector<Score>> out(nu);
+    if (nu == 0 || ns == 0) return out;
+    // ---- the neighbourhood stages' tables with string ids: hop 2's rows (sorted ids) and every user's hop-1 row
+    struct Tables {
+        std::vector<std::string> rows2;                                       // the ids hop 2's rows stand for, ascending
+        std::vector<std::vector<std::pair<std::string, float>>> hop2;         // per row: (item id, raw weight)
+        std::vector<std::vector<std::pair<int32_t, float>>> hop1;             // per user: (hop-2 row, raw weight)
+        bool hop2_weighted = false;
+    };
+    std::vector<Tables> tab(ns);
+    std::vector<std::string> items;
+    std::map<std::string, std::vector<std::string>> cats;
+    int64_t capacity = 0;
+    for (size_t s = 0; s < ns; s++) {
+        const SeqStage &st = stages[s];
+        if (st.CacheSize < 1 || st.CacheSize > GORSE_CAND_MAX_K) throw std::invalid_argument("RecommendSequentialBulk serves CacheSize 1 .. 256");
+        capacity += st.CacheSize;
+        Tables &T = tab[s];
+        if (st.kind == SeqStage::Lists || st.kind == SeqStage::Shared) {
+            if (st.kind == SeqStage::Lists && st.lists.size() != nu) throw std::invalid_argument("a Lists stage needs one list per user");
+            auto take = [&](const std::vector<Score> &l) {
+                for (const Score &sc : l) {
+                    items.push_back(sc.Id);
+                    cats.emplace(sc.Id, sc.Categories);
+                }
+            };
+            if (st.kind == SeqStage::Shared) take(st.shared);
+            for (const auto &l : st.lists) take(l);
+        } else if (st.kind == SeqStage::ItemToItem) {
+            for (const NbrUser &u : users) T.rows2.insert(T.rows2.end(), u.Positives.begin(), u.Positives.end());
+            T.rows2 = sorted_unique(std::move(T.rows2));
+            const auto lists = similar_raw_bulk(client, st.collection, st.type, T.rows2, st.categories, st.CacheSize);
+            T.hop2_weighted = true;
+            for (const auto &l : lists) {
+                T.hop2.emplace_back();
+                for (const auto &nb : l) {
+                    T.hop2.back().emplace_back(nb.Id, nb.Score);
+                    items.push_back(nb.Id);
+                    cats[nb.Id] = nb.Categories;
+                }
+            }
+            for (const NbrUser &u : users) {
+                T.hop1.emplace_back();
+                for (const std::string &id : u.Positives) T.hop1.back().emplace_back(index_of(T.rows2, id), 0.0f);
+            }
+        } else {
+            std::vector<std::string> ids;
+            for (const NbrUser &u : users) ids.push_back(u.Id);
+            const auto lists = similar_raw_bulk(client, st.collection, st.type, ids, {}, st.CacheSize);
+            for (const auto &l : lists)
+                for (const auto &nb : l)
+                    if (st.feedback.count(nb.Id)) T.rows2.push_back(nb.Id);
+            T.rows2 = sorted_unique(std::move(T.rows2));
+            for (const std::string &nb : T.rows2) {
+                T.hop2.emplace_back();
+                for (const std::string &item : st.feedback.at(nb)) {
+                    T.hop2.back().emplace_back(item, 0.0f);
+                    items.push_back(item);
+                }
+            }
+            for (const auto &l : lists) {
+                T.hop1.emplace_back();
+                for (const auto &nb : l) {
+                    const int32_t r = index_of(T.rows2, nb.Id);
+                    if (r >= 0) T.hop1.back().emplace_back(r, nb.Score);  // a neighbour without feedback adds nothing
+                }
+            }
+        }
+    }
+    for (const NbrUser &u : users) items.insert(items.end(), u.Exclude.begin(), u.Exclude.end());
+    items = sorted_unique(std::move(items));
+    if (items.empty()) return out;
+
+    struct Chain {
+        gorse_cand *c = nullptr;
+        std::vector<gorse_nbr *> nbr;
+        ~Chain() {
+            for (gorse_nbr *h : nbr) gorse_nbr_destroy(h);
+            if (c) gorse_cand_destroy(c);
+        }
+    } ch;
+    auto check = [](int32_t rc) {
+        if (rc != GORSE_OK) throw std::runtime_error(gorse_hip_last_error());
+    };
+    Csr excl;
+    for (const NbrUser &u : users) {
+        for (const std::string &id : u.Exclude) excl.idx.push_back(index_of(items, id));
+        excl.close_row();
+    }
+    if (excl.idx.empty()) excl.idx.push_back(0);
+    check(gorse_cand_create(&ch.c, device, (int64_t)items.size()));
+    check(gorse_cand_begin(ch.c, (int64_t)nu, excl.ptr.data(), excl.idx.data(), (int32_t)std::min<int64_t>(capacity, INT32_MAX)));
+    for (size_t s = 0; s < ns; s++) {
+        const SeqStage &st = stages[s];
+        if (st.kind == SeqStage::Lists || st.kind == SeqStage::Shared) {
+            Csr l;
+            std::vector<double> sc;
+            auto put = [&](const std::vector<Score> &list) {
+                for (const Score &x : list) {
+                    l.idx.push_back(index_of(items, x.Id));
+                    sc.push_back(x.Value);
+                }
+                l.close_row();
+            };
+            if (st.kind == SeqStage::Shared) put(st.shared);
+            else
+                for (const auto &list : st.lists) put(list);
+            if (l.idx.empty()) l.idx.push_back(0), sc.push_back(0.0);
+            if (st.kind == SeqStage::Shared)
+                check(gorse_cand_add_shared(ch.c, l.ptr[1], l.idx.data(), sc.data(), st.CacheSize, nullptr));
+            else
+                check(gorse_cand_add_lists(ch.c, l.ptr.data(), l.idx.data(), sc.data(), st.CacheSize, nullptr));
+            continue;
+        }
+        const Tables &T = tab[s];
+        Csr hop1, hop2;
+        for (const auto &row : T.hop2) {
+            for (const auto &e : row) {
+                hop2.idx.push_back(index_of(items, e.first));
+                hop2.w.push_back(e.second);
+            }
+            hop2.close_row();
+        }
+        for (const auto &row : T.hop1) {
+            for (const auto &e : row) {
+                hop1.idx.push_back(e.first);
+                hop1.w.push_back(e.second);
+            }
+            hop1.close_row();
+        }
+        for (Csr *c : {&hop1, &hop2})
+            if (c->idx.empty()) c->idx.push_back(0), c->w.push_back(0.0f);
+        const int32_t transform = st.type == "embedding" ? GORSE_NBR_RECIP : GORSE_NBR_RAW;
+        const double scale = st.type == "auto" ? .5 : 1.0;
+        gorse_nbr *h = nullptr;
+        check(gorse_nbr_create(&h, device, (int64_t)items.size()));
+        ch.nbr.push_back(h);
+        check(gorse_nbr_set_table(h, GORSE_NBR_HOP1, (int64_t)hop1.ptr.size() - 1, hop1.ptr.data(), hop1.idx.data(),
+                                  T.hop2_weighted ? nullptr : hop1.w.data(), transform, scale));
+        check(gorse_nbr_set_table(h, GORSE_NBR_HOP2, (int64_t)hop2.ptr.size() - 1, hop2.ptr.data(), hop2.idx.data(),
+                                  T.hop2_weighted ? hop2.w.data() : nullptr, transform, scale));
+        check(gorse_cand_add_nbr(ch.c, h, nullptr, st.CacheSize, nullptr));
+    }
+    check(gorse_cand_finish(ch.c, nullptr));
+    int64_t total = 0;
+    check(gorse_cand_info(ch.c, nullptr, nullptr, &total, nullptr));
+    std::vector<int64_t> ptr(nu + 1);
+    std::vector<int32_t> got((size_t)total + 1);
+    std::vector<double> val((size_t)total + 1);
+    check(gorse_cand_get(ch.c, ptr.data(), got.data(), val.data(), nullptr));
+    for (size_t t = 0; t < nu; t++)
+        for (int64_t e = ptr[t]; e < ptr[t + 1]; e++) {
+            Score sc;
+            sc.Id = items[(size_t)got[(size_t)e]];
+            sc.Value = val[(size_t)e];
+            auto it = cats.find(sc.Id);
+            if (it != cats.end()) sc.Categories = it->second;
+            out[t].push_back(std::move(sc));
+        }
+    return out;
+}
+
 // MatrixFactorizationUsers (logics/cf.go:122-179): user id -> embedding, and its blob: WriteGob(int64 count), then per
 // user WriteString(id) (little-endian int32 length + bytes) + WriteSlice(embedding) (int32 length + little-endian float32s).
 // The reference iterates a Go map (any order); here ids go out sorted.

@@ -476,6 +476,61 @@ def UserToUserRecommendBulk(client, collection, kind, user_ids, excludes, feedba
     return _nbr_recommend(client, 1, 1, collection, kind, user_ids, [], excludes, feedback, None, cache_size)
 
 
+class SeqStage:
+    """one configured recommender of RecommendSequential (gorse_vectors.hpp logics::SeqStage).  kind "lists": lists = one list of
+    Score per user (recommendCollaborative / recommendExternal); "shared": lists = ONE list of Score for every user (recommendLatest /
+    recommendNonPersonalized); "item_to_item" / "user_to_user": a collection of the vector database, as ItemToItemRecommend /
+    UserToUserRecommend take it"""
+
+    def __init__(self, kind, cache_size, lists=None, collection="", type="", categories=None, feedback=None):
+        assert kind in ("lists", "shared", "item_to_item", "user_to_user")
+        self.kind, self.cache_size, self.lists = kind, int(cache_size), lists
+        self.collection, self.type, self.categories, self.feedback = collection, type, categories, feedback
+
+
+def _recommend_sequential(client, bulk, user_ids, positives, excludes, stages):
+    H = _logics_host()
+    H.gh_logics_seq_add_lists.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int64]
+    H.gh_logics_seq_add_nbr.argtypes = [C.c_int32, C.c_int32] + [C.c_char_p] * 5
+    H.gh_logics_seq_run.argtypes = [C.c_void_p, C.c_int32, C.c_int64] + [C.c_char_p] * 3
+    H.gh_logics_seq_clear.restype = None
+    n = len(user_ids)
+    rec = lambda lists: "\x1e".join("\n".join(map(str, e)) for e in lists).encode()  # noqa: E731
+    H.gh_logics_seq_clear()
+    try:
+        for st in stages:
+            if st.kind in ("lists", "shared"):
+                lists = [st.lists] if st.kind == "shared" else st.lists
+                sc = np.ascontiguousarray([s.Score for l in lists for s in l] or [0.0], np.float64)
+                _ck(H.gh_logics_seq_add_lists(int(st.kind == "shared"), st.cache_size, rec([[s.Id for s in l] for l in lists]),
+                                              sc.ctypes.data_as(C.POINTER(C.c_double)), sc.size))
+            else:
+                fb_users = list(st.feedback or {})
+                _ck(H.gh_logics_seq_add_nbr(int(st.kind == "user_to_user"), st.cache_size, st.collection.encode(), st.type.encode(),
+                                            "\n".join(st.categories or []).encode(), "\n".join(fb_users).encode(),
+                                            rec([st.feedback[u] for u in fb_users])))
+        _ck(H.gh_logics_seq_run(client.h, bulk, n, "\n".join(map(str, user_ids)).encode(), rec(positives or [[]] * n),
+                                rec(excludes or [[]] * n)))
+    finally:
+        H.gh_logics_seq_clear()
+    flat = _scores()
+    cuts = [int(H.gh_vdb_result_split(t)) for t in range(n + 1)]
+    return [flat[cuts[t]:cuts[t + 1]] for t in range(n)]
+
+
+def RecommendSequential(client, user_id, positives, exclude, stages):
+    """RecommendSequential (logics/recommend.go:135-156, limit = 0) for one user, with maps and sets as the reference has them: every
+    stage filtered by the exclude set and cut at its cache_size, its results added to the set before the next one runs.  A "lists"
+    stage's lists holds this user's list alone."""
+    return _recommend_sequential(client, 0, [user_id], [positives], [exclude], stages)[0]
+
+
+def RecommendSequentialBulk(client, user_ids, positives, excludes, stages):
+    """RecommendSequential for many users through one candidate chain (gorse_cand): exclude sets and merged lists stay on the device
+    from the first stage to the last; list for list and bit for bit the per-user loop"""
+    return _recommend_sequential(client, 1, user_ids, positives, excludes, stages)
+
+
 def SetNbrTableFromIndex(client, collection, kind, nbr, which, categories, n):
     """One slot of a capi.NbrRecommender filled on the device from the collection's resident index (HipDatabase::SetNbrTableFromIndex):
     row r = the QueryItemToItem / QueryUserToUser list of the collection's row r, n entries at most, under the hidden / categories

@@ -699,6 +699,81 @@ int32_t gorse_nbr_table_info(gorse_nbr *h, int32_t which, int64_t *n_rows, int64
 int32_t gorse_nbr_get_table(gorse_nbr *h, int32_t which, int64_t *indptr /*host, n_rows+1*/,
                             int32_t *indices /*host, nnz, or NULL*/, float *weights /*host, nnz, or NULL*/);
 
+/* ---- the candidate chain: RecommendSequential for many users at once (logics/recommend.go:135-156) ---------------------------
+ * The worker's offline pass (worker/pipeline.go:124-306) runs the configured recommenders in order; each is filtered by the user's
+ * exclude set, and its results join the exclude set before the next one runs; candidates whose item is gone are dropped
+ * (pipeline.go:228-243) and the rest is ranked by the CTR model.  A gorse_cand keeps the exclusion rows and the candidate rows of
+ * n_queries users on the device for such a pass: the device stages (gorse_mf_recommend, gorse_nbr_recommend) read their seen rows
+ * from it and leave their results in it, the list recommenders (latest, non-personalized, external) are a filter over it, and
+ * gorse_fm_rank_cand takes its candidates from it.  Per stage one row pointer (8 bytes per query) crosses to the host.
+ * All attached handles must number the items alike, 0 .. n_items - 1: that is the caller's responsibility, and mapping between
+ * index spaces is out of scope.  This is the reference's limit = 0 form; the early stop of limit > 0 is not provided.
+ *
+ * gorse_cand_begin starts a pass (dropping the previous one, finished or not).  Row t of the CSR (excl_indptr from 0; NULL: no
+ * rows) is what NewRecommender puts into excludeSet for query t; a row may be unsorted and repeat an item.  The rows are kept
+ * twice: the BASE rows, sorted ascending once, and the CURRENT rows, which start as a copy.  capacity = the candidates one query
+ * can come to hold.
+ * A stage gives query t a list L_t in its final order (limit = 0).  Entries whose item is in t's current row are dropped; then
+ * entries with keep[item] == 0 (recommendUserToUser's data-store filter, recommend.go:317-345: it sits behind the top-k, so what
+ * it drops is neither a candidate nor excluded later; keep == NULL keeps all); the first k survivors are appended to t's
+ * candidates with the stage's number (0, 1, ...), and their items are merged into t's current row: ascending, repeats kept.  A
+ * list that repeats an item keeps both copies (lo.Filter does not deduplicate, and the set is updated after the list).
+ *     add_mf      recommendCollaborative behind updateCollaborativeRecommend (pipeline.go:197-204): L_t = the row
+ *                 gorse_mf_recommend(mf, users, k, item_ok, seen = the BASE rows) returns -- the exclude set is taken at
+ *                 pipeline.go:200, before RecommendSequential has added anything -- and the score is the float widened to double.
+ *                 The filter then applies the current rows: as the first stage it drops nothing.  users[t] < 0 (users == NULL:
+ *                 user t): nothing for query t.
+ *     add_nbr     L_t = the row gorse_nbr_recommend(nbr, rows, k, seen = the CURRENT rows) returns, with the sums' bits; the walk
+ *                 excludes, as recommendItemToItem does.  rows[t] < 0: nothing for query t.
+ *     add_shared  recommendLatest / recommendNonPersonalized: one list of n_list <= 65536 entries for every query, scores passed
+ *                 through untouched.
+ *     add_lists   one host list per query (a CSR, indptr from 0), for external recommenders or lists read back from a cache.
+ * gorse_cand_finish compacts the candidates into a CSR, dropping entries with keep[item] == 0 (the item-exists filter of
+ * pipeline.go:228-243), and closes the pass: gorse_cand_get and gorse_fm_rank_cand need a finished pass, and a further add_* is
+ * GORSE_ERR_INVALID until the next begin.  gorse_cand_get returns that CSR (scores as doubles, the stage number per entry; any
+ * output may be NULL); gorse_cand_get_exclusion the current rows, at any time of a pass; gorse_cand_info the pass's queries, stages
+ * so far, candidates (before finish: appended so far) and current exclusion entries; gorse_cand_stats one stage's device time:
+ * the stage's own search (gorse_mf_recommend_stats / gorse_nbr_recommend_stats; 0 for a list stage) and the chain's kernels
+ * (filter, scan, append, merge).
+ * Everything is validated before anything is launched or replaced, and an error leaves the chain exactly as it was (after a
+ * GORSE_ERR_NOMEM / GORSE_ERR_HIP inside gorse_cand_begin the chain has no pass).
+ * GORSE_ERR_INVALID: k outside 1 .. GORSE_CAND_MAX_K; a stage that could overflow capacity (the candidates so far are bounded by
+ * the sum of the stages' k); more than GORSE_CAND_MAX_STAGES stages; no pass begun, or the pass finished; a malformed pointer
+ * array; n_list > 65536; a stage handle on another device, or one whose item count (the model's I, the tables' n_items, the
+ * catalogue's n_items) differs from the chain's n_items.  GORSE_ERR_RANGE: an item outside [0, n_items) in any input, a user or
+ * row outside the stage handle's range -- the stage call's own rules apply and its message is passed through. */
+#define GORSE_CAND_MAX_K 256      /* per stage; the merge sorts a stage's new items in LDS */
+#define GORSE_CAND_MAX_STAGES 255 /* the stage number of a candidate is one byte */
+typedef struct gorse_cand gorse_cand; /* one pass's exclusion and candidate rows resident on one GPU */
+int32_t gorse_cand_create(gorse_cand **c, int32_t device, int64_t n_items);
+int32_t gorse_cand_destroy(gorse_cand *c);
+int32_t gorse_cand_begin(gorse_cand *c, int64_t n_queries, const int64_t *excl_indptr /*host, n_queries+1, or NULL*/,
+                         const int32_t *excl_items /*host*/, int32_t capacity);
+int32_t gorse_cand_add_mf(gorse_cand *c, gorse_mf *mf, const int32_t *users /*host, n_queries, or NULL*/, int32_t k,
+                          const uint8_t *item_ok /*host, n_items, or NULL*/, const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_add_nbr(gorse_cand *c, gorse_nbr *nbr, const int32_t *rows /*host, n_queries, or NULL*/, int32_t k,
+                           const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_add_shared(gorse_cand *c, int64_t n_list, const int32_t *items /*host*/, const double *scores /*host*/,
+                              int32_t k, const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_add_lists(gorse_cand *c, const int64_t *indptr /*host, n_queries+1*/, const int32_t *items /*host*/,
+                             const double *scores /*host*/, int32_t k, const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_finish(gorse_cand *c, const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_info(gorse_cand *c, int64_t *n_queries, int32_t *n_stages, int64_t *n_candidates, int64_t *n_excluded);
+int32_t gorse_cand_get(gorse_cand *c, int64_t *indptr_out /*host, n_queries+1*/, int32_t *items_out, double *scores_out,
+                       uint8_t *stage_out);
+int32_t gorse_cand_get_exclusion(gorse_cand *c, int64_t *indptr_out /*host, n_queries+1*/, int32_t *items_out);
+int32_t gorse_cand_stats(gorse_cand *c, int32_t stage, double *stage_ms /*the stage's own search*/,
+                         double *chain_ms /*filter, scan, append, merge*/);
+/* gorse_fm_rank_users with the candidates taken from a finished pass: user t's list is row t of the chain's CSR (what
+ * gorse_cand_get returns), read on the device; n_users = the pass's queries.  scores_out / order_out are indexed by that CSR and
+ * hold the bits and the order gorse_fm_rank_users gives on the same lists; gorse_fm_rank_stats covers the call.  Errors as
+ * gorse_fm_rank_users; no finished pass, a chain on another device or with another n_items than the catalogue: GORSE_ERR_INVALID. */
+int32_t gorse_fm_rank_cand(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr /*host, n_queries+1*/,
+                           const int32_t *user_indices /*host*/, const float *user_values /*host*/,
+                           const int32_t *user_lead /*host, n_queries, or NULL*/, int32_t batch_size,
+                           const volatile int32_t *cancel /*host or NULL*/, float *scores_out /*host or NULL*/,
+                           int32_t *order_out /*host or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

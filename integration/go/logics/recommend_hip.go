@@ -130,8 +130,9 @@ func (r *NeighbourRecommender) SetTableFromIndex(which int, index NeighbourIndex
 }
 
 // Recommend returns for query t the n best candidates of a walk from hop-1 row rows[t] (negative: empty list) that are not in
-// seen[t] (nil: no such rows).  RecommendSequential (recommend.go:135-156) adds every earlier recommender's results to the exclude
-// set: the caller appends them to seen[t] before the next recommender's call.
+// seen[t] (nil: no such rows).  This is one recommender on its own.  RecommendSequential (recommend.go:135-156) adds every earlier
+// recommender's results to the exclude set: CandidateChain below keeps that set on the device and runs this walk as one of its
+// stages (AddNeighbour), so no caller has to append lists to seen[t] between two calls.
 func (r *NeighbourRecommender) Recommend(rows []int32, n int, seen [][]int32) ([][]NeighbourScore, error) {
 	if seen != nil && len(seen) != len(rows) {
 		return nil, errors.Errorf("Recommend: %d seen lists for %d queries", len(seen), len(rows))
@@ -170,4 +171,232 @@ func (r *NeighbourRecommender) Recommend(rows []int32, n int, seen [][]int32) ([
 		}
 	}
 	return out, nil
+}
+
+// CandidateChain is RecommendSequential (recommend.go:135-156, limit = 0) for many users with the exclude sets and the candidate
+// lists resident on the device (gorse_cand): Begin uploads what NewRecommender puts into excludeSet, every Add* is one configured
+// recommender -- filtered by the exclude set, its results added to the set before the next one runs --, Finish drops the candidates
+// whose item is gone (worker/pipeline.go:228-243), and the CTR ranker takes its candidates from the chain (RankBy).  Per stage one row
+// pointer crosses to the host.  Every attached handle numbers the items alike; mapping ids to indices stays the caller's.
+type CandidateChain struct {
+	h        *C.gorse_cand
+	numItems int
+	queries  int
+}
+
+// Candidate is one entry of a user's merged list: the recommender (stage) it came from, 0, 1, ... in Add* order.
+type Candidate struct {
+	Item  int32
+	Score float64
+	Stage uint8
+}
+
+func NewCandidateChain(device, numItems int) (*CandidateChain, error) {
+	c := &CandidateChain{numItems: numItems}
+	if rc := C.gorse_cand_create(&c.h, C.int32_t(device), C.int64_t(numItems)); rc != C.GORSE_OK {
+		return nil, nbrError("gorse_cand_create", rc)
+	}
+	return c, nil
+}
+
+func (c *CandidateChain) Close() {
+	if c.h != nil {
+		C.gorse_cand_destroy(c.h)
+		c.h = nil
+	}
+}
+
+func flatten(rows [][]int32) ([]int64, []int32) {
+	indptr := make([]int64, len(rows)+1)
+	indices := make([]int32, 0, 1)
+	for t, r := range rows {
+		indices = append(indices, r...)
+		indptr[t+1] = int64(len(indices))
+	}
+	if len(indices) == 0 {
+		indices = append(indices, 0)
+	}
+	return indptr, indices
+}
+
+func keepPtr(keep []uint8) *C.uint8_t {
+	if keep == nil {
+		return nil
+	}
+	return (*C.uint8_t)(unsafe.Pointer(&keep[0]))
+}
+
+func queryPtr(ids []int32) *C.int32_t {
+	if len(ids) == 0 {
+		return nil
+	}
+	return (*C.int32_t)(unsafe.Pointer(&ids[0]))
+}
+
+// Begin starts a pass: exclude[t] is user t's exclude set as NewRecommender builds it (any order, repeats allowed; nil: empty sets),
+// capacity the candidates one user can come to hold (the sum of the stages' n at least).
+func (c *CandidateChain) Begin(numQueries int, exclude [][]int32, capacity int) error {
+	var ptr *C.int64_t
+	var idx *C.int32_t
+	if exclude != nil {
+		if len(exclude) != numQueries {
+			return errors.Errorf("Begin: %d exclude sets for %d queries", len(exclude), numQueries)
+		}
+		indptr, indices := flatten(exclude)
+		ptr = (*C.int64_t)(unsafe.Pointer(&indptr[0]))
+		idx = (*C.int32_t)(unsafe.Pointer(&indices[0]))
+	}
+	if rc := C.gorse_cand_begin(c.h, C.int64_t(numQueries), ptr, idx, C.int32_t(capacity)); rc != C.GORSE_OK {
+		return nbrError("gorse_cand_begin", rc)
+	}
+	c.queries = numQueries
+	return nil
+}
+
+// AddCollaborative is recommendCollaborative behind updateCollaborativeRecommend (pipeline.go:197-204): the search runs under the
+// exclude sets as Begin got them, the chain's filter applies the current ones.  mf is the model's gorse_mf handle (model/cf/hip.go);
+// users[t] < 0: nothing for query t; itemOK nil: IsItemPredictable.
+func (c *CandidateChain) AddCollaborative(mf unsafe.Pointer, users []int32, n int, itemOK, keep []uint8) error {
+	rc := C.gorse_cand_add_mf(c.h, (*C.gorse_mf)(mf), queryPtr(users), C.int32_t(n), keepPtr(itemOK), keepPtr(keep))
+	if rc != C.GORSE_OK {
+		return nbrError("gorse_cand_add_mf", rc)
+	}
+	return nil
+}
+
+// AddNeighbour is recommendItemToItem or recommendUserToUser: NeighbourRecommender.Recommend with seen = the chain's current
+// exclude sets, read on the device.  keep is recommendUserToUser's data-store filter (:317-345; nil: keep all): what it drops is
+// neither a candidate nor excluded later.
+func (c *CandidateChain) AddNeighbour(r *NeighbourRecommender, rows []int32, n int, keep []uint8) error {
+	if rc := C.gorse_cand_add_nbr(c.h, r.h, queryPtr(rows), C.int32_t(n), keepPtr(keep)); rc != C.GORSE_OK {
+		return nbrError("gorse_cand_add_nbr", rc)
+	}
+	return nil
+}
+
+// AddShared is recommendLatest / recommendNonPersonalized: one list, in its final order, for every user.
+func (c *CandidateChain) AddShared(list []NeighbourScore, n int, keep []uint8) error {
+	items := make([]int32, len(list)+1)
+	scores := make([]float64, len(list)+1)
+	for e, s := range list {
+		items[e], scores[e] = s.Item, s.Score
+	}
+	rc := C.gorse_cand_add_shared(c.h, C.int64_t(len(list)), (*C.int32_t)(unsafe.Pointer(&items[0])), (*C.double)(unsafe.Pointer(&scores[0])),
+		C.int32_t(n), keepPtr(keep))
+	if rc != C.GORSE_OK {
+		return nbrError("gorse_cand_add_shared", rc)
+	}
+	return nil
+}
+
+// AddLists is a recommender whose lists exist on the host: an external recommender, or lists read back from a cache.
+func (c *CandidateChain) AddLists(lists [][]NeighbourScore, n int, keep []uint8) error {
+	if len(lists) != c.queries {
+		return errors.Errorf("AddLists: %d lists for %d queries", len(lists), c.queries)
+	}
+	indptr := make([]int64, len(lists)+1)
+	items := make([]int32, 0, 1)
+	scores := make([]float64, 0, 1)
+	for t, l := range lists {
+		for _, s := range l {
+			items = append(items, s.Item)
+			scores = append(scores, s.Score)
+		}
+		indptr[t+1] = int64(len(items))
+	}
+	if len(items) == 0 {
+		items, scores = append(items, 0), append(scores, 0)
+	}
+	rc := C.gorse_cand_add_lists(c.h, (*C.int64_t)(unsafe.Pointer(&indptr[0])), (*C.int32_t)(unsafe.Pointer(&items[0])),
+		(*C.double)(unsafe.Pointer(&scores[0])), C.int32_t(n), keepPtr(keep))
+	if rc != C.GORSE_OK {
+		return nbrError("gorse_cand_add_lists", rc)
+	}
+	return nil
+}
+
+// Finish closes the pass; exists[i] == 0 drops item i's candidates (pipeline.go:228-243; nil: all exist).
+func (c *CandidateChain) Finish(exists []uint8) error {
+	if rc := C.gorse_cand_finish(c.h, keepPtr(exists)); rc != C.GORSE_OK {
+		return nbrError("gorse_cand_finish", rc)
+	}
+	return nil
+}
+
+// Candidates returns the finished pass: every user's merged list in stage order.
+func (c *CandidateChain) Candidates() ([][]Candidate, error) {
+	var nq, nc C.int64_t
+	if rc := C.gorse_cand_info(c.h, &nq, nil, &nc, nil); rc != C.GORSE_OK {
+		return nil, nbrError("gorse_cand_info", rc)
+	}
+	indptr := make([]int64, int(nq)+1)
+	items := make([]int32, int(nc)+1)
+	scores := make([]float64, int(nc)+1)
+	stages := make([]uint8, int(nc)+1)
+	rc := C.gorse_cand_get(c.h, (*C.int64_t)(unsafe.Pointer(&indptr[0])), (*C.int32_t)(unsafe.Pointer(&items[0])),
+		(*C.double)(unsafe.Pointer(&scores[0])), (*C.uint8_t)(unsafe.Pointer(&stages[0])))
+	if rc != C.GORSE_OK {
+		return nil, nbrError("gorse_cand_get", rc)
+	}
+	out := make([][]Candidate, int(nq))
+	for t := range out {
+		out[t] = make([]Candidate, 0, indptr[t+1]-indptr[t])
+		for e := indptr[t]; e < indptr[t+1]; e++ {
+			out[t] = append(out[t], Candidate{Item: items[e], Score: scores[e], Stage: stages[e]})
+		}
+	}
+	return out, nil
+}
+
+// ExcludeSets returns the current exclude sets, ascending, at any time of a pass.
+func (c *CandidateChain) ExcludeSets() ([][]int32, error) {
+	var nq, nx C.int64_t
+	if rc := C.gorse_cand_info(c.h, &nq, nil, nil, &nx); rc != C.GORSE_OK {
+		return nil, nbrError("gorse_cand_info", rc)
+	}
+	indptr := make([]int64, int(nq)+1)
+	items := make([]int32, int(nx)+1)
+	if rc := C.gorse_cand_get_exclusion(c.h, (*C.int64_t)(unsafe.Pointer(&indptr[0])), (*C.int32_t)(unsafe.Pointer(&items[0]))); rc != C.GORSE_OK {
+		return nil, nbrError("gorse_cand_get_exclusion", rc)
+	}
+	out := make([][]int32, int(nq))
+	for t := range out {
+		out[t] = items[indptr[t]:indptr[t+1]]
+	}
+	return out, nil
+}
+
+// UserRows is the user side of rankByClickTroughRate as gorse_fm_rank_users takes it: one feature row per query.
+type UserRows struct {
+	Indptr  []int64
+	Indices []int32
+	Values  []float32
+	Lead    []int32 // nil: 0 for every user
+}
+
+// RankBy scores and orders every user's finished candidates by the CTR model (gorse_fm_rank_cand; fm is the model's gorse_fm handle,
+// model/ctr/fm_hip.go, with its item catalogue resident): scores and order are flat in the layout of Candidates(), order[p + r] = the
+// position inside the user's list of its r-th ranked candidate.
+func (c *CandidateChain) RankBy(fm unsafe.Pointer, users UserRows, batchSize int) ([]float32, []int32, error) {
+	var nc C.int64_t
+	if rc := C.gorse_cand_info(c.h, nil, nil, &nc, nil); rc != C.GORSE_OK {
+		return nil, nil, nbrError("gorse_cand_info", rc)
+	}
+	scores := make([]float32, int(nc)+1)
+	order := make([]int32, int(nc)+1)
+	indices, values := users.Indices, users.Values
+	if len(indices) == 0 {
+		indices, values = []int32{0}, []float32{0}
+	}
+	var lead *C.int32_t
+	if users.Lead != nil {
+		lead = (*C.int32_t)(unsafe.Pointer(&users.Lead[0]))
+	}
+	rc := C.gorse_fm_rank_cand((*C.gorse_fm)(fm), c.h, (*C.int64_t)(unsafe.Pointer(&users.Indptr[0])), (*C.int32_t)(unsafe.Pointer(&indices[0])),
+		(*C.float)(unsafe.Pointer(&values[0])), lead, C.int32_t(batchSize), nil, (*C.float)(unsafe.Pointer(&scores[0])),
+		(*C.int32_t)(unsafe.Pointer(&order[0])))
+	if rc != C.GORSE_OK {
+		return nil, nil, nbrError("gorse_fm_rank_cand", rc)
+	}
+	return scores[:nc], order[:nc], nil
 }
