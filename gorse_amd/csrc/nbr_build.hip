@@ -1,7 +1,7 @@
 // nbr_build.hip -- neighbour tables of gorse_nbr built on the device from a similarity search's device-resident results:
 // gorse_nbr_set_table_from_topk / _from_sparse, and the read-back of either kind of table (gorse_nbr_get_table / _table_info).
 //
-// The searches (topk.hip / topk_mfma.hip / sparse.hip) leave a block of result lists on the device: per query k = n + 1 (index,
+// The searches (topk.hip / topk_mfma.hip and its units / sparse.hip) leave a block of result lists on the device: per query k = n + 1 (index,
 // distance or score) pairs in rank order and a count.  QueryItemToItem / QueryUserToUser (item_to_item.go:72-86, user_to_user.go:
 // 63-80) make a neighbour list of such a list by one ordered walk: skip the row itself, skip scores <= 0 for the Dot kinds, stop
 // after n.  Here one wave walks one list -- order kept by ballot and prefix count -- into a staging area of stride n; the kept

@@ -1,5 +1,5 @@
 // rank_keys.hpp -- the integer encodings the ranking kernels sort and compare by, usable on host and device: the kernels
-// include it (topk_mfma.hip, sparse_kernels.hpp), and so does the host library's test hook (gorse_amd/host/gorse_host_capi.cpp:
+// include it (topk_mfma_internal.hpp for the units of path B, sparse_kernels.hpp), and so does the host library's test hook (gorse_amd/host/gorse_host_capi.cpp:
 // gh_test_rank_key), so that their order / round-trip properties are checked without a GPU (tests/test_rank_keys_cpu.py).
 #pragma once
 #include <cstdint>

@@ -650,7 +650,7 @@ extern "C" int32_t gorse_hip_test_topk_resweeps(gorse_topk *h, int64_t *n) {
     return GORSE_OK;
 }
 
-// probe: did the main sweep of the last search (its last chunk) take the symmetric form (csrc/topk_mfma.hip, SYM)
+// probe: did the main sweep of the last search (its last chunk) take the symmetric form (csrc/topk_sweep.hip, SYM)
 extern "C" int32_t gorse_hip_test_topk_last_symmetric(gorse_topk *h, int32_t *sym) {
     if (!h || !sym) return fail(GORSE_ERR_INVALID, "NULL argument");
     *sym = h->last_sym ? 1 : 0;

@@ -1,12 +1,13 @@
 // topk_internal.hpp -- the gorse_topk handle shared by topk.hip (path A: exact VALU scan + literal
-// heaps) and topk_mfma.hip (path B: bf16 MFMA candidate sweep + exact rescoring).
+// heaps) and topk_mfma.hip with its units topk_sweep / topk_rescore / topk_tie / topk_tri.hip (path B: bf16 MFMA candidate sweep + exact
+// rescoring; topk_mfma_internal.hpp is what those units share).
 #pragma once
 #include "cf_device.hpp"
 
 #define GORSE_PROF_TOPK_NCLASSES 6
 
 namespace gorse {
-struct TopkChunkState;  // topk_mfma.hip: what the stages of one chunk of an MFMA search share
+struct TopkChunkState;  // topk_mfma_internal.hpp: what the stages of one chunk of an MFMA search share
 }
 
 struct gorse_topk {
@@ -21,7 +22,7 @@ struct gorse_topk {
     gorse::DevBuf<int64_t> qidx;
     gorse::DevBuf<int32_t> out_idx, out_cnt, heap_v, scan_literal;
     gorse::DevBuf<float> out_dist, heap_w;
-    // ---- path B (topk_mfma.hip) ----
+    // ---- path B (topk_mfma.hip and its units) ----
     bool mfma_ok = false;          // operands built and the data admits a rigorous error bound
     int kp = 0;                    // k-steps of 16 of the MFMA operands (KPAD = 16 * kp)
     float err_coef = 0.0f;         // |approx - reference| <= err_coef * |q| * |x| (dot of the operands)
@@ -63,14 +64,14 @@ struct gorse_topk {
     int kernel_metric() const { return bf16_order ? 3 : metric; }
     int64_t n_fallback = 0, n_tie = 0, n_resweep = 0;  // of the last search: path A rows, tie replays, warm starts swept again
     gorse::DevBuf<float> f0, f1;                       // warm-start thresholds of a chunk (topk_mfma_search): pilot, pre-pilot
-    // the symmetric all-pairs sweep (topk_mfma.hip, SYM): per query a foreign candidate list and its counter, the raw-score form
+    // the symmetric all-pairs sweep (topk_sweep.hip, SYM): per query a foreign candidate list and its counter, the raw-score form
     // of the thresholds; last_sym: did the last search's (last chunk's) main sweep take the symmetric form
     gorse::DevBuf<uint2> fbuf;
     gorse::DevBuf<int32_t> fcnt;
     gorse::DevBuf<float> f0raw;
     gorse::DevBuf<unsigned long long> sym_stats;  // counters of the last symmetric search (gorse_hip_test_topk_sym_stats)
     bool last_sym = false;
-    // the state of the search in progress (topk_mfma.hip): its stages run back to back in topk_mfma_search, call by call in the
+    // the state of the search in progress (topk_mfma_internal.hpp: TopkChunkState): its stages run back to back in topk_mfma_search, call by call in the
     // triangle-sharded search (gorse_topk_tri_*), whose message buffers follow
     gorse::TopkChunkState *cstate = nullptr;
     gorse::TopkChunkState *chunk_state();

@@ -1,4 +1,4 @@
-// topk_sym.hpp -- the tile schedule of the symmetric all-pairs sweep (topk_mfma.hip, topk_sweep_kernel<..., SYM>), usable on
+// topk_sym.hpp -- the tile schedule of the symmetric all-pairs sweep (topk_sweep.hip, topk_sweep_kernel<..., SYM>), usable on
 // host and device: the kernel includes it, and so does the host library's test hook (gorse_amd/host/gorse_host_capi.cpp:
 // gh_test_topk_sym_cover), so that "every (query, row) pair is covered exactly once" is checked without a GPU
 // (tests/test_topk_sym_schedule_cpu.py).

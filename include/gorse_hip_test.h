@@ -68,7 +68,7 @@ int32_t gorse_hip_test_topk_get_flags(gorse_topk *h, uint8_t *flags /*host*/, in
 int32_t gorse_hip_test_topk_get_foreign_counts(gorse_topk *h, int32_t *counts /*host*/, int64_t n);
 /* the warm-start thresholds of the last search's last chunk (the first n queries) */
 int32_t gorse_hip_test_topk_get_thresholds(gorse_topk *h, float *out /*host*/, int64_t n);
-/* with GORSE_TEST_TOPK_REPLAY_COUNTERS set, the tie replay (csrc/topk_mfma.hip topk_tie_replay_lane_kernel) of a search counts its work; this
+/* with GORSE_TEST_TOPK_REPLAY_COUNTERS set, the tie replay (csrc/topk_tie.hip topk_tie_replay_lane_kernel) of a search counts its work; this
  * returns the sixteen counters of the handle's last such replay, over its queries: [0] s_memtime ticks summed, [1] the most of one
  * query, [2] recorded entries summed, [3] queries, [4] heap pushes, [5] gaps evaluated (T^gap), [6] those where T was not the
  * identity, [7] literal applications of T summed, [8] the most of one query, [9] the most recorded entries of one query,

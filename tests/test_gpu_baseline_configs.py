@@ -245,7 +245,7 @@ def test_c4_rows_against_the_oracle(oracle):
 
 def test_c4_square_sweep_rows_against_the_oracle(oracle):
     """The SQUARE form of the MFMA sweep at C4's size: a call of 1024 queries that does NOT start on a 128-row boundary (500,000 mod
-    128 = 32) takes the square sweep (pilot + main sweep, exact rescoring, tie replay: csrc/topk_mfma.hip) -- asserted through the
+    128 = 32) takes the square sweep (pilot + main sweep, exact rescoring, tie replay: csrc/topk_mfma.hip and the units it drives) -- asserted through the
     handle's profile, which must show sweep launches, and `last_symmetric()`, which must be false -- and 128 of its rows (every eighth)
     equal Bruteforce.SearchIndex restated (common/ann/bruteforce.go:39-83) in indices AND distance bits.  (Until round 5 this was "the
     kernel bench.py times at C4"; since the symmetric form exists, that one is test_c4_full_symmetric_pass_rows_against_the_oracle.)"""

@@ -1,7 +1,7 @@
-"""GPU parity of top-k path B (gorse_amd/csrc/topk_mfma.hip) at every operand depth its sweep is instantiated for.
+"""GPU parity of top-k path B (gorse_amd/csrc/topk_mfma.hip; its sweep: topk_sweep.hip) at every operand depth its sweep is instantiated for.
 
 The sweep is a template over KP, the operand depth in k-steps of 16: kSupportedKP = {1, 2, 3, 4, 6, 8, 12, 16, 24}, with another tile
-form, workgroup shape and column-block count per depth (launch_sweep, sweep_waves, sweep_dma).  tests/test_gpu_topk_mfma.py reaches
+form, workgroup shape and column-block count per depth (launch_sweep; sweep_waves and sweep_dma of topk_plan.hpp).  tests/test_gpu_topk_mfma.py reaches
 the depths its row widths happen to give; here every depth is reached in both dtypes, with an operand matrix that is the bf16 index
 itself (d == 16 KP), that is full (fp32, 3 d == 16 KP) and that ends in whole k-steps of zeros (pad_bf16_kernel / split_f32_kernel),
 through the main sweep and through the tie path's history sweep.  The bar is path A's: the indices and the fp32 distance bits of

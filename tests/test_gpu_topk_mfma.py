@@ -1,4 +1,4 @@
-"""GPU parity of top-k path B (bf16 MFMA candidate sweep + exact rescoring, gorse_amd/csrc/topk_mfma.hip).
+"""GPU parity of top-k path B (bf16 MFMA candidate sweep + exact rescoring, gorse_amd/csrc/topk_mfma.hip and the units it drives: topk_sweep / topk_rescore / topk_tie.hip).
 
 The bar is the same as for path A: the indices AND the fp32 distances ann.Bruteforce returns
 (common/ann/bruteforce.go:39-83), bit for bit, ties included; the oracle is the checker.  Path B is forced
@@ -199,7 +199,7 @@ V_COLD_SLICES = capi.TOPK_COLD_SLICES
 
 @pytest.mark.parametrize("metric", [capi.METRIC_COSINE, capi.METRIC_NEG_DOT, capi.METRIC_EUCLIDEAN])
 def test_history_slices_started_from_the_main_sweeps_lists(oracle, metric):
-    """Round 6 (csrc/topk_mfma.hip: tie_warm_kernel, sweep_hist_dma).  A bf16 index of d = 128 (eight k-steps: the history sweep takes the
+    """Round 6 (csrc/topk_tie.hip: tie_warm_kernel; csrc/topk_plan.hpp: sweep_hist_dma).  A bf16 index of d = 128 (eight k-steps: the history sweep takes the
     main sweep's eight-wave LDS-DMA form) with planted duplicates, eight row slices forced on a small index: every slice but the first
     starts from the bound the main sweep's list entries in front of it prove (default) -- against the slices that start cold
     (TOPK_COLD_SLICES), every row of the two forms compared, and a sample of tie rows and plain rows against the oracle."""

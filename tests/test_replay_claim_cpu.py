@@ -1,4 +1,4 @@
-"""The claim behind topk_tie_replay_lane_kernel (gorse_amd/csrc/topk_mfma.hip), checked on the CPU with Go's container/heap
+"""The claim behind topk_tie_replay_lane_kernel (gorse_amd/csrc/topk_tie.hip), checked on the CPU with Go's container/heap
 rules restated in pure Python (same rules as gorse_amd/csrc/goheap.hpp / common/heap/pq.go):
 
   Bruteforce's queue (bruteforce.go:46-53: Push, then Pop once it holds more than k) ends in the same heap ARRAY

@@ -1,12 +1,20 @@
 """The tables of tests/topk_cases.py held against the kernels' sources (no GPU): every operand depth path B's sweep is instantiated for
-(kSupportedKP and the cases of dispatch_sweep in csrc/topk_mfma.hip) is named by the depth tests in both dtypes, so that a depth added
-later cannot arrive untested, and the widths of the wide-row tests contain both sides of every edge of csrc/topk.hip's scan_groups."""
+(kSupportedKP in csrc/topk_plan.hpp and the cases of dispatch_sweep in csrc/topk_sweep.hip) is named by the depth tests in both dtypes,
+so that a depth added later cannot arrive untested, and the widths of the wide-row tests contain both sides of every edge of
+csrc/topk.hip's scan_groups.  The rules of csrc/topk_plan.hpp themselves -- the sweep's launch geometry at every instantiated shape,
+the depth rule, the symmetric form's predicate, the triangle's geometry, the slice and queries-per-wave rules -- are checked by value
+in tests/cpp/topk_plan_main.cpp, which is built and run here under AddressSanitizer and UBSan."""
 import os
 import re
+import shutil
+import subprocess
+
+import pytest
 
 import topk_cases as tc
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gorse_amd", "csrc")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gorse_amd", "csrc")
 
 
 def source(name):
@@ -23,14 +31,27 @@ def ints(s):
     return [int(x) for x in re.findall(r"\d+", s)]
 
 
+@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("clang++") is None, reason="no host C++ compiler")
+def test_plan_rules_under_sanitizers(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    exe = str(tmp_path / "topk_plan")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "cpp", "topk_plan_main.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "topk_plan ok" in out.stdout
+
+
 def test_depth_table_names_every_instantiated_depth_in_both_dtypes():
-    text = source("topk_mfma.hip")
-    supported = ints(re.search(r"kSupportedKP\[\]\s*=\s*\{([^}]*)\}", text).group(1))
-    dispatched = ints(" ".join(re.findall(r"case (\d+):", function_body(text, "int32_t dispatch_sweep("))))
+    plan = source("topk_plan.hpp")
+    supported = ints(re.search(r"kSupportedKP\[\]\s*=\s*\{([^}]*)\}", plan).group(1))
+    dispatched = ints(" ".join(re.findall(r"case (\d+):", function_body(source("topk_sweep.hip"), "int32_t gorse::dispatch_sweep("))))
     assert supported == sorted(supported) and supported == dispatched == list(tc.SUPPORTED_KP)
-    # the depth of an index as topk_mfma_prepare derives it, restated by topk_cases.expected_kp
-    prepare = function_body(text, "int32_t topk_mfma_prepare(")
-    assert "ceil_div(bf ? d : 3 * (int64_t)d, 16)" in prepare and "if (c >= need)" in prepare
+    # the depth of an index as topk_mfma_prepare derives it (operand_depth, whose values tests/cpp/topk_plan_main.cpp checks at the
+    # same widths), restated by topk_cases.expected_kp
+    depth = function_body(plan, "inline int operand_depth(")
+    assert "((bf16 ? d : 3 * (int64_t)d) + 15) / 16" in depth and "if (c >= need) return c;" in depth
+    assert "const int kp = operand_depth(bf, d);" in function_body(source("topk_mfma.hip"), "int32_t topk_mfma_prepare(")
     assert [tc.expected_kp(tc.BF16, d) for d in (1, 16, 17, 80, 81, 384, 385)] == [1, 1, 2, 6, 6, 24, None]
     assert [tc.expected_kp(tc.F32, d) for d in (1, 5, 6, 42, 43, 128, 129)] == [1, 1, 2, 8, 12, 24, None]
     for dtype in (tc.F32, tc.BF16):
@@ -52,7 +73,7 @@ def test_depth_table_names_every_instantiated_depth_in_both_dtypes():
 
 
 def test_tie_cases_name_every_history_sweep_shape():
-    text = source("topk_mfma.hip")
+    text = source("topk_plan.hpp")
     supported = ints(re.search(r"kSupportedKP\[\]\s*=\s*\{([^}]*)\}", text).group(1))
     dma = ints(re.search(r"constexpr bool sweep_hist_dma\(int kp\) \{ return ([^;]*); \}", text).group(1))
     waves = re.search(r"constexpr int sweep_waves\(bool hist, int kp\) \{ return ([^;]*); \}", text).group(1)

@@ -2,7 +2,7 @@
 kept apart from the GPU modules so that tests/test_topk_depth_table_cpu.py can hold the tables against the kernels' sources, and
 so that the inputs can be examined with the oracle alone.
 
-Path B (csrc/topk_mfma.hip) instantiates its sweep per operand depth KP: ceil(d / 16) k-steps for a bf16 index, ceil(3 d / 16) for an
+Path B (csrc/topk_mfma.hip; the sweep: csrc/topk_sweep.hip) instantiates its sweep per operand depth KP: ceil(d / 16) k-steps for a bf16 index, ceil(3 d / 16) for an
 fp32 index (hi | lo | hi split), rounded up to the next supported depth.  Path A (csrc/topk.hip) takes 16, 8, 4, 2 or 1 sixteen-lane
 groups per workgroup as the row width grows (scan_groups)."""
 import numpy as np
@@ -10,12 +10,12 @@ import numpy as np
 from gorse_amd import capi
 
 F32, BF16 = capi.DTYPE_F32, capi.DTYPE_BF16
-SUPPORTED_KP = (1, 2, 3, 4, 6, 8, 12, 16, 24)  # kSupportedKP of csrc/topk_mfma.hip (test_topk_depth_table_cpu.py compares)
+SUPPORTED_KP = (1, 2, 3, 4, 6, 8, 12, 16, 24)  # kSupportedKP of csrc/topk_plan.hpp (test_topk_depth_table_cpu.py compares)
 METRICS = (capi.METRIC_NEG_DOT, capi.METRIC_COSINE, capi.METRIC_EUCLIDEAN)
 
 
 def expected_kp(dtype, d):
-    """topk_mfma_prepare: the operand depth of an index, None when it is too deep for path B"""
+    """topk_mfma_prepare (operand_depth of csrc/topk_plan.hpp): the operand depth of an index, None when it is too deep for path B"""
     need = -(-(d if dtype == BF16 else 3 * d) // 16)
     return next((c for c in SUPPORTED_KP if c >= need), None)
 
