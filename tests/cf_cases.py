@@ -59,6 +59,20 @@ def als_half_fp64(A, B, ptr, idx, bptr, w, reg, rows):
     return A[rows]
 
 
+# What ONE grid of each capped matrix-factorisation launch holds before its kernel's grid-stride loop takes a second step.  The tests of
+# tests/test_gpu_cf_past_one_grid.py size their inputs from these literals; tests/test_mf_grid_caps_cpu.py holds every one of them
+# against the launcher's own text, so a cap raised later fails a test instead of leaving the strided iterations unvisited again.
+GRID_USER_RUNS = 65_536       # launch_update_users: 256 * 16 workgroups x 16 groups, one user run each (nFactors 8: two per group)
+GRID_USER_RUNS_D8 = 131_072
+GRID_SAMPLES = 65_536         # launch_update_mode: 256 * 16 workgroups x 16 groups, one sample each
+GRID_SCORE_PAIRS = 131_072    # mf_score_device: 256 * 32 workgroups x 16 groups, one pair each
+GRID_RANK_LISTS = 4_096       # mf_rank_device: expand_users_kernel, one workgroup per list
+GRID_DELTA_FLOATS = 2_097_152  # mf_delta_export_async / _import_async: 2048 workgroups x 256 threads x one float4
+GRID_SORT_SAMPLES = 524_288   # launch_user_sort (bpr_rank_kernel, bpr_scatter_by_kernel): 256 * 8 workgroups x 256 threads
+GRID_FOLD_ELEMENTS = 131_072  # bpr_fold_kernel behind a per-sample launch: 512 workgroups x 256 threads, one row element each
+SCAN_ONE_WORKGROUP = 32_768   # exclusive_scan_i32: up to 16 tiles of 2048 counters by scan_small_kernel, three kernels beyond
+
+
 def rel_err(a, b):
     """Largest element error relative to max(|reference element|, rms of the reference matrix):
     plain element-wise relative error, except that elements far below the matrix scale are
