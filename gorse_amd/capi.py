@@ -193,6 +193,8 @@ SIGNATURES = {
     "gorse_hip_test_set_bpr_acc_fold_every": (None, [C.c_int32]),
     "gorse_hip_test_bpr_acc_state": (C.c_int32, [_vp, _vp, _vp]),
     "gorse_hip_test_bpr_item_classes": (C.c_int32, [_vp, _vp, _vp]),
+    "gorse_hip_test_bpr_fold_tier_stats": (C.c_int32, [_vp, _vp]),
+    "gorse_hip_test_set_bpr_folder_timeout": (None, [C.c_int64]),
     "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
     "gorse_hip_test_set_fm_rank": (None, [C.c_int64, C.c_int32]),
     "gorse_hip_test_fm_rank_sort": (C.c_int32, [_vp, C.c_int64, _i64p, _f32p, _i32p]),

@@ -798,7 +798,9 @@ __device__ __forceinline__ void update_elem(float *pu, float *qi, float *qj, int
 // on a table of that size, onto rows nobody reads at 311: profiles/r04_s_probe_atomics3.txt).  The tier's slots follow the hot ones in
 // items / meta (n_hot .. n_hot + n_acc) and have folder workgroups of their own, kFolderBlocksAcc of them behind the hot tier's, which
 // pass every kDefaultAccFoldEvery-th fold period; the hot tier's folders and their period are what they are without the tier.  In the last
-// pass all folder workgroups share the rows of both tiers.
+// pass all folder workgroups share the rows of both tiers.  That is the ATOMIC fold: the per-sample kernel's, a handle's without the
+// tier, a launch's with the store route open.  A user-run launch on a handle with the tier and the store route closed has no worker
+// that writes Q and folds in the SOLE-WRITER form (below kFolderTimeout): loads and stores instead of the exchange and the add.
 constexpr int kHotReplicas = GORSE_HOT_REPLICAS;
 constexpr int kFolderBlocks = 32;
 // the tier's folders: 2,780 rows x 64 elements at C2 are 178 K (slot, element) pairs, 22 per thread of 32 workgroups and pass -- on
@@ -821,6 +823,23 @@ uint32_t g_fold_period = kDefaultFoldPeriod;  // gorse_hip_test_set_bpr_fold_per
 // folders that have waited this long (10 s) for the workers stop waiting (a launch of the largest chunk takes ~0.13 s): a last pass
 // while workers still run leaves some updates in the replicas, where the next launch's folders find them -- never a hung device
 constexpr uint64_t kFolderTimeout = 1000000000ull;
+uint64_t g_folder_timeout = kFolderTimeout;  // gorse_hip_test_set_bpr_folder_timeout
+// The SOLE-WRITER fold.  On a handle with the accumulated tier every item has a row, so in a user-run launch without the store route
+// no worker instruction writes Q: the folders are the only writers of the Q rows they fold, and their atomics -- an exchange per row
+// and an add onto Q per pass, the add the only atomic of the launch that lands on rows the workers gather -- are not needed.  Such a
+// launch (launch_update_users decides: HotRows::sole) folds with loads and stores instead.  At its start every folder thread copies
+// the Q elements it owns into `base` (a table of (n_hot + n_acc) x d floats of the handle's, private to bpr.hip); a periodic pass
+// LOADS the slot's rows and stores Q <- base + their sum -- nothing is zeroed, the rows grow for the length of the launch -- and the
+// last pass exchanges the rows with zero and stores Q <- base + the sum of what it took.  The exchange stays there on purpose: it
+// leaves every row zero without a race, and after a last pass made while workers still run (the timeout) whatever lands behind it
+// stays in the row, where the next launch -- which starts from base = Q -- finds it.  What makes the stores safe is ownership: every
+// (slot, element group) belongs to ONE thread for the whole launch, periodic and last pass alike (hot_rows.hpp fold_share), so no
+// workgroup still in a periodic pass can overwrite another's final value.  Q = base + (the launch's updates of the row) is one of the
+// associations a Hogwild launch produces anyway, and with one update per row the bits of the atomic form.  Every other launch -- a
+// handle without the tier, the store route, the per-sample kernel -- keeps the atomic fold below.
+#ifndef GORSE_BPR_FOLD_SOLE_WRITER
+#define GORSE_BPR_FOLD_SOLE_WRITER 1  // A/B: 0 = every launch folds with atomics
+#endif
 
 struct HotRows {
     const int32_t *slot;   // I entries: class of an item -- hot_code(first replica row, log2 R_s) of a HOT item, hot_code(its row, 0)
@@ -835,7 +854,28 @@ struct HotRows {
     uint32_t period;       // wall-clock ticks between two folder passes
     int n_acc;             // slots of the accumulated tier (0: the handle has none)
     int acc_every;         // fold periods between two passes of the tier's folders
+    float *base;           // n_hot + n_acc rows of d floats: Q's rows of the slots as the launch found them (the sole-writer fold)
+    int sole;              // the launch folds as Q's sole writer (launch_update_users)
+    uint64_t timeout;      // wall-clock ticks after which the folders stop waiting for the workers
 };
+
+// a group of the sole-writer fold (kFoldGroup = 2 floats, 8-byte aligned: d and the element are even): agent-scope load, store and
+// exchange with zero, the flavours the gathers and the cold-store route use across XCDs; the exchange per element, so that it meets
+// the workers' fp32 adds as the atomic fold's does
+static_assert(kFoldGroup == 2 && kFolderThreads == kBlock, "the sole-writer fold moves float pairs, one per thread of an update workgroup");
+__device__ __forceinline__ float2 load_pair(const float *p) {
+    const unsigned long long x = __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return make_float2(__uint_as_float((unsigned)x), __uint_as_float((unsigned)(x >> 32)));
+}
+__device__ __forceinline__ void store_pair(float *p, float2 v) {
+    __hip_atomic_store((unsigned long long *)p, (unsigned long long)__float_as_uint(v.x) | ((unsigned long long)__float_as_uint(v.y) << 32),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float2 drain_pair(float *p) {
+    const float x = __hip_atomic_exchange(p, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float y = __hip_atomic_exchange(p + 1, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return make_float2(x, y);
+}
 
 // the replica row that group `group` adds a hot item's update to (code: the item's hot_slot word)
 __device__ __forceinline__ float *hot_row(const HotRows &hot, int32_t code, int64_t group) {
@@ -927,12 +967,75 @@ __device__ __forceinline__ void fold_acc_pass(const HotRows &hot, float *Q, int 
     }
 }
 
+// The sole-writer fold (above HotRows).  sh: this thread's share of its tier (hot_rows.hpp fold_share).
+// launch start: base <- Q for the groups this thread owns -- nobody else writes these elements of Q during the launch
+__device__ __forceinline__ void fold_sole_begin(const HotRows &hot, const float *Q, const FoldShare &sh) {
+    const int d = hot.d, groups = fold_groups(sh, d);
+    for (int g = sh.tid; g < groups; g += sh.nthreads) {
+        const int slot = fold_group_slot(sh, g, d), e = fold_group_elem(g, d);
+        *(float2 *)(hot.base + (int64_t)slot * d + e) = load_pair(Q + (int64_t)hot.items[slot] * d + e);
+    }
+}
+// one pass over the groups this thread owns: Q <- base + the sum of the slot's rows (at most ROWS of them: kHotReplicas in the hot
+// tier, 1 in the accumulated tier), the rows loaded in a periodic pass and exchanged with zero in the LAST.  BATCH groups a time, their
+// rows kFoldRowsAtOnce a time: all those loads or exchanges are in flight before the first instruction that depends on one.  Two
+// pairs in either tier: with more, the folders and not the workers set the register count of the nFactors 8 / 16 kernels (64 -> 72
+// VGPRs at 4 pairs of the accumulated tier), which is the workers' occupancy on every handle.
+constexpr int kFoldRowsAtOnce = 2;
+template <bool LAST, int ROWS, int BATCH>
+__device__ __forceinline__ void fold_sole_pass(const HotRows &hot, float *Q, const FoldShare &sh) {
+    constexpr int RC = ROWS < kFoldRowsAtOnce ? ROWS : kFoldRowsAtOnce;
+    const int d = hot.d, groups = fold_groups(sh, d);
+    for (int gb = sh.tid; gb < groups; gb += BATCH * sh.nthreads) {
+        float2 sum[BATCH];
+        int at[BATCH];  // slot * d + element of the group, < 0 = none
+#pragma unroll
+        for (int b = 0; b < BATCH; b++) {
+            const int g = gb + b * sh.nthreads;
+            at[b] = g < groups ? fold_group_slot(sh, g, d) * d + fold_group_elem(g, d) : -1;
+            sum[b] = make_float2(0.0f, 0.0f);
+        }
+#pragma unroll
+        for (int rc = 0; rc < ROWS; rc += RC) {
+            float2 v[BATCH][RC];
+#pragma unroll
+            for (int b = 0; b < BATCH; b++) {
+#pragma unroll
+                for (int r = 0; r < RC; r++) v[b][r] = make_float2(0.0f, 0.0f);
+                if (at[b] >= 0) {
+                    const int32_t code = hot.meta[at[b] / d];
+                    const int nr = 1 << hot_lg(code);
+                    float *r0 = hot.rep + hot_base(code) * d + at[b] % d;
+#pragma unroll
+                    for (int r = 0; r < RC; r++)
+                        if (rc + r < nr) v[b][r] = LAST ? drain_pair(r0 + (int64_t)(rc + r) * d) : load_pair(r0 + (int64_t)(rc + r) * d);
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < BATCH; b++)
+#pragma unroll
+                for (int r = 0; r < RC; r++) sum[b].x += v[b][r].x, sum[b].y += v[b][r].y;  // (row after row, as the atomic fold sums)
+        }
+#pragma unroll
+        for (int b = 0; b < BATCH; b++)
+            if (at[b] >= 0) {
+                const float2 base = *(const float2 *)(hot.base + at[b]);
+                // (a select, not a skipped store: an element nothing was added to keeps its bits, a -0.0 included)
+                store_pair(Q + (int64_t)hot.items[at[b] / d] * d + at[b] % d,
+                           make_float2(sum[b].x != 0.0f ? base.x + sum[b].x : base.x, sum[b].y != 0.0f ? base.y + sum[b].y : base.y));
+            }
+    }
+}
+
 // The folder workgroups (blockIdx.x < folders) of an update launch: the hot tier's kFolderBlocks first, then -- on a handle with the
 // accumulated tier -- the tier's own.  Wave 0 polls the workers' arrival count at the grain of one load round trip and decides for the
 // workgroup: a pass over its tier when its period has run out (the hot tier's: the fold period; the accumulated tier's: acc_every of
 // them), and once every worker has finished, with LAST, the last pass (an agent-scope acquire behind the count the workers released
 // into), in which all folder workgroups share the rows of both tiers.  So the end of the launch never waits for a folder's sleep, and
 // with LAST no fold kernel follows the launch.  Both kinds wait in the same loop, under the same bound (kFolderTimeout).
+// A launch in the sole-writer form (hot.sole, above HotRows) waits and decides in the same way and differs in what a pass does: every
+// thread works on its own share of its own tier's slots in every pass, the last included -- each workgroup decides for itself when
+// its last pass begins, so a row shared out differently in that pass could be stored final by one workgroup and stale by another.
 template <bool LAST>
 __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
     __shared__ int go;
@@ -943,6 +1046,14 @@ __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
     const uint64_t period = acc ? (uint64_t)hot.period * (uint64_t)hot.acc_every : hot.period;
     if (blockIdx.x == 0 && threadIdx.x < kDoneStripes)  // the stripes the launch before this one counted in: zero for the next launch
         __hip_atomic_store(done_set(hot, hot.set ^ 1) + threadIdx.x * kDoneStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the sole-writer form: this thread's share of its tier's slots, the same in every pass of the launch; base <- Q first
+    bool sole = false;
+    FoldShare sh{};
+    if constexpr (LAST && GORSE_BPR_FOLD_SOLE_WRITER) {
+        sole = hot.sole != 0;
+        sh = fold_share((int)blockIdx.x, (int)threadIdx.x, hot.n_hot, hot.n_acc, folders, kFolderBlocks);
+        if (sole) fold_sole_begin(hot, Q, sh);
+    }
     const uint64_t t0 = wall_clock64();
     uint64_t next = t0 + period;
     int passes = 0;
@@ -952,7 +1063,7 @@ __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
             if (threadIdx.x == 0) {
                 const uint64_t now = wall_clock64();
                 int g = 0;
-                if (all || now - t0 > kFolderTimeout) {
+                if (all || now - t0 > hot.timeout) {
                     if constexpr (LAST) {
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -972,14 +1083,31 @@ __device__ void run_folders(const HotRows &hot, float *Q, int folders) {
         if (g == 2 && !LAST) break;
         // a periodic pass (g == 1): this workgroup's tier among the workgroups of its kind; the last pass (g == 2): both tiers among all
         const bool last = g == 2;
-        const int first = last || !acc ? 0 : hotf, among = last ? folders : (acc ? folders - hotf : hotf);
-        const int tid = ((int)blockIdx.x - first) * (int)blockDim.x + (int)threadIdx.x, nthreads = among * (int)blockDim.x;
-        if (last || !acc) fold_pass(hot, Q, 0, hot.n_hot, tid, nthreads);
-        if (last || acc) fold_acc_pass(hot, Q, hot.n_hot, n_all, tid, nthreads);
+        if (sole) {  // both passes over this thread's own share: hot tier one group a time, the other tier two
+            if constexpr (LAST && GORSE_BPR_FOLD_SOLE_WRITER) {
+                if (!acc) {
+                    if (last)
+                        fold_sole_pass<true, kHotReplicas, 1>(hot, Q, sh);
+                    else
+                        fold_sole_pass<false, kHotReplicas, 1>(hot, Q, sh);
+                } else {
+                    if (last)
+                        fold_sole_pass<true, 1, 2>(hot, Q, sh);
+                    else
+                        fold_sole_pass<false, 1, 2>(hot, Q, sh);
+                }
+            }
+        } else {
+            const int first = last || !acc ? 0 : hotf, among = last ? folders : (acc ? folders - hotf : hotf);
+            const int tid = ((int)blockIdx.x - first) * (int)blockDim.x + (int)threadIdx.x, nthreads = among * (int)blockDim.x;
+            if (last || !acc) fold_pass(hot, Q, 0, hot.n_hot, tid, nthreads);
+            if (last || acc) fold_acc_pass(hot, Q, hot.n_hot, n_all, tid, nthreads);
+        }
         passes++;
         if (last) break;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) hot.done[kFoldPassesWord] = passes;
+    // the pass counts of the launch (gorse_hip_test_bpr_fold_stats): the hot tier's first workgroup and the accumulated tier's first
+    if (threadIdx.x == 0 && ((int)blockIdx.x == 0 || (int)blockIdx.x == hotf)) hot.done[kFoldPassesWord + (acc ? 1 : 0)] = passes;
 }
 
 template <int NC, int MODE>
@@ -1460,7 +1588,8 @@ int g_store_mode = kDefaultStoreMode;  // 1 = NEG_STORE of bpr_update_user_kerne
 // the replica rows of a slot lie next to each other (r04_a: 4 KB apart or n_hot rows apart makes no difference); n_hot stays 0 (no
 // replicas, no folders) until the launch opens them: open_hot
 HotRows make_hot(const gorse_mf *h) {
-    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_meta.p, h->hot_rep.p, h->hot_done.p, 0, h->d, 0, g_fold_period, 0, g_acc_fold_every};
+    return HotRows{h->hot_slot.p, h->hot_items.p, h->hot_meta.p, h->hot_rep.p, h->hot_done.p, 0, h->d, 0, g_fold_period, 0, g_acc_fold_every,
+                   h->hot_base.p, 0, g_folder_timeout};
 }
 bool has_hot(const gorse_mf *h) { return h->n_hot > 0 || h->n_acc > 0; }  // any row that takes an item's updates for it
 // an update launch with folders: the replicas open, the launch's set of arrival stripes by launch parity (the set of the launch before
@@ -1491,6 +1620,10 @@ int32_t launch_update_users(gorse_mf *h, const int32_t *sorted, const int32_t *b
     dim3 grid((unsigned)blocks), block(kBlock);
     // cold items by store only in GORSE_BPR_HOGWILD_STORES and where the handle has any (n_cold) -- the atomics-only instantiation otherwise
     const bool neg_store = stores && h->n_cold > 0 && g_store_mode == 1;
+    // The sole-writer fold (above HotRows): with the tier neg_rep is 1 and every item's class word is >= 0, so without the store route
+    // no worker instruction of this kernel addresses Q for writing -- the folders are the only writers of the rows they fold
+    hot.sole = GORSE_BPR_FOLD_SOLE_WRITER && hot.n_acc > 0 && !neg_store && h->hot_base.p != nullptr ? 1 : 0;
+    if (folders > 0) h->fold_sole_last = hot.sole;
 #define LAUNCH2(NC, NEG_STORE)                                                                                         \
     hipExtLaunchKernelGGL((bpr_update_user_kernel<(NC == 0 ? 1 : NC), NEG_STORE, NC == 0>), grid, block, 0, st, start, stop, 0,     \
                           h->P.p, h->Q.p, sorted + cap, sorted + 2 * cap, bucket, (int32_t)h->U, d, lr, reg, exp_mode, loss, hot, \
@@ -1530,9 +1663,10 @@ int32_t launch_update_mode(gorse_mf *h, const int32_t *us, const int32_t *is, co
     if (blocks > cap) blocks = cap;
     HotRows hot = make_hot(h);
     const int folders = MODE == MODE_ATOMIC && has_hot(h) ? open_hot(h, hot) : 0;
+    if (folders > 0) h->fold_sole_last = 0;  // (the per-sample kernel's fold is the atomic one, then bpr_fold_kernel)
     blocks += folders;
     dim3 grid((unsigned)blocks), block(kBlock);
-#define LAUNCH(NC, SH)                                                                                               \
+#define LAUNCH(NC, SH)                                                                                              \
     hipExtLaunchKernelGGL((bpr_update_kernel<NC, MODE>), grid, block, SH, st, start, folders > 0 ? nullptr : stop, 0, h->P.p, \
                           h->Q.p, us, is, js, order, begin, end, d, lr, reg, exp_mode, loss, hot, folders)
     if (d == 16)
@@ -1897,6 +2031,18 @@ extern "C" int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3) {
     if (h->hot_done.p)
         GORSE_HIP_CHECK(hipMemcpy(&passes, h->hot_done.p + kFoldPassesWord, sizeof(int32_t), hipMemcpyDeviceToHost));
     out3[0] = passes, out3[1] = h->n_hot, out3[2] = h->hot_rows;
+    return GORSE_OK;
+}
+extern "C" void gorse_hip_test_set_bpr_folder_timeout(int64_t ticks) { g_folder_timeout = ticks > 0 ? (uint64_t)ticks : kFolderTimeout; }
+extern "C" int32_t gorse_hip_test_bpr_fold_tier_stats(gorse_mf *h, int64_t *out6) {
+    if (!h || !out6) return fail(GORSE_ERR_INVALID, "NULL argument");
+    GORSE_TRY(h->use());
+    GORSE_TRY(mf_sync_streams(h));
+    int32_t passes[2] = {0, 0};
+    if (h->hot_done.p)
+        GORSE_HIP_CHECK(hipMemcpy(passes, h->hot_done.p + kFoldPassesWord, sizeof(passes), hipMemcpyDeviceToHost));
+    out6[0] = passes[0], out6[1] = h->n_acc > 0 ? passes[1] : 0, out6[2] = h->n_hot, out6[3] = h->hot_rows, out6[4] = h->n_acc;
+    out6[5] = h->fold_sole_last;
     return GORSE_OK;
 }
 extern "C" int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items, int32_t *replicas, float *rep) {

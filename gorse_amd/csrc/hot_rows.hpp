@@ -1,6 +1,7 @@
 // hot_rows.hpp -- which items of a BPR handle are HOT, and how many replica rows each one gets (csrc/bpr.hip, HotRows), shared by
 // gorse_mf_create and by the CPU test of the rule (host library hook gh_test_bpr_hot_layout, tests/test_bpr_hot_layout_cpu.py).
-// Pure host C++ apart from the three constexpr helpers the kernels decode a slot's word with.  Reference semantics of the rates: a
+// Pure host C++ apart from the constexpr helpers the kernels call too: the three that decode a slot's word, and the owner mapping of the
+// sole-writer fold at the end (host hook gh_test_bpr_fold_owner, tests/test_bpr_fold_owner_cpu.py).  Reference semantics of the rates: a
 // sample draws its user uniformly among the users with feedback, then a positive uniformly from that user's row, then a negative
 // uniformly from the catalogue (model/cf/model.go:452-468).
 #pragma once
@@ -117,5 +118,29 @@ inline int64_t acc_rows_layout(std::vector<int32_t> &slot, int64_t first_row, in
         }
     return (int64_t)items.size();
 }
+
+// ---- the SOLE-WRITER fold: who owns which elements of which slot (csrc/bpr.hip run_folders, fold_sole_pass) ------------------------
+// On a launch whose workers never write Q (every item has a row: the accumulated tier) the folder workgroups are Q's only writers and
+// fold with loads and stores: Q <- base + (the slot's rows).  What replaces the atomics is this invariant: every (slot, element group)
+// has exactly ONE owner thread for the whole launch, the same in the periodic passes and in the last one.  The hot tier's slots
+// [0, n_hot) are shared among the hot tier's workgroups (the first hot_blocks of the `folders`), the accumulated tier's slots
+// [n_hot, n_hot + n_acc) among the workgroups behind them; a group is kFoldGroup consecutive elements of a slot (d is a multiple of
+// it: user_run_width), groups are numbered slot after slot inside a tier and strided over the tier's threads.
+constexpr int kFoldGroup = 2;        // floats a folder thread moves per access: one 8-byte load or store
+constexpr int kFolderThreads = 256;  // threads of a folder workgroup (the update kernels' block)
+struct FoldShare {
+    int s0, s1;         // the tier's slots
+    int tid, nthreads;  // this thread among the tier's: it owns the groups tid, tid + nthreads, ... of [0, (s1 - s0) * d / kFoldGroup)
+};
+// the share of thread `thread` of folder workgroup `block` (a launch with no workgroups behind the hot tier's: one tier of all slots)
+constexpr FoldShare fold_share(int block, int thread, int n_hot, int n_acc, int folders, int hot_blocks) {
+    if (folders <= hot_blocks) return FoldShare{0, n_hot + n_acc, block * kFolderThreads + thread, folders * kFolderThreads};
+    if (block < hot_blocks) return FoldShare{0, n_hot, block * kFolderThreads + thread, hot_blocks * kFolderThreads};
+    return FoldShare{n_hot, n_hot + n_acc, (block - hot_blocks) * kFolderThreads + thread, (folders - hot_blocks) * kFolderThreads};
+}
+constexpr int fold_groups(const FoldShare &sh, int d) { return (sh.s1 - sh.s0) * (d / kFoldGroup); }
+// group g of a share: its slot and its first element
+constexpr int fold_group_slot(const FoldShare &sh, int g, int d) { return sh.s0 + g / (d / kFoldGroup); }
+constexpr int fold_group_elem(int g, int d) { return (g % (d / kFoldGroup)) * kFoldGroup; }
 
 }  // namespace gorse

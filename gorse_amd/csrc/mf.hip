@@ -400,6 +400,7 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
             GORSE_TRY(h->hot_items.alloc(hot.size() + acc_items.size()));
             GORSE_TRY(h->hot_meta.alloc(hot.size() + acc_items.size()));
             GORSE_TRY(h->hot_rep.alloc(rep_rows * (size_t)d));
+            if (!acc_items.empty()) GORSE_TRY(h->hot_base.alloc((hot.size() + acc_items.size()) * (size_t)d));  // (bpr.hip: the sole-writer fold)
             GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_WORDS));  // (bpr.hip worker_done)
             GORSE_HIP_CHECK(hipMemsetAsync(h->hot_done.p, 0, (size_t)GORSE_HOT_DONE_WORDS * sizeof(int32_t), h->stream));
             GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_slot.p, slot.data(), (size_t)I * sizeof(int32_t), hipMemcpyHostToDevice,

@@ -8,7 +8,8 @@
 
 #define GORSE_HOT_DONE_STRIPES 32  // words of the workers' arrival counter (bpr.hip worker_done), GORSE_HOT_DONE_STRIDE words apart
 #define GORSE_HOT_DONE_STRIDE 64
-// hot_done: two sets of arrival stripes (update launches alternate between them) and one line for the folders' pass count
+// hot_done: two sets of arrival stripes (update launches alternate between them) and one line for the folders' pass counts (two words:
+// the hot tier's, the accumulated tier's)
 #define GORSE_HOT_DONE_WORDS (2 * GORSE_HOT_DONE_STRIPES * GORSE_HOT_DONE_STRIDE + GORSE_HOT_DONE_STRIDE)
 #ifndef GORSE_HOT_REPLICAS
 #define GORSE_HOT_REPLICAS 8  // replica rows of the hottest items (the most a slot gets, gorse_mf_create; bpr.hip kHotReplicas)
@@ -75,6 +76,10 @@ struct gorse_mf {
     // the accumulated tier (hot_rows.hpp acc_rows_layout): n_acc warm items with one row each behind the hot_rows replica rows of
     // hot_rep; their slots are entries n_hot .. n_hot + n_acc of hot_items / hot_meta
     int n_acc = 0;
+    // handles with the tier: n_hot + n_acc rows of d floats, the slots' rows of Q as an update launch in the sole-writer form found
+    // them (bpr.hip, above HotRows); written and read by that launch's folders only, its content means nothing between two launches
+    gorse::DevBuf<float> hot_base;
+    int fold_sole_last = 0;     // whether the last update launch with folders took that form (gorse_hip_test_bpr_fold_tier_stats)
     uint64_t hot_launches = 0;  // update launches with folders so far: the parity picks the launch's set of arrival stripes
     int64_t n_cold = 0;  // items of class "cold" in hot_slot (-2): updates by write-through store (bpr.hip)
     int64_t cold_window = 0;               // what n_cold was computed for (gorse_mf_set_bpr_cold_window)

@@ -1146,6 +1146,30 @@ int32_t gh_test_bpr_acc_layout(int64_t U, int64_t I, int32_t d, const int64_t *u
     out3[0] = rows, out3[1] = (int64_t)hot.size(), out3[2] = n_cold;
     return (int32_t)n_acc;
 }
+// The owner mapping of the BPR sole-writer fold (csrc/hot_rows.hpp fold_share: csrc/bpr.hip run_folders takes a thread's share from it
+// once per launch, and the periodic passes and the last pass all walk that share): for `folders` folder workgroups, the first
+// min(folders, hot_blocks) of them the hot tier's, every thread walks the groups of its share as a pass does.  owner[(slot, element)] =
+// block x threads + thread of the element's owner, -1 where nobody owns it; claims[(slot, element)] = how many threads claimed it.
+// Returns the floats of a group (what one access moves), 0 where d is no multiple of it.
+int32_t gh_test_bpr_fold_owner(int32_t n_hot, int32_t n_acc, int32_t d, int32_t folders, int32_t hot_blocks, int32_t *owner, int32_t *claims) {
+    if (d % gorse::kFoldGroup != 0) return 0;
+    const int64_t n = (int64_t)(n_hot + n_acc) * d;
+    std::fill(owner, owner + n, -1);
+    std::fill(claims, claims + n, 0);
+    for (int b = 0; b < folders; b++)
+        for (int t = 0; t < gorse::kFolderThreads; t++) {
+            const gorse::FoldShare sh = gorse::fold_share(b, t, n_hot, n_acc, folders, hot_blocks);
+            const int groups = gorse::fold_groups(sh, d);
+            for (int g = sh.tid; g < groups; g += sh.nthreads) {
+                const int slot = gorse::fold_group_slot(sh, g, d), e = gorse::fold_group_elem(g, d);
+                for (int k = 0; k < gorse::kFoldGroup; k++) {
+                    owner[(int64_t)slot * d + e + k] = b * gorse::kFolderThreads + t;
+                    claims[(int64_t)slot * d + e + k]++;
+                }
+            }
+        }
+    return gorse::kFoldGroup;
+}
 // the ALS row plan's long-row threshold for a side of `side_entries` feedbacks (csrc/als_plan.hpp, the header als_build_plan includes)
 int64_t gh_test_als_long_row(int64_t side_entries, int32_t d) { return gorse::als_long_row_threshold(side_entries, d); }
 // the 64-bit sparse ranking key itself, and the number of results the reference returns (xvec.go:379-446)

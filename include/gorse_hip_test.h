@@ -219,6 +219,19 @@ void gorse_hip_test_set_bpr_acc_rows(int32_t on);
 void gorse_hip_test_set_bpr_acc_fold_every(int32_t periods);
 int32_t gorse_hip_test_bpr_acc_state(gorse_mf *h, int32_t *items /*host*/, float *rows /*host*/);
 int32_t gorse_hip_test_bpr_item_classes(gorse_mf *h, int32_t *slot /*host, items*/, int64_t *out2 /*host*/);
+/* The folds of an update launch (csrc/bpr.hip, above HotRows).  A user-run launch on a handle with the accumulated tier and the store
+ * route closed has no worker that writes Q: its folders fold as Q's sole writers, with loads and stores (Q <- the row as the launch
+ * found it + the slot's rows); every other launch folds with atomics.
+ * fold_tier_stats, after the handle's streams drain: out6 = {folder passes of the hot tier in the last update launch with folders
+ * (its final pass included; the tier's first workgroup's count), the same of the accumulated tier (0 without it), hot items, replica
+ * rows in all, rows of the accumulated tier, 1 where that launch folded as sole writer / 0 with atomics}.  Atomic dwords the folds of
+ * an atomic-form launch issue: hot passes x (out6[3] + out6[2]) x nFactors + tier passes x 2 x out6[4] x nFactors (its last pass
+ * counts in both); of a sole-writer launch: (out6[3] + out6[4]) x nFactors, the exchanges of its last pass.
+ * set_bpr_folder_timeout: wall-clock ticks (100 MHz) after which the folders of the launches that follow stop waiting for the workers
+ * and make their last pass; <= 0 = the library's default (10 s).  At 1 tick they make it at once: what the workers add afterwards
+ * stays in the rows, and the next launch folds it in. */
+int32_t gorse_hip_test_bpr_fold_tier_stats(gorse_mf *h, int64_t *out6 /*host*/);
+void gorse_hip_test_set_bpr_folder_timeout(int64_t ticks);
 /* gorse_mf_recommend (csrc/recommend.hip).  slices > 0 = the threshold kernel cuts the items into this many slices across workgroups
  * (at most 8 and at most one per item; 0 = by the number of query blocks); buffer > 0 = entries of a query's survivor buffer (raised to
  * k + 2 where smaller, the smallest that can hold k + 1 entries and one more: a compaction per survivor; 0 = max(32, 2 (k + 1)));
