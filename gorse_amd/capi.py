@@ -226,6 +226,11 @@ SIGNATURES = {
     "gorse_cand_get_exclusion": (C.c_int32, [_vp, _i64p, _i32p]),
     "gorse_cand_stats": (C.c_int32, [_vp, C.c_int32, _f64p, _f64p]),
     "gorse_fm_rank_cand": (C.c_int32, [_vp, _vp, _i64p, _i32p, _f32p, _i32p, C.c_int32, _i32p, _f32p, _i32p]),
+    "gorse_cand_add_replacement": (C.c_int32, [_vp, _i64p, _i32p, _u8p, _u8p]),
+    "gorse_cand_get_replacement": (C.c_int32, [_vp, _i64p, _i32p, _u8p]),
+    "gorse_cand_replacement_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p, _f64p]),
+    "gorse_fm_rank_cand_decayed": (C.c_int32, [_vp, _vp, _i64p, _i32p, _f32p, _i32p, C.c_int32, _i32p, C.c_double, C.c_double, _f32p, _f64p,
+                                               _i32p]),
 }
 
 
@@ -666,8 +671,31 @@ class FM:
                                        _p(cancel, _i32p) if cancel is not None else None, _p(sc, _f32p), _p(od, _i32p)))
         return sc, od
 
+    def rank_cand_decayed(self, chain, user_indptr, user_indices, user_values, batch_size, positive_decay, read_decay, user_lead=None,
+                          cancel=None, scores=True, final=True, order=True):
+        """rank_cand followed by the replacement decay and the sort of the decayed scores on the device
+        (gorse_fm_rank_cand_decayed): (the ranker's float32 scores, the decayed float64 scores, the order), flat in the layout of
+        chain.get()'s row pointer.  scores / final / order: True or False."""
+        uptr = _arr(user_indptr, np.int64).reshape(-1)
+        uidx, uval = _arr(user_indices, np.int32).reshape(-1), _arr(user_values, np.float32).reshape(-1)
+        n, _, total, _ = chain.info()
+        if uptr.size != n + 1 or uidx.size != uval.size:
+            raise GorseHipError(ERR_INVALID, "user_indptr holds one entry per query of the chain and one more")
+        if n > 0 and np.all(np.diff(uptr) >= 0) and uptr[0] == 0 and uidx.size < uptr[-1]:
+            raise GorseHipError(ERR_INVALID, "fewer entries than the pointer array names")
+        ul = _arr(user_lead, np.int32).reshape(-1) if user_lead is not None else None
+        if ul is not None and ul.size != n:
+            raise GorseHipError(ERR_INVALID, "one lead per user")
+        sc = np.zeros(total, np.float32) if scores else None
+        fn = np.zeros(total, np.float64) if final else None
+        od = np.zeros(total, np.int32) if order else None
+        check(lib().gorse_fm_rank_cand_decayed(self.h, chain.h, _p(uptr, _i64p), _p(uidx, _i32p), _p(uval, _f32p), _p(ul, _i32p),
+                                               int(batch_size), _p(cancel, _i32p) if cancel is not None else None, float(positive_decay),
+                                               float(read_decay), _p(sc, _f32p), _p(fn, _f64p), _p(od, _i32p)))
+        return sc, fn, od
+
     def rank_stats(self):
-        """the last rank_users / rank_cand: rows scored, slices, launch rounds, lists sorted by the host, device milliseconds"""
+        """the last rank_users / rank_cand / rank_cand_decayed: rows scored, slices, launch rounds, lists sorted by the host, device milliseconds"""
         v = [C.c_int64(0) for _ in range(4)]
         ms = C.c_double(0)
         check(lib().gorse_fm_rank_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
@@ -1232,6 +1260,7 @@ class NbrRecommender:
 
 
 CAND_MAX_K, CAND_MAX_STAGES = 256, 255  # GORSE_CAND_MAX_K, GORSE_CAND_MAX_STAGES
+CAND_STAGE_REPLACEMENT, CAND_KIND_POSITIVE, CAND_KIND_READ = 255, 1, 2  # GORSE_CAND_STAGE_REPLACEMENT, GORSE_CAND_KIND_*
 
 
 class CandidateChain:
@@ -1347,6 +1376,34 @@ class CandidateChain:
         a, b = C.c_double(0), C.c_double(0)
         check(lib().gorse_cand_stats(self.h, int(stage), C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def add_replacement(self, hist_indptr, hist_items, hist_kind, keep=None):
+        """the users' historical items back among the finished candidates (gorse_cand_add_replacement): one history row per query as a
+        CSR, a kind per entry (KIND_POSITIVE / KIND_READ); keep = the items that exist and are not hidden"""
+        it, kd = _arr(hist_items, np.int32).reshape(-1), _arr(hist_kind, np.uint8).reshape(-1)
+        if it.size != kd.size:
+            raise GorseHipError(ERR_INVALID, "one kind per history entry")
+        ip = self._csr(hist_indptr, self.info()[0], it)
+        if it.size == 0:
+            it, kd = np.zeros(1, np.int32), np.ones(1, np.uint8)
+        check(lib().gorse_cand_add_replacement(self.h, _p(ip, _i64p), _p(it, _i32p), _p(kd, _u8p), _p(self._keep(keep), _u8p)))
+
+    def replacement(self):
+        """the pass's replacement rows as a CSR with ascending rows: (indptr, items, uint8 kinds)"""
+        nq = self.info()[0]
+        ip = np.zeros(nq + 1, np.int64)
+        check(lib().gorse_cand_get_replacement(self.h, _p(ip, _i64p), None, None))
+        n = int(ip[-1])
+        it, kd = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        check(lib().gorse_cand_get_replacement(self.h, None, _p(it, _i32p), _p(kd, _u8p)))
+        return ip, it[:n], kd[:n]
+
+    def replacement_stats(self):
+        """(entries appended, positive entries and read entries of the replacement rows, device milliseconds)"""
+        v = [C.c_int64(0) for _ in range(3)]
+        ms = C.c_double(0)
+        check(lib().gorse_cand_replacement_stats(self.h, *[C.byref(x) for x in v], C.byref(ms)))
+        return v[0].value, v[1].value, v[2].value, ms.value
 
 
 # gorse_hip_test_sgemm_last_form (include/gorse_hip_test.h, GORSE_TEST_SGEMM_*)

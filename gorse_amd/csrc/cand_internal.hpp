@@ -1,6 +1,6 @@
-// cand_internal.hpp -- the gorse_cand handle (cand.hip); fm_rank.hip reads a finished pass's rows from it.
+// cand_internal.hpp -- the gorse_cand handle (cand.hip, cand_replace.hip); fm_rank.hip reads a finished pass's rows from it.
 #pragma once
-#include "cand_plan.hpp"
+#include "cand_replace_plan.hpp"
 #include "common.hpp"
 
 struct gorse_cand {
@@ -40,8 +40,21 @@ struct gorse_cand {
     gorse::DevBuf<uint8_t> f_stage;
     std::vector<int64_t> f_ptr_h;
     std::vector<double> stage_ms, chain_ms;
+    // the replacement rows of a pass with pass.replaced (cand_replace.hip): a compact CSR, rows ascending, a kind per item
+    gorse::DevBuf<int64_t> r_ptr;
+    gorse::DevBuf<int32_t> r_item;
+    gorse::DevBuf<uint8_t> r_kind;
+    int64_t r_total = 0, r_added = 0, r_positive = 0, r_read = 0;
+    double r_ms = 0.0;
     int32_t use() {
         GORSE_HIP_CHECK(hipSetDevice(device));
         return GORSE_OK;
     }
 };
+
+namespace gorse {
+// cand_replace.hip: every candidate of the chain's finished rows decayed by its kind in its query's replacement row (scores: the
+// ranker's floats, CSR-indexed, on the device) into fin, and every list of up to cap entries sorted into order; enqueued on st
+int32_t cand_decay_sort(const gorse_cand *c, hipStream_t st, const float *scores, double positive_decay, double read_decay, int32_t cap,
+                        double *fin, int32_t *order);
+}  // namespace gorse

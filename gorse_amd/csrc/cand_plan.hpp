@@ -23,6 +23,7 @@ inline std::string fmt(const char *f, long long a = 0, long long b = 0, long lon
 // What a pass has come to: the stage rule bounds a query's candidates by the sum of the stages' k.
 struct Pass {
     bool begun = false, finished = false;
+    bool replaced = false;  // the finished rows hold the replacement stage's entries (cand_replace_plan.hpp)
     int64_t n_queries = 0;
     int32_t capacity = 0, n_stages = 0;
     int64_t sum_k = 0;

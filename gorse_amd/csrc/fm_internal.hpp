@@ -171,6 +171,7 @@ struct gorse_fm {
     gorse::DevBuf<float> r_uval, r_scores;
     gorse::fm::RoundPlan r_plan;            // the call's slices: segment = user, item = candidate
     gorse::DevBuf<int32_t> r_order;
+    gorse::DevBuf<double> r_final;            // gorse_fm_rank_cand_decayed: the decayed scores
     hipEvent_t r_ev[2] = {nullptr, nullptr};  // timing events of gorse_fm_rank_stats, created by the first rank call
     int64_t rk_rows = 0, rk_slices = 0, rk_rounds = 0, rk_host_sorted = 0;
     double rk_ms = 0.0;

@@ -7,6 +7,8 @@
 // score every (user, candidate) row on the device in BatchPredict's order (fm.go:183-206), and sorts every user's list there:
 //   fm_rank_sort_kernel     one workgroup per user list of up to kSortCap entries: a bitonic sort of (key << 32 | position) in
 //                           LDS.  The keys are unique, so the network's instability cannot show.
+// gorse_fm_rank_cand takes the lists from a finished candidate chain on the device; gorse_fm_rank_cand_decayed scores the same way
+// and hands the scores to cand_replace.hip's decay and sort (cand_decay_sort) in place of the sort above.
 #include "cand_internal.hpp"
 #include "fm_internal.hpp"
 #include "fm_rank_order.hpp"
@@ -242,28 +244,96 @@ extern "C" int32_t gorse_fm_rank_users(gorse_fm *h, int64_t n_users, const int64
                       scores_out, order_out);
 }
 
-extern "C" int32_t gorse_fm_rank_cand(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr, const int32_t *user_indices,
-                                      const float *user_values, const int32_t *user_lead, int32_t batch_size,
-                                      const volatile int32_t *cancel, float *scores_out, int32_t *order_out) {
+// what gorse_fm_rank_cand and gorse_fm_rank_cand_decayed ask of their handles and users before anything runs
+static int32_t check_rank_cand(const gorse_fm *h, const gorse_cand *c, const char *who, const int64_t *user_indptr, const int32_t *user_indices,
+                               const float *user_values, const int32_t *user_lead, int32_t batch_size) {
     if (!h || !c) return fail(GORSE_ERR_INVALID, "handle is NULL");
     if (!h->cat) return fail(GORSE_ERR_INVALID, "no item catalogue (gorse_fm_set_items)");
     if (batch_size <= 0) return fail(GORSE_ERR_INVALID, "batch_size must be positive");
-    if (!c->pass.begun || !c->pass.finished) return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain has no finished pass (gorse_cand_finish)");
-    if (c->device != h->device) return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain is on device %d, the ranker on device %d", c->device, h->device);
+    if (!c->pass.begun || !c->pass.finished) return fail(GORSE_ERR_INVALID, "%s: the chain has no finished pass (gorse_cand_finish)", who);
+    if (c->device != h->device) return fail(GORSE_ERR_INVALID, "%s: the chain is on device %d, the ranker on device %d", who, c->device, h->device);
     if (c->n_items != h->cat->n_items)
-        return fail(GORSE_ERR_INVALID, "gorse_fm_rank_cand: the chain has %lld items, the catalogue %lld", (long long)c->n_items,
+        return fail(GORSE_ERR_INVALID, "%s: the chain has %lld items, the catalogue %lld", who, (long long)c->n_items,
                     (long long)h->cat->n_items);
+    if (c->pass.n_queries == 0) return GORSE_OK;
+    GORSE_TRY(fm::check_side(h, c->pass.n_queries, user_indptr, user_indices, user_values, user_lead, "users"));
+    if (c->f_ptr_h.back() > INT32_MAX) return fail(GORSE_ERR_INVALID, "more than 2^31 - 1 candidates in one call: split the users");
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_fm_rank_cand(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr, const int32_t *user_indices,
+                                      const float *user_values, const int32_t *user_lead, int32_t batch_size,
+                                      const volatile int32_t *cancel, float *scores_out, int32_t *order_out) {
+    GORSE_TRY(check_rank_cand(h, c, "gorse_fm_rank_cand", user_indptr, user_indices, user_values, user_lead, batch_size));
     const int64_t n_users = c->pass.n_queries;
     if (n_users == 0) {
         h->rk_rows = h->rk_slices = h->rk_rounds = h->rk_host_sorted = 0;
         h->rk_ms = 0.0;
         return GORSE_OK;
     }
-    GORSE_TRY(fm::check_side(h, n_users, user_indptr, user_indices, user_values, user_lead, "users"));
-    if (c->f_ptr_h.back() > INT32_MAX) return fail(GORSE_ERR_INVALID, "more than 2^31 - 1 candidates in one call: split the users");
     // (the chain's items lie in [0, n_items): every stage's input was held against it)
     return rank_lists(h, n_users, user_indptr, user_indices, user_values, user_lead, c->f_ptr_h.data(), nullptr, c->f_item.p, batch_size, cancel,
                       scores_out, order_out);
+}
+
+// gorse_fm_rank_cand's scores, then the replacement decay and the sort of the decayed doubles (cand_replace.hip) on the same stream;
+// lists past the device sort's cap by the host with the same order (cand_replace_plan.hpp)
+extern "C" int32_t gorse_fm_rank_cand_decayed(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr, const int32_t *user_indices,
+                                              const float *user_values, const int32_t *user_lead, int32_t batch_size,
+                                              const volatile int32_t *cancel, double positive_decay, double read_decay, float *scores_out,
+                                              double *final_out, int32_t *order_out) {
+    const char *who = "gorse_fm_rank_cand_decayed";
+    GORSE_TRY(check_rank_cand(h, c, who, user_indptr, user_indices, user_values, user_lead, batch_size));
+    std::string msg;
+    const int32_t rc = cand::validate_decays(positive_decay, read_decay, &msg);
+    if (rc != GORSE_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    const int64_t n_users = c->pass.n_queries;
+    if (n_users == 0) {
+        h->rk_rows = h->rk_slices = h->rk_rounds = h->rk_host_sorted = 0;
+        h->rk_ms = 0.0;
+        return GORSE_OK;
+    }
+    const int64_t *cptr = c->f_ptr_h.data();
+    const int64_t total = cptr[n_users];
+    const int32_t cap = fm::g_sort_cap > 0 ? fm::g_sort_cap : fm::kSortCap;
+    int64_t n_long = 0;
+    for (int64_t t = 0; t < n_users; t++) n_long += cptr[t + 1] - cptr[t] > cap;
+    const bool fallback = order_out && n_long > 0;
+    std::vector<float> tmp_scores;
+    float *host_scores = scores_out;
+    if (fallback && !host_scores && total > 0) {
+        tmp_scores.resize((size_t)total);
+        host_scores = tmp_scores.data();
+    }
+    GORSE_TRY(rank_lists(h, n_users, user_indptr, user_indices, user_values, user_lead, cptr, nullptr, c->f_item.p, batch_size, cancel,
+                         host_scores, nullptr));
+    if (total == 0) return GORSE_OK;
+    GORSE_TRY(h->r_final.ensure((size_t)total));
+    GORSE_TRY(h->r_order.ensure((size_t)total));
+    GORSE_HIP_CHECK(hipEventRecord(h->r_ev[0], h->s));
+    GORSE_TRY(cand_decay_sort(c, h->s, h->r_scores.p, positive_decay, read_decay, cap, h->r_final.p, h->r_order.p));
+    GORSE_HIP_CHECK(hipEventRecord(h->r_ev[1], h->s));
+    GORSE_HIP_CHECK(hipStreamSynchronize(h->s));
+    float ms = 0.0f;
+    GORSE_HIP_CHECK(hipEventElapsedTime(&ms, h->r_ev[0], h->r_ev[1]));
+    h->rk_ms += ms;
+    std::vector<double> tmp_final;
+    double *host_final = final_out;
+    if (fallback && !host_final) {
+        tmp_final.resize((size_t)total);
+        host_final = tmp_final.data();
+    }
+    if (host_final) GORSE_HIP_CHECK(hipMemcpy(host_final, h->r_final.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    if (order_out) {
+        GORSE_HIP_CHECK(hipMemcpy(order_out, h->r_order.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (fallback)
+            for (int64_t t = 0; t < n_users; t++) {
+                const int64_t c0 = cptr[t], n = cptr[t + 1] - c0;
+                if (n > cap) cand::decayed_positions(host_scores + c0, host_final + c0, n, order_out + c0);
+            }
+        h->rk_host_sorted = n_long;
+    }
+    return GORSE_OK;
 }
 
 extern "C" int32_t gorse_fm_rank_stats(gorse_fm *h, int64_t *rows, int64_t *slices, int64_t *rounds, int64_t *host_sorted,

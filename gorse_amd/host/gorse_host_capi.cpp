@@ -1000,6 +1000,69 @@ int32_t gh_logics_seq_run(void *h, int32_t bulk, int64_t n_users, const char *us
         stage_scores(res);
     });
 }
+// logics::AddReplacementCandidates / ApplyReplacementDecay / RecommendWithReplacement for one user.  Ids travel '\n'-joined, the
+// scores and the feedback kinds (1 positive, 2 read) as arrays in id order.
+//   gh_logics_replacement_add     stages three lists: the grown candidates, positiveExisting and negativeItems (scores 0)
+//   gh_logics_replacement_decay   stages the decayed, re-sorted results
+//   gh_logics_replacement_run     the whole body; scorer(item id) = the ranker's float32 score of that candidate
+namespace {
+std::vector<logics::Score> scored_ids(const char *ids, const double *scores, int64_t n) {
+    std::vector<logics::Score> out;
+    for (const std::string &id : split_lines(ids)) {
+        logics::Score sc;
+        sc.Id = id;
+        if ((int64_t)out.size() < n && scores) sc.Value = scores[out.size()];
+        out.push_back(std::move(sc));
+    }
+    return out;
+}
+std::vector<logics::ReplacementFeedback> feedback_of(const char *items, const uint8_t *kinds, int64_t n) {
+    std::vector<logics::ReplacementFeedback> out;
+    for (const std::string &id : split_lines(items)) {
+        if ((int64_t)out.size() >= n) throw std::invalid_argument("fewer kinds than feedback items");
+        out.push_back({id, (int)kinds[out.size()]});
+    }
+    return out;
+}
+std::set<std::string> id_set(const char *ids) {
+    const auto v = split_lines(ids);
+    return std::set<std::string>(v.begin(), v.end());
+}
+std::vector<logics::Score> as_scores(const std::set<std::string> &ids) {
+    std::vector<logics::Score> out;
+    for (const std::string &id : ids) {
+        logics::Score sc;
+        sc.Id = id;
+        out.push_back(std::move(sc));
+    }
+    return out;
+}
+}  // namespace
+int32_t gh_logics_replacement_add(const char *cand_ids, const double *cand_scores, int64_t n_cand, const char *fb_items, const uint8_t *fb_kinds,
+                                  int64_t n_fb, const char *existing) {
+    return guard([&] {
+        const auto r = logics::AddReplacementCandidates(scored_ids(cand_ids, cand_scores, n_cand), feedback_of(fb_items, fb_kinds, n_fb), id_set(existing));
+        stage_scores({r.Candidates, as_scores(r.Positive), as_scores(r.Negative)});
+    });
+}
+int32_t gh_logics_replacement_decay(const char *ids, const double *scores, int64_t n, const char *positive, const char *negative,
+                                    double positive_decay, double read_decay) {
+    return guard([&] {
+        stage_scores({logics::ApplyReplacementDecay(scored_ids(ids, scores, n), id_set(positive), id_set(negative), positive_decay, read_decay)});
+    });
+}
+int32_t gh_logics_replacement_run(const char *cand_ids, const double *cand_scores, int64_t n_cand, const char *fb_items, const uint8_t *fb_kinds,
+                                  int64_t n_fb, const char *existing, float (*scorer)(const char *), double positive_decay, double read_decay) {
+    return guard([&] {
+        auto ranker = [&](const std::vector<logics::Score> &c) {
+            std::vector<float> out;
+            for (const logics::Score &sc : c) out.push_back(scorer(sc.Id.c_str()));
+            return out;
+        };
+        stage_scores({logics::RecommendWithReplacement(scored_ids(cand_ids, cand_scores, n_cand), feedback_of(fb_items, fb_kinds, n_fb),
+                                                       id_set(existing), ranker, positive_decay, read_decay)});
+    });
+}
 // HipDatabase::SetNbrTableFromIndex: slot `which` of the gorse_nbr handle `nbr` from the collection's resident index; the row
 // numbering (ids in row order) is staged like a query's results
 int32_t gh_vdb_set_nbr_table_from_index(void *h, const char *collection, void *nbr, int32_t which, const char *type, const char *categories,

@@ -33,6 +33,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1332,6 +1333,89 @@ inline std::vector<std::vector<Score>> RecommendSequentialBulk(vectors::HipDatab
             out[t].push_back(std::move(sc));
         }
     return out;
+}
+
+// ---- replacement (worker/pipeline.go:573-643): the user's historical items back among the candidates, their ranked scores decayed --
+// Per user, on string ids and sets as the reference has them; the bulk route is gorse_cand_add_replacement /
+// gorse_fm_rank_cand_decayed.  Matching a feedback against the positive and read type expressions is the caller's: Kind says what
+// matched (1 positive, 2 read, anything else neither).
+struct ReplacementFeedback {
+    std::string ItemId;
+    int Kind = 0;
+};
+struct ReplacementCandidates {
+    std::vector<Score> Candidates;
+    std::set<std::string> Positive, Negative;  // positiveExisting, negativeItems
+};
+
+// addReplacementCandidates: `existing` = the ids ItemCache.GetSlice returns an item for (it exists and is not hidden).  The reference
+// appends in mapset.ToSlice() order, which nothing pins; here in ascending id order.
+inline ReplacementCandidates AddReplacementCandidates(std::vector<Score> candidates, const std::vector<ReplacementFeedback> &feedbacks,
+                                                      const std::set<std::string> &existing) {
+    std::set<std::string> positiveItems, distinctItems, candidateSet;
+    for (const Score &c : candidates) candidateSet.insert(c.Id);
+    for (const ReplacementFeedback &f : feedbacks) {
+        if (f.Kind == GORSE_CAND_KIND_POSITIVE) {
+            positiveItems.insert(f.ItemId);
+            distinctItems.insert(f.ItemId);
+        } else if (f.Kind == GORSE_CAND_KIND_READ) {
+            distinctItems.insert(f.ItemId);
+        }
+    }
+    ReplacementCandidates r;
+    for (const std::string &id : distinctItems) {
+        if (!existing.count(id)) continue;
+        if (candidateSet.insert(id).second) {
+            Score sc;  // cache.Score{Id, Categories, Timestamp}: the score is 0
+            sc.Id = id;
+            candidates.push_back(std::move(sc));
+        }
+        (positiveItems.count(id) ? r.Positive : r.Negative).insert(id);
+    }
+    r.Candidates = std::move(candidates);
+    return r;
+}
+
+// applyReplacementDecay on results in the ranker's order.  sort.Slice is unstable; here equal scores (and NaNs, last) keep the
+// ranker's order, which is the order gorse_fm_rank_cand_decayed gives.
+inline std::vector<Score> ApplyReplacementDecay(std::vector<Score> results, const std::set<std::string> &positiveItems,
+                                                const std::set<std::string> &negativeItems, double positiveDecay, double readDecay) {
+    bool changed = false;
+    for (Score &sc : results) {
+        if (positiveItems.count(sc.Id)) {
+            sc.Value *= positiveDecay;
+            changed = true;
+        } else if (negativeItems.count(sc.Id)) {
+            sc.Value *= readDecay;
+            changed = true;
+        }
+    }
+    if (changed)
+        std::stable_sort(results.begin(), results.end(), [](const Score &a, const Score &b) {
+            if (a.Value != a.Value) return false;
+            if (b.Value != b.Value) return true;
+            return a.Value > b.Value;
+        });
+    return results;
+}
+
+// The body of Pipeline.Recommend between "candidates found" and "results cached" (pipeline.go:245-286) for one user: replacement
+// candidates, the ranker (one float32 score per candidate, in the candidates' order), cache.SortDocuments as gorse_fm_rank_users
+// states it (descending, equal scores by position, NaN last), the decay.
+inline std::vector<Score> RecommendWithReplacement(std::vector<Score> candidates, const std::vector<ReplacementFeedback> &feedbacks,
+                                                   const std::set<std::string> &existing,
+                                                   const std::function<std::vector<float>(const std::vector<Score> &)> &ranker,
+                                                   double positiveDecay, double readDecay) {
+    ReplacementCandidates r = AddReplacementCandidates(std::move(candidates), feedbacks, existing);
+    const std::vector<float> scores = ranker(r.Candidates);
+    if (scores.size() != r.Candidates.size()) throw std::invalid_argument("the ranker returns one score per candidate");
+    for (size_t i = 0; i < scores.size(); i++) r.Candidates[i].Value = (double)scores[i];
+    std::stable_sort(r.Candidates.begin(), r.Candidates.end(), [](const Score &a, const Score &b) {
+        if (a.Value != a.Value) return false;
+        if (b.Value != b.Value) return true;
+        return a.Value > b.Value;
+    });
+    return ApplyReplacementDecay(std::move(r.Candidates), r.Positive, r.Negative, positiveDecay, readDecay);
 }
 
 // MatrixFactorizationUsers (logics/cf.go:122-179): user id -> embedding, and its blob: WriteGob(int64 count), then per

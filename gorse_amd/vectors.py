@@ -531,6 +531,55 @@ def RecommendSequentialBulk(client, user_ids, positives, excludes, stages):
     return _recommend_sequential(client, 1, user_ids, positives, excludes, stages)
 
 
+def _replacement_args(candidates, feedbacks):
+    sc = np.ascontiguousarray([s.Score for s in candidates] or [0.0], np.float64)
+    kd = np.ascontiguousarray([k for _, k in feedbacks] or [0], np.uint8)
+    return ("\n".join(s.Id for s in candidates).encode(), sc.ctypes.data_as(C.POINTER(C.c_double)), len(candidates),
+            "\n".join(i for i, _ in feedbacks).encode(), kd.ctypes.data_as(C.POINTER(C.c_uint8)), len(feedbacks)), (sc, kd)
+
+
+def _split_scores(n):
+    H = _logics_host()
+    flat = _scores()
+    cuts = [int(H.gh_vdb_result_split(t)) for t in range(n + 1)]
+    return [flat[cuts[t]:cuts[t + 1]] for t in range(n)]
+
+
+def AddReplacementCandidates(candidates, feedbacks, existing):
+    """addReplacementCandidates (worker/pipeline.go:573-615) for one user: candidates = [Score], feedbacks = [(item id, kind)] with
+    kind 1 = matches a positive type, 2 = matches a read type, existing = the ids that exist and are not hidden.  Returns (the grown
+    candidates, positiveExisting, negativeItems); the appended items come in ascending id order with score 0."""
+    H = _logics_host()
+    H.gh_logics_replacement_add.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), C.c_int64, C.c_char_p]
+    args, _alive = _replacement_args(candidates, feedbacks)
+    _ck(H.gh_logics_replacement_add(*args, "\n".join(existing).encode()))
+    grown, positive, negative = _split_scores(3)
+    return grown, {s.Id for s in positive}, {s.Id for s in negative}
+
+
+def ApplyReplacementDecay(results, positive, negative, positive_decay, read_decay):
+    """applyReplacementDecay (worker/pipeline.go:617-643) on results in the ranker's order: equal decayed scores keep that order"""
+    H = _logics_host()
+    H.gh_logics_replacement_decay.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
+    sc = np.ascontiguousarray([s.Score for s in results] or [0.0], np.float64)
+    _ck(H.gh_logics_replacement_decay("\n".join(s.Id for s in results).encode(), sc.ctypes.data_as(C.POINTER(C.c_double)), len(results),
+                                      "\n".join(sorted(positive)).encode(), "\n".join(sorted(negative)).encode(), positive_decay, read_decay))
+    return _split_scores(1)[0]
+
+
+def RecommendWithReplacement(candidates, feedbacks, existing, scorer, positive_decay, read_decay):
+    """replacement candidates, the ranker (scorer(item id) -> its float32 score), the ranker's order and the decay for one user:
+    the per-user yardstick of CandidateChain.add_replacement + FM.rank_cand_decayed"""
+    H = _logics_host()
+    cb_t = C.CFUNCTYPE(C.c_float, C.c_char_p)
+    H.gh_logics_replacement_run.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), C.c_int64, C.c_char_p,
+                                            cb_t, C.c_double, C.c_double]
+    args, _alive = _replacement_args(candidates, feedbacks)
+    cb = cb_t(lambda item: float(scorer(item.decode())))
+    _ck(H.gh_logics_replacement_run(*args, "\n".join(existing).encode(), cb, positive_decay, read_decay))
+    return _split_scores(1)[0]
+
+
 def SetNbrTableFromIndex(client, collection, kind, nbr, which, categories, n):
     """One slot of a capi.NbrRecommender filled on the device from the collection's resident index (HipDatabase::SetNbrTableFromIndex):
     row r = the QueryItemToItem / QueryUserToUser list of the collection's row r, n entries at most, under the hidden / categories

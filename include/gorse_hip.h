@@ -774,6 +774,47 @@ int32_t gorse_fm_rank_cand(gorse_fm *h, gorse_cand *c, const int64_t *user_indpt
                            const volatile int32_t *cancel /*host or NULL*/, float *scores_out /*host or NULL*/,
                            int32_t *order_out /*host or NULL*/);
 
+/* ---- replacement: the user's historical items back among the candidates, their ranked scores decayed ------------------------
+ * worker/pipeline.go:573-643, for recommend.replacement.enable_replacement.  Per feedback of query t the caller gives the item and
+ * its kind: GORSE_CAND_KIND_POSITIVE when the feedback type matches a positive type, GORSE_CAND_KIND_READ when it does not but
+ * matches a read type (matching the type expressions is string work and stays with the caller; other feedback is left out).
+ * gorse_cand_add_replacement needs a finished pass and runs once per pass.  A history row may be unsorted, repeat an item and hold
+ * an item with both kinds.  On the device row t becomes its distinct items, ascending, one kind each (positive wins), without the
+ * items of keep[item] == 0 (ItemCache.GetSlice, pipeline.go:661-686: the item exists and is not hidden; NULL keeps all): the pass's
+ * REPLACEMENT ROW of query t, resident until the next begin, and what gorse_cand_get_replacement returns.  Its items that are not
+ * among t's finished candidates are appended behind them, ascending (the reference appends in Go map order, which nothing pins),
+ * with score bits +0.0 and stage GORSE_CAND_STAGE_REPLACEMENT.  The grown rows ARE the finished pass from then on: gorse_cand_get,
+ * gorse_cand_info and gorse_fm_rank_cand read them.  The exclusion rows are not touched.  One row pointer (8 bytes per query) comes
+ * back.  gorse_cand_replacement_stats: entries appended, positive and read entries of the replacement rows, device milliseconds
+ * (zeros on a pass without the stage, where gorse_cand_get_replacement returns empty rows).
+ * Everything is validated before anything is launched or replaced, and an error (GORSE_ERR_NOMEM included) leaves the finished
+ * pass exactly as it was.  GORSE_ERR_INVALID: no finished pass, a second call in one pass, a malformed pointer, a kind other than
+ * 1 or 2.  GORSE_ERR_RANGE: an item outside [0, n_items).
+ *
+ * gorse_fm_rank_cand_decayed scores exactly as gorse_fm_rank_cand (the same bits in scores_out), then decays and sorts on the
+ * device (applyReplacementDecay, pipeline.go:617-643): a candidate whose item is in its query's replacement row -- appended or
+ * found by a recommender on its own -- gets final = (double)score * positive_decay or * read_decay by its kind (one IEEE double
+ * multiply), every other one final = (double)score.  order_out[f_ptr[t] + r] = the position in t's list of its r-th entry under:
+ * descending final; equal doubles (-0 == +0) in gorse_fm_rank_cand's order; NaN last, in gorse_fm_rank_cand's order -- one of the
+ * outcomes the reference's unstable sort.Slice admits, chosen once.  On a pass without a replacement stage order_out is
+ * gorse_fm_rank_cand's and final_out the widened float.  A decay that is not > 0 (config.go:403-404, validate:"gt=0"):
+ * GORSE_ERR_INVALID; every other error as gorse_fm_rank_cand.  gorse_fm_rank_stats covers the call, the decay and the sort. */
+#define GORSE_CAND_STAGE_REPLACEMENT 255 /* stage numbers of real stages are 0 .. 254 */
+#define GORSE_CAND_KIND_POSITIVE 1
+#define GORSE_CAND_KIND_READ 2
+int32_t gorse_cand_add_replacement(gorse_cand *c, const int64_t *hist_indptr /*host, n_queries+1, from 0*/,
+                                   const int32_t *hist_items /*host*/, const uint8_t *hist_kind /*host, 1 or 2 per entry*/,
+                                   const uint8_t *keep /*host, n_items, or NULL*/);
+int32_t gorse_cand_get_replacement(gorse_cand *c, int64_t *indptr_out /*host, n_queries+1*/, int32_t *items_out,
+                                   uint8_t *kind_out); /* any may be NULL */
+int32_t gorse_cand_replacement_stats(gorse_cand *c, int64_t *n_added, int64_t *n_positive, int64_t *n_read, double *device_ms);
+int32_t gorse_fm_rank_cand_decayed(gorse_fm *h, gorse_cand *c, const int64_t *user_indptr /*host, n_queries+1*/,
+                                   const int32_t *user_indices /*host*/, const float *user_values /*host*/,
+                                   const int32_t *user_lead /*host, n_queries, or NULL*/, int32_t batch_size,
+                                   const volatile int32_t *cancel /*host or NULL*/, double positive_decay, double read_decay,
+                                   float *scores_out /*host or NULL: the ranker's bits*/,
+                                   double *final_out /*host or NULL: decayed*/, int32_t *order_out /*host or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -400,3 +400,75 @@ func (c *CandidateChain) RankBy(fm unsafe.Pointer, users UserRows, batchSize int
 	}
 	return scores[:nc], order[:nc], nil
 }
+
+// Feedback kinds of AddReplacement: what the caller's match against the positive and the read feedback type expressions gave
+// (worker/pipeline.go:584-589); feedback that matches neither is left out.
+const (
+	HistoryPositive uint8 = C.GORSE_CAND_KIND_POSITIVE
+	HistoryRead     uint8 = C.GORSE_CAND_KIND_READ
+	// StageReplacement is the Stage of a candidate that AddReplacement appended.
+	StageReplacement uint8 = C.GORSE_CAND_STAGE_REPLACEMENT
+)
+
+// HistoryItem is one feedback of a user's history: the item and what its type matched.
+type HistoryItem struct {
+	Item int32
+	Kind uint8
+}
+
+// AddReplacement is addReplacementCandidates (worker/pipeline.go:573-615) for every user of a finished pass: history[t] is user t's
+// feedback (any order, repeats allowed, an item with both kinds is positive), exists[i] == 0 says item i is gone or hidden
+// (ItemCache.GetSlice; nil: all exist).  The distinct existing items that are no candidates yet are appended, ascending, with score 0
+// and StageReplacement; Candidates and RankBy read the grown lists.  Once per pass; the exclude sets are not touched.
+func (c *CandidateChain) AddReplacement(history [][]HistoryItem, exists []uint8) error {
+	if len(history) != c.queries {
+		return errors.Errorf("AddReplacement: %d histories for %d queries", len(history), c.queries)
+	}
+	indptr := make([]int64, len(history)+1)
+	items := make([]int32, 0, 1)
+	kinds := make([]uint8, 0, 1)
+	for t, h := range history {
+		for _, f := range h {
+			items = append(items, f.Item)
+			kinds = append(kinds, f.Kind)
+		}
+		indptr[t+1] = int64(len(items))
+	}
+	if len(items) == 0 {
+		items, kinds = append(items, 0), append(kinds, HistoryPositive)
+	}
+	rc := C.gorse_cand_add_replacement(c.h, (*C.int64_t)(unsafe.Pointer(&indptr[0])), (*C.int32_t)(unsafe.Pointer(&items[0])),
+		(*C.uint8_t)(unsafe.Pointer(&kinds[0])), keepPtr(exists))
+	if rc != C.GORSE_OK {
+		return nbrError("gorse_cand_add_replacement", rc)
+	}
+	return nil
+}
+
+// RankByDecayed is RankBy followed by applyReplacementDecay (worker/pipeline.go:617-643) on the device
+// (gorse_fm_rank_cand_decayed): final[p + r] is candidate r's score, multiplied by positiveDecay or readDecay where its item is in
+// the user's history (appended or found by a recommender on its own), and order[p + r] the position of the r-th entry under
+// descending final, ties and NaNs in RankBy's order -- one of the orders the reference's sort.Slice can produce.
+func (c *CandidateChain) RankByDecayed(fm unsafe.Pointer, users UserRows, batchSize int, positiveDecay, readDecay float64) ([]float64, []int32, error) {
+	var nc C.int64_t
+	if rc := C.gorse_cand_info(c.h, nil, nil, &nc, nil); rc != C.GORSE_OK {
+		return nil, nil, nbrError("gorse_cand_info", rc)
+	}
+	final := make([]float64, int(nc)+1)
+	order := make([]int32, int(nc)+1)
+	indices, values := users.Indices, users.Values
+	if len(indices) == 0 {
+		indices, values = []int32{0}, []float32{0}
+	}
+	var lead *C.int32_t
+	if users.Lead != nil {
+		lead = (*C.int32_t)(unsafe.Pointer(&users.Lead[0]))
+	}
+	rc := C.gorse_fm_rank_cand_decayed((*C.gorse_fm)(fm), c.h, (*C.int64_t)(unsafe.Pointer(&users.Indptr[0])),
+		(*C.int32_t)(unsafe.Pointer(&indices[0])), (*C.float)(unsafe.Pointer(&values[0])), lead, C.int32_t(batchSize), nil,
+		C.double(positiveDecay), C.double(readDecay), nil, (*C.double)(unsafe.Pointer(&final[0])), (*C.int32_t)(unsafe.Pointer(&order[0])))
+	if rc != C.GORSE_OK {
+		return nil, nil, nbrError("gorse_fm_rank_cand_decayed", rc)
+	}
+	return final[:nc], order[:nc], nil
+}

@@ -160,8 +160,10 @@ func (p *Pipeline) encodeRankCatalogue(ranker ctrRanker, items []data.Item) (*ra
 // rankByClickThroughRateBulk is rankByClickTroughRate (worker/pipeline.go:451-499) for a block of users: one call scores and
 // ranks all their candidates against the resident catalogue.  ok = false sends the caller to the per-user path for the whole
 // block: no resident model (the predictor is not a ctrRanker, or Fit did not run in this process), a candidate that is not in
-// the catalogue (the item cache moved on: encode it again), or an error from the library.  Replacement candidates and the
-// decay of read items stay in Go around this call, exactly as around the per-user one.
+// the catalogue (the item cache moved on: encode it again), or an error from the library.  Around THIS call replacement
+// candidates and the decay of read items stay in Go, exactly as around the per-user one; a pass that keeps its candidates on the
+// device has them there too: logics.CandidateChain.AddReplacement before the ranking and RankByDecayed in place of RankBy
+// (gorse_cand_add_replacement, gorse_fm_rank_cand_decayed).
 // Ties: the library orders equal scores by candidate position and puts NaN scores last; cache.SortDocuments is
 // sort.Slice(score >), which is not stable, so this is one of the orders it can produce.
 func (p *Pipeline) rankByClickThroughRateBulk(ctx context.Context, predictor ctr.FactorizationMachines, catalogue *rankCatalogue,
