@@ -1,4 +1,4 @@
-// bpr_bins.hpp -- the geometry of the BPR chunk preparation by user bins (csrc/bpr.hip: bpr_bin_count / _offsets / _scatter / _sort
+// bpr_bins.hpp -- the geometry of the BPR chunk preparation by user bins (csrc/bpr_prepare.hip: bpr_bin_count / _offsets / _scatter / _sort
 // kernels), shared by the launch code and by the CPU cover test (host library hook gh_test_bpr_bins_*, tests/test_launch_geometry_cpu.py).
 // Pure host C++: no device code, no HIP types.  Reference semantics of what is being grouped: model/cf/model.go:449-468 (the samples
 // of an epoch, users drawn uniformly); the order in which a Hogwild epoch applies them is free (common/parallel/parallel.go:44-68).

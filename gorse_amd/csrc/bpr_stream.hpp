@@ -5,7 +5,7 @@
 //   the POSITIVE : Int31n(feedbacks of the user), in stored order    (model.go:459-461)
 //   the NEGATIVE : Int31n(items) until one is not in the user's row  (model.go:462-468)
 // The reference spins on both loops; here each gives up after kMaxDraws draws and the sample is skipped.  Every sampling and
-// preparation kernel of bpr.hip composes the functions below (whole triplet; user first, items later by replay; batched first draws
+// preparation kernel of bpr_prepare.hip composes the functions below (whole triplet; user first, items later by replay; batched first draws
 // with a restart from the start of the stream), and so does the host (host/gorse_cf.hpp takes the generator from here):
 // tests/cpp/bpr_stream_main.cpp composes them the same three ways and requires the same triplets.
 // A pure header for hipcc and for a plain host compiler: nothing of HIP is included.

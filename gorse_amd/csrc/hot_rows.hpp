@@ -1,4 +1,4 @@
-// hot_rows.hpp -- which items of a BPR handle are HOT, and how many replica rows each one gets (csrc/bpr.hip, HotRows), shared by
+// hot_rows.hpp -- which items of a BPR handle are HOT, and how many replica rows each one gets (csrc/bpr_fold.hpp, HotRows), shared by
 // gorse_mf_create and by the CPU test of the rule (host library hook gh_test_bpr_hot_layout, tests/test_bpr_hot_layout_cpu.py).
 // Pure host C++ apart from the constexpr helpers the kernels call too: the three that decode a slot's word, and the owner mapping of the
 // sole-writer fold at the end (host hook gh_test_bpr_fold_owner, tests/test_bpr_fold_owner_cpu.py).  Reference semantics of the rates: a
@@ -88,9 +88,9 @@ inline bool item_is_cold(int64_t cnt, int64_t nnz, int64_t I, int64_t window) {
 // Atomics onto rows that the same launch gathers run slower than atomics onto rows nobody reads, and the penalty belongs to small
 // tables: 24 % at 0.9 MB, 6 % at 7.6 MB, 3 % at 268 MB (profiles/r04_s_probe_atomics3.txt: 318 G dwords/s alone, 241 with agent-scope
 // loads of the same rows, 311 with the loads from another table).  Where the whole of Q fits one XCD's L2 (4 MiB) the warm items'
-// updates therefore go to a row of their own too, which the tier's folders add to Q every few fold periods (csrc/bpr.hip).
+// updates therefore go to a row of their own too, which the tier's folders add to Q every few fold periods (csrc/bpr_fold.hpp).
 constexpr int64_t kAccTableBytes = (int64_t)4 << 20;  // I x nFactors x 4 at most: one XCD's L2, between the probe's 0.9 MB and 7.6 MB
-constexpr int64_t kUserRunUsers = 4096;               // users from which a handle takes the user-run schedule (bpr.hip user_runs_supported)
+constexpr int64_t kUserRunUsers = 4096;               // users from which a handle takes the user-run schedule (bpr_plan.hpp bpr_schedule)
 inline bool user_run_width(int d) { return d == 8 || d == 16 || d == 32 || d == 64 || d == 128; }
 
 // whether a handle gets the tier: the user-run schedule natively, no cold item at create (a cold row's update is a store: the store
@@ -119,7 +119,7 @@ inline int64_t acc_rows_layout(std::vector<int32_t> &slot, int64_t first_row, in
     return (int64_t)items.size();
 }
 
-// ---- the SOLE-WRITER fold: who owns which elements of which slot (csrc/bpr.hip run_folders, fold_sole_pass) ------------------------
+// ---- the SOLE-WRITER fold: who owns which elements of which slot (csrc/bpr_fold.hpp run_folders, fold_sole_pass) ------------------------
 // On a launch whose workers never write Q (every item has a row: the accumulated tier) the folder workgroups are Q's only writers and
 // fold with loads and stores: Q <- base + (the slot's rows).  What replaces the atomics is this invariant: every (slot, element group)
 // has exactly ONE owner thread for the whole launch, the same in the periodic passes and in the last one.  The hot tier's slots

@@ -338,7 +338,7 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
             GORSE_TRY(als_build_plan(h, 1, item_indptr, I, 0, I));
         }
         trace.mark("create: item CSR, ALS plan");
-        {   // hot items: share of the training feedback >= 1/8192 (and >= 64 feedbacks), at most 1024 and a quarter of the items (bpr.hip, HotRows)
+        {   // hot items: share of the training feedback >= 1/8192 (and >= 64 feedbacks), at most 1024 and a quarter of the items (bpr_fold.hpp, HotRows)
             std::vector<int64_t> cnt((size_t)I, 0);
             if (h->nnz < ((int64_t)1 << 26) || I > ((int64_t)1 << 22)) {
                 for (int64_t t = 0; t < h->nnz; t++) cnt[user_indices[t]]++;
@@ -355,7 +355,7 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
             }
             const std::vector<int32_t> hot = hot_items_select(cnt, h->nnz);  // (hot_rows.hpp)
             std::vector<int32_t> slot((size_t)I, -1);
-            // cold items (class -2, bpr.hip kCold): a sample touches item i with probability share(i) as its positive and 1 / I as
+            // cold items (class -2, bpr_update_users.hip kCold): a sample touches item i with probability share(i) as its positive and 1 / I as
             // its negative; where fewer than one touch is expected per `cold window` samples the row's update may be a plain
             // write-through store (the reference's own unlocked write) instead of d atomic dwords -- in GORSE_BPR_HOGWILD_STORES
             // only.  The window is the handle's own (gorse_mf_set_bpr_cold_window re-classifies from the counts kept here).
@@ -400,8 +400,8 @@ extern "C" int32_t gorse_mf_create(gorse_mf **out, int32_t device, int64_t U, in
             GORSE_TRY(h->hot_items.alloc(hot.size() + acc_items.size()));
             GORSE_TRY(h->hot_meta.alloc(hot.size() + acc_items.size()));
             GORSE_TRY(h->hot_rep.alloc(rep_rows * (size_t)d));
-            if (!acc_items.empty()) GORSE_TRY(h->hot_base.alloc((hot.size() + acc_items.size()) * (size_t)d));  // (bpr.hip: the sole-writer fold)
-            GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_WORDS));  // (bpr.hip worker_done)
+            if (!acc_items.empty()) GORSE_TRY(h->hot_base.alloc((hot.size() + acc_items.size()) * (size_t)d));  // (bpr_fold.hpp: the sole-writer fold)
+            GORSE_TRY(h->hot_done.alloc((size_t)GORSE_HOT_DONE_WORDS));  // (bpr_fold.hpp worker_done)
             GORSE_HIP_CHECK(hipMemsetAsync(h->hot_done.p, 0, (size_t)GORSE_HOT_DONE_WORDS * sizeof(int32_t), h->stream));
             GORSE_HIP_CHECK(hipMemcpyAsync(h->hot_slot.p, slot.data(), (size_t)I * sizeof(int32_t), hipMemcpyHostToDevice,
                                            h->stream));

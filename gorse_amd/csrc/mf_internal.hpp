@@ -6,13 +6,13 @@
 
 #include "hot_rows.hpp"
 
-#define GORSE_HOT_DONE_STRIPES 32  // words of the workers' arrival counter (bpr.hip worker_done), GORSE_HOT_DONE_STRIDE words apart
+#define GORSE_HOT_DONE_STRIPES 32  // words of the workers' arrival counter (bpr_fold.hpp worker_done), GORSE_HOT_DONE_STRIDE words apart
 #define GORSE_HOT_DONE_STRIDE 64
 // hot_done: two sets of arrival stripes (update launches alternate between them) and one line for the folders' pass counts (two words:
 // the hot tier's, the accumulated tier's)
 #define GORSE_HOT_DONE_WORDS (2 * GORSE_HOT_DONE_STRIPES * GORSE_HOT_DONE_STRIDE + GORSE_HOT_DONE_STRIDE)
 #ifndef GORSE_HOT_REPLICAS
-#define GORSE_HOT_REPLICAS 8  // replica rows of the hottest items (the most a slot gets, gorse_mf_create; bpr.hip kHotReplicas)
+#define GORSE_HOT_REPLICAS 8  // replica rows of the hottest items (the most a slot gets, gorse_mf_create; bpr_fold.hpp kHotReplicas)
 #endif
 
 struct gorse_mf {
@@ -59,7 +59,7 @@ struct gorse_mf {
     // BPR triplet chunk buffers (double-buffered: sampler fills one while the other is applied)
     gorse::DevBuf<int32_t> trip[2];
     size_t trip_cap = 0;  // samples per buffer
-    // user-run schedule (bpr.hip): the chunk's triplets counting-sorted by user
+    // user-run schedule (bpr_prepare.hip, bpr_update_users.hip): the chunk's triplets counting-sorted by user
     gorse::DevBuf<int32_t> sorted[2];  // su | si | sj, each trip_cap long
     gorse::DevBuf<int32_t> ubucket[2]; // U + 2 run offsets per triplet buffer (sorted on stream2)
     gorse::DevBuf<int32_t> urank[2];   // arrival rank of a sample inside its user's run, per triplet buffer
@@ -67,7 +67,7 @@ struct gorse_mf {
     gorse::DevBuf<int32_t> ubins;      // binned preparation: bin totals, bin starts at kMaxBins (preparations are serial: one copy)
     gorse::DevBuf<int32_t> ubinmat;    // binned preparation: the tile x bin count matrix
     int64_t chunk_seq = 0;             // chunks enqueued so far: buffer = chunk_seq & 1, across calls
-    // hot-row replicas of the Hogwild schedule (bpr.hip): popular items' updates land here.  hot_meta[slot] = hot_code(first row,
+    // hot-row replicas of the Hogwild schedule (bpr_fold.hpp): popular items' updates land here.  hot_meta[slot] = hot_code(first row,
     // log2 replica count) (hot_rows.hpp), the same word hot_slot holds for the slot's item; hot_rep holds hot_rows rows of d floats.
     gorse::DevBuf<int32_t> hot_slot, hot_items, hot_meta, hot_done;
     gorse::DevBuf<float> hot_rep;
@@ -77,11 +77,11 @@ struct gorse_mf {
     // hot_rep; their slots are entries n_hot .. n_hot + n_acc of hot_items / hot_meta
     int n_acc = 0;
     // handles with the tier: n_hot + n_acc rows of d floats, the slots' rows of Q as an update launch in the sole-writer form found
-    // them (bpr.hip, above HotRows); written and read by that launch's folders only, its content means nothing between two launches
+    // them (bpr_fold.hpp, above HotRows); written and read by that launch's folders only, its content means nothing between two launches
     gorse::DevBuf<float> hot_base;
     int fold_sole_last = 0;     // whether the last update launch with folders took that form (gorse_hip_test_bpr_fold_tier_stats)
     uint64_t hot_launches = 0;  // update launches with folders so far: the parity picks the launch's set of arrival stripes
-    int64_t n_cold = 0;  // items of class "cold" in hot_slot (-2): updates by write-through store (bpr.hip)
+    int64_t n_cold = 0;  // items of class "cold" in hot_slot (-2): updates by write-through store (bpr_update_users.hip)
     int64_t cold_window = 0;               // what n_cold was computed for (gorse_mf_set_bpr_cold_window)
     std::vector<int32_t> h_item_count;     // training feedbacks per item and
     std::vector<int32_t> h_hot_slot;       // the class of every item (hot_code, -1 warm, -2 cold) as last uploaded: host copies for a re-classification
@@ -142,7 +142,7 @@ struct gorse_mf {
 };
 
 namespace gorse {
-// implemented in bpr.hip / als.hip, used across files
+// implemented in mf.hip / als.hip, used across files (the BPR units' own: bpr_internal.hpp)
 int32_t mf_sync_streams(gorse_mf *h);
 // epoch pacing: mark the begin / end of one epoch on the update stream; read the finished ones (wait = block for all of them)
 // (begin: `record` = the caller issues other work of the epoch in front of its first update launch, *attach = the start event that

@@ -1209,7 +1209,7 @@ int32_t gh_test_bpr_acc_layout(int64_t U, int64_t I, int32_t d, const int64_t *u
     out3[0] = rows, out3[1] = (int64_t)hot.size(), out3[2] = n_cold;
     return (int32_t)n_acc;
 }
-// The owner mapping of the BPR sole-writer fold (csrc/hot_rows.hpp fold_share: csrc/bpr.hip run_folders takes a thread's share from it
+// The owner mapping of the BPR sole-writer fold (csrc/hot_rows.hpp fold_share: csrc/bpr_fold.hpp run_folders takes a thread's share from it
 // once per launch, and the periodic passes and the last pass all walk that share): for `folders` folder workgroups, the first
 // min(folders, hot_blocks) of them the hot tier's, every thread walks the groups of its share as a pass does.  owner[(slot, element)] =
 // block x threads + thread of the element's owner, -1 where nobody owns it; claims[(slot, element)] = how many threads claimed it.

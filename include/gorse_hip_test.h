@@ -144,7 +144,7 @@ void gorse_hip_test_set_als_plan(int32_t long_row, int32_t chunk);
 /* probe: samples per chunk of a gorse_mf handle created AFTERWARDS (0 = the library's choice: 32 x users, clamped to
  * [4M, 128M]); the user-run schedule applies a chunk at a time. */
 void gorse_hip_test_set_bpr_chunk(int64_t samples);
-/* which item updates of the user-run BPR kernel may take the STORE route (csrc/bpr.hip NEG_STORE): bit 0 = the NEGATIVE item of a
+/* which item updates of the user-run BPR kernel may take the STORE route (csrc/bpr_update_users.hip NEG_STORE): bit 0 = the NEGATIVE item of a
  * sample, when its class is "cold", is updated by one write-through store of fma(t, lr, row) instead of d atomic dwords (the
  * reference's own unlocked write, model.go:478-488; its row is then gathered one sample ahead instead of two); < 0 = the
  * library's default.  Only bit 0 is looked at: the forms that bits 1 and 2 once asked for (the positive item by store, the store
@@ -171,13 +171,13 @@ double gorse_hip_test_sgemm_last_ms(void);
 #define GORSE_TEST_SGEMM_NT_LONG 0x200
 int32_t gorse_hip_test_sgemm_last_form(void);
 /* test hook: runs the user-run schedule's preparation of ONE chunk (user draws, counting sort of the sample ids by user, item
- * draws by run: csrc/bpr.hip launch_prepare_users) for samples [sample_base, sample_base + n) and returns the run offsets
+ * draws by run: csrc/bpr_prepare.hip bpr_launch_prepare_users) for samples [sample_base, sample_base + n) and returns the run offsets
  * (off[u] .. off[u + 1] = the positions of user u's samples; off[U] .. off[U + 1] = samples whose user draw failed) and the
  * (positive, negative) pair at every position; a pair of -1 = no negative found.  The multiset of triplets equals what
  * gorse_bpr_sample_triplets returns for the same range. */
 int32_t gorse_hip_test_bpr_prepare_chunk(gorse_mf *h, int64_t n, uint64_t seed, uint64_t epoch, int64_t sample_base,
                                          int32_t *off /*U + 2, host*/, int32_t *si /*n, host*/, int32_t *sj /*n, host*/);
-/* the binned preparation finishes a bin in one LDS-resident pass (csrc/bpr.hip bpr_bin_finish_kernel): *samples = the samples of a
+/* the binned preparation finishes a bin in one LDS-resident pass (csrc/bpr_prepare.hip bpr_bin_finish_kernel): *samples = the samples of a
  * bin that pass holds (a larger bin goes through it a slice at a time), *row_entries = the entries of a bin's users' rows it copies
  * into LDS at most (longer ranges are read from global memory).  GORSE_TEST_BPR_THREE_KERNELS of gorse_hip_test_set_variant: the three
  * kernels that pass replaces (sort, item draws, grouping), whatever the shape.  Results never depend on either beyond the order of the
@@ -190,7 +190,7 @@ int32_t gorse_hip_test_bpr_fail_count(gorse_mf *h, int32_t *count /*host*/);
 /* items expected to be touched (as a positive: their share of the feedback; as a negative: 1 / items) less than once per
  * `samples` samples are of class "cold" in handles created AFTERWARDS; 0 = no cold items (every update an atomic). */
 void gorse_hip_test_set_bpr_cold_window(int64_t samples);
-/* hot-row replicas of the Hogwild BPR schedules (csrc/bpr.hip HotRows, csrc/hot_rows.hpp).  Handles created AFTERWARDS give a hot item
+/* hot-row replicas of the Hogwild BPR schedules (csrc/bpr_fold.hpp HotRows, csrc/hot_rows.hpp).  Handles created AFTERWARDS give a hot item
  * R = the smallest power of two >= (its expected updates per sample) / unit replica rows, 1 .. 8; unit <= 0 = the library's default.
  * Results never depend on it beyond the Hogwild race itself. */
 void gorse_hip_test_set_bpr_replica_unit(double unit);
@@ -204,7 +204,7 @@ int32_t gorse_hip_test_bpr_fold_stats(gorse_mf *h, int64_t *out3 /*host*/);
  * follow those of slot s - 1), rep = every replica row (sum of R x nFactors floats; all zero between two update launches).  Any of the
  * three may be NULL. */
 int32_t gorse_hip_test_bpr_hot_state(gorse_mf *h, int32_t *items /*host*/, int32_t *replicas /*host*/, float *rep /*host*/);
-/* The accumulated tier (csrc/hot_rows.hpp acc_rows_layout, csrc/bpr.hip): on a handle that takes the user-run schedule natively, has
+/* The accumulated tier (csrc/hot_rows.hpp acc_rows_layout, csrc/bpr_fold.hpp): on a handle that takes the user-run schedule natively, has
  * no cold item at create and whose item factors fit 4 MiB, every warm item has ONE accumulator row behind the replica rows; the
  * workers add its updates there and folder workgroups of the tier's own add the rows to Q every `periods` fold periods.  The two hooks
  * above keep reporting the hot tier only.
@@ -219,7 +219,7 @@ void gorse_hip_test_set_bpr_acc_rows(int32_t on);
 void gorse_hip_test_set_bpr_acc_fold_every(int32_t periods);
 int32_t gorse_hip_test_bpr_acc_state(gorse_mf *h, int32_t *items /*host*/, float *rows /*host*/);
 int32_t gorse_hip_test_bpr_item_classes(gorse_mf *h, int32_t *slot /*host, items*/, int64_t *out2 /*host*/);
-/* The folds of an update launch (csrc/bpr.hip, above HotRows).  A user-run launch on a handle with the accumulated tier and the store
+/* The folds of an update launch (csrc/bpr_fold.hpp, above HotRows).  A user-run launch on a handle with the accumulated tier and the store
  * route closed has no worker that writes Q: its folders fold as Q's sole writers, with loads and stores (Q <- the row as the launch
  * found it + the slot's rows); every other launch folds with atomics.
  * fold_tier_stats, after the handle's streams drain: out6 = {folder passes of the hot tier in the last update launch with folders

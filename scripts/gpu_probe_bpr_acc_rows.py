@@ -1,4 +1,4 @@
-"""Probe of the accumulated tier's fold interval (csrc/bpr.hip kDefaultAccFoldEvery) on S-ml1m: for nFactors 8 / 16 / 64 and the tier
+"""Probe of the accumulated tier's fold interval (csrc/bpr_fold.hpp kDefaultAccFoldEvery) on S-ml1m: for nFactors 8 / 16 / 64 and the tier
 off / folded every 2 / 4 / 8 fold periods -- device milliseconds per epoch (15 epochs enqueued back to back, after 3) and NDCG@10 after
 30 epochs of the production mode on three sampler seeds (the fixtures of tests/test_gpu_bpr_positive_series.py; the sequential oracle's
 figures for the same streams are printed by tests/test_gpu_bpr_acc_rows.py).  usage: python scripts/gpu_probe_bpr_acc_rows.py [out.txt]"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU probe: the user-run BPR update with write-through stores on the cold NEGATIVE item rows (csrc/bpr.hip NEG_STORE), against the atomics-only
+"""GPU probe: the user-run BPR update with write-through stores on the cold NEGATIVE item rows (csrc/bpr_update_users.hip NEG_STORE), against the atomics-only
 form, per shape: update-kernel ms per epoch, end-to-end rate, NDCG@10 next to the sequential oracle, and the lost updates.
 
 Lost updates are counted, not guessed: with P = 2^-10 everywhere, Q = 0, reg = 0 and lr = 2^-20 every sample moves its positive

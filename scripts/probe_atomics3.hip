@@ -1,6 +1,6 @@
 // probe_atomics3.hip -- the atomic unit under BPR's access mix: a 16-lane group adds a whole 256-byte row (d = 64: four 64-byte
 // pieces) at a random row of an N-row table, (a) nothing else, (b) after LOADING that row (agent-scope loads, as the gathers of
-// csrc/bpr.hip) two iterations earlier, (c) the same with plain cached loads, (d) rows drawn only from the eighth of the table that
+// csrc/bpr_update_users.hip) two iterations earlier, (c) the same with plain cached loads, (d) rows drawn only from the eighth of the table that
 // belongs to the XCD the wave runs on (are atomics cheaper when a line is only ever touched from one XCD?), (e) a zipf-like draw.
 // build: hipcc --offload-arch=gfx950 -O3 -munsafe-fp-atomics scripts/probe_atomics3.hip -o gpurun_bin/probe_atomics3
 #include <hip/hip_runtime.h>

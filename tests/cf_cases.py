@@ -62,9 +62,9 @@ def als_half_fp64(A, B, ptr, idx, bptr, w, reg, rows):
 # What ONE grid of each capped matrix-factorisation launch holds before its kernel's grid-stride loop takes a second step.  The tests of
 # tests/test_gpu_cf_past_one_grid.py size their inputs from these literals; tests/test_mf_grid_caps_cpu.py holds every one of them
 # against the launcher's own text, so a cap raised later fails a test instead of leaving the strided iterations unvisited again.
-GRID_USER_RUNS = 65_536       # launch_update_users: 256 * 16 workgroups x 16 groups, one user run each (nFactors 8: two per group)
+GRID_USER_RUNS = 65_536       # bpr_launch_update_users (bpr_plan.hpp bpr_user_run_workers): 256 * 16 workgroups x 16 groups, one user run each (nFactors 8: two per group)
 GRID_USER_RUNS_D8 = 131_072
-GRID_SAMPLES = 65_536         # launch_update_mode: 256 * 16 workgroups x 16 groups, one sample each
+GRID_SAMPLES = 65_536         # launch_update_mode (bpr_plan.hpp bpr_sample_workers): 256 * 16 workgroups x 16 groups, one sample each
 GRID_SCORE_PAIRS = 131_072    # mf_score_device: 256 * 32 workgroups x 16 groups, one pair each
 GRID_RANK_LISTS = 4_096       # mf_rank_device: expand_users_kernel, one workgroup per list
 GRID_DELTA_FLOATS = 2_097_152  # mf_delta_export_async / _import_async: 2048 workgroups x 256 threads x one float4

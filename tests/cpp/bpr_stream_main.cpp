@@ -1,7 +1,7 @@
 // Stand-alone check of gorse_amd/csrc/bpr_stream.hpp (the BPR sample stream: model/cf/model.go:449-468), built by
 // tests/test_bpr_stream_cpu.py with AddressSanitizer and UBSan.  usage: bpr_stream WORLD OUT
 // WORLD: "U I" | U + 1 row pointers | the rows in stored order | the rows sorted | the number of runs | per run "seed epoch base n".
-// Every sample of every run is drawn the three ways the kernels of csrc/bpr.hip compose the header's functions:
+// Every sample of every run is drawn the three ways the kernels of csrc/bpr_prepare.hip compose the header's functions:
 //   1. the whole triplet in one go                                   (bpr_sample_kernel)
 //   2. the user first, the items later by replay                     (bpr_sample_user_kernel, bpr_sample_items_kernel, the bins' finish)
 //   3. the first user draw and the first negative candidate inline, the rest by a restart from the start of the stream

@@ -1,7 +1,7 @@
-"""The per-bin finish of the BPR chunk preparation and the one-read offsets kernel (csrc/bpr.hip: bpr_bin_finish_kernel,
+"""The per-bin finish of the BPR chunk preparation and the one-read offsets kernel (csrc/bpr_prepare.hip: bpr_bin_finish_kernel,
 bpr_bin_offsets_kernel) compile for gfx950 without spills and without scratch, and the finish kernel's LDS -- all of it static: the
 launch asks for none beyond it -- leaves room for two workgroups on a CU's 160 KiB.  Checked on the gfx950 assembly hipcc emits for
-bpr.hip (no device)."""
+bpr_prepare.hip (no device)."""
 import ctypes as C
 import os
 import re
@@ -19,7 +19,7 @@ LDS_PER_CU = 160 * 1024
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_finish_and_offsets_kernels_without_spills_scratch_or_excess_lds():
-    src = os.path.join(ROOT, "gorse_amd", "csrc", "bpr.hip")
+    src = os.path.join(ROOT, "gorse_amd", "csrc", "bpr_prepare.hip")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa_census.py"), src, "bpr_bin_"],
                          capture_output=True, text=True, check=True).stdout
     seen = {}

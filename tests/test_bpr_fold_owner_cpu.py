@@ -1,5 +1,5 @@
 """Who owns which element in the sole-writer fold of the BPR user-run launches (gorse_amd/csrc/hot_rows.hpp fold_share, reached through
-the host library's hook gh_test_bpr_fold_owner; csrc/bpr.hip run_folders takes a thread's share from that function once per launch and
+the host library's hook gh_test_bpr_fold_owner; csrc/bpr_fold.hpp run_folders takes a thread's share from that function once per launch and
 walks it in every periodic pass and in the last one).  Such a launch folds with loads and stores, so the atomics' place is taken by
 one invariant: every element of every slot has exactly one owner thread.  Checked for tiers of one slot, for the C2 shape (926 hot
 slots, 2,780 of the accumulated tier) and a smaller one, at every user-run width, with 64 folder workgroups (32 per tier: what a
@@ -18,7 +18,7 @@ import pytest
 
 from gorse_amd import cf
 
-HOT_BLOCKS, THREADS = 32, 256  # csrc/bpr.hip kFolderBlocks, the update kernels' workgroup
+HOT_BLOCKS, THREADS = 32, 256  # csrc/bpr_plan.hpp kFolderBlocks, the update kernels' workgroup
 
 
 def owners(n_hot, n_acc, d, folders):

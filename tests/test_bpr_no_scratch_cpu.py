@@ -1,6 +1,7 @@
-"""No BPR update kernel spills or uses scratch (csrc/bpr.hip): the folder workgroups of an update launch (run_folders, fold_pass)
-keep a slot's replica values in registers whatever its replica count, and the workers address a hot item's replica row from the
-item's class word alone.  Checked on the gfx950 assembly hipcc emits for bpr.hip (no device)."""
+"""No BPR update kernel spills or uses scratch (csrc/bpr_update_users.hip, csrc/bpr_update.hip): the folder workgroups of an update
+launch (csrc/bpr_fold.hpp run_folders, fold_pass) keep a slot's replica values in registers whatever its replica count, and the workers
+address a hot item's replica row from the item's class word alone.  Checked on the gfx950 assembly hipcc emits for the two update
+units (no device)."""
 import os
 import re
 import shutil
@@ -14,8 +15,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_no_bpr_update_kernel_spills_or_scratch():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa_census.py"), os.path.join(ROOT, "gorse_amd", "csrc", "bpr.hip"),
-                          "update"], capture_output=True, text=True, check=True).stdout
+    out = "".join(subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa_census.py"), os.path.join(ROOT, "gorse_amd", "csrc", unit),
+                                  "update"], capture_output=True, text=True, check=True).stdout
+                  for unit in ("bpr_update_users.hip", "bpr_update.hip"))
     seen = {}
     for line in out.splitlines():
         m = re.match(r"^(?:void )?(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+sgpr\s+(\d+)\s+spills: vgpr (\d+) sgpr (\d+)\s+scratch (\d+) B", line)

@@ -1,5 +1,5 @@
 """The BPR sample stream (gorse_amd/csrc/bpr_stream.hpp) without a device: tests/cpp/bpr_stream_main.cpp, built with AddressSanitizer
-and UBSan, draws every sample the three ways the kernels of csrc/bpr.hip compose the header's functions and requires the same
+and UBSan, draws every sample the three ways the kernels of csrc/bpr_prepare.hip compose the header's functions and requires the same
 triplets and the same given-up samples; route 1's triplets are compared here with the oracle's orc_bpr_sample
 (model/cf/model.go:449-468), on every world."""
 import os

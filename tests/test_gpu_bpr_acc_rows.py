@@ -1,4 +1,4 @@
-"""The accumulated tier of the Hogwild BPR schedules (csrc/hot_rows.hpp acc_rows_layout, csrc/bpr.hip run_folders / fold_acc_pass): on a
+"""The accumulated tier of the Hogwild BPR schedules (csrc/hot_rows.hpp acc_rows_layout, csrc/bpr_fold.hpp run_folders / fold_acc_pass): on a
 handle that takes the user-run schedule natively, has no cold item and whose item factors fit 4 MiB, every warm item's updates land in
 one accumulator row behind the hot items' replica rows, and folder workgroups of the tier's own add those rows to Q inside the launch.
 Checked at the smallest shape that reaches every edge (4096 users, 512 items, rows of 8), at nFactors 8 / 16 / 64 / 128, in both

@@ -1,4 +1,4 @@
-"""The per-bin finish of the binned BPR chunk preparation (csrc/bpr.hip: bpr_bin_finish_kernel).
+"""The per-bin finish of the binned BPR chunk preparation (csrc/bpr_prepare.hip: bpr_bin_finish_kernel).
 
 One workgroup per bin of user ids sorts the bin's samples by user, draws their items and groups equal positives, all in LDS; it
 replaces bpr_bin_sort_kernel, bpr_sample_items_kernel and bpr_group_positives_kernel, which variant bit 19 brings back.  Every case
@@ -16,7 +16,7 @@ from gorse_amd import capi
 pytestmark = pytest.mark.gpu
 
 VARIANT_THREE_KERNELS, VARIANT_ARRIVAL_ORDER = 1 << 19, 1 << 20
-GROUP_CAP = 1024  # csrc/bpr.hip kGroupCap: the longest run whose order is fixed
+GROUP_CAP = 1024  # csrc/bpr_prepare.hip kGroupCap: the longest run whose order is fixed
 TILE = 4096       # csrc/bpr_bins.hpp prep_bins: samples per workgroup of the count / scatter kernels (chunks under 2M samples)
 SEED, EPOCH, BASE = (1 << 32) + 12345, 3, 1 << 40
 

@@ -1,4 +1,4 @@
-"""The sole-writer fold of the BPR user-run launches (csrc/bpr.hip, above HotRows; csrc/hot_rows.hpp fold_share): on a handle with the
+"""The sole-writer fold of the BPR user-run launches (csrc/bpr_fold.hpp, above HotRows; csrc/hot_rows.hpp fold_share): on a handle with the
 accumulated tier no worker writes Q, and the launch's folders fold with loads and stores -- Q <- base + the slot's rows, base = the
 row as the launch found it -- instead of an exchange and an atomic add per pass.  The shape and the counting trick are those of
 tests/test_gpu_bpr_acc_rows.py (4096 users, 512 items, rows of 8; P = 2^-10, reg = 0, lr = 2^-20: every sample moves its positive's row

@@ -1,4 +1,4 @@
-"""Hot items with one replica row and with eight (csrc/hot_rows.hpp, csrc/bpr.hip HotRows): after ONE Hogwild update call -- in the
+"""Hot items with one replica row and with eight (csrc/hot_rows.hpp, csrc/bpr_fold.hpp HotRows): after ONE Hogwild update call -- in the
 user-run schedule one update launch whose folders make the last pass, no fold kernel and no other launch behind it; in the per-sample
 schedule the launch and its fold kernel -- Q holds every update of both items, whether it came as the positive or (user-run schedule)
 as the negative, and every replica row reads zero.  The style of test_gpu_cf_parity.py::test_bpr_atomic_hot_rows_fold_exactly: reg = 0 and a

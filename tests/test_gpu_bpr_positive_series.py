@@ -1,4 +1,4 @@
-"""Positive series of the user-run schedule (csrc/bpr.hip: bpr_group_positives_kernel, POSITIVE SERIES in bpr_update_user_kernel).
+"""Positive series of the user-run schedule (csrc/bpr_prepare.hip: bpr_group_positives_kernel; csrc/bpr_update_users.hip: POSITIVE SERIES in bpr_update_user_kernel).
 
 The preparation of a chunk puts the samples of a run that share their positive next to each other; the update kernel walks such a
 stretch (a series) with the positive's row in registers and sends the summed change as one atomic row update.  Checked here:
@@ -19,7 +19,7 @@ from oracle import oracle as orc
 pytestmark = pytest.mark.gpu
 
 VARIANT_USER_RUNS, VARIANT_STABLE_RANK = 128, 1 << 29
-GROUP_CAP = 1024  # csrc/bpr.hip kGroupCap: the longest run the grouping pass orders
+GROUP_CAP = 1024  # csrc/bpr_prepare.hip kGroupCap: the longest run the grouping pass orders
 
 
 def bits(a):

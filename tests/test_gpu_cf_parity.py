@@ -437,7 +437,7 @@ def test_bpr_user_runs_equal_the_sequential_result_when_items_are_disjoint(oracl
 # (the case at 64 keeps the id it had while the test fixed d = 64: "1"; the others are "1-d8", ...)
 @pytest.mark.parametrize("store_mode,d", [pytest.param(1, d, id="1" if d == 64 else "1-d%d" % d) for d in (64, 8, 16, 32, 128)])
 def test_bpr_user_runs_cold_rows_by_store_are_bit_exact(oracle, store_mode, d):
-    """The cold-row route of the user-run schedule (csrc/bpr.hip NEG_STORE): an item expected to be touched less than once per cold
+    """The cold-row route of the user-run schedule (csrc/bpr_update_users.hip NEG_STORE): an item expected to be touched less than once per cold
     window gets its update as ONE write-through store of fma(t, lr, row) -- the reference's own unlocked write (model.go:478-488)
     -- instead of d atomic dwords.  With every item row touched by one sample and ranks in stream order the result is unique:
     P bit-exact, and the rows that took the store route equal the sequential oracle BIT FOR BIT (one fma, where the atomic
@@ -505,7 +505,7 @@ def _sorted_triples(u, i, j):
 
 def test_prepared_chunk_holds_the_sampled_triplets(oracle, small):
     """The user-run schedule prepares a chunk in two passes -- user draws + counting sort of the sample ids, then the item draws
-    run by run (csrc/bpr.hip launch_prepare_users) -- and must produce exactly the triplets of the per-sample sampler
+    run by run (csrc/bpr_prepare.hip bpr_launch_prepare_users) -- and must produce exactly the triplets of the per-sample sampler
     (model.go:449-468 through the shared Philox stream; test_sampler_matches_oracle pins that one to the oracle), each in the
     run of its user."""
     L = capi.lib()
@@ -558,7 +558,7 @@ def test_prepared_chunk_at_a_size_the_product_takes_the_path(oracle):
 
 def test_prepared_chunk_above_the_item_batch_threshold(oracle):
     """A handle of 8,396,000 feedbacks, just over the 8 Mi beyond which the item draws of a prepared chunk are
-    bpr_sample_items_batch_kernel's (csrc/bpr.hip kItemsBatchFrom: four positions per thread, the first negative candidate inline, the
+    bpr_sample_items_batch_kernel's (csrc/bpr_plan.hpp kItemsBatchFrom: four positions per thread, the first negative candidate inline, the
     rest by a restart of the sample's stream) -- the route of every C3 shape.  No test switch.  Three users without feedback, one
     holding every item (its samples are given up on), every other user half of the items: half of the first candidates are
     rejected, so the restart is taken throughout.  Asserts what test_prepared_chunk_holds_the_sampled_triplets asserts."""
@@ -593,7 +593,7 @@ def test_prepared_chunk_above_the_item_batch_threshold(oracle):
 
 
 def test_prepared_chunk_binned_and_unbinned_on_many_users(oracle):
-    """The binned preparation (csrc/bpr.hip, bpr_bin_count / _scatter / _sort kernels: bins of 2^shift user ids, here 1024 ids per bin
+    """The binned preparation (csrc/bpr_prepare.hip, bpr_bin_count / _scatter / _sort kernels: bins of 2^shift user ids, here 1024 ids per bin
     and several tiles) and the preparation without bins (variant bit 21) hold the same runs: the triplets of the per-sample sampler,
     each in the run of its user; users without feedback (every third id) never own a run."""
     L = capi.lib()

@@ -1,6 +1,6 @@
 """The matrix-factorisation kernels past their grid caps, where their grid-stride loops take a second step.
 
-Every launch of csrc/bpr.hip, csrc/mf_rank.hip and csrc/mf.hip caps its grid and walks the rest of its work in a grid-stride loop; the
+Every launch of the BPR units (csrc/bpr_prepare.hip, csrc/bpr_update.hip, csrc/bpr_update_users.hip), csrc/mf_rank.hip and csrc/mf.hip caps its grid and walks the rest of its work in a grid-stride loop; the
 neighbouring modules pin these kernels per element at every factor width but give none of them more work than one grid holds.  The
 strided iteration is where state survives from one item of work to the next -- the LDS rows a group reuses behind a wave barrier, the
 "last two samples" history of a user-run group -- and it is what the product's shapes run (S-ml1m: 6040 users, C3: a million).  The
@@ -78,7 +78,7 @@ def run_stream(S, rng):
 
 @pytest.mark.parametrize("d", [16, 32, 64, 128, 8])
 def test_bpr_user_runs_past_one_grid_equal_the_sequential_result(oracle, d):
-    """bpr_update_user_kernel<NC, false, D8> through launch_update_users, whose grid holds 256 * 16 workgroups x 16 groups = 65,536
+    """bpr_update_user_kernel<NC, false, D8> through bpr_launch_update_users, whose grid holds 256 * 16 workgroups x 16 groups = 65,536
     user runs (131,072 at nFactors 8: a run per half group): U = cap + 37, so groups 0 .. 36 walk a SECOND user (cap + slot) with the
     history (im1 .. jm2), the series state and the registers the first run left.  The recipe and the assertions of
     test_bpr_user_runs_equal_the_sequential_result_when_items_are_disjoint (tests/test_gpu_cf_parity.py): every item row touched by one

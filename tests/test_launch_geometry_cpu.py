@@ -1,4 +1,4 @@
-"""The geometry of the BPR chunk preparation by user bins (gorse_amd/csrc/bpr_bins.hpp, included by csrc/bpr.hip's launch code and by
+"""The geometry of the BPR chunk preparation by user bins (gorse_amd/csrc/bpr_bins.hpp, included by csrc/bpr_prepare.hip's launch code through csrc/bpr_plan.hpp and by
 the host library's hooks): for every shape the product can meet, the bins fit the kernels' LDS, the tile x bin matrix a handle
 allocates holds every chunk up to its capacity, and the four passes -- restated on the CPU in the kernels' arithmetic -- leave every
 sample in the run of its user with the run offsets the update kernel reads.  Reference semantics: the samples of an epoch

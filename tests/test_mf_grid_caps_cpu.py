@@ -1,5 +1,7 @@
 """The grid caps that tests/test_gpu_cf_past_one_grid.py sizes its inputs from (the GRID_* literals of tests/cf_cases.py), held against
 the launchers' own text (no GPU): a cap raised later fails here instead of silently leaving a kernel's grid-stride loop unvisited again.
+The BPR launchers (csrc/bpr_update_users.hip, csrc/bpr_update.hip, csrc/bpr_prepare.hip; named below without their bpr_ prefix) take
+their grids from csrc/bpr_plan.hpp: the text read here is the plan function's and the launcher's call of it.
 
 Every capped launch of the matrix-factorisation sources, what one grid of it holds, and the test that gives it more:
 
@@ -69,26 +71,40 @@ def group_geometry():
 def test_group_kernels_hold_what_the_tests_assume():
     k_group, k_block, groups = group_geometry()
     assert (k_group, k_block, groups) == (16, 256, 16)
-    bpr = source("bpr.hip")
+    # the BPR launches take their grids from csrc/bpr_plan.hpp (whose values tests/cpp/bpr_plan_main.cpp checks one by one)
+    plan = source("bpr_plan.hpp")
+    assert constant(plan, "kRunsPerBlock") == groups and "static_assert(kRunsPerBlock == kGroupsPerBlock" in source("bpr_internal.hpp")
+    blocks = product(re.search(r"constexpr int64_t kUpdateBlocks = ([\d *]+);", plan).group(1))
     # user runs: a run per group, two at nFactors 8 while GORSE_BPR_D8_PAIRS is on
-    users = function_body(bpr, "int32_t launch_update_users(gorse_mf *h")
-    assert "int64_t blocks = ceil_div(h->U, (int64_t)kGroupsPerBlock * (d == 8 && GORSE_BPR_D8_PAIRS ? 2 : 1));" in users
-    cap = re.search(r"const int64_t capb = ([\d *]+);\s*if \(blocks > capb\) blocks = capb;", users)
-    assert product(cap.group(1)) * groups == cc.GRID_USER_RUNS == 65_536
-    assert re.search(r"#define GORSE_BPR_D8_PAIRS 1\b", bpr) and "dim3 grid((unsigned)blocks), block(kBlock);" in users
+    users_unit = source("bpr_update_users.hip")
+    users = function_body(users_unit, "int32_t gorse::bpr_launch_update_users(gorse_mf *h")
+    assert "int64_t blocks = bpr_user_run_workers(h->U, d, GORSE_BPR_D8_PAIRS);" in users
+    workers = function_body(plan + "\n}\n", "inline int64_t bpr_user_run_workers(int64_t U, int d, bool d8_pairs) {")
+    assert "const int64_t per = (int64_t)kRunsPerBlock * (d == 8 && d8_pairs ? 2 : 1);" in workers
+    assert "return std::min<int64_t>((U + per - 1) / per, kUpdateBlocks);" in workers
+    assert blocks * groups == cc.GRID_USER_RUNS == 65_536
+    assert re.search(r"#define GORSE_BPR_D8_PAIRS 1\b", users_unit) and "dim3 grid((unsigned)blocks), block(kBlock);" in users
     assert 2 * cc.GRID_USER_RUNS == cc.GRID_USER_RUNS_D8 == 131_072
-    kernel = function_body(bpr, "void bpr_update_user_kernel(")
+    kernel = function_body(users_unit, "void bpr_update_user_kernel(")
     assert "const int64_t ngroups = (int64_t)((int)gridDim.x - folders) * kGroupsPerBlock * SUBS;" in kernel
     assert "for (int64_t u = group; u < U; u += ngroups) {" in kernel
     # per-sample schedule: a sample per group
-    mode = function_body(bpr, "int32_t launch_update_mode(gorse_mf *h")
-    assert "int64_t blocks = ceil_div(n, kGroupsPerBlock);" in mode
-    cap = re.search(r"const int64_t cap = ([\d *]+);[^\n]*\n\s*if \(blocks > cap\) blocks = cap;", mode)
-    assert product(cap.group(1)) * groups == cc.GRID_SAMPLES == 65_536
+    sample_unit = source("bpr_update.hip")
+    mode = function_body(sample_unit, "int32_t launch_update_mode(gorse_mf *h")
+    assert "int64_t blocks = bpr_sample_workers(n);" in mode and "dim3 grid((unsigned)blocks), block(kBlock);" in mode
+    assert ("inline int64_t bpr_sample_workers(int64_t n) { return std::min<int64_t>((n + kRunsPerBlock - 1) / kRunsPerBlock, kUpdateBlocks); }"
+            in plan)
+    assert blocks * groups == cc.GRID_SAMPLES == 65_536
+    kernel = function_body(sample_unit, "void bpr_update_kernel(")
+    assert "const int64_t ngroups = (int64_t)((int)gridDim.x - folders) * kGroupsPerBlock;" in kernel
+    assert "for (int64_t s = begin + group; s < end; s += ngroups) {" in kernel
     # its fold kernel: an element of a hot or accumulated row per thread
-    fold = re.search(r"ceil_div\(\(int64_t\)\(hot\.n_hot \+ hot\.n_acc\) \* d, (\d+)\), (\d+)\);\s*hipExtLaunchKernelGGL\(bpr_fold_kernel, "
-                     r"dim3\(\(unsigned\)fb\), dim3\((\d+)\)", mode)
-    assert fold.group(1) == fold.group(3) and int(fold.group(2)) * int(fold.group(3)) == cc.GRID_FOLD_ELEMENTS == 131_072
+    assert "const int64_t fb = bpr_fold_grid(hot.n_hot, hot.n_acc, d);" in mode
+    assert "hipExtLaunchKernelGGL(bpr_fold_kernel, dim3((unsigned)fb), dim3(kFoldThreads)" in mode
+    fold = re.search(r"return std::min<int64_t>\(\(\(int64_t\)\(n_hot \+ n_acc\) \* d \+ kFoldThreads - 1\) / kFoldThreads, (\d+)\);",
+                     function_body(plan + "\n}\n", "inline int64_t bpr_fold_grid(int n_hot, int n_acc, int d) {"))
+    assert int(fold.group(1)) * constant(plan, "kFoldThreads") == cc.GRID_FOLD_ELEMENTS == 131_072
+    assert "w < work; w += (int64_t)gridDim.x * blockDim.x) {" in function_body(sample_unit, "void bpr_fold_kernel(")
     # score: a pair per group
     rank = source("mf_rank.hip")
     score = function_body(rank, "int32_t gorse::mf_score_device(")
@@ -109,15 +125,25 @@ def test_flat_kernels_hold_what_the_tests_assume():
         cap = re.search(r"std::min<int64_t>\(ceil_div\(n4, (\d+)\), (\d+)\);\s*%s<<<dim3\(\(unsigned\)blocks\), dim3\((\d+)\)" % kernel, body)
         assert cap.group(1) == cap.group(3)
         assert int(cap.group(2)) * int(cap.group(3)) * 4 == cc.GRID_DELTA_FLOATS == 2_097_152  # a float4 per thread
-    bpr = source("bpr.hip")
-    sort = function_body(bpr, "int32_t launch_user_sort(")
-    cap = re.search(r"const int64_t blocks = std::min<int64_t>\(ceil_div\(n, (\d+)\), ([\d *]+)\);", sort)
-    assert sort.count("<<<dim3((unsigned)blocks), dim3(%s)" % cap.group(1)) == 2  # bpr_rank_kernel, bpr_scatter_by_kernel
-    assert int(cap.group(1)) * product(cap.group(2)) == cc.GRID_SORT_SAMPLES == 524_288
-    scan = function_body(bpr, "int32_t exclusive_scan_i32(")
-    tiles = re.search(r"if \(nt <= (\d+)\) \{\s*scan_small_kernel", scan)
-    assert "const int64_t nt = ceil_div(m, kScanTile);" in scan
-    assert int(tiles.group(1)) * constant(bpr, "kScanTile") == cc.SCAN_ONE_WORKGROUP == 32_768
+    # the flat kernels of the BPR preparation: the grid is csrc/bpr_plan.hpp's, for every launch of them
+    plan, prep = source("bpr_plan.hpp"), source("bpr_prepare.hip")
+    cap = re.search(r"inline int64_t bpr_flat_grid\(int64_t n\) \{ return std::min<int64_t>\(\(n \+ kFlatThreads - 1\) / kFlatThreads, ([\d *]+)\); \}",
+                    plan)
+    sort = function_body(prep, "int32_t gorse::bpr_launch_user_sort(")
+    assert "const int64_t blocks = bpr_flat_grid(n);" in sort
+    assert sort.count("<<<dim3((unsigned)blocks), dim3(kFlatThreads)") == 2  # bpr_rank_kernel, bpr_scatter_by_kernel
+    assert constant(plan, "kFlatThreads") * product(cap.group(1)) == cc.GRID_SORT_SAMPLES == 524_288
+    for head in ("int32_t gorse::bpr_launch_sampler(", "int32_t gorse::bpr_launch_prepare_users("):
+        body = function_body(prep, head)
+        assert "blocks = bpr_flat_grid(n);" in body and "dim3((unsigned)blocks), dim3(kFlatThreads)" in body, head
+    for kernel in ("bpr_sample_kernel", "bpr_sample_user_kernel", "bpr_scatter_ids_kernel", "bpr_sample_items_kernel", "bpr_rank_kernel",
+                   "bpr_scatter_by_kernel"):
+        assert re.search(r"< n; \w \+= \(int64_t\)gridDim\.x \* blockDim\.x\)", function_body(prep, "void %s(" % kernel)), kernel
+    scan = function_body(prep, "int32_t exclusive_scan_i32(")
+    assert re.search(r"if \(bpr_scan_one_workgroup\(m\)\) \{\s*scan_small_kernel", scan) and "const int64_t nt = bpr_scan_tiles(m);" in scan
+    assert "inline int64_t bpr_scan_tiles(int64_t m) { return (m + kScanTile - 1) / kScanTile; }" in plan
+    assert "inline bool bpr_scan_one_workgroup(int64_t m) { return bpr_scan_tiles(m) <= kScanSmallTiles; }" in plan
+    assert constant(plan, "kScanSmallTiles") * constant(plan, "kScanTile") == cc.SCAN_ONE_WORKGROUP == 32_768
 
 
 def test_the_tests_named_above_exist():
