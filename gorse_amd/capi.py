@@ -54,6 +54,8 @@ SIGNATURES = {
     "gorse_mf_rank": (C.c_int32, [_vp, C.c_int64, _i32p, _i64p, _i32p, C.c_int32, _i32p, _i32p]),
     "gorse_mf_recommend": (C.c_int32, [_vp, C.c_int64, _i32p, C.c_int32, C.POINTER(C.c_uint8), _i64p, _i32p, _i32p, _f32p, _i32p]),
     "gorse_mf_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
+    "gorse_mf_set_recommend_route": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_mf_get_recommend_route": (C.c_int32, [_vp, _i32p, _i32p]),
     "gorse_mf_sample_user_negatives": (C.c_int32, [_vp, _i64p, _i32p, C.c_int32, C.c_uint64, _i32p, _i32p]),
     "gorse_mf_resident_candidates": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_mf_resident_generation": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
@@ -365,6 +367,16 @@ class MF:
         nf, nl, ms = C.c_int64(0), C.c_int64(0), C.c_double(0)
         check(lib().gorse_mf_recommend_stats(self.h, C.byref(nf), C.byref(nl), C.byref(ms)))
         return nf.value, nl.value, ms.value
+
+    def set_recommend_route(self, route):
+        """which kernel scores recommend()'s threshold queries: 0 = vector ALU (default), 1 = matrix cores (falls back where unserved)"""
+        check(lib().gorse_mf_set_recommend_route(self.h, int(route)))
+
+    def recommend_route(self):
+        """(the route asked for, the route that served the last recommend()'s threshold queries)"""
+        req, used = C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_mf_get_recommend_route(self.h, C.byref(req), C.byref(used)))
+        return req.value, used.value
 
     def sample_user_negatives(self, test_indptr, test_indices, num_candidates, seed=0, fetch=True):
         """dataset.SampleUserNegatives on the device: (neg U x n padded with -1, len U); the candidate lists of the users with

@@ -131,6 +131,7 @@ struct gorse_mf {
     gorse::DevBuf<char> rec_seen;  // gorse_mf_recommend's seen rows, sorted (row pointer | items); the candidate chain brings its own
     int64_t rec_fast = 0, rec_literal = 0;
     double rec_ms = 0.0;
+    int32_t rec_route = 0, rec_route_used = 0;  // gorse_mf_set_recommend_route: 0 = vector kernel, 1 = matrix kernel; what the last call ran
     gorse::KernelProfile prof{GORSE_PROF_NCLASSES};
 
     int32_t use() const {

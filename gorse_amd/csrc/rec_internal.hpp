@@ -1,0 +1,61 @@
+// rec_internal.hpp -- what the units of gorse_mf_recommend share: the launch's arguments, the candidate test and the survivor
+// buffer's compaction (recommend.hip: the vector kernel, the merge, the literal path, the planner and its constants;
+// recommend_mfma.hip: the matrix-core kernel).
+#pragma once
+#include <cmath>
+
+#include "mf_internal.hpp"
+
+namespace gorse {
+
+struct RecArgs {
+    const float *P, *Q;
+    const int32_t *users;  // null: query t is user t
+    const int64_t *uptr;
+    const int32_t *uidx_sorted;
+    const int64_t *sptr;  // null: no seen rows
+    const int32_t *seen;  // every row sorted ascending
+    const uint8_t *item_ok;
+    int64_t q0, nq;  // the launch's queries are [q0, q0 + nq)
+    int32_t I, d, k, kk, cap, slices, slice_len, tile_items;
+    float *buf_s;     // nq * slices * 2 * cap: two halves per (query, slice), a compaction moves from one to the other
+    int32_t *buf_i;
+    float *out_s;     // nq * slices * kk: the slice's kk best, sorted by score descending
+    int32_t *out_i;
+    int32_t *out_cnt;   // nq * slices
+    int32_t *nan_flag;  // nq
+};
+
+__device__ __forceinline__ bool rec_candidate(const uint8_t *__restrict__ item_ok, const int32_t *trow, int64_t tn, const int32_t *srow,
+                                              int64_t sn, int32_t item) {
+    return item_ok[item] != 0 && !row_contains(trow, tn, item) && !(sn > 0 && row_contains(srow, sn, item));
+}
+
+// One 16-lane group: the kk best of cnt buffered entries to dst, sorted by score descending (equal scores in buffer order).  Every
+// entry is ranked by counting the entries ahead of it.  Returns the kk-th best score (-inf when there are fewer).  No NaN is buffered.
+__device__ __forceinline__ float rec_compact(const float *ss, const int32_t *si, int cnt, float *ds, int32_t *di, int kk, int lane) {
+    float kth = -INFINITY;
+    for (int e = lane; e < cnt; e += kGroup) {
+        const float s = ss[e];
+        int rank = 0;
+        for (int j = 0; j < cnt; j++) {
+            const float o = ss[j];
+            rank += (o > s || (o == s && j < e)) ? 1 : 0;
+        }
+        if (rank < kk) {
+            ds[rank] = s;
+            di[rank] = si[e];
+            if (rank == kk - 1) kth = s;
+        }
+    }
+    for (int m = 8; m >= 1; m >>= 1) kth = fmaxf(kth, __shfl_xor(kth, m, kGroup));
+    return kth;
+}
+
+// recommend_mfma.hip: the matrix-core producer of out_s / out_i / out_cnt / nan_flag (route 1).  It serves nFactors = 16, 32, ... 256;
+// a workgroup owns kRecMfmaQueries queries and one slice, so the grid is ceil(nq / kRecMfmaQueries) x slices.
+constexpr int kRecMfmaQueries = 128;
+constexpr bool rec_mfma_serves(int d) { return d % 16 == 0 && d >= 16 && d <= 256; }
+int32_t rec_mfma_launch(const RecArgs &A, hipStream_t stream);
+
+}  // namespace gorse

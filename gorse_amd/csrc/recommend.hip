@@ -13,12 +13,14 @@
 //   survive, as a sorted sequence of values; the finish kernel merges the slices' lists and keeps the kk best of all.
 //   Tie rule: a query whose kk best scores hold an equal pair (-0 == +0), or that met a NaN candidate score, is left to the literal
 //   path; for every other query the k best items are uniquely ordered by score and that order IS the heap's.
+// Matrix route (gorse_mf_set_recommend_route(h, 1), recommend_mfma.hip): rec_mfma_kernel produces what rec_fast_kernel produces, with the
+// scores formed on the matrix cores in the same bits, for nFactors = 16, 32, ... 256; everything behind it is shared.
 // Literal path: the query's candidate list is materialised on the device in ascending order (rec_candidates_kernel) and handed to
 // mf_rank_device, in chunks of bounded size; its scores come from mf_score_device.
 #include <algorithm>
 #include <cmath>
 
-#include "mf_internal.hpp"
+#include "rec_internal.hpp"
 
 using namespace gorse;
 
@@ -34,50 +36,6 @@ constexpr size_t kRecScratchBytes = (size_t)256 << 20;  // the fast path's buffe
 int g_rec_slices = 0;              // test hook: > 0 forces the slice count
 int g_rec_buffer = 0;              // test hook: > 0 forces the buffer size (raised to k + 2 where smaller)
 int64_t g_rec_literal_chunk = 0;   // test hook: > 0 replaces kRecLiteralChunk
-
-struct RecArgs {
-    const float *P, *Q;
-    const int32_t *users;  // null: query t is user t
-    const int64_t *uptr;
-    const int32_t *uidx_sorted;
-    const int64_t *sptr;  // null: no seen rows
-    const int32_t *seen;  // every row sorted ascending
-    const uint8_t *item_ok;
-    int64_t q0, nq;  // the launch's queries are [q0, q0 + nq)
-    int32_t I, d, k, kk, cap, slices, slice_len, tile_items;
-    float *buf_s;     // nq * slices * 2 * cap: two halves per (query, slice), a compaction moves from one to the other
-    int32_t *buf_i;
-    float *out_s;     // nq * slices * kk: the slice's kk best, sorted by score descending
-    int32_t *out_i;
-    int32_t *out_cnt;   // nq * slices
-    int32_t *nan_flag;  // nq
-};
-
-__device__ __forceinline__ bool rec_candidate(const uint8_t *__restrict__ item_ok, const int32_t *trow, int64_t tn, const int32_t *srow,
-                                              int64_t sn, int32_t item) {
-    return item_ok[item] != 0 && !row_contains(trow, tn, item) && !(sn > 0 && row_contains(srow, sn, item));
-}
-
-// One 16-lane group: the kk best of cnt buffered entries to dst, sorted by score descending (equal scores in buffer order).  Every
-// entry is ranked by counting the entries ahead of it.  Returns the kk-th best score (-inf when there are fewer).  No NaN is buffered.
-__device__ __forceinline__ float rec_compact(const float *ss, const int32_t *si, int cnt, float *ds, int32_t *di, int kk, int lane) {
-    float kth = -INFINITY;
-    for (int e = lane; e < cnt; e += kGroup) {
-        const float s = ss[e];
-        int rank = 0;
-        for (int j = 0; j < cnt; j++) {
-            const float o = ss[j];
-            rank += (o > s || (o == s && j < e)) ? 1 : 0;
-        }
-        if (rank < kk) {
-            ds[rank] = s;
-            di[rank] = si[e];
-            if (rank == kk - 1) kth = s;
-        }
-    }
-    for (int m = 8; m >= 1; m >>= 1) kth = fmaxf(kth, __shfl_xor(kth, m, kGroup));
-    return kth;
-}
 
 // NC > 0: d == 16 * NC, the user's row in registers; NC == 0: any d, the user's row in LDS behind the tile
 template <int NC>
@@ -321,6 +279,20 @@ extern "C" int32_t gorse_mf_recommend_stats(gorse_mf *h, int64_t *n_fast, int64_
     return GORSE_OK;
 }
 
+extern "C" int32_t gorse_mf_set_recommend_route(gorse_mf *h, int32_t route) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (route != 0 && route != 1) return fail(GORSE_ERR_INVALID, "recommend route %d is neither 0 (vector) nor 1 (matrix)", route);
+    h->rec_route = route;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_mf_get_recommend_route(gorse_mf *h, int32_t *requested, int32_t *last_used) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (requested) *requested = h->rec_route;
+    if (last_used) *last_used = h->rec_route_used;
+    return GORSE_OK;
+}
+
 namespace gorse {
 
 int32_t mf_recommend_check(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k) {
@@ -341,6 +313,7 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
     GORSE_TRY(mf_sync_streams(h));  // behind every epoch still enqueued on the handle
     h->rec_fast = h->rec_literal = 0;
     h->rec_ms = 0.0;
+    h->rec_route_used = 0;
     if (n_users == 0) return GORSE_OK;
     if (dev && k > kRecMaxK) return fail(GORSE_ERR_INVALID, "device rows are served for k <= %d", kRecMaxK);
 
@@ -398,8 +371,11 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
         A.cap = std::max(32, 2 * A.kk);
         if (g_rec_buffer > 0) A.cap = std::max(A.kk + 1, g_rec_buffer);
         // too few query blocks to fill the chip: the items in slices across workgroups
+        const bool matrix = h->rec_route == 1 && rec_mfma_serves(d);
+        const int block_queries = matrix ? kRecMfmaQueries : kGroupsPerBlock;  // queries of a workgroup
+        h->rec_route_used = matrix ? 1 : 0;
         int slices = 1;
-        const int64_t blocks = ceil_div(n_users, kGroupsPerBlock);
+        const int64_t blocks = ceil_div(n_users, block_queries);
         while (slices < kRecMaxSlices && blocks * slices < 512 && I / (slices * 2) >= 256) slices *= 2;
         if (g_rec_slices > 0) slices = g_rec_slices;
         slices = (int)std::min<int64_t>(slices, I);
@@ -434,9 +410,13 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
             A.nq = nq;
             GORSE_TRY(timer.begin(h->stream));
             GORSE_HIP_CHECK(hipMemsetAsync(A.nan_flag, 0, (size_t)nq * 4, h->stream));
-            const dim3 grid((unsigned)ceil_div(nq, kGroupsPerBlock), (unsigned)slices);
-            with_factor_chunks(d, [&](auto nc) { rec_fast_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds_fast, h->stream>>>(A); });
-            GORSE_HIP_CHECK(hipGetLastError());
+            if (matrix) {
+                GORSE_TRY(rec_mfma_launch(A, h->stream));
+            } else {
+                const dim3 grid((unsigned)ceil_div(nq, kGroupsPerBlock), (unsigned)slices);
+                with_factor_chunks(d, [&](auto nc) { rec_fast_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds_fast, h->stream>>>(A); });
+                GORSE_HIP_CHECK(hipGetLastError());
+            }
             rec_finish_kernel<<<dim3((unsigned)nq), dim3(kBlock), lds_fin, h->stream>>>(A, d_ri, d_rs, d_rc, d_lit);
             GORSE_HIP_CHECK(hipGetLastError());
             GORSE_TRY(timer.end(h->stream));

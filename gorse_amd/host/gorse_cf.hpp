@@ -701,6 +701,7 @@ class MatrixFactorization {
     // recreated from bare factors) and the items of seen[t].  So that no caller gets a user's training items back by accident, a
     // model whose handle holds no rows REQUIRES the seen lists (std::logic_error otherwise; pass empty lists to say "nothing seen").
     // itemOk = one flag per item index, empty = IsItemPredictable.  Unknown or unpredictable users get an empty list.
+    // route = gorse_mf_set_recommend_route's value for this call (0: the vector kernel, 1: the matrix kernel; the same lists either way).
     struct Recommended {
         std::string Id;
         float Score = 0;
@@ -708,12 +709,12 @@ class MatrixFactorization {
     bool HandleHoldsTrainingRows() const { return h_ != nullptr && handle_train_ != nullptr; }
     std::vector<std::vector<Recommended>> RecommendUnseen(const std::vector<std::string> &userIds, int n,
                                                           const std::vector<std::vector<std::string>> &seen = {},
-                                                          const std::vector<bool> &itemOk = {});
+                                                          const std::vector<bool> &itemOk = {}, int route = 0);
     // the same on indices: users[t] < 0 or unpredictable = empty list; seen rows as CSR over item indices (seenPtr empty = none given);
     // items / scores are users.size() x n padded with -1 / 0
     void RecommendUnseenIndexed(const std::vector<int32_t> &users, int n, const std::vector<int64_t> &seenPtr,
                                 const std::vector<int32_t> &seenItems, const std::vector<bool> &itemOk, std::vector<int32_t> &items,
-                                std::vector<float> &scores, std::vector<int32_t> &count);
+                                std::vector<float> &scores, std::vector<int32_t> &count, int route = 0);
 
     model::Params Params;
     std::shared_ptr<dataset::FreqDict> UserIndex, ItemIndex;

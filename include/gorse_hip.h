@@ -136,6 +136,14 @@ int32_t gorse_mf_recommend(gorse_mf *h, int64_t n_users, const int32_t *users /*
 /* the handle's last gorse_mf_recommend: queries answered by the threshold kernel (queries with u < 0, which need no answer, are
  * counted here) / literally, and the device time of its launches (hipEvents around them, copies excluded) */
 int32_t gorse_mf_recommend_stats(gorse_mf *h, int64_t *n_fast, int64_t *n_literal, double *device_ms);
+/* Which kernel scores the threshold queries of gorse_mf_recommend (and of gorse_cand_add_mf, which searches through the same
+ * handle).  route 0 (the default): the vector-ALU kernel.  route 1: the matrix-core kernel, which forms the same score bits; it
+ * serves nFactors = 16, 32, ... 256 and k <= 256, and a call it does not serve falls back to route 0.  Results, the tie rule and
+ * gorse_mf_recommend_stats' split are the same on either route.  Any other value: GORSE_ERR_INVALID, the setting is kept.
+ * get: the route asked for and the route that served the threshold queries of the handle's last call (0 when it had none);
+ * either pointer may be NULL. */
+int32_t gorse_mf_set_recommend_route(gorse_mf *h, int32_t route);
+int32_t gorse_mf_get_recommend_route(gorse_mf *h, int32_t *requested, int32_t *last_used);
 
 /* dataset.SampleUserNegatives on the device (dataset/dataset.go:242-253 through RandomGenerator.SampleInt32,
  * common/util/random.go:108-132): for EVERY user num_candidates distinct items outside (the user's feedback in the test split

@@ -23,6 +23,15 @@ type Recommended struct {
 	Score float32
 }
 
+// SetRecommendRoute picks the kernel that scores RecommendUnseen's threshold queries: 0 = vector ALU (the default), 1 = matrix cores
+// (the same lists; widths and n it does not serve fall back to 0).
+func (m *hipModel) SetRecommendRoute(route int) error {
+	if rc := C.gorse_mf_set_recommend_route(m.h, C.int32_t(route)); rc != C.GORSE_OK {
+		return hipError("gorse_mf_set_recommend_route", rc)
+	}
+	return nil
+}
+
 // RecommendUnseen ranks for users[t] (an index of the model's user dictionary; negative = not predictable, empty list) the items
 // that itemOk admits (nil: the items with training feedback = IsItemPredictable) and that are neither in the user's training row
 // held by the handle nor in seen[t] (nil: no such rows).  numItems = the model's item count: the library reads that many itemOk
