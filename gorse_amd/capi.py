@@ -56,6 +56,9 @@ SIGNATURES = {
     "gorse_mf_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
     "gorse_mf_set_recommend_route": (C.c_int32, [_vp, C.c_int32]),
     "gorse_mf_get_recommend_route": (C.c_int32, [_vp, _i32p, _i32p]),
+    "gorse_mf_set_recommend_schedule": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_mf_get_recommend_schedule": (C.c_int32, [_vp, _i32p, _i32p]),
+    "gorse_mf_recommend_sweep_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p]),
     "gorse_mf_sample_user_negatives": (C.c_int32, [_vp, _i64p, _i32p, C.c_int32, C.c_uint64, _i32p, _i32p]),
     "gorse_mf_resident_candidates": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_mf_resident_generation": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
@@ -198,6 +201,8 @@ SIGNATURES = {
     "gorse_hip_test_bpr_fold_tier_stats": (C.c_int32, [_vp, _vp]),
     "gorse_hip_test_set_bpr_folder_timeout": (None, [C.c_int64]),
     "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
+    "gorse_hip_test_set_recommend_sweep": (None, [C.c_int32]),
+    "gorse_hip_test_recommend_sweep_plan": (None, [C.c_int64, C.c_int32, C.c_int64, _i32p, _i32p, _i32p]),
     "gorse_hip_test_set_fm_rank": (None, [C.c_int64, C.c_int32]),
     "gorse_hip_test_fm_rank_sort": (C.c_int32, [_vp, C.c_int64, _i64p, _f32p, _i32p]),
     "gorse_hip_test_set_fm_evaluate": (None, [C.c_int64, C.c_int32]),
@@ -377,6 +382,23 @@ class MF:
         req, used = C.c_int32(0), C.c_int32(0)
         check(lib().gorse_mf_get_recommend_route(self.h, C.byref(req), C.byref(used)))
         return req.value, used.value
+
+    def set_recommend_schedule(self, schedule):
+        """how recommend()'s threshold queries find their threshold: 0 = while walking the items (default), 1 = from a pilot sample,
+        then one matrix-core sweep (falls back where unserved)"""
+        check(lib().gorse_mf_set_recommend_schedule(self.h, int(schedule)))
+
+    def recommend_schedule(self):
+        """(the schedule asked for, the schedule that answered the last recommend()'s threshold queries)"""
+        req, used = C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_mf_get_recommend_schedule(self.h, C.byref(req), C.byref(used)))
+        return req.value, used.value
+
+    def recommend_sweep_stats(self):
+        """the last recommend(): (queries the sweep answered, queries it handed back to schedule 0, survivor entries written)"""
+        ns, nb, sv = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gorse_mf_recommend_sweep_stats(self.h, C.byref(ns), C.byref(nb), C.byref(sv)))
+        return ns.value, nb.value, sv.value
 
     def sample_user_negatives(self, test_indptr, test_indices, num_candidates, seed=0, fetch=True):
         """dataset.SampleUserNegatives on the device: (neg U x n padded with -1, len U); the candidate lists of the users with

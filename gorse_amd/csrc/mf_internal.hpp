@@ -132,6 +132,8 @@ struct gorse_mf {
     int64_t rec_fast = 0, rec_literal = 0;
     double rec_ms = 0.0;
     int32_t rec_route = 0, rec_route_used = 0;  // gorse_mf_set_recommend_route: 0 = vector kernel, 1 = matrix kernel; what the last call ran
+    int32_t rec_schedule = 0, rec_schedule_used = 0;  // gorse_mf_set_recommend_schedule: 0 = running threshold, 1 = pilot threshold
+    int64_t rec_sweep_n = 0, rec_sweep_back = 0, rec_sweep_surv = 0;  // the last call's gorse_mf_recommend_sweep_stats
     gorse::KernelProfile prof{GORSE_PROF_NCLASSES};
 
     int32_t use() const {

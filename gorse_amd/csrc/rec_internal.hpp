@@ -1,6 +1,6 @@
 // rec_internal.hpp -- what the units of gorse_mf_recommend share: the launch's arguments, the candidate test and the survivor
 // buffer's compaction (recommend.hip: the vector kernel, the merge, the literal path, the planner and its constants;
-// recommend_mfma.hip: the matrix-core kernel).
+// recommend_mfma.hip: the matrix-core kernel; recommend_sweep.hip: the pilot-threshold schedule).
 #pragma once
 #include <cmath>
 
@@ -24,7 +24,26 @@ struct RecArgs {
     int32_t *out_i;
     int32_t *out_cnt;   // nq * slices
     int32_t *nan_flag;  // nq
+    // the pilot schedule's second launch (rec_fast_kernel and rec_finish_kernel only): launch query tq is query qmap[tq] of the
+    // call, and its result row is qmap[tq] - q0; null: query q0 + tq, row tq
+    const int64_t *qmap;
 };
+
+// recommend_sweep.hip: the pilot-threshold schedule (gorse_mf_set_recommend_schedule(h, 1)).  One round over the queries [q0, q0 + nq) of
+// R: the pilot's thresholds, the sweep's survivor lists, and rec_finish_kernel's result arrays for every query it answers; hb[t] = 1
+// marks a query handed back to schedule 0 (its result row is not written), cnt[t] = survivors the sweep counted for it.
+struct RecSweepArgs {
+    RecArgs R;  // P .. item_ok, q0, nq, I, d, k, kk; the rest is schedule 0's
+    int32_t stride, n_sample, samp_ld, cap, pilot_slices, pilot_slice_len, sweep_slices, sweep_slice_len;
+    float *samp;       // ceil(nq / 128) * 128 * samp_ld: the sampled scores, a row per query of every launched block
+    float *tau;        // nq
+    int32_t *cnt;      // nq
+    int32_t *hb;       // nq
+    int32_t *surv_i;   // nq * cap
+    float *surv_s;
+    size_t select_lds, finish_lds;
+};
+int32_t rec_sweep_launch(const RecSweepArgs &S, int32_t *res_items, float *res_scores, int32_t *res_cnt, int32_t *lit, hipStream_t stream);
 
 __device__ __forceinline__ bool rec_candidate(const uint8_t *__restrict__ item_ok, const int32_t *trow, int64_t tn, const int32_t *srow,
                                               int64_t sn, int32_t item) {

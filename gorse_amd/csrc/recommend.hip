@@ -15,12 +15,16 @@
 //   path; for every other query the k best items are uniquely ordered by score and that order IS the heap's.
 // Matrix route (gorse_mf_set_recommend_route(h, 1), recommend_mfma.hip): rec_mfma_kernel produces what rec_fast_kernel produces, with the
 // scores formed on the matrix cores in the same bits, for nFactors = 16, 32, ... 256; everything behind it is shared.
+// Pilot schedule (gorse_mf_set_recommend_schedule(h, 1), recommend_sweep.hip): the thresholds come from a strided sample, one matrix
+// sweep keeps what reaches them and rec_sweep_finish_kernel writes what rec_finish_kernel writes; the queries it hands back are
+// answered here, by rec_fast_kernel over RecArgs.qmap.
 // Literal path: the query's candidate list is materialised on the device in ascending order (rec_candidates_kernel) and handed to
 // mf_rank_device, in chunks of bounded size; its scores come from mf_score_device.
 #include <algorithm>
 #include <cmath>
 
 #include "rec_internal.hpp"
+#include "rec_sweep_plan.hpp"
 
 using namespace gorse;
 
@@ -36,6 +40,7 @@ constexpr size_t kRecScratchBytes = (size_t)256 << 20;  // the fast path's buffe
 int g_rec_slices = 0;              // test hook: > 0 forces the slice count
 int g_rec_buffer = 0;              // test hook: > 0 forces the buffer size (raised to k + 2 where smaller)
 int64_t g_rec_literal_chunk = 0;   // test hook: > 0 replaces kRecLiteralChunk
+int g_rec_sweep_stride = 0;        // test hook: > 0 replaces the pilot schedule's base sample stride
 
 // NC > 0: d == 16 * NC, the user's row in registers; NC == 0: any d, the user's row in LDS behind the tile
 template <int NC>
@@ -49,8 +54,9 @@ __global__ __launch_bounds__(kBlock) void rec_fast_kernel(const RecArgs A) {
     const int sl = blockIdx.y;
     const int i0 = sl * A.slice_len;
     const int i1 = min(A.I, i0 + A.slice_len);
+    const int64_t gq = tq < A.nq ? (A.qmap ? A.qmap[tq] : A.q0 + tq) : 0;  // the query of the call
     int u = -1;
-    if (tq < A.nq) u = A.users ? A.users[A.q0 + tq] : (int)(A.q0 + tq);
+    if (tq < A.nq) u = A.users ? A.users[gq] : (int)gq;
     const bool active = u >= 0;
     const VecShape vs(d);
     float a[NC > 0 ? NC : 1];
@@ -69,8 +75,8 @@ __global__ __launch_bounds__(kBlock) void rec_fast_kernel(const RecArgs A) {
         trow = A.uidx_sorted + A.uptr[u];
         tn = A.uptr[u + 1] - A.uptr[u];
         if (A.sptr) {
-            srow = A.seen + A.sptr[A.q0 + tq];
-            sn = A.sptr[A.q0 + tq + 1] - A.sptr[A.q0 + tq];
+            srow = A.seen + A.sptr[gq];
+            sn = A.sptr[gq + 1] - A.sptr[gq];
         }
     }
     const int cap = A.cap, kk = A.kk;
@@ -185,13 +191,14 @@ __global__ __launch_bounds__(kBlock) void rec_finish_kernel(const RecArgs A, int
     __syncthreads();
     const int tie = s_tie;
     const int cntk = tie ? 0 : min(n, k);
+    const int64_t row = A.qmap ? A.qmap[tq] - A.q0 : tq;
     if (tid == 0) {
-        lit[tq] = tie;
-        res_cnt[tq] = cntk;
+        lit[row] = tie;
+        res_cnt[row] = cntk;
     }
     for (int r = tid; r < k; r += kBlock) {
-        res_items[tq * k + r] = r < cntk ? ti[r] : -1;
-        res_scores[tq * k + r] = r < cntk ? ts[r] : 0.0f;
+        res_items[row * k + r] = r < cntk ? ti[r] : -1;
+        res_scores[row * k + r] = r < cntk ? ts[r] : 0.0f;
     }
 }
 
@@ -293,6 +300,38 @@ extern "C" int32_t gorse_mf_get_recommend_route(gorse_mf *h, int32_t *requested,
     return GORSE_OK;
 }
 
+extern "C" int32_t gorse_mf_set_recommend_schedule(gorse_mf *h, int32_t schedule) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (schedule != 0 && schedule != 1)
+        return fail(GORSE_ERR_INVALID, "recommend schedule %d is neither 0 (running threshold) nor 1 (pilot threshold)", schedule);
+    h->rec_schedule = schedule;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_mf_get_recommend_schedule(gorse_mf *h, int32_t *requested, int32_t *last_used) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (requested) *requested = h->rec_schedule;
+    if (last_used) *last_used = h->rec_schedule_used;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_mf_recommend_sweep_stats(gorse_mf *h, int64_t *n_sweep, int64_t *n_handed_back, int64_t *survivors) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (n_sweep) *n_sweep = h->rec_sweep_n;
+    if (n_handed_back) *n_handed_back = h->rec_sweep_back;
+    if (survivors) *survivors = h->rec_sweep_surv;
+    return GORSE_OK;
+}
+
+extern "C" void gorse_hip_test_set_recommend_sweep(int32_t stride) { g_rec_sweep_stride = stride > 0 ? stride : 0; }
+
+extern "C" void gorse_hip_test_recommend_sweep_plan(int64_t n_items, int32_t k, int64_t n_users, int32_t *stride, int32_t *n_sample, int32_t *cap) {
+    const recsweep::Plan p = recsweep::make_plan(n_items, k, n_users, g_rec_sweep_stride);
+    if (stride) *stride = p.stride;
+    if (n_sample) *n_sample = p.n_sample;
+    if (cap) *cap = p.cap;
+}
+
 namespace gorse {
 
 int32_t mf_recommend_check(gorse_mf *h, int64_t n_users, const int32_t *users, int32_t k) {
@@ -314,6 +353,8 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
     h->rec_fast = h->rec_literal = 0;
     h->rec_ms = 0.0;
     h->rec_route_used = 0;
+    h->rec_schedule_used = 0;
+    h->rec_sweep_n = h->rec_sweep_back = h->rec_sweep_surv = 0;
     if (n_users == 0) return GORSE_OK;
     if (dev && k > kRecMaxK) return fail(GORSE_ERR_INVALID, "device rows are served for k <= %d", kRecMaxK);
 
@@ -370,12 +411,15 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
         A.kk = k + 1;
         A.cap = std::max(32, 2 * A.kk);
         if (g_rec_buffer > 0) A.cap = std::max(A.kk + 1, g_rec_buffer);
-        // too few query blocks to fill the chip: the items in slices across workgroups
-        const bool matrix = h->rec_route == 1 && rec_mfma_serves(d);
+        // the pilot schedule scores on the matrix cores itself; the few queries it hands back go to the vector kernel
+        const bool sweep = h->rec_schedule == 1 && recsweep::serves(d, k);
+        const bool matrix = !sweep && h->rec_route == 1 && rec_mfma_serves(d);
+        h->rec_schedule_used = sweep ? 1 : 0;
         const int block_queries = matrix ? kRecMfmaQueries : kGroupsPerBlock;  // queries of a workgroup
         h->rec_route_used = matrix ? 1 : 0;
+        // too few query blocks to fill the chip: the items in slices across workgroups
         int slices = 1;
-        const int64_t blocks = ceil_div(n_users, block_queries);
+        const int64_t blocks = sweep ? 1 : ceil_div(n_users, block_queries);
         while (slices < kRecMaxSlices && blocks * slices < 512 && I / (slices * 2) >= 256) slices *= 2;
         if (g_rec_slices > 0) slices = g_rec_slices;
         slices = (int)std::min<int64_t>(slices, I);
@@ -387,12 +431,21 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
         const size_t per_query = (size_t)slices * ((size_t)2 * A.cap * 8 + (size_t)A.kk * 8 + 4) + (size_t)k * 8 + 16;
         int64_t chunk = (int64_t)(kRecScratchBytes / per_query) / kGroupsPerBlock * kGroupsPerBlock;
         chunk = std::min<int64_t>(std::max<int64_t>(chunk, kGroupsPerBlock), n_users);
+        recsweep::Plan plan;
+        if (sweep) {  // the round is the smaller of the two: schedule 0's buffers are sized for a round handed back whole
+            plan = recsweep::make_plan(I, k, n_users, g_rec_sweep_stride);
+            chunk = std::min(chunk, plan.chunk);
+        }
         Carver sc;
         const size_t o_bs = sc.take((size_t)chunk * slices * 2 * A.cap * 4), o_bi = sc.take((size_t)chunk * slices * 2 * A.cap * 4),
                      o_os = sc.take((size_t)chunk * slices * A.kk * 4), o_oi = sc.take((size_t)chunk * slices * A.kk * 4),
                      o_oc = sc.take((size_t)chunk * slices * 4), o_nan = sc.take((size_t)chunk * 4),
                      o_ri = sc.take((size_t)chunk * k * 4), o_rs = sc.take((size_t)chunk * k * 4), o_rc = sc.take((size_t)chunk * 4),
                      o_lit = sc.take((size_t)chunk * 4);
+        const size_t o_samp = sc.take(sweep ? (size_t)ceil_div(chunk, recsweep::kQueries) * recsweep::kQueries * plan.samp_ld * 4 : 0), o_tau = sc.take(sweep ? (size_t)chunk * 4 : 0),
+                     o_cnt = sc.take(sweep ? (size_t)chunk * 4 : 0), o_hb = sc.take(sweep ? (size_t)chunk * 4 : 0),
+                     o_si = sc.take(sweep ? (size_t)chunk * plan.cap * 4 : 0), o_ss = sc.take(sweep ? (size_t)chunk * plan.cap * 4 : 0),
+                     o_qmap = sc.take(sweep ? (size_t)chunk * 8 : 0);
         GORSE_TRY(h->rec_buf.ensure(sc.off));
         char *base = h->rec_buf.p;
         A.buf_s = (float *)(base + o_bs);
@@ -404,22 +457,61 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
         int32_t *d_ri = (int32_t *)(base + o_ri), *d_rc = (int32_t *)(base + o_rc), *d_lit = (int32_t *)(base + o_lit);
         float *d_rs = (float *)(base + o_rs);
         std::vector<int32_t> lit_host((size_t)chunk);
+        RecSweepArgs S{};
+        std::vector<int32_t> hb_host, cnt_host;
+        std::vector<int64_t> qmap_host;
+        if (sweep) {
+            S.stride = plan.stride, S.n_sample = plan.n_sample, S.samp_ld = plan.samp_ld, S.cap = plan.cap;
+            S.pilot_slices = plan.pilot_slices, S.pilot_slice_len = plan.pilot_slice_len;
+            S.sweep_slices = plan.sweep_slices, S.sweep_slice_len = plan.sweep_slice_len;
+            S.select_lds = plan.select_lds, S.finish_lds = plan.finish_lds;
+            S.samp = (float *)(base + o_samp), S.tau = (float *)(base + o_tau);
+            S.cnt = (int32_t *)(base + o_cnt), S.hb = (int32_t *)(base + o_hb);
+            S.surv_i = (int32_t *)(base + o_si), S.surv_s = (float *)(base + o_ss);
+            hb_host.resize((size_t)chunk), cnt_host.resize((size_t)chunk);
+        }
         for (int64_t q0 = 0; q0 < n_users; q0 += chunk) {
             const int64_t nq = std::min(chunk, n_users - q0);
             A.q0 = q0;
             A.nq = nq;
-            GORSE_TRY(timer.begin(h->stream));
-            GORSE_HIP_CHECK(hipMemsetAsync(A.nan_flag, 0, (size_t)nq * 4, h->stream));
-            if (matrix) {
-                GORSE_TRY(rec_mfma_launch(A, h->stream));
-            } else {
-                const dim3 grid((unsigned)ceil_div(nq, kGroupsPerBlock), (unsigned)slices);
-                with_factor_chunks(d, [&](auto nc) { rec_fast_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds_fast, h->stream>>>(A); });
-                GORSE_HIP_CHECK(hipGetLastError());
+            A.qmap = nullptr;
+            if (sweep) {  // ---- pilot, sweep, finish; what they hand back becomes the launch below, over qmap
+                S.R = A;
+                GORSE_TRY(timer.begin(h->stream));
+                GORSE_TRY(rec_sweep_launch(S, d_ri, d_rs, d_rc, d_lit, h->stream));
+                GORSE_TRY(timer.end(h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(hb_host.data(), S.hb, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+                GORSE_HIP_CHECK(hipMemcpyAsync(cnt_host.data(), S.cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+                GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+                qmap_host.clear();
+                for (int64_t t = 0; t < nq; t++) {
+                    if (hb_host[(size_t)t]) qmap_host.push_back(q0 + t);
+                    h->rec_sweep_surv += std::min(cnt_host[(size_t)t], plan.cap);
+                }
+                h->rec_sweep_back += (int64_t)qmap_host.size();
+                h->rec_sweep_n += nq - (int64_t)qmap_host.size();
+                if (!qmap_host.empty()) {
+                    int64_t *d_qmap = (int64_t *)(base + o_qmap);
+                    GORSE_HIP_CHECK(hipMemcpyAsync(d_qmap, qmap_host.data(), qmap_host.size() * 8, hipMemcpyHostToDevice, h->stream));
+                    A.qmap = d_qmap;
+                    A.nq = (int64_t)qmap_host.size();
+                }
             }
-            rec_finish_kernel<<<dim3((unsigned)nq), dim3(kBlock), lds_fin, h->stream>>>(A, d_ri, d_rs, d_rc, d_lit);
-            GORSE_HIP_CHECK(hipGetLastError());
-            GORSE_TRY(timer.end(h->stream));
+            if (!sweep || A.qmap) {  // schedule 0's launch: every query of the round, or the ones handed back
+                const int64_t nl = A.nq;
+                GORSE_TRY(timer.begin(h->stream));
+                GORSE_HIP_CHECK(hipMemsetAsync(A.nan_flag, 0, (size_t)nl * 4, h->stream));
+                if (matrix) {
+                    GORSE_TRY(rec_mfma_launch(A, h->stream));
+                } else {
+                    const dim3 grid((unsigned)ceil_div(nl, kGroupsPerBlock), (unsigned)slices);
+                    with_factor_chunks(d, [&](auto nc) { rec_fast_kernel<decltype(nc)::value><<<grid, dim3(kBlock), lds_fast, h->stream>>>(A); });
+                    GORSE_HIP_CHECK(hipGetLastError());
+                }
+                rec_finish_kernel<<<dim3((unsigned)nl), dim3(kBlock), lds_fin, h->stream>>>(A, d_ri, d_rs, d_rc, d_lit);
+                GORSE_HIP_CHECK(hipGetLastError());
+                GORSE_TRY(timer.end(h->stream));
+            }
             if (dev) {  // the chunk's rows stay on the device
                 GORSE_HIP_CHECK(hipMemcpyAsync(dev->items + q0 * k, d_ri, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, h->stream));
                 GORSE_HIP_CHECK(hipMemcpyAsync(dev->scores + q0 * k, d_rs, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, h->stream));

@@ -144,6 +144,19 @@ int32_t gorse_mf_recommend_stats(gorse_mf *h, int64_t *n_fast, int64_t *n_litera
  * either pointer may be NULL. */
 int32_t gorse_mf_set_recommend_route(gorse_mf *h, int32_t route);
 int32_t gorse_mf_get_recommend_route(gorse_mf *h, int32_t *requested, int32_t *last_used);
+/* How the threshold queries of gorse_mf_recommend (and of gorse_cand_add_mf) find their threshold.  schedule 0 (the default): the
+ * running threshold, learned while the items are walked, scored by the kernel gorse_mf_set_recommend_route names.  schedule 1: the
+ * pilot threshold -- every query's threshold is taken from a strided sample of the catalogue first (the (k + 1)-th best sampled
+ * candidate: safe by construction), then ONE matrix-core sweep over all items keeps what reaches it and only those survivors are
+ * tested for exclusion and ranked.  It serves nFactors = 16, 32, ... 256 and k <= 256; a call outside that takes schedule 0 as a
+ * whole.  Inside a served call a query the sweep cannot finish (a sample with fewer than k + 1 candidates or with a NaN, a survivor
+ * list beyond its capacity) is handed back to schedule 0's vector kernel.  Results, the tie rule and gorse_mf_recommend_stats'
+ * split are the same on either schedule.  Any other value: GORSE_ERR_INVALID, the setting is kept.
+ * get: the schedule asked for and the one that answered the threshold queries of the handle's last call (0 when it had none).
+ * sweep_stats, of the last call: queries the sweep answered, queries it handed back, survivor entries it wrote.  Pointers may be NULL. */
+int32_t gorse_mf_set_recommend_schedule(gorse_mf *h, int32_t schedule);
+int32_t gorse_mf_get_recommend_schedule(gorse_mf *h, int32_t *requested, int32_t *last_used);
+int32_t gorse_mf_recommend_sweep_stats(gorse_mf *h, int64_t *n_sweep, int64_t *n_handed_back, int64_t *survivors);
 
 /* dataset.SampleUserNegatives on the device (dataset/dataset.go:242-253 through RandomGenerator.SampleInt32,
  * common/util/random.go:108-132): for EVERY user num_candidates distinct items outside (the user's feedback in the test split

@@ -237,6 +237,10 @@ void gorse_hip_test_set_bpr_folder_timeout(int64_t ticks);
  * k + 2 where smaller, the smallest that can hold k + 1 entries and one more: a compaction per survivor; 0 = max(32, 2 (k + 1)));
  * literal_chunk > 0 = candidates materialised per launch of the literal path at most (0 = 2^22).  Results never depend on them. */
 void gorse_hip_test_set_recommend(int32_t slices, int32_t buffer, int64_t literal_chunk);
+/* gorse_mf_recommend under schedule 1 (csrc/rec_sweep_plan.hpp), calls AFTERWARDS: stride > 0 = the base sample stride (0 = the
+ * plan's); results never depend on it.  _plan: the stride, sample size and survivor capacity the plan gives a call of that shape. */
+void gorse_hip_test_set_recommend_sweep(int32_t stride);
+void gorse_hip_test_recommend_sweep_plan(int64_t n_items, int32_t k, int64_t n_users, int32_t *stride, int32_t *n_sample, int32_t *cap);
 /* gorse_fm_rank_users (csrc/fm_rank.hip), calls AFTERWARDS: round_rows > 0 = rows of a launch round at most (raised to the call's
  * batch_size where smaller: a slice is never split; 0 = by the scratch budget); sort_cap > 0 = entries of the longest list the
  * device sorts (at most 4096, the default; longer lists are sorted by the host).  Results never depend on them. */

@@ -32,6 +32,15 @@ func (m *hipModel) SetRecommendRoute(route int) error {
 	return nil
 }
 
+// SetRecommendSchedule picks how RecommendUnseen's threshold queries find their threshold: 0 = while the items are walked (the
+// default), 1 = from a pilot sample, followed by one matrix-core sweep (the same lists; widths and n it does not serve fall back to 0).
+func (m *hipModel) SetRecommendSchedule(schedule int) error {
+	if rc := C.gorse_mf_set_recommend_schedule(m.h, C.int32_t(schedule)); rc != C.GORSE_OK {
+		return hipError("gorse_mf_set_recommend_schedule", rc)
+	}
+	return nil
+}
+
 // RecommendUnseen ranks for users[t] (an index of the model's user dictionary; negative = not predictable, empty list) the items
 // that itemOk admits (nil: the items with training feedback = IsItemPredictable) and that are neither in the user's training row
 // held by the handle nor in seen[t] (nil: no such rows).  numItems = the model's item count: the library reads that many itemOk

@@ -17,7 +17,11 @@ for `new`; the over-fetch route there needs k = 100 + the longest row of a batch
 --routes 0,1 measures instead the kernels of gorse_mf_set_recommend_route against each other (0 = vector ALU, 1 = matrix cores): `new`
 alone, on ONE handle and the same inputs, the routes alternating inside a repetition after a warm-up of each; their rows must be
 equal in every bit or the run fails.  Route 0 is the yardstick.  Default output then: profiles/recommend_matrix_bench.json.
-usage: bench_recommend.py [--workloads ml1m,c3] [--reps 5] [--compiled [--compiled-users 1024]] [--routes 0,1] [--out profiles/recommend_bench.json]"""
+--schedules 0,1 does the same for gorse_mf_set_recommend_schedule (0 = running threshold, 1 = pilot threshold and one matrix sweep),
+route 0 throughout; schedule 0 is the yardstick; --stride N sets the pilot's base sample stride for the run (0 = the plan's).  The
+sweep's survivors per query and handed-back queries are reported.  Default output then: profiles/recommend_sweep_bench.json.
+usage: bench_recommend.py [--workloads ml1m,c3] [--reps 5] [--compiled [--compiled-users 1024]] [--routes 0,1 | --schedules 0,1 [--stride N]]
+                          [--out profiles/recommend_bench.json]"""
 import argparse
 import json
 import os
@@ -141,29 +145,34 @@ def run(name, data, d, n_new, n_old, reps, n_compiled):
     return res
 
 
-def run_routes(name, data, d, n_users, reps, route_list):
+def run_routes(name, data, d, n_users, reps, route_list, what="route"):
+    """what = "route" or "schedule": the setter whose values route_list holds"""
     P, Q = synth.init_factors(data.U, data.I, d, 0.0, 0.1, 1)
     mf = capi.MF(data.U, data.I, d, np.asarray(data.uptr), np.asarray(data.uidx))
     mf.set_factors(P, Q)
     ok = np.ones(data.I, np.uint8)
-    wall, dev, rows, split, used = ({r: [] for r in route_list} for _ in range(5))
+    wall, dev, rows, split, used, sweep = ({r: [] for r in route_list} for _ in range(6))
     for rep in range(reps + 1):  # repetition 0 warms up
         for r in route_list:
-            mf.set_recommend_route(r)
+            getattr(mf, "set_recommend_" + what)(r)
             t, rows[r] = timed(lambda: mf.recommend(n_users, K, ok))
-            print("%s rep %d route %d %.4f s" % (name, rep, r, t), file=sys.stderr, flush=True)
+            print("%s rep %d %s %d %.4f s" % (name, rep, what, r, t), file=sys.stderr, flush=True)
             if rep:
                 wall[r].append(t)
                 nf, nl, ms = mf.recommend_stats()
                 dev[r].append(ms * 1e-3)
-                split[r], used[r] = (nf, nl), mf.recommend_route()[1]
+                split[r], used[r], sweep[r] = (nf, nl), getattr(mf, "recommend_" + what)()[1], mf.recommend_sweep_stats()
     first = rows[route_list[0]]
     for r in route_list[1:]:
-        assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(first, rows[r])), "route %d rows differ" % r
+        assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(first, rows[r])), "%s %d rows differ" % (what, r)
         assert split[r] == split[route_list[0]]
     res = {"workload": name, "items": int(data.I), "nFactors": d, "k": K, "users": n_users, "rows_equal": True,
            "routes": {str(r): {"last_used": used[r], "wall": stats(wall[r]), "device": stats(dev[r]), "n_fast": split[r][0], "n_literal": split[r][1],
                                "pairs_per_s": n_users * float(data.I) / float(np.median(wall[r]))} for r in route_list}}
+    if what == "schedule":
+        res["compared"] = "schedules"
+        for r in route_list:
+            res["routes"][str(r)].update(n_handed_back=sweep[r][1], survivors_per_query=sweep[r][2] / max(1, sweep[r][0]))
     if len(route_list) > 1:
         res["wall_ratio_first_over_last"] = float(np.median(wall[route_list[0]]) / np.median(wall[route_list[-1]]))
         res["device_ratio_first_over_last"] = float(np.median(dev[route_list[0]]) / np.median(dev[route_list[-1]]))
@@ -178,20 +187,25 @@ def main():
     ap.add_argument("--compiled", action="store_true", help="ml1m: also the two compiled worker calls through hip://")
     ap.add_argument("--compiled-users", type=int, default=1024, help="ml1m: users the two compiled calls are run on")
     ap.add_argument("--routes", default="", help="e.g. 0,1: compare gorse_mf_set_recommend_route's kernels instead of the over-fetch route")
+    ap.add_argument("--schedules", default="", help="e.g. 0,1: compare gorse_mf_set_recommend_schedule's schedules the same way")
+    ap.add_argument("--stride", type=int, default=0, help="--schedules: the pilot's base sample stride (0 = the plan's)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    route_list = [int(r) for r in a.routes.split(",") if r]
-    a.out = a.out or os.path.join(ROOT, "profiles", "recommend_matrix_bench.json" if route_list else "recommend_bench.json")
+    route_list = [int(r) for r in (a.schedules or a.routes).split(",") if r]
+    what = "schedule" if a.schedules else "route"
+    capi.lib().gorse_hip_test_set_recommend_sweep(a.stride)
+    a.out = a.out or os.path.join(ROOT, "profiles", "recommend_sweep_bench.json" if a.schedules else
+                                  "recommend_matrix_bench.json" if route_list else "recommend_bench.json")
     res = []
     if os.path.exists(a.out):  # a workload run on its own replaces its own entry
-        res = [r for r in json.load(open(a.out)) if "routes" in r]
+        res = [r for r in json.load(open(a.out)) if "routes" in r or "what" in r]  # ("what": a kernel-trace entry written by hand)
     for w in a.workloads.split(","):
         if w == "ml1m":
             data = synth.s_ml1m()
-            r = run_routes("S-ml1m", data, 64, data.U, a.reps, route_list) if route_list else run("S-ml1m", data, 64, data.U, data.U, a.reps, min(a.compiled_users, data.U) if a.compiled else 0)
+            r = run_routes("S-ml1m", data, 64, data.U, a.reps, route_list, what) if route_list else run("S-ml1m", data, 64, data.U, data.U, a.reps, min(a.compiled_users, data.U) if a.compiled else 0)
         else:
             data = synth.s_big_shard(0, 8)  # one rank's 125,000 users of the 1M x 200K x 100M set: the same rows, items and widths
-            r = run_routes("C3", data, 128, 65536, a.reps, route_list) if route_list else run("C3", data, 128, 65536, a.old_users, a.reps, 0)
+            r = run_routes("C3", data, 128, 65536, a.reps, route_list, what) if route_list else run("C3", data, 128, 65536, a.old_users, a.reps, 0)
         res = [x for x in res if x["workload"] != r["workload"]] + [r]
         print(json.dumps(r), flush=True)
         with open(a.out, "w") as f:
