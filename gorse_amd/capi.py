@@ -59,6 +59,9 @@ SIGNATURES = {
     "gorse_mf_set_recommend_schedule": (C.c_int32, [_vp, C.c_int32]),
     "gorse_mf_get_recommend_schedule": (C.c_int32, [_vp, _i32p, _i32p]),
     "gorse_mf_recommend_sweep_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p]),
+    "gorse_mf_set_recommend_literal": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_mf_get_recommend_literal": (C.c_int32, [_vp, _i32p, _i32p]),
+    "gorse_mf_recommend_literal_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p]),
     "gorse_mf_sample_user_negatives": (C.c_int32, [_vp, _i64p, _i32p, C.c_int32, C.c_uint64, _i32p, _i32p]),
     "gorse_mf_resident_candidates": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_mf_resident_generation": (C.c_int32, [_vp, C.POINTER(C.c_uint64)]),
@@ -202,6 +205,7 @@ SIGNATURES = {
     "gorse_hip_test_set_bpr_folder_timeout": (None, [C.c_int64]),
     "gorse_hip_test_set_recommend": (None, [C.c_int32, C.c_int32, C.c_int64]),
     "gorse_hip_test_set_recommend_sweep": (None, [C.c_int32]),
+    "gorse_hip_test_set_recommend_literal": (None, [C.c_int32]),
     "gorse_hip_test_recommend_sweep_plan": (None, [C.c_int64, C.c_int32, C.c_int64, _i32p, _i32p, _i32p]),
     "gorse_hip_test_set_fm_rank": (None, [C.c_int64, C.c_int32]),
     "gorse_hip_test_fm_rank_sort": (C.c_int32, [_vp, C.c_int64, _i64p, _f32p, _i32p]),
@@ -399,6 +403,23 @@ class MF:
         ns, nb, sv = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().gorse_mf_recommend_sweep_stats(self.h, C.byref(ns), C.byref(nb), C.byref(sv)))
         return ns.value, nb.value, sv.value
+
+    def set_recommend_literal(self, mode):
+        """how recommend()'s literal queries (ties, NaN scores, k > 256) are answered: 0 = candidate lists ranked by one thread per
+        query (default), 1 = one workgroup per query with the heap in LDS (the same rows; falls back where unserved)"""
+        check(lib().gorse_mf_set_recommend_literal(self.h, int(mode)))
+
+    def recommend_literal(self):
+        """(the literal mode asked for, the mode the last recommend() answered its literal queries in)"""
+        req, used = C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_mf_get_recommend_literal(self.h, C.byref(req), C.byref(used)))
+        return req.value, used.value
+
+    def recommend_literal_stats(self):
+        """the last recommend(): (literal queries mode 1 answered, candidates it pushed, candidates it fast-forwarded)"""
+        nq, npu, nsk = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gorse_mf_recommend_literal_stats(self.h, C.byref(nq), C.byref(npu), C.byref(nsk)))
+        return nq.value, npu.value, nsk.value
 
     def sample_user_negatives(self, test_indptr, test_indices, num_candidates, seed=0, fetch=True):
         """dataset.SampleUserNegatives on the device: (neg U x n padded with -1, len U); the candidate lists of the users with

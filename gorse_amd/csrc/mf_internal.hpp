@@ -134,6 +134,8 @@ struct gorse_mf {
     int32_t rec_route = 0, rec_route_used = 0;  // gorse_mf_set_recommend_route: 0 = vector kernel, 1 = matrix kernel; what the last call ran
     int32_t rec_schedule = 0, rec_schedule_used = 0;  // gorse_mf_set_recommend_schedule: 0 = running threshold, 1 = pilot threshold
     int64_t rec_sweep_n = 0, rec_sweep_back = 0, rec_sweep_surv = 0;  // the last call's gorse_mf_recommend_sweep_stats
+    int32_t rec_lit_mode = 0, rec_lit_used = 0;  // gorse_mf_set_recommend_literal: 0 = candidate lists and mf_rank_device, 1 = the LDS-heap kernel
+    int64_t rec_lit_queries = 0, rec_lit_pushed = 0, rec_lit_skipped = 0;  // the last call's gorse_mf_recommend_literal_stats
     gorse::KernelProfile prof{GORSE_PROF_NCLASSES};
 
     int32_t use() const {
@@ -189,7 +191,7 @@ int32_t mf_rank_device(gorse_mf *h, const UserLists &L, int32_t topk, int32_t *r
 // core: the search.  The seen rows are a CSR on the device with ASCENDING rows (d_sptr from 0; NULL: no seen rows).  dev == NULL: the
 // result rows go to the host arrays (each may be NULL), as gorse_mf_recommend returns them.  dev != NULL (k <= 256): the n_users * k
 // rows and the counts are left in the caller's device buffers instead -- the threshold path's chunks copied device to device, the
-// literal path's few rows uploaded at the end -- and the host arrays are not written.  Returns with the handle's stream idle.
+// literal path's few rows uploaded at the end (literal mode 1: written in place by its kernel) -- and the host arrays are not written.  Returns with the handle's stream idle.
 struct MfDeviceRows {
     int32_t *items = nullptr;
     float *scores = nullptr;

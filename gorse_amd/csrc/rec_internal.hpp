@@ -1,6 +1,6 @@
 // rec_internal.hpp -- what the units of gorse_mf_recommend share: the launch's arguments, the candidate test and the survivor
 // buffer's compaction (recommend.hip: the vector kernel, the merge, the literal path, the planner and its constants;
-// recommend_mfma.hip: the matrix-core kernel; recommend_sweep.hip: the pilot-threshold schedule).
+// recommend_mfma.hip: the matrix-core kernel; recommend_sweep.hip: the pilot-threshold schedule; recommend_literal.hip: literal mode 1).
 #pragma once
 #include <cmath>
 
@@ -76,5 +76,33 @@ __device__ __forceinline__ float rec_compact(const float *ss, const int32_t *si,
 constexpr int kRecMfmaQueries = 128;
 constexpr bool rec_mfma_serves(int d) { return d % 16 == 0 && d >= 16 && d <= 256; }
 int32_t rec_mfma_launch(const RecArgs &A, hipStream_t stream);
+
+// recommend_literal.hip: literal mode 1 (gorse_mf_set_recommend_literal(h, 1)).  One workgroup per literal query q of [0, nl): user
+// lit_user[q], seen row lit_query[q]; the result row -- items, the heap's weights as scores, the -1 / 0 padding, the count -- goes to
+// row lit_query[q] of items / scores / cnt (scatter != 0: the call's own device rows) or to row q (a compact nl * k buffer).
+// stats[0] / stats[1] gain the candidates that went through push / that were fast-forwarded; the caller clears them.
+struct RecLiteralArgs {
+    const float *P, *Q;
+    const int64_t *uptr;
+    const int32_t *uidx_sorted;
+    const int64_t *sptr;  // null: no seen rows
+    const int32_t *seen;
+    const uint8_t *item_ok;
+    const int32_t *lit_user;
+    const int64_t *lit_query;
+    int32_t I, d, k, scatter, no_skip;
+    int64_t q0;  // (the launcher's: first query of the launch)
+    int32_t *items;
+    float *scores;
+    int32_t *cnt;
+    unsigned long long *stats;
+};
+// The kernel's LDS: the heap's k + 1 entries, two tiles of buffered candidates and, where it is not held in registers, the user's
+// row.  It serves every (d, k) whose sum fits this budget -- k <= 4095 at any nFactors up to 4096 -- and the call takes mode 0
+// as a whole otherwise.
+constexpr size_t kRecLiteralLdsBytes = (size_t)64 << 10;
+size_t rec_literal_lds(int d, int k);
+bool rec_literal_serves(int d, int k);
+int32_t rec_literal_launch(const RecLiteralArgs &A, int64_t nl, hipStream_t stream);
 
 }  // namespace gorse

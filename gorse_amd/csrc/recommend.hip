@@ -20,6 +20,8 @@
 // answered here, by rec_fast_kernel over RecArgs.qmap.
 // Literal path: the query's candidate list is materialised on the device in ascending order (rec_candidates_kernel) and handed to
 // mf_rank_device, in chunks of bounded size; its scores come from mf_score_device.
+// Literal mode 1 (gorse_mf_set_recommend_literal(h, 1), recommend_literal.hip): one workgroup per literal query walks the catalogue,
+// scores the candidates and keeps TopKFilter's heap in LDS; the same rows, no list, no count, no chunk.
 #include <algorithm>
 #include <cmath>
 
@@ -355,6 +357,8 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
     h->rec_route_used = 0;
     h->rec_schedule_used = 0;
     h->rec_sweep_n = h->rec_sweep_back = h->rec_sweep_surv = 0;
+    h->rec_lit_used = 0;
+    h->rec_lit_queries = h->rec_lit_pushed = h->rec_lit_skipped = 0;
     if (n_users == 0) return GORSE_OK;
     if (dev && k > kRecMaxK) return fail(GORSE_ERR_INVALID, "device rows are served for k <= %d", kRecMaxK);
 
@@ -541,7 +545,55 @@ int32_t mf_recommend_core(gorse_mf *h, int64_t n_users, const int32_t *users, in
 
     // ---- literal path: candidate lists on the device -> mf_rank_device, in chunks; scores of the ranked items afterwards
     const int64_t nl = (int64_t)lit_query.size();
-    if (nl > 0) {
+    const bool lit1 = h->rec_lit_mode == 1 && rec_literal_serves(d, k);
+    h->rec_lit_used = lit1 ? 1 : 0;
+    if (nl > 0 && lit1) {
+        // ---- literal mode 1 (recommend_literal.hip): a workgroup per query, no candidate list, no count, no chunk; the rows come back
+        // in one buffer (the host scatters them) or are written where they belong on the device
+        std::vector<int32_t> lit_user((size_t)nl);
+        for (int64_t q = 0; q < nl; q++) lit_user[(size_t)q] = users ? users[lit_query[(size_t)q]] : (int32_t)lit_query[(size_t)q];
+        Carver lc;
+        const size_t o_lu = lc.take((size_t)nl * 4), o_lq = lc.take((size_t)nl * 8), o_st = lc.take(16),
+                     o_ri = lc.take(dev ? 0 : (size_t)nl * k * 4), o_rs = lc.take(dev ? 0 : (size_t)nl * k * 4),
+                     o_rc = lc.take(dev ? 0 : (size_t)nl * 4);
+        GORSE_TRY(h->rec_buf.ensure(lc.off));
+        char *base = h->rec_buf.p;
+        RecLiteralArgs L{};
+        L.P = h->P.p, L.Q = h->Q.p, L.uptr = h->uptr.p, L.uidx_sorted = h->uidx_sorted.p;
+        L.sptr = d_sptr, L.seen = d_seen, L.item_ok = d_ok;
+        L.lit_user = (int32_t *)(base + o_lu), L.lit_query = (int64_t *)(base + o_lq);
+        L.I = (int32_t)I, L.d = d, L.k = k, L.scatter = dev ? 1 : 0;
+        L.items = dev ? dev->items : (int32_t *)(base + o_ri);
+        L.scores = dev ? dev->scores : (float *)(base + o_rs);
+        L.cnt = dev ? dev->cnt : (int32_t *)(base + o_rc);
+        L.stats = (unsigned long long *)(base + o_st);
+        GORSE_HIP_CHECK(hipMemcpyAsync(base + o_lu, lit_user.data(), (size_t)nl * 4, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipMemcpyAsync(base + o_lq, lit_query.data(), (size_t)nl * 8, hipMemcpyHostToDevice, h->stream));
+        GORSE_HIP_CHECK(hipMemsetAsync(L.stats, 0, 16, h->stream));
+        GORSE_TRY(timer.begin(h->stream));
+        GORSE_TRY(rec_literal_launch(L, nl, h->stream));
+        GORSE_TRY(timer.end(h->stream));
+        unsigned long long stats[2] = {0, 0};
+        GORSE_HIP_CHECK(hipMemcpyAsync(stats, L.stats, 16, hipMemcpyDeviceToHost, h->stream));
+        std::vector<int32_t> li, lc_host;
+        std::vector<float> ls;
+        if (!dev) {
+            li.resize((size_t)nl * k), ls.resize((size_t)nl * k), lc_host.resize((size_t)nl);
+            GORSE_HIP_CHECK(hipMemcpyAsync(li.data(), L.items, (size_t)nl * k * 4, hipMemcpyDeviceToHost, h->stream));
+            GORSE_HIP_CHECK(hipMemcpyAsync(ls.data(), L.scores, (size_t)nl * k * 4, hipMemcpyDeviceToHost, h->stream));
+            GORSE_HIP_CHECK(hipMemcpyAsync(lc_host.data(), L.cnt, (size_t)nl * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
+        for (int64_t q = 0; q < nl && !dev; q++) {
+            const int64_t t = lit_query[(size_t)q];
+            std::copy(li.begin() + q * k, li.begin() + (q + 1) * k, items_out + t * k);
+            std::copy(ls.begin() + q * k, ls.begin() + (q + 1) * k, scores_out + t * k);
+            count_out[t] = lc_host[(size_t)q];
+        }
+        h->rec_lit_queries = nl;
+        h->rec_lit_pushed = (int64_t)stats[0];
+        h->rec_lit_skipped = (int64_t)stats[1];
+    } else if (nl > 0) {
         std::vector<int32_t> lit_user((size_t)nl), cnt_host((size_t)nl);
         for (int64_t q = 0; q < nl; q++) lit_user[(size_t)q] = users ? users[lit_query[(size_t)q]] : (int32_t)lit_query[(size_t)q];
         Carver lc;

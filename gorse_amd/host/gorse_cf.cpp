@@ -195,7 +195,7 @@ void MatrixFactorization::ensure_resident() {
 void MatrixFactorization::RecommendUnseenIndexed(const std::vector<int32_t> &users, int n, const std::vector<int64_t> &seenPtr,
                                                  const std::vector<int32_t> &seenItems, const std::vector<bool> &itemOk,
                                                  std::vector<int32_t> &items, std::vector<float> &scores, std::vector<int32_t> &count,
-                                                 int route, int schedule) {
+                                                 int route, int schedule, int literal) {
     if (n <= 0) throw std::invalid_argument("RecommendUnseen: n must be positive");
     if (!seenPtr.empty() && seenPtr.size() != users.size() + 1) throw std::invalid_argument("RecommendUnseen: one seen list per user");
     ensure_resident();
@@ -216,13 +216,14 @@ void MatrixFactorization::RecommendUnseenIndexed(const std::vector<int32_t> &use
     const int32_t dummy = 0;
     check(gorse_mf_set_recommend_route(h_, route));
     check(gorse_mf_set_recommend_schedule(h_, schedule));
+    check(gorse_mf_set_recommend_literal(h_, literal));
     check(gorse_mf_recommend(h_, (int64_t)us.size(), us.data(), n, ok.data(), seenPtr.empty() ? nullptr : seenPtr.data(),
                              seenItems.empty() ? &dummy : seenItems.data(), items.data(), scores.data(), count.data()));
 }
 
 std::vector<std::vector<MatrixFactorization::Recommended>> MatrixFactorization::RecommendUnseen(
     const std::vector<std::string> &userIds, int n, const std::vector<std::vector<std::string>> &seen, const std::vector<bool> &itemOk,
-    int route, int schedule) {
+    int route, int schedule, int literal) {
     if (!seen.empty() && seen.size() != userIds.size()) throw std::invalid_argument("RecommendUnseen: one seen list per user");
     if (Invalid()) throw std::runtime_error("model is not fitted");
     const int32_t I = ItemIndex->Count();
@@ -240,7 +241,7 @@ std::vector<std::vector<MatrixFactorization::Recommended>> MatrixFactorization::
     }
     std::vector<int32_t> items, count;
     std::vector<float> scores;
-    RecommendUnseenIndexed(users, n, ptr, flat, itemOk, items, scores, count, route, schedule);
+    RecommendUnseenIndexed(users, n, ptr, flat, itemOk, items, scores, count, route, schedule, literal);
     std::vector<std::vector<Recommended>> out(userIds.size());
     for (size_t t = 0; t < userIds.size(); t++)
         for (int32_t r = 0; r < count[t]; r++) {

@@ -703,6 +703,8 @@ class MatrixFactorization {
     // itemOk = one flag per item index, empty = IsItemPredictable.  Unknown or unpredictable users get an empty list.
     // route = gorse_mf_set_recommend_route's value for this call (0: the vector kernel, 1: the matrix kernel; the same lists either way).
     // schedule = gorse_mf_set_recommend_schedule's (0: the running threshold, 1: the pilot threshold and one matrix sweep; the same lists).
+    // literal = gorse_mf_set_recommend_literal's (0: candidate lists ranked by one thread per query, 1: one workgroup per query with
+    // the heap in LDS; the same lists).
     struct Recommended {
         std::string Id;
         float Score = 0;
@@ -710,12 +712,13 @@ class MatrixFactorization {
     bool HandleHoldsTrainingRows() const { return h_ != nullptr && handle_train_ != nullptr; }
     std::vector<std::vector<Recommended>> RecommendUnseen(const std::vector<std::string> &userIds, int n,
                                                           const std::vector<std::vector<std::string>> &seen = {},
-                                                          const std::vector<bool> &itemOk = {}, int route = 0, int schedule = 0);
+                                                          const std::vector<bool> &itemOk = {}, int route = 0, int schedule = 0,
+                                                          int literal = 0);
     // the same on indices: users[t] < 0 or unpredictable = empty list; seen rows as CSR over item indices (seenPtr empty = none given);
     // items / scores are users.size() x n padded with -1 / 0
     void RecommendUnseenIndexed(const std::vector<int32_t> &users, int n, const std::vector<int64_t> &seenPtr,
                                 const std::vector<int32_t> &seenItems, const std::vector<bool> &itemOk, std::vector<int32_t> &items,
-                                std::vector<float> &scores, std::vector<int32_t> &count, int route = 0, int schedule = 0);
+                                std::vector<float> &scores, std::vector<int32_t> &count, int route = 0, int schedule = 0, int literal = 0);
 
     model::Params Params;
     std::shared_ptr<dataset::FreqDict> UserIndex, ItemIndex;

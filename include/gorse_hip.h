@@ -157,6 +157,21 @@ int32_t gorse_mf_get_recommend_route(gorse_mf *h, int32_t *requested, int32_t *l
 int32_t gorse_mf_set_recommend_schedule(gorse_mf *h, int32_t schedule);
 int32_t gorse_mf_get_recommend_schedule(gorse_mf *h, int32_t *requested, int32_t *last_used);
 int32_t gorse_mf_recommend_sweep_stats(gorse_mf *h, int64_t *n_sweep, int64_t *n_handed_back, int64_t *survivors);
+/* How the literal queries of gorse_mf_recommend (and of gorse_cand_add_mf) are answered: the queries the tie rule above keeps from
+ * the threshold kernels, and every query when k > 256.  mode 0 (the default): the query's candidate list is materialised on the
+ * device, scored pair by pair and ranked by one thread per query.  mode 1: one workgroup per query walks the catalogue, scores only
+ * the candidates and feeds them in ascending order to the same heap, held in on-chip memory; a candidate that would be pushed and
+ * popped straight away without moving anything in the heap is not pushed at all.  The rows are the same bit for bit in either mode,
+ * and so is gorse_mf_recommend_stats' split.  Mode 1 serves every (nFactors, k) whose heap, buffers and user row fit 64 KiB of
+ * on-chip memory (k <= 4095 at any nFactors up to 4096); a call outside that takes mode 0 as a whole.  It is independent of route
+ * and schedule.  Any other value: GORSE_ERR_INVALID, the setting is kept.
+ * get: the mode asked for and the mode the handle's last call answered its literal queries in (what it would have answered them in
+ * when it had none).
+ * literal_stats, of the last call: literal queries mode 1 answered, candidates it pushed, candidates it skipped (pushed + skipped =
+ * the candidates of those queries); all 0 when mode 0 ran.  Pointers may be NULL. */
+int32_t gorse_mf_set_recommend_literal(gorse_mf *h, int32_t mode);
+int32_t gorse_mf_get_recommend_literal(gorse_mf *h, int32_t *requested, int32_t *last_used);
+int32_t gorse_mf_recommend_literal_stats(gorse_mf *h, int64_t *n_queries, int64_t *n_pushed, int64_t *n_skipped);
 
 /* dataset.SampleUserNegatives on the device (dataset/dataset.go:242-253 through RandomGenerator.SampleInt32,
  * common/util/random.go:108-132): for EVERY user num_candidates distinct items outside (the user's feedback in the test split

@@ -241,6 +241,9 @@ void gorse_hip_test_set_recommend(int32_t slices, int32_t buffer, int64_t litera
  * plan's); results never depend on it.  _plan: the stride, sample size and survivor capacity the plan gives a call of that shape. */
 void gorse_hip_test_set_recommend_sweep(int32_t stride);
 void gorse_hip_test_recommend_sweep_plan(int64_t n_items, int32_t k, int64_t n_users, int32_t *stride, int32_t *n_sample, int32_t *cap);
+/* gorse_mf_recommend under literal mode 1 (csrc/recommend_literal.hip), calls AFTERWARDS: no_skip != 0 = every candidate takes the
+ * serial push / pop (gorse_mf_recommend_literal_stats then counts no skipped candidate); results never depend on it. */
+void gorse_hip_test_set_recommend_literal(int32_t no_skip);
 /* gorse_fm_rank_users (csrc/fm_rank.hip), calls AFTERWARDS: round_rows > 0 = rows of a launch round at most (raised to the call's
  * batch_size where smaller: a slice is never split; 0 = by the scratch budget); sort_cap > 0 = entries of the longest list the
  * device sorts (at most 4096, the default; longer lists are sorted by the host).  Results never depend on them. */

@@ -41,6 +41,16 @@ func (m *hipModel) SetRecommendSchedule(schedule int) error {
 	return nil
 }
 
+// SetRecommendLiteral picks how RecommendUnseen answers the queries the threshold kernels leave to the literal path (tied scores, NaN
+// scores, n > 256): 0 = candidate lists ranked by one thread per query (the default), 1 = one workgroup per query with the heap in
+// on-chip memory (the same lists; widths and n it does not serve fall back to 0).
+func (m *hipModel) SetRecommendLiteral(mode int) error {
+	if rc := C.gorse_mf_set_recommend_literal(m.h, C.int32_t(mode)); rc != C.GORSE_OK {
+		return hipError("gorse_mf_set_recommend_literal", rc)
+	}
+	return nil
+}
+
 // RecommendUnseen ranks for users[t] (an index of the model's user dictionary; negative = not predictable, empty list) the items
 // that itemOk admits (nil: the items with training feedback = IsItemPredictable) and that are neither in the user's training row
 // held by the handle nor in seen[t] (nil: no such rows).  numItems = the model's item count: the library reads that many itemOk

@@ -20,7 +20,12 @@ equal in every bit or the run fails.  Route 0 is the yardstick.  Default output 
 --schedules 0,1 does the same for gorse_mf_set_recommend_schedule (0 = running threshold, 1 = pilot threshold and one matrix sweep),
 route 0 throughout; schedule 0 is the yardstick; --stride N sets the pilot's base sample stride for the run (0 = the plan's).  The
 sweep's survivors per query and handed-back queries are reported.  Default output then: profiles/recommend_sweep_bench.json.
-usage: bench_recommend.py [--workloads ml1m,c3] [--reps 5] [--compiled [--compiled-users 1024]] [--routes 0,1 | --schedules 0,1 [--stride N]]
+--literal 0,1 does the same for gorse_mf_set_recommend_literal (0 = candidate lists ranked by one thread per query, 1 = one workgroup
+per query with the heap in LDS), route 0 throughout and under the schedule --schedule names; mode 0 is the yardstick.  The literal
+queries, and the candidates mode 1 pushed and skipped, are reported.  Default output then: profiles/recommend_literal_bench.json,
+one entry per (workload, schedule).
+usage: bench_recommend.py [--workloads ml1m,c3] [--reps 5] [--compiled [--compiled-users 1024]]
+                          [--routes 0,1 | --schedules 0,1 [--stride N] | --literal 0,1 [--schedule S]]
                           [--out profiles/recommend_bench.json]"""
 import argparse
 import json
@@ -145,13 +150,15 @@ def run(name, data, d, n_new, n_old, reps, n_compiled):
     return res
 
 
-def run_routes(name, data, d, n_users, reps, route_list, what="route"):
-    """what = "route" or "schedule": the setter whose values route_list holds"""
+def run_routes(name, data, d, n_users, reps, route_list, what="route", schedule=0):
+    """what = "route", "schedule" or "literal": the setter whose values route_list holds; schedule = the one a "literal" run is under"""
     P, Q = synth.init_factors(data.U, data.I, d, 0.0, 0.1, 1)
     mf = capi.MF(data.U, data.I, d, np.asarray(data.uptr), np.asarray(data.uidx))
     mf.set_factors(P, Q)
     ok = np.ones(data.I, np.uint8)
-    wall, dev, rows, split, used, sweep = ({r: [] for r in route_list} for _ in range(6))
+    if what == "literal":
+        mf.set_recommend_schedule(schedule)
+    wall, dev, rows, split, used, sweep, lit = ({r: [] for r in route_list} for _ in range(7))
     for rep in range(reps + 1):  # repetition 0 warms up
         for r in route_list:
             getattr(mf, "set_recommend_" + what)(r)
@@ -162,6 +169,7 @@ def run_routes(name, data, d, n_users, reps, route_list, what="route"):
                 nf, nl, ms = mf.recommend_stats()
                 dev[r].append(ms * 1e-3)
                 split[r], used[r], sweep[r] = (nf, nl), getattr(mf, "recommend_" + what)()[1], mf.recommend_sweep_stats()
+                lit[r] = mf.recommend_literal_stats()
     first = rows[route_list[0]]
     for r in route_list[1:]:
         assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(first, rows[r])), "%s %d rows differ" % (what, r)
@@ -173,6 +181,10 @@ def run_routes(name, data, d, n_users, reps, route_list, what="route"):
         res["compared"] = "schedules"
         for r in route_list:
             res["routes"][str(r)].update(n_handed_back=sweep[r][1], survivors_per_query=sweep[r][2] / max(1, sweep[r][0]))
+    if what == "literal":
+        res.update(compared="literal modes", schedule=schedule)
+        for r in route_list:
+            res["routes"][str(r)].update(literal_queries=lit[r][0], pushed=lit[r][1], skipped=lit[r][2])
     if len(route_list) > 1:
         res["wall_ratio_first_over_last"] = float(np.median(wall[route_list[0]]) / np.median(wall[route_list[-1]]))
         res["device_ratio_first_over_last"] = float(np.median(dev[route_list[0]]) / np.median(dev[route_list[-1]]))
@@ -189,12 +201,14 @@ def main():
     ap.add_argument("--routes", default="", help="e.g. 0,1: compare gorse_mf_set_recommend_route's kernels instead of the over-fetch route")
     ap.add_argument("--schedules", default="", help="e.g. 0,1: compare gorse_mf_set_recommend_schedule's schedules the same way")
     ap.add_argument("--stride", type=int, default=0, help="--schedules: the pilot's base sample stride (0 = the plan's)")
+    ap.add_argument("--literal", default="", help="e.g. 0,1: compare gorse_mf_set_recommend_literal's modes the same way")
+    ap.add_argument("--schedule", type=int, default=0, help="--literal: the schedule the threshold queries run under")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    route_list = [int(r) for r in (a.schedules or a.routes).split(",") if r]
-    what = "schedule" if a.schedules else "route"
+    route_list = [int(r) for r in (a.literal or a.schedules or a.routes).split(",") if r]
+    what = "literal" if a.literal else "schedule" if a.schedules else "route"
     capi.lib().gorse_hip_test_set_recommend_sweep(a.stride)
-    a.out = a.out or os.path.join(ROOT, "profiles", "recommend_sweep_bench.json" if a.schedules else
+    a.out = a.out or os.path.join(ROOT, "profiles", "recommend_literal_bench.json" if a.literal else "recommend_sweep_bench.json" if a.schedules else
                                   "recommend_matrix_bench.json" if route_list else "recommend_bench.json")
     res = []
     if os.path.exists(a.out):  # a workload run on its own replaces its own entry
@@ -202,11 +216,11 @@ def main():
     for w in a.workloads.split(","):
         if w == "ml1m":
             data = synth.s_ml1m()
-            r = run_routes("S-ml1m", data, 64, data.U, a.reps, route_list, what) if route_list else run("S-ml1m", data, 64, data.U, data.U, a.reps, min(a.compiled_users, data.U) if a.compiled else 0)
+            r = run_routes("S-ml1m", data, 64, data.U, a.reps, route_list, what, a.schedule) if route_list else run("S-ml1m", data, 64, data.U, data.U, a.reps, min(a.compiled_users, data.U) if a.compiled else 0)
         else:
             data = synth.s_big_shard(0, 8)  # one rank's 125,000 users of the 1M x 200K x 100M set: the same rows, items and widths
-            r = run_routes("C3", data, 128, 65536, a.reps, route_list, what) if route_list else run("C3", data, 128, 65536, a.old_users, a.reps, 0)
-        res = [x for x in res if x["workload"] != r["workload"]] + [r]
+            r = run_routes("C3", data, 128, 65536, a.reps, route_list, what, a.schedule) if route_list else run("C3", data, 128, 65536, a.old_users, a.reps, 0)
+        res = [x for x in res if (x["workload"], x.get("schedule")) != (r["workload"], r.get("schedule"))] + [r]
         print(json.dumps(r), flush=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
