@@ -4,7 +4,7 @@
 //
 // Semantics are the reference's (NOT BLAS beta=0): the NN, TN and TT cases accumulate into C
 // through an l-ascending FMA chain per element (clang contracts `c += a*b` in _mm512_mm), the NT
-// case overwrites C with floats.Dot of two rows in AVX512 lane order.  The f32 chain is exactly
+// case overwrites C with floats.Dot of two rows in AVX512 lane order (on the matrix cores too: sgemm_nt.hip).  The f32 chain is exactly
 // what one accumulator of v_mfma_f32_32x32x2_f32 does -- checked bit for bit on the device
 // (scripts/probe_mfma_f32_chain.hip, profiles/r04_q_probe_mfma_f32_chain.txt: wide exponent ranges, signed
 // zeros) -- so the three chain cases run on the matrix cores (sgemm_mfma_kernel, round 4) and stay
@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "cf_device.hpp"
+#include "sgemm_internal.hpp"
 
 using namespace gorse;
 
@@ -178,7 +179,8 @@ __global__ __launch_bounds__(256) void sgemm_last_step_kernel(int m, int n, int 
     }
 }
 
-// NT: C[i][j] = floats.Dot(A row i, B row j) in AVX512 order; one 16-lane group per element.
+// NT: C[i][j] = floats.Dot(A row i, B row j) in AVX512 order; one 16-lane group per element.  (Small results, and k < 16; larger ones
+// take sgemm_nt_mfma_kernel, sgemm_nt.hip: sgemm_nt_mfma_auto.)
 __global__ __launch_bounds__(kBlock) void sgemm_nt_kernel(int m, int n, int k, const float *__restrict__ a, int lda,
                                                           const float *__restrict__ b, int ldb, float *__restrict__ c,
                                                           int ldc) {
@@ -219,12 +221,14 @@ __global__ __launch_bounds__(kBlock) void sgemm_nt_long_kernel(int m, int n, int
 }
 
 int g_sgemm_valu = 0;  // test hook: 1 = the vector-ALU chain whatever the shape (gorse_hip_test_set_sgemm_valu)
+int g_sgemm_nt = 0;    // test hook: 0 = sgemm_nt_mfma_auto, 1 = always the per-element NT kernels, 2 = sgemm_nt_mfma_kernel wherever it serves
 double g_sgemm_last_ms = 0.0;  // kernel time of the last call (hipEvents around the launch): gorse_hip_test_sgemm_last_ms
 int32_t g_sgemm_last_form = 0;  // what the last call launched (GORSE_TEST_SGEMM_*, set on the host): gorse_hip_test_sgemm_last_form
 
 }  // namespace
 
 extern "C" void gorse_hip_test_set_sgemm_valu(int32_t on) { g_sgemm_valu = on; }
+extern "C" void gorse_hip_test_set_sgemm_nt(int32_t mode) { g_sgemm_nt = mode; }
 extern "C" double gorse_hip_test_sgemm_last_ms(void) { return g_sgemm_last_ms; }
 extern "C" int32_t gorse_hip_test_sgemm_last_form(void) { return g_sgemm_last_form; }
 
@@ -267,7 +271,11 @@ int32_t sgemm_on_device(hipStream_t st, EventPair &ev, int32_t transA, int32_t t
     const int a_rows = transA ? k : m, a_cols = transA ? m : k;
     const int b_rows = transB ? n : k, b_cols = transB ? k : n;
     (void)hipEventRecord(ev.ev0, st);
-    if (!transA && transB) {
+    if (!transA && transB && g_sgemm_nt != 1 && (g_sgemm_nt == 2 ? sgemm_nt_mfma_serves(m, n, k) : sgemm_nt_mfma_auto(m, n, k))) {
+        // tiles of C on the matrix cores (sgemm_nt.hip): the same bits as the two kernels below, every operand row read once per tile
+        g_sgemm_last_form = GORSE_TEST_SGEMM_NT | GORSE_TEST_SGEMM_NT_MFMA;
+        GORSE_TRY(sgemm_nt_mfma_launch(st, m, n, k, da, lda, db, ldb, dc, ldc));
+    } else if (!transA && transB) {
         int64_t blocks = std::min<int64_t>(ceil_div((int64_t)m * n, kGroupsPerBlock), 8192);
         if (k <= kNtStagedK) {
             g_sgemm_last_form = GORSE_TEST_SGEMM_NT;

@@ -160,8 +160,9 @@ double gorse_hip_test_sgemm_last_ms(void);
  * sgemm_on_device chooses it (no device code): one of NONE (m or n == 0, k == 0 outside the NT case, or the call was refused), NT
  * (one AVX512-order dot per element), VALU (sgemm_chain_kernel), MFMA64 / MFMA128 (sgemm_mfma_kernel on 64 x 64 / 128 x 128 tiles),
  * or'ed with IN_PLACE when the MFMA kernel ran on the caller's operands where they lie (whole tiles, k a multiple of 16) and with
- * NT_LONG when the NT rows were longer than the LDS staging takes (k > 512) and were read from global memory.  A test asserts the
- * form it was written for, so that a moved threshold cannot leave it testing another kernel. */
+ * NT_LONG when the NT rows were longer than the LDS staging takes (k > 512) and were read from global memory, or with NT_MFMA when
+ * the NT case ran as tiles on the matrix cores (csrc/sgemm_nt.hip sgemm_nt_mfma_kernel).  A test asserts the form it was written
+ * for, so that a moved threshold cannot leave it testing another kernel. */
 #define GORSE_TEST_SGEMM_NONE 0
 #define GORSE_TEST_SGEMM_NT 1
 #define GORSE_TEST_SGEMM_VALU 2
@@ -169,7 +170,12 @@ double gorse_hip_test_sgemm_last_ms(void);
 #define GORSE_TEST_SGEMM_MFMA128 4
 #define GORSE_TEST_SGEMM_IN_PLACE 0x100
 #define GORSE_TEST_SGEMM_NT_LONG 0x200
+#define GORSE_TEST_SGEMM_NT_MFMA 0x400
 int32_t gorse_hip_test_sgemm_last_form(void);
+/* which kernels the NT case runs: 0 = the library's rule (sgemm_nt_mfma_kernel for k >= 16, min(m, n) >= 32 and m n >= 2^18, the
+ * one-dot-per-element kernels otherwise), 1 = always the one-dot-per-element kernels, 2 = sgemm_nt_mfma_kernel for every NT call it
+ * can serve (k >= 16, any m, n >= 1).  Both give floats.Dot's bits in every element. */
+void gorse_hip_test_set_sgemm_nt(int32_t mode);
 /* test hook: runs the user-run schedule's preparation of ONE chunk (user draws, counting sort of the sample ids by user, item
  * draws by run: csrc/bpr_prepare.hip bpr_launch_prepare_users) for samples [sample_base, sample_base + n) and returns the run offsets
  * (off[u] .. off[u + 1] = the positions of user u's samples; off[U] .. off[U + 1] = samples whose user draw failed) and the
