@@ -122,6 +122,16 @@ SIGNATURES = {
     "gorse_sparse_set_profiling": (C.c_int32, [_vp, C.c_int32]),
     "gorse_sparse_get_profile": (C.c_int32, [_vp, _i64p, _f64p]),
     "gorse_sparse_last_stats": (C.c_int32, [_vp, _i64p, _i64p]),
+    "gorse_sq_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p]),
+    "gorse_sq_destroy": (C.c_int32, [_vp]),
+    "gorse_sq_set_mask": (C.c_int32, [_vp, _vp]),
+    "gorse_sq_search_vector": (C.c_int32, [_vp, _f32p, C.c_int64, C.c_int32, _i32p, _f32p, _i32p]),
+    "gorse_sq_search_rows": (C.c_int32, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _i32p, _f32p, _i32p]),
+    "gorse_sq_get_codes": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _f32p]),
+    "gorse_sq_last_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p]),
+    "gorse_sq_set_profiling": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_sq_get_profile": (C.c_int32, [_vp, C.c_int32, _i64p, _f64p]),
+    "gorse_hip_test_set_sq": (None, [C.c_int32, C.c_int32]),
     "gorse_hip_sgemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int32,
                                     _f32p, C.c_int32, _f32p, C.c_int32]),
     "gorse_hip_sgemm_device": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32,
@@ -1211,6 +1221,77 @@ class Sparse:
         out = (C.c_int64 * 4)()
         lib().gorse_hip_test_sparse_path_stats(self.h, out)
         return tuple(int(x) for x in out)
+
+
+SQ_PATH_PLAN, SQ_PATH_SCAN, SQ_PATH_SWEEP = 0, 1, 2
+SQ_PROF = ("encode", "pilot", "sweep", "select", "scan")  # GORSE_PROF_SQ_*
+
+
+def set_sq(path=SQ_PATH_PLAN, list_capacity=0):
+    """gorse_hip_test_set_sq: the path of the SQIndex searches that follow and the sweep's survivor-list capacity (0 = the plan's)"""
+    lib().gorse_hip_test_set_sq(int(path), int(list_capacity))
+
+
+class SQIndex:
+    """One gorse_sq handle: N rows of d floats kept as int8 codes on one GPU, searched exactly over the codes."""
+
+    def __init__(self, X, metric, bits=8, device=0):
+        X = _arr(X, np.float32)
+        self.N, self.d = X.shape
+        self.h = _vp()
+        check(lib().gorse_sq_create(C.byref(self.h), device, self.N, self.d, metric, bits, _p(X, _f32p)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gorse_sq_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_mask(self, admissible=None):
+        m = None if admissible is None else _arr(admissible, np.uint8)
+        if m is not None and m.size != self.N:
+            raise GorseHipError(ERR_INVALID, "mask must have N entries")
+        check(lib().gorse_sq_set_mask(self.h, None if m is None else m.ctypes.data_as(_vp)))
+
+    def search_vector(self, Q, k):
+        Q = _arr(Q, np.float32).reshape(-1, self.d)
+        nq = Q.shape[0]
+        idx, sc, cnt = np.empty((nq, k), np.int32), np.empty((nq, k), np.float32), np.empty(nq, np.int32)
+        check(lib().gorse_sq_search_vector(self.h, _p(Q, _f32p), nq, k, _p(idx, _i32p), _p(sc, _f32p), _p(cnt, _i32p)))
+        return idx, sc, cnt
+
+    def search_rows(self, k, q_begin=0, q_end=None, exclude_self=False):
+        q_end = self.N if q_end is None else q_end
+        nq = max(q_end - q_begin, 0)
+        idx, sc, cnt = np.empty((nq, k), np.int32), np.empty((nq, k), np.float32), np.empty(nq, np.int32)
+        check(lib().gorse_sq_search_rows(self.h, q_begin, q_end, k, int(bool(exclude_self)), _p(idx, _i32p), _p(sc, _f32p),
+                                         _p(cnt, _i32p)))
+        return idx, sc, cnt
+
+    def codes(self, r_begin=0, r_end=None):
+        """(int8 codes, fp32 scales) of the stored rows [r_begin, r_end)"""
+        r_end = self.N if r_end is None else r_end
+        codes, scale = np.empty((r_end - r_begin, self.d), np.int8), np.empty(r_end - r_begin, np.float32)
+        check(lib().gorse_sq_get_codes(self.h, r_begin, r_end, codes.ctypes.data_as(_vp), _p(scale, _f32p)))
+        return codes, scale
+
+    def last_stats(self):
+        """the last search: (queries the sweep answered, queries the scan answered, of those handed back by the sweep)"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gorse_sq_last_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_profiling(self, on):
+        check(lib().gorse_sq_set_profiling(self.h, int(bool(on))))
+
+    def get_profile(self):
+        out = {}
+        for cls, name in enumerate(SQ_PROF):
+            n, ms = C.c_int64(0), C.c_double(0)
+            check(lib().gorse_sq_get_profile(self.h, cls, C.byref(n), C.byref(ms)))
+            out[name] = (n.value, ms.value)
+        return out
 
 
 NBR_HOP1, NBR_HOP2 = 0, 1

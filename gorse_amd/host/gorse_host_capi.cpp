@@ -647,6 +647,14 @@ int32_t gh_vdb_describe(void *h, const char *name, int32_t *dim, int32_t *distan
         *bits = info.Config.Bits;
     });
 }
+// the collection's quantization type into buf (NUL-terminated); returns the length needed or a negative error
+int64_t gh_vdb_describe_type(void *h, const char *name, char *buf, int64_t cap) {
+    std::string type;
+    int32_t rc = guard([&] { type = vdb(h).DescribeCollection(name).Config.Type; });
+    if (rc != 0) return rc;
+    if ((int64_t)type.size() + 1 <= cap) std::memcpy(buf, type.c_str(), type.size() + 1);
+    return (int64_t)type.size() + 1;
+}
 // '\n'-joined names into buf (NUL-terminated); returns the length needed or a negative error
 int64_t gh_vdb_list(void *h, char *buf, int64_t cap) {
     std::string joined;

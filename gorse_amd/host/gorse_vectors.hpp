@@ -21,7 +21,11 @@
 //     zero scores dropped (xvec.go:419-421).  The hidden / categories filter goes to the device as an admissibility mask,
 //     so there are no over-fetch rounds.  Vectors are stored as given (GetVectors returns them unchanged) and indexed
 //     with their entries sorted by index; a repeated index is rejected.
-//   * Quantized collections are ErrNotSupported.
+//   * Quantized collections are ErrNotSupported, unless the database was opened with the option ("hip://?quantization=sq"):
+//     then a DENSE collection may be given VectorConfig{Type "sq", Bits 0 or 8}.  Its vectors are kept as given (GetVectors
+//     returns the floats), its queries are answered from a gorse_sq handle (int8 codes, exact search over the codes: gorse_hip.h)
+//     with the hidden / categories filter as the device mask, and Score is that handle's reported score.  pq, rq, other bit
+//     counts and sparse collections stay ErrNotSupported.
 // Errors are the reference's sentinels (storage/errors.go:20-24) as exception types; all methods are serialised by one
 // mutex per database (the reference requires goroutine safety; a GPU handle must be used by one caller at a time).
 #pragma once
@@ -196,9 +200,14 @@ private:
 
 class HipDatabase {
 public:
-    explicit HipDatabase(std::shared_ptr<Searcher> searcher = nullptr, std::shared_ptr<SparseSearcher> sparse = nullptr)
+    explicit HipDatabase(std::shared_ptr<Searcher> searcher = nullptr, std::shared_ptr<SparseSearcher> sparse = nullptr,
+                         bool allow_sq = false)
         : searcher_(searcher ? std::move(searcher) : std::make_shared<HipSearcher>()),
-          sparse_(sparse ? std::move(sparse) : std::make_shared<HipSparseSearcher>()) {}
+          sparse_(sparse ? std::move(sparse) : std::make_shared<HipSparseSearcher>()),
+          allow_sq_(allow_sq) {}
+    ~HipDatabase() {
+        for (auto &kv : sq_) gorse_sq_destroy(kv.second);
+    }
 
     void Init() {}
     void Optimize(const std::string &) {}
@@ -223,7 +232,11 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         check_open();
         if (dimensions < 0) throw std::invalid_argument("invalid vector dimension " + std::to_string(dimensions));
-        if (!config.Type.empty()) throw storage::ErrNotSupported("quantization type " + config.Type + " for hip not supported");
+        if (!config.Type.empty()) {
+            if (!allow_sq_ || config.Type != "sq") throw storage::ErrNotSupported("quantization type " + config.Type + " for hip not supported");
+            if (config.Bits != 0 && config.Bits != 8) throw storage::ErrNotSupported("sq with " + std::to_string(config.Bits) + " bits for hip not supported");
+            if (dimensions == 0) throw storage::ErrNotSupported("quantization of a sparse collection for hip not supported");
+        }
         if (distance != Cosine && distance != Euclidean && distance != Dot) throw storage::ErrNotSupported("distance method not supported");
         if (dimensions == 0 && distance != Dot)  // xvec.go:243-245
             throw storage::ErrNotSupported("distance method for sparse vector not supported");
@@ -382,6 +395,30 @@ public:
         for (int64_t r = 0; r < n; r++) {
             ok[(size_t)r] = admissible(c.rows[(size_t)r], categories);
             filtered = filtered || !ok[(size_t)r];
+        }
+        if (c.info.Config.Type == "sq") {  // the int8 index: one search, the filter as its mask, Score as it reports it
+            if (topK > 1024) throw storage::ErrNotSupported("topK > 1024 on a quantized collection for hip not supported");
+            auto check = [](int32_t rc) {
+                if (rc != GORSE_OK) throw std::runtime_error(gorse_hip_last_error());
+            };
+            gorse_sq *&h = sq_[name];
+            if (!h) {
+                const int32_t rc = gorse_sq_create(&h, 0, n, d, metric, c.info.Config.Bits, c.data.data());
+                if (rc != GORSE_OK) sq_.erase(name);
+                check(rc);
+            }
+            std::vector<int32_t> idx((size_t)(nq * topK)), cnt((size_t)nq);
+            std::vector<float> score((size_t)(nq * topK));
+            check(gorse_sq_set_mask(h, filtered ? ok.data() : nullptr));
+            check(gorse_sq_search_vector(h, queries.data(), nq, topK, idx.data(), score.data(), cnt.data()));
+            for (int64_t t = 0; t < nq; t++)
+                for (int e = 0; e < cnt[(size_t)t]; e++) {
+                    ScoredVector s;
+                    static_cast<Vector &>(s) = c.rows[(size_t)idx[(size_t)(t * topK + e)]];
+                    s.Score = score[(size_t)(t * topK + e)];
+                    out[(size_t)t].push_back(std::move(s));
+                }
+            return out;
         }
         if (filtered) {  // the filter as a device mask, where the searcher offers it: one search with k = topK
             const int64_t k1 = std::min<int64_t>(n, topK);
@@ -584,6 +621,11 @@ private:
     void drop_index(const std::string &name) {
         searcher_->invalidate(name);
         sparse_->invalidate(name);
+        auto it = sq_.find(name);
+        if (it != sq_.end()) {
+            gorse_sq_destroy(it->second);
+            sq_.erase(it);
+        }
     }
     void check_open() const {
         if (closed_) throw std::runtime_error("hip vector database is closed");
@@ -598,6 +640,8 @@ private:
     bool closed_ = false;
     std::shared_ptr<Searcher> searcher_;
     std::shared_ptr<SparseSearcher> sparse_;
+    bool allow_sq_ = false;                  // opened with ?quantization=sq
+    std::map<std::string, gorse_sq *> sq_;   // one int8 index per quantized collection, dropped on every change
     std::map<std::string, Collection> collections_;
 };
 
@@ -605,7 +649,13 @@ private:
 using Creator = std::function<std::shared_ptr<HipDatabase>(const std::string &path, const std::string &tablePrefix)>;
 inline std::map<std::string, Creator> &creators() {
     static std::map<std::string, Creator> c = {
-        {"hip://", [](const std::string &, const std::string &) { return std::make_shared<HipDatabase>(); }}};
+        {"hip://", [](const std::string &path, const std::string &) {
+             // the one option: hip://?quantization=sq lets dense collections be scalar-quantised
+             const size_t q = path.find('?');
+             const std::string query = q == std::string::npos ? "" : path.substr(q + 1);
+             if (!query.empty() && query != "quantization=sq") throw std::runtime_error("hip://: unknown option " + query);
+             return std::make_shared<HipDatabase>(nullptr, nullptr, !query.empty());
+         }}};
     return c;
 }
 inline void Register(const std::vector<std::string> &prefixes, Creator creator) {

@@ -59,6 +59,8 @@ def _host():
             getattr(H, n).argtypes = args
         H.gh_vdb_list.restype = C.c_int64
         H.gh_vdb_list.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        H.gh_vdb_describe_type.restype = C.c_int64
+        H.gh_vdb_describe_type.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64]
         H.gh_vdb_count.restype = C.c_int64
         H.gh_vdb_count.argtypes = [C.c_void_p, C.c_char_p]
         H.gh_vdb_stage_vector.restype = None
@@ -164,7 +166,9 @@ class Database:
     def DescribeCollection(self, name):
         d, dist, bits = C.c_int32(), C.c_int32(), C.c_int32()
         _ck(_host().gh_vdb_describe(self.h, name.encode(), C.byref(d), C.byref(dist), C.byref(bits)))
-        return {"Name": name, "Dimension": d.value, "Distance": dist.value, "Type": "", "Bits": bits.value}
+        buf = C.create_string_buffer(16)
+        _ck(_host().gh_vdb_describe_type(self.h, name.encode(), buf, 16))
+        return {"Name": name, "Dimension": d.value, "Distance": dist.value, "Type": buf.value.decode(), "Bits": bits.value}
 
     def AddCollection(self, name, dimensions, distance, quantization="", bits=0):
         _ck(_host().gh_vdb_add_collection(self.h, name.encode(), dimensions, distance, quantization.encode(), bits))
@@ -253,7 +257,8 @@ class Database:
 
 
 def Open(path, tablePrefix=""):
-    """vectors.Open (database.go:167-175): creators by URL prefix; 'hip://' is the one registered here."""
+    """vectors.Open (database.go:167-175): creators by URL prefix; 'hip://' is the one registered here.
+    'hip://?quantization=sq' lets dense collections be added with quantization="sq" (bits 0 or 8): see gorse_vectors.hpp."""
     return Database(url=path)
 
 

@@ -462,6 +462,40 @@ int32_t gorse_sparse_set_profiling(gorse_sparse *h, int32_t on);
 int32_t gorse_sparse_get_profile(gorse_sparse *h, int64_t *launches, double *total_ms);
 int32_t gorse_sparse_last_stats(gorse_sparse *h, int64_t *postings, int64_t *hits);
 
+/* ---- scalar-quantised (int8) exact top-k: VectorConfig{Type: "sq"} of storage/vectors/database.go:35-82 ----------------
+ * N stored rows of d floats, 1 <= d <= 4096, N < 2^31, kept as int8 codes; the search is EXACT over the codes.
+ * Row r (stored or query): a_r = max_j |x_rj|, s_r = a_r / 127, c_rj = rint(x_rj / s_r) (round half to even, in [-127, 127];
+ * a_r = 0: s_r = 0 and every code 0); n_r = sum_j c_rj^2, sn_r = (s_r * s_r) * (float)n_r, rn_r = sqrtf(sn_r).  All fp32, every
+ * operation rounded, none fused.  A row with a non-finite value or a non-finite sn_r: GORSE_ERR_INVALID, the handle as it was.
+ * Pair (q, x): t = sum_j c_qj * c_xj (exact int32), p = ((float)t * s_x) * s_q.  Reported score (higher is better, the host
+ * mirror's Score): NEG_DOT p; COSINE p / (rn_q * rn_x) - 1.0f, exactly -1.0f when rn_q * rn_x == 0; EUCLIDEAN
+ * -sqrtf(fmaxf((sn_q + sn_x) - (p + p), 0.0f)).  GORSE_METRIC_EUCLIDEAN_BF16, bits other than 0 or 8: GORSE_ERR_INVALID.
+ * Result per query: the admissible rows (minus the query's own row where asked) in descending score, scores compared as IEEE
+ * values (-0 equals +0), equal scores in ascending row order, cut to k (1 <= k <= 1024).  idx_out / score_out are nq x k padded
+ * with -1 / -inf, count_out[t] = valid entries.  All three are host memory and required. */
+typedef struct gorse_sq gorse_sq;
+int32_t gorse_sq_create(gorse_sq **h, int32_t device, int64_t N, int32_t d, int32_t metric, int32_t bits /*0 or 8*/, const float *X /*host*/);
+int32_t gorse_sq_destroy(gorse_sq *h);
+int32_t gorse_sq_set_mask(gorse_sq *h, const uint8_t *admissible /*host, N bytes, or NULL*/);
+int32_t gorse_sq_search_vector(gorse_sq *h, const float *Q /*host, nq x d*/, int64_t nq, int32_t k, int32_t *idx_out, float *score_out,
+                               int32_t *count_out);
+/* the stored codes of rows [q_begin, q_end) as queries; exclude_self != 0 leaves row q out of its own list */
+int32_t gorse_sq_search_rows(gorse_sq *h, int64_t q_begin, int64_t q_end, int32_t k, int32_t exclude_self, int32_t *idx_out,
+                             float *score_out, int32_t *count_out);
+/* codes ((r_end - r_begin) x d, the padding left out) and scales of stored rows; either output may be NULL */
+int32_t gorse_sq_get_codes(gorse_sq *h, int64_t r_begin, int64_t r_end, int8_t *codes /*host*/, float *scale /*host*/);
+/* the last search: queries the matrix-core sweep answered, queries the scan answered, and how many of the latter the sweep handed
+ * back (too few admissible sampled rows for a threshold, or a survivor list that overflowed) */
+int32_t gorse_sq_last_stats(gorse_sq *h, int64_t *n_sweep, int64_t *n_scan, int64_t *n_handed_back);
+#define GORSE_PROF_SQ_ENCODE 0 /* sq_encode_kernel                                     */
+#define GORSE_PROF_SQ_PILOT 1  /* sq_sweep_kernel over the sample + sq_pilot_select_kernel */
+#define GORSE_PROF_SQ_SWEEP 2  /* sq_sweep_kernel over all rows                        */
+#define GORSE_PROF_SQ_SELECT 3 /* sq_select_kernel                                     */
+#define GORSE_PROF_SQ_SCAN 4   /* sq_scan_kernel                                       */
+#define GORSE_PROF_SQ_NCLASSES 5
+int32_t gorse_sq_set_profiling(gorse_sq *h, int32_t on);
+int32_t gorse_sq_get_profile(gorse_sq *h, int32_t kernel_class, int64_t *launches, double *total_ms);
+
 /* ---- floats.MM / blas.SGEMM, common/floats/floats.go:241, mm.go:19-49 ------------------------
  * Row-major C(m x n) = op(A) op(B) with the reference's own semantics: the NN, TN and TT
  * cases ACCUMULATE into C, the NT case overwrites it (mm.go:20-48, floats_avx512.c:443-480).

@@ -277,6 +277,10 @@ int32_t gorse_hip_test_mf_evaluate_tables(float *inv_log /*host, n*/, float *idc
  * library's 13056; a query takes the LDS path when its bound + 1 fits), so that small inputs reach the global path; query_chunk > 0 =
  * queries per launch at most, so that they run the launch loop.  0 restores the library's choice.  Results never depend on them. */
 void gorse_hip_test_set_nbr(int32_t lds_slots, int64_t query_chunk);
+/* gorse_sq searches (csrc/sq.hip), calls AFTERWARDS: path 0 = by plan (csrc/sq_plan.hpp), 1 = the scan only, 2 = the matrix-core sweep
+ * wherever it serves (d <= 1024, k <= 256, enough sampled rows for a threshold); list_capacity > 0 = keys of a query's survivor list
+ * in the sweep, so that small inputs reach the hand-back (0 = the plan's).  Results never depend on them. */
+void gorse_hip_test_set_sq(int32_t path, int32_t list_capacity);
 
 #ifdef __cplusplus
 }

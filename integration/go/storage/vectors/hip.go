@@ -13,6 +13,7 @@ import (
 	"fmt"
 	"slices"
 	"sort"
+	"strings"
 	"sync"
 	"time"
 	"unsafe"
@@ -25,11 +26,23 @@ import (
 // EXACTLY on one MI355X (dense: gorse_topk_*, sparse: gorse_sparse_*).  The semantics are the xvec backend's
 // (xvec.go): upsert by Id, millisecond cut-off deletes, hidden / CONTAIN_ALL filters, Score = the inner product for Dot
 // and the negated distance otherwise, zero scores dropped from sparse results after the cut to topK.
+//
+// One option: "hip://?quantization=sq" lets a DENSE collection be added with VectorConfig{Type: QuantizationSQ, Bits: 0 or 8}.
+// Its vectors are kept as given (GetVectors returns the floats); its queries are answered from a gorse_sq handle (int8 codes,
+// exact search over the codes, gorse_hip.h) and Score is that handle's reported score.  pq, rq, other bit counts and sparse
+// collections stay ErrNotSupported, and so does every quantization without the option.
 const HipPrefix = "hip://"
 
 func init() {
 	Register([]string{HipPrefix}, func(path, tablePrefix string, _ ...storage.Option) (Database, error) {
-		return &Hip{collections: make(map[string]*hipCollection)}, nil
+		option := ""
+		if at := strings.IndexByte(path, '?'); at >= 0 {
+			option = path[at+1:]
+		}
+		if option != "" && option != "quantization=sq" {
+			return nil, errors.Errorf("hip://: unknown option %s", option)
+		}
+		return &Hip{collections: make(map[string]*hipCollection), allowSQ: option != ""}, nil
 	})
 }
 
@@ -40,6 +53,7 @@ type hipCollection struct {
 	// dense: rows x Dimension, row-major, and its device index (rebuilt lazily after a change)
 	data  []float32
 	dense *C.gorse_topk
+	sq    *C.gorse_sq // a quantized collection's int8 index instead of `dense`
 	// sparse: the rows as CSR with ascending indices, and its device index
 	indptr  []int64
 	indices []uint32
@@ -48,6 +62,10 @@ type hipCollection struct {
 }
 
 func (c *hipCollection) dropIndex() {
+	if c.sq != nil {
+		C.gorse_sq_destroy(c.sq)
+		c.sq = nil
+	}
 	if c.dense != nil {
 		C.gorse_topk_destroy(c.dense)
 		c.dense = nil
@@ -64,6 +82,7 @@ type Hip struct {
 	mu          sync.Mutex
 	collections map[string]*hipCollection
 	closed      bool
+	allowSQ     bool // opened with ?quantization=sq
 }
 
 func (db *Hip) Init() error { return nil }
@@ -143,7 +162,15 @@ func (db *Hip) AddCollection(ctx context.Context, name string, dimensions int, d
 		return errors.Errorf("invalid vector dimension %d", dimensions)
 	}
 	if config.Type != QuantizationNone {
-		return fmt.Errorf("quantization type %s for hip %w", config.Type, storage.ErrNotSupported)
+		if !db.allowSQ || config.Type != QuantizationSQ {
+			return fmt.Errorf("quantization type %s for hip %w", config.Type, storage.ErrNotSupported)
+		}
+		if config.Bits != 0 && config.Bits != 8 {
+			return fmt.Errorf("sq with %d bits for hip %w", config.Bits, storage.ErrNotSupported)
+		}
+		if dimensions == 0 {
+			return fmt.Errorf("quantization of a sparse collection for hip %w", storage.ErrNotSupported)
+		}
 	}
 	if dimensions == 0 && distance != Dot { // xvec.go:243-245
 		return fmt.Errorf("distance method for sparse vector %w", storage.ErrNotSupported)
@@ -303,14 +330,17 @@ func (db *Hip) queryDense(c *hipCollection, q []float32, categories []string, to
 	if n == 0 || topK <= 0 {
 		return []ScoredVector{}, nil
 	}
+	metric := C.int32_t(C.GORSE_METRIC_COSINE)
+	switch c.info.Distance {
+	case Dot:
+		metric = C.GORSE_METRIC_NEG_DOT
+	case Euclidean:
+		metric = C.GORSE_METRIC_EUCLIDEAN
+	}
+	if c.info.VectorConfig.Type == QuantizationSQ {
+		return db.querySQ(c, metric, q, categories, topK)
+	}
 	if c.dense == nil {
-		metric := C.int32_t(C.GORSE_METRIC_COSINE)
-		switch c.info.Distance {
-		case Dot:
-			metric = C.GORSE_METRIC_NEG_DOT
-		case Euclidean:
-			metric = C.GORSE_METRIC_EUCLIDEAN
-		}
 		if rc := C.gorse_topk_create(&c.dense, 0, C.int64_t(n), C.int32_t(d), C.GORSE_DTYPE_F32, metric, unsafe.Pointer(&c.data[0])); rc != 0 {
 			return nil, lastError("gorse_topk_create")
 		}
@@ -334,6 +364,39 @@ func (db *Hip) queryDense(c *hipCollection, q []float32, categories []string, to
 	results := make([]ScoredVector, 0, int(cnt))
 	for t := 0; t < int(cnt); t++ {
 		results = append(results, ScoredVector{Vector: c.rows[idx[t]], Score: -dist[t]}) // Dot: a.b; else the negated distance
+	}
+	return results, nil
+}
+
+// querySQ: queryDense on a quantized collection's gorse_sq handle; Score is the handle's reported score as it stands.
+func (db *Hip) querySQ(c *hipCollection, metric C.int32_t, q []float32, categories []string, topK int) ([]ScoredVector, error) {
+	d, n := c.info.Dimension, len(c.rows)
+	if topK > 1024 {
+		return nil, fmt.Errorf("topK > 1024 on a quantized collection for hip %w", storage.ErrNotSupported)
+	}
+	if c.sq == nil {
+		if rc := C.gorse_sq_create(&c.sq, 0, C.int64_t(n), C.int32_t(d), metric, C.int32_t(c.info.VectorConfig.Bits), (*C.float)(unsafe.Pointer(&c.data[0]))); rc != 0 {
+			return nil, lastError("gorse_sq_create")
+		}
+	}
+	ok := make([]uint8, n)
+	for t := range c.rows {
+		if admissible(&c.rows[t], categories) {
+			ok[t] = 1
+		}
+	}
+	if rc := C.gorse_sq_set_mask(c.sq, (*C.uint8_t)(unsafe.Pointer(&ok[0]))); rc != 0 {
+		return nil, lastError("gorse_sq_set_mask")
+	}
+	idx, score := make([]int32, topK), make([]float32, topK)
+	var cnt C.int32_t
+	if rc := C.gorse_sq_search_vector(c.sq, (*C.float)(unsafe.Pointer(&q[0])), 1, C.int32_t(topK), (*C.int32_t)(unsafe.Pointer(&idx[0])),
+		(*C.float)(unsafe.Pointer(&score[0])), &cnt); rc != 0 {
+		return nil, lastError("gorse_sq_search_vector")
+	}
+	results := make([]ScoredVector, 0, int(cnt))
+	for t := 0; t < int(cnt); t++ {
+		results = append(results, ScoredVector{Vector: c.rows[idx[t]], Score: score[t]})
 	}
 	return results, nil
 }
