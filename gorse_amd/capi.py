@@ -21,7 +21,7 @@ PROF_BPR_UPDATE, PROF_BPR_SAMPLE, PROF_ALS_SWEEP, PROF_ALS_GRAM, PROF_BPR_SORT, 
 COMM_ID_BYTES = 128
 MF_EVAL_MAX_TOPK = 128  # GORSE_MF_EVAL_MAX_TOPK
 OPT_SGD, OPT_ADAM = 0, 1
-PROF_TOPK_SCORE, PROF_TOPK_RESCORE, PROF_TOPK_SWEEP, PROF_TOPK_SELECT, PROF_TOPK_HIST, PROF_TOPK_REPLAY = 0, 1, 2, 3, 4, 5
+PROF_TOPK_SCORE, PROF_TOPK_RESCORE, PROF_TOPK_SWEEP, PROF_TOPK_SELECT, PROF_TOPK_HIST, PROF_TOPK_REPLAY, PROF_TOPK_DEEP = 0, 1, 2, 3, 4, 5, 6
 # gorse_hip_test_set_topk_variant (include/gorse_hip_test.h, GORSE_TEST_TOPK_*)
 TOPK_TILE64, TOPK_COARSE_OFF, TOPK_COARSE_ON, TOPK_REPLAY_COUNTERS = 1 << 0, 1 << 2, 1 << 3, 1 << 4
 TOPK_WARM_OFF, TOPK_WARM_ALWAYS, TOPK_PILOT_KTH2, TOPK_COLD_SLICES = 1 << 8, 1 << 9, 1 << 10, 1 << 11
@@ -113,6 +113,8 @@ SIGNATURES = {
     "gorse_topk_set_profiling": (C.c_int32, [_vp, C.c_int32]),
     "gorse_topk_get_profile": (C.c_int32, [_vp, C.c_int32, _i64p, _f64p]),
     "gorse_topk_last_stats": (C.c_int32, [_vp, _i64p, _i64p]),
+    "gorse_topk_set_deep_sweep": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_topk_get_deep_sweep": (C.c_int32, [_vp, _i32p, _i32p, _i32p]),
     "gorse_sparse_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64, _i64p, _vp, _f32p]),
     "gorse_sparse_destroy": (C.c_int32, [_vp]),
     "gorse_sparse_set_mask": (C.c_int32, [_vp, _vp]),
@@ -1001,6 +1003,16 @@ class TopK:
         if m is not None and m.size != self.N:
             raise GorseHipError(ERR_INVALID, "mask must have N entries")
         check(lib().gorse_topk_set_mask(self.h, None if m is None else m.ctypes.data_as(_vp)))
+
+    def set_deep_sweep(self, mode):
+        """gorse_topk_set_deep_sweep: 1 = the matrix-core sweep for rows too wide for path B today (bf16 384 < d <= 4096, fp32 128 < d <= 1536)"""
+        check(lib().gorse_topk_set_deep_sweep(self.h, int(mode)))
+
+    def get_deep_sweep(self):
+        """(mode asked for, the index has deep operands, the last search's main sweep was the deep kernel)"""
+        a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_topk_get_deep_sweep(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def resweeps(self):
         n = C.c_int64(0)

@@ -287,7 +287,8 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
     // can take them (its history sweep + heap replay answer a tie query in tens of milliseconds) they go there.
     // (not with a mask: the replay counts the rows between two recorded ones, masked rows included, so the MFMA path sends a
     // masked tie query back to the literal kernel anyway -- after a full sweep)
-    reroute = reroute && !g_scan_literal_only && !h->has_mask && topk_mfma_usable(h, kMinRerouteQueries, k);
+    // (nor to a deep handle, which has no tie path: its sweep would hand them back to this scan)
+    reroute = reroute && !g_scan_literal_only && !h->has_mask && !h->deep && topk_mfma_usable(h, kMinRerouteQueries, k);
     if (!g_scan_literal_only) {
         GORSE_TRY(h->scan_literal.ensure((size_t)nq));
         literal = h->scan_literal.p;
@@ -375,6 +376,7 @@ int32_t topk_search_stored(gorse_topk *h, const int64_t *src_host, int64_t nq, i
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
+    h->last_deep = false;
     const int d = h->d;
     const bool mfma = topk_mfma_usable(h, nq, k);
     const int64_t bq = mfma ? nq : std::min(topk_scan_block_queries(h), nq);  // path B takes its query vectors all at once
@@ -492,6 +494,7 @@ extern "C" int32_t gorse_topk_search_index(gorse_topk *h, const int64_t *q, int6
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
+    h->last_deep = false;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, q, -1, nullptr, nq, k, prune0, idx_out, dist_out, count_out);
     const int64_t bq = topk_scan_block_queries(h);
     GORSE_TRY(h->qidx.ensure((size_t)std::min(bq, nq)));
@@ -517,6 +520,7 @@ extern "C" int32_t gorse_topk_search_vector(gorse_topk *h, const void *qv, int64
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
+    h->last_deep = false;
     if (topk_mfma_usable(h, nq, k)) {  // all query vectors to the device as fp32, then path B
         GORSE_TRY(h->qf32.ensure((size_t)nq * h->d));
         if (h->dtype == GORSE_DTYPE_BF16) {
@@ -564,6 +568,7 @@ extern "C" int32_t gorse_topk_all_pairs(gorse_topk *h, int64_t q_begin, int64_t 
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
+    h->last_deep = false;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, nullptr, q_begin, nullptr, nq, k, 0, idx_out, dist_out, nullptr);
     const int64_t bq = topk_scan_block_queries(h);
     const int64_t mb = std::min(bq, nq);
@@ -622,6 +627,12 @@ __global__ void masked_scale_kernel(const uint8_t *__restrict__ mask, const floa
         out[i] = (i < n && mask[i]) ? base[i] : __builtin_nanf("");
 }
 
+int32_t gorse::topk_masked_scale(gorse_topk *h) {
+    masked_scale_kernel<<<dim3(1024), dim3(256), 0, h->stream>>>(h->mask.p, h->rscale.p, h->N, h->N + gorse::kTopkRowPad, h->rscale_m.p);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
 extern "C" int32_t gorse_topk_set_mask(gorse_topk *h, const uint8_t *admissible) {
     if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
     GORSE_TRY(h->use());
@@ -635,11 +646,27 @@ extern "C" int32_t gorse_topk_set_mask(gorse_topk *h, const uint8_t *admissible)
     for (int64_t r = 0; r < h->N; r++) h->n_admissible += admissible[r] != 0;
     if (h->mfma_ok) {
         GORSE_TRY(h->rscale_m.ensure((size_t)h->N + gorse::kTopkRowPad));
-        masked_scale_kernel<<<dim3(1024), dim3(256), 0, h->stream>>>(h->mask.p, h->rscale.p, h->N, h->N + gorse::kTopkRowPad, h->rscale_m.p);
-        GORSE_HIP_CHECK(hipGetLastError());
+        GORSE_TRY(topk_masked_scale(h));
     }
     GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
     h->has_mask = true;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_topk_set_deep_sweep(gorse_topk *h, int32_t mode) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (mode != 0 && mode != 1) return fail(GORSE_ERR_INVALID, "deep sweep mode %d: 0 or 1", mode);
+    GORSE_TRY(h->use());
+    const int32_t rc = topk_deep_prepare(h, mode == 1);
+    h->deep_requested = rc == GORSE_OK ? mode : 0;
+    if (rc != GORSE_OK) (void)topk_deep_prepare(h, false);
+    return rc;
+}
+extern "C" int32_t gorse_topk_get_deep_sweep(gorse_topk *h, int32_t *requested, int32_t *serves, int32_t *last_used) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (requested) *requested = h->deep_requested;
+    if (serves) *serves = h->deep ? 1 : 0;
+    if (last_used) *last_used = h->last_deep ? 1 : 0;
     return GORSE_OK;
 }
 

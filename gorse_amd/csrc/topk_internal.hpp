@@ -4,7 +4,7 @@
 #pragma once
 #include "cf_device.hpp"
 
-#define GORSE_PROF_TOPK_NCLASSES 6
+#define GORSE_PROF_TOPK_NCLASSES 7
 
 namespace gorse {
 struct TopkChunkState;  // topk_mfma_internal.hpp: what the stages of one chunk of an MFMA search share
@@ -31,6 +31,11 @@ struct gorse_topk {
     float rs_min = 0.0f, rs_max = 0.0f;  // cosine: bounds of the row scales 1 / sqrt(norm2[i]) (the DMA sweeps' block bound)
     gorse::DevBuf<uint16_t> opA_own, opB_own;  // bf16 operand matrices N x KPAD (candidate / query roles)
     const uint16_t *opA = nullptr, *opB = nullptr;  // may alias Xb
+    // gorse_topk_set_deep_sweep (topk_deep.hip): deep = the operands above are the deep form's -- whole K-slices, kp > 24, built on request
+    // for an index too deep for the register-resident sweep; such a handle has no tie path, no symmetric and no triangle form
+    bool deep = false;
+    int deep_requested = 0;        // the mode asked for (0 / 1)
+    bool last_deep = false;        // the last search's main sweep was the deep kernel
     gorse::DevBuf<float> rscale;   // the sweep's per-row value: cosine 1 / sqrt(norm2[i]), Euclidean -norm2[i] / 2, -dot 1; N + kTopkRowPad
                                    // entries, the padding NaN (what the sweep's tiles read for the rows past N)
     gorse::DevBuf<uint16_t> opQ;   // query operands of the current chunk when they are not rows of opB
@@ -176,6 +181,7 @@ protected:
 
 // topk.hip
 int32_t topk_compute_norms(gorse_topk *h, const float *V, int64_t n, float *out);
+int32_t topk_masked_scale(gorse_topk *h);  // h->rscale_m = h->rscale with NaN for the rows h->mask hides
 // Stored rows src_host[0 .. nq) as query VECTORS (the row itself is not excluded, as gorse_topk_search_vector does not exclude it),
 // prune0 = 0, under the current mask: the same search as the public call on those rows' vectors, gathered on the device from the
 // index's fp32 image, every block's results handed to `consumer`.
@@ -190,6 +196,9 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
 int64_t topk_scan_block_queries(const gorse_topk *h);
 // topk_mfma.hip
 int32_t topk_mfma_prepare(gorse_topk *h);  // at create: operands, scales, error bound
+// gorse_topk_set_deep_sweep: builds (on != 0) or drops the deep operands of an index the deep form serves (topk_deep_plan.hpp);
+// h->deep says whether it has them afterwards.  A failure leaves nothing built.
+int32_t topk_deep_prepare(gorse_topk *h, bool on);
 // Queries: stored vectors qid_host[0..nq) (exclude_self) or, when qid_host is NULL and qv_dev is given, nq fp32
 // query vectors already on the device.  Host outputs may be NULL.
 int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_contig_begin, const float *qv_dev,

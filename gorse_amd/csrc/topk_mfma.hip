@@ -21,6 +21,7 @@
 // each through its stages -- operands and margins, pilot sweeps, the main sweep (topk_sweep.hip), rescoring (topk_rescore.hip), the
 // tie path for what that leaves undecided (topk_tie.hip), the literal scan (topk.hip) for what THAT leaves.  topk_tri.hip runs the
 // same stages call by call; topk_mfma_internal.hpp is what the units share, topk_plan.hpp the rules the host decides by.
+#include "topk_deep_plan.hpp"
 #include "topk_mfma_internal.hpp"
 
 using namespace gorse;
@@ -150,18 +151,28 @@ bool topk_mfma_usable(const gorse_topk *h, int64_t nq, int k) {
     // Below ~800 queries the scan (path A: distances in the reference's order, select_fast_kernel) is faster: 0.12 ms per query at
     // N = 1M, against the ~40-100 ms one or two workgroups need to sweep a million rows on their own (profiles/
     // r02_v / r02_w_probe_query_latency.txt: 64 queries 7.4 ms on the scan, 41 ms on the sweep; 512 queries 96 ms on the sweep).
-    return g_topk_force_path >= 2 || nq >= kMinSweepQueries;
+    return g_topk_force_path >= 2 || nq >= (h->deep ? topk_deep_plan::kMinDeepQueries : kMinSweepQueries);
 }
+
+static int32_t build_operands(gorse_topk *h, int kpad);
 
 int32_t topk_mfma_prepare(gorse_topk *h) {
     h->mfma_ok = false;
     if (h->metric != GORSE_METRIC_NEG_DOT && h->metric != GORSE_METRIC_COSINE && h->metric != GORSE_METRIC_EUCLIDEAN)
         return GORSE_OK;
-    const int64_t N = h->N;
     const int d = h->d;
     const bool bf = h->dtype == GORSE_DTYPE_BF16;
     const int kp = operand_depth(bf, d);
     if (kp == 0) return GORSE_OK;  // too deep for register-resident query operands: path A
+    return build_operands(h, kp * 16);
+}
+
+// the operands of kpad values per row (whole k-steps; the deep form: whole K-slices), the per-row values and the error bound;
+// h->mfma_ok says whether the data admitted them
+int32_t build_operands(gorse_topk *h, int kpad) {
+    const int64_t N = h->N;
+    const int d = h->d;
+    const bool bf = h->dtype == GORSE_DTYPE_BF16;
     // the error bound needs finite norms (and non-zero ones for cosine, whose reference distance is then NaN)
     std::vector<float> n2((size_t)N);
     GORSE_HIP_CHECK(hipMemcpyAsync(n2.data(), h->norm2.p, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
@@ -182,8 +193,7 @@ int32_t topk_mfma_prepare(gorse_topk *h) {
             h->rs_max = (1.0f / std::sqrt(mn2)) * (1.0f + 1e-6f);
         }
     }
-    h->kp = kp;
-    const int kpad = kp * 16;
+    h->kp = kpad / 16;
     // forward error of two different summation orders of the same K' exact products (the reference's fp32
     // chain, gamma <= K' u, and the MFMA's, gamma <= 2 K' u allowing truncating adders), plus the fp32 roundings
     // of the cosine formula; fp32 inputs add the dropped lo.lo / residual terms of the RNE split (3 * 2^-16).
@@ -220,6 +230,37 @@ int32_t topk_mfma_prepare(gorse_topk *h) {
     GORSE_HIP_CHECK(hipGetLastError());
     GORSE_HIP_CHECK(hipStreamSynchronize(h->stream));
     h->mfma_ok = true;
+    return GORSE_OK;
+}
+
+int32_t topk_deep_prepare(gorse_topk *h, bool on) {
+    const int kpad = topk_deep_plan::padded_depth(h->dtype == GORSE_DTYPE_BF16, h->d);
+    if (kpad == 0 || (h->mfma_ok && !h->deep)) return GORSE_OK;  // not a deep index: nothing to build or drop
+    auto drop = [&]() {
+        (void)hipStreamSynchronize(h->stream);
+        h->mfma_ok = h->deep = false;
+        h->opA = h->opB = nullptr;
+        h->opA_own.release();
+        h->opB_own.release();
+        h->rscale.release();
+        h->rscale_m.release();
+    };
+    if (!on) {
+        if (h->deep) drop();
+        return GORSE_OK;
+    }
+    if (h->deep) return GORSE_OK;
+    if (h->metric != GORSE_METRIC_NEG_DOT && h->metric != GORSE_METRIC_COSINE && h->metric != GORSE_METRIC_EUCLIDEAN) return GORSE_OK;
+    int32_t rc = build_operands(h, kpad);
+    if (rc == GORSE_OK && h->mfma_ok && h->has_mask) {  // the mask was set while the index had no per-row values
+        rc = h->rscale_m.ensure((size_t)h->N + kTopkRowPad);
+        if (rc == GORSE_OK) rc = topk_masked_scale(h);
+    }
+    if (rc != GORSE_OK) {
+        drop();
+        return rc;
+    }
+    h->deep = h->mfma_ok;
     return GORSE_OK;
 }
 
@@ -448,7 +489,8 @@ static int32_t tie_path(gorse_topk *h, const ChunkState &cs, int64_t n_flagged, 
     if (n_flagged <= 0) return GORSE_OK;
     // (with a mask the replay's gap arithmetic -- which counts the rows between two recorded ones -- would count masked
     // rows too: those queries take the literal scan, which skips masked rows)
-    if (g_topk_force_path == 3 || h->has_mask) return fetch_flagged(h, 0, n_flagged, rest);
+    // (a deep handle has no history sweep: its flagged queries take the literal scan as well)
+    if (g_topk_force_path == 3 || h->has_mask || h->deep) return fetch_flagged(h, 0, n_flagged, rest);
     std::vector<uint8_t> f2;
     for (int64_t f0 = 0; f0 < n_flagged; f0 += kReplayChunk) {
         const int64_t m2 = std::min<int64_t>(kReplayChunk, n_flagged - f0);
@@ -530,7 +572,7 @@ int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_conti
         const int64_t m = std::min(kChunkQ, nq - c0);
         cs.c0 = c0, cs.m = m;
         GORSE_TRY(chunk_prepare(h, cs));
-        int tok = h->prof.begin(GORSE_PROF_TOPK_SWEEP, h->stream);
+        int tok = h->prof.begin(h->deep ? GORSE_PROF_TOPK_DEEP : GORSE_PROF_TOPK_SWEEP, h->stream);
         if (cs.warm) {
             GORSE_TRY(h->f0.ensure((size_t)cs.mb));
             GORSE_TRY(h->f1.ensure((size_t)cs.mb));
@@ -538,6 +580,7 @@ int32_t topk_mfma_search(gorse_topk *h, const int64_t *qid_host, int64_t q_conti
         }
         GORSE_TRY(chunk_main(h, cs));
         h->last_sym = cs.sym;
+        h->last_deep = h->deep;
         // The queries whose warm start failed its verification carry flag 2: topk_rescore_kernel leaves flagged queries alone
         // and stage 2 of chunk_finish (history sweep from -inf + literal replay) answers them together with the tie queries -- a sweep
         // of their own would cost one workgroup a full pass over the rows (48 ms for 86 queries, profiles/r02_h_*).

@@ -1,6 +1,7 @@
 // topk_mfma_internal.hpp -- what the units of path B of the exact top-k share: the parameter blocks of its kernels, the state of a
 // chunk, the small device helpers more than one unit needs and the host entry points that cross units.  One unit per stage:
 //   topk_sweep.hip    the bf16 MFMA candidate sweep (main, pilot, history and symmetric forms) and its dispatch
+//   topk_deep.hip     the same sweep's main / pilot form for operands deeper than 24 k-steps (gorse_topk_set_deep_sweep)
 //   topk_rescore.hip  exact rescoring and ranking of the candidate lists, the list of the queries that leaves undecided
 //   topk_tie.hip      the tie path of one chunk of undecided queries: history sweep, sort, lane-heap replay
 //   topk_mfma.hip     operands, error bound and the chunk driver (topk_mfma_prepare / _search)
@@ -194,6 +195,8 @@ using ChunkState = TopkChunkState;
 
 // topk_sweep.hip: the sweep of h's operand depth -- hist: a history sweep (p.nslices row slices); sym: the symmetric form
 int32_t dispatch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym = false);
+// topk_deep.hip: the main / pilot sweep of a deep handle (dispatch_sweep hands it over)
+int32_t dispatch_deep_sweep(gorse_topk *h, const SweepParams &p);
 // topk_rescore.hip: exact rescoring and ranking of the chunk's lists; the queries that leaves undecided are listed on the device
 // (h->fl_pos, h->fl_self), *n_flagged of them
 int32_t rescore_chunk(gorse_topk *h, const ChunkState &cs, int64_t *n_flagged);

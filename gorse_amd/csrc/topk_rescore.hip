@@ -1,6 +1,7 @@
 // topk_rescore.hip -- the second stage of path B of the exact top-k (topk_mfma.hip): the candidate lists the sweep left are rescored
 // in the reference's own arithmetic order and ranked; the queries that cannot be decided from their lists (ties in the top k + 1,
 // NaN, an overflowed list, a warm start that cannot be verified) are flagged and listed for the tie path (topk_tie.hip).
+#include "topk_deep_plan.hpp"
 #include "topk_mfma_internal.hpp"
 
 using namespace gorse;
@@ -8,12 +9,16 @@ using namespace gorse;
 namespace {
 
 // ---- exact rescoring + ranking of one query's candidate list ------------------------------------------
+// G = the 16-lane groups that compute exact distances, each staging two rows of d floats: all kGroupsPerBlock of the workgroup, or
+// -- rows of a deep index, whose staging would not fit LDS (topk_deep_plan::rescore_groups) -- the first G of them.  The distances
+// are the same chains over the same LDS images whichever group computes them.
+template <int G = kGroupsPerBlock>
 __global__ __launch_bounds__(kBlock) void topk_rescore_kernel(RescoreParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int d = p.d;
     float *sq = smem_f;                          // d
-    float *sx = sq + d;                          // 2 * kGroupsPerBlock * d
-    float *s_e = sx + (size_t)2 * kGroupsPerBlock * d;  // kCapT
+    float *sx = sq + d;                          // 2 * G * d
+    float *s_e = sx + (size_t)2 * G * d;         // kCapT
     int *s_i = reinterpret_cast<int *>(s_e + kCapT);  // kCapT
     int *s_misc = s_i + kCapT;                   // [0] nonpositive in top-k, [1] flag, [2] SYM: candidates that clear the warm start,
                                                  // [3], [4] the histogram selection's bin and remainder, [5] survivors of the pruning
@@ -155,11 +160,11 @@ __global__ __launch_bounds__(kBlock) void topk_rescore_kernel(RescoreParams p) {
     __syncthreads();
     const int n = s_misc[5];
     // exact distances, two candidates per 16-lane group and step (their gathers in flight together: the loop is latency-bound)
-    for (int c0 = gib; c0 < n; c0 += 2 * kGroupsPerBlock) {
-        const int c1 = c0 + kGroupsPerBlock;
+    for (int c0 = gib; c0 < n && gib < G; c0 += 2 * G) {
+        const int c1 = c0 + G;
         const bool two = c1 < n;
         const int64_t i0 = s_i[c0], i1 = s_i[two ? c1 : c0];
-        float *row0 = sx + (size_t)gib * d, *row1 = sx + (size_t)(kGroupsPerBlock + gib) * d;
+        float *row0 = sx + (size_t)gib * d, *row1 = sx + (size_t)(G + gib) * d;
         gather_row(row0, p.X, p.Xb, i0, d, lane);
         gather_row(row1, p.X, p.Xb, i1, d, lane);
         __builtin_amdgcn_wave_barrier();
@@ -334,6 +339,24 @@ __global__ __launch_bounds__(1024) void flag_compact_kernel(const uint8_t *__res
     });
 }
 
+// deep rows: as many staging groups as LDS holds (more than the 64 KB a launch may ask for without the attribute)
+template <int G>
+int32_t launch_rescore_groups(gorse_topk *h, const RescoreParams &rp, int64_t m) {
+    const size_t lds = rescore_lds_bytes(h->d, G);
+    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_rescore_kernel<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    topk_rescore_kernel<G><<<dim3((unsigned)m), dim3(kBlock), lds, h->stream>>>(rp);
+    return GORSE_OK;
+}
+int32_t launch_rescore_deep(gorse_topk *h, const RescoreParams &rp, int64_t m) {
+    switch (topk_deep_plan::rescore_groups(h->d)) {
+        case 16: return launch_rescore_groups<16>(h, rp, m);
+        case 8: return launch_rescore_groups<8>(h, rp, m);
+        case 4: return launch_rescore_groups<4>(h, rp, m);
+        case 2: return launch_rescore_groups<2>(h, rp, m);
+    }
+    return launch_rescore_groups<1>(h, rp, m);
+}
+
 }  // namespace
 
 int32_t gorse::rescore_chunk(gorse_topk *h, const ChunkState &cs, int64_t *n_flagged) {
@@ -369,7 +392,11 @@ int32_t gorse::rescore_chunk(gorse_topk *h, const ChunkState &cs, int64_t *n_fla
     rp.kth = cs.kth;
     const size_t lds = rescore_lds_bytes(h->d, kGroupsPerBlock);
     const int tok = h->prof.begin(GORSE_PROF_TOPK_SELECT, h->stream);
-    topk_rescore_kernel<<<dim3((unsigned)m), dim3(kBlock), lds, h->stream>>>(rp);
+    if (h->deep) {
+        GORSE_TRY(launch_rescore_deep(h, rp, m));
+    } else {
+        topk_rescore_kernel<<<dim3((unsigned)m), dim3(kBlock), lds, h->stream>>>(rp);
+    }
     GORSE_HIP_CHECK(hipGetLastError());
     h->prof.end(tok, h->stream);
     // The queries the sweep + rescoring could not decide (ties in the top k + 1, NaN, overflow; of a triangle shard: among the queries

@@ -101,7 +101,9 @@ struct Searcher {
 // One gorse_topk handle per collection, rebuilt lazily after a change (like BruteforceHIP.sync in INTEGRATION.md).
 class HipSearcher : public Searcher {
 public:
-    explicit HipSearcher(int device = 0) : device_(device) {}
+    // deep_sweep: every index is switched to gorse_topk_set_deep_sweep(h, 1) -- the matrix-core path for rows wider than 384 (bf16)
+    // / 128 (fp32) values; an index it does not serve is searched as before
+    explicit HipSearcher(int device = 0, bool deep_sweep = false) : device_(device), deep_sweep_(deep_sweep) {}
     ~HipSearcher() override {
         for (auto &kv : handles_) gorse_topk_destroy(kv.second);
     }
@@ -118,6 +120,12 @@ public:
             if (gorse_topk_create(&h, device_, n, d, GORSE_DTYPE_F32, metric, X) != GORSE_OK) {
                 handles_.erase(collection);
                 throw std::runtime_error(std::string("gorse_topk_create: ") + gorse_hip_last_error());
+            }
+            if (deep_sweep_ && gorse_topk_set_deep_sweep(h, 1) != GORSE_OK) {
+                const std::string why = gorse_hip_last_error();
+                gorse_topk_destroy(h);
+                handles_.erase(collection);
+                throw std::runtime_error("gorse_topk_set_deep_sweep: " + why);
             }
         }
         return h;
@@ -143,6 +151,7 @@ public:
 
 private:
     int device_;
+    bool deep_sweep_;
     std::map<std::string, gorse_topk *> handles_;
 };
 
@@ -650,11 +659,20 @@ using Creator = std::function<std::shared_ptr<HipDatabase>(const std::string &pa
 inline std::map<std::string, Creator> &creators() {
     static std::map<std::string, Creator> c = {
         {"hip://", [](const std::string &path, const std::string &) {
-             // the one option: hip://?quantization=sq lets dense collections be scalar-quantised
+             // two options, alone or joined by '&': quantization=sq lets dense collections be scalar-quantised; deep_sweep=1 switches
+             // every dense collection's index to the deep sweep (gorse_topk_set_deep_sweep)
              const size_t q = path.find('?');
-             const std::string query = q == std::string::npos ? "" : path.substr(q + 1);
-             if (!query.empty() && query != "quantization=sq") throw std::runtime_error("hip://: unknown option " + query);
-             return std::make_shared<HipDatabase>(nullptr, nullptr, !query.empty());
+             std::string query = q == std::string::npos ? "" : path.substr(q + 1);
+             bool sq = false, deep = false;
+             while (!query.empty()) {
+                 const size_t amp = query.find('&');
+                 const std::string option = query.substr(0, amp);
+                 if (option == "quantization=sq") sq = true;
+                 else if (option == "deep_sweep=1") deep = true;
+                 else throw std::runtime_error("hip://: unknown option " + option);
+                 query = amp == std::string::npos ? "" : query.substr(amp + 1);
+             }
+             return std::make_shared<HipDatabase>(deep ? std::make_shared<HipSearcher>(0, true) : nullptr, nullptr, sq);
          }}};
     return c;
 }

@@ -258,7 +258,8 @@ class Database:
 
 def Open(path, tablePrefix=""):
     """vectors.Open (database.go:167-175): creators by URL prefix; 'hip://' is the one registered here.
-    'hip://?quantization=sq' lets dense collections be added with quantization="sq" (bits 0 or 8): see gorse_vectors.hpp."""
+    'hip://?quantization=sq' lets dense collections be added with quantization="sq" (bits 0 or 8); 'hip://?deep_sweep=1' switches every
+    dense collection's index to the deep matrix-core sweep (gorse_topk_set_deep_sweep); both joined by '&': see gorse_vectors.hpp."""
     return Database(url=path)
 
 

@@ -411,6 +411,7 @@ int32_t gorse_topk_synchronize(gorse_topk *h);
 #define GORSE_PROF_TOPK_SELECT 3  /* path B: topk_rescore_kernel (exact rescoring + ranking of the lists)     */
 #define GORSE_PROF_TOPK_HIST 4    /* path B: history sweep of the queries with ties in their top k+1           */
 #define GORSE_PROF_TOPK_REPLAY 5  /* path B: topk_tie_sort_kernel + topk_tie_replay_kernel (literal heap replay) */
+#define GORSE_PROF_TOPK_DEEP 6    /* path B: topk_deep_sweep_kernel, main and pilot sweeps of a deep handle (not counted under SWEEP) */
 int32_t gorse_topk_set_profiling(gorse_topk *h, int32_t on);
 int32_t gorse_topk_get_profile(gorse_topk *h, int32_t kernel_class, int64_t *launches, double *total_ms);
 /* admissible[r] == 0 removes row r from every later search -- as if ann.Bruteforce held the admissible rows only (their ids
@@ -418,6 +419,24 @@ int32_t gorse_topk_get_profile(gorse_topk *h, int32_t kernel_class, int64_t *lau
  * per filter instead of an over-fetch loop around the search.  NULL = all rows (the default).  The mask is applied inside the
  * candidate sweep (a masked row scores NaN) and in the literal scan. */
 int32_t gorse_topk_set_mask(gorse_topk *h, const uint8_t *admissible /*host, N bytes, or NULL*/);
+/* The matrix-core path for rows too wide for it today.  Path B keeps a query's operand in registers and ends at 24 k-steps: bf16
+ * rows of d <= 384, fp32 rows of d <= 128; a wider index is searched by the vector-ALU scan.  mode 1 builds operands for the DEEP
+ * sweep form (csrc/topk_deep.hip: a K-loop with both operands streamed through LDS) if the index qualifies, and lets
+ * gorse_topk_search_index, _search_vector, _all_pairs and gorse_nbr_set_table_from_topk use it.  mode 0 (the default) drops them:
+ * today's behaviour.  Any other value: GORSE_ERR_INVALID, the setting is kept.  GORSE_ERR_NOMEM when the operands cannot be
+ * allocated: the handle is left in mode 0 with nothing built.
+ * Served: the metrics path B serves (NEG_DOT, COSINE, EUCLIDEAN, EUCLIDEAN_BF16), bf16 rows of 384 < d <= 4096, fp32 rows of
+ * 128 < d <= 1536, norms finite (and non-zero under cosine).  An index path B serves already keeps its sweep and reports serves = 0;
+ * so does an index outside the ranges or with such norms, which the scan answers as before.
+ * Fallback: calls with fewer queries than the sweep takes, and k > 255, take the scan.  Queries the sweep cannot decide (equal
+ * distances among the k + 1 best, a NaN, an overflowed list, a warm start that failed its verification) are answered by the literal
+ * scan and counted in gorse_topk_last_stats' n_fallback; a deep handle has no tie replay.  The triangle-sharded calls
+ * (gorse_topk_tri_*) treat a deep handle as an index that is too deep.
+ * Results are identical in either mode, ties included: indices, distance bits, counts.
+ * get: the mode asked for, whether the index has deep operands, whether the last search's main sweep was the deep kernel; any
+ * pointer may be NULL. */
+int32_t gorse_topk_set_deep_sweep(gorse_topk *h, int32_t mode);
+int32_t gorse_topk_get_deep_sweep(gorse_topk *h, int32_t *requested, int32_t *serves, int32_t *last_used);
 /* statistics of the last all_pairs / search call: queries that took the exact fallback path */
 int32_t gorse_topk_last_stats(gorse_topk *h, int64_t *n_fallback, int64_t *n_tie_resolved);
 

@@ -31,18 +31,28 @@ import (
 // Its vectors are kept as given (GetVectors returns the floats); its queries are answered from a gorse_sq handle (int8 codes,
 // exact search over the codes, gorse_hip.h) and Score is that handle's reported score.  pq, rq, other bit counts and sparse
 // collections stay ErrNotSupported, and so does every quantization without the option.
+//
+// Another: "hip://?deep_sweep=1" switches every dense collection's index to the deep matrix-core sweep
+// (gorse_topk_set_deep_sweep): embeddings of 129 .. 1536 dimensions are then searched on the matrix cores instead of the
+// vector-ALU scan, with the same results.  The two options may be joined by '&'.
 const HipPrefix = "hip://"
 
 func init() {
 	Register([]string{HipPrefix}, func(path, tablePrefix string, _ ...storage.Option) (Database, error) {
-		option := ""
-		if at := strings.IndexByte(path, '?'); at >= 0 {
-			option = path[at+1:]
+		db := &Hip{collections: make(map[string]*hipCollection)}
+		if at := strings.IndexByte(path, '?'); at >= 0 && at+1 < len(path) {
+			for _, option := range strings.Split(path[at+1:], "&") {
+				switch option {
+				case "quantization=sq":
+					db.allowSQ = true
+				case "deep_sweep=1":
+					db.deepSweep = true
+				default:
+					return nil, errors.Errorf("hip://: unknown option %s", option)
+				}
+			}
 		}
-		if option != "" && option != "quantization=sq" {
-			return nil, errors.Errorf("hip://: unknown option %s", option)
-		}
-		return &Hip{collections: make(map[string]*hipCollection), allowSQ: option != ""}, nil
+		return db, nil
 	})
 }
 
@@ -83,6 +93,7 @@ type Hip struct {
 	collections map[string]*hipCollection
 	closed      bool
 	allowSQ     bool // opened with ?quantization=sq
+	deepSweep   bool // opened with ?deep_sweep=1
 }
 
 func (db *Hip) Init() error { return nil }
@@ -343,6 +354,14 @@ func (db *Hip) queryDense(c *hipCollection, q []float32, categories []string, to
 	if c.dense == nil {
 		if rc := C.gorse_topk_create(&c.dense, 0, C.int64_t(n), C.int32_t(d), C.GORSE_DTYPE_F32, metric, unsafe.Pointer(&c.data[0])); rc != 0 {
 			return nil, lastError("gorse_topk_create")
+		}
+		if db.deepSweep {
+			if rc := C.gorse_topk_set_deep_sweep(c.dense, 1); rc != 0 {
+				err := lastError("gorse_topk_set_deep_sweep")
+				C.gorse_topk_destroy(c.dense)
+				c.dense = nil
+				return nil, err
+			}
 		}
 	}
 	ok := make([]uint8, n)

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 from gorse_amd import capi, synth  # noqa: E402
 
 N_LIST = 100
-TOPK_CLASSES = 6  # GORSE_PROF_TOPK_NCLASSES
+TOPK_CLASSES = 7  # GORSE_PROF_TOPK_NCLASSES
 
 
 def stats(ts):
