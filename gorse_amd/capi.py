@@ -115,6 +115,8 @@ SIGNATURES = {
     "gorse_topk_last_stats": (C.c_int32, [_vp, _i64p, _i64p]),
     "gorse_topk_set_deep_sweep": (C.c_int32, [_vp, C.c_int32]),
     "gorse_topk_get_deep_sweep": (C.c_int32, [_vp, _i32p, _i32p, _i32p]),
+    "gorse_topk_set_deep_tie_replay": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_topk_get_deep_tie_replay": (C.c_int32, [_vp, _i32p, _i32p]),
     "gorse_sparse_create": (C.c_int32, [C.POINTER(_vp), C.c_int32, C.c_int64, _i64p, _vp, _f32p]),
     "gorse_sparse_destroy": (C.c_int32, [_vp]),
     "gorse_sparse_set_mask": (C.c_int32, [_vp, _vp]),
@@ -1013,6 +1015,16 @@ class TopK:
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         check(lib().gorse_topk_get_deep_sweep(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def set_deep_tie_replay(self, mode):
+        """gorse_topk_set_deep_tie_replay: 1 = a deep handle's tie queries take path B's tie path (deep history sweep + heap replay), not the scan"""
+        check(lib().gorse_topk_set_deep_tie_replay(self.h, int(mode)))
+
+    def get_deep_tie_replay(self):
+        """(mode asked for, the last search ran a deep history sweep)"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_topk_get_deep_tie_replay(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def resweeps(self):
         n = C.c_int64(0)

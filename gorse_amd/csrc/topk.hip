@@ -287,8 +287,8 @@ int32_t topk_scan_block(gorse_topk *h, int64_t nq, const int64_t *qidx_dev, cons
     // can take them (its history sweep + heap replay answer a tie query in tens of milliseconds) they go there.
     // (not with a mask: the replay counts the rows between two recorded ones, masked rows included, so the MFMA path sends a
     // masked tie query back to the literal kernel anyway -- after a full sweep)
-    // (nor to a deep handle, which has no tie path: its sweep would hand them back to this scan)
-    reroute = reroute && !g_scan_literal_only && !h->has_mask && !h->deep && topk_mfma_usable(h, kMinRerouteQueries, k);
+    // (nor to a deep handle without its tie path, gorse_topk_set_deep_tie_replay: its sweep would hand them back to this scan)
+    reroute = reroute && !g_scan_literal_only && !h->has_mask && (!h->deep || h->deep_ties) && topk_mfma_usable(h, kMinRerouteQueries, k);
     if (!g_scan_literal_only) {
         GORSE_TRY(h->scan_literal.ensure((size_t)nq));
         literal = h->scan_literal.p;
@@ -376,7 +376,7 @@ int32_t topk_search_stored(gorse_topk *h, const int64_t *src_host, int64_t nq, i
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
-    h->last_deep = false;
+    h->last_deep = h->last_deep_hist = false;
     const int d = h->d;
     const bool mfma = topk_mfma_usable(h, nq, k);
     const int64_t bq = mfma ? nq : std::min(topk_scan_block_queries(h), nq);  // path B takes its query vectors all at once
@@ -494,7 +494,7 @@ extern "C" int32_t gorse_topk_search_index(gorse_topk *h, const int64_t *q, int6
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
-    h->last_deep = false;
+    h->last_deep = h->last_deep_hist = false;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, q, -1, nullptr, nq, k, prune0, idx_out, dist_out, count_out);
     const int64_t bq = topk_scan_block_queries(h);
     GORSE_TRY(h->qidx.ensure((size_t)std::min(bq, nq)));
@@ -520,7 +520,7 @@ extern "C" int32_t gorse_topk_search_vector(gorse_topk *h, const void *qv, int64
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
-    h->last_deep = false;
+    h->last_deep = h->last_deep_hist = false;
     if (topk_mfma_usable(h, nq, k)) {  // all query vectors to the device as fp32, then path B
         GORSE_TRY(h->qf32.ensure((size_t)nq * h->d));
         if (h->dtype == GORSE_DTYPE_BF16) {
@@ -568,7 +568,7 @@ extern "C" int32_t gorse_topk_all_pairs(gorse_topk *h, int64_t q_begin, int64_t 
     GORSE_TRY(h->use());
     h->n_fallback = 0;
     h->scan_last_nq = 0;
-    h->last_deep = false;
+    h->last_deep = h->last_deep_hist = false;
     if (topk_mfma_usable(h, nq, k)) return topk_mfma_search(h, nullptr, q_begin, nullptr, nq, k, 0, idx_out, dist_out, nullptr);
     const int64_t bq = topk_scan_block_queries(h);
     const int64_t mb = std::min(bq, nq);
@@ -667,6 +667,21 @@ extern "C" int32_t gorse_topk_get_deep_sweep(gorse_topk *h, int32_t *requested, 
     if (requested) *requested = h->deep_requested;
     if (serves) *serves = h->deep ? 1 : 0;
     if (last_used) *last_used = h->last_deep ? 1 : 0;
+    return GORSE_OK;
+}
+
+// the tie path of a deep handle (topk_deep_hist.hip): a setting only -- tie_path / topk_scan_block read it while the handle is deep,
+// and the replay's buffers are allocated by the first tie chunk
+extern "C" int32_t gorse_topk_set_deep_tie_replay(gorse_topk *h, int32_t mode) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (mode != 0 && mode != 1) return fail(GORSE_ERR_INVALID, "deep tie replay mode %d: 0 or 1", mode);
+    h->deep_ties = mode;
+    return GORSE_OK;
+}
+extern "C" int32_t gorse_topk_get_deep_tie_replay(gorse_topk *h, int32_t *requested, int32_t *last_used) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (requested) *requested = h->deep_ties;
+    if (last_used) *last_used = h->last_deep_hist ? 1 : 0;
     return GORSE_OK;
 }
 

@@ -32,10 +32,13 @@ struct gorse_topk {
     gorse::DevBuf<uint16_t> opA_own, opB_own;  // bf16 operand matrices N x KPAD (candidate / query roles)
     const uint16_t *opA = nullptr, *opB = nullptr;  // may alias Xb
     // gorse_topk_set_deep_sweep (topk_deep.hip): deep = the operands above are the deep form's -- whole K-slices, kp > 24, built on request
-    // for an index too deep for the register-resident sweep; such a handle has no tie path, no symmetric and no triangle form
+    // for an index too deep for the register-resident sweep; such a handle has no symmetric and no triangle form, and a tie path only
+    // on request (gorse_topk_set_deep_tie_replay, topk_deep_hist.hip): without it its tie queries take the literal scan
     bool deep = false;
     int deep_requested = 0;        // the mode asked for (0 / 1)
     bool last_deep = false;        // the last search's main sweep was the deep kernel
+    int deep_ties = 0;             // gorse_topk_set_deep_tie_replay's mode (0 / 1); read only while deep
+    bool last_deep_hist = false;   // the last search ran a deep history sweep
     gorse::DevBuf<float> rscale;   // the sweep's per-row value: cosine 1 / sqrt(norm2[i]), Euclidean -norm2[i] / 2, -dot 1; N + kTopkRowPad
                                    // entries, the padding NaN (what the sweep's tiles read for the rows past N)
     gorse::DevBuf<uint16_t> opQ;   // query operands of the current chunk when they are not rows of opB

@@ -310,6 +310,7 @@ int32_t search_setup(gorse_topk *h, ChunkState &cs, const int64_t *qid_host, int
     h->n_fallback = 0;
     h->n_tie = 0;
     h->n_resweep = 0;
+    h->last_deep_hist = false;
     return GORSE_OK;
 }
 
@@ -489,8 +490,9 @@ static int32_t tie_path(gorse_topk *h, const ChunkState &cs, int64_t n_flagged, 
     if (n_flagged <= 0) return GORSE_OK;
     // (with a mask the replay's gap arithmetic -- which counts the rows between two recorded ones -- would count masked
     // rows too: those queries take the literal scan, which skips masked rows)
-    // (a deep handle has no history sweep: its flagged queries take the literal scan as well)
-    if (g_topk_force_path == 3 || h->has_mask || h->deep) return fetch_flagged(h, 0, n_flagged, rest);
+    // (a deep handle's history sweep, topk_deep_hist.hip, is opt-in -- gorse_topk_set_deep_tie_replay: without it its flagged queries
+    // take the literal scan as well)
+    if (g_topk_force_path == 3 || h->has_mask || (h->deep && !h->deep_ties)) return fetch_flagged(h, 0, n_flagged, rest);
     std::vector<uint8_t> f2;
     for (int64_t f0 = 0; f0 < n_flagged; f0 += kReplayChunk) {
         const int64_t m2 = std::min<int64_t>(kReplayChunk, n_flagged - f0);

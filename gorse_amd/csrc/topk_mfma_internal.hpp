@@ -3,6 +3,7 @@
 //   topk_sweep.hip    the bf16 MFMA candidate sweep (main, pilot, history and symmetric forms) and its dispatch
 //   topk_deep.hip     the same sweep's main / pilot form for operands deeper than 24 k-steps (gorse_topk_set_deep_sweep)
 //   topk_rescore.hip  exact rescoring and ranking of the candidate lists, the list of the queries that leaves undecided
+//   topk_deep_hist.hip  its history form: the first stage of a deep handle's tie path (gorse_topk_set_deep_tie_replay)
 //   topk_tie.hip      the tie path of one chunk of undecided queries: history sweep, sort, lane-heap replay
 //   topk_mfma.hip     operands, error bound and the chunk driver (topk_mfma_prepare / _search)
 //   topk_tri.hip      the triangle-sharded all-pairs search (gorse_topk_tri_*)
@@ -197,6 +198,8 @@ using ChunkState = TopkChunkState;
 int32_t dispatch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym = false);
 // topk_deep.hip: the main / pilot sweep of a deep handle (dispatch_sweep hands it over)
 int32_t dispatch_deep_sweep(gorse_topk *h, const SweepParams &p);
+// topk_deep_hist.hip: the history sweep of a deep handle (dispatch_sweep hands it over; gorse_topk_set_deep_tie_replay)
+int32_t dispatch_deep_hist_sweep(gorse_topk *h, const SweepParams &p);
 // topk_rescore.hip: exact rescoring and ranking of the chunk's lists; the queries that leaves undecided are listed on the device
 // (h->fl_pos, h->fl_self), *n_flagged of them
 int32_t rescore_chunk(gorse_topk *h, const ChunkState &cs, int64_t *n_flagged);

@@ -723,7 +723,10 @@ int32_t launch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym = 
 }  // namespace
 
 int32_t gorse::dispatch_sweep(gorse_topk *h, const SweepParams &p, bool hist, bool sym) {
-    if (h->deep) return hist || sym ? fail(GORSE_ERR_INVALID, "the deep sweep has no history or symmetric form") : dispatch_deep_sweep(h, p);
+    if (h->deep) {
+        if (sym) return fail(GORSE_ERR_INVALID, "the deep sweep has no symmetric form");
+        return hist ? dispatch_deep_hist_sweep(h, p) : dispatch_deep_sweep(h, p);
+    }
     switch (h->kp) {
         case 1: return launch_sweep<1, kNcbMain>(h, p, hist);
         case 2: return launch_sweep<2, kNcbMain>(h, p, hist, sym);

@@ -14,6 +14,7 @@
 // (ReplayParams, the kernels' parameter block: topk_mfma_internal.hpp.)
 #include <type_traits>
 
+#include "topk_deep_hist_plan.hpp"
 #include "topk_mfma_internal.hpp"
 
 using namespace gorse;
@@ -22,14 +23,18 @@ namespace {
 
 // stage 1 of the tie path: exact distances (the reference's arithmetic) of one query's recorded vectors, sorted by
 // index; one workgroup per query, everything parallel.  Output: sidx / sdst (kReplayCap slots per query), scount.
+// G = the 16-lane groups that compute exact distances, each staging one row of d floats: all kGroupsPerBlock of the workgroup, or --
+// rows of a deep index, whose staging would not fit LDS (topk_deep_hist_plan::tie_sort_groups) -- the first G of them.  The
+// distances are the same chains over the same LDS images whichever group computes them.
+template <int G = kGroupsPerBlock>
 __global__ __launch_bounds__(kBlock) void topk_tie_sort_kernel(ReplayParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int d = p.d;
     int *s_idx = reinterpret_cast<int *>(smem_f);           // kReplayCap
     float *s_dst = smem_f + kReplayCap;                      // kReplayCap
     float *sq = s_dst + kReplayCap;                          // d
-    float *sx = sq + d;                                      // kGroupsPerBlock * d
-    int *s_misc = reinterpret_cast<int *>(sx + (size_t)kGroupsPerBlock * d);  // [0] NaN seen, [1] recorded rows kept by the join
+    float *sx = sq + d;                                      // G * d
+    int *s_misc = reinterpret_cast<int *>(sx + (size_t)G * d);  // [0] NaN seen, [1] recorded rows kept by the join
     const int64_t t = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (kGroup - 1), gib = tid / kGroup;
     // Join of the row slices.  Slice s swept its rows from a cold threshold, so its list + history hold every row of the slice
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void topk_tie_sort_kernel(ReplayParams p) {
     __syncthreads();
     const VecShape vs(d);
     const float qq = p.metric == GORSE_METRIC_COSINE ? p.qn2[row] : 0.0f;
-    for (int c = gib; c < n; c += kGroupsPerBlock) {  // exact distances, as topk_rescore_kernel
+    for (int c = gib < G ? gib : n; c < n; c += G) {  // exact distances, as topk_rescore_kernel
         const int64_t i = s_idx[c];
         float *xr = sx + (size_t)gib * d;
         gather_row(xr, p.X, p.Xb, i, d, lane);
@@ -509,6 +514,16 @@ __global__ __launch_bounds__(64) void tie_warm_kernel(WarmParams p) {
     }
 }
 
+template <int G>
+int32_t launch_tie_sort(gorse_topk *h, const ReplayParams &pp, int64_t m2) {
+    const size_t lds = tie_sort_lds_bytes(h->d, G);
+    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_tie_sort_kernel<G>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    topk_tie_sort_kernel<G><<<dim3((unsigned)m2), dim3(kBlock), lds, h->stream>>>(pp);
+    GORSE_HIP_CHECK(hipGetLastError());
+    return GORSE_OK;
+}
+
 }  // namespace
 
 // One replay chunk: the flagged queries' operands and margins gathered, the slices' starting thresholds, the history sweep, the sort
@@ -542,7 +557,8 @@ int32_t gorse::tie_replay_chunk(gorse_topk *h, const ChunkState &cs, int64_t f0,
     if (nsl > 1 && !(g_topk_variant & GORSE_TEST_TOPK_COLD_SLICES)) {
         GORSE_TRY(h->rp_fwarm.ensure(sm2));
         WarmParams wp;
-        wp.pos = pos_dev, wp.m2 = m2, wp.N = h->N, wp.nsl = nsl, wp.tile_rows = kHistTileRows, wp.kth = cs.kth;
+        wp.pos = pos_dev, wp.m2 = m2, wp.N = h->N, wp.nsl = nsl, wp.kth = cs.kth;
+        wp.tile_rows = h->deep ? topk_deep_hist_plan::kDeepHistTileRows : kHistTileRows;  // the rows the sweep's slices start at
         wp.cbuf = h->cbuf.p, wp.ccnt = h->ccnt.p;
         wp.own_slices = sym ? std::max(1, cs.sym_slices) : 1, wp.own_stride = cs.mb;
         wp.fbuf = sym ? h->fbuf.p : nullptr, wp.fcnt = sym ? h->fcnt.p : nullptr;
@@ -565,6 +581,7 @@ int32_t gorse::tie_replay_chunk(gorse_topk *h, const ChunkState &cs, int64_t f0,
     int tok = h->prof.begin(GORSE_PROF_TOPK_HIST, h->stream);
     GORSE_TRY(dispatch_sweep(h, hp, true));
     h->prof.end(tok, h->stream);
+    h->last_deep_hist = h->deep;
     ReplayParams pp;
     pp.X = h->X.p;
     pp.Xb = h->dtype == GORSE_DTYPE_BF16 ? h->Xb.p : nullptr;
@@ -597,12 +614,15 @@ int32_t gorse::tie_replay_chunk(gorse_topk *h, const ChunkState &cs, int64_t f0,
     pp.sidx = h->rp_sidx.p;
     pp.sdst = h->rp_sdst.p;
     pp.scount = h->rp_scount.p;
-    const size_t rlds = tie_sort_lds_bytes(d, kGroupsPerBlock);
-    GORSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_tie_sort_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
     tok = h->prof.begin(GORSE_PROF_TOPK_REPLAY, h->stream);
-    topk_tie_sort_kernel<<<dim3((unsigned)m2), dim3(kBlock), rlds, h->stream>>>(pp);
-    GORSE_HIP_CHECK(hipGetLastError());
+    // deep rows: as many staging groups as LDS holds (topk_deep_hist_plan::tie_sort_groups); every other handle all sixteen
+    switch (h->deep ? topk_deep_hist_plan::tie_sort_groups(d) : kGroupsPerBlock) {
+        case 16: GORSE_TRY(launch_tie_sort<16>(h, pp, m2)); break;
+        case 8: GORSE_TRY(launch_tie_sort<8>(h, pp, m2)); break;
+        case 4: GORSE_TRY(launch_tie_sort<4>(h, pp, m2)); break;
+        case 2: GORSE_TRY(launch_tie_sort<2>(h, pp, m2)); break;
+        default: return fail(GORSE_ERR_INVALID, "no sort kernel form for rows of %d values", d);  // (one group: d > 4914, wider than any deep index)
+    }
     {  // one lane per query
         const int slots = k + 1;
         const int qpw = replay_queries_per_wave(g_topk_variant, slots, m2);

@@ -102,8 +102,10 @@ struct Searcher {
 class HipSearcher : public Searcher {
 public:
     // deep_sweep: every index is switched to gorse_topk_set_deep_sweep(h, 1) -- the matrix-core path for rows wider than 384 (bf16)
-    // / 128 (fp32) values; an index it does not serve is searched as before
-    explicit HipSearcher(int device = 0, bool deep_sweep = false) : device_(device), deep_sweep_(deep_sweep) {}
+    // / 128 (fp32) values; an index it does not serve is searched as before.  deep_ties: gorse_topk_set_deep_tie_replay(h, 1) as well --
+    // such an index's tie queries take path B's tie replay instead of the literal scan
+    explicit HipSearcher(int device = 0, bool deep_sweep = false, bool deep_ties = false)
+        : device_(device), deep_sweep_(deep_sweep), deep_ties_(deep_ties) {}
     ~HipSearcher() override {
         for (auto &kv : handles_) gorse_topk_destroy(kv.second);
     }
@@ -126,6 +128,12 @@ public:
                 gorse_topk_destroy(h);
                 handles_.erase(collection);
                 throw std::runtime_error("gorse_topk_set_deep_sweep: " + why);
+            }
+            if (deep_ties_ && gorse_topk_set_deep_tie_replay(h, 1) != GORSE_OK) {
+                const std::string why = gorse_hip_last_error();
+                gorse_topk_destroy(h);
+                handles_.erase(collection);
+                throw std::runtime_error("gorse_topk_set_deep_tie_replay: " + why);
             }
         }
         return h;
@@ -151,7 +159,7 @@ public:
 
 private:
     int device_;
-    bool deep_sweep_;
+    bool deep_sweep_, deep_ties_;
     std::map<std::string, gorse_topk *> handles_;
 };
 
@@ -659,20 +667,23 @@ using Creator = std::function<std::shared_ptr<HipDatabase>(const std::string &pa
 inline std::map<std::string, Creator> &creators() {
     static std::map<std::string, Creator> c = {
         {"hip://", [](const std::string &path, const std::string &) {
-             // two options, alone or joined by '&': quantization=sq lets dense collections be scalar-quantised; deep_sweep=1 switches
-             // every dense collection's index to the deep sweep (gorse_topk_set_deep_sweep)
+             // three options, alone or joined by '&': quantization=sq lets dense collections be scalar-quantised; deep_sweep=1 switches
+             // every dense collection's index to the deep sweep (gorse_topk_set_deep_sweep); deep_ties=1, with deep_sweep=1 only, switches
+             // on such an index's tie replay as well (gorse_topk_set_deep_tie_replay)
              const size_t q = path.find('?');
              std::string query = q == std::string::npos ? "" : path.substr(q + 1);
-             bool sq = false, deep = false;
+             bool sq = false, deep = false, ties = false;
              while (!query.empty()) {
                  const size_t amp = query.find('&');
                  const std::string option = query.substr(0, amp);
                  if (option == "quantization=sq") sq = true;
                  else if (option == "deep_sweep=1") deep = true;
+                 else if (option == "deep_ties=1") ties = true;
                  else throw std::runtime_error("hip://: unknown option " + option);
                  query = amp == std::string::npos ? "" : query.substr(amp + 1);
              }
-             return std::make_shared<HipDatabase>(deep ? std::make_shared<HipSearcher>(0, true) : nullptr, nullptr, sq);
+             if (ties && !deep) throw std::runtime_error("hip://: deep_ties=1 needs deep_sweep=1 (the tie replay of a deep index)");
+             return std::make_shared<HipDatabase>(deep ? std::make_shared<HipSearcher>(0, true, ties) : nullptr, nullptr, sq);
          }}};
     return c;
 }

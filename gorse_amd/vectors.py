@@ -259,7 +259,9 @@ class Database:
 def Open(path, tablePrefix=""):
     """vectors.Open (database.go:167-175): creators by URL prefix; 'hip://' is the one registered here.
     'hip://?quantization=sq' lets dense collections be added with quantization="sq" (bits 0 or 8); 'hip://?deep_sweep=1' switches every
-    dense collection's index to the deep matrix-core sweep (gorse_topk_set_deep_sweep); both joined by '&': see gorse_vectors.hpp."""
+    dense collection's index to the deep matrix-core sweep (gorse_topk_set_deep_sweep); 'hip://?deep_sweep=1&deep_ties=1' also sends
+    such an index's tie queries to path B's tie replay instead of the literal scan (gorse_topk_set_deep_tie_replay; deep_ties=1
+    without deep_sweep=1 is an error); the options are joined by '&': see gorse_vectors.hpp."""
     return Database(url=path)
 
 

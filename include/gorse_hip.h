@@ -430,13 +430,27 @@ int32_t gorse_topk_set_mask(gorse_topk *h, const uint8_t *admissible /*host, N b
  * so does an index outside the ranges or with such norms, which the scan answers as before.
  * Fallback: calls with fewer queries than the sweep takes, and k > 255, take the scan.  Queries the sweep cannot decide (equal
  * distances among the k + 1 best, a NaN, an overflowed list, a warm start that failed its verification) are answered by the literal
- * scan and counted in gorse_topk_last_stats' n_fallback; a deep handle has no tie replay.  The triangle-sharded calls
- * (gorse_topk_tri_*) treat a deep handle as an index that is too deep.
+ * scan and counted in gorse_topk_last_stats' n_fallback, unless the handle's tie replay is switched on
+ * (gorse_topk_set_deep_tie_replay below; off by default).  The triangle-sharded calls (gorse_topk_tri_*) treat a deep handle as an
+ * index that is too deep.
  * Results are identical in either mode, ties included: indices, distance bits, counts.
  * get: the mode asked for, whether the index has deep operands, whether the last search's main sweep was the deep kernel; any
  * pointer may be NULL. */
 int32_t gorse_topk_set_deep_sweep(gorse_topk *h, int32_t mode);
 int32_t gorse_topk_get_deep_sweep(gorse_topk *h, int32_t *requested, int32_t *serves, int32_t *last_used);
+/* The tie replay of a deep handle.  mode 1: the queries a deep handle's sweep cannot decide take path B's tie path -- a history
+ * sweep in the deep form (csrc/topk_deep_hist.hip), the join of its row slices, the literal heap replay -- as on an index the
+ * register-resident sweep serves, instead of the literal scan (one thread per query over all N rows).  They are then counted in
+ * gorse_topk_last_stats' n_tie_resolved; what the replay leaves undecided (an overflowed list or history, a NaN) still takes the
+ * scan and is counted in n_fallback, and so does every such query of a masked handle.  Small calls that take the scan send their
+ * tie queries to this tie path as well, as on a shallow index.  mode 0 (the default): today's behaviour.  Any other value:
+ * GORSE_ERR_INVALID, the setting is kept.  May be set on any handle at any time: it takes effect only while the handle has deep
+ * operands (gorse_topk_set_deep_sweep(h, 1) on an index that qualifies) and allocates nothing before the first chunk of tie
+ * queries.  Results are identical in either mode: indices, distance bits, counts.  History-sweep time is reported under
+ * GORSE_PROF_TOPK_HIST, sort and replay time under GORSE_PROF_TOPK_REPLAY.
+ * get: the mode asked for, whether the last search ran a deep history sweep; either pointer may be NULL. */
+int32_t gorse_topk_set_deep_tie_replay(gorse_topk *h, int32_t mode);
+int32_t gorse_topk_get_deep_tie_replay(gorse_topk *h, int32_t *requested, int32_t *last_used);
 /* statistics of the last all_pairs / search call: queries that took the exact fallback path */
 int32_t gorse_topk_last_stats(gorse_topk *h, int64_t *n_fallback, int64_t *n_tie_resolved);
 

@@ -34,7 +34,9 @@ import (
 //
 // Another: "hip://?deep_sweep=1" switches every dense collection's index to the deep matrix-core sweep
 // (gorse_topk_set_deep_sweep): embeddings of 129 .. 1536 dimensions are then searched on the matrix cores instead of the
-// vector-ALU scan, with the same results.  The two options may be joined by '&'.
+// vector-ALU scan, with the same results.  With it, "deep_ties=1" also sends such an index's tie queries (equal distances among
+// the k + 1 best) to the matrix-core tie replay instead of the literal scan (gorse_topk_set_deep_tie_replay); without
+// "deep_sweep=1" it is an error.  The options may be joined by '&'.
 const HipPrefix = "hip://"
 
 func init() {
@@ -47,10 +49,15 @@ func init() {
 					db.allowSQ = true
 				case "deep_sweep=1":
 					db.deepSweep = true
+				case "deep_ties=1":
+					db.deepTies = true
 				default:
 					return nil, errors.Errorf("hip://: unknown option %s", option)
 				}
 			}
+		}
+		if db.deepTies && !db.deepSweep {
+			return nil, errors.New("hip://: deep_ties=1 needs deep_sweep=1 (the tie replay of a deep index)")
 		}
 		return db, nil
 	})
@@ -94,6 +101,7 @@ type Hip struct {
 	closed      bool
 	allowSQ     bool // opened with ?quantization=sq
 	deepSweep   bool // opened with ?deep_sweep=1
+	deepTies    bool // opened with ?deep_sweep=1&deep_ties=1
 }
 
 func (db *Hip) Init() error { return nil }
@@ -361,6 +369,14 @@ func (db *Hip) queryDense(c *hipCollection, q []float32, categories []string, to
 				C.gorse_topk_destroy(c.dense)
 				c.dense = nil
 				return nil, err
+			}
+			if db.deepTies {
+				if rc := C.gorse_topk_set_deep_tie_replay(c.dense, 1); rc != 0 {
+					err := lastError("gorse_topk_set_deep_tie_replay")
+					C.gorse_topk_destroy(c.dense)
+					c.dense = nil
+					return nil, err
+				}
 			}
 		}
 	}
