@@ -14,6 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GORSE_HIP_LIB") or os.path.join(HERE, "lib", "libgorse_hip.so")  # the override serves probe builds
 
 OK, ERR_INVALID, ERR_HIP, ERR_CANCELLED, ERR_NO_DEVICE, ERR_RANGE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
+# gorse_mf_get_als_form's last_used (GORSE_ALS_FAMILY_*)
+ALS_FAMILY_NONE, ALS_FAMILY_RESIDUAL, ALS_FAMILY_TILES, ALS_FAMILY_WIDE, ALS_FAMILY_DEEP = -1, 0, 1, 2, 3
 BPR_HOGWILD_ATOMIC, BPR_SEQUENTIAL, BPR_HOGWILD_RACY, BPR_HOGWILD_STORES = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_NEG_DOT, METRIC_EUCLIDEAN, METRIC_COSINE, METRIC_EUCLIDEAN_BF16 = 0, 1, 2, 3
@@ -56,6 +58,8 @@ SIGNATURES = {
     "gorse_mf_recommend_stats": (C.c_int32, [_vp, _i64p, _i64p, _f64p]),
     "gorse_mf_set_recommend_route": (C.c_int32, [_vp, C.c_int32]),
     "gorse_mf_get_recommend_route": (C.c_int32, [_vp, _i32p, _i32p]),
+    "gorse_mf_set_als_form": (C.c_int32, [_vp, C.c_int32]),
+    "gorse_mf_get_als_form": (C.c_int32, [_vp, _i32p, _i32p]),
     "gorse_mf_set_recommend_schedule": (C.c_int32, [_vp, C.c_int32]),
     "gorse_mf_get_recommend_schedule": (C.c_int32, [_vp, _i32p, _i32p]),
     "gorse_mf_recommend_sweep_stats": (C.c_int32, [_vp, _i64p, _i64p, _i64p]),
@@ -559,6 +563,16 @@ class MF:
 
     def als_set_ranges(self, u_begin, u_end, i_begin, i_end):
         check(lib().gorse_als_set_ranges(self.h, u_begin, u_end, i_begin, i_end))
+
+    def set_als_form(self, form):
+        """which family ALS half-sweeps run: 0 = by nFactors (default), 1 = Deep for nFactors 129..256 (form 0 everywhere else)"""
+        check(lib().gorse_mf_set_als_form(self.h, int(form)))
+
+    def als_form(self):
+        """(the form asked for, the family the last half-sweep ran: ALS_FAMILY_*)"""
+        req, used = C.c_int32(0), C.c_int32(0)
+        check(lib().gorse_mf_get_als_form(self.h, C.byref(req), C.byref(used)))
+        return req.value, used.value
 
     def als_half_epoch(self, side, weight, reg):
         check(lib().gorse_als_half_epoch(self.h, side, weight, reg))

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "als_deep_plan.hpp"
 #include "als_plan.hpp"
 #include "mf_internal.hpp"
 #include <type_traits>
@@ -1870,10 +1871,18 @@ int32_t run_side_wide(gorse_mf *h, int side, float *A, const float *B, const int
 //   Residual  run_gram + run_sweep: the reference's own recurrence, any nFactors
 //   Tiles     run_gram_mfma + run_side_gram: the Gram form on MFMA tiles held by one wave, nFactors <= 64
 //   Wide      run_gram_mfma_wide + run_side_wide: the Gram form of als_wide_kernel, 64 < nFactors <= 128
-enum class AlsForm { Residual, Tiles, Wide };
+//   Deep      als_deep_half_epoch (als_deep.hip): the Gram form over M's packed block triangle, 128 < nFactors <= 256 -- only on a
+//             handle that asked for it (gorse_mf_set_als_form(h, 1)); every other handle and width keeps the three lines above
+// (the values are the header's GORSE_ALS_FAMILY_*)
+enum class AlsForm { Residual = GORSE_ALS_FAMILY_RESIDUAL, Tiles = GORSE_ALS_FAMILY_TILES, Wide = GORSE_ALS_FAMILY_WIDE,
+                     Deep = GORSE_ALS_FAMILY_DEEP };
 int32_t als_form(const gorse_mf *h, AlsForm &form) {
     const int d = h->d;
     form = AlsForm::Residual;  // path 1, and nFactors > 128
+    if (g_als_path == 0 && h->als_form_req == 1 && deep_serves(d)) {
+        form = AlsForm::Deep;
+        return GORSE_OK;
+    }
     if (g_als_path == 2) {
         if (d > 64) return fail(GORSE_ERR_INVALID, "the Gram-form ALS kernels cover nFactors <= 64 (got %d)", d);
         form = AlsForm::Tiles;
@@ -1892,7 +1901,10 @@ int32_t half_epoch(gorse_mf *h, int side, float weight, float reg) {
     const int32_t *idx = side == 0 ? h->uidx.p : h->iidx.p;
     AlsForm form;
     GORSE_TRY(als_form(h, form));
+    h->als_form_used = (int32_t)form;
     switch (form) {
+    case AlsForm::Deep:
+        return als_deep_half_epoch(h, side, A, B, ptr, idx, weight, reg);
     case AlsForm::Tiles:
         GORSE_TRY(run_gram_mfma(h, B, 1 - side));
         return run_side_gram(h, side, A, B, ptr, idx, weight, reg);
@@ -1964,6 +1976,20 @@ extern "C" int32_t gorse_als_set_ranges(gorse_mf *h, int64_t u_begin, int64_t u_
     h->als_hi[1] = i_end;
     GORSE_TRY(als_build_plan(h, 0, h->h_uptr.data(), h->U, u_begin, u_end));
     GORSE_TRY(als_build_plan(h, 1, h->h_iptr.data(), h->I, i_begin, i_end));
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_mf_set_als_form(gorse_mf *h, int32_t form) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (form != 0 && form != 1) return fail(GORSE_ERR_INVALID, "ALS form %d is neither 0 (by nFactors) nor 1 (Deep where it serves)", form);
+    h->als_form_req = form;
+    return GORSE_OK;
+}
+
+extern "C" int32_t gorse_mf_get_als_form(gorse_mf *h, int32_t *requested, int32_t *last_used) {
+    if (!h) return fail(GORSE_ERR_INVALID, "handle is NULL");
+    if (requested) *requested = h->als_form_req;
+    if (last_used) *last_used = h->als_form_used;
     return GORSE_OK;
 }
 

@@ -111,6 +111,7 @@ struct gorse_mf {
     int64_t als_lo[2] = {0, 0}, als_hi[2] = {0, 0};  // row range of each side this handle solves (gorse_als_set_ranges)
     gorse::DevBuf<float> als_partial;  // n_chunks x (d*d + d) partial Gram matrices + column sums
     gorse::DevBuf<float> als_reduced;  // n_long x (d*d + d): a long row's partials added up (als_partial_reduce_kernel)
+    int32_t als_form_req = 0, als_form_used = -1;  // gorse_mf_set_als_form: 0 = by nFactors, 1 = Deep where it serves; the last half-sweep's family
     // Evaluate's resident split (eval.hip): the test rows, every user's sampled negatives, and the candidate CSR of the users
     // with test feedback (user ids ascending, "test items then negatives" per user)
     gorse::DevBuf<int64_t> ev_tptr, ev_upos, ev_cpos, ev_cptr;
@@ -161,6 +162,8 @@ int32_t mf_epoch_harvest(gorse_mf *h, bool wait);
 int32_t mf_delta_export_async(gorse_mf *h, float *dst);        // mf.hip: dst <- Q - Q_sync, enqueued on h->stream
 int32_t mf_delta_import_async(gorse_mf *h, const float *src);  // mf.hip: Q <- Q_sync + src; Q_sync <- Q
 int32_t als_build_plan(gorse_mf *h, int side, const int64_t *ptr, int64_t rows, int64_t lo, int64_t hi);
+// als_deep.hip: one half-sweep of `side` in the Deep form (128 < nFactors <= 256), enqueued on h->stream
+int32_t als_deep_half_epoch(gorse_mf *h, int side, float *A, const float *B, const int64_t *ptr, const int32_t *idx, float w, float reg);
 int32_t mf_score_device(gorse_mf *h, const int32_t *us, const int32_t *is, int64_t n, float *out);  // mf_rank.hip: internalPredict, device pointers
 
 // Users' lists ON THE DEVICE, as Rank and Evaluate take them: n_users user ids, their candidate CSR (n_cand entries in all) and, for

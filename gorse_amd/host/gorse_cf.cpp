@@ -459,6 +459,7 @@ Score ALS::Fit(dataset::Dataset &trainSet, dataset::Dataset &valSet, const FitCo
     Init(trainSet);
     const auto t2 = clk::now();
     create_handle(trainSet, true, config.Device, config.Resident);
+    check(gorse_mf_set_als_form(h_, deepForm_ ? 1 : 0));  // (a lent handle may carry another model's setting)
     if (config.Log) config.Log(fmt("fit als setup draws=%.3fms init=%.3fms handle=%.3fms", ms(t0, t1), ms(t1, t2), ms(t2, clk::now())));
     return fit_loop("als", nEpochs, trainSet, valSet, config,
                     [&](int) { return gorse_als_epoch(h_, weight, reg, config.Cancel); });

@@ -816,6 +816,9 @@ class ALS : public MatrixFactorization {
         weight = Params.GetFloat32(model::Alpha, 0.001f);
     }
     Score Fit(dataset::Dataset &trainSet, dataset::Dataset &valSet, const FitConfig &config) override;
+    // gorse_mf_set_als_form for the handle Fit trains on: true = the Deep kernel family for nFactors 129..256 (every other width is
+    // unchanged); off by default
+    void SetDeepForm(bool on) { deepForm_ = on; }
     model::Params SuggestParams(Trial &trial) override {  // model.go:588-596
         model::Params p;
         p[model::NFactors] = 16;
@@ -827,6 +830,9 @@ class ALS : public MatrixFactorization {
     }
     int nEpochs = 50;
     float reg = 0.06f, initMean = 0, initStdDev = 0.1f, weight = 0.001f;
+
+   private:
+    bool deepForm_ = false;
 };
 
 // ---- hyper-parameter search: ModelSearch (optimize.go:28-85) + the study that drives it (master/tasks.go:1268-1316) ----

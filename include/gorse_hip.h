@@ -271,6 +271,21 @@ int32_t gorse_als_half_epoch(gorse_mf *h, int32_t side, float weight, float reg)
  * gorse_mf_synchronize ends the epoch): what a caller driving several handles from one thread uses, so that the devices
  * solve their row ranges at the same time. */
 int32_t gorse_als_half_epoch_enqueue(gorse_mf *h, int32_t side, float weight, float reg);
+/* Which kernel family the half-sweeps of this handle run.  form 0 (the default): by nFactors -- TILES up to 64, WIDE for 65..128,
+ * RESIDUAL (the reference's own recurrence on the vector ALU) beyond.  form 1: DEEP for nFactors 129..256 -- the Gram form of TILES /
+ * WIDE over the packed upper block triangle of the row's d x d system, every product on the fp32 matrix unit (GORSE_ALS_GRAM changes
+ * nothing there), 64-bit gather addresses (factor matrices of any size), no atomics: two runs give the same bits; at every other
+ * nFactors form 1 is form 0.  Both forms meet the same parity bar; their bits differ.  Any other value: GORSE_ERR_INVALID, the
+ * setting is kept.  gorse_als_epoch, gorse_als_half_epoch(_enqueue) and gorse_als_set_ranges follow the setting.
+ * get: the form asked for and the family the handle's last half-sweep ran (GORSE_ALS_FAMILY_NONE before the first); either pointer
+ * may be NULL. */
+#define GORSE_ALS_FAMILY_NONE (-1)
+#define GORSE_ALS_FAMILY_RESIDUAL 0
+#define GORSE_ALS_FAMILY_TILES 1
+#define GORSE_ALS_FAMILY_WIDE 2
+#define GORSE_ALS_FAMILY_DEEP 3
+int32_t gorse_mf_set_als_form(gorse_mf *h, int32_t form);
+int32_t gorse_mf_get_als_form(gorse_mf *h, int32_t *requested, int32_t *last_used);
 /* factor rows [begin,end) of side 0 (P) / 1 (Q) -> / <- a device buffer owned by the caller */
 int32_t gorse_mf_rows_export(gorse_mf *h, int32_t side, int64_t begin, int64_t end, float *dst /*device*/);
 int32_t gorse_mf_rows_import(gorse_mf *h, int32_t side, int64_t begin, int64_t end, const float *src /*device*/);

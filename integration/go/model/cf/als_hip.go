@@ -17,6 +17,10 @@ import (
 	"go.uber.org/zap"
 )
 
+// ALSDeepForm is gorse_mf_set_als_form's value for the handle Fit trains on: true = the Deep kernel family for nFactors 129..256
+// (every other width is unchanged).  Off by default, as cf::ALS::SetDeepForm of the host mirror.
+var ALSDeepForm = false
+
 // Fit the ALS (eALS) model on one MI355X: model.go:609-775 with the epoch body (S = sum q q^T, user sweep, S = sum p p^T,
 // item sweep; model.go:641-738) as one gorse_als_epoch call.
 func (als *ALS) Fit(ctx context.Context, trainSet, valSet dataset.CFSplit, config *FitConfig) Score {
@@ -32,6 +36,10 @@ func (als *ALS) Fit(ctx context.Context, trainSet, valSet dataset.CFSplit, confi
 		return Score{}
 	}
 	defer hm.close()
+	if rc := C.gorse_mf_set_als_form(hm.h, C.int32_t(lo.Ternary(ALSDeepForm, 1, 0))); rc != C.GORSE_OK {
+		log.Logger().Error("fit als", zap.Error(hipError("gorse_mf_set_als_form", rc)))
+		return Score{}
+	}
 	const evalSeed = 0 // util.NewRandomGenerator(0) of dataset.go:244: the negatives' own stream
 	score := hm.evaluateResident(valSet, trainSet, config.TopK, config.Candidates, evalSeed, NDCG, Precision, Recall)
 	scores := []lo.Tuple2[int, float32]{{A: 0, B: score[0]}}
