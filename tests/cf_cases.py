@@ -71,6 +71,10 @@ GRID_DELTA_FLOATS = 2_097_152  # mf_delta_export_async / _import_async: 2048 wor
 GRID_SORT_SAMPLES = 524_288   # launch_user_sort (bpr_rank_kernel, bpr_scatter_by_kernel): 256 * 8 workgroups x 256 threads
 GRID_FOLD_ELEMENTS = 131_072  # bpr_fold_kernel behind a per-sample launch: 512 workgroups x 256 threads, one row element each
 SCAN_ONE_WORKGROUP = 32_768   # exclusive_scan_i32: up to 16 tiles of 2048 counters by scan_small_kernel, three kernels beyond
+# The Deep ALS form (csrc/als_deep.hip): tests/test_gpu_als_deep_past_one_grid.py sizes itself from these two, and
+# tests/test_als_deep_grid_caps_cpu.py holds them against the source.
+GRID_ALS_DEEP_ITEMS = 2048    # deep_launch (als_deep_kernel, rows or chunks) and the als_deep_long_kernel launch: a workgroup per row or chunk
+ALS_GRAM_CHUNK_ROWS = 1024    # als_build_plan's kGramChunk: rows with feedback per chunk of the S Gram
 
 
 def rel_err(a, b):

@@ -4,7 +4,10 @@ Every value is held to a float64 restatement of that solve, written here in nump
 sweep over it -- with the project's ALS bar (cf_cases.assert_als_close; DESIGN.md section 4 "ALS").  Form 0 at these widths (the
 residual recurrence) is a second witness against the same reference.  The dataset has, on both sides, an empty row, a one-entry
 row, rows of 31 / 32 / 33 entries (one short of, equal to and one past the kernel's gather batch) and a row of 150; with the row plan
-(64, 64) that row is a long one of three chunks, so the chunk kernel, the partials' reduce and the long solve all run."""
+(64, 64) that row is a long one of three chunks, so the chunk kernel, the partials' reduce and the long solve all run.  The widths are
+both edges of every block count ceil(nFactors / 32) = 5 .. 8, each a kernel instance of its own.  What 200 rows cannot reach -- a
+second trip of a grid-stride loop, a Gram of several chunks, a row of eight partials or more -- is
+tests/test_gpu_als_deep_past_one_grid.py's."""
 import numpy as np
 import pytest
 
@@ -41,44 +44,73 @@ def long_rows():
     capi.lib().gorse_hip_test_set_als_plan(0, 0)
 
 
-def gram_half_fp64(A, B, ptr, idx, bptr):
+def gram_half_fp64(A, B, ptr, idx, bptr, w=W):
     A, B = np.asarray(A, np.float64).copy(), np.asarray(B, np.float64)
     has = np.diff(bptr) > 0
     S = B[has].T @ B[has]
     for u in range(A.shape[0]):
         Bu = B[idx[ptr[u]:ptr[u + 1]]]
-        M, s, p = (1 - W) * (Bu.T @ Bu) + W * S, Bu.sum(axis=0), A[u]
+        M, s, p = (1 - w) * (Bu.T @ Bu) + w * S, Bu.sum(axis=0), A[u]
         for f in range(p.size):
             p[f] = (s[f] - (M[f] @ p - M[f, f] * p[f])) / (M[f, f] + REG)
     return A
 
 
-def half(data, d, side, form, ranges=None):
+def half(data, d, side, form, ranges=None, w=W):
     """factors of `side` after one half-sweep from the seeded start, on a fresh handle (form None: the setter is never called)"""
     mf, P, Q = make_mf(data, d, std=0.1)
     if form is not None:
         mf.set_als_form(form)
     if ranges:
         mf.als_set_ranges(*ranges)
-    mf.als_half_epoch(side, W, REG)
+    mf.als_half_epoch(side, w, REG)
     got, used = mf.get_factors()[side], mf.als_form()[1]
     mf.close()
     return (P, Q), got, used
 
 
-@pytest.mark.parametrize("d", [129, 160, 255, 256])
-def test_half_sweeps_meet_the_float64_gram_solve(data, long_rows, d):
+def both_forms_meet_the_float64_gram_solve(data, d, w):
     for side in (0, 1):
         ptr, idx, bptr = (data.uptr, data.uidx, data.iptr) if side == 0 else (data.iptr, data.iidx, data.uptr)
-        start, deep, used = half(data, d, side, 1)
+        start, deep, used = half(data, d, side, 1, w=w)
         assert used == capi.ALS_FAMILY_DEEP
-        _, plain, used0 = half(data, d, side, 0)
+        _, plain, used0 = half(data, d, side, 0, w=w)
         assert used0 == capi.ALS_FAMILY_RESIDUAL
-        ref = gram_half_fp64(start[side], start[1 - side], ptr, idx, bptr)
-        label = "nFactors %d side %d" % (d, side)
+        ref = gram_half_fp64(start[side], start[1 - side], ptr, idx, bptr, w)
+        label = "nFactors %d w %g side %d" % (d, w, side)
         print(label, "worst / bar: deep %.3f residual %.3f deep against residual %.3f" % (
             assert_als_close(deep, ref, label + " deep"), assert_als_close(plain, ref, label + " residual"),
             assert_als_close(deep, plain, label + " deep against residual")))
+
+
+# both edges of every block count NB = ceil(d / 32): 5 for 129..160, 6 to 192, 7 to 224, 8 to 256 (a kernel instance each)
+@pytest.mark.parametrize("d", [129, 160, 161, 192, 193, 224, 225, 255, 256])
+def test_half_sweeps_meet_the_float64_gram_solve(data, long_rows, d):
+    both_forms_meet_the_float64_gram_solve(data, d, W)
+
+
+@pytest.mark.parametrize("d", [192, 224])
+@pytest.mark.parametrize("w", [0.0, 1.0])
+def test_half_sweeps_meet_the_float64_gram_solve_where_one_term_vanishes(data, long_rows, d, w):
+    """M = (1 - w) G + w S at w = 0 and w = 1: swapped or misapplied factors show plainly.  At w = 0 the empty row's M is all zeros
+    and its reference row exactly zero, so the bar there is zero and both forms must write exact zeros.  A float32 restatement of the
+    Gram form on this data reaches 0.04 of the bar at w = 0 and 0.02 at w = 1 with the module's reg: the input stays well-conditioned."""
+    both_forms_meet_the_float64_gram_solve(data, d, w)
+
+
+@pytest.mark.parametrize("d", [160, 192, 224, 256])
+def test_epoch_meets_the_float64_epoch(data, long_rows, d):
+    """users first, then the items from the user factors just written"""
+    mf, P, Q = make_mf(data, d, std=0.1)
+    mf.set_als_form(1)
+    mf.als_epoch(W, REG)
+    assert mf.als_form() == (1, capi.ALS_FAMILY_DEEP)
+    gotP, gotQ = mf.get_factors()
+    mf.close()
+    refP = gram_half_fp64(P, Q, data.uptr, data.uidx, data.iptr)
+    refQ = gram_half_fp64(Q, refP, data.iptr, data.iidx, data.uptr)
+    print("nFactors %d epoch worst / bar: users %.3f items %.3f" % (
+        d, assert_als_close(gotP, refP, "nFactors %d epoch users" % d), assert_als_close(gotQ, refQ, "nFactors %d epoch items" % d)))
 
 
 def test_two_handles_three_epochs_same_bits(data, long_rows):
